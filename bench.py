@@ -81,7 +81,13 @@ def parse(argv=None):
     ap.add_argument("--verify", action="store_true",
                     help="after the timed run: the pipelined loop's outputs (merged rows, crop boxes, enhanced crops; JPEG files with jpeg_io) over 25 steps against "
                          "synchronous calls on fresh buffers, byte for byte, with 1 lane, 2 lanes and once with JPEG decode/encode in the span -> \"verify\" in the JSON line")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed loop returned for its last step (rank 0's frames: merged detections, crop boxes, "
+                         "enhanced crops) as DIR/<name>.npy in float32 / float64, at most 64 MB in all; the inputs are seeded, so two builds compare output for output")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def _cpu_budget():
@@ -236,6 +242,7 @@ class Runner:
         self.host_supers, self.slots = {}, {}
         self.state, self.pending, self.queue, self.group = {}, {}, [], {}
         self.sr_px = 0
+        self.keep_step, self.kept, self.last_batch = None, {}, None      # --dump-outputs: what step keep_step returned (set for the timed loop only)
         self.tm = {}                                   # host-side wall time per stage over the timed loop (seconds)
         self.lat_t0, self.lat = {}, []                 # per-frame latency: handed to the pipeline -> enhanced crops on the host
         if _n_lanes is None and self.n_lanes > 1:
@@ -388,6 +395,7 @@ class Runner:
         keys = {x[0] for x in self.queue if len(x[2])}
         ids = [x[3] for x in self.queue]
         vmeta = [(x[3], x[2]) for x in self.queue if len(x[2])] if self.verify else None
+        kmeta = [(x[3], len(x[2])) for x in self.queue if len(x[2])] if self.keep_step is not None else None
         self.queue.clear()
         if not q:
             t1 = time.perf_counter()
@@ -403,6 +411,8 @@ class Runner:
         self.pending["frame_ids"] = ids
         if vmeta is not None:
             self.pending["v"], self.pending["offs"] = vmeta, np.array(offs, copy=True)
+        if kmeta is not None:
+            self.last_batch = (kmeta, offs)            # offsets of this batch's crops in host_sr once drain_sr has copied it
         if self.jpeg_io:
             bx = np.concatenate([x[1] for x in q], 0).astype(np.int64)
             bx = np.stack([np.clip(bx[:, 0], 0, self.W), np.clip(bx[:, 1], 0, self.H), np.clip(bx[:, 2], 0, self.W), np.clip(bx[:, 3], 0, self.H)], 1)   # as the library clamps
@@ -472,9 +482,13 @@ class Runner:
                     self.queue.append((slot_key, sf[f * H:(f + 1) * H], boxes, (i, fb)))
                     if self.verify:
                         self.rec[(i, fb)] = {"rows": rows.copy(), "boxes": np.array(boxes, copy=True)}
+                    if i == self.keep_step:
+                        self.kept[(i, fb)] = {"rows": rows, "boxes": boxes}
                 else:
                     if self.verify:
                         self.rec[(i, fb)] = {"rows": rows.copy(), "boxes": None}
+                    if i == self.keep_step:
+                        self.kept[(i, fb)] = {"rows": rows, "boxes": None}
                     self.lat.append(time.perf_counter() - self.lat_t0.pop((i, fb)))
             if a.sr_crops > 0 and (len(self.queue) >= self.SB or last):
                 prof = self.prof_flush is not None and self.flush_no == self.prof_flush     # the kernel times of ONE whole SR batch
@@ -640,21 +654,26 @@ class Runner:
 
     def setup(self, warmup, steps):
         """Untimed, like loading weights: lay out, tune and graph-capture the detector plan of every group size, and the enhancer plan of
-        every capacity bucket the loops will meet (a plan is keyed by capacity, not by crop sizes: a stream builds each bucket once)."""
-        for r in [self] + self.sub:
+        every capacity bucket the loops will meet (a plan is keyed by capacity, not by crop sizes: a stream builds each bucket once).
+        The rehearsals run lane after lane, the warm-up's and the timed loop's own sequences twice each: a plan is built on its first run and
+        graph-captured on its second, and a capture is invalidated when another lane's thread allocates or synchronises meanwhile (the first use
+        of a frame slot or of the second SR output buffer, e.g. with --steps 23). The threaded loops that follow meet captured plans only."""
+        lanes = [self] + self.sub
+        for r in lanes:
             for gsz in sorted({g[2] for n in (warmup, steps) for g in r.my_groups(n)}):
                 sf, ev = r.upload(0, r.Bl * gsz)
                 if ev is not None:
                     ev.synchronize()
                 for _ in range(3):
                     r.pipe.detect(sf, r.H, r.W, r.Bl * gsz, exchange=r.exchange, mode=r.mode)
-        self.loop(max(warmup, 2 * self.DB * self.n_lanes))
-        if self.args.sr_crops > 0:
-            self.loop(steps)                           # rehearsal with the timed loop's own crop sizes: every bucket it meets exists afterwards
-        for r in [self] + self.sub:
+        for n in (max(warmup, 2 * self.DB * self.n_lanes),) + ((warmup, steps) * 2 if self.args.sr_crops > 0 else ()):
+            for r in lanes:
+                r.loop_own(n)
+        for r in lanes:
             r.sr_px = 0
 
-    def timed(self, warmup, steps, profile_last=True):
+    def timed(self, warmup, steps, profile_last=True, keep_last=False):
+        """keep_last: what the last timed step returned ends up in self.last_outputs (kept_outputs)."""
         import torch.distributed as dist
         self.setup(warmup, steps)
         self.loop(warmup)
@@ -663,6 +682,7 @@ class Runner:
         for r in lanes:
             r.sr_px = 0
             r.tm, r.lat, r.lat_t0 = {}, [], {}
+            r.keep_step, r.kept, r.last_batch = (steps - 1 if keep_last else None), {}, None
             if r.jpeg_io:
                 r.jpeg_bytes_in = r.jpeg_bytes_out = 0
                 r.frames_in = 0
@@ -675,6 +695,10 @@ class Runner:
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
         self.dt_own = time.perf_counter() - t0
+        if keep_last:
+            self.last_outputs = self.kept_outputs()    # before profile_pass refills lane 0's host buffers
+            for r in lanes:
+                r.keep_step = None
         for r in self.sub:                             # one view of the run: stage times summed over the lanes' host threads, every frame's latency
             for k, v in r.tm.items():
                 self.tm[k] = self.tm.get(k, 0.0) + v
@@ -690,6 +714,37 @@ class Runner:
         if profile_last:
             self.profile_pass()
         return dt
+
+    def kept_outputs(self):
+        """What the timed loop returned for the frames of step keep_step on this rank: per frame the merged detection rows, the crop boxes and
+        the enhanced crops (BGR, height x width x 3). The frame's crops are in the final SR batch of the lane that ran the step, and that
+        lane's pinned host buffer still holds the batch after the loop."""
+        rows, boxes, crops = [], [], []
+        for r in [self] + self.sub:
+            for fid in sorted(r.kept):
+                k = r.kept[fid]
+                rows.append(k["rows"])
+                if k["boxes"] is None or not len(k["boxes"]):
+                    continue
+                if r.jpeg_io:
+                    raise RuntimeError("enhanced crops leave as JPEG files with jpeg_io: there are no host pixels to keep")
+                meta, offs = r.last_batch
+                first = 0
+                for mfid, n in meta:
+                    if mfid == fid:
+                        break
+                    first += n
+                else:
+                    raise RuntimeError(f"the crops of frame {fid} are not in the lane's last SR batch")
+                host, sc = r.host_sr.numpy(), r.pipe.sr.scale
+                for j, b in enumerate(k["boxes"]):
+                    h = max(0, min(r.H, int(b[3])) - max(0, int(b[1]))) * sc      # the box clamped to the frame, as the library crops it
+                    w = max(0, min(r.W, int(b[2])) - max(0, int(b[0]))) * sc
+                    o, nb = int(offs[first + j]), h * w * 3
+                    assert int(offs[first + j + 1]) - o == (nb + 15) // 16 * 16, "crop offsets do not match the boxes"
+                    crops.append(host[o:o + nb].reshape(h, w, 3).copy())
+                boxes.append(k["boxes"])
+        return {"rows": rows, "boxes": boxes, "crops": crops}
 
     def profile_pass(self):
         """The kernel events behind `roofline` / `conv_profile_last_step`: ONE extra pass after the timed region, on lane 0 alone (no other lane's
@@ -728,6 +783,40 @@ class Runner:
         return (f"{self.W}x{self.H} frame, YOLO11{a.arch}-pose (random-init), SAHI {a.slice}x{a.slice}/{a.overlap} ({self.items_per_frame - 1} slices + full frame), "
                 f"net input {self.imgsz}, conf {a.conf}, NMS 0.7, {self.pp_type}/IOS/0.5{'/agnostic' if self.class_agnostic else ''} merge"
                 + (f", Real-ESRGAN x4 on {a.sr_crops} crops/frame (sizes {self.sr_sizes})" if a.sr_crops > 0 else ", no SR"))
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, out):
+    """--dump-outputs DIR: Runner.kept_outputs as .npy files, DUMP_BYTES at most in all. Returns the bytes written.
+        detections.npy            merged detection rows as the pipeline returns them (box, score, class, keypoints), float32, frame after frame
+        crop_boxes.npy            the boxes the enhancer cropped, float64 (n, 4)
+        enhanced_crops.npy        pixels of the enhanced crops (BGR, row-major), float32, one crop after the other
+        enhanced_crop_shapes.npy  (height, width, 3) of each crop in enhanced_crops.npy, float64
+        enhanced_crop_index.npy   position in crop_boxes of each crop in enhanced_crops.npy, float64: every crop, or a fixed seeded sample of
+                                  them when all their pixels would not fit the budget"""
+    files = {"detections": np.concatenate(out["rows"], 0).astype(np.float32) if out["rows"] else np.zeros((0, 0), np.float32)}
+    if out["boxes"]:
+        crops = out["crops"]
+        files["crop_boxes"] = np.concatenate(out["boxes"], 0).astype(np.float64)
+        room = (DUMP_BYTES - files["detections"].nbytes - files["crop_boxes"].nbytes - 32 * len(crops) - 5 * 256) // 4    # 256: an .npy header at most
+        take, used = [], 0
+        for j in np.random.default_rng(0).permutation(len(crops)):
+            if used + crops[j].size <= room:
+                take.append(int(j))
+                used += crops[j].size
+        take.sort()
+        files["enhanced_crops"] = np.concatenate([crops[j].reshape(-1) for j in take] + [np.zeros(0, np.uint8)]).astype(np.float32)
+        files["enhanced_crop_shapes"] = np.asarray([crops[j].shape for j in take], np.float64).reshape(-1, 3)
+        files["enhanced_crop_index"] = np.asarray(take, np.float64)
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, a in files.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+        total += os.path.getsize(os.path.join(path, name + ".npy"))
+    assert total <= DUMP_BYTES, total
+    return total
 
 
 def make_ctx(args, rank=0, world=1, local_rank=0, dev=None, backend="nccl"):
@@ -949,7 +1038,10 @@ def main():
         return int(total - free)
 
     main_r = Runner(args, ctx)
-    dt = main_r.timed(args.warmup, args.steps)
+    dt = main_r.timed(args.warmup, args.steps, keep_last=bool(args.dump_outputs))
+    if args.dump_outputs and rank == 0:
+        nb = dump_outputs(args.dump_outputs, main_r.last_outputs)
+        print(f"[bench] --dump-outputs: step {args.steps - 1} of the timed loop, {nb / 1e6:.1f} MB in {args.dump_outputs}", file=sys.stderr, flush=True)
     hbm_headline = sample_hbm()
     main_mem = main_r.mem()
     B = main_r.B

@@ -181,3 +181,71 @@ def test_bench_lanes_deal_every_group_exactly_once():
                 if all_groups:
                     owner = (len(all_groups) - 1) % L
                     assert lanes[owner].my_groups(n_steps)[-1][0] == len(all_groups) - 1
+
+
+def test_bench_dump_outputs_reads_the_last_batch_and_keeps_the_budget(tmp_path):
+    """bench.py --dump-outputs: the kept frame's crops are cut out of the lane's last SR batch (16-byte aligned entries, boxes clamped
+    to the frame, the frame's crops after those of earlier frames in the batch, the frame on another lane); the .npy files are float
+    and round-trip the pixels; a budget too small for every crop keeps the same seeded sample on every call."""
+    import importlib.util
+    import types
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert bench.parse(["--steps", "3", "--dump-outputs", "d"]).dump_outputs == "d"
+    rng = np.random.default_rng(1)
+    H, W, sc = 200, 300, 4
+
+    def lane(batch, kept_fid):
+        r = bench.Runner.__new__(bench.Runner)
+        r.H, r.W, r.jpeg_io, r.sub = H, W, False, []
+        r.pipe = types.SimpleNamespace(sr=types.SimpleNamespace(scale=sc))
+        meta, offs, chunks, want = [], [0], [], None
+        for fid, boxes in batch:
+            meta.append((fid, len(boxes)))
+            crops = []
+            for x0, y0, x1, y1 in boxes:
+                c = rng.integers(0, 256, ((min(H, y1) - max(0, y0)) * sc, (min(W, x1) - max(0, x0)) * sc, 3), dtype=np.uint8)
+                pad = (c.size + 15) // 16 * 16
+                chunks.append(np.concatenate([c.reshape(-1), np.full(pad - c.size, 77, np.uint8)]))
+                offs.append(offs[-1] + pad)
+                crops.append(c)
+            if fid == kept_fid:
+                want = crops
+        r.host_sr = torch.from_numpy(np.concatenate(chunks + [np.zeros(64, np.uint8)]))
+        r.last_batch = (meta, np.asarray(offs, np.int64))
+        r.kept = {kept_fid: {"rows": rng.random((5, 21)).astype(np.float32), "boxes": np.asarray(dict(batch)[kept_fid], np.int32)}}
+        return r, want
+
+    def boxes(n):
+        s = rng.choice([24, 32, 48], n)
+        x, y = rng.integers(-10, W - 10, n), rng.integers(-10, H - 10, n)
+        return [(int(a), int(b), int(a + c), int(b + c)) for a, b, c in zip(x, y, s)]
+
+    r0, want0 = lane([((7, 0), boxes(4)), ((8, 0), boxes(5)), ((9, 0), boxes(3))], (9, 0))
+    got = r0.kept_outputs()
+    assert len(got["crops"]) == 3 and all(np.array_equal(a, b) for a, b in zip(got["crops"], want0))
+    r1, want1 = lane([((3, 0), boxes(2)), ((4, 0), boxes(6))], (4, 0))
+    r0.kept, r0.sub = {}, [r1]
+    got = r0.kept_outputs()
+    assert len(got["rows"]) == 1 and len(got["crops"]) == 6 and all(np.array_equal(a, b) for a, b in zip(got["crops"], want1))
+
+    bench.dump_outputs(str(tmp_path / "all"), got)
+    f = {p.stem: np.load(p) for p in (tmp_path / "all").iterdir()}
+    assert set(f) == {"detections", "crop_boxes", "enhanced_crops", "enhanced_crop_shapes", "enhanced_crop_index"}
+    assert all(a.dtype in (np.float32, np.float64) for a in f.values())
+    assert np.array_equal(f["detections"], got["rows"][0]) and f["enhanced_crop_index"].tolist() == list(range(6))
+    o = 0
+    for c, s in zip(want1, f["enhanced_crop_shapes"].astype(int)):
+        assert np.array_equal(f["enhanced_crops"][o:o + s.prod()].reshape(s), c)
+        o += s.prod()
+    assert o == f["enhanced_crops"].size
+
+    bench.DUMP_BYTES = 200_000
+    picks = []
+    for k in range(2):
+        n = bench.dump_outputs(str(tmp_path / f"small{k}"), got)
+        assert n <= 200_000
+        picks.append(np.load(tmp_path / f"small{k}" / "enhanced_crop_index.npy").tolist())
+    assert 0 < len(picks[0]) < 6 and picks[0] == picks[1]
