@@ -208,7 +208,7 @@ def _as_frame(frame: np.ndarray) -> np.ndarray:
 
 
 class Detector:
-    """YOLO11{n,s}-pose on one GPU (ffp_det_*)."""
+    """YOLO11{n,s,m,l}-pose on one GPU (ffp_det_*); `arch` is the scale ("n", "s", "m" or "l", see arch.yolo11_scale_of)."""
 
     def __init__(self, weights, arch: str = "s", nc: int = 1, nkpt: int = 5, device: int = 0, precision: int = PREC_F32):
         buf = _weights_bytes(weights)

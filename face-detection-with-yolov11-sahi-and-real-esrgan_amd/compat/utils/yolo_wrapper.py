@@ -15,7 +15,7 @@ from typing import List, Optional
 import numpy as np
 
 import ffp_amd  # noqa: F401
-from ffp_amd import _lib, synth, weights_io
+from ffp_amd import _lib, arch, synth, weights_io
 from sahi.models.base import DetectionModel
 from sahi.prediction import ObjectPrediction
 
@@ -73,8 +73,7 @@ class YOLO:
         else:
             raise ValueError(f"{model_path}: Ultralytics .pt checkpoints are pickled module graphs; convert them once with "
                              "weights_io.from_ultralytics_state_dict where `ultralytics` is installed and pass the .ffpw file")
-        c0 = W["model.0.conv.weight"].shape[0]
-        self.arch = {16: "n", 32: "s"}[c0]
+        self.arch = arch.yolo11_scale_of(W)       # n / s / m / l by the inventory; a custom or unknown layout is refused by name
         self.nc = int(W["model.23.cv3.0.2.weight"].shape[0])
         self.nkpt = int(W["model.23.cv4.0.2.weight"].shape[0]) // 3
         self._det = _lib.Detector(W, arch=self.arch, nc=self.nc, nkpt=self.nkpt, device=_device_index(device),

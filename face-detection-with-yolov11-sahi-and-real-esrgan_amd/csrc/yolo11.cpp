@@ -1,4 +1,4 @@
-// yolo11.cpp — YOLO11{n,s}-pose as a plan of HIP launches over a ragged batch of crops.
+// yolo11.cpp — YOLO11{n,s,m,l}-pose as a plan of HIP launches over a ragged batch of crops.
 //
 // Graph: Ultralytics `yolo11-pose.yaml`; the reference reaches it through
 // `self.model.predict(...)` at utils/yolo_wrapper.py:74-80. Every Concat is virtual: producers write straight into
@@ -29,7 +29,8 @@ void letterbox_geometry(int h, int w, int imgsz, int32_t* o) {
 }
 
 DetEngine::DetEngine(const void* weights, size_t nbytes, int arch, int nc, int nkpt, int device, int precision) {
-  FFP_CHECK(arch == 'n' || arch == 's', FFP_ERR_ARG, "arch must be 'n' or 's'");
+  FFP_CHECK(arch == 'n' || arch == 's' || arch == 'm' || arch == 'l', FFP_ERR_ARG,
+            "arch '%c': the detector is built for YOLO11 scales n, s, m and l", arch > 32 && arch < 127 ? (char)arch : '?');
   FFP_CHECK(nc >= 1 && nc <= 256 && nkpt >= 0 && nkpt <= 32, FFP_ERR_ARG, "nc/nkpt out of range");
   FFP_CHECK(precision == FFP_PREC_F32 || precision == FFP_PREC_F16 || precision == FFP_PREC_F32X3, FFP_ERR_ARG, "precision");
   int ndev = 0;
@@ -88,8 +89,12 @@ void DetEngine::build_plan(DetPlan& P, const std::vector<int>& hs, const std::ve
     for (int i = 0; i < n; ++i) { h[i] = hs[i] >> l; w[i] = ws[i] >> l; }
     P.L[l] = P.add_level(h, w, st_);
   }
-  const double width = scale_ == 'n' ? 0.25 : 0.50;
-  auto ch = [&](int c) { return make_div8(std::min(c, 1024) * width); };
+  // [depth, width, max_channels] of yolo11-pose.yaml; scales m and l also force C3k inside every C3k2 (Ultralytics parse_model)
+  const double width = scale_ == 'n' ? 0.25 : scale_ == 's' ? 0.50 : 1.00;
+  const int max_ch = (scale_ == 'n' || scale_ == 's') ? 1024 : 512;
+  const int reps = scale_ == 'l' ? 2 : 1;                  // max(round(2 * depth), 1): C3k2 and C2PSA repeats
+  const bool force_c3k = scale_ == 'm' || scale_ == 'l';
+  auto ch = [&](int c) { return make_div8(std::min(c, max_ch) * width); };
   const int c64 = ch(64), c128 = ch(128), c256 = ch(256), c512 = ch(512), c1024 = ch(1024);
   const DType T = dt_;
 
@@ -114,28 +119,33 @@ void DetEngine::build_plan(DetPlan& P, const std::vector<int>& hs, const std::ve
     cv(p + ".cv1.conv", x, t, 1, ACT_SILU);
     cv(p + ".cv2.conv", t, out, 1, ACT_SILU, &x);
   };
-  // C3k2(c1, c2, n=1, c3k, e): cat = [a | b | m(b)]; out = cv2(cat)
-  auto c3k2 = [&](const std::string& p, const TView& in, const TView& out, int c2, bool c3k, double e, const TView* up2 = nullptr) {
+  // C3k(c, c, n=2) on view b into view mo: cv3(cat(m(cv1(b)), cv2(b)))
+  auto c3k = [&](const std::string& p, const TView& b, const TView& mo, int c) {
+    const int c_ = c / 2;
+    TView cat2 = P.alloc(b.lvl, 2 * c_, T);
+    TView a0 = P.alloc(b.lvl, c_, T), a1 = P.alloc(b.lvl, c_, T);
+    const int side = 10;                               // C3k's second branch (one 1x1 conv over b) runs beside the bottleneck chain
+    if (P.lane_mode() == 1) P.fork(side);
+    P.cur_lane = P.lane_mode() == 1 ? side : 0;
+    cv(p + ".cv2.conv", b, cat2.slice(c_, c_), 1, ACT_SILU);
+    P.cur_lane = 0;
+    cv(p + ".cv1.conv", b, a0, 1, ACT_SILU);
+    bottleneck(p + ".m.0", a0, a1, c_);
+    bottleneck(p + ".m.1", a1, cat2.slice(0, c_), c_);
+    if (P.lane_mode() == 1) P.join(side);              // each C3k joins its side lane before the next one forks it again
+    cv(p + ".cv3.conv", cat2, mo, 1, ACT_SILU);
+  };
+  // C3k2(c1, c2, n, c3k, e): cat = [a | b | m.0(b) | m.1(m.0(b)) ...]; out = cv2(cat)
+  auto c3k2 = [&](const std::string& p, const TView& in, const TView& out, int c2, bool use_c3k, double e, const TView* up2 = nullptr) {
     const int c = (int)(c2 * e);
-    TView cat = P.alloc(in.lvl, 3 * c, T);
+    use_c3k = use_c3k || force_c3k;
+    TView cat = P.alloc(in.lvl, (2 + reps) * c, T);
     cv(p + ".cv1.conv", in, cat.slice(0, 2 * c), 1, ACT_SILU, nullptr, up2);
-    const TView b = cat.slice(c, c), mo = cat.slice(2 * c, c);
-    if (!c3k) {
-      bottleneck(p + ".m.0", b, mo, c / 2);
-    } else {     // C3k(c, c, n=2): cv3(cat(m(cv1(x)), cv2(x)))
-      const int c_ = c / 2;
-      TView cat2 = P.alloc(in.lvl, 2 * c_, T);
-      TView a0 = P.alloc(in.lvl, c_, T), a1 = P.alloc(in.lvl, c_, T);
-      const int side = 10;                               // C3k's second branch (one 1x1 conv over b) runs beside the bottleneck chain
-      if (P.lane_mode() == 1) P.fork(side);
-      P.cur_lane = P.lane_mode() == 1 ? side : 0;
-      cv(p + ".m.0.cv2.conv", b, cat2.slice(c_, c_), 1, ACT_SILU);
-      P.cur_lane = 0;
-      cv(p + ".m.0.cv1.conv", b, a0, 1, ACT_SILU);
-      bottleneck(p + ".m.0.m.0", a0, a1, c_);
-      bottleneck(p + ".m.0.m.1", a1, cat2.slice(0, c_), c_);
-      if (P.lane_mode() == 1) P.join(side);
-      cv(p + ".m.0.cv3.conv", cat2, mo, 1, ACT_SILU);
+    for (int i = 0; i < reps; ++i) {
+      const TView b = cat.slice((1 + i) * c, c), mo = cat.slice((2 + i) * c, c);
+      const std::string pm = p + ".m." + std::to_string(i);
+      if (!use_c3k) bottleneck(pm, b, mo, c / 2);
+      else c3k(pm, b, mo, c);
     }
     cv(p + ".cv2.conv", cat, out, 1, ACT_SILU);
   };
@@ -166,6 +176,8 @@ void DetEngine::build_plan(DetPlan& P, const std::vector<int>& hs, const std::ve
     // the image-input conv's output bound is known from the weights alone (inputs in [0, 1], |SiLU(v)| <= max(|v|, 0.279)), so the
     // first MFMA conv finds its input's exponent without a pass over the data
     P.set_amax_bound(x0, std::max(o.pc->out_bound, 0.3f));
+    // YOLO11m/l (64 stem channels) keep the two-kernel path: a four-chunk form of the fused loader lost to it at imgsz 1024 and tied at
+    // 512 (profiles/r05_stem_ab_yolo11m.txt)
     if (direct && stem_conv_eligible(o, m1)) {
       // fp32-split YOLO11s: model.0 runs inside model.1's loader on the matrix cores; x0 is never stored
       o.flops = conv_flops_of(*o.pc, x0.lvl->actual_px());
@@ -217,24 +229,27 @@ void DetEngine::build_plan(DetPlan& P, const std::vector<int>& hs, const std::ve
     TView pb = P.alloc(P.L[5], 2 * h, T);
     cv("model.10.cv1.conv", x9, pb, 1, ACT_SILU);
     const TView b = pb.slice(h, h);
-    TView qkv = P.alloc(P.L[5], nh * (2 * kd + hd), T);
-    cv("model.10.m.0.attn.qkv.conv", b, qkv, 1, ACT_NONE);
-    TView ao = P.alloc(P.L[5], h, T);
-    P.add([qkv, ao, nh, kd, hd](hipStream_t s) { launch_psa_attention(qkv, ao, nh, kd, hd, s); });
-    TView xa = P.alloc(P.L[5], h, T);
-    {
-      DwConvOp o;
-      o.pc = conv("model.10.m.0.attn.pe.conv");
-      o.in = qkv; o.in.C = h; o.out = xa; o.act = ACT_NONE;
-      o.grp = hd; o.grp_stride = 2 * kd + hd; o.grp_off = 2 * kd;
-      o.has_res = true; o.res = ao;
-      P.add([o](hipStream_t s) { launch_dwconv(o, s); });
+    for (int i = 0; i < reps; ++i) {                  // PSABlocks m.0, m.1, ... each in place on b
+      const std::string pm = "model.10.m." + std::to_string(i);
+      TView qkv = P.alloc(P.L[5], nh * (2 * kd + hd), T);
+      cv(pm + ".attn.qkv.conv", b, qkv, 1, ACT_NONE);
+      TView ao = P.alloc(P.L[5], h, T);
+      P.add([qkv, ao, nh, kd, hd](hipStream_t s) { launch_psa_attention(qkv, ao, nh, kd, hd, s); });
+      TView xa = P.alloc(P.L[5], h, T);
+      {
+        DwConvOp o;
+        o.pc = conv(pm + ".attn.pe.conv");
+        o.in = qkv; o.in.C = h; o.out = xa; o.act = ACT_NONE;
+        o.grp = hd; o.grp_stride = 2 * kd + hd; o.grp_off = 2 * kd;
+        o.has_res = true; o.res = ao;
+        P.add([o](hipStream_t s) { launch_dwconv(o, s); });
+      }
+      TView b2 = P.alloc(P.L[5], h, T);
+      cv(pm + ".attn.proj.conv", xa, b2, 1, ACT_NONE, &b);
+      TView f1 = P.alloc(P.L[5], 2 * h, T);
+      cv(pm + ".ffn.0.conv", b2, f1, 1, ACT_SILU);
+      cv(pm + ".ffn.1.conv", f1, b, 1, ACT_NONE, &b2);
     }
-    TView b2 = P.alloc(P.L[5], h, T);
-    cv("model.10.m.0.attn.proj.conv", xa, b2, 1, ACT_NONE, &b);
-    TView f1 = P.alloc(P.L[5], 2 * h, T);
-    cv("model.10.m.0.ffn.0.conv", b2, f1, 1, ACT_SILU);
-    cv("model.10.m.0.ffn.1.conv", f1, b, 1, ACT_NONE, &b2);
     cv("model.10.cv2.conv", pb, x10, 1, ACT_SILU);
   }
   // ---- neck ------------------------------------------------------------------------------------------------------------

@@ -77,8 +77,8 @@ int ffp_letterbox_geometry(int h, int w, int imgsz, int32_t* out6);
  * YOLOv11PoseDetectionModel.load_model / perform_inference (utils/yolo_wrapper.py:47-56, 63-82)
  * ------------------------------------------------------------------------------------------------------- */
 
-/* weights: FFPW container (see weights_io.py) holding the fused conv tensors of YOLO11{n,s}-pose.
- * arch: 'n' or 's'.  nc classes, nkpt keypoints of 3 values.  precision: FFP_PREC_*. */
+/* weights: FFPW container (see weights_io.py) holding the fused conv tensors of YOLO11{n,s,m,l}-pose.
+ * arch: 'n', 's', 'm' or 'l' (YOLO11 scales; any other is FFP_ERR_ARG).  nc classes, nkpt keypoints of 3 values.  precision: FFP_PREC_*. */
 int ffp_det_create(const void* weights, size_t nbytes, int arch, int nc, int nkpt, int device, int precision,
                    ffp_det** out);
 void ffp_det_destroy(ffp_det* d);

@@ -1,5 +1,5 @@
 """Per-layer time, algorithmic HBM bytes and achieved GB/s of the detector's convolutions for a 2-frame group (122 items).
-Usage on the GPU box: python tools/det_layers.py [--f32] [--all]"""
+Usage on the GPU box: python tools/det_layers.py [--arch n|s|m|l] [--f32] [--all]"""
 import os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -8,9 +8,10 @@ from ffp_amd import _lib, pipeline, synth
 import torch
 
 H, W, NF = 2160, 3840, 2
+ARCH = sys.argv[sys.argv.index("--arch") + 1] if "--arch" in sys.argv else "s"
 cfg = pipeline.PipeConfig(sr_crops=0)
-Wd = synth.yolo11_pose_weights("s")
-pipe = pipeline.FramePipeline(Wd, None, cfg, arch="s", det_precision=_lib.PREC_F32 if "--f32" in sys.argv else _lib.PREC_F32X3)
+Wd = synth.yolo11_pose_weights(ARCH)
+pipe = pipeline.FramePipeline(Wd, None, cfg, arch=ARCH, det_precision=_lib.PREC_F32 if "--f32" in sys.argv else _lib.PREC_F32X3)
 frame = torch.from_numpy(np.concatenate([synth.synthetic_frame(H, W, seed=i) for i in range(NF)], 0)).cuda()
 for it in range(4):
     pipe.det.set_profile(it == 3)
@@ -36,7 +37,7 @@ for x in det:
     by = px_in * (3 if name == "model.0.conv" else cin) * es + px_out * cout * 4
     rows.append((x["ms"], name, variant, cin, cout, k, by))
     tot_ms += x["ms"]; tot_b += by
-print(f"total conv {tot_ms:.3f} ms for {NF} frames, algorithmic bytes {tot_b/1e9:.2f} GB -> {tot_b/tot_ms/1e9:.2f} TB/s average; graph-mode stage ms:", pipe.det.last_ms())
+print(f"YOLO11{ARCH}-pose, total conv {tot_ms:.3f} ms for {NF} frames, algorithmic bytes {tot_b/1e9:.2f} GB -> {tot_b/tot_ms/1e9:.2f} TB/s average; graph-mode stage ms:", pipe.det.last_ms())
 flops = {x["name"].split(" ", 1)[1]: x["flops"] for x in det}
 split = 1 if "--f32" in sys.argv else 3              # MFMA products per algorithmic MAC in the split arithmetic
 # which roof binds a layer: its algorithmic bytes at 8 TB/s (what streams at best is 6.0-6.2, MI355X_MICROARCH.md) or its MFMA work (x3 in the split
