@@ -20,6 +20,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FFP_LIB") or os.path.join(_HERE, "libffp.so")
 
 PREC_F32, PREC_F16, PREC_F32X3 = 0, 1, 2
+SR_ALPHA_REALESRGAN, SR_ALPHA_LINEAR = 0, 1          # ffp_sr_enhance_ex alpha_mode (include/ffp.h)
 CHAN_AS_BGR, CHAN_AS_RGB = 0, 1
 PP_NMS, PP_GREEDYNMM = 0, 1
 METRIC_IOU, METRIC_IOS = 0, 1
@@ -74,6 +75,8 @@ _SIGS = {
     "ffp_sr_create": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_void_p)]),
     "ffp_sr_destroy": (None, [C.c_void_p]),
     "ffp_sr_enhance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "ffp_sr_enhance_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                    C.c_int, C.c_int, C.c_void_p]),
     "ffp_sr_enhance_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "ffp_sr_enhance_batch": (C.c_int, [C.c_void_p, C.c_int, _p(C.c_void_p), _p(C.c_int32), _p(C.c_int32), C.c_int, C.c_int, C.c_int,
                                        _p(C.c_void_p)]),
@@ -121,6 +124,7 @@ _SIGS = {
                                      C.c_int, _p(C.c_float)]),
     "ffp_op_conv2d": (C.c_int, [C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_float), _p(C.c_float), C.c_int,
                                 C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_float), C.c_float, _p(C.c_float)]),
+    "ffp_op_resize_lanczos4": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -430,6 +434,22 @@ class Enhancer:
         _check(lib().ffp_sr_enhance_batch(self._h, n, ip, _ip(hs), _ip(ws), tile, tile_pad, pre_pad, op))
         return outs
 
+    def enhance_ex(self, img: np.ndarray, max_range: int = 255, alpha_mode: int = SR_ALPHA_REALESRGAN, out_h: Optional[int] = None,
+                   out_w: Optional[int] = None, tile: int = 0, tile_pad: int = 10, pre_pad: int = 0) -> np.ndarray:
+        """ffp_sr_enhance_ex: RealESRGANer.enhance for an HxW (gray), HxWx3 (BGR) or HxWx4 (BGRA) uint8 / uint16 array with the
+        given max_range (255 / 65535), alpha upsampler and output size (default scale*h x scale*w; any other size is a Lanczos4
+        resize of the result). Returns uint16 when max_range == 65535, else uint8, with the input's number of channels."""
+        a = np.ascontiguousarray(img)
+        if a.dtype not in (np.uint8, np.uint16) or a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] not in (3, 4)):
+            raise ValueError(f"expected an HxW, HxWx3 or HxWx4 uint8 / uint16 array, got {a.dtype} {a.shape}")
+        h, w = a.shape[:2]
+        oh = h * self.scale if out_h is None else int(out_h)
+        ow = w * self.scale if out_w is None else int(out_w)
+        out = np.zeros((oh, ow) + a.shape[2:], np.uint16 if max_range == 65535 else np.uint8)
+        _check(lib().ffp_sr_enhance_ex(self._h, a.ctypes.data, h, w, 1 if a.ndim == 2 else a.shape[2], 8 * a.itemsize, int(max_range),
+                                       int(alpha_mode), oh, ow, tile, tile_pad, pre_pad, out.ctypes.data))
+        return out
+
     def enhance_crops_dev(self, d_frames: Sequence[int], H: int, W: int, boxes: np.ndarray, d_out: int, out_cap: int,
                           frame_of_box: Optional[np.ndarray] = None, tile: int = 400, tile_pad: int = 10, wait: bool = True) -> np.ndarray:
         """Crops of resident BGR frame(s) (device pointers) -> enhanced crops packed in device memory at d_out.
@@ -623,6 +643,19 @@ def op_conv1x1_up2(coarse: np.ndarray, fine: np.ndarray, w: np.ndarray, b: np.nd
     y = np.zeros((n, h, wd, w.shape[0]), np.float32)
     _check(lib().ffp_op_conv1x1_up2(device, precision, _fp(coarse), _fp(fine), n, h, wd, coarse.shape[3], cf, _fp(w), _fp(b), w.shape[0], act, _fp(y)))
     return y
+
+
+def op_resize_lanczos4(img: np.ndarray, out_h: int, out_w: int, device: int = 0) -> np.ndarray:
+    """cv2.resize(img, (out_w, out_h), interpolation=INTER_LANCZOS4) through the HIP kernel (ffp_op_resize_lanczos4).
+    img: HxW, HxWx3 or HxWx4, uint8 or uint16; the result has the same type and channels."""
+    a = np.ascontiguousarray(img)
+    if a.dtype not in (np.uint8, np.uint16) or a.ndim not in (2, 3):
+        raise ValueError(f"expected an HxW or HxWxC uint8 / uint16 array, got {a.dtype} {a.shape}")
+    h, w = a.shape[:2]
+    out = np.zeros((int(out_h), int(out_w)) + a.shape[2:], a.dtype)
+    _check(lib().ffp_op_resize_lanczos4(device, a.ctypes.data, h, w, 1 if a.ndim == 2 else a.shape[2], 8 * a.itemsize, int(out_h), int(out_w),
+                                        out.ctypes.data))
+    return out
 
 
 def op_conv2d_shape(shape: int = -1) -> None:

@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import os
 import time
+from typing import NamedTuple
 
 import numpy as np
 from PIL import Image
@@ -45,11 +46,58 @@ class RealESRGANer:
         self._sr = _lib.Enhancer(W, scale, nb, device=gpu_id or 0, half=bool(half))
 
     def enhance(self, img, outscale=None, alpha_upsampler="realesrgan"):
-        if img.ndim != 3 or img.shape[2] != 3 or img.dtype != np.uint8:
-            raise ValueError("this build enhances 3-channel uint8 BGR images (the face-crop path)")
-        if outscale is not None and float(outscale) != float(self.scale):
-            raise NotImplementedError("outscale != scale (Lanczos resize) is never used by the reference (utils/enhancer.py:214)")
-        return self._sr.enhance(np.ascontiguousarray(img), self.tile_size, self.tile_pad, self.pre_pad), "RGB"
+        """realesrgan 0.3.0 RealESRGANer.enhance: gray / BGR / BGRA, 8- or 16-bit, any outscale -> (image, mode)."""
+        img = np.asarray(img)
+        lay = enhance_layout(img.shape, img.dtype, img.max() if img.size and img.dtype in (np.uint8, np.uint16) else 0, self.scale, outscale,
+                             alpha_upsampler)
+        img = np.ascontiguousarray(img)
+        if lay.fast_path:           # 3-channel uint8 at the net's scale: the path FaceEnhancer takes (utils/enhancer.py:214)
+            return self._sr.enhance(img, self.tile_size, self.tile_pad, self.pre_pad), lay.mode
+        return self._sr.enhance_ex(img, lay.max_range, lay.alpha_mode, lay.out_h, lay.out_w, self.tile_size, self.tile_pad, self.pre_pad), lay.mode
+
+
+class EnhanceLayout(NamedTuple):
+    mode: str                   # 'L', 'RGB' or 'RGBA'
+    max_range: int              # 255 or 65535
+    out_dtype: type             # np.uint8 or np.uint16
+    out_h: int
+    out_w: int
+    resize: bool                # out size != scale * input size: a Lanczos4 resize of the result
+    alpha_mode: int             # _lib.SR_ALPHA_REALESRGAN / SR_ALPHA_LINEAR (meaningful for 'RGBA')
+    fast_path: bool             # 3-channel uint8 without a resize (Enhancer.enhance)
+
+
+def enhance_layout(shape, dtype, img_max, scale, outscale=None, alpha_upsampler="realesrgan") -> EnhanceLayout:
+    """What realesrgan 0.3.0's RealESRGANer.enhance(img, outscale, alpha_upsampler) makes of an input of this shape, dtype and
+    maximum (reference call utils/enhancer.py:214). Raises ValueError for what this build does not enhance: other dtypes and
+    shapes, an empty image or an outscale that gives an empty output, and a uint16 image with maximum exactly 256 under the
+    'cv2' alpha upsampler (its alpha is 256/255 > 1, and realesrgan's uint8 cast of the result is then platform-defined)."""
+    dtype = np.dtype(dtype)
+    if dtype not in (np.uint8, np.uint16):
+        raise ValueError(f"RealESRGANer.enhance takes uint8 or uint16 images, got {dtype}")
+    if len(shape) == 2:
+        mode = "L"
+    elif len(shape) == 3 and shape[2] == 4:
+        mode = "RGBA"
+    elif len(shape) == 3 and shape[2] == 3:
+        mode = "RGB"
+    else:
+        raise ValueError(f"RealESRGANer.enhance takes HxW, HxWx3 or HxWx4 images, got shape {tuple(shape)}")
+    h, w = int(shape[0]), int(shape[1])
+    if h < 1 or w < 1:
+        raise ValueError(f"empty image {tuple(shape)}")
+    max_range = 65535 if float(img_max) > 256 else 255
+    alpha_mode = _lib.SR_ALPHA_REALESRGAN if alpha_upsampler == "realesrgan" else _lib.SR_ALPHA_LINEAR
+    if mode == "RGBA" and alpha_mode == _lib.SR_ALPHA_LINEAR and dtype == np.uint16 and float(img_max) == 256:
+        raise ValueError("uint16 image with maximum 256 and alpha_upsampler 'cv2': realesrgan's result is platform-defined")
+    out_h, out_w = h * scale, w * scale
+    if outscale is not None and float(outscale) != float(scale):
+        out_h, out_w = int(h * outscale), int(w * outscale)
+        if out_h < 1 or out_w < 1:
+            raise ValueError(f"outscale {outscale} gives an empty {out_w}x{out_h} output for a {w}x{h} image")
+    resize = (out_h, out_w) != (h * scale, w * scale)
+    return EnhanceLayout(mode, max_range, np.uint16 if max_range == 65535 else np.uint8, out_h, out_w, resize, alpha_mode,
+                         mode == "RGB" and dtype == np.uint8 and not resize)
 
 
 def _imread_bgr(path):

@@ -71,6 +71,16 @@ void upload_frame(DetEngine& e, const uint8_t* frame, int H, int W) {
   FFP_HIP(hipMemcpyAsync(e.scratch_frame.p, frame, nb, hipMemcpyHostToDevice, e.stream()));
 }
 
+// the host side of a Lanczos4 resize: tables built here, uploaded on `st` into `tab` (the host copy must outlive the upload)
+void resize_lanczos4_dev(const void* d_src, int h, int w, int cn, int wide, int out_h, int out_w, void* d_dst, DevBuf& tab,
+                         std::vector<uint8_t>& host_tab, hipStream_t st) {
+  host_tab.resize(lanczos4_table_bytes(out_h, out_w));
+  lanczos4_pack(lanczos4_axis(w, out_w), lanczos4_axis(h, out_h), wide, host_tab.data());
+  tab.ensure(host_tab.size());
+  FFP_HIP(hipMemcpyAsync(tab.p, host_tab.data(), host_tab.size(), hipMemcpyHostToDevice, st));
+  launch_resize_lanczos4(d_src, h, w, cn, wide, tab.p, out_h, out_w, d_dst, st);
+}
+
 }  // namespace
 
 extern "C" {
@@ -374,6 +384,57 @@ int ffp_sr_enhance(ffp_sr* s, const uint8_t* bgr, int h, int w, int tile, int ti
   uint8_t* outs[1] = {out_bgr};
   const int32_t hs[1] = {h}, ws[1] = {w};
   return ffp_sr_enhance_batch(s, 1, ins, hs, ws, tile, tile_pad, pre_pad, outs);
+}
+
+// realesrgan 0.3.0 RealESRGANer.enhance for every layout (reference call utils/enhancer.py:214; rules in include/ffp.h):
+// the colour image and, for alpha_mode REALESRGAN, the alpha plane go through the network as ONE ragged batch (two SrImages
+// over the same input / canvas, differing in their channel selection); the LINEAR alpha and the Lanczos4 outscale follow on
+// the enhancer's stream, and the final buffer is copied to the host once.
+int ffp_sr_enhance_ex(ffp_sr* s, const void* img, int h, int w, int channels, int bits, int max_range, int alpha_mode, int out_h, int out_w,
+                      int tile, int tile_pad, int pre_pad, void* out) {
+  FFP_API_BEGIN
+  FFP_CHECK(s && img && out, FFP_ERR_ARG, "null argument");
+  FFP_CHECK(h >= 1 && w >= 1 && out_h >= 1 && out_w >= 1, FFP_ERR_ARG, "empty image (%dx%d -> %dx%d)", h, w, out_h, out_w);
+  FFP_CHECK(channels == 1 || channels == 3 || channels == 4, FFP_ERR_ARG, "channels %d (1, 3 or 4)", channels);
+  FFP_CHECK(bits == 8 || bits == 16, FFP_ERR_ARG, "bits %d (8 or 16)", bits);
+  FFP_CHECK(max_range == 255 || (max_range == 65535 && bits == 16), FFP_ERR_ARG, "max_range %d with %d-bit input", max_range, bits);
+  FFP_CHECK(alpha_mode == FFP_SR_ALPHA_REALESRGAN || alpha_mode == FFP_SR_ALPHA_LINEAR, FFP_ERR_ARG, "alpha_mode %d", alpha_mode);
+  SrEngine& e = s->eng;
+  FFP_HIP(hipSetDevice(e.device()));
+  e.wait_done();                      // one enhancement in flight per handle: its scratch buffers are about to be reused
+  const int sc = e.scale();
+  const int ch = h * sc, cw = w * sc;
+  SrFmt fin, fout;
+  fin.cn = fout.cn = channels;
+  fin.wide = bits == 16;
+  fout.wide = max_range == 65535;
+  fin.range = fout.range = (float)max_range;
+  fin.sel = fout.sel = channels == 1 ? SR_SEL_GRAY : SR_SEL_BGR;
+  const size_t in_bytes = (size_t)h * w * fin.px_bytes(), canvas_bytes = (size_t)ch * cw * fout.px_bytes();
+  const size_t out_bytes = (size_t)out_h * out_w * fout.px_bytes();
+  const bool resize = out_h != ch || out_w != cw;
+  const size_t final_off = resize ? (canvas_bytes + 255) / 256 * 256 : 0;
+  e.scratch_in.ensure(in_bytes);
+  e.scratch_out.ensure(final_off + (resize ? out_bytes : canvas_bytes));
+  FFP_HIP(hipMemcpyAsync(e.scratch_in.p, img, in_bytes, hipMemcpyHostToDevice, e.stream()));
+  std::vector<SrImage> v(1);
+  v[0].in_off = 0; v[0].in_stride = w * fin.px_bytes(); v[0].h = h; v[0].w = w;
+  v[0].out_off = 0; v[0].out_stride = cw * fout.px_bytes();
+  v[0].in_fmt = fin; v[0].out_fmt = fout;
+  if (channels == 4 && alpha_mode == FFP_SR_ALPHA_REALESRGAN) {
+    v.push_back(v[0]);
+    v[1].in_fmt.sel = v[1].out_fmt.sel = SR_SEL_ALPHA;
+  }
+  e.enhance_dev(e.scratch_in.as<uint8_t>(), e.scratch_out.as<uint8_t>(), v, tile, tile_pad, pre_pad, false);
+  if (channels == 4 && alpha_mode == FFP_SR_ALPHA_LINEAR)
+    launch_alpha_linear(e.scratch_in.p, h, w, fin.wide, fin.range, ch, cw, e.scratch_out.p, fout.wide, e.stream());
+  std::vector<uint8_t> host_tab;
+  if (resize)
+    resize_lanczos4_dev(e.scratch_out.p, ch, cw, channels, fout.wide, out_h, out_w, e.scratch_out.as<uint8_t>() + final_off, e.scratch_tab,
+                        host_tab, e.stream());
+  e.wait_done();
+  FFP_HIP(hipMemcpy(out, e.scratch_out.as<uint8_t>() + final_off, out_bytes, hipMemcpyDeviceToHost));
+  FFP_API_END
 }
 
 // crops of one or several resident frames (frame_of_box == nullptr: all from d_frames[0]) -> one ragged SR batch
@@ -954,6 +1015,39 @@ int ffp_op_conv2d_time(int device, int precision, int n, int h, int w, int cin, 
     throw;
   }
   (void)hipStreamDestroy(st);
+  FFP_API_END
+}
+
+int ffp_op_resize_lanczos4(int device, const void* src, int h, int w, int channels, int bits, int out_h, int out_w, void* dst) {
+  FFP_API_BEGIN
+  FFP_CHECK(src && dst, FFP_ERR_ARG, "resize_lanczos4: null argument");
+  FFP_CHECK(h >= 1 && w >= 1 && out_h >= 1 && out_w >= 1, FFP_ERR_ARG, "resize_lanczos4: empty image (%dx%d -> %dx%d)", h, w, out_h, out_w);
+  FFP_CHECK(channels == 1 || channels == 3 || channels == 4, FFP_ERR_ARG, "resize_lanczos4: channels %d (1, 3 or 4)", channels);
+  FFP_CHECK(bits == 8 || bits == 16, FFP_ERR_ARG, "resize_lanczos4: bits %d (8 or 16)", bits);
+  const int wide = bits == 16;
+  const size_t in_bytes = ((size_t)h * w * channels) << wide, out_bytes = ((size_t)out_h * out_w * channels) << wide;
+  if (out_h == h && out_w == w) {     // cv::resize of the same size is a copy
+    std::memcpy(dst, src, out_bytes);
+    return FFP_OK;
+  }
+  int ndev = 0;
+  FFP_CHECK(hipGetDeviceCount(&ndev) == hipSuccess && device >= 0 && device < ndev, FFP_ERR_HIP, "resize_lanczos4: no HIP device %d", device);
+  FFP_HIP(hipSetDevice(device));
+  hipStream_t st;
+  FFP_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  try {
+    DevBuf din(in_bytes), dout(out_bytes), tab;
+    std::vector<uint8_t> host_tab;
+    FFP_HIP(hipMemcpyAsync(din.p, src, in_bytes, hipMemcpyHostToDevice, st));
+    resize_lanczos4_dev(din.p, h, w, channels, wide, out_h, out_w, dout.p, tab, host_tab, st);
+    FFP_HIP(hipStreamSynchronize(st));
+    FFP_HIP(hipMemcpy(dst, dout.p, out_bytes, hipMemcpyDeviceToHost));
+  } catch (...) {
+    (void)hipStreamSynchronize(st);
+    (void)hipStreamDestroy(st);
+    throw;
+  }
+  FFP_HIP(hipStreamDestroy(st));
   FFP_API_END
 }
 

@@ -225,11 +225,11 @@ void SrEngine::enhance_dev(const uint8_t* d_in, uint8_t* d_out, const std::vecto
         FFP_CHECK(shuf == 1 || (t.h % 2 == 0 && t.w % 2 == 0 && sxp % 2 == 0 && syp % 2 == 0), FFP_ERR_ARG,
                   "enhance: x2 model needs even tile geometry (tile %d, pad %d)", tile, tile_pad);
         t.src.src_off = im.in_off; t.src.src_stride = im.in_stride; t.src.src_h = im.h; t.src.src_w = im.w; t.src.pre_h = im.h + pre_pad; t.src.pre_w = im.w + pre_pad;
-        t.src.x0 = sxp; t.src.y0 = syp;
+        t.src.x0 = sxp; t.src.y0 = syp; t.src.fmt = im.in_fmt;
         // core region in output pixels, clipped to the un-padded output
         const int ox = sx * s, oy = sy * s;
         const int cw = std::min(ex * s, out_w) - ox, chh = std::min(ey * s, out_h) - oy;
-        t.dst.dst_off = im.out_off; t.dst.dst_stride = im.out_stride;
+        t.dst.dst_off = im.out_off; t.dst.dst_stride = im.out_stride; t.dst.fmt = im.out_fmt;
         t.dst.ox = ox; t.dst.oy = oy; t.dst.cw = std::max(cw, 0); t.dst.ch = std::max(chh, 0);
         t.dst.tx = (sx - sxp) * s; t.dst.ty = (sy - syp) * s;
         tiles.push_back(t);

@@ -3,7 +3,9 @@
 // Restates RealESRGANer.enhance's array handling (reference call utils/enhancer.py:214; realesrgan 0.3.0, SURVEY.md
 // Appendix D.2): uint8 BGR -> /255 -> RGB -> (reflect pre_pad / mod pad) -> [pixel_unshuffle for x2] -> net ->
 // clamp(0,1) -> BGR -> (x*255).round() uint8, with the tile loop's "copy the core of each padded tile" done by
-// the store kernel.
+// the store kernel. The pixel format is data in the tile tables (SrFmt): 8- or 16-bit storage with max_range 255 or
+// 65535, 1/3/4 channels, and which channels feed the network (BGR, gray or alpha replicated to RGB) and which channel
+// the result lands in (BGR, or BGR2GRAY into channel 0 / 3). Default: 3-channel uint8 BGR.
 #include "sr_ops.hpp"
 
 namespace ffp {
@@ -25,6 +27,16 @@ __device__ __forceinline__ int reflect2(int i, int n_pre, int n) {   // F.pad(..
   return i;
 }
 
+__device__ __forceinline__ float ld_px(const uint8_t* p, int c, int wide) {
+  return wide ? (float)reinterpret_cast<const uint16_t*>(p)[c] : (float)p[c];
+}
+
+__device__ __forceinline__ void st_px(uint8_t* o, int c, float v, const SrFmt& f) {    // (v * max_range).round() -> u8 / u16
+  const float q = rintf(v * f.range);
+  if (f.wide) reinterpret_cast<uint16_t*>(o)[c] = (uint16_t)q;
+  else o[c] = (uint8_t)q;
+}
+
 // SHUF = 1: one thread per input pixel, 3 channels. SHUF = 2: pixel_unshuffle(2): 12 channels c*4 + dy*2 + dx.
 template <typename T, int SHUF, int CPAD>
 __global__ void sr_pre_kernel(const uint8_t* __restrict__ base, const SrSrc* __restrict__ srcs, const int4* __restrict__ tab,
@@ -39,14 +51,18 @@ __global__ void sr_pre_kernel(const uint8_t* __restrict__ base, const SrSrc* __r
   const int y = lp / t.z, x = lp - y * t.z;
   T* op = out + (size_t)gp * CPAD;
   const uint8_t* img = base + s.src_off;
+  const SrFmt f = s.fmt;
 #pragma unroll
   for (int dy = 0; dy < SHUF; ++dy)
 #pragma unroll
     for (int dx = 0; dx < SHUF; ++dx) {
       const int sy = reflect2(s.y0 + y * SHUF + dy, s.pre_h, s.src_h), sx = reflect2(s.x0 + x * SHUF + dx, s.pre_w, s.src_w);
-      const uint8_t* p = img + (size_t)sy * s.src_stride + (size_t)sx * 3;
-      // source is BGR; network channel order is RGB
-      const float r = (float)p[2] / 255.0f, g = (float)p[1] / 255.0f, b = (float)p[0] / 255.0f;
+      const uint8_t* p = img + (size_t)sy * s.src_stride + (size_t)sx * f.px_bytes();
+      // network channel order is RGB; the source is BGR (or one channel replicated: GRAY2RGB of the gray / alpha plane)
+      float r, g, b;
+      if (f.sel == SR_SEL_BGR) { r = ld_px(p, 2, f.wide); g = ld_px(p, 1, f.wide); b = ld_px(p, 0, f.wide); }
+      else r = g = b = ld_px(p, f.sel == SR_SEL_GRAY ? 0 : 3, f.wide);
+      r = r / f.range; g = g / f.range; b = b / f.range;
       if (SHUF == 1) { op[0] = (T)r; op[1] = (T)g; op[2] = (T)b; }
       else {
         const int k = dy * SHUF + dx;
@@ -71,11 +87,14 @@ __global__ void sr_post_kernel(const float* __restrict__ net_out, int cs, const 
   if (lp >= d.cw * d.ch) return;              // padding entry (capacity-mode batch) or empty core
   const int y = lp / d.cw, x = lp - y * d.cw;
   const float* p = net_out + ((size_t)t.x + (size_t)(d.ty + y) * t.z + (d.tx + x)) * cs;
-  uint8_t* o = base + d.dst_off + (size_t)(d.oy + y) * d.dst_stride + (size_t)(d.ox + x) * 3;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    float v = fminf(fmaxf(p[2 - c], 0.f), 1.f);       // RGB -> BGR
-    o[c] = (uint8_t)rintf(v * 255.0f);
+  const SrFmt f = d.fmt;
+  uint8_t* o = base + d.dst_off + (size_t)(d.oy + y) * d.dst_stride + (size_t)(d.ox + x) * f.px_bytes();
+  const float B = fminf(fmaxf(p[2], 0.f), 1.f), G = fminf(fmaxf(p[1], 0.f), 1.f), R = fminf(fmaxf(p[0], 0.f), 1.f);   // RGB -> BGR
+  if (f.sel == SR_SEL_BGR) {
+    st_px(o, 0, B, f); st_px(o, 1, G, f); st_px(o, 2, R, f);
+  } else {                                    // cv2 BGR2GRAY (float32), into channel 0 (mode 'L') or 3 (the alpha plane)
+    const float Y = B * 0.114f + G * 0.587f + R * 0.299f;
+    st_px(o, f.sel == SR_SEL_GRAY ? 0 : 3, Y, f);
   }
 }
 

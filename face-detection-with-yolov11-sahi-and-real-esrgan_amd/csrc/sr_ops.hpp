@@ -4,12 +4,28 @@
 
 namespace ffp {
 
+// Pixel format of an image the SR path reads or writes (realesrgan 0.3.0 RealESRGANer.enhance, reference call
+// utils/enhancer.py:214). The default is today's 3-channel uint8 BGR.
+enum SrSel : int {
+  SR_SEL_BGR = 0,        // read: BGR from channels 0-2 (3- or 4-channel pixel); write: BGR into channels 0-2
+  SR_SEL_GRAY = 1,       // read: channel 0 replicated to RGB (mode 'L'); write: BGR2GRAY into channel 0 (1-channel canvas)
+  SR_SEL_ALPHA = 2,      // read: channel 3 replicated to RGB (mode 'RGBA'); write: BGR2GRAY into channel 3 (4-channel canvas)
+};
+struct SrFmt {
+  int cn = 3;            // channels per pixel (1, 3, 4)
+  int wide = 0;          // 0: 8-bit storage, 1: 16-bit storage
+  float range = 255.f;   // max_range: value = stored / range on read, rint(value * range) on write
+  int sel = SR_SEL_BGR;
+  __host__ __device__ int px_bytes() const { return cn << wide; }
+};
+
 struct SrSrc {          // where one network tile reads its pixels
   long long src_off;    // byte offset of the source image inside the base allocation
   int src_stride;       // bytes per source row
   int src_h, src_w;     // source size
   int pre_h, pre_w;     // size after pre_pad; rows beyond reflect about it first (mod pad), then about the source
   int x0, y0;           // tile origin in padded-source coordinates
+  SrFmt fmt;
 };
 struct SrDst {          // where the core of one tile's output lands
   long long dst_off;    // byte offset of the output canvas inside the base allocation
@@ -17,11 +33,30 @@ struct SrDst {          // where the core of one tile's output lands
   int ox, oy;           // core origin in the canvas
   int cw, ch;           // core size (output pixels)
   int tx, ty;           // core origin inside the tile's network output
+  SrFmt fmt;
 };
 
 void launch_sr_pre(const uint8_t* d_base, const SrSrc* d_srcs, const TView& out, int shuf, hipStream_t st);
 void launch_sr_post(const TView& net_out, const SrDst* d_dsts, const long long* d_core_off, long long total_core, uint8_t* d_base,
                     hipStream_t st);
+// realesrgan's post-resizes (resize.hip). The Lanczos4 tables are built on the host (libm sin / cos in double) and read as is.
+struct Lanczos4Axis {           // one axis of cv::resize(INTER_LANCZOS4): first tap sx - 3 and 8 weights per output index
+  std::vector<int> ofs;         // sx (taps sx-3 .. sx+4, clamped to [0, n_in - 1] by the kernel)
+  std::vector<float> coef;      // 8 per output index (16-bit path)
+  std::vector<int16_t> icoef;   // rint(coef * 2048) (8-bit path)
+};
+Lanczos4Axis lanczos4_axis(int n_in, int n_out);
+// src: h x w x cn (u8 or u16), dst: out_h x out_w x cn. The table (lanczos4_pack) holds xofs[out_w], yofs[out_h] as int, then
+// 8 coefficients per output column and per output row: float for 16-bit (wide) data, int16 for 8-bit data.
+size_t lanczos4_table_bytes(int out_h, int out_w);
+void lanczos4_pack(const Lanczos4Axis& ax, const Lanczos4Axis& ay, int wide, void* host_tab);
+void launch_resize_lanczos4(const void* d_src, int h, int w, int cn, int wide, const void* d_tab, int out_h, int out_w, void* d_dst,
+                            hipStream_t st);
+// the 'cv2' alpha upsampler: cv2.resize(alpha / range, (out_w, out_h), INTER_LINEAR) in float32, quantised to rint(a * range)
+// into channel 3 of a 4-channel canvas of 8-bit (dst_wide 0) or 16-bit elements; src is the 4-channel input
+void launch_alpha_linear(const void* d_src, int h, int w, int src_wide, float range, int out_h, int out_w, void* d_dst, int dst_wide,
+                         hipStream_t st);
+
 void launch_crop_gather(const uint8_t* d_frame, int W, const int4* d_boxes, const long long* d_offs, int n, uint8_t* d_out,
                         hipStream_t st);
 
@@ -43,6 +78,7 @@ struct SrPlan : Plan {
 struct SrImage {           // one image of a batch: offsets are relative to the in/out base allocations
   long long in_off; int in_stride; int h, w;
   long long out_off; int out_stride;
+  SrFmt in_fmt, out_fmt;   // strides are in bytes; two images may share a buffer and differ in their channel selection
 };
 
 class SrEngine {
@@ -52,7 +88,7 @@ class SrEngine {
   int scale() const { return scale_; }
   int device() const { return device_; }
   hipStream_t stream() const { return st_; }
-  // all images live in device memory: inputs at d_in + in_off (BGR u8, in_stride bytes/row), outputs at d_out + out_off
+  // all images live in device memory: inputs at d_in + in_off (in_fmt, in_stride bytes/row), outputs at d_out + out_off (out_fmt)
   // wait = false: return as soon as the work is enqueued on the engine's stream (wait_done() completes it), so that the
   // caller can overlap the next frame's detection (own stream) with this frame's super-resolution
   void enhance_dev(const uint8_t* d_in, uint8_t* d_out, const std::vector<SrImage>& imgs, int tile, int tile_pad, int pre_pad, bool wait = true);
@@ -66,7 +102,7 @@ class SrEngine {
   size_t weight_bytes() const { return weight_bytes_; }
   int plans_resident() const { return (int)plans_.size(); }
 
-  DevBuf scratch_in, scratch_out, scratch_boxes, scratch_offs;
+  DevBuf scratch_in, scratch_out, scratch_boxes, scratch_offs, scratch_tab;
   HostPinned crop_stage;
   ConvProfile prof;
   float last_ms = 0.f;

@@ -172,6 +172,22 @@ int ffp_sr_enhance(ffp_sr* s, const uint8_t* bgr_hwc, int h, int w, int tile, in
  * whole picture, utils/enhancer.py:189-235, then get_sliced_prediction on the result) without a host round trip. */
 int ffp_sr_enhance_dev(ffp_sr* s, const uint8_t* d_bgr_hwc, int h, int w, int tile, int tile_pad, int pre_pad, uint8_t* d_out_bgr);
 
+/* RealESRGANer.enhance(img, outscale, alpha_upsampler) of realesrgan 0.3.0 for every layout it accepts (reference call
+ * utils/enhancer.py:214; the layout rules are the caller's, compat/utils/enhancer.py::enhance_layout):
+ *   img: h x w x channels, 8-bit (bits 8) or 16-bit (bits 16) elements. channels 1 = mode 'L' (gray replicated to RGB,
+ *        result BGR2GRAY), 3 = BGR, 4 = BGRA (mode 'RGBA': BGR through the network, alpha by alpha_mode).
+ *   max_range: 255 or 65535 (the caller's `np.max(img) > 256` rule; 65535 needs bits 16). Pixels are divided by it, the
+ *        result is rint(v * max_range); output elements are uint16 exactly when max_range == 65535, else uint8.
+ *   alpha_mode (channels 4): FFP_SR_ALPHA_REALESRGAN = the alpha plane replicated to RGB through the network in the same
+ *        batch as the colour image, result BGR2GRAY; FFP_SR_ALPHA_LINEAR = cv2.resize(alpha, INTER_LINEAR) in float32.
+ *   out_h x out_w: (scale*h) x (scale*w), or any other size for cv2.resize(..., INTER_LANCZOS4) of the result (outscale).
+ *   out: out_h x out_w x channels. Any other combination (channels 2, bits 8 with max_range 65535, a size of 0, ...) is
+ *   FFP_ERR_ARG before anything is launched. */
+#define FFP_SR_ALPHA_REALESRGAN 0
+#define FFP_SR_ALPHA_LINEAR 1
+int ffp_sr_enhance_ex(ffp_sr* s, const void* img, int h, int w, int channels, int bits, int max_range, int alpha_mode, int out_h,
+                      int out_w, int tile, int tile_pad, int pre_pad, void* out);
+
 /* n independent images in one ragged batch (one launch per layer for all of them). */
 int ffp_sr_enhance_batch(ffp_sr* s, int n, const uint8_t* const* imgs, const int32_t* hs, const int32_t* ws, int tile,
                          int tile_pad, int pre_pad, uint8_t* const* outs);
@@ -233,6 +249,12 @@ int ffp_det_stream_wait_event(ffp_det* d, void* hip_event);
 /* ---------------------------------------------------------------------------------------------------------
  * single-operator entry points (layer-wise parity tests; host NHWC fp32 in/out, computed on `device` in `precision`)
  * ------------------------------------------------------------------------------------------------------- */
+
+/* cv2.resize(src, (out_w, out_h), interpolation=INTER_LANCZOS4) — the outscale step of RealESRGANer.enhance (reference call
+ * utils/enhancer.py:214) alone. src: h x w x channels (1, 3, 4), bits 8 (uint8) or 16 (uint16); dst: out_h x out_w x channels
+ * of the same type. Same size is a copy. 8-bit: int16 weights (x2048), int32 sums, (v + 2^21) >> 22 saturated; 16-bit: float
+ * weights, float sums, rint saturated. Weight tables are built on the host (sin / cos in double). */
+int ffp_op_resize_lanczos4(int device, const void* src, int h, int w, int channels, int bits, int out_h, int out_w, void* dst);
 
 /* y = act(conv2d(x, w) + b) [* s1 + res]; x: [n][h][w][cin] fp32 NHWC; w: OIHW fp32 (groups: 1 or cin==cout
  * depthwise); k in {1,3}; stride in {1,2}; pad = k/2; act: 0 none, 1 SiLU, 2 LeakyReLU(0.2); up: nearest x2 of x

@@ -1,0 +1,226 @@
+"""GPU parity of RealESRGANer.enhance's extra layouts (gray, BGRA under both alpha upsamplers, 16-bit, outscale) against
+the CPU oracle in tests/realesrgan_formats_ref.py (realesrgan 0.3.0; reference call utils/enhancer.py:214).
+Bars are tests/test_gpu_sr.py's: fp32 |diff| <= 1 LSB and >= 55 dB, fp16 >= 50 dB; 16-bit results are compared after
+dividing by 257. The 'cv2' alpha and the Lanczos4 outscale do not depend on the network and are compared exactly."""
+import numpy as np
+import pytest
+
+import realesrgan_formats_ref as R
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def W4(gpu_lib):
+    from ffp_amd import synth
+    return synth.rrdbnet_weights(4, 23)
+
+
+@pytest.fixture(scope="module")
+def ref4(W4):
+    from oracle.rrdbnet_ref import RRDBNetRef
+    return RRDBNetRef(W4, 4, 23)
+
+
+@pytest.fixture(scope="module")
+def uppers(W4):
+    from ffp_amd.compat.utils.enhancer import RealESRGANer, RRDBNet
+    return {half: RealESRGANer(scale=4, model_path=W4, model=RRDBNet(scale=4, num_block=23), tile=0, half=half, gpu_id=0)
+            for half in (False, True)}
+
+
+def bgr(seed, h, w):
+    from ffp_amd import synth
+    return synth.synthetic_frame(max(h, 64), max(w, 64), seed=seed, n_blobs=6)[:h, :w][..., ::-1].copy()
+
+
+def make(kind, seed, h, w):
+    """Test images: 'gray', 'bgr', 'bgra' in 8 bits; 'gray16', 'bgr16', 'bgra16' in 16 bits (maximum > 256)."""
+    im = bgr(seed, h, w)
+    yy, xx = np.mgrid[0:h, 0:w]
+    alpha = np.clip(128 + 120 * np.sin(xx / 3.1 + seed) * np.cos(yy / 4.3), 0, 255).astype(np.uint8)
+    base = {"gray": im[..., 1], "bgr": im, "bgra": np.dstack([im, alpha])}[kind.rstrip("16")]
+    if kind.endswith("16"):
+        noise = np.random.default_rng(seed).integers(0, 257, base.shape)
+        return (base.astype(np.int64) * 256 + noise).clip(0, 65535).astype(np.uint16)
+    return np.ascontiguousarray(base)
+
+
+_oracle_cache = {}
+
+
+def oracle(ref, kind, seed, h, w, alpha="realesrgan", **kw):
+    key = (id(ref), kind, seed, h, w, alpha, tuple(sorted(kw.items())))
+    if key not in _oracle_cache:
+        _oracle_cache[key] = R.enhance(ref, make(kind, seed, h, w), None, alpha, **kw)
+    return _oracle_cache[key]
+
+
+def psnr(a, b, peak):
+    mse = np.mean((a.astype(np.float64) - b.astype(np.float64)) ** 2)
+    return 99.0 if mse == 0 else 10 * np.log10(peak ** 2 / mse)
+
+
+def assert_close(out, ref, half, planes=None):
+    """u8: the test_gpu_sr bars; u16: the same bars on value / 257."""
+    assert out.dtype == ref.dtype and out.shape == ref.shape, (out.dtype, out.shape, ref.dtype, ref.shape)
+    a, b = out.astype(np.float64), ref.astype(np.float64)
+    if planes is not None:
+        a, b = a[..., planes], b[..., planes]
+    if out.dtype == np.uint16:
+        a, b = a / 257.0, b / 257.0
+    p = psnr(a, b, 255.0)
+    if half:
+        assert p >= 50.0, p
+    else:
+        d = np.abs(a - b).max()
+        assert p >= 55.0 and d <= 1.0, (p, d)
+
+
+CASES = [("gray", "realesrgan"), ("bgra", "realesrgan"), ("bgra", "cv2"), ("bgr16", "realesrgan"), ("gray16", "realesrgan"),
+         ("bgra16", "realesrgan"), ("bgra16", "cv2")]
+
+
+@pytest.mark.parametrize("half", [False, True], ids=["f32", "f16"])
+@pytest.mark.parametrize("kind,alpha", CASES, ids=[f"{k}-{a}" for k, a in CASES])
+def test_layout_matches_oracle(uppers, ref4, half, kind, alpha):
+    h, w = 22, 27
+    img = make(kind, 7, h, w)
+    want, mode = oracle(ref4, kind, 7, h, w, alpha)
+    got, gmode = uppers[half].enhance(img, outscale=None, alpha_upsampler=alpha)
+    assert gmode == mode == {"gray": "L", "bgr": "RGB", "bgra": "RGBA"}[kind.rstrip("16")]
+    assert got.dtype == (np.uint16 if kind.endswith("16") else np.uint8)
+    assert got.shape == want.shape == ((4 * h, 4 * w) if mode == "L" else (4 * h, 4 * w, img.shape[2]))
+    if mode == "RGBA" and alpha == "cv2":
+        assert np.abs(got[..., 3].astype(int) - want[..., 3].astype(int)).max() <= 1    # does not depend on the network
+        assert_close(got, want, half, planes=slice(0, 3))
+    else:
+        assert_close(got, want, half)
+
+
+@pytest.mark.parametrize("kind", ["bgra", "bgra16"])
+@pytest.mark.parametrize("alpha", ["realesrgan", "cv2"])
+def test_bgra_colour_planes_equal_the_3_channel_call(uppers, kind, alpha):
+    img = make(kind, 11, 19, 23)
+    assert img[..., :3].max() > 256 or img.dtype == np.uint8               # both calls take the same max_range
+    up = uppers[True]
+    four, _ = up.enhance(img, alpha_upsampler=alpha)
+    three, _ = up.enhance(np.ascontiguousarray(img[..., :3]))
+    assert np.array_equal(four[..., :3], three)
+
+
+def test_16bit_with_small_maximum_takes_the_8bit_path(uppers, ref4):
+    img = make("bgr", 3, 17, 21).astype(np.uint16)
+    img[0, 0, 0] = 256
+    got, mode = uppers[False].enhance(img)
+    want, _ = R.enhance(ref4, img)
+    assert mode == "RGB" and got.dtype == want.dtype == np.uint8
+    assert_close(got, want, False)
+
+
+@pytest.mark.parametrize("kind", ["gray", "bgr", "bgra", "bgr16", "bgra16"])
+@pytest.mark.parametrize("hw,outscale", [((20, 26), 2), ((20, 26), 3.5), ((13, 9), 5), ((1, 11), 3.5), ((9, 1), 2), ((12, 16), 1.37)])
+def test_outscale_is_lanczos4_of_the_own_output(uppers, kind, hw, outscale):
+    h, w = hw
+    img = make(kind, h * 31 + w, h, w)
+    up = uppers[True]
+    base, mode = up.enhance(img)
+    got, gmode = up.enhance(img, outscale=outscale)
+    want = R.resize_lanczos4(base, int(w * outscale), int(h * outscale))
+    assert gmode == mode and got.shape == want.shape and got.dtype == want.dtype
+    if got.dtype == np.uint8:
+        assert np.array_equal(got, want)
+    else:
+        assert np.abs(got.astype(int) - want.astype(int)).max() <= 1
+
+
+@pytest.mark.parametrize("dtype", [np.uint8, np.uint16])
+@pytest.mark.parametrize("cn", [1, 3, 4])
+@pytest.mark.parametrize("src,dst", [((40, 52), (140, 182)), ((64, 48), (21, 30)), ((1, 17), (3, 40)), ((23, 1), (7, 5)),
+                                     ((30, 30), (30, 31)), ((16, 16), (16, 16))])
+def test_op_resize_lanczos4(gpu_lib, dtype, cn, src, dst):
+    rng = np.random.default_rng(src[0] * 1000 + dst[1] + cn)
+    shape = src if cn == 1 else src + (cn,)
+    img = rng.integers(0, np.iinfo(dtype).max, shape, endpoint=True).astype(dtype)
+    got = gpu_lib.op_resize_lanczos4(img, dst[0], dst[1])
+    want = R.resize_lanczos4(img, dst[1], dst[0])
+    assert got.shape == want.shape and got.dtype == dtype
+    if dtype == np.uint8:
+        assert np.array_equal(got, want)
+    else:
+        assert np.abs(got.astype(int) - want.astype(int)).max() <= 1
+
+
+@pytest.mark.parametrize("kind,alpha", [("gray", "realesrgan"), ("bgra", "realesrgan"), ("bgra16", "cv2")])
+def test_tiled_and_pre_pad(W4, ref4, kind, alpha):
+    from ffp_amd.compat.utils.enhancer import RealESRGANer, RRDBNet
+    up = RealESRGANer(scale=4, model_path=W4, model=RRDBNet(scale=4, num_block=23), tile=40, tile_pad=10, pre_pad=3, half=False, gpu_id=0)
+    h, w = 47, 52
+    img = make(kind, 5, h, w)
+    got, mode = up.enhance(img, alpha_upsampler=alpha)
+    want, wmode = R.enhance(ref4, img, None, alpha, tile=40, tile_pad=10, pre_pad=3)
+    assert mode == wmode
+    assert_close(got, want, False)
+
+
+@pytest.mark.parametrize("kind", ["gray", "bgra", "gray16"])
+def test_x2_model_odd_sizes(gpu_lib, kind):
+    from ffp_amd import synth
+    from ffp_amd.compat.utils.enhancer import RealESRGANer, RRDBNet
+    from oracle.rrdbnet_ref import RRDBNetRef
+    W2 = synth.rrdbnet_weights(2, 23)
+    ref2 = RRDBNetRef(W2, 2, 23)
+    up = RealESRGANer(scale=2, model_path=W2, model=RRDBNet(scale=2, num_block=23), tile=0, pre_pad=1, half=False, gpu_id=0)
+    for (h, w) in [(31, 45), (17, 20)]:
+        img = make(kind, h + w, h, w)
+        got, mode = up.enhance(img)
+        want, wmode = R.enhance(ref2, img, pre_pad=1)
+        assert mode == wmode and got.shape[:2] == (2 * h, 2 * w)
+        assert_close(got, want, False)
+        got35, _ = up.enhance(img, outscale=3.5)
+        want35 = R.resize_lanczos4(got, int(w * 3.5), int(h * 3.5))
+        assert np.abs(got35.astype(int) - want35.astype(int)).max() <= (1 if got.dtype == np.uint16 else 0)
+
+
+@pytest.mark.parametrize("half", [False, True], ids=["f32", "f16"])
+def test_enhance_ex_bgr_u8_equals_enhance(gpu_lib, W4, half):
+    e = gpu_lib.Enhancer(W4, 4, 23, half=half)
+    for (h, w) in [(24, 37), (50, 41)]:
+        img = bgr(h * 7 + w, h, w)
+        assert np.array_equal(e.enhance_ex(img), e.enhance(img))
+        assert np.array_equal(e.enhance_ex(img, tile=20, tile_pad=6, pre_pad=2), e.enhance(img, 20, 6, 2))
+
+
+def test_enhance_ex_rejects_bad_arguments(gpu_lib, W4):
+    from ffp_amd import _lib
+    e = gpu_lib.Enhancer(W4, 4, 23, half=True)
+    l = _lib.lib()
+    img8 = np.zeros((8, 8, 3), np.uint8)
+    out = np.zeros((64, 64, 4), np.uint16)
+    bad = [(3, 8, 65535, 0, 32, 32), (2, 8, 255, 0, 32, 32), (5, 8, 255, 0, 32, 32), (3, 12, 255, 0, 32, 32), (3, 8, 1000, 0, 32, 32),
+           (4, 8, 255, 7, 32, 32), (3, 8, 255, 0, 0, 32), (3, 8, 255, 0, 32, -1)]
+    for (cn, bits, rng, am, oh, ow) in bad:
+        assert l.ffp_sr_enhance_ex(e.handle, img8.ctypes.data, 8, 8, cn, bits, rng, am, oh, ow, 0, 10, 0, out.ctypes.data) == 1
+    assert l.ffp_sr_enhance_ex(e.handle, img8.ctypes.data, 0, 8, 3, 8, 255, 0, 32, 32, 0, 10, 0, out.ctypes.data) == 1
+    assert l.ffp_op_resize_lanczos4(0, img8.ctypes.data, 8, 8, 2, 8, 4, 4, out.ctypes.data) == 1
+    assert l.ffp_op_resize_lanczos4(0, img8.ctypes.data, 8, 8, 3, 32, 4, 4, out.ctypes.data) == 1
+    assert l.ffp_op_resize_lanczos4(0, img8.ctypes.data, 8, 8, 3, 8, 0, 4, out.ctypes.data) == 1
+    assert np.array_equal(e.enhance_ex(img8), e.enhance(img8))        # the handle still works
+
+
+def test_wrapper_rejections_and_types(uppers):
+    up = uppers[True]
+    with pytest.raises(ValueError):
+        up.enhance(np.zeros((8, 8, 3), np.float32))
+    with pytest.raises(ValueError):
+        up.enhance(np.zeros((8, 8, 2), np.uint8))
+    with pytest.raises(ValueError):
+        up.enhance(np.zeros((8, 8, 3), np.uint8), outscale=0.05)
+    a = np.zeros((8, 8, 4), np.uint16)
+    a[0, 0, 3] = 256
+    with pytest.raises(ValueError):
+        up.enhance(a, alpha_upsampler="cv2")
+    out, mode = up.enhance(a)                                            # the network alpha is clamped: defined
+    assert mode == "RGBA" and out.dtype == np.uint8 and out.shape == (32, 32, 4)
+    out, mode = up.enhance(np.zeros((5, 6), np.uint8))
+    assert mode == "L" and out.shape == (20, 24) and out.dtype == np.uint8
