@@ -109,6 +109,9 @@ _SIGS = {
     "ffp_eval_wider_pr": (C.c_int, [C.c_int, _p(C.c_double), _p(C.c_int64), _p(C.c_double), _p(C.c_int64), _p(C.c_uint8), C.c_int, C.c_double, C.c_int,
                                     _p(C.c_int64)]),
     "ffp_eval_dual_match": (C.c_int, [C.c_int, _p(C.c_double), _p(C.c_int64), _p(C.c_double), _p(C.c_int64), _p(C.c_uint8), C.c_int, C.c_double, _p(C.c_int32)]),
+    "ffp_eval_coco_bbox": (C.c_int, [C.c_int, C.c_int, C.c_int, _p(C.c_double), _p(C.c_int64), _p(C.c_double), _p(C.c_int64), _p(C.c_double), C.c_int,
+                                     _p(C.c_double), C.c_int, _p(C.c_double), C.c_int, _p(C.c_int32), C.c_int, _p(C.c_double), _p(C.c_double),
+                                     _p(C.c_double), _p(C.c_double), _p(C.c_uint8), _p(C.c_double), _p(C.c_uint8)]),
     "ffp_jpeg_encode": (C.c_int, [C.c_int, _p(C.c_uint8), C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_uint8), C.c_int64, _p(C.c_int64)]),
     "ffp_jpeg_encode_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _p(C.c_uint8), C.c_int64, _p(C.c_int64)]),
     "ffp_jpeg_encode_batch_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, _p(C.c_int64), _p(C.c_int32), _p(C.c_int32), _p(C.c_int64), C.c_int, C.c_int, _p(C.c_uint8),
@@ -631,6 +634,43 @@ def eval_dual_match(preds, faces, valid, iou_thr: float = 0.5, device: int = 0):
     _check(lib().ffp_eval_dual_match(device, p.ctypes.data_as(_p(C.c_double)), po.ctypes.data_as(_p(C.c_int64)), f.ctypes.data_as(_p(C.c_double)),
                                      fo.ctypes.data_as(_p(C.c_int64)), v.ctypes.data_as(_p(C.c_uint8)), len(po) - 1, iou_thr, flags.ctypes.data_as(_p(C.c_int32))))
     return [flags[po[i]:po[i + 1]] for i in range(len(po) - 1)]
+
+
+def eval_coco_bbox(dets, det_off, gts, gt_off, n_img: int, n_cat: int, iou_thrs, rec_thrs, area_rng, max_dets, matches: bool = False,
+                   device: int = 0) -> dict:
+    """pycocotools COCOeval (bbox) evaluate + accumulate on the device (ffp_eval_coco_bbox). dets [sum D][7] = x, y, w, h, score, area, id and
+    gts [sum G][8] = x, y, w, h, area, iscrowd, ignore, id, ragged per unit by the int64 offsets det_off / gt_off [n_cat * n_img + 1]
+    (category-major, images in sorted id order). -> dict of numpy arrays: precision / scores [T,R,K,A,M], recall [T,K,A,M] and, with
+    matches=True, dt_matches / dt_ignore [A,T,ndc], gt_matches [A,T,ng], gt_ignore [A,ng] plus cut_off [U+1] (see include/ffp.h)."""
+    d = np.ascontiguousarray(np.asarray(dets, np.float64).reshape(-1, 7))
+    g = np.ascontiguousarray(np.asarray(gts, np.float64).reshape(-1, 8))
+    do = np.ascontiguousarray(det_off, np.int64)
+    go = np.ascontiguousarray(gt_off, np.int64)
+    it = np.ascontiguousarray(iou_thrs, np.float64).reshape(-1)
+    rt = np.ascontiguousarray(rec_thrs, np.float64).reshape(-1)
+    ar = np.ascontiguousarray(area_rng, np.float64).reshape(-1, 2)
+    md = np.ascontiguousarray(max_dets, np.int32).reshape(-1)
+    U = int(n_img) * int(n_cat)
+    if len(do) != U + 1 or len(go) != U + 1:
+        raise ValueError(f"offsets must have n_cat * n_img + 1 = {U + 1} entries")
+    T, R, K, A, M = len(it), len(rt), int(n_cat), len(ar), len(md)
+    prec, sc = np.zeros((T, R, K, A, M)), np.zeros((T, R, K, A, M))
+    rec = np.zeros((T, K, A, M))
+    out = {"precision": prec, "recall": rec, "scores": sc}
+    ptrs = [None] * 4
+    if matches:
+        cut = np.zeros(U + 1, np.int64)
+        if U and len(md):
+            np.cumsum(np.minimum(np.diff(do), int(md[-1])), out=cut[1:])
+        ndc, ng = int(cut[-1]), int(go[-1]) if U else 0
+        out.update(cut_off=cut, dt_matches=np.zeros((A, T, ndc)), dt_ignore=np.zeros((A, T, ndc), np.uint8), gt_matches=np.zeros((A, T, ng)),
+                   gt_ignore=np.zeros((A, ng), np.uint8))
+        ptrs = [out["dt_matches"].ctypes.data_as(_p(C.c_double)), out["dt_ignore"].ctypes.data_as(_p(C.c_uint8)),
+                out["gt_matches"].ctypes.data_as(_p(C.c_double)), out["gt_ignore"].ctypes.data_as(_p(C.c_uint8))]
+    dp = lambda a: a.ctypes.data_as(_p(C.c_double))
+    _check(lib().ffp_eval_coco_bbox(device, int(n_img), int(n_cat), dp(d), do.ctypes.data_as(_p(C.c_int64)), dp(g), go.ctypes.data_as(_p(C.c_int64)),
+                                    dp(it), T, dp(rt), R, dp(ar), A, md.ctypes.data_as(_p(C.c_int32)), M, dp(prec), dp(rec), dp(sc), *ptrs))
+    return out
 
 
 def op_conv1x1_up2(coarse: np.ndarray, fine: np.ndarray, w: np.ndarray, b: np.ndarray, act: int = 0, precision: int = PREC_F32X3, device: int = 0) -> np.ndarray:

@@ -1,8 +1,10 @@
 // api.cpp — the C-ABI of libffp.so (include/ffp.h). Every entry point catches engine exceptions, stores a
 // thread-local message and returns an error code; nothing here computes on the CPU.
 #include <algorithm>
+#include <climits>
 #include <cmath>
 
+#include "coco_eval.hpp"
 #include "eval.hpp"
 #include "jpeg.hpp"
 #include "sr_ops.hpp"
@@ -665,6 +667,72 @@ int ffp_eval_dual_match(int device, const double* preds, const int64_t* pred_off
                       flags.as<int>(), st);
     FFP_HIP(hipStreamSynchronize(st));
     if (np) FFP_HIP(hipMemcpy(out_flags, flags.p, sizeof(int32_t) * (size_t)np, hipMemcpyDeviceToHost));
+  } catch (...) {
+    (void)hipStreamDestroy(st);
+    throw;
+  }
+  (void)hipStreamDestroy(st);
+  FFP_API_END
+}
+
+// ---- COCO bbox evaluation (pycocotools COCOeval.evaluate + accumulate) ----------------------------------------------------------
+int ffp_eval_coco_bbox(int device, int n_img, int n_cat, const double* dets, const int64_t* det_off, const double* gts, const int64_t* gt_off,
+                       const double* iou_thrs, int n_iou, const double* rec_thrs, int n_rec, const double* area_rng, int n_area,
+                       const int32_t* max_dets, int n_max_dets, double* precision, double* recall, double* scores, double* dt_matches,
+                       uint8_t* dt_ignore, double* gt_matches, uint8_t* gt_ignore) {
+  FFP_API_BEGIN
+  FFP_CHECK(n_img >= 0 && n_cat >= 0 && n_iou > 0 && n_rec > 0 && n_area > 0 && n_max_dets > 0, FFP_ERR_ARG, "eval_coco_bbox: bad sizes");
+  FFP_CHECK(iou_thrs && rec_thrs && area_rng && max_dets && precision && recall && scores, FFP_ERR_ARG, "eval_coco_bbox: null parameter or output");
+  const long long U = (long long)n_img * n_cat;
+  FFP_CHECK(U <= INT_MAX && U * n_area * n_iou <= INT_MAX && (long long)n_cat * n_area * n_max_dets * n_iou <= INT_MAX, FFP_ERR_ARG,
+            "eval_coco_bbox: %lld units x %d areas x %d thresholds is too large", U, n_area, n_iou);
+  for (int m = 0; m < n_max_dets; ++m)
+    FFP_CHECK(max_dets[m] >= 0 && (m == 0 || max_dets[m] >= max_dets[m - 1]), FFP_ERR_ARG, "eval_coco_bbox: maxDets must be ascending and >= 0");
+  int ndev = 0;
+  FFP_CHECK(hipGetDeviceCount(&ndev) == hipSuccess && device >= 0 && device < ndev, FFP_ERR_HIP, "eval_coco_bbox: no HIP device %d (no CPU path)", device);
+  FFP_HIP(hipSetDevice(device));
+  check_offsets(det_off, (int)U, "detection");
+  check_offsets(gt_off, (int)U, "ground-truth");
+  const int64_t nd = det_off[U], ng = gt_off[U];
+  FFP_CHECK((nd == 0 || dets) && (ng == 0 || gts), FFP_ERR_ARG, "eval_coco_bbox: null data");
+  std::vector<int64_t> cut_off((size_t)U + 1, 0);
+  const int64_t max_det = max_dets[n_max_dets - 1];
+  for (long long u = 0; u < U; ++u) {
+    FFP_CHECK(det_off[u + 1] - det_off[u] <= INT_MAX && gt_off[u + 1] - gt_off[u] <= INT_MAX, FFP_ERR_ARG, "eval_coco_bbox: unit %lld is too large", u);
+    cut_off[u + 1] = cut_off[u] + std::min<int64_t>(det_off[u + 1] - det_off[u], max_det);
+  }
+  const int64_t ndc = cut_off[U];
+  FFP_CHECK(ndc <= (1LL << 30), FFP_ERR_ARG, "eval_coco_bbox: %lld detections after the maxDets cut is too many", (long long)ndc);
+  for (int64_t i = 0; i < nd; ++i)   // loadRes numbers dets from 1: a GT is taken when gtMatches > 0, so every id must be positive
+    FFP_CHECK(!std::isnan(dets[i * 7 + 4]) && dets[i * 7 + 6] > 0, FFP_ERR_ARG, "eval_coco_bbox: detection %lld has a NaN score or an id <= 0", (long long)i);
+  for (int64_t g = 0; g < ng; ++g)   // _prepare sets ignore = iscrowd: a crowd GT is always ignored (at most one TP per kept GT)
+    FFP_CHECK(gts[g * 8 + 5] == 0 || gts[g * 8 + 6] != 0, FFP_ERR_ARG, "eval_coco_bbox: ground truth %lld is a crowd but not ignored", (long long)g);
+  const int T = n_iou, R = n_rec, A = n_area, M = n_max_dets, K = n_cat;
+  const size_t n_pr = (size_t)T * R * K * A * M, n_rc = (size_t)T * K * A * M;
+  hipStream_t st;
+  FFP_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  try {
+    DevBuf dd = upload(dets, (size_t)nd * 7), ddo = upload(det_off, (size_t)U + 1), dg = upload(gts, (size_t)ng * 8), dgo = upload(gt_off, (size_t)U + 1),
+           dco = upload(cut_off.data(), cut_off.size()), dit = upload(iou_thrs, (size_t)T), drt = upload(rec_thrs, (size_t)R),
+           dar = upload(area_rng, (size_t)A * 2), dmd = upload(max_dets, (size_t)M);
+    DevBuf dprec(sizeof(double) * std::max<size_t>(n_pr, 1)), drec(sizeof(double) * std::max<size_t>(n_rc, 1)), dsc(sizeof(double) * std::max<size_t>(n_pr, 1)),
+           ddtm(sizeof(double) * (size_t)A * T * std::max<int64_t>(ndc, 1)), ddig((size_t)A * T * std::max<int64_t>(ndc, 1)),
+           dgtm(sizeof(double) * (size_t)A * T * std::max<int64_t>(ng, 1)), dgig((size_t)A * std::max<int64_t>(ng, 1)),
+           scratch(coco_eval_scratch_bytes(ndc, ng, A, M, T));
+    CocoEvalArgs a{n_img, n_cat, T, R, A, M, dd.as<double>(), dg.as<double>(), ddo.as<long long>(), dgo.as<long long>(), dco.as<long long>(),
+                   dit.as<double>(), drt.as<double>(), dar.as<double>(), dmd.as<int>(), nd, ng, ndc, dprec.as<double>(), drec.as<double>(),
+                   dsc.as<double>(), ddtm.as<double>(), dgtm.as<double>(), ddig.as<unsigned char>(), dgig.as<unsigned char>()};
+    launch_coco_eval(a, scratch.p, st);
+    FFP_HIP(hipStreamSynchronize(st));
+    if (n_pr) {
+      FFP_HIP(hipMemcpy(precision, dprec.p, sizeof(double) * n_pr, hipMemcpyDeviceToHost));
+      FFP_HIP(hipMemcpy(scores, dsc.p, sizeof(double) * n_pr, hipMemcpyDeviceToHost));
+      FFP_HIP(hipMemcpy(recall, drec.p, sizeof(double) * n_rc, hipMemcpyDeviceToHost));
+    }
+    if (dt_matches && ndc) FFP_HIP(hipMemcpy(dt_matches, ddtm.p, sizeof(double) * (size_t)A * T * ndc, hipMemcpyDeviceToHost));
+    if (dt_ignore && ndc) FFP_HIP(hipMemcpy(dt_ignore, ddig.p, (size_t)A * T * ndc, hipMemcpyDeviceToHost));
+    if (gt_matches && ng) FFP_HIP(hipMemcpy(gt_matches, dgtm.p, sizeof(double) * (size_t)A * T * ng, hipMemcpyDeviceToHost));
+    if (gt_ignore && ng) FFP_HIP(hipMemcpy(gt_ignore, dgig.p, (size_t)A * ng, hipMemcpyDeviceToHost));
   } catch (...) {
     (void)hipStreamDestroy(st);
     throw;

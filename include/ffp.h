@@ -284,6 +284,21 @@ int ffp_eval_wider_pr(int device, const double* preds, const int64_t* pred_off, 
 int ffp_eval_dual_match(int device, const double* preds, const int64_t* pred_off, const double* faces, const int64_t* face_off, const uint8_t* valid,
                         int n_img, double iou_thr, int32_t* out_flags);
 
+/* COCO bbox evaluation: pycocotools 2.0.x `COCOeval(cocoGt, cocoDt, 'bbox')` `.evaluate()` + `.accumulate()` (cocoeval.py, with
+ * maskApi.c `bbIou`) for a whole dataset, bit-identical to it; `summarize()` stays with the caller (numpy's pairwise mean). A unit is an
+ * (image, category) pair; the n_cat * n_img units come in evalImgs order (category-major, image ids sorted). dets [det_off[U]][7] =
+ * x, y, w, h, score, area, id in loadRes order per unit (ids > 0, scores not NaN); gts [gt_off[U]][8] = x, y, w, h, area, iscrowd,
+ * ignore, id in annotation order per unit (ignore = iscrowd after _prepare; a crowd must be ignored). Params exactly as the host holds
+ * them (never recomputed here): iou_thrs [T], rec_thrs [R], area_rng [A][2], max_dets [M] ascending. Outputs as accumulate builds
+ * them, -1 where it leaves -1: precision / scores [T][R][K][A][M], recall [T][K][A][M]. Optional (NULL = skip), the evalImgs match
+ * arrays per area a and threshold t: dt_matches / dt_ignore [A][T][ndc] (ndc = sum over units of min(#dets, max_dets[M-1]); a
+ * unit's dets in score order from its cut offset), gt_matches [A][T][gt_off[U]] and gt_ignore [A][gt_off[U]] (a unit's GTs in that
+ * area's "ignored last" order). Malformed offsets, sizes or ids: FFP_ERR_ARG, nothing is truncated. */
+int ffp_eval_coco_bbox(int device, int n_img, int n_cat, const double* dets, const int64_t* det_off, const double* gts, const int64_t* gt_off,
+                       const double* iou_thrs, int n_iou, const double* rec_thrs, int n_rec, const double* area_rng, int n_area,
+                       const int32_t* max_dets, int n_max_dets, double* precision, double* recall, double* scores, double* dt_matches,
+                       uint8_t* dt_ignore, double* gt_matches, uint8_t* gt_ignore);
+
 /* ---------------------------------------------------------------------------------------------------------
  * JPEG at the file boundaries
  * ------------------------------------------------------------------------------------------------------- */
