@@ -10,9 +10,13 @@ enhanced crops back in host memory: frame upload (copy stream, overlapped with t
 512x512 / 0.2 slicing (60 slices + the full-frame pass), YOLO11s-pose on every item at net input 512, per-item NMS,
 int-truncate + shift, [RCCL all-gather of the fixed-cap boxes when a frame's items are spread over ranks], SAHI
 GREEDYNMM/IOS/0.5 merge, merged detections to host, Real-ESRGAN x4 on 32 crops per frame whose sizes change every frame,
-enhanced crops to host. Rank 0 prints ONE JSON line (contract in the task statement) with `roofline`, `secondary`
-(the reference-default image_size=1024, the eval merge NMS/IOS/agnostic, the exact-fp32 detector, fixed crop sizes, frames
-already resident in HBM; at N>1 the forced all-gather and ONE frame's slices across the ranks) and, at N=1, `cpu_baseline`.
+enhanced crops to host. Rank 0 prints ONE JSON line (contract in the task statement).
+
+A plain run does only what that line's headline needs: set-up, warm-up, the timed steps, --dump-outputs if given, the line.
+--full adds what takes runs of its own: the profiled pass behind `roofline`, `conv_profile_last_step` and `stage_ms_last_call`,
+`secondary` (the reference-default image_size=1024, the eval merge NMS/IOS/agnostic, the exact-fp32 detector, fixed crop sizes,
+frames already resident in HBM, the drop-in API, the other BASELINE configs; at N>1 the forced all-gather and ONE frame's slices
+across the ranks) and, at N=1, `cpu_baseline`.
 """
 from __future__ import annotations
 
@@ -66,17 +70,20 @@ def parse(argv=None):
                     help="consecutive steps whose frames are detected together as one ragged batch of slices (1: per step)")
     ap.add_argument("--lanes", type=int, default=2,
                     help="pipeline lanes per process: L detector + enhancer handle pairs driven by L host threads, detection groups dealt round-robin "
-                         "(their kernels interleave on the card; secondary.one_lane is the same loop on one lane). The kernel events behind `roofline` are "
-                         "taken on ONE lane in an extra profiled pass after the timed region, with the card to itself. Only where the ranks run independent "
-                         "frames (no collective in the loop): other layouts run one lane")
+                         "(their kernels interleave on the card; secondary.one_lane is the same loop on one lane). With --full, the kernel events behind "
+                         "`roofline` are taken on ONE lane in an extra profiled pass after the timed region, with the card to itself. Only where the ranks run "
+                         "independent frames (no collective in the loop): other layouts run one lane")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what it does not need: the profiled pass (roofline, conv_profile_last_step, stage_ms_last_call, "
+                         "sr_ms_last_call), the secondary rows and the CPU baseline")
     ap.add_argument("--conv-totals", action="store_true",
                     help="count launches, algorithmic FLOPs and bytes of every conv launch of the process (ffp_conv_totals_*) and print them as \"conv_totals\": "
                          "what tools/pmc_traffic.py needs beside a rocprofv3 --pmc pass of this same command")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-sample", action="store_true", help="CPU baseline on a bounded sample (3 slices + 3 crops) instead of one whole frame")
-    ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: leave the secondary rows out")
     ap.add_argument("--secondary-steps", type=int, default=20)
-    ap.add_argument("--secondary-only", default="", help="comma-separated names: measure only these secondary rows (experiments)")
+    ap.add_argument("--secondary-only", default="", help="with --full, comma-separated names: measure only these secondary rows (experiments)")
     ap.add_argument("--sr-exclusive", action="store_true", help="experiment: wait for every SR batch before the next detection group (no overlap of the two streams)")
     ap.add_argument("--verify", action="store_true",
                     help="after the timed run: the pipelined loop's outputs (merged rows, crop boxes, enhanced crops; JPEG files with jpeg_io) over 25 steps against "
@@ -87,6 +94,8 @@ def parse(argv=None):
     args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full and (args.secondary_only or args.cpu_sample):
+        ap.error("--secondary-only and --cpu-sample shape what --full measures: add --full")
     return args
 
 
@@ -1038,7 +1047,7 @@ def main():
         return int(total - free)
 
     main_r = Runner(args, ctx)
-    dt = main_r.timed(args.warmup, args.steps, keep_last=bool(args.dump_outputs))
+    dt = main_r.timed(args.warmup, args.steps, profile_last=args.full, keep_last=bool(args.dump_outputs))
     if args.dump_outputs and rank == 0:
         nb = dump_outputs(args.dump_outputs, main_r.last_outputs)
         print(f"[bench] --dump-outputs: step {args.steps - 1} of the timed loop, {nb / 1e6:.1f} MB in {args.dump_outputs}", file=sys.stderr, flush=True)
@@ -1049,12 +1058,13 @@ def main():
     main_report = main_r.report(args.steps)
     pipe = main_r.prof_pipe                        # the lane that carried the kernel events of the timed loop (lane 0 when there is one lane)
     pipes = main_r.pipes
-    prof = [dict(p, stage="det") for p in pipe.det.profile()]
-    if pipe.sr is not None:
-        prof += [dict(p, stage="sr") for p in pipe.sr.profile()]
-    prof.sort(key=lambda p: -p["ms"])
-    stage_ms = pipe.det.last_ms()
-    sr_ms = pipe.sr.last_ms() if pipe.sr is not None else None
+    if args.full:
+        prof = [dict(p, stage="det") for p in pipe.det.profile()]
+        if pipe.sr is not None:
+            prof += [dict(p, stage="sr") for p in pipe.sr.profile()]
+        prof.sort(key=lambda p: -p["ms"])
+        stage_ms = pipe.det.last_ms()
+        sr_ms = pipe.sr.last_ms() if pipe.sr is not None else None
     sr_state = pipe.sr.plan_state() if pipe.sr is not None else None
     det_graph = pipe.det.graph_status()
     main_state = dict(main_r.state)
@@ -1062,7 +1072,7 @@ def main():
 
     # ---- secondary rows, measured in this same run (--secondary-steps, default 20 like the headline): what the headline configuration is NOT ------------------------
     secondary = {}
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         ss, sw = max(2, args.secondary_steps), max(2, min(args.warmup, main_r.DB))     # whole detection groups: a warm-up of 4 would lay out a 4-frame plan beside the 5-frame one
 
         only = set(x for x in args.secondary_only.split(",") if x)
@@ -1186,17 +1196,17 @@ def main():
 
     if rank == 0:
         roof = None
-        pmc = {}
-        pmc_src = None
-        for name in ("r04_pmc_traffic.json", "r03_pmc_traffic.json", "r02_pmc_traffic.json", "r01_pmc_traffic.json"):   # HBM bytes per launch from the committed PMC passes, keyed by kernel variant
-            try:
-                with open(os.path.join(ROOT, "profiles", name)) as fh:
-                    pmc = json.load(fh).get("kernels", {})
-                pmc_src = name
-                break
-            except Exception:
-                pmc = {}
-        if prof:
+        if args.full and prof:
+            pmc = {}
+            pmc_src = None
+            for name in ("r04_pmc_traffic.json", "r03_pmc_traffic.json", "r02_pmc_traffic.json", "r01_pmc_traffic.json"):   # HBM bytes per launch from the committed PMC passes, keyed by kernel variant
+                try:
+                    with open(os.path.join(ROOT, "profiles", name)) as fh:
+                        pmc = json.load(fh).get("kernels", {})
+                    pmc_src = name
+                    break
+                except Exception:
+                    pmc = {}
             d = prof[0]
             dtp = d["variant"].split("_")[0]
             ach = d["flops"] / (d["ms"] * 1e-3) / 1e12 if d["ms"] > 0 else 0.0
@@ -1227,9 +1237,9 @@ def main():
                        "frames_per_step": B, "det_batch_frames": main_r.DB, "sr_batch_frames": main_r.SB, "mode": main_r.mode,
                        "lanes": main_r.n_lanes,
                        "lanes_note": ("detection groups are dealt round-robin to %d lanes (one detector + enhancer handle pair and one host thread each) whose kernels "
-                                      "interleave on the card; the kernel events behind roofline / conv_profile_last_step / stage_ms_last_call come from an extra pass "
-                                      "AFTER the timed region, on lane 0 alone; per_rank stage times are summed over the lanes' host threads"
-                                      % main_r.n_lanes) if main_r.n_lanes > 1 else None,
+                                      "interleave on the card; %sper_rank stage times are summed over the lanes' host threads"
+                                      % (main_r.n_lanes, "the kernel events behind roofline / conv_profile_last_step / stage_ms_last_call come from an extra pass "
+                                                         "AFTER the timed region, on lane 0 alone; " if args.full else "")) if main_r.n_lanes > 1 else None,
                        "collective": {"backend": ("rccl" if backend == "nccl" else backend) if world > 1 else None, "ranks": world,
                                       "communicator_ranks": (dist.get_world_size() if world > 1 else 1),
                                       "all_gathers_per_group": int(bool(main_state.get("gathered"))),
@@ -1245,18 +1255,21 @@ def main():
                        "det_graph_status": det_graph, "sr_plan_state": sr_state},
             "latency_ms_rank0": main_report[0]["latency_ms"],
             "per_rank": main_report,
-            "stage_ms_last_call": {k: round(v, 3) for k, v in stage_ms.items()},
-            "sr_ms_last_call": round(sr_ms, 3) if sr_ms is not None else None,
-            "conv_profile_last_step": [{"kernel": p["variant"], "stage": p["stage"], "ms": round(p["ms"], 3), "launches": p["launches"],
-                                        "tflops": round(p["flops"] / max(p["ms"], 1e-9) / 1e9, 2)} for p in prof],
-            "roofline": roof,
-            "secondary": secondary,
         }
+        if args.full:
+            res.update({
+                "stage_ms_last_call": {k: round(v, 3) for k, v in stage_ms.items()},
+                "sr_ms_last_call": round(sr_ms, 3) if sr_ms is not None else None,
+                "conv_profile_last_step": [{"kernel": p["variant"], "stage": p["stage"], "ms": round(p["ms"], 3), "launches": p["launches"],
+                                            "tflops": round(p["flops"] / max(p["ms"], 1e-9) / 1e9, 2)} for p in prof],
+                "roofline": roof,
+                "secondary": secondary,
+            })
         if world == 1 and args.verify:
             res["verify"] = verify_rows(args, ctx, pipes, steps=max(25, args.steps))
             if not all(v["ok"] for v in res["verify"].values()):
                 print("[bench] --verify: the pipelined loop's outputs differ from the synchronous calls", file=sys.stderr, flush=True)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             base_r = Runner(args, ctx, pipes=pipes, resident=True, lanes=1)
             sf, _ = base_r.upload(0, 1)
             d, c, _, _ = base_r.pipe.detect(sf, H, W, 1)

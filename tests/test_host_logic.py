@@ -183,6 +183,20 @@ def test_bench_lanes_deal_every_group_exactly_once():
                     assert lanes[owner].my_groups(n_steps)[-1][0] == len(all_groups) - 1
 
 
+def test_bench_full_is_opt_in():
+    """bench.py: a plain run measures the headline alone; the profiled pass, secondary rows and CPU baseline need --full, and the
+    options that only shape those are refused without it rather than ignored."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert bench.parse([]).full is False
+    assert bench.parse(["--full", "--secondary-only", "frame_by_frame", "--cpu-sample"]).full is True
+    for extra in (["--secondary-only", "frame_by_frame"], ["--cpu-sample"]):
+        with pytest.raises(SystemExit):
+            bench.parse(extra)
+
+
 def test_bench_dump_outputs_reads_the_last_batch_and_keeps_the_budget(tmp_path):
     """bench.py --dump-outputs: the kept frame's crops are cut out of the lane's last SR batch (16-byte aligned entries, boxes clamped
     to the frame, the frame's crops after those of earlier frames in the batch, the frame on another lane); the .npy files are float

@@ -7,9 +7,9 @@ TAG=${1:-r04}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/${TAG}_prof
 mkdir -p $O
-B="python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary"
+B="python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-secondary"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/stats -o s --output-format csv -- $B > $O/bench_under_rocprof.json 2> $O/stats.log && echo stats ok
-S="python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-secondary --conv-totals"
+S="python3 bench.py --steps 10 --warmup 2 --full --no-cpu-baseline --no-secondary --conv-totals"
 timeout -k 10 400 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/fetch -o f --output-format csv -- $S > $O/fetch_bench.json 2> $O/fetch.log && echo fetch ok
 timeout -k 10 400 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/write -o w --output-format csv -- $S > /dev/null 2> $O/write.log && echo write ok
 timeout -k 10 400 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE -d $O/sq1 -o p --output-format csv -- $S > /dev/null 2> $O/sq1.log && echo sq1 ok

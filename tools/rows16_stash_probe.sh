@@ -16,5 +16,5 @@ for n, cin, cout in ((2048, 128, 32), (2048, 64, 32), (2048, 192, 64), (4700, 16
     us = min(_lib.op_conv2d_time(n, 16, 16, cin, cout, 3, 1, False, _lib.PREC_F16, 40, 0, 9) for _ in range(3))
     print(f"tiles={n} {cin}->{cout}: {us:.1f} us  {flops / us / 1e6:.0f} TF/s", flush=True)
 PY
-  timeout -k 10 300 python bench.py --no-cpu-baseline --no-secondary 2>/dev/null | python -c "import sys,json; r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('bench', r['value'], r['ms_per_step'], r['roofline']['frac'], r['roofline']['avg_launch_us'])"
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-secondary 2>/dev/null | python -c "import sys,json; r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('bench', r['value'], r['ms_per_step'], r['roofline']['frac'], r['roofline']['avg_launch_us'])"
 done
