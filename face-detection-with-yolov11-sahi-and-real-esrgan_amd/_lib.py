@@ -128,6 +128,15 @@ _SIGS = {
     "ffp_op_conv2d": (C.c_int, [C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_float), _p(C.c_float), C.c_int,
                                 C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_float), C.c_float, _p(C.c_float)]),
     "ffp_op_resize_lanczos4": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "ffp_scrfd_create": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, _p(C.c_void_p)]),
+    "ffp_scrfd_destroy": (None, [C.c_void_p]),
+    "ffp_scrfd_describe": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
+    "ffp_scrfd_infer_tiles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _p(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_float,
+                                        C.c_float, _p(C.c_float), C.c_int, _p(C.c_int32)]),
+    "ffp_scrfd_forward_raw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _p(C.c_int32), C.c_int, C.c_int, C.c_int, _p(C.c_float),
+                                        C.c_size_t, _p(C.c_int64)]),
+    "ffp_scrfd_info": (C.c_int, [C.c_void_p, _p(C.c_int32), _p(C.c_double)]),
+    "ffp_scrfd_geometry": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_int32), _p(C.c_float)]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -212,6 +221,96 @@ def _as_frame(frame: np.ndarray) -> np.ndarray:
     if f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3:
         raise ValueError(f"expected an HxWx3 uint8 array, got {f.dtype} {f.shape}")
     return f
+
+
+def scrfd_describe(onnx_bytes: bytes, n: int = 1, det_w: int = 640, det_h: int = 640) -> str:
+    """The lowered step list of an SCRFD ONNX file (host only, no device). Raises FfpError with the refusal message."""
+    buf = C.create_string_buffer(bytes(onnx_bytes), len(onnx_bytes))
+    out = C.create_string_buffer(1 << 20)
+    _check(lib().ffp_scrfd_describe(buf, len(onnx_bytes), n, det_w, det_h, out, len(out)))
+    return out.value.decode()
+
+
+def scrfd_geometry(h: int, w: int, net_w: int, net_h: int) -> Tuple[int, int, float]:
+    """RetinaFace.detect's (new_w, new_h, det_scale) of an h x w crop at net size net_w x net_h (host only)."""
+    o = np.zeros(2, np.int32)
+    s = C.c_float(0)
+    _check(lib().ffp_scrfd_geometry(h, w, net_w, net_h, _ip(o), C.byref(s)))
+    return int(o[0]), int(o[1]), float(s.value)
+
+
+class FaceDetector:
+    """InsightFace's SCRFD face detector (an ONNX file of a model pack, e.g. buffalo_l/det_10g.onnx) on one GPU (ffp_scrfd_*)."""
+
+    STRIDE = 21          # FFP_DET_STRIDE(5)
+
+    def __init__(self, onnx, device: int = 0, precision: int = PREC_F32, n: int = 1):
+        buf = _weights_bytes(onnx) if not isinstance(onnx, dict) else None
+        if buf is None:
+            raise TypeError("FaceDetector takes the ONNX file's bytes or its path")
+        self._h = C.c_void_p()
+        self.device, self.precision = device, precision
+        cbuf = C.create_string_buffer(buf, len(buf))
+        _check(lib().ffp_scrfd_create(cbuf, len(buf), n, device, precision, C.byref(self._h)))
+        n_out = C.c_int32(0)
+        _check(lib().ffp_scrfd_info(self._h, C.byref(n_out), None))
+        self.n_outputs = int(n_out.value)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            lib().ffp_scrfd_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def last_conv_flops(self) -> float:
+        f = C.c_double(0)
+        _check(lib().ffp_scrfd_info(self._h, None, C.byref(f)))
+        return float(f.value)
+
+    def infer_tiles(self, frame: np.ndarray, tiles: Sequence[Sequence[int]], det_size=(640, 640), det_thresh: float = 0.5,
+                    nms_thresh: float = 0.4, chan_order: int = CHAN_AS_BGR, cap: int = 1024) -> List[np.ndarray]:
+        """-> per tile (n_i, 21) float32 rows [x1,y1,x2,y2,score,0, 5 x (x,y,1)] in tile-local pixels (not truncated)."""
+        f = _as_frame(frame)
+        t = np.ascontiguousarray(np.asarray(tiles, np.int32).reshape(-1, 4))
+        n = t.shape[0]
+        while True:
+            dets = np.zeros((n, cap, self.STRIDE), np.float32)
+            counts = np.zeros(n, np.int32)
+            rc = lib().ffp_scrfd_infer_tiles(self._h, f.ctypes.data, f.shape[0], f.shape[1], chan_order, _ip(t), n, int(det_size[0]),
+                                             int(det_size[1]), det_thresh, nms_thresh, _fp(dets), cap, _ip(counts))
+            if rc != 0 and int(counts.max(initial=0)) > cap:
+                cap = int(counts.max())                # out_counts are not capped: retry once with room for every face
+                continue
+            _check(rc)
+            return [dets[i, :counts[i]].copy() for i in range(n)]
+
+    def forward_raw(self, frame: np.ndarray, tiles: Sequence[Sequence[int]], det_size=(640, 640),
+                    chan_order: int = CHAN_AS_BGR) -> List[List[np.ndarray]]:
+        """-> per tile the graph outputs in file order, each (anchors, values) float32 (scores after the sigmoid)."""
+        f = _as_frame(frame)
+        t = np.ascontiguousarray(np.asarray(tiles, np.int32).reshape(-1, 4))
+        n = t.shape[0]
+        W, H = int(det_size[0]), int(det_size[1])
+        per = sum((H // s) * (W // s) * 2 * v for s in (8, 16, 32) for v in (1, 4, 10))
+        out = np.zeros(per * n, np.float32)
+        sizes = np.zeros(self.n_outputs, np.int64)
+        _check(lib().ffp_scrfd_forward_raw(self._h, f.ctypes.data, f.shape[0], f.shape[1], chan_order, _ip(t), n, W, H, _fp(out), out.size,
+                                           sizes.ctypes.data_as(_p(C.c_int64))))
+        res, o = [], 0
+        widths = [1] * 3 + [4] * 3 + [10] * 3
+        for i in range(n):
+            outs = []
+            for k in range(self.n_outputs):
+                m = int(sizes[k])
+                outs.append(out[o:o + m].reshape(-1, widths[k]).copy())
+                o += m
+            res.append(outs)
+        return res
 
 
 class Detector:

@@ -8,6 +8,7 @@
 #include "eval.hpp"
 #include "jpeg.hpp"
 #include "sr_ops.hpp"
+#include "scrfd.hpp"
 #include "yolo11.hpp"
 
 namespace ffp {
@@ -15,6 +16,7 @@ const std::string& last_error();
 }
 
 struct ffp_det { ffp::DetEngine eng; ffp_det(const void* w, size_t n, int a, int nc, int nk, int dev, int pr) : eng(w, n, a, nc, nk, dev, pr) {} };
+struct ffp_scrfd { ffp::ScrfdEngine eng; ffp_scrfd(const void* b, size_t nb, int n, int dev, int pr) : eng(b, nb, n, dev, pr) {} };
 struct ffp_sr { ffp::SrEngine eng; ffp_sr(const void* w, size_t n, int s, int nb, int dev, int h) : eng(w, n, s, nb, dev, h) {} };
 
 using namespace ffp;
@@ -1116,6 +1118,77 @@ int ffp_op_resize_lanczos4(int device, const void* src, int h, int w, int channe
     throw;
   }
   FFP_HIP(hipStreamDestroy(st));
+  FFP_API_END
+}
+
+// ---- SCRFD (InsightFace RetinaFace) --------------------------------------------------------------------------------------------
+
+int ffp_scrfd_create(const void* onnx_bytes, size_t nbytes, int n, int device, int precision, ffp_scrfd** out) {
+  FFP_API_BEGIN
+  FFP_CHECK(out && onnx_bytes && nbytes > 0, FFP_ERR_ARG, "null argument");
+  FFP_CHECK(n >= 1, FFP_ERR_ARG, "batch hint %d", n);
+  *out = new ffp_scrfd(onnx_bytes, nbytes, n, device, precision);
+  FFP_API_END
+}
+
+void ffp_scrfd_destroy(ffp_scrfd* s) { delete s; }
+
+int ffp_scrfd_describe(const void* onnx_bytes, size_t nbytes, int n, int det_w, int det_h, char* out, size_t cap) {
+  std::string text;
+  int rc = FFP_OK;
+  try {
+    text = ffp::onnx::lower(ffp::onnx::parse(onnx_bytes, nbytes), n, det_w, det_h).describe();
+  } catch (const ffp::Error& e) {
+    ffp::set_last_error(e.what());
+    text = e.what();
+    rc = e.code;
+  } catch (const std::bad_alloc&) {
+    ffp::set_last_error("host out of memory");
+    return FFP_ERR_NOMEM;
+  } catch (const std::exception& e) {
+    ffp::set_last_error(e.what());
+    text = e.what();
+    rc = FFP_ERR_STATE;
+  }
+  if (out && cap > 0) {
+    const size_t k = std::min(text.size(), cap - 1);
+    std::memcpy(out, text.data(), k);
+    out[k] = 0;
+  }
+  return rc;
+}
+
+int ffp_scrfd_infer_tiles(ffp_scrfd* s, const uint8_t* frame, int H, int W, int chan_order, const int32_t* tiles, int n_tiles, int det_w, int det_h,
+                          float det_thresh, float nms_thresh, float* out_dets, int cap, int32_t* out_counts) {
+  FFP_API_BEGIN
+  FFP_CHECK(s, FFP_ERR_ARG, "null handle");
+  s->eng.infer_tiles(frame, H, W, chan_order, tiles, n_tiles, det_w, det_h, det_thresh, nms_thresh, out_dets, cap, out_counts);
+  FFP_API_END
+}
+
+int ffp_scrfd_forward_raw(ffp_scrfd* s, const uint8_t* frame, int H, int W, int chan_order, const int32_t* tiles, int n_tiles, int det_w, int det_h,
+                          float* out, size_t cap, int64_t* out_sizes) {
+  FFP_API_BEGIN
+  FFP_CHECK(s && out && out_sizes, FFP_ERR_ARG, "null argument");
+  s->eng.forward_raw(frame, H, W, chan_order, tiles, n_tiles, det_w, det_h, out, cap, out_sizes);
+  FFP_API_END
+}
+
+int ffp_scrfd_geometry(int h, int w, int net_w, int net_h, int32_t* out2, float* det_scale) {
+  FFP_API_BEGIN
+  FFP_CHECK(out2 && det_scale && h > 0 && w > 0 && net_w > 0 && net_h > 0, FFP_ERR_ARG, "scrfd_geometry: sizes must be positive");
+  int nw, nh;
+  scrfd_geometry(h, w, net_w, net_h, &nw, &nh, det_scale);
+  out2[0] = nw;
+  out2[1] = nh;
+  FFP_API_END
+}
+
+int ffp_scrfd_info(ffp_scrfd* s, int32_t* out_n_outputs, double* out_last_conv_flops) {
+  FFP_API_BEGIN
+  FFP_CHECK(s, FFP_ERR_ARG, "null handle");
+  if (out_n_outputs) *out_n_outputs = s->eng.n_outputs();
+  if (out_last_conv_flops) *out_last_conv_flops = s->eng.last_conv_flops;
   FFP_API_END
 }
 

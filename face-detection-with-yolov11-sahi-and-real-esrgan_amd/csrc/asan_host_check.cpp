@@ -6,7 +6,9 @@
 //   * seeded byte / bit mutations, with extra weight on the marker segments (DHT, DQT, SOF, SOS, DRI),
 //   * hand-made malformed streams (over-subscribed DHT, all-ones codes, fill bytes at the end, zero-length segments, RGB-coded files),
 // and expects each call to either succeed or throw ffp::Error — any out-of-bounds access, overflow or undefined shift aborts the
-// process through the sanitizer runtime. Usage: asan_host_check jpeg <file>... ffpw <file>...
+// process through the sanitizer runtime. ONNX models (onnx_graph.cpp) are parsed and lowered (SCRFD subset) under the same cases:
+// every truncation of the first 4 KiB and at a stride through the body, and seeded byte / bit mutations.
+// Usage: asan_host_check jpeg <file>... ffpw <file>... onnx <file>...
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -15,6 +17,7 @@
 #include <vector>
 
 #include "jpeg.hpp"
+#include "onnx_graph.hpp"
 #include "weights.hpp"
 
 using namespace ffp;
@@ -185,17 +188,56 @@ static void ffpw_cases(const Bytes& good, unsigned seed) {
   }
 }
 
+static bool try_onnx(const Bytes& b) {
+  std::unique_ptr<unsigned char[]> d(new unsigned char[b.size() ? b.size() : 1]);     // exact-size copy: a redzone right behind it
+  if (!b.empty()) memcpy(d.get(), b.data(), b.size());
+  try {
+    const onnx::Graph g = onnx::parse(d.get(), b.size());
+    (void)onnx::lower(g, 2, 64, 64).describe();
+    ++g_ok;
+    return true;
+  } catch (const Error&) {
+    ++g_rejected;
+    return false;
+  }
+}
+
+static void onnx_cases(const Bytes& good, unsigned seed) {
+  if (!try_onnx(good)) { fprintf(stderr, "a valid model was rejected\n"); exit(3); }
+  const size_t he = good.size() < 4096 ? good.size() : 4096;
+  for (size_t n = 0; n <= he; ++n) try_onnx(Bytes(good.begin(), good.begin() + n));
+  for (size_t n = he; n < good.size(); n += 1 + good.size() / 512) try_onnx(Bytes(good.begin(), good.begin() + n));
+  std::mt19937 rng(seed);
+  for (int it = 0; it < 3000; ++it) {
+    Bytes m = good;
+    const int k = 1 + (int)(rng() % 4);
+    for (int q = 0; q < k; ++q) {
+      const size_t pos = rng() % m.size();
+      switch (rng() % 4) {
+        case 0: m[pos] = (unsigned char)rng(); break;
+        case 1: m[pos] = 0xFF; break;
+        case 2: m[pos] = 0x80; break;
+        default: m[pos] ^= (unsigned char)(1u << (rng() % 8)); break;
+      }
+    }
+    if (rng() % 4 == 0) m.resize(rng() % m.size());
+    try_onnx(m);
+  }
+}
+
 int main(int argc, char** argv) {
-  enum { NONE, JPEG, FFPW } mode = NONE;
+  enum { NONE, JPEG, FFPW, ONNX } mode = NONE;
   unsigned seed = 1;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
     if (a == "jpeg") { mode = JPEG; continue; }
     if (a == "ffpw") { mode = FFPW; continue; }
+    if (a == "onnx") { mode = ONNX; continue; }
     const Bytes b = slurp(argv[i]);
     if (mode == JPEG) jpeg_cases(b, seed++);
     else if (mode == FFPW) ffpw_cases(b, seed++);
-    else { fprintf(stderr, "usage: %s jpeg <file>... ffpw <file>...\n", argv[0]); return 2; }
+    else if (mode == ONNX) onnx_cases(b, seed++);
+    else { fprintf(stderr, "usage: %s jpeg <file>... ffpw <file>... onnx <file>...\n", argv[0]); return 2; }
   }
   printf("asan_host_check: %lld inputs parsed, %lld rejected, no sanitizer report\n", g_ok, g_rejected);
   return 0;

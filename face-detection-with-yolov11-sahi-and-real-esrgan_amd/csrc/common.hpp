@@ -170,6 +170,6 @@ struct TView {
 };
 
 // ---- activation codes ------------------------------------------------------------------------------------
-enum Act : int { ACT_NONE = 0, ACT_SILU = 1, ACT_LRELU = 2 };
+enum Act : int { ACT_NONE = 0, ACT_SILU = 1, ACT_LRELU = 2, ACT_RELU = 3 };
 
 }  // namespace ffp

@@ -22,6 +22,7 @@ struct ConvArgs {
   int out_cs, out_coff, cout;
   int r1_cs, r1_coff, r2_cs, r2_coff;
   float s1, s2;
+  int act_post;         // activation applied after the residual terms (SCRFD: Relu(Add(conv, x))); ACT_NONE for every other plan
   int act, out_f32, up, n_nblk, ncg, ntiles32, vec_ok, fast_out;
   int force_shape;   // tuning only: -1 auto
   int dbg;   // tuning only (ffp_op_conv2d_time): 1 skip stores, 2 skip MFMAs, 4 skip chunk refetch, 8 skip LDS stash
@@ -149,6 +150,7 @@ __device__ __forceinline__ float apply_act(float v, int act) {
   // 256 px x 64 ch block otherwise spends ~2.7 us in the activation alone
   if (act == ACT_SILU) return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));
   if (act == ACT_LRELU) return v >= 0.f ? v : v * 0.2f;
+  if (act == ACT_RELU) return fmaxf(v, 0.f);
   return v;
 }
 

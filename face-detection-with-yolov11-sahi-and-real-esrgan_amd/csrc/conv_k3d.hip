@@ -369,6 +369,10 @@ __global__ void __launch_bounds__(256, (K3Geo<S, WM, WN, MI, NIW>::OCC)) conv_k3
 #pragma unroll
             for (int q = 0; q < 4; ++q) v[q] = v[q] * a.s2 + r[q];
           }
+          if (a.act_post) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v[q] = apply_act(v[q], a.act_post);
+          }
           if (oks[it]) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) am = fmaxf(am, fabsf(v[q]));

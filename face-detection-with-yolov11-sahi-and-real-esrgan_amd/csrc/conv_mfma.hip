@@ -688,6 +688,10 @@ __global__ void __launch_bounds__(256, (Geo<T, KS, STRIDE, WM, WN, MI, NIW, KC>:
 #pragma unroll
             for (int q = 0; q < CPL; ++q) v[q] = v[q] * a.s2 + (float)r[q];
           }
+          if (a.act_post) {
+#pragma unroll
+            for (int q = 0; q < CPL; ++q) v[q] = apply_act(v[q], a.act_post);
+          }
           if constexpr (SPLIT) {
 #pragma unroll
             for (int q = 0; q < CPL; ++q) amax_run[mi] = fmaxf(amax_run[mi], fabsf(v[q]));
@@ -770,6 +774,10 @@ __global__ void __launch_bounds__(256, (Geo<T, KS, STRIDE, WM, WN, MI, NIW, KC>:
           else for (int j = 0; j < 4; ++j) if (ch + j < a.cout) r[j] = (float)rp[j];
 #pragma unroll
           for (int j = 0; j < 4; ++j) v[j] = v[j] * a.s2 + r[j];
+        }
+        if (a.act_post) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) v[j] = apply_act(v[j], a.act_post);
         }
         if constexpr (SPLIT) {
 #pragma unroll
@@ -1064,7 +1072,7 @@ ConvArgs make_conv_args(const ConvOp& op) {
   a.out_cs = op.out.cs; a.out_coff = op.out.coff; a.cout = pc.cout;
   a.r1_cs = op.res1.cs; a.r1_coff = op.res1.coff; a.r2_cs = op.res2.cs; a.r2_coff = op.res2.coff;
   a.s1 = op.s1; a.s2 = op.s2;
-  a.act = op.act; a.out_f32 = (op.out.dt == F32) ? 1 : 0; a.up = op.up;
+  a.act = op.act; a.act_post = op.act_post; a.out_f32 = (op.out.dt == F32) ? 1 : 0; a.up = op.up;
   a.ncg = pc.ncg; a.ntiles32 = pc.cout_pad / 32;
   bool vec = pc.cout % 4 == 0 && op.out.cs % 4 == 0 && op.out.coff % 4 == 0;
   if (op.has_res1) {

@@ -342,7 +342,7 @@ __global__ void __launch_bounds__((NW + (ST ? 1 : 0)) * 64, 2) conv_pw_kernel(co
 #endif
     // ---- epilogue: register i of a tile = pixel row 8*(i>>2) + 4*hh + (i&3), this lane's channel
     const auto rs_out = rsrc(block_span(a.out, pb, a.out_cs, a.out_coff));
-    const bool silu = a.act == ACT_SILU;
+    const bool silu = a.act == ACT_SILU, relu = a.act == ACT_RELU;
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi) {
       float am = 0.f;
@@ -355,6 +355,7 @@ __global__ void __launch_bounds__((NW + (ST ? 1 : 0)) * 64, 2) conv_pw_kernel(co
         for (int i = 0; i < 16; ++i) {
           float v = fmaf(acc[mi][nt][i], osc, bias_n[nt]);
           if (silu) v = v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));
+          else if (relu) v = fmaxf(v, 0.f);
           if (px0 + 8 * (i >> 2) + (i & 3) < rend_f[mi] && cbyte[nt] != PW_OOB) am = fmaxf(am, fabsf(v));      // padding pixels / channels do not count
           __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rs_out, vo + (unsigned)(8 * (i >> 2) + (i & 3)) * ocs4, 0, 0);
         }
@@ -462,7 +463,7 @@ void conv_pw_init() { Pw14::init(); Pw22::init(); Pw21::init(); Pw14w::init(); P
 static bool pw_common(const ConvOp& op, const ConvArgs& a) {
   const PackedConv& pc = *op.pc;
   if (op.has_up2 && (long long)op.up2.lvl->total_px * op.up2.cs * 4 >= 0x7FFFFFF0ll) return false;      // one buffer resource spans the coarser tensor
-  return pc.split && pc.k == 1 && op.stride == 1 && !op.has_res1 && !op.has_res2 && a.out_f32 && pc.cin % 32 == 0 &&
+  return pc.split && pc.k == 1 && op.stride == 1 && !op.has_res1 && !op.has_res2 && !op.act_post && a.out_f32 && pc.cin % 32 == 0 &&
          pc.cin_pad == pc.cin && !op.out.lvl->capacity() && a.total_px > 0;
 }
 

@@ -19,10 +19,12 @@ __device__ __forceinline__ void lin_coef(int d, double scale, int n_src, bool ze
   c1 = (int)rintf(f * 2048.0f);
 }
 
-// One pixel of the letterboxed network image (u8 per channel, source channel order): pad 114 outside the resized picture,
-// a plain copy when the crop is not resized, else the fixed-point bilinear sample.
-__device__ __forceinline__ void letterbox_sample(const uint8_t* __restrict__ frame, int W, const LetterboxImg& L, int y, int x, int (&px)[3]) {
-  px[0] = px[1] = px[2] = 114;
+// One pixel of the letterboxed network image (u8 per channel, source channel order): `pad` (Ultralytics: 114; InsightFace's
+// RetinaFace.detect: 0, picture at the top-left) outside the resized picture, a plain copy when the crop is not resized, else the
+// fixed-point bilinear sample.
+__device__ __forceinline__ void letterbox_sample(const uint8_t* __restrict__ frame, int W, const LetterboxImg& L, int y, int x, int (&px)[3],
+                                                 int pad = 114) {
+  px[0] = px[1] = px[2] = pad;
   const int ry = y - L.top, rx = x - L.left;
   if (ry >= 0 && ry < L.new_h && rx >= 0 && rx < L.new_w) {
     const uint8_t* src = frame + ((size_t)L.y0 * W + L.x0) * 3;

@@ -6,13 +6,14 @@
 namespace ffp {
 
 // Dense convolution k in {1,3}, stride in {1,2}, pad k/2, as an implicit GEMM on MFMA (conv_mfma.hip).
-//   out = epilogue( conv(in) + bias ),   epilogue: act, then optional  v = v*s1 + res1,  v = v*s2 + res2
+//   out = epilogue( conv(in) + bias ),   epilogue: act, then optional  v = v*s1 + res1,  v = v*s2 + res2, then act_post
 // `up` = 1 reads the input through a nearest x2 upsample (ESRGAN conv_up1/2). Depthwise convs go to DwConvOp.
 struct ConvOp {
   const PackedConv* pc = nullptr;
   TView in, out;
   int stride = 1;
   int act = ACT_NONE;
+  int act_post = ACT_NONE;   // after the residual terms (ResNet BasicBlock: Relu(Add(conv, identity))); kernels that take no residual refuse it
   int up = 0;
   bool has_res1 = false, has_res2 = false;
   TView res1, res2;

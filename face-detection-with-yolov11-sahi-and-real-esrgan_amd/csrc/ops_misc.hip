@@ -13,6 +13,7 @@ template <typename T> __device__ __forceinline__ void stf(T* p, float v) { *p = 
 __device__ __forceinline__ float act_fn(float v, int act) {
   if (act == ACT_SILU) return v / (1.0f + expf(-v));
   if (act == ACT_LRELU) return v >= 0.f ? v : v * 0.2f;
+  if (act == ACT_RELU) return fmaxf(v, 0.f);
   return v;
 }
 
@@ -627,7 +628,7 @@ inline unsigned blocks_for(long long n, int bs) { return (unsigned)((n + bs - 1)
 
 bool conv_direct_eligible(const ConvOp& op) {
   const PackedConv& pc = *op.pc;
-  return pc.w_direct.p != nullptr && pc.k == 3 && !op.up && !op.has_res1 && !op.has_res2 && op.out.dt == pc.dt && op.in.coff == 0 &&
+  return pc.w_direct.p != nullptr && pc.k == 3 && !op.up && !op.has_res1 && !op.has_res2 && !op.act_post && op.out.dt == pc.dt && op.in.coff == 0 &&
          (pc.cout == 16 || pc.cout == 32 || pc.cout == 64) && op.out.cs % 4 == 0 && op.out.coff % 4 == 0 && op.in.cs == (pc.dt == F16 ? 8 : 4);
 }
 

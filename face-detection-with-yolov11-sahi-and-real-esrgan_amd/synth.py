@@ -106,3 +106,276 @@ def synthetic_frame(h: int, w: int, seed: int = 0, n_blobs: int = 48) -> np.ndar
         patch = img[y0:y1, x0:x1]
         patch[:] = patch * (1 - m) + (tone * (1 - 0.7 * eyes)) * m
     return np.clip(img * 255.0 + 0.5, 0, 255).astype(np.uint8)
+
+
+# ---- SCRFD (InsightFace det_*.onnx) ---------------------------------------------------------------------------------------------
+# A small ONNX writer (protobuf wire format, no onnx package) and an SCRFD-10G-KPS-shaped random graph: ResNet-v1e backbone (deep stem,
+# BasicBlock stages with avg_down shortcuts), PAFPN neck, per-stride head towers with a learned Scale on the bbox branch, InsightFace's
+# 9 outputs. BatchNorm statistics are calibrated on a synthetic frame while the graph is built (each conv's output comes out roughly
+# zero-mean, unit-variance), score biases so that ~1 % of anchors clear 0.5, bbox biases so that boxes are positive and overlap.
+
+def _pb_varint(v: int) -> bytes:
+    v &= (1 << 64) - 1
+    out = bytearray()
+    while True:
+        b = v & 0x7F
+        v >>= 7
+        if v:
+            out.append(b | 0x80)
+        else:
+            out.append(b)
+            return bytes(out)
+
+
+def _pb_key(field: int, wt: int) -> bytes:
+    return _pb_varint((field << 3) | wt)
+
+
+def _pb_bytes(field: int, data: bytes) -> bytes:
+    return _pb_key(field, 2) + _pb_varint(len(data)) + data
+
+
+def _pb_str(field: int, s: str) -> bytes:
+    return _pb_bytes(field, s.encode())
+
+
+def _pb_int(field: int, v: int) -> bytes:
+    return _pb_key(field, 0) + _pb_varint(int(v))
+
+
+def _pb_packed_ints(field: int, vals) -> bytes:
+    return _pb_bytes(field, b"".join(_pb_varint(int(v)) for v in vals))
+
+
+def onnx_tensor(name: str, a: np.ndarray, typed: bool = False) -> bytes:
+    """TensorProto: float32 / int64, raw_data (typed=True: float_data / int64_data)."""
+    a = np.asarray(a)
+    if a.dtype.kind == "f":
+        a = a.astype("<f4")
+        dt = 1
+    else:
+        a = a.astype("<i8")
+        dt = 7
+    out = _pb_packed_ints(1, a.shape) + _pb_int(2, dt) + _pb_str(8, name)
+    if typed:
+        out += _pb_bytes(4, a.tobytes()) if dt == 1 else _pb_packed_ints(7, a.ravel())
+    else:
+        out += _pb_bytes(9, a.tobytes())
+    return out
+
+
+def _onnx_attr(name: str, v) -> bytes:
+    out = _pb_str(1, name)
+    if isinstance(v, float):
+        return out + _pb_key(2, 5) + np.float32(v).tobytes() + _pb_int(20, 1)
+    if isinstance(v, (bool, int, np.integer)):
+        return out + _pb_int(3, int(v)) + _pb_int(20, 2)
+    if isinstance(v, str):
+        return out + _pb_bytes(4, v.encode()) + _pb_int(20, 3)
+    if isinstance(v, np.ndarray):
+        return out + _pb_bytes(5, onnx_tensor("", v)) + _pb_int(20, 4)
+    if isinstance(v, (list, tuple)) and v and all(isinstance(x, float) for x in v):
+        return out + _pb_bytes(7, np.asarray(v, "<f4").tobytes()) + _pb_int(20, 6)
+    return out + _pb_packed_ints(8, v) + _pb_int(20, 7)
+
+
+def _onnx_value_info(name: str, shape) -> bytes:
+    dims = b"".join(_pb_bytes(1, _pb_int(1, d) if isinstance(d, int) and d > 0 else _pb_str(2, str(d))) for d in shape)
+    ttype = _pb_int(1, 1) + _pb_bytes(2, dims)
+    return _pb_str(1, name) + _pb_bytes(2, _pb_bytes(1, ttype))
+
+
+def onnx_model(g: dict, opset: int = 11) -> bytes:
+    """ModelProto bytes of a graph dict {nodes: [{op, name, inputs, outputs, attrs}], init: {name: array}, input: (name, shape),
+    outputs: [(name, shape)]}."""
+    body = b""
+    for nd in g["nodes"]:
+        n = b"".join(_pb_str(1, s) for s in nd["inputs"]) + b"".join(_pb_str(2, s) for s in nd["outputs"])
+        n += _pb_str(3, nd["name"]) + _pb_str(4, nd["op"])
+        n += b"".join(_pb_bytes(5, _onnx_attr(k, v)) for k, v in nd.get("attrs", {}).items())
+        body += _pb_bytes(1, n)
+    body += _pb_str(2, g.get("name", "scrfd"))
+    for k, v in g["init"].items():
+        body += _pb_bytes(5, onnx_tensor(k, v, typed=k in g.get("typed", ())))
+    body += _pb_bytes(11, _onnx_value_info(*g["input"]))
+    for name, shape in g["outputs"]:
+        body += _pb_bytes(12, _onnx_value_info(name, shape))
+    opset_b = _pb_str(1, "") + _pb_int(2, opset)
+    return _pb_int(1, 7) + _pb_str(2, "ffp-synth") + _pb_bytes(8, opset_b) + _pb_bytes(7, body)
+
+
+def scrfd_onnx(seed: int = 0, style: str = "unfolded", stem: int = 28, widths=(56, 88, 88, 224), depths=(3, 4, 2, 3), neck: int = 56,
+               head: int = 80, stacked: int = 3, kps: bool = True, calib_size: int = 320, head_order: str = "batched"):
+    """-> (onnx_bytes, graph dict). style 'unfolded': BatchNormalization nodes, Resize sizes from Shape; 'folded': BN folded into
+    the convs, Resize with constant scales. head_order 'batched': Sigmoid -> Transpose(0,2,3,1) -> Reshape; 'export': the batch-1
+    export's Transpose(2,3,0,1) -> Reshape -> Sigmoid. The graph dict is what tests/scrfd_ref.py interprets (no protobuf library needed)."""
+    import torch
+    import torch.nn.functional as F
+    rng = np.random.default_rng(seed)
+    folded = style == "folded"
+    g = {"nodes": [], "init": {}, "input": ("input.1", ["None", 3, "?", "?"]), "outputs": [], "typed": set()}
+    cnt = [0]
+
+    def uid(p):
+        cnt[0] += 1
+        return f"{p}_{cnt[0]}"
+
+    def node(op, inputs, attrs=None, n_out=1):
+        name = uid(op)
+        outs = [f"{name}_out{i}" for i in range(n_out)]
+        g["nodes"].append({"op": op, "name": name, "inputs": list(inputs), "outputs": outs, "attrs": attrs or {}})
+        return outs[0] if n_out == 1 else outs
+
+    def init(name, a):
+        g["init"][name] = a
+        return name
+
+    # calibrated on picture-like input, as the tests feed: a frame and a x2-upscaled crop of it (slices are resized to the net size)
+    img = synthetic_frame(calib_size, calib_size, seed=seed + 1)
+    up = np.repeat(np.repeat(img[: calib_size // 2, : calib_size // 2], 2, 0), 2, 1)
+    x0 = ((np.stack([img, up]).astype(np.float32) - 127.5) / 128.0).transpose(0, 3, 1, 2).copy()
+    vals = {"input.1": torch.from_numpy(x0)}
+
+    def conv(x, cout, k=3, s=1, bn=True, relu=True, gamma=(0.8, 1.2), wstd=None):
+        t = vals[x]
+        cin = t.shape[1]
+        w = (rng.standard_normal((cout, cin, k, k)) * (wstd if wstd is not None else np.sqrt(2.0 / (cin * k * k)))).astype(np.float32)
+        y = F.conv2d(t, torch.from_numpy(w), None, s, k // 2)
+        b = np.zeros(cout, np.float32)
+        if bn:
+            m = y.mean(dim=(0, 2, 3)).numpy().astype(np.float32)
+            v = y.var(dim=(0, 2, 3)).numpy().astype(np.float32) + 1e-3
+            m = m + rng.normal(0, 0.05, cout).astype(np.float32) * np.sqrt(v)
+            ga = rng.uniform(*gamma, cout).astype(np.float32)
+            be = rng.normal(0, 0.1, cout).astype(np.float32)
+            eps = 1e-5
+            if folded:
+                sc = ga / np.sqrt(v + eps)
+                w = (w * sc[:, None, None, None]).astype(np.float32)
+                b = (be - m * sc).astype(np.float32)
+        else:
+            b = rng.normal(0, 0.1, cout).astype(np.float32)
+        ins = [x, init(uid("w"), w)]
+        if not (bn and not folded):
+            ins.append(init(uid("b"), b))
+        out = node("Conv", ins, {"kernel_shape": [k, k], "strides": [s, s], "pads": [k // 2] * 4, "dilations": [1, 1], "group": 1})
+        y = F.conv2d(t, torch.from_numpy(w), torch.from_numpy(b) if len(ins) == 3 else None, s, k // 2)
+        if bn and not folded:
+            out = node("BatchNormalization", [out, init(uid("g"), ga), init(uid("be"), be), init(uid("m"), m), init(uid("v"), v)], {"epsilon": eps})
+            y = F.batch_norm(y, torch.from_numpy(m), torch.from_numpy(v), torch.from_numpy(ga), torch.from_numpy(be), False, 0.0, eps)
+        vals[out] = y
+        if relu:
+            r = node("Relu", [out])
+            vals[r] = F.relu(y)
+            return r
+        return out
+
+    def add_relu(a, b):
+        o = node("Add", [a, b])
+        vals[o] = vals[a] + vals[b]
+        r = node("Relu", [o])
+        vals[r] = F.relu(vals[o])
+        return r
+
+    def basic_block(x, cout, s):
+        cin = vals[x].shape[1]
+        y = conv(x, cout, 3, s)
+        y = conv(y, cout, 3, 1, relu=False, gamma=(0.2, 0.4))
+        idt = x
+        if s != 1 or cin != cout:
+            if s != 1:
+                idt = node("AveragePool", [x], {"kernel_shape": [s, s], "strides": [s, s], "ceil_mode": 1, "count_include_pad": 0})
+                vals[idt] = F.avg_pool2d(vals[x], s, s, ceil_mode=True, count_include_pad=False)
+            idt = conv(idt, cout, 1, 1, relu=False)
+        return add_relu(y, idt)
+
+    def up2(x, like):
+        if folded:
+            sc = init(uid("scales"), np.array([1.0, 1.0, 2.0, 2.0], np.float32))
+            o = node("Resize", [x, "", sc], {"mode": "nearest", "coordinate_transformation_mode": "asymmetric", "nearest_mode": "floor"})
+        else:
+            sh = node("Shape", [like])
+            st = init(uid("st"), np.array([2], np.int64))
+            en = init(uid("en"), np.array([4], np.int64))
+            hw = node("Slice", [sh, st, en])
+            shx = node("Shape", [x])
+            st0 = init(uid("st"), np.array([0], np.int64))
+            en0 = init(uid("en"), np.array([2], np.int64))
+            nc = node("Slice", [shx, st0, en0])
+            sizes = node("Concat", [nc, hw], {"axis": 0})
+            o = node("Resize", [x, "", "", sizes], {"mode": "nearest", "coordinate_transformation_mode": "asymmetric", "nearest_mode": "floor"})
+        vals[o] = F.interpolate(vals[x], scale_factor=2, mode="nearest")
+        return o
+
+    # ---- backbone
+    x = conv("input.1", stem, 3, 2)
+    x = conv(x, stem, 3, 1)
+    x = conv(x, 2 * stem, 3, 1)
+    mp = node("MaxPool", [x], {"kernel_shape": [3, 3], "strides": [2, 2], "pads": [1, 1, 1, 1]})
+    vals[mp] = F.max_pool2d(vals[x], 3, 2, 1)
+    x = mp
+    feats = []
+    for si, (c, d) in enumerate(zip(widths, depths)):
+        for bi in range(d):
+            x = basic_block(x, c, 2 if (si > 0 and bi == 0) else 1)
+        feats.append(x)
+    c2, c3, c4 = feats[1], feats[2], feats[3]
+    # ---- PAFPN
+    lat = [conv(f, neck, 1, 1, bn=False, relu=False, wstd=1.0 / np.sqrt(vals[f].shape[1])) for f in (c2, c3, c4)]
+    for i in (2, 1):
+        u = up2(lat[i], lat[i - 1])
+        o = node("Add", [lat[i - 1], u])
+        vals[o] = vals[lat[i - 1]] + vals[u]
+        lat[i - 1] = o
+    outs = [conv(l, neck, 3, 1, bn=False, relu=False, wstd=1.0 / np.sqrt(9 * neck)) for l in lat]
+    for i in (0, 1):
+        dn = conv(outs[i], neck, 3, 2, bn=False, relu=False, wstd=1.0 / np.sqrt(9 * neck))
+        o = node("Add", [outs[i + 1], dn])
+        vals[o] = vals[outs[i + 1]] + vals[dn]
+        outs[i + 1] = o
+    outs = [outs[0]] + [conv(o, neck, 3, 1, bn=False, relu=False, wstd=1.0 / np.sqrt(9 * neck)) for o in outs[1:]]
+    # ---- heads
+    scores, bboxes, kpss = [], [], []
+    A = 2
+    for li, f in enumerate(outs):
+        t = f
+        for _ in range(stacked):
+            t = conv(t, head, 3, 1)
+        # score: calibrated so that ~1 % of the anchors clear 0.5
+        # logits rescaled to std 0.3 (scores stay far from saturation on other inputs too: no exact ties at 1.0)
+        cls = conv(t, A, 3, 1, bn=False, relu=False, wstd=1.0 / np.sqrt(9 * head))
+        wname, bname = g["nodes"][-1]["inputs"][1], g["nodes"][-1]["inputs"][2]
+        lg = vals[cls].numpy() - g["init"][bname][None, :, None, None]
+        k = np.float32(0.3 / max(float(lg.std()), 1e-6))
+        g["init"][wname] = (g["init"][wname] * k).astype(np.float32)
+        lg = lg * k
+        q = float(np.quantile(lg, 0.99))
+        g["init"][bname] = np.full(A, -q, np.float32)
+        vals[cls] = torch.from_numpy((lg - q).astype(np.float32))
+
+        def layout(x, width, sigmoid=False):
+            if head_order == "export":
+                tr = node("Transpose", [x], {"perm": [2, 3, 0, 1]})
+                r = node("Reshape", [tr, init(uid("shape"), np.array([-1, width], np.int64))])
+                return node("Sigmoid", [r]) if sigmoid else r
+            if sigmoid:
+                x = node("Sigmoid", [x])
+            tr = node("Transpose", [x], {"perm": [0, 2, 3, 1]})
+            return node("Reshape", [tr, init(uid("shape"), np.array([-1, width], np.int64))])
+
+        scores.append(layout(cls, 1, sigmoid=True))
+        # bbox: positive distances of a few strides (overlapping boxes), then the learned Scale
+        reg = conv(t, 4 * A, 3, 1, bn=False, relu=False, wstd=0.3 / np.sqrt(9 * head))
+        wname, bname = g["nodes"][-1]["inputs"][1], g["nodes"][-1]["inputs"][2]
+        dv = vals[reg].numpy() - g["init"][bname][None, :, None, None]
+        g["init"][wname] = (g["init"][wname] * np.float32(0.05 / max(float(dv.std()), 1e-6))).astype(np.float32)    # distances stay positive
+        g["init"][bname] = rng.uniform(2.0, 3.0, 4 * A).astype(np.float32)
+        scale = np.array(rng.uniform(0.8, 1.2), np.float32).reshape(())
+        ms = node("Mul", [reg, init(uid("scale"), scale)])
+        bboxes.append(layout(ms, 4))
+        if kps:
+            kp = conv(t, 10 * A, 3, 1, bn=False, relu=False, wstd=0.3 / np.sqrt(9 * head))
+            kpss.append(layout(kp, 10))
+    for nm, w in [(s, 1) for s in scores] + [(b, 4) for b in bboxes] + [(k, 10) for k in kpss]:
+        g["outputs"].append((nm, ["?", w]))
+    return onnx_model(g), g

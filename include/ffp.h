@@ -388,6 +388,49 @@ int ffp_conv_totals_get(int i, char* name, int name_cap, double* out_flops, doub
 int ffp_det_profile_detail(ffp_det* d, int i, char* name, int name_cap, double* out_flops, float* out_ms);
 int ffp_sr_profile_detail(ffp_sr* s, int i, char* name, int name_cap, double* out_flops, float* out_ms);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * face detector of InsightFace's model packs (SCRFD, e.g. buffalo_l/det_10g.onnx) — replaces
+ * insightface.model_zoo.retinaface.RetinaFace (prepare / detect / nms, insightface 0.7.3 model_zoo/retinaface.py), reached
+ * through insightface.app.FaceAnalysis.get (app/face_analysis.py) behind utils/insightface_wrapper.py's InsightFaceDetectionModel
+ * ------------------------------------------------------------------------------------------------------- */
+typedef struct ffp_scrfd ffp_scrfd;
+
+/* onnx_bytes: the ONNX model file (self-contained; external data is refused). The graph is lowered to the supported op subset
+ * (see ffp_scrfd_describe); anything outside it fails with FFP_ERR_ARG and a message naming the node, its op and attribute.
+ * n: the batch the graph is checked at on creation (plans themselves are laid out per call shape, for any batch).
+ * precision: FFP_PREC_F32 or FFP_PREC_F32X3.
+ * (RetinaFace.__init__ + prepare, model_zoo/retinaface.py) */
+int ffp_scrfd_create(const void* onnx_bytes, size_t nbytes, int n, int device, int precision, ffp_scrfd** out);
+void ffp_scrfd_destroy(ffp_scrfd* s);
+
+/* Host only, no device needed: the lowered step list of the model for batch n at net size det_w x det_h, one line per step,
+ * then one line per graph output; or the refusal message (returned as the error, and written to out as well).
+ * out: NUL-terminated, truncated to cap bytes. */
+int ffp_scrfd_describe(const void* onnx_bytes, size_t nbytes, int n, int det_w, int det_h, char* out, size_t cap);
+
+/* RetinaFace.detect(img, input_size=(det_w, det_h), max_num=0) over n_tiles crops of one HxWx3 uint8 frame, batched:
+ * per crop the resize into the top-left of the net size (det_scale = new_h / h), blobFromImage((v - 127.5) / 128, swapRB),
+ * the network, scores >= det_thresh, distance2bbox / distance2kps, / det_scale, NMS at nms_thresh (areas with +1, kept when
+ * overlap <= nms_thresh; equal scores in ascending anchor order).
+ * out_dets: [n_tiles][cap][FFP_DET_STRIDE(5)] rows x1,y1,x2,y2,score,0, then 5 x (x, y, 1.0); crop-local floats, not truncated.
+ * out_counts[n_tiles]: faces kept per crop, NOT capped; the call returns FFP_ERR_ARG when any exceeds cap.
+ * chan_order as for the YOLO detector: SAHI hands RGB arrays and swapRB flips them, so FFP_CHAN_AS_BGR reproduces the reference.
+ * A crop that resizes to zero width or height (cv2.resize raises there) returns FFP_ERR_ARG. */
+int ffp_scrfd_infer_tiles(ffp_scrfd* s, const uint8_t* frame_hwc, int H, int W, int chan_order, const int32_t* tiles_xyxy,
+                          int n_tiles, int det_w, int det_h, float det_thresh, float nms_thresh, float* out_dets, int cap,
+                          int32_t* out_counts);
+
+/* The graph outputs of every crop (net_outs of RetinaFace.forward), for parity tests: per crop, per output in file order,
+ * anchors x values floats in the graph's (Transpose + Reshape) order; scores are the sigmoid values the decode thresholds.
+ * out_sizes[n_outputs]: floats per crop of each output. */
+int ffp_scrfd_forward_raw(ffp_scrfd* s, const uint8_t* frame_hwc, int H, int W, int chan_order, const int32_t* tiles_xyxy,
+                          int n_tiles, int det_w, int det_h, float* out, size_t cap, int64_t* out_sizes);
+/* RetinaFace.detect's resize geometry of one h x w crop at net size net_w x net_h, host only:
+ * out2 = {new_w, new_h} (either may be 0: such a crop is refused by ffp_scrfd_infer_tiles), *det_scale = float32(new_h / h). */
+int ffp_scrfd_geometry(int h, int w, int net_w, int net_h, int32_t* out2, float* det_scale);
+/* number of graph outputs (9 with keypoints, 6 without) and the FLOPs of the convs of the last call's plan */
+int ffp_scrfd_info(ffp_scrfd* s, int32_t* out_n_outputs, double* out_last_conv_flops);
+
 #ifdef __cplusplus
 }
 #endif
