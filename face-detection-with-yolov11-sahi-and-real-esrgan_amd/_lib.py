@@ -137,6 +137,14 @@ _SIGS = {
                                         C.c_size_t, _p(C.c_int64)]),
     "ffp_scrfd_info": (C.c_int, [C.c_void_p, _p(C.c_int32), _p(C.c_double)]),
     "ffp_scrfd_geometry": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_int32), _p(C.c_float)]),
+    "ffp_rtdetr_create": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, _p(C.c_void_p)]),
+    "ffp_rtdetr_destroy": (None, [C.c_void_p]),
+    "ffp_rtdetr_predict": (C.c_int, [C.c_void_p, _p(C.c_void_p), _p(C.c_int32), C.c_int, C.c_int, C.c_float, _p(C.c_float), _p(C.c_int32)]),
+    "ffp_rtdetr_forward_raw": (C.c_int, [C.c_void_p, _p(C.c_void_p), _p(C.c_int32), C.c_int, C.c_int, _p(C.c_float), _p(C.c_int32)]),
+    "ffp_rtdetr_info": (C.c_int, [C.c_void_p, _p(C.c_int32), _p(C.c_double), _p(C.c_int32)]),
+    "ffp_rtdetr_set_profile": (C.c_int, [C.c_void_p, C.c_int]),
+    "ffp_rtdetr_profile_count": (C.c_int, [C.c_void_p, _p(C.c_int32)]),
+    "ffp_rtdetr_profile_get": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_int, _p(C.c_float)]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -311,6 +319,79 @@ class FaceDetector:
                 o += m
             res.append(outs)
         return res
+
+
+class RTDETRDetector:
+    """Ultralytics RT-DETR-l (rtdetr-l.yaml) on one GPU (ffp_rtdetr_*): FFPW weights from weights_io.from_ultralytics_rtdetr_state_dict
+    (or synth.rtdetr_l_weights), a path to them, or the tensors as a dict."""
+
+    NQ = 300
+
+    def __init__(self, weights, device: int = 0, precision: int = PREC_F32):
+        buf = _weights_bytes(weights)
+        self._h = C.c_void_p()
+        self.device, self.precision = device, precision
+        cbuf = C.create_string_buffer(buf, len(buf))
+        _check(lib().ffp_rtdetr_create(cbuf, len(buf), device, precision, C.byref(self._h)))
+        nc = C.c_int32(0)
+        _check(lib().ffp_rtdetr_info(self._h, C.byref(nc), None, None))
+        self.nc = int(nc.value)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            lib().ffp_rtdetr_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self) -> dict:
+        f, g = C.c_double(0), C.c_int32(0)
+        _check(lib().ffp_rtdetr_info(self._h, None, C.byref(f), C.byref(g)))
+        return {"nc": self.nc, "conv_flops": float(f.value), "graph_state": int(g.value)}
+
+    def profile(self, images: Sequence[np.ndarray], imgsz: int = 640, conf: float = 0.25) -> List[Tuple[str, float]]:
+        """One eager predict() with HIP events around every launch: [("<kernel> <layer>", ms)] in launch order."""
+        _check(lib().ffp_rtdetr_set_profile(self._h, 1))
+        try:
+            self.predict(images, imgsz, conf)
+        finally:
+            _check(lib().ffp_rtdetr_set_profile(self._h, 0))
+        n = C.c_int32(0)
+        _check(lib().ffp_rtdetr_profile_count(self._h, C.byref(n)))
+        out, name, ms = [], C.create_string_buffer(256), C.c_float(0)
+        for i in range(n.value):
+            _check(lib().ffp_rtdetr_profile_get(self._h, i, name, len(name), C.byref(ms)))
+            out.append((name.value.decode(), float(ms.value)))
+        return out
+
+    @staticmethod
+    def _batch(images):
+        ims = [_as_frame(im) for im in images]
+        ptrs = (C.c_void_p * len(ims))(*[im.ctypes.data for im in ims])
+        hw = np.ascontiguousarray(np.array([im.shape[:2] for im in ims], np.int32).reshape(-1))
+        return ims, ptrs, hw
+
+    def predict(self, images: Sequence[np.ndarray], imgsz: int = 640, conf: float = 0.25) -> List[np.ndarray]:
+        """BGR uint8 images -> per image (k, 6) float32 rows {x1, y1, x2, y2, score, cls} in original pixels, query order."""
+        ims, ptrs, hw = self._batch(images)
+        n = len(ims)
+        out = np.zeros((n, self.NQ, 6), np.float32)
+        counts = np.zeros(n, np.int32)
+        _check(lib().ffp_rtdetr_predict(self._h, ptrs, _ip(hw), n, imgsz, conf, _fp(out), _ip(counts)))
+        return [out[i, :counts[i]].copy() for i in range(n)]
+
+    def forward_raw(self, images: Sequence[np.ndarray], imgsz: int = 640) -> Tuple[np.ndarray, np.ndarray]:
+        """-> ([n, 300, 4 + nc] boxes cxcywh (normalised) ++ sigmoid scores, [n, 300] encoder token of every query)."""
+        ims, ptrs, hw = self._batch(images)
+        n = len(ims)
+        out = np.zeros((n, self.NQ, 4 + self.nc), np.float32)
+        topk = np.zeros((n, self.NQ), np.int32)
+        _check(lib().ffp_rtdetr_forward_raw(self._h, ptrs, _ip(hw), n, imgsz, _fp(out), _ip(topk)))
+        return out, topk
 
 
 class Detector:

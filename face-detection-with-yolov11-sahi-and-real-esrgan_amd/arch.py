@@ -211,3 +211,17 @@ def rrdbnet_convs(scale: int = 4, num_block: int = 23, num_feat: int = 64, num_g
     S.append(ConvSpec("conv_hr", num_feat, num_feat, 3))
     S.append(ConvSpec("conv_last", num_feat, num_out_ch, 3, act=False))
     return S
+
+
+# ---- RT-DETR-l (Ultralytics rtdetr-l.yaml) -------------------------------------------------------------------------------
+# backbone HGBlocks as (layer index, c1, cm, c2, k, light, shortcut); the DWConv(c, 3, 2, act=False) layers sit at 2, 4 and 8
+RTDETR_L_HGBLOCKS = [(1, 48, 48, 128, 3, False, False), (3, 128, 96, 512, 3, False, False), (5, 512, 192, 1024, 5, True, False),
+                     (6, 1024, 192, 1024, 5, True, True), (7, 1024, 192, 1024, 5, True, True), (9, 1024, 384, 2048, 5, True, False)]
+RTDETR_L_DWCONVS = [(2, 128), (4, 512), (8, 1024)]
+RTDETR_L_REPC3 = [16, 21, 24, 27]            # RepC3(512 -> 256, n=3, e=1): cv3 is the identity
+RTDETR_HD, RTDETR_NQ, RTDETR_HEADS, RTDETR_LEVELS, RTDETR_POINTS, RTDETR_LAYERS, RTDETR_FFN = 256, 300, 8, 3, 4, 6, 1024
+
+
+def rtdetr_nc_of(weights: Mapping[str, "np.ndarray"]) -> int:
+    """Class count of RT-DETR-l weights (fused or not): rows of the encoder score head."""
+    return int(weights["model.28.enc_score_head.weight"].shape[0])

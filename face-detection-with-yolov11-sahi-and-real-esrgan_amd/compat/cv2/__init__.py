@@ -2,7 +2,8 @@
 build): the image-file calls they make — `cv2.imread` for the image size (pipeline_v4_yolo/app_yolo_sahi.py:37-42),
 `cv2.imwrite` with `[cv2.IMWRITE_JPEG_QUALITY, q]` (utils/enhancer.py:273-278), `cv2.cvtColor` BGR<->RGB, `cv2.resize` —
 on Pillow + numpy, BGR arrays like OpenCV's. A real OpenCV further down sys.path always wins: this module then
-re-exports it untouched. Drawing primitives are not provided (utils.visualization of this build draws with Pillow).
+re-exports it untouched. Drawing: `cv2.rectangle` (pixel-exact for thickness 1, 2 and filled) and `cv2.putText` (through Pillow,
+not OpenCV's glyphs) for pipeline_v3_RTDETR/inference.py; utils.visualization of this build draws with Pillow.
 
 `.jpg` files go through this build's JPEG codec on the GPU (csrc/jpeg.hip: ffp_jpeg_decode / ffp_jpeg_encode) whenever a device is
 visible; its output is byte-identical (files) and pixel-identical (decoded arrays) to the libjpeg-turbo inside OpenCV and Pillow
@@ -134,6 +135,60 @@ else:
             return True
         except Exception:
             return False
+
+    FONT_HERSHEY_SIMPLEX, LINE_8, FILLED = 0, 8, -1
+
+    def _paint(img, y0, y1, x0, x1, color):
+        h, w = img.shape[:2]
+        y0, y1, x0, x1 = max(y0, 0), min(y1, h - 1), max(x0, 0), min(x1, w - 1)
+        if y0 <= y1 and x0 <= x1:
+            c = np.asarray(color, np.float64).reshape(-1)
+            img[y0:y1 + 1, x0:x1 + 1] = c[0] if img.ndim == 2 else np.resize(c, img.shape[2])[: img.shape[2]] if c.size < img.shape[2] else c[: img.shape[2]]
+
+    def rectangle(img, pt1, pt2, color, thickness=1, lineType=LINE_8, shift=0):
+        """Axis-aligned cv2.rectangle with LINE_8 and shift 0, in place, pixel for pixel as imgproc/drawing.cpp draws it:
+        thickness 1 is the one-pixel outline x1..x2 / y1..y2; thickness 2 is each edge as a filled polygon one pixel either side of
+        the edge (three-pixel bands spanning the edge's own length) plus a radius-1 filled circle (a plus) at every corner, so the
+        four outer diagonal corner pixels stay unpainted; thickness < 0 fills x1..x2 x y1..y2. Other thicknesses, anti-aliased lines
+        and sub-pixel shifts are not restated and raise NotImplementedError."""
+        if shift or lineType not in (LINE_8, 4, 8):
+            raise NotImplementedError("cv2 shim: rectangle with shift or anti-aliasing")
+        x1, x2 = sorted((int(pt1[0]), int(pt2[0])))
+        y1, y2 = sorted((int(pt1[1]), int(pt2[1])))
+        t = int(thickness)
+        if t < 0:
+            _paint(img, y1, y2, x1, x2, color)
+        elif t <= 1:
+            _paint(img, y1, y1, x1, x2, color); _paint(img, y2, y2, x1, x2, color)
+            _paint(img, y1, y2, x1, x1, color); _paint(img, y1, y2, x2, x2, color)
+        elif t == 2:
+            for y in (y1, y2):
+                _paint(img, y - 1, y + 1, x1, x2, color)
+            for x in (x1, x2):
+                _paint(img, y1, y2, x - 1, x + 1, color)
+            for (x, y) in ((x1, y1), (x2, y1), (x2, y2), (x1, y2)):
+                _paint(img, y, y, x - 1, x + 1, color); _paint(img, y - 1, y + 1, x, x, color)
+        else:
+            raise NotImplementedError(f"cv2 shim: rectangle thickness {t} (1, 2 and filled are provided)")
+        return img
+
+    def putText(img, text, org, fontFace, fontScale, color, thickness=1, lineType=LINE_8, bottomLeftOrigin=False):
+        """Text through Pillow, in place: NOT OpenCV's Hershey glyphs, so the pixels differ from cv2.putText's. DejaVu Sans (Pillow's
+        built-in font when it is missing) at about the cap height FONT_HERSHEY_SIMPLEX has at fontScale (22 * fontScale px), with `org`
+        the left end of the baseline as in OpenCV; `thickness` widens the strokes."""
+        from PIL import ImageDraw, ImageFont
+        size = max(int(round(22 * float(fontScale))), 6)
+        try:
+            font = ImageFont.truetype("DejaVuSans.ttf", size)
+        except OSError:
+            font = ImageFont.load_default()
+        a = np.ascontiguousarray(img)
+        pil = Image.fromarray(a)
+        c = tuple(int(v) for v in np.asarray(color).reshape(-1)[: (1 if a.ndim == 2 else a.shape[2])])
+        ImageDraw.Draw(pil).text((int(org[0]), int(org[1])), str(text), fill=c[0] if a.ndim == 2 else c, font=font, anchor="ls",
+                                 stroke_width=max(int(thickness) - 1, 0), stroke_fill=c[0] if a.ndim == 2 else c)
+        img[...] = np.asarray(pil)
+        return img
 
     def cvtColor(img, code):
         if code != COLOR_BGR2RGB:

@@ -9,6 +9,7 @@
 #include "jpeg.hpp"
 #include "sr_ops.hpp"
 #include "scrfd.hpp"
+#include "rtdetr.hpp"
 #include "yolo11.hpp"
 
 namespace ffp {
@@ -16,6 +17,7 @@ const std::string& last_error();
 }
 
 struct ffp_det { ffp::DetEngine eng; ffp_det(const void* w, size_t n, int a, int nc, int nk, int dev, int pr) : eng(w, n, a, nc, nk, dev, pr) {} };
+struct ffp_rtdetr { ffp::RtdetrEngine eng; ffp_rtdetr(const void* b, size_t nb, int dev, int pr) : eng(b, nb, dev, pr) {} };
 struct ffp_scrfd { ffp::ScrfdEngine eng; ffp_scrfd(const void* b, size_t nb, int n, int dev, int pr) : eng(b, nb, n, dev, pr) {} };
 struct ffp_sr { ffp::SrEngine eng; ffp_sr(const void* w, size_t n, int s, int nb, int dev, int h) : eng(w, n, s, nb, dev, h) {} };
 
@@ -1189,6 +1191,67 @@ int ffp_scrfd_info(ffp_scrfd* s, int32_t* out_n_outputs, double* out_last_conv_f
   FFP_CHECK(s, FFP_ERR_ARG, "null handle");
   if (out_n_outputs) *out_n_outputs = s->eng.n_outputs();
   if (out_last_conv_flops) *out_last_conv_flops = s->eng.last_conv_flops;
+  FFP_API_END
+}
+
+// ---- RT-DETR-l (ultralytics.RTDETR, pipeline_v3_RTDETR/inference.py) -----------------------------------------------------------
+
+int ffp_rtdetr_create(const void* weights, size_t nbytes, int device, int precision, ffp_rtdetr** out) {
+  FFP_API_BEGIN
+  FFP_CHECK(out && weights && nbytes > 0, FFP_ERR_ARG, "null argument");
+  *out = new ffp_rtdetr(weights, nbytes, device, precision);
+  FFP_API_END
+}
+
+void ffp_rtdetr_destroy(ffp_rtdetr* r) { delete r; }
+
+int ffp_rtdetr_predict(ffp_rtdetr* r, const uint8_t* const* frames, const int32_t* hw, int n, int imgsz, float conf, float* out_dets,
+                       int32_t* out_counts) {
+  FFP_API_BEGIN
+  FFP_CHECK(r && frames && hw && out_dets && out_counts, FFP_ERR_ARG, "null argument");
+  r->eng.predict(frames, hw, n, imgsz, conf, out_dets, out_counts);
+  FFP_API_END
+}
+
+int ffp_rtdetr_forward_raw(ffp_rtdetr* r, const uint8_t* const* frames, const int32_t* hw, int n, int imgsz, float* out, int32_t* out_topk) {
+  FFP_API_BEGIN
+  FFP_CHECK(r && frames && hw && out, FFP_ERR_ARG, "null argument");
+  r->eng.forward_raw(frames, hw, n, imgsz, out, out_topk);
+  FFP_API_END
+}
+
+int ffp_rtdetr_set_profile(ffp_rtdetr* r, int on) {
+  FFP_API_BEGIN
+  FFP_CHECK(r, FFP_ERR_ARG, "null handle");
+  r->eng.profile = on != 0;
+  FFP_API_END
+}
+
+int ffp_rtdetr_profile_count(ffp_rtdetr* r, int32_t* out_n) {
+  FFP_API_BEGIN
+  FFP_CHECK(r && out_n, FFP_ERR_ARG, "null argument");
+  *out_n = (int32_t)r->eng.profile_ms.size();
+  FFP_API_END
+}
+
+int ffp_rtdetr_profile_get(ffp_rtdetr* r, int i, char* name, int name_cap, float* out_ms) {
+  FFP_API_BEGIN
+  FFP_CHECK(r && name && name_cap > 0 && out_ms, FFP_ERR_ARG, "null argument");
+  FFP_CHECK(i >= 0 && i < (int)r->eng.profile_ms.size(), FFP_ERR_ARG, "profile entry %d of %d", i, (int)r->eng.profile_ms.size());
+  const auto& e = r->eng.profile_ms[i];
+  const size_t k = std::min(e.first.size(), (size_t)name_cap - 1);
+  std::memcpy(name, e.first.data(), k);
+  name[k] = 0;
+  *out_ms = e.second;
+  FFP_API_END
+}
+
+int ffp_rtdetr_info(ffp_rtdetr* r, int32_t* out_nc, double* out_last_conv_flops, int32_t* out_graph_state) {
+  FFP_API_BEGIN
+  FFP_CHECK(r, FFP_ERR_ARG, "null handle");
+  if (out_nc) *out_nc = r->eng.nc();
+  if (out_last_conv_flops) *out_last_conv_flops = r->eng.last_conv_flops;
+  if (out_graph_state) *out_graph_state = r->eng.last_graph_state;
   FFP_API_END
 }
 

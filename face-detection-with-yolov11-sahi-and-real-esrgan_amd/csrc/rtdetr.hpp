@@ -1,0 +1,81 @@
+// rtdetr.hpp — Ultralytics RT-DETR-l (rtdetr-l.yaml, eval path) as a plan of HIP launches: every conv and every Linear over tokens on the
+// shared conv kernels, everything else (LayerNorm, softmax, attention, top-k, deformable sampling) in rtdetr_ops.hip, fp32.
+#pragma once
+#include "engine.hpp"
+
+namespace ffp {
+
+constexpr int RT_NQ = 300;
+
+// the three encoder levels: per-image token ranges [start[l], start[l + 1]) of [P3 | P4 | P5], their sizes and (enc_prep only) the
+// input_proj outputs they are flattened from
+struct RtLevels {
+  int start[4];
+  int h[3], w[3];
+  const float* src[3];
+  int src_cs[3];
+};
+
+void launch_rt_dwconv(const TView& in, const TView& out, const float* w, const float* b, int k, int s, int act, hipStream_t st);
+void launch_rt_maxpool2(const TView& in, const TView& out, hipStream_t st);
+void launch_rt_add(const TView& a, const float* b, int b_cs, long long period, const TView& out, hipStream_t st);
+void launch_rt_layernorm(const TView& x, const float* gamma, const float* beta, const TView& out, hipStream_t st);
+void launch_rt_gelu(const TView& x, hipStream_t st);
+void launch_rt_attention(const TView& qk, const TView& v, const TView& out, int L, hipStream_t st);
+void launch_rt_enc_prep(const RtLevels& lv, const float* valid, const TView& t, const TView& tm, int n, hipStream_t st);
+void launch_rt_topk(const TView& s, int nc, int NT, int n, unsigned* keys, int* idx, hipStream_t st);
+void launch_rt_gather(const TView& e, const int* idx, const float* anchors, int NT, int n, const TView& q, float* anc, hipStream_t st);
+void launch_rt_ref(const TView& delta, const float* anc, const TView& ref, hipStream_t st);
+void launch_rt_deform(const TView& val, const TView& oa, const TView& ref, const RtLevels& lv, const TView& out, hipStream_t st);
+void launch_rt_raw(const TView& ref, const TView& s, int nc, float* raw, hipStream_t st);
+void launch_rt_post(const TView& ref, const TView& s, int nc, float conf, const float2* orig_wh, int n, float* det, int* counts, hipStream_t st);
+
+// host tables, constant per imgsz (RTDETRDecoder._generate_anchors, AIFI.build_2d_sincos_position_embedding)
+void rtdetr_anchors(int imgsz, std::vector<float>& anchors, std::vector<float>& valid);
+void rtdetr_pos_embed(int w, int h, std::vector<float>& pos);
+
+struct RtdetrPlan : Plan {
+  int n = 0, imgsz = 0, NT = 0;
+  void add_named(const std::string& name, std::function<void(hipStream_t)> f) { add(std::move(f)); steps.back().name = name; }
+  unsigned long long last_use = 0;
+  TView input, ref, scores;
+  DevBuf d_lb, d_wh, d_anchors, d_valid, d_pos, d_keys, d_idx, d_anc, d_raw, d_det, d_counts;
+};
+
+class RtdetrEngine {
+ public:
+  RtdetrEngine(const void* weights, size_t nbytes, int device, int precision);
+  ~RtdetrEngine();
+  int nc() const { return nc_; }
+  // images: n host BGR u8 frames (sizes may differ); out: [n][300][6] {x1, y1, x2, y2, score, cls} in original pixels, counts[n]
+  void predict(const uint8_t* const* frames, const int32_t* hw, int n, int imgsz, float conf, float* out, int32_t* counts);
+  // out: [n][300][4 + nc] {cx, cy, w, h (normalised), sigmoid scores}; topk (may be null): [n][300] encoder token of every query
+  void forward_raw(const uint8_t* const* frames, const int32_t* hw, int n, int imgsz, float* out, int32_t* topk);
+  // profile: the next calls run their plan eagerly with a pair of events around every launch (no hipGraph); profile_ms holds the last call's
+  // {"<kernel> <layer>", ms} per launch in issue order
+  bool profile = false;
+  std::vector<std::pair<std::string, float>> profile_ms;
+  double last_conv_flops = 0;
+  int last_graph_state = 0;
+
+ private:
+  RtdetrPlan* prepare(const uint8_t* const* frames, const int32_t* hw, int n, int imgsz);
+  RtdetrPlan* plan_for(int n, int imgsz);
+  void build_plan(RtdetrPlan& P);
+  const PackedConv& conv(const std::string& name);           // packed once per engine
+  const HostTensor& t(const std::string& name) const { return wf_.get(name); }
+  const float* dev(const std::string& name);                  // fp32 copy on the device (LayerNorm parameters, depthwise weights)
+
+  std::vector<uint8_t> bytes_;
+  WeightFile wf_;
+  std::map<std::string, std::unique_ptr<PackedConv>> convs_;
+  std::map<std::string, DevBuf> dev_;
+  std::map<std::vector<int>, std::unique_ptr<RtdetrPlan>> plans_;
+  unsigned long long use_clock_ = 0;
+  int device_ = 0, nc_ = 0;
+  bool split_ = false;
+  hipStream_t st_ = nullptr;
+  DevBuf frame_;
+};
+
+}  // namespace ffp

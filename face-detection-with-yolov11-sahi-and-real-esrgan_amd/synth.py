@@ -379,3 +379,126 @@ def scrfd_onnx(seed: int = 0, style: str = "unfolded", stem: int = 28, widths=(5
     for nm, w in [(s, 1) for s in scores] + [(b, 4) for b in bboxes] + [(k, 10) for k in kpss]:
         g["outputs"].append((nm, ["?", w]))
     return onnx_model(g), g
+
+
+# ---- RT-DETR-l ----------------------------------------------------------------------------------------------------------------
+def rtdetr_l_state_dict(nc: int = 1, seed: int = 0, calibrated: bool = True) -> Dict[str, np.ndarray]:
+    """An unfused Ultralytics RT-DETR-l state dict (the key names and shapes of `RTDETR('rtdetr-l.pt').model.state_dict()`) with
+    random tensors: He-style conv weights under near-identity BatchNorm statistics (eps 1e-3), unit LayerNorms, and heads
+    calibrated so that a synthetic frame gives encoder / decoder logits spread around sigmoid^-1(0.25) (tens of detections per
+    image at conf 0.25, a clear gap at the 300th encoder score) and boxes that stay near their anchors."""
+    rng = np.random.default_rng(seed + 7000)
+    sd: Dict[str, np.ndarray] = {}
+    f32 = lambda a: np.asarray(a, np.float32)
+
+    def conv(p, c1, c2, k, g=1, gain=np.sqrt(2.0)):
+        sd[p + ".conv.weight"] = f32(rng.standard_normal((c2, c1 // g, k, k)) * gain / np.sqrt(c1 // g * k * k))
+        sd[p + ".bn.weight"] = f32(rng.uniform(0.8, 1.2, c2))
+        sd[p + ".bn.bias"] = f32(rng.normal(0, 0.05, c2))
+        sd[p + ".bn.running_mean"] = f32(rng.normal(0, 0.05, c2))
+        sd[p + ".bn.running_var"] = f32(rng.uniform(0.8, 1.2, c2))
+        sd[p + ".bn.num_batches_tracked"] = np.zeros((), np.float32)
+
+    def lin(p, c1, c2, gain=1.0, bias=0.02):
+        sd[p + ".weight"] = f32(rng.standard_normal((c2, c1)) * gain / np.sqrt(c1))
+        sd[p + ".bias"] = f32(rng.normal(0, bias, c2))
+
+    def ln(p, c):
+        sd[p + ".weight"] = f32(rng.uniform(0.9, 1.1, c))
+        sd[p + ".bias"] = f32(rng.normal(0, 0.02, c))
+
+    def mha(p, d):
+        sd[p + ".in_proj_weight"] = f32(rng.standard_normal((3 * d, d)) / np.sqrt(d))
+        sd[p + ".in_proj_bias"] = f32(rng.normal(0, 0.02, 3 * d))
+        lin(p + ".out_proj", d, d)
+
+    conv("model.0.stem1", 3, 32, 3)
+    conv("model.0.stem2a", 32, 16, 2)
+    conv("model.0.stem2b", 16, 32, 2)
+    conv("model.0.stem3", 64, 32, 3)
+    conv("model.0.stem4", 32, 48, 1)
+    for (li, c1, cm, c2, k, light, _sc) in arch.RTDETR_L_HGBLOCKS:
+        for i in range(6):
+            ci = c1 if i == 0 else cm
+            if light:
+                conv(f"model.{li}.m.{i}.conv1", ci, cm, 1, gain=1.0)
+                conv(f"model.{li}.m.{i}.conv2", cm, cm, k, g=cm)
+            else:
+                conv(f"model.{li}.m.{i}", ci, cm, k)
+        conv(f"model.{li}.sc", c1 + 6 * cm, c2 // 2, 1)
+        conv(f"model.{li}.ec", c2 // 2, c2, 1, gain=1.0)
+    for (li, c) in arch.RTDETR_L_DWCONVS:
+        conv(f"model.{li}", c, c, 3, g=c, gain=1.0)
+    hd = arch.RTDETR_HD
+    conv("model.10", 2048, hd, 1, gain=1.0)
+    mha("model.11.ma", hd)
+    lin("model.11.fc1", hd, 1024, gain=np.sqrt(2.0))
+    lin("model.11.fc2", 1024, hd)
+    ln("model.11.norm1", hd)
+    ln("model.11.norm2", hd)
+    conv("model.12", hd, hd, 1)
+    conv("model.14", 1024, hd, 1, gain=1.0)
+    conv("model.17", hd, hd, 1)
+    conv("model.19", 512, hd, 1, gain=1.0)
+    conv("model.22", hd, hd, 3)
+    conv("model.25", hd, hd, 3)
+    for li in arch.RTDETR_L_REPC3:
+        conv(f"model.{li}.cv1", 2 * hd, hd, 1)
+        conv(f"model.{li}.cv2", 2 * hd, hd, 1)
+        for j in range(3):
+            conv(f"model.{li}.m.{j}.conv1", hd, hd, 3, gain=1.0)
+            conv(f"model.{li}.m.{j}.conv2", hd, hd, 1, gain=0.5)
+    d = "model.28"
+    for i in range(3):
+        sd[f"{d}.input_proj.{i}.0.weight"] = f32(rng.standard_normal((hd, hd, 1, 1)) / np.sqrt(hd))
+        sd[f"{d}.input_proj.{i}.1.weight"] = f32(rng.uniform(0.8, 1.2, hd))
+        sd[f"{d}.input_proj.{i}.1.bias"] = f32(rng.normal(0, 0.05, hd))
+        sd[f"{d}.input_proj.{i}.1.running_mean"] = f32(rng.normal(0, 0.05, hd))
+        sd[f"{d}.input_proj.{i}.1.running_var"] = f32(rng.uniform(0.8, 1.2, hd))
+        sd[f"{d}.input_proj.{i}.1.num_batches_tracked"] = np.zeros((), np.float32)
+    sd[f"{d}.denoising_class_embed.weight"] = f32(rng.standard_normal((nc + 1, hd)))
+    lin(f"{d}.enc_output.0", hd, hd, bias=0.0)          # an invalid anchor's feature is LayerNorm(bias): keep it far below the top 300
+    sd[f"{d}.enc_output.0.bias"][:] = 0
+    ln(f"{d}.enc_output.1", hd)
+    sd[f"{d}.enc_output.1.bias"][:] = 0
+    for j, (a, b) in enumerate([(hd, hd), (hd, hd), (hd, 4)]):
+        lin(f"{d}.enc_bbox_head.layers.{j}", a, b, gain=np.sqrt(2.0) if j < 2 else 0.1)
+    lin(f"{d}.query_pos_head.layers.0", 4, 2 * hd, gain=np.sqrt(2.0) * 2)
+    lin(f"{d}.query_pos_head.layers.1", 2 * hd, hd)
+    L, H, P = arch.RTDETR_LEVELS, arch.RTDETR_HEADS, arch.RTDETR_POINTS
+    for i in range(arch.RTDETR_LAYERS):
+        p = f"{d}.decoder.layers.{i}"
+        mha(p + ".self_attn", hd)
+        ln(p + ".norm1", hd)
+        lin(p + ".cross_attn.sampling_offsets", hd, H * L * P * 2, gain=1.0, bias=0.5)
+        lin(p + ".cross_attn.attention_weights", hd, H * L * P, gain=1.0)
+        lin(p + ".cross_attn.value_proj", hd, hd)
+        lin(p + ".cross_attn.output_proj", hd, hd)
+        ln(p + ".norm2", hd)
+        lin(p + ".linear1", hd, arch.RTDETR_FFN, gain=np.sqrt(2.0))
+        lin(p + ".linear2", arch.RTDETR_FFN, hd)
+        ln(p + ".norm3", hd)
+        for j, (a, b) in enumerate([(hd, hd), (hd, hd), (hd, 4)]):
+            lin(f"{d}.dec_bbox_head.{i}.layers.{j}", a, b, gain=np.sqrt(2.0) if j < 2 else 0.1)
+    # class heads last, from their own stream: everything above does not depend on nc. The decoder's queries share a large common
+    # component (random weights, no training): the score head is scaled up and centred on the mean final query embedding measured
+    # on synthetic frames (synth_calib_rtdetr.json), so that logits spread about -1.1 with a std near 1.
+    rng = np.random.default_rng(seed + 7001)
+    cal = {}
+    if calibrated:
+        with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "synth_calib_rtdetr.json")) as f:
+            cal = json.load(f)
+    mean = np.asarray(cal.get(f"dec_mean_nc{nc}", cal.get("dec_mean_nc1")), np.float64) if calibrated else np.zeros(hd)
+    lin(f"{d}.enc_score_head", hd, nc, gain=1.0)
+    sd[f"{d}.enc_score_head.bias"][:] = -1.1
+    for i in range(arch.RTDETR_LAYERS):
+        w = rng.standard_normal((nc, hd)) * (12.0 if calibrated else 1.0) / np.sqrt(hd)
+        sd[f"{d}.dec_score_head.{i}.weight"] = f32(w)
+        sd[f"{d}.dec_score_head.{i}.bias"] = f32(-1.1 - w @ mean)
+    return sd
+
+
+def rtdetr_l_weights(nc: int = 1, seed: int = 0, calibrated: bool = True) -> Dict[str, np.ndarray]:
+    """rtdetr_l_state_dict through the checkpoint converter: the FFPW tensors ffp_rtdetr_create loads."""
+    from .weights_io import from_ultralytics_rtdetr_state_dict
+    return from_ultralytics_rtdetr_state_dict(rtdetr_l_state_dict(nc, seed, calibrated))

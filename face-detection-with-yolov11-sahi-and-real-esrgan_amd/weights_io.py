@@ -134,3 +134,76 @@ def from_ultralytics_state_dict(sd: Mapping[str, "np.ndarray"], bn_eps: float = 
                 continue
             out[k] = get(k).astype(np.float32)
     return out
+
+
+def from_ultralytics_rtdetr_state_dict(sd: Mapping[str, "np.ndarray"], bn_eps=1e-3, dtype=np.float32) -> Dict[str, np.ndarray]:
+    """Unfused Ultralytics RT-DETR-l state dict (`RTDETR('rtdetr-l.pt').model.state_dict()`) -> FFPW tensors the RT-DETR engine
+    loads (csrc/rtdetr.cpp). To be run where the checkpoint can be unpickled (needs `ultralytics`; not available offline).
+
+    - every Conv's BatchNorm, and the decoder's `input_proj.i.1` BatchNorm, folded into `<conv>.weight` / `<conv>.bias`; `bn_eps` is a
+      float or a {module prefix: eps} mapping of the checkpoint's modules (Ultralytics' initialize_weights sets 1e-3 on every BatchNorm2d)
+    - each RepConv (`conv1` 3x3 + `conv2` 1x1, both with BN, no identity branch) folded into one 3x3 `<repconv>.conv.{weight,bias}`
+    - `nn.MultiheadAttention.in_proj_{weight,bias}` split into `{q,k,v}_proj.{weight,bias}`
+    - training-only tensors (`denoising_class_embed`, `num_batches_tracked`) dropped.
+    `dtype` float64 keeps the folded tensors unrounded (to check the folding itself; FFPW files hold float32).
+
+    A state dict does not record BatchNorm eps. To fold with the eps the loaded modules actually carry, build the mapping from the model:
+
+        from ultralytics import RTDETR
+        m = RTDETR("best.pt").model
+        eps = {name: mod.eps for name, mod in m.named_modules() if isinstance(mod, torch.nn.BatchNorm2d)}
+        tensors = from_ultralytics_rtdetr_state_dict(m.state_dict(), bn_eps=eps)
+
+    (the keys are module prefixes such as "model.0.stem1.bn" or "model.28.input_proj.0.1"; a module missing from the mapping uses 1e-3)."""
+    get = lambda k: (sd[k].detach().cpu().numpy() if hasattr(sd[k], "detach") else np.asarray(sd[k])).astype(np.float64)
+
+    def eps_of(p):
+        return float(bn_eps.get(p, 1e-3)) if isinstance(bn_eps, Mapping) else float(bn_eps)
+
+    def fold(w, bnp, eps):
+        g, b = get(bnp + ".weight"), get(bnp + ".bias")
+        m, v = get(bnp + ".running_mean"), get(bnp + ".running_var")
+        s = g / np.sqrt(v + eps)
+        return w * s[:, None, None, None], b - m * s
+
+    out: Dict[str, np.ndarray] = {}
+    shp = lambda k: tuple(sd[k].shape)
+    rep = {k[: -len(".conv1.conv.weight")] for k in sd if k.endswith(".conv1.conv.weight") and k[: -len(".conv1.conv.weight")] + ".conv2.conv.weight" in sd
+           and shp(k)[2:] == (3, 3) and shp(k[: -len(".conv1.conv.weight")] + ".conv2.conv.weight") == shp(k)[:2] + (1, 1)}     # not LightConv
+    done = {k for k in sd for p in rep if k.startswith(p + ".conv2.")}
+    done |= {k for k in sd if ".input_proj." in k and k.rsplit(".", 2)[-2] == "1"}
+    for k in sd:
+        if k in done or k.endswith("num_batches_tracked") or ".denoising_class_embed." in k:
+            continue
+        if k.endswith(".conv1.conv.weight") and k[: -len(".conv1.conv.weight")] in rep:     # RepConv
+            p = k[: -len(".conv1.conv.weight")]
+            w3, b3 = fold(get(k), p + ".conv1.bn", eps_of(p + ".conv1.bn"))
+            w1, b1 = fold(get(p + ".conv2.conv.weight"), p + ".conv2.bn", eps_of(p + ".conv2.bn"))
+            w3 = w3.copy()
+            w3[:, :, 1:2, 1:2] += w1
+            out[p + ".conv.weight"] = w3.astype(dtype)
+            out[p + ".conv.bias"] = (b3 + b1).astype(dtype)
+            done.update(x for x in sd if x.startswith(p + ".conv1.") or x.startswith(p + ".conv2."))
+        elif k.endswith(".conv.weight") and k[: -len(".conv.weight")] + ".bn.weight" in sd:
+            p = k[: -len(".conv.weight")]
+            w, b = fold(get(k), p + ".bn", eps_of(p + ".bn"))
+            out[p + ".conv.weight"] = w.astype(dtype)
+            out[p + ".conv.bias"] = b.astype(dtype)
+            done.update(x for x in sd if x.startswith(p + ".bn."))
+        elif ".input_proj." in k and k.endswith(".0.weight"):                       # decoder input_proj: Conv2d(bias=False) + BN
+            p = k[: -len(".0.weight")]
+            w, b = fold(get(k), p + ".1", eps_of(p + ".1"))
+            out[p + ".0.weight"] = w.astype(dtype)
+            out[p + ".0.bias"] = b.astype(dtype)
+            done.update(x for x in sd if x.startswith(p + ".1."))
+        elif k.endswith(".in_proj_weight") or k.endswith(".in_proj_bias"):
+            p, kind = k.rsplit(".in_proj_", 1)
+            a = get(k)
+            d = a.shape[0] // 3
+            for i, nm in enumerate("qkv"):
+                out[f"{p}.{nm}_proj.{kind}"] = a[i * d:(i + 1) * d].astype(dtype)
+        elif ".bn." in k:
+            continue
+        else:
+            out[k] = get(k).astype(dtype)
+    return out

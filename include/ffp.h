@@ -431,6 +431,37 @@ int ffp_scrfd_geometry(int h, int w, int net_w, int net_h, int32_t* out2, float*
 /* number of graph outputs (9 with keypoints, 6 without) and the FLOPs of the convs of the last call's plan */
 int ffp_scrfd_info(ffp_scrfd* s, int32_t* out_n_outputs, double* out_last_conv_flops);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Ultralytics RT-DETR-l (rtdetr-l.yaml, fine-tuned at imgsz 640 by pipeline_v3_RTDETR/train_rtdetr.py:162,183) — replaces
+ * ultralytics.RTDETR (models/rtdetr/model.py, predict.py RTDETRPredictor, nn/modules/head.py RTDETRDecoder) as
+ * pipeline_v3_RTDETR/inference.py uses it
+ * ------------------------------------------------------------------------------------------------------- */
+typedef struct ffp_rtdetr ffp_rtdetr;
+
+/* weights: FFPW tensors from weights_io.from_ultralytics_rtdetr_state_dict (BatchNorm and RepConv folded, in_proj split); nc is read
+ * from the encoder score head. precision: FFP_PREC_F32 or FFP_PREC_F32X3. (self.model = RTDETR(weights_path), inference.py:20) */
+int ffp_rtdetr_create(const void* weights, size_t nbytes, int device, int precision, ffp_rtdetr** out);
+void ffp_rtdetr_destroy(ffp_rtdetr* r);
+/* RTDETRPredictor over n BGR uint8 images (frames[i]: hw[2i] x hw[2i+1] x 3, sizes may differ), one network batch at imgsz (a multiple
+ * of 32): LetterBox(auto=False, scale_fill=True) = a cv2 INTER_LINEAR stretch, BGR -> RGB, / 255; the model; postprocess: sigmoid
+ * scores, xywh -> xyxy, max over classes > conf, x * width, y * height, query order, no NMS (predict.py RTDETRPredictor.postprocess).
+ * out_dets: [n][300][6] {x1, y1, x2, y2, score, cls}; out_counts[n].
+ * (self.model.predict(source=image_path | frame, conf=self.conf, ...), inference.py:36-41 and 138-141, read back at :47-51) */
+int ffp_rtdetr_predict(ffp_rtdetr* r, const uint8_t* const* frames, const int32_t* hw, int n, int imgsz, float conf, float* out_dets,
+                       int32_t* out_counts);
+/* The model output of every image (RTDETRDecoder.forward in eval: dec_bboxes ++ sigmoid(dec_scores), what the predict calls of
+ * inference.py:36 post-process), for parity tests: out: [n][300][4 + nc] {cx, cy, w, h (normalised), scores};
+ * out_topk (may be NULL): [n][300] encoder token of each query. */
+int ffp_rtdetr_forward_raw(ffp_rtdetr* r, const uint8_t* const* frames, const int32_t* hw, int n, int imgsz, float* out, int32_t* out_topk);
+/* class count (result.names of inference.py), FLOPs of the convs of the last call's plan and its hipGraph state (1 replaying, 0 not
+ * captured yet, -1 eager) */
+int ffp_rtdetr_info(ffp_rtdetr* r, int32_t* out_nc, double* out_last_conv_flops, int32_t* out_graph_state);
+/* Profiling (no counterpart in the reference): with on != 0 later calls run their plan eagerly with HIP events around every launch;
+ * entry i of the last call is "<kernel> <layer>" and its milliseconds, in launch order (FFP_ERR_ARG past the end). */
+int ffp_rtdetr_set_profile(ffp_rtdetr* r, int on);
+int ffp_rtdetr_profile_count(ffp_rtdetr* r, int32_t* out_n);
+int ffp_rtdetr_profile_get(ffp_rtdetr* r, int i, char* name, int name_cap, float* out_ms);
+
 #ifdef __cplusplus
 }
 #endif
