@@ -127,6 +127,20 @@ _SIGS = {
                                      C.c_int, _p(C.c_float)]),
     "ffp_op_conv2d": (C.c_int, [C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_float), _p(C.c_float), C.c_int,
                                 C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_float), C.c_float, _p(C.c_float)]),
+    "ffp_op_variant": (C.c_int, [C.c_int, C.c_int]),
+    "ffp_op_sppf_pool": (C.c_int, [C.c_int, C.c_int, C.c_int, _p(C.c_int32), _p(C.c_int32), C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int,
+                                   _p(C.c_float), C.c_int, C.c_int, C.c_int, C.c_int]),
+    "ffp_op_upsample2x": (C.c_int, [C.c_int, C.c_int, C.c_int, _p(C.c_int32), _p(C.c_int32), C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int,
+                                    _p(C.c_float), C.c_int, C.c_int]),
+    "ffp_op_psa_attention": (C.c_int, [C.c_int, C.c_int, C.c_int, _p(C.c_int32), _p(C.c_int32), C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int,
+                                       _p(C.c_float), C.c_int, C.c_int]),
+    "ffp_op_dwconv3x3": (C.c_int, [C.c_int, C.c_int, C.c_int, _p(C.c_int32), _p(C.c_int32), C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int,
+                                   C.c_int, C.c_int, C.c_int, _p(C.c_float), _p(C.c_float), C.c_int, _p(C.c_float), C.c_int, C.c_int,
+                                   _p(C.c_float), C.c_int, C.c_int]),
+    "ffp_op_det_post": (C.c_int, [C.c_int, C.c_int, _p(C.c_int32), _p(C.c_int32), C.c_int, C.c_int, C.c_int, _p(C.c_float), _p(C.c_float),
+                                  _p(C.c_float), _p(C.c_float), _p(C.c_int32), C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                  _p(C.c_float), _p(C.c_float), _p(C.c_int32)]),
+    "ffp_op_rt_topk": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, _p(C.c_int32)]),
     "ffp_op_resize_lanczos4": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "ffp_scrfd_create": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, _p(C.c_void_p)]),
     "ffp_scrfd_destroy": (None, [C.c_void_p]),
@@ -712,6 +726,142 @@ def op_conv2d(x: np.ndarray, w: np.ndarray, b: Optional[np.ndarray], stride: int
     _check(lib().ffp_op_conv2d(device, precision, _fp(x), n, h, wd, cin, _fp(w), _fp(bb) if bb is not None else None, cout, k, stride,
                                groups, act, int(up), _fp(rr) if rr is not None else None, res_scale, _fp(y)))
     return y
+
+
+# ---- the detector's non-convolution kernels one at a time (tests/test_gpu_ops.py). A ragged batch is a list of (h, w, cs) arrays, one
+# per image, holding WHOLE pixel records; the operator reads / writes the channel slice the offsets name. Output buffers are passed in
+# (`y`, same list form) and come back with the slice written and every other value as it went in.
+OP_SPPF, OP_ATTENTION, OP_DWCONV = 0, 1, 2
+OP_VARIANTS = {OP_SPPF: {"lds": 1, "direct": 2}, OP_ATTENTION: {"mfma": 1, "valu": 2}, OP_DWCONV: {"col": 1, "strip": 2}}
+
+
+def op_variant(family: int, variant=0) -> None:
+    """Pin the kernel the following op_sppf_pool / op_psa_attention / op_dwconv3x3 calls launch (a name of OP_VARIANTS[family], or 0 / None
+    for the automatic choice)."""
+    v = OP_VARIANTS[family][variant] if isinstance(variant, str) else int(variant or 0)
+    _check(lib().ffp_op_variant(int(family), v))
+
+
+def _op_pack(imgs: Sequence[np.ndarray]):
+    imgs = [np.asarray(a, np.float32) for a in imgs]
+    if not imgs or any(a.ndim != 3 or a.shape[2] != imgs[0].shape[2] for a in imgs):
+        raise ValueError("a batch is a non-empty list of (h, w, cs) arrays with one record size")
+    hs = np.asarray([a.shape[0] for a in imgs], np.int32)
+    ws = np.asarray([a.shape[1] for a in imgs], np.int32)
+    cs = int(imgs[0].shape[2])
+    flat = np.ascontiguousarray(np.concatenate([a.reshape(-1, cs) for a in imgs], 0))
+    return flat, hs, ws, cs
+
+
+def _op_unpack(flat: np.ndarray, hs, ws) -> List[np.ndarray]:
+    out, p = [], 0
+    for h, w in zip(hs, ws):
+        out.append(flat[p:p + int(h) * int(w)].reshape(int(h), int(w), -1).copy())
+        p += int(h) * int(w)
+    return out
+
+
+def _op_same_batch(hs, ws, hs2, ws2, what):
+    if not (np.array_equal(hs, hs2) and np.array_equal(ws, ws2)):
+        raise ValueError(f"{what}: image sizes differ from the input's")
+
+
+def op_sppf_pool(x, c: int, x_coff: int, y, y_coffs, px_align: int = 1, precision: int = PREC_F32, device: int = 0) -> List[np.ndarray]:
+    """y[..., y_coffs[k] : y_coffs[k] + c] = (k+1) chained MaxPool2d(5, 1, 2) of x[..., x_coff : x_coff + c], k = 0..2."""
+    xf, hs, ws, xcs = _op_pack(x)
+    yf, hs2, ws2, ycs = _op_pack(y)
+    _op_same_batch(hs, ws, hs2, ws2, "sppf_pool")
+    o1, o2, o3 = (int(v) for v in y_coffs)
+    _check(lib().ffp_op_sppf_pool(device, precision, len(hs), _ip(hs), _ip(ws), px_align, c, _fp(xf), xcs, x_coff, _fp(yf), ycs, o1, o2, o3))
+    return _op_unpack(yf, hs, ws)
+
+
+def op_upsample2x(x, c: int, x_coff: int, y, y_coff: int, px_align: int = 1, precision: int = PREC_F32, device: int = 0) -> List[np.ndarray]:
+    """y[..., y_coff : y_coff + c] = nearest x2 of x[..., x_coff : x_coff + c]; the images of y are twice as high and wide."""
+    xf, hs, ws, xcs = _op_pack(x)
+    yf, hs2, ws2, ycs = _op_pack(y)
+    _op_same_batch(hs * 2, ws * 2, hs2, ws2, "upsample2x")
+    _check(lib().ffp_op_upsample2x(device, precision, len(hs), _ip(hs), _ip(ws), px_align, c, _fp(xf), xcs, x_coff, _fp(yf), ycs, y_coff))
+    return _op_unpack(yf, hs2, ws2)
+
+
+def op_psa_attention(qkv, nh: int, q_coff: int, out, o_coff: int, px_align: int = 1, precision: int = PREC_F32, device: int = 0) -> List[np.ndarray]:
+    """out[..., o_coff : o_coff + nh*64] = attention over each image's pixels of the nh heads [q(32) | k(32) | v(64)] at q_coff of qkv."""
+    qf, hs, ws, qcs = _op_pack(qkv)
+    of, hs2, ws2, ocs = _op_pack(out)
+    _op_same_batch(hs, ws, hs2, ws2, "psa_attention")
+    _check(lib().ffp_op_psa_attention(device, precision, len(hs), _ip(hs), _ip(ws), px_align, nh, _fp(qf), qcs, q_coff, _fp(of), ocs, o_coff))
+    return _op_unpack(of, hs, ws)
+
+
+def op_dwconv3x3(x, c: int, x_coff: int, w: np.ndarray, b: Optional[np.ndarray], y, y_coff: int, act: int = 0, grp: int = 0, grp_stride: int = 0,
+                 grp_off: int = 0, res=None, r_coff: int = 0, px_align: int = 1, precision: int = PREC_F32, device: int = 0) -> List[np.ndarray]:
+    """y[..., y_coff : y_coff + c] = act(depthwise3x3(x) + b) [+ res[..., r_coff : r_coff + c]]; w: (c, 3, 3). grp > 0: input channel ch is
+    x[..., x_coff + (ch // grp) * grp_stride + grp_off + ch % grp], else x[..., x_coff + ch]."""
+    xf, hs, ws, xcs = _op_pack(x)
+    yf, hs2, ws2, ycs = _op_pack(y)
+    _op_same_batch(hs, ws, hs2, ws2, "dwconv3x3")
+    w = np.ascontiguousarray(w, np.float32)
+    if w.shape != (c, 3, 3):
+        raise ValueError(f"dwconv3x3: weights {w.shape}, expected {(c, 3, 3)}")
+    bb = np.ascontiguousarray(b, np.float32) if b is not None else None
+    if bb is not None and bb.shape != (c,):
+        raise ValueError(f"dwconv3x3: bias {bb.shape}, expected {(c,)}")
+    rf, rcs = None, 0
+    if res is not None:
+        rf, hs3, ws3, rcs = _op_pack(res)
+        _op_same_batch(hs, ws, hs3, ws3, "dwconv3x3 residual")
+    _check(lib().ffp_op_dwconv3x3(device, precision, len(hs), _ip(hs), _ip(ws), px_align, c, _fp(xf), xcs, x_coff, grp, grp_stride, grp_off, _fp(w),
+                                  _fp(bb) if bb is not None else None, act, _fp(rf) if rf is not None else None, rcs, r_coff, _fp(yf), ycs, y_coff))
+    return _op_unpack(yf, hs, ws)
+
+
+def op_det_post(heads, nc: int, nkpt: int, geom, conf: float = 0.25, iou: float = 0.7, max_det: int = 300, round_boxes: bool = False,
+                shift: bool = False, full_hw: Tuple[int, int] = (0, 0), raw: bool = True, nms: bool = True, px_align: int = 1, device: int = 0):
+    """Pose-head post-processing of given head tensors. heads: per image a triple of (H/s, W/s, 64 + nc + 3*nkpt) arrays for s = 8, 16, 32;
+    geom: per image (gain, pad_x, pad_y, crop_w, crop_h, x0, y0). Returns (raws, dets, counts): raws[i] the (4 + nc + 3*nkpt, anchors)
+    inference-mode output (None when raw=False); dets (n, max_det, 6 + 3*nkpt) and counts (n,) after NMS (None when nms=False)."""
+    n = len(heads)
+    cs = 64 + nc + 3 * nkpt
+    lv = []
+    for l in range(3):
+        f, hs, ws, c = _op_pack([h[l] for h in heads])
+        if c != cs:
+            raise ValueError(f"det_post: head records of {c}, expected {cs}")
+        lv.append((f, hs, ws))
+    H, Wd = lv[0][1] * 8, lv[0][2] * 8
+    for l in (1, 2):
+        if not (np.array_equal(lv[l][1] * (8 << l), H) and np.array_equal(lv[l][2] * (8 << l), Wd)):
+            raise ValueError("det_post: the three levels must be the net input size over 8, 16 and 32")
+    g = np.asarray(geom, np.float64).reshape(n, 7)
+    gp = np.ascontiguousarray(g[:, :3], np.float32)
+    rc = np.ascontiguousarray(np.rint(g[:, 3:]), np.int32)
+    A = [int(sum(int(lv[l][1][i]) * int(lv[l][2][i]) for l in range(3))) for i in range(n)]
+    no, stride = 4 + nc + 3 * nkpt, 6 + 3 * nkpt
+    o_raw = np.zeros(no * sum(A), np.float32) if raw else None
+    o_dets = np.zeros((n, max_det, stride), np.float32) if nms else None
+    o_cnt = np.zeros(n, np.int32) if nms else None
+    _check(lib().ffp_op_det_post(device, n, _ip(np.ascontiguousarray(H, np.int32)), _ip(np.ascontiguousarray(Wd, np.int32)), px_align, nc, nkpt,
+                                 _fp(lv[0][0]), _fp(lv[1][0]), _fp(lv[2][0]), _fp(gp), _ip(rc), conf, iou, max_det, int(round_boxes), int(shift),
+                                 int(full_hw[0]), int(full_hw[1]), _fp(o_raw) if raw else None, _fp(o_dets) if nms else None,
+                                 _ip(o_cnt) if nms else None))
+    raws = None
+    if raw:
+        raws, p = [], 0
+        for a in A:
+            raws.append(o_raw[p:p + no * a].reshape(no, a).copy())
+            p += no * a
+    return raws, o_dets, o_cnt
+
+
+def op_rt_topk(scores: np.ndarray, nc: Optional[int] = None, s_coff: int = 0, device: int = 0) -> np.ndarray:
+    """scores (n, NT, cs) -> (n, 300) token indices by (max over the nc class logits at s_coff descending, index ascending)."""
+    s = np.ascontiguousarray(scores, np.float32)
+    n, nt, cs = s.shape
+    nc = cs - s_coff if nc is None else nc
+    out = np.zeros((n, 300), np.int32)
+    _check(lib().ffp_op_rt_topk(device, n, nt, nc, _fp(s), cs, s_coff, _ip(out)))
+    return out
 
 
 def jpeg_encode(img: np.ndarray, quality: int = 95, bgr: bool = False, device: int = 0) -> bytes:

@@ -1026,6 +1026,269 @@ int ffp_op_conv1x1_up2(int device, int precision, const float* coarse, const flo
   FFP_API_END
 }
 
+// ---- single-operator entry points of the detector's non-convolution kernels (tests/test_gpu_ops.py) --------------------------------
+// Host arrays hold the images of a ragged batch back to back, [sum h*w][cs] fp32 — whole pixel records, so a view may be a channel
+// slice of a wider buffer. On the device they sit in the layout of a Level built with `px_align` (padding pixels between images are
+// NaN going in and are not copied back); output buffers are in/out: the caller's contents go up first, so bytes outside the written
+// slice come back as they went in.
+static int g_op_variant[3] = {0, 0, 0};
+int ffp_op_variant(int family, int variant) {
+  FFP_API_BEGIN
+  FFP_CHECK(family >= 0 && family < 3 && variant >= 0 && variant <= 2, FFP_ERR_ARG, "op_variant: family %d / variant %d unknown", family, variant);
+  g_op_variant[family] = variant;
+  FFP_API_END
+}
+
+namespace {
+
+struct OpCtx {       // device + a stream of its own for one operator call
+  hipStream_t st = nullptr;
+  explicit OpCtx(int device, const char* what) {
+    int ndev = 0;
+    FFP_CHECK(hipGetDeviceCount(&ndev) == hipSuccess && device >= 0 && device < ndev, FFP_ERR_HIP, "%s: no HIP device %d (no CPU path)", what, device);
+    FFP_HIP(hipSetDevice(device));
+    FFP_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  }
+  ~OpCtx() { if (st) (void)hipStreamDestroy(st); }
+  OpCtx(const OpCtx&) = delete;
+  OpCtx& operator=(const OpCtx&) = delete;
+};
+
+void op_check_batch(const char* what, int n, const int32_t* hs, const int32_t* ws, int px_align) {
+  FFP_CHECK(n > 0 && n <= 4096 && hs && ws && px_align >= 1 && px_align <= 4096, FFP_ERR_ARG, "%s: bad batch description", what);
+  for (int i = 0; i < n; ++i) FFP_CHECK(hs[i] > 0 && ws[i] > 0 && hs[i] <= 8192 && ws[i] <= 8192, FFP_ERR_ARG, "%s: image %d is %dx%d", what, i, ws[i], hs[i]);
+}
+void op_check_view(const char* what, int cs, int coff, int C) {
+  FFP_CHECK(C > 0 && coff >= 0 && cs > 0 && coff + C <= cs, FFP_ERR_ARG, "%s: channels [%d, %d) do not fit records of %d", what, coff, coff + C, cs);
+}
+DType op_dtype(const char* what, int precision) {
+  FFP_CHECK(precision == FFP_PREC_F32 || precision == FFP_PREC_F16, FFP_ERR_ARG, "%s: precision must be FFP_PREC_F32 or FFP_PREC_F16", what);
+  return precision == FFP_PREC_F16 ? F16 : F32;
+}
+
+DevBuf op_upload(const Level& L, DType T, const float* src, int cs) {
+  const size_t tot = (size_t)L.total_px * cs;
+  DevBuf b(tot * dsize(T) + 256);
+  std::vector<float> t(tot, std::nanf(""));
+  size_t sp = 0;
+  for (int i = 0; i < L.n; ++i) {
+    const size_t np = (size_t)L.h[i] * L.w[i];
+    std::memcpy(&t[(size_t)L.off[i] * cs], src + sp * cs, np * cs * sizeof(float));
+    sp += np;
+  }
+  if (T == F32) {
+    FFP_HIP(hipMemcpy(b.p, t.data(), tot * 4, hipMemcpyHostToDevice));
+  } else {
+    std::vector<_Float16> h(tot);
+    for (size_t i = 0; i < tot; ++i) h[i] = (_Float16)t[i];
+    FFP_HIP(hipMemcpy(b.p, h.data(), tot * 2, hipMemcpyHostToDevice));
+  }
+  return b;
+}
+
+void op_download(const Level& L, DType T, const DevBuf& b, int cs, float* dst) {
+  const size_t tot = (size_t)L.total_px * cs;
+  std::vector<float> t(tot);
+  if (T == F32) {
+    FFP_HIP(hipMemcpy(t.data(), b.p, tot * 4, hipMemcpyDeviceToHost));
+  } else {
+    std::vector<_Float16> h(tot);
+    FFP_HIP(hipMemcpy(h.data(), b.p, tot * 2, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < tot; ++i) t[i] = (float)h[i];
+  }
+  size_t sp = 0;
+  for (int i = 0; i < L.n; ++i) {
+    const size_t np = (size_t)L.h[i] * L.w[i];
+    std::memcpy(dst + sp * cs, &t[(size_t)L.off[i] * cs], np * cs * sizeof(float));
+    sp += np;
+  }
+}
+
+}  // namespace
+
+int ffp_op_sppf_pool(int device, int precision, int n, const int32_t* hs, const int32_t* ws, int px_align, int c, const float* x, int x_cs,
+                     int x_coff, float* y, int y_cs, int y1_coff, int y2_coff, int y3_coff) {
+  FFP_API_BEGIN
+  FFP_CHECK(x && y, FFP_ERR_ARG, "sppf_pool: null argument");
+  op_check_batch("sppf_pool", n, hs, ws, px_align);
+  op_check_view("sppf_pool input", x_cs, x_coff, c);
+  const int yo[3] = {y1_coff, y2_coff, y3_coff};
+  for (int i = 0; i < 3; ++i) {
+    op_check_view("sppf_pool output", y_cs, yo[i], c);
+    for (int j = 0; j < i; ++j) FFP_CHECK(yo[i] >= yo[j] + c || yo[j] >= yo[i] + c, FFP_ERR_ARG, "sppf_pool: output slices %d and %d overlap", j + 1, i + 1);
+  }
+  const DType T = op_dtype("sppf_pool", precision);
+  OpCtx cx(device, "sppf_pool");
+  Level L;
+  L.build(std::vector<int>(hs, hs + n), std::vector<int>(ws, ws + n), cx.st, px_align);
+  DevBuf din = op_upload(L, T, x, x_cs), dout = op_upload(L, T, y, y_cs);
+  const TView vin{din.p, T, x_cs, x_coff, c, &L};
+  const TView v1{dout.p, T, y_cs, y1_coff, c, &L}, v2{dout.p, T, y_cs, y2_coff, c, &L}, v3{dout.p, T, y_cs, y3_coff, c, &L};
+  launch_sppf_pool(vin, v1, v2, v3, cx.st, g_op_variant[0]);
+  FFP_HIP(hipStreamSynchronize(cx.st));
+  op_download(L, T, dout, y_cs, y);
+  FFP_API_END
+}
+
+int ffp_op_upsample2x(int device, int precision, int n, const int32_t* hs, const int32_t* ws, int px_align, int c, const float* x, int x_cs,
+                      int x_coff, float* y, int y_cs, int y_coff) {
+  FFP_API_BEGIN
+  FFP_CHECK(x && y, FFP_ERR_ARG, "upsample2x: null argument");
+  op_check_batch("upsample2x", n, hs, ws, px_align);
+  op_check_view("upsample2x input", x_cs, x_coff, c);
+  op_check_view("upsample2x output", y_cs, y_coff, c);
+  const DType T = op_dtype("upsample2x", precision);
+  OpCtx cx(device, "upsample2x");
+  Level L, L2;
+  std::vector<int> h2(n), w2(n);
+  for (int i = 0; i < n; ++i) { h2[i] = hs[i] * 2; w2[i] = ws[i] * 2; }
+  L.build(std::vector<int>(hs, hs + n), std::vector<int>(ws, ws + n), cx.st, px_align);
+  L2.build(h2, w2, cx.st, px_align);
+  DevBuf din = op_upload(L, T, x, x_cs), dout = op_upload(L2, T, y, y_cs);
+  launch_upsample2x(TView{din.p, T, x_cs, x_coff, c, &L}, TView{dout.p, T, y_cs, y_coff, c, &L2}, cx.st);
+  FFP_HIP(hipStreamSynchronize(cx.st));
+  op_download(L2, T, dout, y_cs, y);
+  FFP_API_END
+}
+
+int ffp_op_psa_attention(int device, int precision, int n, const int32_t* hs, const int32_t* ws, int px_align, int nh, const float* qkv, int q_cs,
+                         int q_coff, float* out, int o_cs, int o_coff) {
+  FFP_API_BEGIN
+  FFP_CHECK(qkv && out && nh > 0 && nh <= 64, FFP_ERR_ARG, "psa_attention: bad arguments");
+  op_check_batch("psa_attention", n, hs, ws, px_align);
+  constexpr int KD = 32, HD = 64;
+  op_check_view("psa_attention qkv", q_cs, q_coff, nh * (2 * KD + HD));
+  op_check_view("psa_attention output", o_cs, o_coff, nh * HD);
+  const DType T = op_dtype("psa_attention", precision);
+  OpCtx cx(device, "psa_attention");
+  Level L;
+  L.build(std::vector<int>(hs, hs + n), std::vector<int>(ws, ws + n), cx.st, px_align);
+  DevBuf din = op_upload(L, T, qkv, q_cs), dout = op_upload(L, T, out, o_cs);
+  launch_psa_attention(TView{din.p, T, q_cs, q_coff, nh * (2 * KD + HD), &L}, TView{dout.p, T, o_cs, o_coff, nh * HD, &L}, nh, KD, HD, cx.st,
+                       g_op_variant[1]);
+  FFP_HIP(hipStreamSynchronize(cx.st));
+  op_download(L, T, dout, o_cs, out);
+  FFP_API_END
+}
+
+int ffp_op_dwconv3x3(int device, int precision, int n, const int32_t* hs, const int32_t* ws, int px_align, int c, const float* x, int x_cs,
+                     int x_coff, int grp, int grp_stride, int grp_off, const float* wt, const float* bias, int act, const float* res, int r_cs,
+                     int r_coff, float* y, int y_cs, int y_coff) {
+  FFP_API_BEGIN
+  FFP_CHECK(x && wt && y && c > 0 && act >= ACT_NONE && act <= ACT_RELU, FFP_ERR_ARG, "dwconv3x3: bad arguments");
+  op_check_batch("dwconv3x3", n, hs, ws, px_align);
+  FFP_CHECK(x_cs > 0 && x_coff >= 0 && grp >= 0 && grp_stride >= 0 && grp_off >= 0, FFP_ERR_ARG, "dwconv3x3: negative channel addressing");
+  if (grp > 0) {      // channel ch is read at x_coff + (ch / grp) * grp_stride + grp_off + ch % grp
+    FFP_CHECK(c % grp == 0 && grp_off + grp <= grp_stride, FFP_ERR_ARG, "dwconv3x3: groups of %d at offset %d do not fit records of %d (C = %d)", grp, grp_off, grp_stride, c);
+    FFP_CHECK((long long)x_coff + (long long)(c / grp) * grp_stride <= x_cs, FFP_ERR_ARG, "dwconv3x3: %d group records of %d exceed the pixel record of %d", c / grp, grp_stride, x_cs);
+  } else {
+    FFP_CHECK(grp_stride == 0 && grp_off == 0, FFP_ERR_ARG, "dwconv3x3: grp_stride / grp_off without grp");
+    op_check_view("dwconv3x3 input", x_cs, x_coff, c);
+  }
+  op_check_view("dwconv3x3 output", y_cs, y_coff, c);
+  if (res) op_check_view("dwconv3x3 residual", r_cs, r_coff, c);
+  const DType T = op_dtype("dwconv3x3", precision);
+  OpCtx cx(device, "dwconv3x3");
+  PackedConv pc;
+  pack_conv(pc, "op", wt, bias, c, c, 3, c, T, cx.st, false);
+  Level L;
+  L.build(std::vector<int>(hs, hs + n), std::vector<int>(ws, ws + n), cx.st, px_align);
+  DevBuf din = op_upload(L, T, x, x_cs), dout = op_upload(L, T, y, y_cs), dres;
+  if (res) dres = op_upload(L, T, res, r_cs);
+  DwConvOp o;
+  o.pc = &pc;
+  o.in = TView{din.p, T, x_cs, x_coff, c, &L};
+  o.out = TView{dout.p, T, y_cs, y_coff, c, &L};
+  o.act = act; o.grp = grp; o.grp_stride = grp_stride; o.grp_off = grp_off;
+  if (res) { o.has_res = true; o.res = TView{dres.p, T, r_cs, r_coff, c, &L}; }
+  o.force = g_op_variant[2];
+  launch_dwconv(o, cx.st);
+  FFP_HIP(hipStreamSynchronize(cx.st));
+  op_download(L, T, dout, y_cs, y);
+  FFP_API_END
+}
+
+int ffp_op_det_post(int device, int n, const int32_t* hs, const int32_t* ws, int px_align, int nc, int nkpt, const float* head8, const float* head16,
+                    const float* head32, const float* gain_pad, const int32_t* rects, float conf, float iou, int max_det, int round_boxes,
+                    int shift, int full_h, int full_w, float* out_raw, float* out_dets, int32_t* out_counts) {
+  FFP_API_BEGIN
+  FFP_CHECK(head8 && head16 && head32 && gain_pad && rects && nc >= 1 && nc <= 1024 && nkpt >= 0 && nkpt <= 64, FFP_ERR_ARG, "det_post: bad arguments");
+  FFP_CHECK((out_dets != nullptr) == (out_counts != nullptr) && (out_raw || out_dets), FFP_ERR_ARG, "det_post: dets and counts come together, and something must be asked for");
+  op_check_batch("det_post", n, hs, ws, px_align);
+  for (int i = 0; i < n; ++i) {
+    FFP_CHECK(hs[i] % 32 == 0 && ws[i] % 32 == 0, FFP_ERR_ARG, "det_post: net input %dx%d of image %d is not a multiple of 32", ws[i], hs[i], i);
+    FFP_CHECK(gain_pad[3 * i] > 0.f && rects[4 * i] > 0 && rects[4 * i + 1] > 0, FFP_ERR_ARG, "det_post: image %d has no gain or no size", i);
+  }
+  if (out_dets) FFP_CHECK(max_det >= 1 && max_det <= 1024 && conf >= 0.f, FFP_ERR_ARG, "det_post: max_det %d outside [1,1024] or negative conf", max_det);
+  OpCtx cx(device, "det_post");
+  const int cs = 64 + nc + 3 * nkpt, no = 4 + nc + 3 * nkpt, stride = 6 + 3 * nkpt;
+  Level L[3];
+  DevBuf dh[3];
+  const float* heads[3] = {head8, head16, head32};
+  for (int l = 0; l < 3; ++l) {
+    std::vector<int> h(n), w(n);
+    for (int i = 0; i < n; ++i) { h[i] = hs[i] / (8 << l); w[i] = ws[i] / (8 << l); }
+    L[l].build(h, w, cx.st, px_align);
+    dh[l] = op_upload(L[l], F32, heads[l], cs);
+  }
+  std::vector<int> aoff(n + 1, 0);
+  std::vector<long long> roff(n);
+  long long rtot = 0;
+  for (int i = 0; i < n; ++i) {
+    int a = 0;
+    for (int l = 0; l < 3; ++l) a += L[l].h[i] * L[l].w[i];
+    aoff[i + 1] = aoff[i] + a;
+    roff[i] = rtot;
+    rtot += (long long)no * a;
+  }
+  const int total = aoff[n];
+  std::vector<DetImg> di(n);
+  for (int i = 0; i < n; ++i) {
+    di[i].gain = gain_pad[3 * i]; di[i].pad_x = gain_pad[3 * i + 1]; di[i].pad_y = gain_pad[3 * i + 2];
+    di[i].sw = rects[4 * i]; di[i].sh = rects[4 * i + 1]; di[i].x0 = rects[4 * i + 2]; di[i].y0 = rects[4 * i + 3];
+  }
+  DevBuf d_aoff = upload(aoff.data(), aoff.size()), d_roff = upload(roff.data(), roff.size()), d_imgs = upload(di.data(), di.size());
+  DecodeArgs a{};
+  for (int l = 0; l < 3; ++l) { a.head[l] = dh[l].as<float>(); a.tab[l] = L[l].d_tab.as<int4>(); }
+  a.head_cs = cs; a.nc = nc; a.nkpt = nkpt; a.n_img = n; a.anchor_off = d_aoff.as<int>(); a.total_anchors = total;
+  if (out_raw) {
+    DevBuf d_raw(sizeof(float) * (size_t)rtot);
+    launch_decode_raw(a, d_raw.as<float>(), d_roff.as<long long>(), cx.st);
+    FFP_HIP(hipStreamSynchronize(cx.st));
+    FFP_HIP(hipMemcpy(out_raw, d_raw.p, sizeof(float) * (size_t)rtot, hipMemcpyDeviceToHost));
+  }
+  if (out_dets) {
+    DevBuf d_boxes(sizeof(float4) * (size_t)total), d_scores(sizeof(float) * (size_t)total), d_classes(sizeof(int) * (size_t)total),
+        d_cand(sizeof(int) * (size_t)total), d_cscore(sizeof(float) * (size_t)total);
+    const size_t nd = (size_t)n * max_det * stride;
+    DevBuf d_dets(sizeof(float) * nd), d_counts(sizeof(int) * (size_t)n);
+    FFP_HIP(hipMemsetAsync(d_dets.p, 0, sizeof(float) * nd, cx.st));
+    launch_decode(a, conf, d_boxes.as<float4>(), d_scores.as<float>(), d_classes.as<int>(), cx.st);
+    launch_nms(a, d_boxes.as<float4>(), d_scores.as<float>(), d_classes.as<int>(), d_cand.as<int>(), d_cscore.as<float>(), d_imgs.as<DetImg>(), iou,
+               max_det, round_boxes, stride, d_dets.as<float>(), d_counts.as<int>(), cx.st);
+    if (shift) launch_truncate_shift(d_dets.as<float>(), d_counts.as<int>(), d_imgs.as<DetImg>(), n, max_det, stride, nkpt, full_h, full_w, cx.st);
+    FFP_HIP(hipStreamSynchronize(cx.st));
+    FFP_HIP(hipMemcpy(out_dets, d_dets.p, sizeof(float) * nd, hipMemcpyDeviceToHost));
+    FFP_HIP(hipMemcpy(out_counts, d_counts.p, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
+  }
+  FFP_API_END
+}
+
+int ffp_op_rt_topk(int device, int n, int nt, int nc, const float* scores, int s_cs, int s_coff, int32_t* out_idx) {
+  FFP_API_BEGIN
+  FFP_CHECK(scores && out_idx && n > 0 && n <= 4096 && nt >= RT_NQ && nt <= (1 << 22), FFP_ERR_ARG, "rt_topk: needs n in [1,4096] images of [%d, 2^22] tokens", RT_NQ);
+  op_check_view("rt_topk scores", s_cs, s_coff, nc);
+  OpCtx cx(device, "rt_topk");
+  const size_t tok = (size_t)n * nt;
+  DevBuf ds = upload(scores, tok * s_cs), keys(sizeof(unsigned) * tok), idx(sizeof(int) * (size_t)n * RT_NQ);
+  Level L;
+  L.build(std::vector<int>(n, 1), std::vector<int>(n, nt), cx.st);
+  launch_rt_topk(TView{ds.p, F32, s_cs, s_coff, nc, &L}, nc, nt, n, keys.as<unsigned>(), idx.as<int>(), cx.st);
+  FFP_HIP(hipStreamSynchronize(cx.st));
+  FFP_HIP(hipMemcpy(out_idx, idx.p, sizeof(int) * (size_t)n * RT_NQ, hipMemcpyDeviceToHost));
+  FFP_API_END
+}
+
 // tuning hook: average device time (HIP events) of `iters` launches of one dense convolution on synthetic data
 int ffp_op_conv2d_time(int device, int precision, int n, int h, int w, int cin, int cout, int k, int stride, int up, int iters,
                        int dbg_mask, int force_shape, float* out_us) {

@@ -54,6 +54,7 @@ struct DwConvOp {
   int grp = 0, grp_stride = 0, grp_off = 0;
   bool has_res = false;
   TView res;
+  int force = 0;      // tests only: 1 column-walk kernel, 2 strip kernel (0: automatic)
 };
 void launch_dwconv(const DwConvOp& op, hipStream_t st);      // raises op.out.amax when set
 // slots[i] = init[i] (bit patterns of max-|value| bounds known without looking at data; 0 elsewhere): first step of a plan
@@ -62,13 +63,15 @@ void launch_amax_init(unsigned* slots, const unsigned* init, int n, hipStream_t 
 void launch_amax_max(unsigned* dst, const unsigned* src, hipStream_t st, int n = 1);       // n slots (per-image slots: TView::amax_n)
 
 // SPPF: y1,y2,y3 = 5x5/9x9/13x13 stride-1 max pools of `in` (== three chained MaxPool2d(5,1,2)), written to three slices.
-void launch_sppf_pool(const TView& in, const TView& y1, const TView& y2, const TView& y3, hipStream_t st);
+// force (tests only): 1 the LDS kernel (maps of at most 1024 px), 2 the direct kernel; 0: automatic.
+void launch_sppf_pool(const TView& in, const TView& y1, const TView& y2, const TView& y3, hipStream_t st, int force = 0);
 
 // nearest x2 upsample of `in` (level L) into `out` (level with doubled dims)
 void launch_upsample2x(const TView& in, const TView& out, hipStream_t st);
 
 // Multi-head attention of C2PSA: qkv [px][nh*(2kd+hd)] -> out [px][nh*hd] = softmax(q^T k * scale) applied to v.
-void launch_psa_attention(const TView& qkv, const TView& out, int nh, int kd, int hd, hipStream_t st);
+// force (tests only): 1 the MFMA kernel (views aligned to 4 channels), 2 the VALU kernel; 0: automatic.
+void launch_psa_attention(const TView& qkv, const TView& out, int nh, int kd, int hd, hipStream_t st, int force = 0);
 
 // ---- detector pre/post ------------------------------------------------------------------------------------
 struct LetterboxImg {     // one network input image cut from the frame

@@ -43,47 +43,12 @@ template <> __device__ __forceinline__ void st4<_Float16>(_Float16* p, float4 v)
   *reinterpret_cast<uint2*>(p) = o.u;
 }
 
-// ---- depthwise 3x3 s1 p1: one thread = one pixel x 4 channels ------------------------------------------------------
-template <typename T>
-__global__ void dwconv3x3_kernel(const T* __restrict__ in, int in_cs, int in_coff, int grp, int grp_stride, int grp_off,
-                                 T* __restrict__ out, int out_cs, int out_coff, const float* __restrict__ w /*[9][C]*/,
-                                 const float* __restrict__ bias, const T* __restrict__ res, int r_cs, int r_coff, int C,
-                                 int act, const int4* __restrict__ tab, int n_img, long long total_px) {
-  const int C4 = C >> 2;
-  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= total_px * C4) return;
-  const int c = (int)(idx % C4) * 4;
-  const long long gp = idx / C4;
-  const int im = find_img(tab, n_img, gp);
-  const int4 t = tab[im];
-  const int lp = (int)(gp - t.x), y = lp / t.z, x = lp - y * t.z;
-  const int cin = in_coff + (c / grp) * grp_stride + grp_off + (c % grp);
-  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-  for (int ky = 0; ky < 3; ++ky) {
-    const int yy = y + ky - 1;
-    if ((unsigned)yy >= (unsigned)t.y) continue;
-#pragma unroll
-    for (int kx = 0; kx < 3; ++kx) {
-      const int xx = x + kx - 1;
-      if ((unsigned)xx >= (unsigned)t.z) continue;
-      const float4 v = ld4<T>(in + ((size_t)t.x + (size_t)yy * t.z + xx) * in_cs + cin);
-      const float4 k = *reinterpret_cast<const float4*>(w + (ky * 3 + kx) * C + c);
-      acc.x = fmaf(v.x, k.x, acc.x); acc.y = fmaf(v.y, k.y, acc.y); acc.z = fmaf(v.z, k.z, acc.z); acc.w = fmaf(v.w, k.w, acc.w);
-    }
-  }
-  const float4 b = *reinterpret_cast<const float4*>(bias + c);
-  float4 v = make_float4(act_fn(acc.x + b.x, act), act_fn(acc.y + b.y, act), act_fn(acc.z + b.z, act), act_fn(acc.w + b.w, act));
-  if (res) {
-    const float4 r = ld4<T>(res + (size_t)gp * r_cs + r_coff + c);
-    v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w;
-  }
-  st4<T>(out + (size_t)gp * out_cs + out_coff + c, v);
-}
-
-// Same op, one thread = FOUR horizontally adjacent pixels x 4 channels: 18 input vectors instead of 36 and one image lookup
-// instead of four (the per-pixel form runs at ~40 % of its HBM roofline on the stride-8 cls-tower layers). Taps are
-// accumulated in the same (ky, kx) order with zeros for out-of-image taps: bit-identical to dwconv3x3_kernel.
+// ---- depthwise 3x3 s1 p1 ------------------------------------------------------------------------------------------
+// One thread = FOUR horizontally adjacent pixels x 4 channels: 18 input vectors instead of 36 and one image lookup instead
+// of four (a per-pixel form ran at ~40 % of its HBM roofline on the stride-8 cls-tower layers). Taps are accumulated in
+// (ky, kx) order, out-of-image taps as zeros in the strip and skipped in the pixel-by-pixel tail — fma(0, k, acc) leaves a
+// finite acc unchanged, so both are the same sum, and dwconv3x3_col_kernel below accumulates in that order too: the two
+// kernels are bit-identical (tests/test_gpu_ops.py compares them with array_equal).
 template <typename T>
 __device__ __forceinline__ void dwconv_strip_body(const T* __restrict__ in, int in_cs, int in_coff, int grp, int grp_stride, int grp_off,
                                                   T* __restrict__ out, int out_cs, int out_coff, const float* __restrict__ w,
@@ -326,7 +291,7 @@ __global__ void __launch_bounds__(256) conv3x3_c3_direct_kernel(const T* __restr
 
 // ---- C2PSA attention ----------------------------------------------------------------------------------------------
 // grid (ceil(Nmax/256), nh, n_img), 256 threads: one query per thread, keys/values streamed through LDS 64 at a time,
-// fp32 online softmax. qkv pixel record per head: [q(kd) | k(kd) | v(hd)].
+// fp32 online softmax with one rescale per 64-key block. qkv pixel record per head: [q(kd) | k(kd) | v(hd)].
 template <typename T, int KD, int HD>
 __global__ void __launch_bounds__(256) psa_attention_kernel(const T* __restrict__ qkv, int q_cs, int q_coff,
                                                             T* __restrict__ out, int o_cs, int o_coff,
@@ -361,23 +326,34 @@ __global__ void __launch_bounds__(256) psa_attention_kernel(const T* __restrict_
     }
     __syncthreads();
     const int jn = min(KB, N - j0);
+    // the block's keys are summed among themselves first and folded into the running sums once per block, as the MFMA kernel does:
+    // adding 1024 terms one by one to o[] lost up to 5.5e-6 of the result (a large early term, then hundreds of small ones each
+    // rounded at the accumulator's ulp) — more than 4 x a plain float32 evaluation (tests/test_gpu_ops.py::test_psa_attention)
+    float bm = -INFINITY;
     for (int j = 0; j < jn; ++j) {
       float s = 0.f;
 #pragma unroll
       for (int d = 0; d < KD; ++d) s = fmaf(q[d], ks[j][d], s);
-      s *= scale;
-      if (s > m) {
-        const float f = expf(m - s);
-        l *= f;
-#pragma unroll
-        for (int d = 0; d < HD; ++d) o[d] *= f;
-        m = s;
-      }
-      const float pj = expf(s - m);
-      l += pj;
-#pragma unroll
-      for (int d = 0; d < HD; ++d) o[d] = fmaf(pj, vs[j][d], o[d]);
+      bm = fmaxf(bm, s * scale);
     }
+    const float mn = fmaxf(m, bm);
+    float lb = 0.f, ob[HD];
+#pragma unroll
+    for (int d = 0; d < HD; ++d) ob[d] = 0.f;
+    for (int j = 0; j < jn; ++j) {
+      float s = 0.f;
+#pragma unroll
+      for (int d = 0; d < KD; ++d) s = fmaf(q[d], ks[j][d], s);
+      const float pj = expf(s * scale - mn);
+      lb += pj;
+#pragma unroll
+      for (int d = 0; d < HD; ++d) ob[d] = fmaf(pj, vs[j][d], ob[d]);
+    }
+    const float f = expf(m - mn);
+    l = l * f + lb;
+#pragma unroll
+    for (int d = 0; d < HD; ++d) o[d] = o[d] * f + ob[d];
+    m = mn;
   }
   if (!active) return;
   const float inv = 1.0f / l;
@@ -686,7 +662,10 @@ void launch_dwconv(const DwConvOp& op, hipStream_t st) {
   const int4* tab = op.out.lvl->d_tab.as<int4>();
   static const bool col_walk = [] { const char* e = getenv("FFP_DW_STRIP"); return !(e && e[0] == '1'); }();      // FFP_DW_STRIP=1: the strip kernel (A/B aid)
   const int amax_img = op.out.amax && op.out.amax_n > 1 ? 1 : 0;
-  if ((col_walk || amax_img) && !op.out.lvl->capacity()) {
+  FFP_CHECK(op.force >= 0 && op.force <= 2, FFP_ERR_ARG, "dwconv: unknown kernel variant %d", op.force);
+  FFP_CHECK(op.force != 1 || !op.out.lvl->capacity(), FFP_ERR_ARG, "dwconv: the column-walk kernel needs an exact-mode level");
+  const bool use_col = op.force ? op.force == 1 : (col_walk || amax_img);
+  if (use_col && !op.out.lvl->capacity()) {
     constexpr int RB = 8;
     int n_tiles = 0;
     const int* d_count = nullptr;
@@ -740,7 +719,7 @@ void launch_amax_max(unsigned* dst, const unsigned* src, hipStream_t st, int n) 
   FFP_HIP(hipGetLastError());
 }
 
-void launch_sppf_pool(const TView& in, const TView& y1, const TView& y2, const TView& y3, hipStream_t st) {
+void launch_sppf_pool(const TView& in, const TView& y1, const TView& y2, const TView& y3, hipStream_t st, int force) {
   FFP_CHECK(y1.ptr == y2.ptr && y2.ptr == y3.ptr && y1.cs == y2.cs && y2.cs == y3.cs, FFP_ERR_ARG, "sppf: outputs must be slices of one buffer");
   const int C = in.C;
   FFP_CHECK(C % 4 == 0 && in.cs % 4 == 0 && in.coff % 4 == 0 && y1.cs % 4 == 0 && y1.coff % 4 == 0 && y2.coff % 4 == 0 && y3.coff % 4 == 0,
@@ -750,7 +729,9 @@ void launch_sppf_pool(const TView& in, const TView& y1, const TView& y2, const T
   const int4* tab = in.lvl->d_tab.as<int4>();
   int max_px = 0;
   for (int i = 0; i < in.lvl->n; ++i) max_px = std::max(max_px, in.lvl->h[i] * in.lvl->w[i]);
-  if (max_px <= 1024) {
+  FFP_CHECK(force >= 0 && force <= 2, FFP_ERR_ARG, "sppf: unknown kernel variant %d", force);
+  FFP_CHECK(force != 1 || max_px <= 1024, FFP_ERR_ARG, "sppf: the LDS kernel holds maps of at most 1024 pixels (largest here: %d)", max_px);
+  if (force ? force == 1 : max_px <= 1024) {
     const dim3 grid(C / 4, in.lvl->n);
     if (in.dt == F32)
       hipLaunchKernelGGL(sppf_pool_lds_kernel<float>, grid, dim3(256), 0, st, (const float*)in.ptr, in.cs, in.coff, (float*)y1.ptr, (float*)y2.ptr,
@@ -785,14 +766,17 @@ void launch_upsample2x(const TView& in, const TView& out, hipStream_t st) {
   FFP_HIP(hipGetLastError());
 }
 
-void launch_psa_attention(const TView& qkv, const TView& out, int nh, int kd, int hd, hipStream_t st) {
+void launch_psa_attention(const TView& qkv, const TView& out, int nh, int kd, int hd, hipStream_t st, int force) {
   FFP_CHECK(kd == 32 && hd == 64, FFP_ERR_ARG, "psa attention: only key_dim 32 / head_dim 64 (YOLO11 n/s) is instantiated");
   FFP_CHECK(qkv.C == nh * (2 * kd + hd) && out.C == nh * hd && qkv.lvl == out.lvl, FFP_ERR_ARG, "psa attention: view mismatch");
   int nmax = 0;
   for (int i = 0; i < qkv.lvl->n; ++i) nmax = std::max(nmax, qkv.lvl->h[i] * qkv.lvl->w[i]);
   const float scale = 1.0f / sqrtf((float)kd);
   static const bool valu = [] { const char* e = getenv("FFP_ATTN_VALU"); return e && e[0] == '1'; }();
-  if (!valu && qkv.cs % 4 == 0 && qkv.coff % 4 == 0 && out.cs % 4 == 0 && out.coff % 4 == 0) {
+  const bool aligned = qkv.cs % 4 == 0 && qkv.coff % 4 == 0 && out.cs % 4 == 0 && out.coff % 4 == 0;
+  FFP_CHECK(force >= 0 && force <= 2, FFP_ERR_ARG, "psa attention: unknown kernel variant %d", force);
+  FFP_CHECK(force != 1 || aligned, FFP_ERR_ARG, "psa attention: the MFMA kernel needs views aligned to 4 channels");
+  if (force ? force == 1 : (!valu && aligned)) {
     dim3 g2((nmax + 127) / 128, nh, qkv.lvl->n);
     if (qkv.dt == F32)
       hipLaunchKernelGGL((psa_attention_mfma_kernel<float>), g2, dim3(256), 0, st, (const float*)qkv.ptr, qkv.cs, qkv.coff, (float*)out.ptr, out.cs,

@@ -348,6 +348,54 @@ int ffp_op_conv1x1_up2(int device, int precision, const float* coarse, const flo
  * of the following ffp_op_conv2d call. */
 int ffp_op_conv2d_shape(int force_shape);
 
+/* ---- the detector's non-convolution kernels one at a time (operator parity tests) ----------------------------------------
+ * A batch is n images of hs[i] x ws[i] pixels; host arrays hold them back to back as [sum hs*ws][cs] fp32 pixel records, and a
+ * view is `c` channels at `coff` of records of `cs` — a channel slice of a wider buffer, as the plans use them. On the device the
+ * images are laid out with every image starting at a multiple of `px_align` pixels (1: packed). precision: FFP_PREC_F32 or
+ * FFP_PREC_F16 storage (values are rounded to fp16 on the way in). Output arrays are in/out: the caller's contents are uploaded
+ * first, so everything outside the written slice comes back unchanged. Bad arguments: FFP_ERR_ARG, nothing is launched. */
+
+/* Test hook: pin the kernel ffp_op_sppf_pool (family 0: 1 LDS, 2 direct), ffp_op_psa_attention (family 1: 1 MFMA, 2 VALU) or
+ * ffp_op_dwconv3x3 (family 2: 1 column walk, 2 strip) launches from now on (process-wide; 0 = the automatic choice, the default).
+ * A variant that cannot run the op is an error of the following op call. Engines are not affected. */
+int ffp_op_variant(int family, int variant);
+
+/* SPPF: y1, y2, y3 = three chained MaxPool2d(5, 1, 2) of x, written to the slices y*_coff of one buffer y. */
+int ffp_op_sppf_pool(int device, int precision, int n, const int32_t* hs, const int32_t* ws, int px_align, int c, const float* x, int x_cs,
+                     int x_coff, float* y, int y_cs, int y1_coff, int y2_coff, int y3_coff);
+
+/* nearest x2: y (images of 2 hs[i] x 2 ws[i]) = upsample(x). */
+int ffp_op_upsample2x(int device, int precision, int n, const int32_t* hs, const int32_t* ws, int px_align, int c, const float* x, int x_cs,
+                      int x_coff, float* y, int y_cs, int y_coff);
+
+/* C2PSA attention, key_dim 32 / head_dim 64: qkv view of nh * 128 channels, per head [q(32) | k(32) | v(64)]; out view of nh * 64
+ * channels = softmax(q^T k / sqrt(32)) applied to v, over the h*w pixels of each image. */
+int ffp_op_psa_attention(int device, int precision, int n, const int32_t* hs, const int32_t* ws, int px_align, int nh, const float* qkv, int q_cs,
+                         int q_coff, float* out, int o_cs, int o_coff);
+
+/* depthwise 3x3, stride 1, pad 1: y = act(conv(x) + bias) [+ res]. wt: [c][3][3], bias: [c] or NULL; act: 0 none, 1 SiLU,
+ * 2 LeakyReLU(0.2), 3 ReLU. grp > 0 reads input channel ch at x_coff + (ch / grp) * grp_stride + grp_off + ch % grp (the PSA
+ * positional conv reading v in place from the [q|k|v] records); grp = 0: channel ch at x_coff + ch. res: optional, NULL = none. */
+int ffp_op_dwconv3x3(int device, int precision, int n, const int32_t* hs, const int32_t* ws, int px_align, int c, const float* x, int x_cs,
+                     int x_coff, int grp, int grp_stride, int grp_off, const float* wt, const float* bias, int act, const float* res, int r_cs,
+                     int r_coff, float* y, int y_cs, int y_coff);
+
+/* Pose-head post-processing on given head tensors. hs / ws: net input size per image (multiples of 32); head8 / head16 / head32:
+ * [sum (hs/s)*(ws/s)][64 + nc + 3*nkpt] fp32 records (64 DFL logits | class logits | keypoint raws). gain_pad [n][3] = gain,
+ * pad_x, pad_y and rects [n][4] = crop width, crop height, x0, y0: the un-letterboxing geometry of each image.
+ * out_raw (NULL = skip): per image the inference-mode head output [4 + nc + 3*nkpt][anchors], images back to back.
+ * out_dets / out_counts (both or neither): [n][max_det][6 + 3*nkpt] rows x1, y1, x2, y2, score, class, keypoints after decode
+ * (score > conf), NMS (IoU > iou, per class) and scale_boxes / scale_coords, rows past out_counts[i] zero; round_boxes rounds the
+ * box; shift = 1 also applies the wrapper's int truncation, clip to full_w / full_h and shift by (x0, y0). */
+int ffp_op_det_post(int device, int n, const int32_t* hs, const int32_t* ws, int px_align, int nc, int nkpt, const float* head8, const float* head16,
+                    const float* head32, const float* gain_pad, const int32_t* rects, float conf, float iou, int max_det, int round_boxes,
+                    int shift, int full_h, int full_w, float* out_raw, float* out_dets, int32_t* out_counts);
+
+/* RT-DETR query selection: per image the indices of the 300 tokens with the largest max-over-classes logit, ordered by (logit
+ * descending, index ascending). scores: [n][nt][s_cs] fp32, the nc class logits at s_coff. Logits are ordered by their bit
+ * patterns (+0.0 above -0.0, which float comparison calls equal). out_idx: [n][300]. */
+int ffp_op_rt_topk(int device, int n, int nt, int nc, const float* scores, int s_cs, int s_coff, int32_t* out_idx);
+
 /* Tuning hook: mean device time (HIP events, microseconds) of `iters` back-to-back launches of one dense convolution on
  * synthetic data. dbg_mask skips kernel phases (1 stores, 2 MFMAs, 4 chunk refetch, 8 LDS stash) to attribute time —
  * results are then wrong by construction; force_shape pins the workgroup shape (-1: automatic). */

@@ -67,6 +67,43 @@ def test_bad_arguments_are_reported(lib):
     assert lib.ffp_letterbox_geometry(0, 10, 512, None) == 1
 
 
+def test_operator_entry_points_check_arguments_before_touching_the_device(lib):
+    """ffp_op_* of the non-convolution kernels: bad views, sizes and variants are FFP_ERR_ARG (code 1) — decided on the host,
+    so it holds with or without a GPU — and a well-formed call without a GPU fails loudly instead of computing on the CPU."""
+    z = lambda h, w, c: [np.zeros((h, w, c), np.float32)]
+    bad = [
+        lambda: _lib.op_sppf_pool(z(4, 4, 8), 8, 4, z(4, 4, 32), (0, 8, 16)),                 # input slice past the record
+        lambda: _lib.op_sppf_pool(z(4, 4, 8), 8, 0, z(4, 4, 32), (0, 4, 16)),                 # overlapping output slices
+        lambda: _lib.op_sppf_pool(z(4, 4, 8), 8, 0, z(4, 4, 32), (0, 8, 28)),                 # output slice past the record
+        lambda: _lib.op_sppf_pool(z(4, 4, 8), 8, 0, z(4, 4, 32), (0, 8, 16), precision=_lib.PREC_F32X3),
+        lambda: _lib.op_upsample2x(z(2, 2, 8), 8, 0, z(4, 4, 8), 4),
+        lambda: _lib.op_psa_attention(z(2, 2, 256), 2, 4, z(2, 2, 128), 0),
+        lambda: _lib.op_psa_attention(z(2, 2, 256), 2, 0, z(2, 2, 128), 4),
+        lambda: _lib.op_dwconv3x3(z(3, 3, 256), 128, 0, np.zeros((128, 3, 3)), None, z(3, 3, 128), 0, grp=64, grp_stride=128, grp_off=96),
+        lambda: _lib.op_dwconv3x3(z(3, 3, 256), 128, 4, np.zeros((128, 3, 3)), None, z(3, 3, 128), 0, grp=64, grp_stride=128, grp_off=64),
+        lambda: _lib.op_dwconv3x3(z(3, 3, 8), 8, 0, np.zeros((8, 3, 3)), None, z(3, 3, 8), 0, act=7),
+        lambda: _lib.op_det_post([[np.zeros((8, 8, 80), np.float32), np.zeros((4, 4, 80), np.float32), np.zeros((2, 2, 80), np.float32)]], 1, 5,
+                                 [(0, 0, 0, 64, 64, 0, 0)]),                                  # no gain
+        lambda: _lib.op_det_post([[np.zeros((8, 8, 80), np.float32), np.zeros((4, 4, 80), np.float32), np.zeros((2, 2, 80), np.float32)]], 1, 5,
+                                 [(1, 0, 0, 64, 64, 0, 0)], max_det=2000),
+        lambda: _lib.op_rt_topk(np.zeros((1, 299, 4), np.float32)),
+        lambda: _lib.op_rt_topk(np.zeros((1, 300, 4), np.float32), nc=4, s_coff=1),
+        lambda: _lib.op_variant(_lib.OP_SPPF, 3),
+        lambda: _lib.op_variant(3, 1),
+    ]
+    for i, f in enumerate(bad):
+        with pytest.raises(_lib.FfpError) as e:
+            f()
+        assert e.value.code == 1, (i, str(e.value))
+    if _lib.device_count() == 0:
+        with pytest.raises(_lib.FfpError) as e:
+            _lib.op_sppf_pool(z(4, 4, 8), 8, 0, z(4, 4, 32), (0, 8, 16))
+        assert "no HIP device" in str(e.value)
+        with pytest.raises(_lib.FfpError) as e:
+            _lib.op_rt_topk(np.zeros((1, 300, 4), np.float32))
+        assert "no HIP device" in str(e.value)
+
+
 def test_weights_container_roundtrip():
     W = synth.yolo11_pose_weights("n")
     buf = weights_io.pack(W)
