@@ -1,4 +1,6 @@
-// conv_args.hpp — kernel argument block and device helpers shared by the MFMA convolution kernels (conv_mfma.hip, conv_rows.hip).
+// conv_args.hpp — kernel argument block, device helpers and launcher declarations shared by the convolution kernels: conv_mfma.hip (which
+// dispatches to the others), conv_rows.hip, conv_pw.hip, conv_k3d.hip, rtdetr_ops.hip, and — through rows16_parts.hpp — conv_rows16.hip,
+// conv_rows16pc.hip and conv_trunk.hip.
 #pragma once
 #include "ops.hpp"
 
@@ -165,6 +167,7 @@ bool conv_rows16_eligible(const ConvOp& op, const ConvArgs& a);
 void launch_conv_rows16(ConvArgs& a, const PackedConv& pc, Level* out_lvl, hipStream_t st);
 void conv_rows16_init();
 bool conv_rows16_enabled();     // FFP_ROWS16=0 keeps the first-generation kernel (A/B aid)
+unsigned rows16_grid(int n_tiles, int n_nblk, int min_ws, int tcap, const char* what);      // launch extent 8 x Ws of the item dealing (conv_rows16.hip), checked
 // the same convs with producer / consumer waves (conv_rows16pc.hip): OPT-IN (force_shape 24 or FFP_ROWS16_PC=1; measured 0.73-0.94x); bit-identical results
 bool conv_rows16pc_selected(const ConvArgs& a);
 void launch_conv_rows16pc(ConvArgs& a, const PackedConv& pc, Level* out_lvl, hipStream_t st);

@@ -23,21 +23,12 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "conv_args.hpp"
+#include "rows16_parts.hpp"
 
 #ifndef FFP_R16_DBG
 #define FFP_R16_DBG 0          // 1: also build the phase-skip instantiations of the kernel (tools/rows16_phase_probe.py); compile-time masks, so
 #endif                         //    that what is left keeps the production kernel's instruction schedule
 
-#ifndef FFP_R16_PRIO
-#define FFP_R16_PRIO 0         // 1: s_setprio 1 over the MFMA stream of a chunk (A/B)
-#endif
-#ifndef FFP_R16_STASH
-#define FFP_R16_STASH 0        // experiment: 1 = the next chunk's ten pieces are written to LDS and re-requested BEFORE the chunk's MFMA stream, 2 = AFTER it
-#endif                         //             (0: one piece per MFMA step, the shipped schedule)
-#ifndef FFP_R16_STORE_AUX
-#define FFP_R16_STORE_AUX 0   // cache policy of the output stores (experiment): 16 = sc1 (write-through: nothing dirty left in L2 for the kernel-end write-back), 17 = sc0 sc1, 2 = nt
-#endif
 #ifndef FFP_R16_STAMP
 #define FFP_R16_STAMP 0        // 1: diagnostic build — s_memtime stamps around the phases of every chunk, sums printed by the first workgroups
 #endif                         //    (MI355X guide, "In-kernel stamps"); never in a shipped build, the stamps cost ~10 % of the kernel
@@ -46,16 +37,7 @@ namespace ffp {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-struct R16Geo {
-  static constexpr int IN_PX = 336;                           // 18 x 18 halo pixels + 12 dummies: 21 whole wave-pieces of 64 vectors
-  static constexpr int IN_BYTES = IN_PX * 64;                 // 21504
-  static constexpr int W_BYTES = 9 * 2 * 1024;                // [tap][M-tile][lane] : 18 wave-pieces
-  static constexpr int STAGE = IN_BYTES + W_BYTES;            // 39936
-  static constexpr int NP = 10;                               // wave-pieces per wave and chunk: 5 input, 4 weight, 1 mixed (see piece_fetch)
-  static constexpr int TCAP = 40;                             // work items one workgroup walks (descriptor table in LDS)
+struct R16Lds : R16Geo {                                      // the LDS image of conv_rows16_kernel: [stage 0][stage 1][descriptors]
   static constexpr int DESC = 2 * STAGE;                      // int4 x 3 per item: tile {img, y0, x0}, input {base, h, w}, output {base, h, w}
   static constexpr int LDS = 2 * STAGE + TCAP * 48;           // 81792 <= 80 KiB
   // weight-resident form (RES): [input stage 0][input stage 1][all chunks' weight fragments of the workgroup's channel block][descriptors];
@@ -66,12 +48,9 @@ struct R16Geo {
   static constexpr int res_lds(int nc) { return 2 * IN_BYTES + nc * W_BYTES + TCAP * 48; }
 };
 
-// Items are dealt so that each XCD (workgroups b, b + 8, ... share one) gets a contiguous run of logical ids (pixel tile x
-// 32-channel block) and the workgroups of an XCD take consecutive ids at the same time: the channel blocks of a pixel tile
-// and neighbouring tiles meet in that XCD's L2. The mapping only affects speed.
 template <int DBG, bool RES = false>             // phase-skip bits: 1 epilogue, 2 MFMA, 4 staging requests, 8 staging LDS writes, 16 fragment reads, 32 barriers
 __global__ void __launch_bounds__(256, (RES ? 1 : 2)) conv_rows16_kernel(const ConvArgs a) {
-  using G = R16Geo;
+  using G = R16Lds;
   constexpr int NP = RES ? G::NPR : G::NP;
   constexpr int STG = RES ? G::IN_BYTES : G::STAGE;            // bytes of one LDS stage
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -80,51 +59,31 @@ __global__ void __launch_bounds__(256, (RES ? 1 : 2)) conv_rows16_kernel(const C
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int pc = lane & 15, g = lane >> 4;             // pixel column inside the tile, channel group / k slot
 
-  // ---- this workgroup's items: logical ids first + j * Ws, j < J --------------------------------------------------------------
-  const int n_items = (a.n_tiles_dev ? __builtin_amdgcn_readfirstlane(*a.n_tiles_dev) : a.ntiles_host) * a.n_nblk;
-  const int Ws = (int)gridDim.x >> 3;
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-  int per_xcd = (n_items + 7) >> 3;
-  per_xcd = (per_xcd + a.n_nblk - 1) / a.n_nblk * a.n_nblk;
-  const int first = xcd * per_xcd + slot;
-  const int last = min(n_items, (xcd + 1) * per_xcd);
-  const int J = first < last ? min((last - first + Ws - 1) / Ws, G::TCAP) : 0;      // the launcher sizes Ws so that J <= TCAP
+  const R16Deal deal = r16_deal(a, G::TCAP);
+  const int J = deal.J;
   if (J == 0) return;
-  const int nt0 = first % a.n_nblk;                    // Ws and per_xcd are multiples of n_nblk: ONE channel block per workgroup
+  const int nt0 = deal.first % a.n_nblk;               // Ws and per_xcd are multiples of n_nblk: ONE channel block per workgroup
 
   const int NC = a.cin >> 5;
   int4* desc = reinterpret_cast<int4*>(smem + (RES ? G::RES_W + NC * G::W_BYTES : G::DESC));
-  if (tid < J) {
-    const int4 t = a.tiles[(first + tid * Ws) / a.n_nblk];
-    desc[tid * 3] = t;
-    desc[tid * 3 + 1] = a.in_tab[t.x];
-    desc[tid * 3 + 2] = a.out_tab[t.x];
-  }
-  __syncthreads();
+  r16_fill_desc(desc, a, deal, tid);
 
-  constexpr unsigned OOB = 0xFFFFFFFFu;
-  auto uniform_ptr = [](const unsigned char* q) {
-    const unsigned long long u = reinterpret_cast<unsigned long long>(q);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-    return reinterpret_cast<unsigned char*>(((unsigned long long)hi << 32) | lo);
-  };
   auto sgpr = [](int v) { return __builtin_amdgcn_readfirstlane(v); };
   const unsigned char* wb = reinterpret_cast<const unsigned char*>(a.wpk) + (long long)nt0 * NC * G::W_BYTES;
-  const auto rs_w = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(wb), 0, 0x7FFFFFF0, 0x00020000);
+  const auto rs_w = r16_rsrc(wb);
   auto rs_in = rs_w;                                   // rebuilt per item (setup_pf)
   auto rs_wp = rs_w;                                   // the prefetcher's view of the weights (emptied when the stream ends)
-  auto bload = [](decltype(rs_w) rs, unsigned off, int soff = 0) {      // soff: wave-uniform byte offset (an SGPR operand, no VALU)
-    const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs, off, soff, 0);
-    return make_uint4(v[0], v[1], v[2], v[3]);
-  };
 
+  // (this kernel keeps its OWN text of the staging below — the same as r16_stage_tables .. r16_advance_pf of rows16_parts.hpp, which
+  // conv_rows16pc_kernel runs: moving any of it, or the fragment offsets, or zero_acc, into free functions changes hipcc's register allocation
+  // of the chunk loop, and the shipped kernel's instruction stream is kept as it was measured)
   // ---- staging: a chunk = 21 input + 18 weight wave-pieces (64 lanes x 16 bytes); wave w stages, in its NP slots,
   //   slots 0..4: input pieces w, w+4, .., w+16; slots 5..8: weight pieces w, w+4, w+8, w+12;
   //   slot 9: wave 0 input piece 20, wave 1 / 2 weight pieces 16 / 17, wave 3 weight piece 17 again (same bytes to the same place)
   // so every slot is a whole wave-instruction for every wave: no divergence, no validity tests in the pipeline.
   const bool s9_in = wave == 0;
   const int s9_piece = wave == 0 ? 20 : wave == 1 ? 16 : 17;
-  unsigned isrc[6];        // byte offset of (pixel, slot) of the item being PREFETCHED from its image base; OOB: zeros
+  unsigned isrc[6];        // byte offset of (pixel, slot) of the item being PREFETCHED from its image base; R16_OOB: zeros
   unsigned idst[6];        // LDS byte offset of that vector inside the stage (item independent)
   unsigned wrel[5];        // weight pieces: byte offset inside a chunk's 18 KiB, also the LDS offset behind IN_BYTES
   unsigned hyx[6];         // the slot's halo pixel and vector slot (slot << 16 | row << 8 | column): item independent, so that an item's set-up is adds and compares
@@ -151,13 +110,13 @@ __global__ void __launch_bounds__(256, (RES ? 1 : 2)) conv_rows16_kernel(const C
     const int oy0 = sgpr(t.y), ox0 = sgpr(t.z), Hi = sgpr(it.y), Wi = sgpr(it.z);
     const int Hv = Hi << a.up, Wv = Wi << a.up;
     const unsigned char* inb = reinterpret_cast<const unsigned char*>(a.in) + ((long long)sgpr(it.x) * a.in_cs + a.in_coff) * 2;
-    rs_in = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(inb), 0, 0x7FFFFFF0, 0x00020000);
+    rs_in = r16_rsrc(inb);
 #pragma unroll
     for (int i = 0; i < 6; ++i) {                      // hyx[i]: the slot's halo pixel (row << 8 | column) and vector slot, fixed per lane; 0xFFFF: padding pixel
       const int hy = (int)(hyx[i] >> 8) & 0xFF, hx = (int)hyx[i] & 0xFF, sl = (int)(hyx[i] >> 16) & 3;
       const int iy = oy0 - 1 + hy, ix = ox0 - 1 + hx;
       const bool ok = (hyx[i] & 0xFFFFu) != 0xFFFFu && (unsigned)iy < (unsigned)Hv && (unsigned)ix < (unsigned)Wv;
-      isrc[i] = ok ? (unsigned)(((iy >> a.up) * Wi + (ix >> a.up)) * a.in_cs * 2 + sl * 16) : OOB;
+      isrc[i] = ok ? (unsigned)(((iy >> a.up) * Wi + (ix >> a.up)) * a.in_cs * 2 + sl * 16) : R16_OOB;
     }
   };
   uint4 ra[NP] = {}, rb[NP] = {};                      // two register sets
@@ -165,16 +124,16 @@ __global__ void __launch_bounds__(256, (RES ? 1 : 2)) conv_rows16_kernel(const C
     if (DBG & 4) return;
     if constexpr (RES) {                               // input pieces only: slots 0..4 as below, slot 5 = input piece 20 for every wave
       const unsigned o = isrc[p];
-      r = bload(rs_in, o != OOB ? o + (unsigned)(pf_c * 64) : OOB);
+      r = r16_bload(rs_in, o != R16_OOB ? o + (unsigned)(pf_c * 64) : R16_OOB);
       return;
     }
     if (p < 5) {
-      r = bload(rs_in, isrc[p] != OOB ? isrc[p] + (unsigned)(pf_c * 64) : OOB);
+      r = r16_bload(rs_in, isrc[p] != R16_OOB ? isrc[p] + (unsigned)(pf_c * 64) : R16_OOB);
     } else if (p < 9) {
-      r = bload(rs_wp, wrel[p - 5], pf_c * G::W_BYTES);
+      r = r16_bload(rs_wp, wrel[p - 5], pf_c * G::W_BYTES);
     } else {                                           // the mixed slot: wave-uniform choice, no branch
-      const unsigned oi = isrc[5] != OOB ? isrc[5] + (unsigned)(pf_c * 64) : OOB;
-      r = bload(s9_in ? rs_in : rs_wp, s9_in ? oi : wrel[4], s9_in ? 0 : pf_c * G::W_BYTES);
+      const unsigned oi = isrc[5] != R16_OOB ? isrc[5] + (unsigned)(pf_c * 64) : R16_OOB;
+      r = r16_bload(s9_in ? rs_in : rs_wp, s9_in ? oi : wrel[4], s9_in ? 0 : pf_c * G::W_BYTES);
     }
   };
   auto piece_stash = [&](unsigned char* sb, int p, const uint4& r) {
@@ -191,7 +150,7 @@ __global__ void __launch_bounds__(256, (RES ? 1 : 2)) conv_rows16_kernel(const C
       if (++pf_item < J) {
         setup_pf(pf_item);
       } else {                                         // stream exhausted: every later request is out of range (zeros, no traffic)
-        rs_in = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(wb), 0, 0, 0x00020000);
+        rs_in = r16_rsrc(wb, 0);
         rs_wp = rs_in;
       }
     }
@@ -256,18 +215,10 @@ __global__ void __launch_bounds__(256, (RES ? 1 : 2)) conv_rows16_kernel(const C
 #pragma unroll
       for (int m = 0; m < 2; ++m) aq[q][m] = *reinterpret_cast<const uint4*>((RES ? wres : sb) + aoff + ((tap * 2 + m) << 10));
     };
-#if FFP_R16_STASH == 1
-#pragma unroll
-    for (int p = 0; p < NP; ++p) { piece_stash(sbn, p, set[p]); piece_fetch(p, set[p]); }
-    __builtin_amdgcn_sched_barrier(0);
-#endif
     ldB(0, 0);
     ldA(0, 0);
     ldA(1, 1);
     __builtin_amdgcn_sched_barrier(0);
-#if FFP_R16_PRIO
-    __builtin_amdgcn_s_setprio(1);                             // the MFMA stream outranks the partner wave's epilogue / set-up VALU work
-#endif
 #if FFP_R16_STAMP
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     st_t1 = __builtin_amdgcn_s_memtime();
@@ -278,13 +229,11 @@ __global__ void __launch_bounds__(256, (RES ? 1 : 2)) conv_rows16_kernel(const C
       if (s + 2 < 9) ldA(s + 2, (s + 2) % 3);
       if (ky == 0 && kx < 2) ldB(kx + 1, (kx + 1) & 1);
       // staging slots per step: {0} {1} {2} {3} {4} {5} {6} {7} {8, 9}
-#if FFP_R16_STASH == 0
 #pragma unroll
       for (int p = s; p < (RES ? (s < NP ? s + 1 : s) : (s == 8 ? 10 : s + 1)); ++p) {
         piece_stash(sbn, p, set[p]);
         piece_fetch(p, set[p]);
       }
-#endif
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -302,13 +251,6 @@ __global__ void __launch_bounds__(256, (RES ? 1 : 2)) conv_rows16_kernel(const C
       }
       __builtin_amdgcn_sched_barrier(0);
     }
-#if FFP_R16_PRIO
-    __builtin_amdgcn_s_setprio(0);
-#endif
-#if FFP_R16_STASH == 2
-#pragma unroll
-    for (int p = 0; p < NP; ++p) { piece_stash(sbn, p, set[p]); piece_fetch(p, set[p]); }
-#endif
     advance_pf();
   };
 
@@ -321,9 +263,7 @@ __global__ void __launch_bounds__(256, (RES ? 1 : 2)) conv_rows16_kernel(const C
     const unsigned char* r1b = a.res1 ? reinterpret_cast<const unsigned char*>(a.res1) + (out_base * a.r1_cs + a.r1_coff) * 2 : wb;
     const unsigned char* r2b = a.res2 ? reinterpret_cast<const unsigned char*>(a.res2) + (out_base * a.r2_cs + a.r2_coff) * 2 : wb;
     unsigned char* ob = reinterpret_cast<unsigned char*>(a.out) + (out_base * a.out_cs + a.out_coff) * 2;
-    const auto rs_r1 = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(r1b), 0, 0x7FFFFFF0, 0x00020000);
-    const auto rs_r2 = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(r2b), 0, 0x7FFFFFF0, 0x00020000);
-    const auto rs_o = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(ob), 0, 0x7FFFFFF0, 0x00020000);
+    const auto rs_r1 = r16_rsrc(r1b), rs_r2 = r16_rsrc(r2b), rs_o = r16_rsrc(ob);
     const int ox = ox0 + pc;
     const int ch0 = nt0 * 32 + 8 * g;
 #pragma unroll
@@ -332,32 +272,10 @@ __global__ void __launch_bounds__(256, (RES ? 1 : 2)) conv_rows16_kernel(const C
       const bool ok = oy < Ho && ox < Wo;
       const unsigned rel_px = (unsigned)(oy * Wo + ox);
       uint4 r1v = make_uint4(0u, 0u, 0u, 0u), r2v = r1v;
-      if (a.res1) r1v = bload(rs_r1, ok ? (rel_px * a.r1_cs + ch0) * 2 : OOB);
-      if (a.res2) r2v = bload(rs_r2, ok ? (rel_px * a.r2_cs + ch0) * 2 : OOB);
-      float v[8];
-      v[0] = acc[i][0][0]; v[1] = acc[i][0][1]; v[2] = acc[i][0][2]; v[3] = acc[i][0][3];
-      v[4] = acc[i][1][0]; v[5] = acc[i][1][1]; v[6] = acc[i][1][2]; v[7] = acc[i][1][3];
-      if (a.act == ACT_LRELU) {                        // max(x, 0.2 x): two VALU ops per value
-#pragma unroll
-        for (int q = 0; q < 8; ++q) v[q] = fmaxf(v[q], v[q] * 0.2f);
-      } else if (a.act == ACT_SILU) {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) v[q] = apply_act(v[q], ACT_SILU);
-      }
-      if (a.res1) {
-        const _Float16* r = reinterpret_cast<const _Float16*>(&r1v);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) v[q] = v[q] * a.s1 + (float)r[q];
-      }
-      if (a.res2) {
-        const _Float16* r = reinterpret_cast<const _Float16*>(&r2v);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) v[q] = v[q] * a.s2 + (float)r[q];
-      }
-      union { u32x4 u; _Float16 h[8]; } ov;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) ov.h[q] = (_Float16)v[q];
-      __builtin_amdgcn_raw_buffer_store_b128(ov.u, rs_o, ok ? (rel_px * a.out_cs + ch0) * 2 : OOB, 0, FFP_R16_STORE_AUX);
+      if (a.res1) r1v = r16_bload(rs_r1, ok ? (rel_px * a.r1_cs + ch0) * 2 : R16_OOB);
+      if (a.res2) r2v = r16_bload(rs_r2, ok ? (rel_px * a.r2_cs + ch0) * 2 : R16_OOB);
+      const u32x4 ov = r16_finish_px(acc[i][0], acc[i][1], a.act, a.res1 != nullptr, r1v, a.s1, a.res2 != nullptr, r2v, a.s2);
+      __builtin_amdgcn_raw_buffer_store_b128(ov, rs_o, ok ? (rel_px * a.out_cs + ch0) * 2 : R16_OOB, 0, 0);
     }
   };
 
@@ -383,7 +301,7 @@ __global__ void __launch_bounds__(256, (RES ? 1 : 2)) conv_rows16_kernel(const C
       uint4 t[8];
 #pragma unroll
       for (int k = 0; k < 8; ++k)
-        if (p0 + 4 * k < n_wp) t[k] = bload(rs_w, (unsigned)lane * 16u, sgpr((p0 + 4 * k) << 10));
+        if (p0 + 4 * k < n_wp) t[k] = r16_bload(rs_w, (unsigned)lane * 16u, sgpr((p0 + 4 * k) << 10));
 #pragma unroll
       for (int k = 0; k < 8; ++k)
         if (p0 + 4 * k < n_wp) *reinterpret_cast<uint4*>(smem + G::RES_W + ((p0 + 4 * k) << 10) + lane * 16) = t[k];
@@ -440,8 +358,8 @@ constexpr int kR16Masks[] = {0, 1};
 template <int I = 0> void r16_for_mask(int mask, bool res, bool init, const ConvArgs* a, unsigned grid, int lds, hipStream_t st) {
   if constexpr (I < (int)(sizeof(kR16Masks) / sizeof(int))) {
     if (init) {
-      FFP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_rows16_kernel<kR16Masks[I], false>), hipFuncAttributeMaxDynamicSharedMemorySize, R16Geo::LDS));
-      FFP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_rows16_kernel<kR16Masks[I], true>), hipFuncAttributeMaxDynamicSharedMemorySize, R16Geo::res_lds(R16Geo::RES_MAXC)));
+      FFP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_rows16_kernel<kR16Masks[I], false>), hipFuncAttributeMaxDynamicSharedMemorySize, R16Lds::LDS));
+      FFP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_rows16_kernel<kR16Masks[I], true>), hipFuncAttributeMaxDynamicSharedMemorySize, R16Lds::res_lds(R16Lds::RES_MAXC)));
       r16_for_mask<I + 1>(mask, res, init, a, grid, lds, st);
     } else if (mask == kR16Masks[I]) {
       if (res) hipLaunchKernelGGL((conv_rows16_kernel<kR16Masks[I], true>), dim3(grid), dim3(256), lds, st, *a);
@@ -460,7 +378,7 @@ void conv_rows16_init() { r16_for_mask<>(0, false, true, nullptr, 0, 0, nullptr)
 // the weight-resident form: force_shape 23, or every eligible layer with FFP_ROWS16_RES=1 (A/B aid)
 static bool rows16_resident(const ConvArgs& a) {
   static const bool env_on = [] { const char* e = getenv("FFP_ROWS16_RES"); return e && e[0] == '1'; }();
-  return (a.force_shape == 23 || (a.force_shape < 0 && env_on)) && (a.cin >> 5) <= R16Geo::RES_MAXC;
+  return (a.force_shape == 23 || (a.force_shape < 0 && env_on)) && (a.cin >> 5) <= R16Lds::RES_MAXC;
 }
 
 bool conv_rows16_eligible(const ConvOp& op, const ConvArgs& a) {
@@ -470,8 +388,20 @@ bool conv_rows16_eligible(const ConvOp& op, const ConvArgs& a) {
          pc.cout <= 128 && a.fast_out && op.out.cs % 8 == 0 && op.out.coff % 8 == 0;
 }
 
+// 8 x Ws workgroups, Ws >= min_ws, a multiple of the channel blocks per tile (a workgroup then keeps ONE channel block: weights and bias
+// are item independent) and large enough that no workgroup walks more than tcap items (what r16_deal on the device relies on)
+unsigned rows16_grid(int n_tiles, int n_nblk, int min_ws, int tcap, const char* what) {
+  const long long items = (long long)n_tiles * n_nblk;
+  long long per_xcd = (items + 7) / 8;
+  per_xcd = (per_xcd + n_nblk - 1) / n_nblk * n_nblk;
+  long long ws = std::max<long long>(min_ws, (per_xcd + tcap - 1) / tcap);
+  ws = (ws + n_nblk - 1) / n_nblk * n_nblk;
+  FFP_CHECK(8 * ws < (1ll << 31) && (per_xcd + ws - 1) / ws <= tcap, FFP_ERR_STATE, "%s: launch geometry", what);
+  return (unsigned)(8 * ws);
+}
+
 void launch_conv_rows16(ConvArgs& a, const PackedConv& pc, Level* out_lvl, hipStream_t st) {
-  using G = R16Geo;
+  using G = R16Lds;
   static_assert(G::LDS <= 80 * 1024, "rows16 kernel: two workgroups per CU");
   a.wpk = pc.w16.p;
   int n_tiles = 0;
@@ -479,17 +409,10 @@ void launch_conv_rows16(ConvArgs& a, const PackedConv& pc, Level* out_lvl, hipSt
   if (n_tiles == 0) return;
   a.ntiles_host = n_tiles;
   a.n_nblk = a.ntiles32;
-  // 8 x Ws workgroups, Ws a multiple of the channel blocks per tile (a workgroup then keeps ONE channel block: weights and bias
-  // are item independent) and large enough that no workgroup walks more than TCAP items; Ws = 64 is two workgroups per CU
-  const long long items = (long long)n_tiles * a.n_nblk;
-  long long per_xcd = (items + 7) / 8;
-  per_xcd = (per_xcd + a.n_nblk - 1) / a.n_nblk * a.n_nblk;
   const bool res = rows16_resident(a);
   static const int ws_env = [] { const char* e = getenv("FFP_ROWS16_WS"); return e ? atoi(e) : 0; }();      // experiment: workgroups per XCD (64 = two per CU)
-  long long ws = std::max<long long>(ws_env > 0 ? ws_env : (res ? 32 : 64), (per_xcd + G::TCAP - 1) / G::TCAP);          // resident weights: one workgroup per CU
-  ws = (ws + a.n_nblk - 1) / a.n_nblk * a.n_nblk;
-  FFP_CHECK(8 * ws < (1ll << 31) && (per_xcd + ws - 1) / ws <= G::TCAP, FFP_ERR_STATE, "rows16: launch geometry");
-  r16_for_mask<>(a.dbg, res, false, &a, (unsigned)(8 * ws), res ? G::res_lds(a.cin >> 5) : G::LDS, st);
+  const unsigned grid = rows16_grid(n_tiles, a.n_nblk, ws_env > 0 ? ws_env : (res ? 32 : 64), G::TCAP, "rows16");      // resident weights: one workgroup per CU
+  r16_for_mask<>(a.dbg, res, false, &a, grid, res ? G::res_lds(a.cin >> 5) : G::LDS, st);
 }
 
 }  // namespace ffp

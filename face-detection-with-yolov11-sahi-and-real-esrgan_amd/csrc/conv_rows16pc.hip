@@ -27,22 +27,13 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "conv_args.hpp"
+#include "rows16_parts.hpp"
 
 namespace ffp {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-struct PCGeo {
-  static constexpr int IN_PX = 336;
-  static constexpr int IN_BYTES = IN_PX * 64;                 // 21504
-  static constexpr int W_BYTES = 9 * 2 * 1024;                // 18432
-  static constexpr int STAGE = IN_BYTES + W_BYTES;            // 39936
-  static constexpr int NP = 10;
-  static constexpr int TCAP = 40;
+struct PCGeo : R16Geo {                                       // conv_rows16_kernel's stages, then
   static constexpr int DUMP = 2 * STAGE;                      // four exchange blocks of 8 KiB: [consumer wave][row i][M-tile m][lane] x 16 B
   static constexpr int DUMP_W = 8192;
   static constexpr int DESC = DUMP + 4 * DUMP_W;
@@ -61,42 +52,19 @@ __global__ void __launch_bounds__(512, 2) conv_rows16pc_kernel(const ConvArgs a)
   const int wave = wave8 & 3;
   const int pc = lane & 15, g = lane >> 4;
 
-  // ---- this workgroup's items (conv_rows16_kernel's dealing) -------------------------------------------------------------------------
-  const int n_items = (a.n_tiles_dev ? __builtin_amdgcn_readfirstlane(*a.n_tiles_dev) : a.ntiles_host) * a.n_nblk;
-  const int Ws = (int)gridDim.x >> 3;
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-  int per_xcd = (n_items + 7) >> 3;
-  per_xcd = (per_xcd + a.n_nblk - 1) / a.n_nblk * a.n_nblk;
-  const int first = xcd * per_xcd + slot;
-  const int last = min(n_items, (xcd + 1) * per_xcd);
-  const int J = first < last ? min((last - first + Ws - 1) / Ws, G::TCAP) : 0;
+  const R16Deal deal = r16_deal(a, G::TCAP);           // conv_rows16_kernel's dealing
+  const int J = deal.J;
   if (J == 0) return;                                  // whole workgroup: no barrier is skipped by part of it
-  const int nt0 = first % a.n_nblk;
+  const int nt0 = deal.first % a.n_nblk;
 
   int4* desc = reinterpret_cast<int4*>(smem + G::DESC);
-  if (tid < J) {
-    const int4 t = a.tiles[(first + tid * Ws) / a.n_nblk];
-    desc[tid * 3] = t;
-    desc[tid * 3 + 1] = a.in_tab[t.x];
-    desc[tid * 3 + 2] = a.out_tab[t.x];
-  }
-  __syncthreads();
+  r16_fill_desc(desc, a, deal, tid);
 
-  constexpr unsigned OOB = 0xFFFFFFFFu;
-  auto uniform_ptr = [](const unsigned char* q) {
-    const unsigned long long u = reinterpret_cast<unsigned long long>(q);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-    return reinterpret_cast<unsigned char*>(((unsigned long long)hi << 32) | lo);
-  };
   auto sgpr = [](int v) { return __builtin_amdgcn_readfirstlane(v); };
   const int NC = a.cin >> 5;
   const int Q = J * NC;                                // chunks of this workgroup: both roles run exactly Q iterations, one barrier each
   const unsigned char* wb = reinterpret_cast<const unsigned char*>(a.wpk) + (long long)nt0 * NC * G::W_BYTES;
-  const auto rs_w = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(wb), 0, 0x7FFFFFF0, 0x00020000);
-  auto bload = [](decltype(rs_w) rs, unsigned off, int soff = 0) {
-    const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs, off, soff, 0);
-    return make_uint4(v[0], v[1], v[2], v[3]);
-  };
+  const auto rs_w = r16_rsrc(wb);
   unsigned char* dump = smem + G::DUMP + wave * G::DUMP_W + lane * 16;       // this wave pair's exchange block
 
   if (producer) {
@@ -104,62 +72,14 @@ __global__ void __launch_bounds__(512, 2) conv_rows16pc_kernel(const ConvArgs a)
     auto rs_in = rs_w;
     auto rs_wp = rs_w;
     const bool s9_in = wave == 0;
-    const int s9_piece = wave == 0 ? 20 : wave == 1 ? 16 : 17;
     unsigned isrc[6], idst[6], wrel[5], hyx[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-      const int idx = (i < 5 ? wave + 4 * i : 20) * 64 + lane;
-      const int px = idx >> 2, s = idx & 3;
-      const int hy = px / 18, hx = px - hy * 18;
-      idst[i] = (unsigned)(px * 64 + ((s ^ ((hx >> 1) & 2)) << 4));
-      hyx[i] = px < 324 ? (unsigned)((s << 16) | (hy << 8) | hx) : (unsigned)((s << 16) | 0xFFFF);
-    }
-#pragma unroll
-    for (int i = 0; i < 5; ++i) wrel[i] = (unsigned)(((i < 4 ? wave + 4 * i : s9_piece) * 64 + lane) * 16);
+    r16_stage_tables(wave, lane, idst, hyx, wrel);
 
     int pf_item = 0, pf_c = 0;
-    auto setup_pf = [&](int j) {
-      const int4 t = desc[j * 3], it = desc[j * 3 + 1];
-      const int oy0 = sgpr(t.y), ox0 = sgpr(t.z), Hi = sgpr(it.y), Wi = sgpr(it.z);
-      const int Hv = Hi << a.up, Wv = Wi << a.up;
-      const unsigned char* inb = reinterpret_cast<const unsigned char*>(a.in) + ((long long)sgpr(it.x) * a.in_cs + a.in_coff) * 2;
-      rs_in = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(inb), 0, 0x7FFFFFF0, 0x00020000);
-#pragma unroll
-      for (int i = 0; i < 6; ++i) {
-        const int hy = (int)(hyx[i] >> 8) & 0xFF, hx = (int)hyx[i] & 0xFF, sl = (int)(hyx[i] >> 16) & 3;
-        const int iy = oy0 - 1 + hy, ix = ox0 - 1 + hx;
-        const bool ok = (hyx[i] & 0xFFFFu) != 0xFFFFu && (unsigned)iy < (unsigned)Hv && (unsigned)ix < (unsigned)Wv;
-        isrc[i] = ok ? (unsigned)(((iy >> a.up) * Wi + (ix >> a.up)) * a.in_cs * 2 + sl * 16) : OOB;
-      }
-    };
     uint4 sets[NS][NP];
-    auto piece_fetch = [&](int p, uint4& r) {
-      if (p < 5) {
-        r = bload(rs_in, isrc[p] != OOB ? isrc[p] + (unsigned)(pf_c * 64) : OOB);
-      } else if (p < 9) {
-        r = bload(rs_wp, wrel[p - 5], pf_c * G::W_BYTES);
-      } else {
-        const unsigned oi = isrc[5] != OOB ? isrc[5] + (unsigned)(pf_c * 64) : OOB;
-        r = bload(s9_in ? rs_in : rs_wp, s9_in ? oi : wrel[4], s9_in ? 0 : pf_c * G::W_BYTES);
-      }
-    };
-    auto piece_stash = [&](unsigned char* sb, int p, const uint4& r) {
-      if (p < 5) *reinterpret_cast<uint4*>(sb + idst[p]) = r;
-      else if (p < 9) *reinterpret_cast<uint4*>(sb + G::IN_BYTES + wrel[p - 5]) = r;
-      else *reinterpret_cast<uint4*>(sb + (s9_in ? idst[5] : G::IN_BYTES + wrel[4])) = r;
-    };
-    auto advance_pf = [&]() {
-      if (pf_item >= J) return;
-      if (++pf_c == NC) {
-        pf_c = 0;
-        if (++pf_item < J) {
-          setup_pf(pf_item);
-        } else {
-          rs_in = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(wb), 0, 0, 0x00020000);
-          rs_wp = rs_in;
-        }
-      }
-    };
+    auto piece_fetch = [&](int p, uint4& r) { r16_piece_fetch(p, r, rs_in, rs_wp, isrc, wrel, pf_c, s9_in); };
+    auto piece_stash = [&](unsigned char* sb, int p, const uint4& r) { r16_piece_stash(sb, p, r, idst, wrel, s9_in); };
+    auto advance_pf = [&]() { r16_advance_pf(a, desc, J, NC, wb, pf_item, pf_c, hyx, isrc, rs_in, rs_wp); };
     auto fetch_all = [&](uint4 (&q)[NP]) {
 #pragma unroll
       for (int p = 0; p < NP; ++p) piece_fetch(p, q[p]);
@@ -188,9 +108,7 @@ __global__ void __launch_bounds__(512, 2) conv_rows16pc_kernel(const ConvArgs a)
       const unsigned char* r1b = a.res1 ? reinterpret_cast<const unsigned char*>(a.res1) + (out_base * a.r1_cs + a.r1_coff) * 2 : wb;
       const unsigned char* r2b = a.res2 ? reinterpret_cast<const unsigned char*>(a.res2) + (out_base * a.r2_cs + a.r2_coff) * 2 : wb;
       unsigned char* ob = reinterpret_cast<unsigned char*>(a.out) + (out_base * a.out_cs + a.out_coff) * 2;
-      const auto rs_r1 = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(r1b), 0, 0x7FFFFFF0, 0x00020000);
-      const auto rs_r2 = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(r2b), 0, 0x7FFFFFF0, 0x00020000);
-      const auto rs_o = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(ob), 0, 0x7FFFFFF0, 0x00020000);
+      const auto rs_r1 = r16_rsrc(r1b), rs_r2 = r16_rsrc(r2b), rs_o = r16_rsrc(ob);
       const int ox = ox0 + pc;
       const int ch0 = nt0 * 32 + 8 * g;
 #pragma unroll
@@ -199,37 +117,15 @@ __global__ void __launch_bounds__(512, 2) conv_rows16pc_kernel(const ConvArgs a)
         const bool ok = oy < Ho && ox < Wo;
         const unsigned rel_px = (unsigned)(oy * Wo + ox);
         uint4 r1v = make_uint4(0u, 0u, 0u, 0u), r2v = r1v;
-        if (a.res1) r1v = bload(rs_r1, ok ? (rel_px * a.r1_cs + ch0) * 2 : OOB);
-        if (a.res2) r2v = bload(rs_r2, ok ? (rel_px * a.r2_cs + ch0) * 2 : OOB);
-        float v[8];
-        v[0] = acc[i][0][0]; v[1] = acc[i][0][1]; v[2] = acc[i][0][2]; v[3] = acc[i][0][3];
-        v[4] = acc[i][1][0]; v[5] = acc[i][1][1]; v[6] = acc[i][1][2]; v[7] = acc[i][1][3];
-        if (a.act == ACT_LRELU) {
-#pragma unroll
-          for (int q = 0; q < 8; ++q) v[q] = fmaxf(v[q], v[q] * 0.2f);
-        } else if (a.act == ACT_SILU) {
-#pragma unroll
-          for (int q = 0; q < 8; ++q) v[q] = apply_act(v[q], ACT_SILU);
-        }
-        if (a.res1) {
-          const _Float16* r = reinterpret_cast<const _Float16*>(&r1v);
-#pragma unroll
-          for (int q = 0; q < 8; ++q) v[q] = v[q] * a.s1 + (float)r[q];
-        }
-        if (a.res2) {
-          const _Float16* r = reinterpret_cast<const _Float16*>(&r2v);
-#pragma unroll
-          for (int q = 0; q < 8; ++q) v[q] = v[q] * a.s2 + (float)r[q];
-        }
-        union { u32x4 u; _Float16 h[8]; } ov;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) ov.h[q] = (_Float16)v[q];
-        __builtin_amdgcn_raw_buffer_store_b128(ov.u, rs_o, ok ? (rel_px * a.out_cs + ch0) * 2 : OOB, 0, 0);
+        if (a.res1) r1v = r16_bload(rs_r1, ok ? (rel_px * a.r1_cs + ch0) * 2 : R16_OOB);
+        if (a.res2) r2v = r16_bload(rs_r2, ok ? (rel_px * a.r2_cs + ch0) * 2 : R16_OOB);
+        const u32x4 ov = r16_finish_px(acc[i][0], acc[i][1], a.act, a.res1 != nullptr, r1v, a.s1, a.res2 != nullptr, r2v, a.s2);
+        __builtin_amdgcn_raw_buffer_store_b128(ov, rs_o, ok ? (rel_px * a.out_cs + ch0) * 2 : R16_OOB, 0, 0);
       }
     };
 
     // ---- prologue: chunks 0 .. NS-1 requested (set c holds chunk c mod NS), chunk 0 into stage 0, its set re-requested for chunk NS -------
-    setup_pf(0);
+    r16_setup_pf(a, desc, 0, hyx, isrc, rs_in);
 #pragma unroll
     for (int k = 0; k < NS; ++k) fetch_all(sets[k]);
 #pragma unroll
@@ -257,20 +153,10 @@ __global__ void __launch_bounds__(512, 2) conv_rows16pc_kernel(const ConvArgs a)
   const float4 bias0 = *reinterpret_cast<const float4*>(a.bias + nt0 * 32 + 8 * g);
   const float4 bias1 = *reinterpret_cast<const float4*>(a.bias + nt0 * 32 + 8 * g + 4);
   unsigned boff[3];
-#pragma unroll
-  for (int kx = 0; kx < 3; ++kx) {
-    const int hx = pc + kx;
-    boff[kx] = (unsigned)(((4 * wave) * 18 + hx) * 64 + ((g ^ ((hx >> 1) & 2)) << 4));
-  }
+  r16_frag_offsets(4 * wave, pc, g, boff);
   const unsigned aoff = G::IN_BYTES + lane * 16;
   f32x4 acc[4][2];
-  auto zero_acc = [&]() {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      acc[i][0] = f32x4{bias0.x, bias0.y, bias0.z, bias0.w};
-      acc[i][1] = f32x4{bias1.x, bias1.y, bias1.z, bias1.w};
-    }
-  };
+  auto zero_acc = [&]() { r16_zero_acc(acc, bias0, bias1); };
   zero_acc();
   // one step = one tap: 2 weight fragments x 4 output rows = 8 MFMAs; weight fragments two steps, input-row fragments one kx ahead
   auto chunk = [&](const unsigned char* sb) {
@@ -351,15 +237,10 @@ void launch_conv_rows16pc(ConvArgs& a, const PackedConv& pc, Level* out_lvl, hip
   if (n_tiles == 0) return;
   a.ntiles_host = n_tiles;
   a.n_nblk = a.ntiles32;
-  const long long items = (long long)n_tiles * a.n_nblk;
-  long long per_xcd = (items + 7) / 8;
-  per_xcd = (per_xcd + a.n_nblk - 1) / a.n_nblk * a.n_nblk;
-  long long ws = std::max<long long>(32, (per_xcd + G::TCAP - 1) / G::TCAP);          // 8 x 32 workgroups: one per CU
-  ws = (ws + a.n_nblk - 1) / a.n_nblk * a.n_nblk;
-  FFP_CHECK(8 * ws < (1ll << 31) && (per_xcd + ws - 1) / ws <= G::TCAP, FFP_ERR_STATE, "rows16pc: launch geometry");
+  const unsigned grid = rows16_grid(n_tiles, a.n_nblk, 32, G::TCAP, "rows16pc");          // 8 x 32 workgroups: one per CU
   static const int ns = [] { const char* e = getenv("FFP_ROWS16_PC_SETS"); return e ? atoi(e) : 2; }();       // 4 sets (five chunks ahead) measured SLOWER than 2: 0.68-0.85x vs 0.78-0.95x of conv_rows16_kernel
-  if (ns == 2) hipLaunchKernelGGL(conv_rows16pc_kernel<2>, dim3((unsigned)(8 * ws)), dim3(512), G::LDS, st, a);
-  else hipLaunchKernelGGL(conv_rows16pc_kernel<4>, dim3((unsigned)(8 * ws)), dim3(512), G::LDS, st, a);
+  if (ns == 2) hipLaunchKernelGGL(conv_rows16pc_kernel<2>, dim3(grid), dim3(512), G::LDS, st, a);
+  else hipLaunchKernelGGL(conv_rows16pc_kernel<4>, dim3(grid), dim3(512), G::LDS, st, a);
 }
 
 }  // namespace ffp

@@ -37,7 +37,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "conv_args.hpp"
+#include "rows16_parts.hpp"
 #include "trunk.hpp"
 
 #ifndef FFP_TRUNK_DBG
@@ -50,9 +50,6 @@
 namespace ffp {
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 struct TG {
   static constexpr int TH = 32;                               // tile rows (tile columns: 16)
@@ -137,11 +134,7 @@ __global__ void __launch_bounds__(768, 3) conv_trunk_kernel(const TrunkArgs a) {
 
   // fragment read offsets (compute wave w: output rows 8w..8w+7): halo rows 8 * wave + r (r = 0..9), column pc + kx, slot g
   unsigned boff[3];
-#pragma unroll
-  for (int kx = 0; kx < 3; ++kx) {
-    const int hx = pc + kx;
-    boff[kx] = (unsigned)(((8 * (wave & 3)) * G::HC + hx) * 64 + ((g ^ ((hx >> 1) & 2)) << 4));
-  }
+  r16_frag_offsets(8 * (wave & 3), pc, g, boff);
   unsigned isrc[6];        // loader waves 1..7: byte offset of the lane's 16 bytes of chunk 0 from the image's first pixel record (+ in_coff), or OOB
 
   // ---- control (wave 0): the queue, the tile entries and the dependency counters of the next three items -----------------------------------------
@@ -350,11 +343,7 @@ __global__ void __launch_bounds__(768, 3) conv_trunk_kernel(const TrunkArgs a) {
     const float* b = reinterpret_cast<const float*>(bias);
     const float4 b0 = *reinterpret_cast<const float4*>(b + 8 * g);
     const float4 b1 = *reinterpret_cast<const float4*>(b + 8 * g + 4);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      acc[i][0] = f32x4{b0.x, b0.y, b0.z, b0.w};
-      acc[i][1] = f32x4{b1.x, b1.y, b1.z, b1.w};
-    }
+    r16_zero_acc(acc, b0, b1);
   };
   // A chunk is 18 tap steps of 8 MFMAs: for kx: for row group grp (rows 4 grp .. + 3): for ky — every accumulator still meets its taps in
   // conv_rows16's order (kx-major), so the sums are the same bits. Tap step (kx, grp, ky) multiplies input rows 4 grp + ky + i (i = 0..3) of
@@ -433,12 +422,7 @@ __global__ void __launch_bounds__(768, 3) conv_trunk_kernel(const TrunkArgs a) {
     const float s1 = e.s1, s2 = e.s2;
     const int o_cs = e.o_cs, r1_cs = e.r1_cs, r2_cs = e.r2_cs;
     const bool has1 = e.has1, has2 = e.has2;
-    auto mk = [](const unsigned char* q) {
-      const unsigned long long u = reinterpret_cast<unsigned long long>(q);
-      const unsigned lo = rfl((unsigned)u), hi = rfl((unsigned)(u >> 32));
-      return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<unsigned char*>(((unsigned long long)hi << 32) | lo), 0, 0x7FFFFFF0, 0x00020000);
-    };
-    const auto rs_o = mk(e.ob), rs_r1 = mk(e.r1b), rs_r2 = mk(e.r2b);
+    const auto rs_o = r16_rsrc(e.ob), rs_r1 = r16_rsrc(e.r1b), rs_r2 = r16_rsrc(e.r2b);
     const int ox = it.x0 + pc;
     const int ch0 = it.nb * 32 + 8 * g;
 #pragma unroll
@@ -450,30 +434,8 @@ __global__ void __launch_bounds__(768, 3) conv_trunk_kernel(const TrunkArgs a) {
       u32x4 r1v = {0u, 0u, 0u, 0u}, r2v = r1v;
       if (has1) r1v = __builtin_amdgcn_raw_buffer_load_b128(rs_r1, ok ? (rel * r1_cs + ch0) * 2 : OOB, 0, AUXC);
       if (has2) r2v = __builtin_amdgcn_raw_buffer_load_b128(rs_r2, ok ? (rel * r2_cs + ch0) * 2 : OOB, 0, AUXC);
-      float v[8];
-      v[0] = acc[i][0][0]; v[1] = acc[i][0][1]; v[2] = acc[i][0][2]; v[3] = acc[i][0][3];
-      v[4] = acc[i][1][0]; v[5] = acc[i][1][1]; v[6] = acc[i][1][2]; v[7] = acc[i][1][3];
-      if (act == ACT_LRELU) {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) v[q] = fmaxf(v[q], v[q] * 0.2f);
-      } else if (act == ACT_SILU) {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) v[q] = apply_act(v[q], ACT_SILU);
-      }
-      if (has1) {
-        const _Float16* r = reinterpret_cast<const _Float16*>(&r1v);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) v[q] = v[q] * s1 + (float)r[q];
-      }
-      if (has2) {
-        const _Float16* r = reinterpret_cast<const _Float16*>(&r2v);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) v[q] = v[q] * s2 + (float)r[q];
-      }
-      union { u32x4 u; _Float16 h[8]; } ov;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) ov.h[q] = (_Float16)v[q];
-      __builtin_amdgcn_raw_buffer_store_b128(ov.u, rs_o, ok ? (rel * o_cs + ch0) * 2 : OOB, 0, AUXC);
+      const u32x4 ov = r16_finish_px(acc[i][0], acc[i][1], act, has1, r1v, s1, has2, r2v, s2);
+      __builtin_amdgcn_raw_buffer_store_b128(ov, rs_o, ok ? (rel * o_cs + ch0) * 2 : OOB, 0, AUXC);
     }
   };
   // ---- the epilogue's other form. Global stores issue at ~14 B/clk per CU: an item's 32 KiB cost its compute waves ~4 us with the matrix pipe
@@ -484,28 +446,15 @@ __global__ void __launch_bounds__(768, 3) conv_trunk_kernel(const TrunkArgs a) {
   auto xchg_write = [&](unsigned char* xs, int act) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-      float v[8];
-      v[0] = acc[i][0][0]; v[1] = acc[i][0][1]; v[2] = acc[i][0][2]; v[3] = acc[i][0][3];
-      v[4] = acc[i][1][0]; v[5] = acc[i][1][1]; v[6] = acc[i][1][2]; v[7] = acc[i][1][3];
-      if (act == ACT_LRELU) {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) v[q] = fmaxf(v[q], v[q] * 0.2f);
-      } else if (act == ACT_SILU) {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) v[q] = apply_act(v[q], ACT_SILU);
-      }
-      union { uint4 u; _Float16 h[8]; } ov;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) ov.h[q] = (_Float16)v[q];
-      *reinterpret_cast<uint4*>(xs + ((8 * (wave & 3) + i) << 10) + lane * 16) = ov.u;
+      const u32x4 none = {0u, 0u, 0u, 0u};
+      *reinterpret_cast<u32x4*>(xs + ((8 * (wave & 3) + i) << 10) + lane * 16) = r16_finish_px(acc[i][0], acc[i][1], act, false, none, 0.f, false, none, 0.f);
     }
   };
   auto xchg_store = [&](const unsigned char* xs, const Item& it) {
     const LPtr L = layers + it.layer;
     const int o_cs = L->out_cs;
     unsigned char* ob = reinterpret_cast<unsigned char*>(L->out) + ((long long)it.px0 * o_cs + L->out_coff) * 2;
-    const unsigned long long u = reinterpret_cast<unsigned long long>(ob);
-    const auto rs_o = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<unsigned char*>(((unsigned long long)rfl((unsigned)(u >> 32)) << 32) | rfl((unsigned)u)), 0, 0x7FFFFFF0, 0x00020000);
+    const auto rs_o = r16_rsrc(ob);
     const int ox = it.x0 + pc, ch0 = it.nb * 32 + 8 * g;
     u32x4 d[4];
 #pragma unroll
