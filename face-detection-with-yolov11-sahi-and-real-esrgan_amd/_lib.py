@@ -22,6 +22,8 @@ LIB_PATH = os.environ.get("FFP_LIB") or os.path.join(_HERE, "libffp.so")
 PREC_F32, PREC_F16, PREC_F32X3 = 0, 1, 2
 SR_ALPHA_REALESRGAN, SR_ALPHA_LINEAR = 0, 1          # ffp_sr_enhance_ex alpha_mode (include/ffp.h)
 CHAN_AS_BGR, CHAN_AS_RGB = 0, 1
+IQA_F32_CHW, IQA_U8_HWC = 0, 1                       # ffp_iqa_niqe_features layout
+NIQE_FEATURES = 36
 PP_NMS, PP_GREEDYNMM = 0, 1
 METRIC_IOU, METRIC_IOS = 0, 1
 PP_TYPES = {"NMS": PP_NMS, "GREEDYNMM": PP_GREEDYNMM}
@@ -159,6 +161,13 @@ _SIGS = {
     "ffp_rtdetr_set_profile": (C.c_int, [C.c_void_p, C.c_int]),
     "ffp_rtdetr_profile_count": (C.c_int, [C.c_void_p, _p(C.c_int32)]),
     "ffp_rtdetr_profile_get": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_int, _p(C.c_float)]),
+    "ffp_iqa_create": (C.c_int, [C.c_int, _p(C.c_void_p)]),
+    "ffp_iqa_destroy": (None, [C.c_void_p]),
+    "ffp_iqa_niqe_blocks": (C.c_int, [C.c_int, C.c_int, _p(C.c_int64)]),
+    "ffp_iqa_niqe_features": (C.c_int, [C.c_void_p, C.c_int, _p(C.c_void_p), _p(C.c_int32), _p(C.c_int32), _p(C.c_int32), C.c_int, C.c_int, C.c_int,
+                                        _p(C.c_double), _p(C.c_double), C.c_int64, _p(C.c_int64)]),
+    "ffp_iqa_niqe_luma": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_float)]),
+    "ffp_iqa_niqe_score": (C.c_int, [_p(C.c_double), _p(C.c_int64), C.c_int, _p(C.c_double), _p(C.c_double), _p(C.c_double)]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -1038,3 +1047,101 @@ def op_conv2d_time(n, h, w, cin, cout, k=3, stride=1, up=False, precision=PREC_F
     us = C.c_float(0)
     _check(lib().ffp_op_conv2d_time(device, precision, n, h, w, cin, cout, k, stride, int(up), iters, dbg, shape, C.byref(us)))
     return us.value
+
+
+def niqe_blocks(h: int, w: int) -> int:
+    """96x96 blocks of an h x w image (host)."""
+    n = C.c_int64(0)
+    _check(lib().ffp_iqa_niqe_blocks(int(h), int(w), C.byref(n)))
+    return n.value
+
+
+def niqe_score(feat: np.ndarray, block_off: np.ndarray, mu: np.ndarray, cov: np.ndarray) -> np.ndarray:
+    """ffp_iqa_niqe_score (host, float64): one score per image from [blocks, 36] features and the pristine model."""
+    f = np.ascontiguousarray(feat, np.float64).reshape(-1, NIQE_FEATURES)
+    off = np.ascontiguousarray(block_off, np.int64)
+    m = np.ascontiguousarray(np.asarray(mu, np.float64).reshape(-1))
+    c = np.ascontiguousarray(cov, np.float64)
+    if m.shape != (NIQE_FEATURES,) or c.shape != (NIQE_FEATURES, NIQE_FEATURES):
+        raise ValueError(f"the NIQE model is a 36-vector and a 36x36 matrix, got {m.shape} and {c.shape}")
+    if off.ndim != 1 or off.size < 1 or off[-1] != f.shape[0]:
+        raise ValueError("block offsets do not match the feature rows")
+    out = np.zeros(off.size - 1, np.float64)
+    dp = _p(C.c_double)
+    _check(lib().ffp_iqa_niqe_score(f.ctypes.data_as(dp), off.ctypes.data_as(_p(C.c_int64)), off.size - 1, m.ctypes.data_as(dp), c.ctypes.data_as(dp),
+                                    out.ctypes.data_as(dp)))
+    return out
+
+
+class IQA:
+    """No-reference image quality on one GPU (ffp_iqa_*): NIQE block features on the device, the score in float64 on the host."""
+
+    def __init__(self, device: int = 0):
+        self._h = C.c_void_p()
+        self.device = device
+        _check(lib().ffp_iqa_create(device, C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            lib().ffp_iqa_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def niqe_features(self, images: Sequence[np.ndarray], chan_order: int = CHAN_AS_RGB) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """A ragged batch, all images in one form: float32 planar (C, H, W) or (H, W) in [0,1] (RGB), or uint8 (H, W, C) or (H, W) in
+        `chan_order`; C is 1 or 3. Returns features [blocks, 36] float64, per-block sharpness [blocks] and block offsets [n + 1]."""
+        ims = [np.ascontiguousarray(i) for i in images]
+        if not ims:
+            raise ValueError("no images")
+        kinds = {i.dtype == np.uint8 for i in ims}
+        if len(kinds) != 1 or any(i.dtype not in (np.uint8, np.float32) for i in ims):
+            raise ValueError("images must be all uint8 (H, W, C) or all float32 (C, H, W)")
+        u8 = ims[0].dtype == np.uint8
+        shp = []
+        for i in ims:
+            if i.ndim == 2:
+                shp.append((i.shape[0], i.shape[1], 1))
+            elif i.ndim == 3:
+                shp.append((i.shape[0], i.shape[1], i.shape[2]) if u8 else (i.shape[1], i.shape[2], i.shape[0]))
+            else:
+                raise ValueError(f"expected a 2-d or 3-d image, got shape {i.shape}")
+        return self._features([i.ctypes.data for i in ims], shp, IQA_U8_HWC if u8 else IQA_F32_CHW, chan_order, False)
+
+    def luma(self, image: np.ndarray, chan_order: int = CHAN_AS_RGB) -> np.ndarray:
+        """The rounded luma of one image's crop (ffp_iqa_niqe_luma): float32 holding integers 0..255."""
+        a = np.ascontiguousarray(image)
+        u8 = a.dtype == np.uint8
+        if a.dtype not in (np.uint8, np.float32) or a.ndim not in (2, 3):
+            raise ValueError(f"expected a uint8 (H, W, C) or float32 (C, H, W) image, got {a.dtype} {a.shape}")
+        h, w, c = (a.shape[0], a.shape[1], 1) if a.ndim == 2 else ((a.shape[0], a.shape[1], a.shape[2]) if u8 else (a.shape[1], a.shape[2], a.shape[0]))
+        out = np.zeros((max(h // 96 * 96, 1), max(w // 96 * 96, 1)), np.float32)
+        _check(lib().ffp_iqa_niqe_luma(self._h, a.ctypes.data, h, w, c, IQA_U8_HWC if u8 else IQA_F32_CHW, int(chan_order), _fp(out)))
+        return out
+
+    def niqe_features_dev(self, ptrs: Sequence[int], shapes: Sequence[Tuple[int, int, int]]) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The same for float32 planar images already in device memory: pointers and (C, H, W) per image; the caller has synchronised."""
+        return self._features(list(ptrs), [(h, w, c) for c, h, w in shapes], IQA_F32_CHW, CHAN_AS_RGB, True)
+
+    def _features(self, ptrs, shp, layout, chan_order, on_device):
+        n = len(ptrs)
+        hs = np.asarray([s[0] for s in shp], np.int32)
+        ws = np.asarray([s[1] for s in shp], np.int32)
+        cs = np.asarray([s[2] for s in shp], np.int32)
+        nb = max(1, sum((int(h) // 96) * (int(w) // 96) for h, w in zip(hs, ws)))
+        feat = np.zeros((nb, NIQE_FEATURES), np.float64)
+        sharp = np.zeros(nb, np.float64)
+        off = np.zeros(n + 1, np.int64)
+        ip = (C.c_void_p * n)(*ptrs)
+        _check(lib().ffp_iqa_niqe_features(self._h, n, ip, _ip(hs), _ip(ws), _ip(cs), layout, int(chan_order), int(on_device),
+                                           feat.ctypes.data_as(_p(C.c_double)), sharp.ctypes.data_as(_p(C.c_double)), nb, off.ctypes.data_as(_p(C.c_int64))))
+        return feat[:off[-1]], sharp[:off[-1]], off
+
+    def niqe(self, images: Sequence[np.ndarray], mu: np.ndarray, cov: np.ndarray, chan_order: int = CHAN_AS_RGB) -> np.ndarray:
+        """One NIQE score (float64, lower is better) per image against the pristine model (mu [36], cov [36, 36])."""
+        feat, _, off = self.niqe_features(images, chan_order)
+        return niqe_score(feat, off, mu, cov)

@@ -6,6 +6,7 @@
 
 #include "coco_eval.hpp"
 #include "eval.hpp"
+#include "iqa.hpp"
 #include "jpeg.hpp"
 #include "sr_ops.hpp"
 #include "scrfd.hpp"
@@ -19,6 +20,7 @@ const std::string& last_error();
 struct ffp_det { ffp::DetEngine eng; ffp_det(const void* w, size_t n, int a, int nc, int nk, int dev, int pr) : eng(w, n, a, nc, nk, dev, pr) {} };
 struct ffp_rtdetr { ffp::RtdetrEngine eng; ffp_rtdetr(const void* b, size_t nb, int dev, int pr) : eng(b, nb, dev, pr) {} };
 struct ffp_scrfd { ffp::ScrfdEngine eng; ffp_scrfd(const void* b, size_t nb, int n, int dev, int pr) : eng(b, nb, n, dev, pr) {} };
+struct ffp_iqa { ffp::IqaEngine eng; explicit ffp_iqa(int dev) : eng(dev) {} };
 struct ffp_sr { ffp::SrEngine eng; ffp_sr(const void* w, size_t n, int s, int nb, int dev, int h) : eng(w, n, s, nb, dev, h) {} };
 
 using namespace ffp;
@@ -676,6 +678,46 @@ int ffp_eval_dual_match(int device, const double* preds, const int64_t* pred_off
     throw;
   }
   (void)hipStreamDestroy(st);
+  FFP_API_END
+}
+
+// ---- NIQE (pyiqa.create_metric('niqe')) ------------------------------------------------------------------------------------------
+int ffp_iqa_create(int device, ffp_iqa** out) {
+  FFP_API_BEGIN
+  FFP_CHECK(out, FFP_ERR_ARG, "iqa_create: null output");
+  *out = new ffp_iqa(device);
+  FFP_API_END
+}
+
+void ffp_iqa_destroy(ffp_iqa* q) { delete q; }
+
+int ffp_iqa_niqe_blocks(int h, int w, int64_t* out_blocks) {
+  if (!out_blocks || h <= 0 || w <= 0) { ffp::set_last_error("iqa_niqe_blocks: bad arguments"); return FFP_ERR_ARG; }
+  *out_blocks = niqe_blocks(h, w);
+  return FFP_OK;
+}
+
+int ffp_iqa_niqe_features(ffp_iqa* q, int n, const void* const* imgs, const int32_t* h, const int32_t* w, const int32_t* c, int layout,
+                          int chan_order, int on_device, double* out_feat, double* out_sharp, int64_t cap_blocks, int64_t* out_block_off) {
+  FFP_API_BEGIN
+  FFP_CHECK(q, FFP_ERR_ARG, "iqa_niqe_features: null handle");
+  q->eng.niqe_features(n, imgs, h, w, c, layout, chan_order, on_device != 0, out_feat, out_sharp, cap_blocks, out_block_off);
+  FFP_API_END
+}
+
+int ffp_iqa_niqe_luma(ffp_iqa* q, const void* img, int h, int w, int c, int layout, int chan_order, float* out_y) {
+  FFP_API_BEGIN
+  FFP_CHECK(q, FFP_ERR_ARG, "iqa_niqe_luma: null handle");
+  q->eng.luma(img, h, w, c, layout, chan_order, out_y);
+  FFP_API_END
+}
+
+int ffp_iqa_niqe_score(const double* feat, const int64_t* block_off, int n, const double* mu, const double* cov, double* out_scores) {
+  FFP_API_BEGIN
+    FFP_CHECK(n >= 0 && mu && cov && out_scores, FFP_ERR_ARG, "iqa_niqe_score: bad arguments");
+    check_offsets(block_off, n, "block");
+    FFP_CHECK(block_off[n] == 0 || feat, FFP_ERR_ARG, "iqa_niqe_score: null features");
+    niqe_score(feat, block_off, n, mu, cov, out_scores);
   FFP_API_END
 }
 

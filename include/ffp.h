@@ -510,6 +510,41 @@ int ffp_rtdetr_set_profile(ffp_rtdetr* r, int on);
 int ffp_rtdetr_profile_count(ffp_rtdetr* r, int32_t* out_n);
 int ffp_rtdetr_profile_get(ffp_rtdetr* r, int i, char* name, int name_cap, float* out_ms);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * No-reference image quality: NIQE — replaces pyiqa.create_metric('niqe', device=...) and the call of the metric on an image
+ * tensor (pipeline_v4_yolo/1_Inference.py:122-126 and :171-176). The algorithm is Mittal et al. 2013 with pyiqa 0.1.x's choices
+ * as DESIGN.md states them; parity with pyiqa itself has not been run. BRISQUE is not built.
+ * ------------------------------------------------------------------------------------------------------- */
+#define FFP_IQA_F32_CHW 0 /* float32 planar C x H x W in [0,1], RGB: the tensor pyiqa's metrics are called with */
+#define FFP_IQA_U8_HWC 1  /* uint8 H x W x C, channel order FFP_CHAN_AS_BGR / FFP_CHAN_AS_RGB */
+#define FFP_NIQE_FEATURES 36
+
+typedef struct ffp_iqa ffp_iqa;
+
+/* pyiqa.create_metric(name, device=device) (1_Inference.py:124): the engine holds the device, a stream, the AGGD Gamma tables and
+ * the filter taps. The pristine model (pyiqa's niqe_modelparameters.mat) is an argument of the score call, not of the engine. */
+int ffp_iqa_create(int device, ffp_iqa** out);
+void ffp_iqa_destroy(ffp_iqa* q);
+/* Host: number of 96x96 blocks of an h x w image, floor(h / 96) * floor(w / 96), to size the buffers of the next call. */
+int ffp_iqa_niqe_blocks(int h, int w, int64_t* out_blocks);
+/* The feature half of pyiqa's niqe() for a ragged batch (what `metric(img_tensor)` computes before the distance, :175): image i is
+ * h[i] x w[i] x c[i] (c 1 or 3) in `layout`; chan_order applies to FFP_IQA_U8_HWC with 3 channels. on_device != 0: imgs[i] are
+ * device pointers whose producer the caller has synchronised. Each image is cropped to whole 96x96 blocks from its top-left
+ * corner; an image with fewer than two blocks is FFP_ERR_ARG (one block has no covariance). out_feat [blocks][36] float64 (scale 1, then
+ * scale 2; blocks row-major per image), out_sharp [blocks] = mean local sigma of the scale-1 block (the paper's patch selection),
+ * out_block_off [n + 1]. cap_blocks: capacity of out_feat / out_sharp; more blocks than that is FFP_ERR_ARG. A flat block gives NaN
+ * where its arithmetic does. */
+int ffp_iqa_niqe_features(ffp_iqa* q, int n, const void* const* imgs, const int32_t* h, const int32_t* w, const int32_t* c, int layout,
+                          int chan_order, int on_device, double* out_feat, double* out_sharp, int64_t cap_blocks, int64_t* out_block_off);
+/* Step one of the same alone, for parity tests: the rounded luma (pyiqa's to_y_channel(img, 255, 'yiq').round()) of one host
+ * image's crop, out_y [floor(h / 96) * 96][floor(w / 96) * 96] float32 holding integers 0..255. */
+int ffp_iqa_niqe_luma(ffp_iqa* q, const void* img, int h, int w, int c, int layout, int chan_order, float* out_y);
+/* The distance half of pyiqa's niqe() (host, float64): per image sqrt((mu - m)^T pinv((cov + C) / 2) (mu - m)) with m the
+ * per-feature nanmean of the image's blocks, C their sample covariance over blocks without NaN, and singular values below
+ * 36 * 2.2e-16 * the largest treated as zero. mu [36], cov [36][36]: the pristine model (mu_prisparam / cov_prisparam).
+ * out_scores [n]; an image with fewer than two NaN-free blocks scores NaN. */
+int ffp_iqa_niqe_score(const double* feat, const int64_t* block_off, int n, const double* mu, const double* cov, double* out_scores);
+
 #ifdef __cplusplus
 }
 #endif
