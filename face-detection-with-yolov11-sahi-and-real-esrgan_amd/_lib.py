@@ -143,6 +143,19 @@ _SIGS = {
                                   _p(C.c_float), _p(C.c_float), _p(C.c_int32), C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                   _p(C.c_float), _p(C.c_float), _p(C.c_int32)]),
     "ffp_op_rt_topk": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, _p(C.c_int32)]),
+    "ffp_op_rt_dwconv": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, _p(C.c_float), _p(C.c_float), _p(C.c_float), C.c_int, C.c_int, _p(C.c_uint32)]),
+    "ffp_op_rt_maxpool2": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, _p(C.c_uint32)]),
+    "ffp_op_rt_add": (C.c_int, [C.c_int, C.c_longlong, C.c_int, _p(C.c_float), C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, C.c_longlong, _p(C.c_float), C.c_int, C.c_int, _p(C.c_uint32)]),
+    "ffp_op_rt_layernorm": (C.c_int, [C.c_int, C.c_longlong, _p(C.c_float), C.c_int, C.c_int, _p(C.c_float), _p(C.c_float), _p(C.c_float), C.c_int, C.c_int, _p(C.c_uint32)]),
+    "ffp_op_rt_gelu": (C.c_int, [C.c_int, C.c_longlong, C.c_int, _p(C.c_float), C.c_int, C.c_int, _p(C.c_uint32)]),
+    "ffp_op_rt_attention": (C.c_int, [C.c_int, C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, _p(C.c_uint32)]),
+    "ffp_op_rt_enc_prep": (C.c_int, [C.c_int, C.c_int, _p(C.c_int32), _p(C.c_int32), _p(C.c_float), _p(C.c_float), _p(C.c_float), _p(C.c_int32), _p(C.c_int32), _p(C.c_float), C.c_longlong, _p(C.c_float), _p(C.c_float), _p(C.c_uint32), _p(C.c_uint32)]),
+    "ffp_op_rt_gather": (C.c_int, [C.c_int, C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, _p(C.c_int32), _p(C.c_float), _p(C.c_float), C.c_int, C.c_int, _p(C.c_float), _p(C.c_uint32)]),
+    "ffp_op_rt_ref": (C.c_int, [C.c_int, C.c_longlong, _p(C.c_float), C.c_int, C.c_int, _p(C.c_float), _p(C.c_float), C.c_int, C.c_int, _p(C.c_uint32)]),
+    "ffp_op_rt_deform": (C.c_int, [C.c_int, C.c_int, _p(C.c_int32), _p(C.c_int32), _p(C.c_float), C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, _p(C.c_uint32)]),
+    "ffp_op_rt_decode": (C.c_int, [C.c_int, C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, C.c_float, _p(C.c_float), _p(C.c_float), _p(C.c_float), _p(C.c_int32)]),
+    "ffp_op_scrfd_pool": (C.c_int, [C.c_int, C.c_int, _p(C.c_int32), _p(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int]),
+    "ffp_op_scrfd_post": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_int32), C.c_int, _p(_p(C.c_float)), _p(C.c_int32), _p(C.c_int32), _p(C.c_float), C.c_float, C.c_float, C.c_int, _p(C.c_float), _p(C.c_int32), _p(C.c_float)]),
     "ffp_op_resize_lanczos4": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "ffp_scrfd_create": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, _p(C.c_void_p)]),
     "ffp_scrfd_destroy": (None, [C.c_void_p]),
@@ -871,6 +884,208 @@ def op_rt_topk(scores: np.ndarray, nc: Optional[int] = None, s_coff: int = 0, de
     out = np.zeros((n, 300), np.int32)
     _check(lib().ffp_op_rt_topk(device, n, nt, nc, _fp(s), cs, s_coff, _ip(out)))
     return out
+
+
+# ---- the RT-DETR and SCRFD kernels one at a time (tests/test_gpu_rtdetr_ops.py, tests/test_gpu_scrfd_ops.py). Arrays hold whole records
+# (..., cs); outputs are passed in and come back with the slice written. `amax`: None (no slot) or the initial value of the output
+# buffer's max-|value| slot as a float; the operator then returns (output, final slot bits as int).
+def _f32(a):
+    return np.ascontiguousarray(a, np.float32)
+
+
+def _slot(amax):
+    return None if amax is None else np.asarray([np.float32(amax)], np.float32).view(np.uint32).copy()
+
+
+def _up(s):
+    return s.ctypes.data_as(_p(C.c_uint32)) if s is not None else None
+
+
+def _ret(out, s):
+    return out if s is None else (out, int(s[0]))
+
+
+def op_rt_dwconv(x, c: int, x_coff: int, w, b, y, y_coff: int, k: int, s: int, act: int = 0, amax=None, device: int = 0):
+    """x (n, h, w, cs) -> y (n, ho, wo, cs') slice = act(depthwise k x k stride s pad k // 2 + b); w (c, k, k)."""
+    x, y, w, b = _f32(x), _f32(y).copy(), _f32(w), _f32(b)
+    n, h, wd, xcs = x.shape
+    if w.shape != (c, k, k) or b.shape != (c,) or y.shape[:3] != (n, (h - 1) // s + 1, (wd - 1) // s + 1):
+        raise ValueError("rt_dwconv: shapes")
+    sl = _slot(amax)
+    _check(lib().ffp_op_rt_dwconv(device, n, h, wd, c, k, s, act, _fp(x), xcs, x_coff, _fp(w), _fp(b), _fp(y), y.shape[3], y_coff, _up(sl)))
+    return _ret(y, sl)
+
+
+def op_rt_maxpool2(x, c: int, x_coff: int, y, y_coff: int, amax=None, device: int = 0):
+    """HGStem's pool: y slice = max over the 2x2 window at each pixel of x, zeros past the bottom / right edge."""
+    x, y = _f32(x), _f32(y).copy()
+    n, h, wd, xcs = x.shape
+    if y.shape[:3] != (n, h, wd):
+        raise ValueError("rt_maxpool2: shapes")
+    sl = _slot(amax)
+    _check(lib().ffp_op_rt_maxpool2(device, n, h, wd, c, _fp(x), xcs, x_coff, _fp(y), y.shape[3], y_coff, _up(sl)))
+    return _ret(y, sl)
+
+
+def op_rt_add(a, c: int, a_coff: int, b, b_coff: int, y, y_coff: int, period: int = 0, amax=None, device: int = 0):
+    """a (npx, cs), b (period or npx, cs') -> y slice = a + b[p % period] (period 0: b[p])."""
+    a, b, y = _f32(a), _f32(b), _f32(y).copy()
+    if b.shape[0] != (period or a.shape[0]) or y.shape[0] != a.shape[0]:
+        raise ValueError("rt_add: shapes")
+    sl = _slot(amax)
+    _check(lib().ffp_op_rt_add(device, a.shape[0], c, _fp(a), a.shape[1], a_coff, _fp(b), b.shape[1], b_coff, period, _fp(y), y.shape[1], y_coff, _up(sl)))
+    return _ret(y, sl)
+
+
+def op_rt_layernorm(x, x_coff: int, gamma, beta, y, y_coff: int, amax=None, device: int = 0):
+    """LayerNorm over 256 channels, eps 1e-5: x (npx, cs) -> y slice; x None: in place on the slice of y."""
+    y, g, b = _f32(y).copy(), _f32(gamma), _f32(beta)
+    xx = _f32(x) if x is not None else None
+    if g.shape != (256,) or b.shape != (256,) or (xx is not None and xx.shape[0] != y.shape[0]):
+        raise ValueError("rt_layernorm: shapes")
+    sl = _slot(amax)
+    _check(lib().ffp_op_rt_layernorm(device, y.shape[0], _fp(xx) if xx is not None else None, xx.shape[1] if xx is not None else 0, x_coff, _fp(g), _fp(b),
+                                     _fp(y), y.shape[1], y_coff, _up(sl)))
+    return _ret(y, sl)
+
+
+def op_rt_gelu(x, c: int, coff: int, amax=None, device: int = 0):
+    """Exact GELU in place on c channels at coff of x (npx, cs)."""
+    x = _f32(x).copy()
+    sl = _slot(amax)
+    _check(lib().ffp_op_rt_gelu(device, x.shape[0], c, _fp(x), x.shape[1], coff, _up(sl)))
+    return _ret(x, sl)
+
+
+def op_rt_attention(qk, qk_coff: int, v, v_coff: int, y, y_coff: int, amax=None, device: int = 0):
+    """qk (n, L, cs) with [q 256 | k 256] at qk_coff, v (n, L, cs') -> y (n, L, cs'') slice of 256: 8 heads of 32 over each image's tokens."""
+    qk, v, y = _f32(qk), _f32(v), _f32(y).copy()
+    n, L = qk.shape[:2]
+    if v.shape[:2] != (n, L) or y.shape[:2] != (n, L):
+        raise ValueError("rt_attention: shapes")
+    sl = _slot(amax)
+    _check(lib().ffp_op_rt_attention(device, n, L, _fp(qk), qk.shape[2], qk_coff, _fp(v), v.shape[2], v_coff, _fp(y), y.shape[2], y_coff, _up(sl)))
+    return _ret(y, sl)
+
+
+def op_rt_enc_prep(srcs, src_coffs, valid, t, tm, amax_t=None, amax_tm=None, device: int = 0):
+    """srcs: three (n, h_l, w_l, cs_l) arrays with 256 channels at src_coffs[l]; valid (tokens,); t, tm: (rows, 256) with rows >= n * tokens.
+    Returns (t, tm, slot bits of t or None, slot bits of tm or None)."""
+    srcs = [_f32(a) for a in srcs]
+    n = srcs[0].shape[0]
+    hs = np.asarray([a.shape[1] for a in srcs], np.int32)
+    ws = np.asarray([a.shape[2] for a in srcs], np.int32)
+    cs = np.asarray([a.shape[3] for a in srcs], np.int32)
+    co = np.asarray(src_coffs, np.int32)
+    valid, t, tm = _f32(valid), _f32(t).copy(), _f32(tm).copy()
+    if valid.shape != (int((hs * ws).sum()),) or t.shape != tm.shape or t.shape[1] != 256 or any(a.shape[0] != n for a in srcs):
+        raise ValueError("rt_enc_prep: shapes")
+    s1, s2 = _slot(amax_t), _slot(amax_tm)
+    _check(lib().ffp_op_rt_enc_prep(device, n, _ip(hs), _ip(ws), _fp(srcs[0]), _fp(srcs[1]), _fp(srcs[2]), _ip(cs), _ip(co), _fp(valid), t.shape[0],
+                                    _fp(t), _fp(tm), _up(s1), _up(s2)))
+    return t, tm, None if s1 is None else int(s1[0]), None if s2 is None else int(s2[0])
+
+
+def op_rt_gather(e, e_coff: int, idx, anchors, q, q_coff: int, anc, amax=None, device: int = 0):
+    """e (n, NT, cs), idx (n, 300), anchors (NT, 4) -> (q (n, 300, cs') slice of 256, anc (n, 300, 4)) [, slot bits]."""
+    e, q, anchors, anc = _f32(e), _f32(q).copy(), _f32(anchors), _f32(anc).copy()
+    idx = np.ascontiguousarray(idx, np.int32)
+    n, nt = e.shape[:2]
+    if idx.shape != (n, 300) or anchors.shape != (nt, 4) or q.shape[:2] != (n, 300) or anc.shape != (n, 300, 4):
+        raise ValueError("rt_gather: shapes")
+    sl = _slot(amax)
+    _check(lib().ffp_op_rt_gather(device, n, nt, _fp(e), e.shape[2], e_coff, _ip(idx), _fp(anchors), _fp(q), q.shape[2], q_coff, _fp(anc), _up(sl)))
+    return (q, anc) if sl is None else (q, anc, int(sl[0]))
+
+
+def op_rt_ref(delta, d_coff: int, ref, r_coff: int, anc=None, amax=None, device: int = 0):
+    """delta (nq, cs), ref (nq, cs') -> ref slice of 4 = sigmoid(delta + anc) (anc (nq, 4) given) or sigmoid(delta + inverse_sigmoid(ref))."""
+    delta, ref = _f32(delta), _f32(ref).copy()
+    an = _f32(anc) if anc is not None else None
+    if ref.shape[0] != delta.shape[0] or (an is not None and an.shape != (delta.shape[0], 4)):
+        raise ValueError("rt_ref: shapes")
+    sl = _slot(amax)
+    _check(lib().ffp_op_rt_ref(device, delta.shape[0], _fp(delta), delta.shape[1], d_coff, _fp(an) if an is not None else None, _fp(ref), ref.shape[1],
+                               r_coff, _up(sl)))
+    return _ret(ref, sl)
+
+
+def op_rt_deform(shapes, val, v_coff: int, oa, oa_coff: int, ref, r_coff: int, y, y_coff: int, amax=None, device: int = 0):
+    """shapes: three (h, w); val (n, tokens, cs) slice of 256, oa (n, 300, cs') slice of 288, ref (n, 300, cs'') slice of 4 -> y (n, 300, cs''')
+    slice of 256."""
+    val, oa, ref, y = _f32(val), _f32(oa), _f32(ref), _f32(y).copy()
+    hs = np.asarray([s[0] for s in shapes], np.int32)
+    ws = np.asarray([s[1] for s in shapes], np.int32)
+    n = val.shape[0]
+    if val.shape[1] != int((hs * ws).sum()) or oa.shape[:2] != (n, 300) or ref.shape[:2] != (n, 300) or y.shape[:2] != (n, 300):
+        raise ValueError("rt_deform: shapes")
+    sl = _slot(amax)
+    _check(lib().ffp_op_rt_deform(device, n, _ip(hs), _ip(ws), _fp(val), val.shape[2], v_coff, _fp(oa), oa.shape[2], oa_coff, _fp(ref), ref.shape[2],
+                                  r_coff, _fp(y), y.shape[2], y_coff, _up(sl)))
+    return _ret(y, sl)
+
+
+def op_rt_decode(ref, r_coff: int, scores, s_coff: int, nc: int, conf: Optional[float] = None, orig_wh=None, raw=None, det=None, device: int = 0):
+    """ref (n, 300, cs) slice of 4, scores (n, 300, cs') slice of nc logits. raw: (n, 300, 4 + nc) array to fill, or None; det: (n, 300, 6)
+    array to fill (needs conf and orig_wh (n, 2) = width, height), or None. Returns (raw, det, counts)."""
+    ref, scores = _f32(ref), _f32(scores)
+    n = ref.shape[0]
+    if ref.shape[:2] != (n, 300) or scores.shape[:2] != (n, 300):
+        raise ValueError("rt_decode: shapes")
+    o_raw = _f32(raw).copy() if raw is not None else None
+    o_det = _f32(det).copy() if det is not None else None
+    cnt = np.full(n, -1, np.int32) if det is not None else None
+    wh = _f32(orig_wh) if orig_wh is not None else None
+    if (o_raw is not None and o_raw.shape != (n, 300, 4 + nc)) or (o_det is not None and (o_det.shape != (n, 300, 6) or wh is None or wh.shape != (n, 2))):
+        raise ValueError("rt_decode: output shapes")
+    _check(lib().ffp_op_rt_decode(device, n, nc, _fp(ref), ref.shape[2], r_coff, _fp(scores), scores.shape[2], s_coff, float(conf or 0.0),
+                                  _fp(wh) if wh is not None else None, _fp(o_raw) if o_raw is not None else None,
+                                  _fp(o_det) if o_det is not None else None, _ip(cnt) if cnt is not None else None))
+    return o_raw, o_det, cnt
+
+
+def op_scrfd_pool(x, c: int, x_coff: int, y, y_coff: int, maxpool: bool, k: int = 2, px_align: int = 1, device: int = 0) -> List[np.ndarray]:
+    """Ragged batch (lists of (h, w, cs) arrays): MaxPool 3x3 s2 p1, or AveragePool k x k stride k ceil_mode count_include_pad=0."""
+    xf, hs, ws, xcs = _op_pack(x)
+    yf, hs2, ws2, ycs = _op_pack(y)
+    want = ((hs - 1) // 2 + 1, (ws - 1) // 2 + 1) if maxpool else (-(-hs // k), -(-ws // k))
+    _op_same_batch(want[0], want[1], hs2, ws2, "scrfd_pool")
+    _check(lib().ffp_op_scrfd_pool(device, len(hs), _ip(hs), _ip(ws), px_align, c, int(bool(maxpool)), k, _fp(xf), xcs, x_coff, _fp(yf), ycs, y_coff))
+    return _op_unpack(yf, hs2, ws2)
+
+
+def op_scrfd_post(net_hw, A: int, score, bbox, kps, coffs, det_scale, thresh: float, nms_thresh: float, out, strides=(8, 16, 32), px_align: int = 1,
+                  raw_scores: bool = False, device: int = 0):
+    """score / bbox / kps: per level an (n, h_l, w_l, cs) array (kps None: the 6-output variant) holding A / 4A / 10A values per pixel at
+    coffs = (score, bbox, kps offset); scores are logits. out: (n, cap, 21) array to fill. Returns (out, counts[, raw (n, anchors)]):
+    counts[i] = faces kept for image i, above cap when the list was cut."""
+    net_h, net_w = net_hw
+    n = len(det_scale)
+    ptrs = (_p(C.c_float) * 9)()
+    keep = []
+    cs = np.zeros(3, np.int32)
+    for kind, lv in enumerate((score, bbox, kps)):
+        if lv is None:
+            continue
+        for l in range(3):
+            a = _f32(lv[l])
+            if a.shape[:3] != (n, net_h // strides[l], net_w // strides[l]) or (l and a.shape[3] != cs[kind]):
+                raise ValueError("scrfd_post: head shapes")
+            cs[kind] = a.shape[3]
+            keep.append(a)
+            ptrs[3 * kind + l] = _fp(a)
+    co = np.asarray(list(coffs) + [0] * (3 - len(coffs)), np.int32)
+    st = np.asarray(strides, np.int32)
+    ds = _f32(det_scale)
+    o = _f32(out).copy()
+    if o.ndim != 3 or o.shape[0] != n or o.shape[2] != 21:
+        raise ValueError("scrfd_post: out must be (n, cap, 21)")
+    cnt = np.full(n, -1, np.int32)
+    per_img = sum((net_h // s) * (net_w // s) * A for s in strides)
+    rs = np.zeros((n, per_img), np.float32) if raw_scores else None
+    _check(lib().ffp_op_scrfd_post(device, n, net_h, net_w, A, _ip(st), px_align, ptrs, _ip(cs), _ip(co), _fp(ds), thresh, nms_thresh, o.shape[1], _fp(o),
+                                   _ip(cnt), _fp(rs) if rs is not None else None))
+    return (o, cnt, rs) if raw_scores else (o, cnt)
 
 
 def jpeg_encode(img: np.ndarray, quality: int = 95, bgr: bool = False, device: int = 0) -> bytes:

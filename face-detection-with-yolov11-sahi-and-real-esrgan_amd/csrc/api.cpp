@@ -1331,6 +1331,379 @@ int ffp_op_rt_topk(int device, int n, int nt, int nc, const float* scores, int s
   FFP_API_END
 }
 
+// ---- single-operator entry points of the RT-DETR and SCRFD kernels (tests/test_gpu_rtdetr_ops.py, tests/test_gpu_scrfd_ops.py) -------
+// The rt_* kernels address image i at i * h * w without padding, so host arrays go up as they are; the launches are the plans' own.
+namespace {
+
+struct OpSlot {       // a max-|value| slot: the caller's bit pattern goes up, the final one comes back
+  DevBuf d;
+  uint32_t* host;
+  explicit OpSlot(uint32_t* h) : host(h) { if (h) d = upload(h, 1); }
+  unsigned* ptr() const { return host ? d.as<unsigned>() : nullptr; }
+  void fetch() { if (host) FFP_HIP(hipMemcpy(host, d.p, sizeof(uint32_t), hipMemcpyDeviceToHost)); }
+};
+
+void op_check_view4(const char* what, int cs, int coff, int C) {
+  op_check_view(what, cs, coff, C);
+  FFP_CHECK(C % 4 == 0 && cs % 4 == 0 && coff % 4 == 0, FFP_ERR_ARG, "%s: channels, offset and record size must be multiples of 4 (%d at %d of %d)", what, C, coff, cs);
+}
+
+void op_flat_level(Level& L, int n, long long per_image, hipStream_t st) {      // n images of per_image records each
+  FFP_CHECK(per_image >= 1 && per_image <= INT_MAX && n >= 1 && n <= 4096 && (long long)n * per_image <= (1ll << 28), FFP_ERR_ARG,
+            "op: %d images of %lld records", n, per_image);
+  L.build(std::vector<int>(n, 1), std::vector<int>(n, (int)per_image), st);
+}
+
+struct OpView : TView {      // fp32 channels [coff, coff + C) of a buffer of cs-wide records
+  OpView(const DevBuf& b, int cs_, int coff_, int C_, Level* L, unsigned* slot = nullptr) : TView{b.p, F32, cs_, coff_, C_, L} { amax = slot; }
+};
+
+void op_fetch(const DevBuf& b, float* dst, size_t n) { FFP_HIP(hipMemcpy(dst, b.p, n * sizeof(float), hipMemcpyDeviceToHost)); }
+
+void op_rt_levels(const char* what, const int32_t* hs, const int32_t* ws, RtLevels& lv) {
+  FFP_CHECK(hs && ws, FFP_ERR_ARG, "%s: null level sizes", what);
+  lv.start[0] = 0;
+  for (int l = 0; l < 3; ++l) {
+    FFP_CHECK(hs[l] >= 1 && ws[l] >= 1 && hs[l] <= 4096 && ws[l] <= 4096, FFP_ERR_ARG, "%s: level %d is %dx%d", what, l, ws[l], hs[l]);
+    lv.h[l] = hs[l]; lv.w[l] = ws[l];
+    lv.start[l + 1] = lv.start[l] + hs[l] * ws[l];
+  }
+}
+
+}  // namespace
+
+int ffp_op_rt_dwconv(int device, int n, int h, int w, int c, int k, int s, int act, const float* x, int x_cs, int x_coff, const float* wt,
+                     const float* bias, float* y, int y_cs, int y_coff, uint32_t* amax) {
+  FFP_API_BEGIN
+  FFP_CHECK(x && wt && bias && y, FFP_ERR_ARG, "rt_dwconv: null argument");
+  FFP_CHECK((k == 5 && s == 1) || (k == 3 && s == 2), FFP_ERR_ARG, "rt_dwconv: k%d s%d (k5 s1 or k3 s2)", k, s);
+  FFP_CHECK(act == ACT_NONE || act == ACT_RELU, FFP_ERR_ARG, "rt_dwconv: act %d (0 none, 3 ReLU)", act);
+  FFP_CHECK(n >= 1 && n <= 4096 && h >= 1 && w >= 1 && h <= 8192 && w <= 8192, FFP_ERR_ARG, "rt_dwconv: %d images of %dx%d", n, w, h);
+  op_check_view4("rt_dwconv input", x_cs, x_coff, c);
+  op_check_view4("rt_dwconv output", y_cs, y_coff, c);
+  const int ho = (h - 1) / s + 1, wo = (w - 1) / s + 1;
+  OpCtx cx(device, "rt_dwconv");
+  Level Li, Lo;
+  Li.build(std::vector<int>(n, h), std::vector<int>(n, w), cx.st);
+  Lo.build(std::vector<int>(n, ho), std::vector<int>(n, wo), cx.st);
+  const std::vector<float> wp = rtdetr_pack_depthwise(wt, c, k * k);
+  DevBuf dx = upload(x, (size_t)n * h * w * x_cs), dy = upload(y, (size_t)n * ho * wo * y_cs), dw = upload(wp.data(), wp.size()), db = upload(bias, (size_t)c);
+  OpSlot slot(amax);
+  launch_rt_dwconv(OpView(dx, x_cs, x_coff, c, &Li), OpView(dy, y_cs, y_coff, c, &Lo, slot.ptr()), dw.as<float>(), db.as<float>(), k, s, act, cx.st);
+  FFP_HIP(hipStreamSynchronize(cx.st));
+  op_fetch(dy, y, (size_t)n * ho * wo * y_cs);
+  slot.fetch();
+  FFP_API_END
+}
+
+int ffp_op_rt_maxpool2(int device, int n, int h, int w, int c, const float* x, int x_cs, int x_coff, float* y, int y_cs, int y_coff, uint32_t* amax) {
+  FFP_API_BEGIN
+  FFP_CHECK(x && y, FFP_ERR_ARG, "rt_maxpool2: null argument");
+  FFP_CHECK(n >= 1 && n <= 4096 && h >= 1 && w >= 1 && h <= 8192 && w <= 8192, FFP_ERR_ARG, "rt_maxpool2: %d images of %dx%d", n, w, h);
+  op_check_view4("rt_maxpool2 input", x_cs, x_coff, c);
+  op_check_view4("rt_maxpool2 output", y_cs, y_coff, c);
+  OpCtx cx(device, "rt_maxpool2");
+  Level L;
+  L.build(std::vector<int>(n, h), std::vector<int>(n, w), cx.st);
+  const size_t px = (size_t)n * h * w;
+  DevBuf dx = upload(x, px * x_cs), dy = upload(y, px * y_cs);
+  OpSlot slot(amax);
+  launch_rt_maxpool2(OpView(dx, x_cs, x_coff, c, &L), OpView(dy, y_cs, y_coff, c, &L, slot.ptr()), cx.st);
+  FFP_HIP(hipStreamSynchronize(cx.st));
+  op_fetch(dy, y, px * y_cs);
+  slot.fetch();
+  FFP_API_END
+}
+
+int ffp_op_rt_add(int device, long long npx, int c, const float* a, int a_cs, int a_coff, const float* b, int b_cs, int b_coff, long long period,
+                  float* y, int y_cs, int y_coff, uint32_t* amax) {
+  FFP_API_BEGIN
+  FFP_CHECK(a && b && y, FFP_ERR_ARG, "rt_add: null argument");
+  FFP_CHECK(period >= 0 && period <= npx, FFP_ERR_ARG, "rt_add: period %lld of %lld records", period, npx);
+  op_check_view4("rt_add a", a_cs, a_coff, c);
+  op_check_view4("rt_add b", b_cs, b_coff, c);
+  op_check_view4("rt_add output", y_cs, y_coff, c);
+  OpCtx cx(device, "rt_add");
+  Level L;
+  op_flat_level(L, 1, npx, cx.st);
+  DevBuf da = upload(a, (size_t)npx * a_cs), db = upload(b, (size_t)(period ? period : npx) * b_cs), dy = upload(y, (size_t)npx * y_cs);
+  OpSlot slot(amax);
+  launch_rt_add(OpView(da, a_cs, a_coff, c, &L), db.as<float>() + b_coff, b_cs, period, OpView(dy, y_cs, y_coff, c, &L, slot.ptr()), cx.st);
+  FFP_HIP(hipStreamSynchronize(cx.st));
+  op_fetch(dy, y, (size_t)npx * y_cs);
+  slot.fetch();
+  FFP_API_END
+}
+
+int ffp_op_rt_layernorm(int device, long long npx, const float* x, int x_cs, int x_coff, const float* gamma, const float* beta, float* y, int y_cs,
+                        int y_coff, uint32_t* amax) {
+  FFP_API_BEGIN
+  FFP_CHECK(gamma && beta && y, FFP_ERR_ARG, "rt_layernorm: null argument");
+  if (x) op_check_view4("rt_layernorm input", x_cs, x_coff, 256);
+  op_check_view4("rt_layernorm output", y_cs, y_coff, 256);
+  OpCtx cx(device, "rt_layernorm");
+  Level L;
+  op_flat_level(L, 1, npx, cx.st);
+  DevBuf dy = upload(y, (size_t)npx * y_cs), dx, dg = upload(gamma, (size_t)256), db = upload(beta, (size_t)256);
+  if (x) dx = upload(x, (size_t)npx * x_cs);
+  OpSlot slot(amax);
+  const TView out = OpView(dy, y_cs, y_coff, 256, &L, slot.ptr());
+  launch_rt_layernorm(x ? OpView(dx, x_cs, x_coff, 256, &L) : out, dg.as<float>(), db.as<float>(), out, cx.st);
+  FFP_HIP(hipStreamSynchronize(cx.st));
+  op_fetch(dy, y, (size_t)npx * y_cs);
+  slot.fetch();
+  FFP_API_END
+}
+
+int ffp_op_rt_gelu(int device, long long npx, int c, float* x, int cs, int coff, uint32_t* amax) {
+  FFP_API_BEGIN
+  FFP_CHECK(x, FFP_ERR_ARG, "rt_gelu: null argument");
+  op_check_view4("rt_gelu", cs, coff, c);
+  OpCtx cx(device, "rt_gelu");
+  Level L;
+  op_flat_level(L, 1, npx, cx.st);
+  DevBuf dx = upload(x, (size_t)npx * cs);
+  OpSlot slot(amax);
+  launch_rt_gelu(OpView(dx, cs, coff, c, &L, slot.ptr()), cx.st);
+  FFP_HIP(hipStreamSynchronize(cx.st));
+  op_fetch(dx, x, (size_t)npx * cs);
+  slot.fetch();
+  FFP_API_END
+}
+
+int ffp_op_rt_attention(int device, int n, int L, const float* qk, int qk_cs, int qk_coff, const float* v, int v_cs, int v_coff, float* y, int y_cs,
+                        int y_coff, uint32_t* amax) {
+  FFP_API_BEGIN
+  FFP_CHECK(qk && v && y, FFP_ERR_ARG, "rt_attention: null argument");
+  op_check_view("rt_attention qk", qk_cs, qk_coff, 512);
+  op_check_view("rt_attention v", v_cs, v_coff, 256);
+  op_check_view("rt_attention output", y_cs, y_coff, 256);
+  OpCtx cx(device, "rt_attention");
+  Level Lv;
+  op_flat_level(Lv, n, L, cx.st);
+  const size_t tok = (size_t)n * L;
+  DevBuf dq = upload(qk, tok * qk_cs), dv = upload(v, tok * v_cs), dy = upload(y, tok * y_cs);
+  OpSlot slot(amax);
+  launch_rt_attention(OpView(dq, qk_cs, qk_coff, 512, &Lv), OpView(dv, v_cs, v_coff, 256, &Lv), OpView(dy, y_cs, y_coff, 256, &Lv, slot.ptr()), L, cx.st);
+  FFP_HIP(hipStreamSynchronize(cx.st));
+  op_fetch(dy, y, tok * y_cs);
+  slot.fetch();
+  FFP_API_END
+}
+
+int ffp_op_rt_enc_prep(int device, int n, const int32_t* hs, const int32_t* ws, const float* src0, const float* src1, const float* src2,
+                       const int32_t* src_cs, const int32_t* src_coff, const float* valid, long long rows, float* t, float* tm, uint32_t* amax_t,
+                       uint32_t* amax_tm) {
+  FFP_API_BEGIN
+  FFP_CHECK(src0 && src1 && src2 && src_cs && src_coff && valid && t && tm, FFP_ERR_ARG, "rt_enc_prep: null argument");
+  RtLevels lv{};
+  op_rt_levels("rt_enc_prep", hs, ws, lv);
+  const int NT = lv.start[3];
+  FFP_CHECK(n >= 1 && n <= 4096 && NT >= 1 && rows >= (long long)n * NT && rows <= (1ll << 24), FFP_ERR_ARG, "rt_enc_prep: %d images of %d tokens in %lld records", n, NT, rows);
+  for (int l = 0; l < 3; ++l) op_check_view4("rt_enc_prep level", src_cs[l], src_coff[l], 256);
+  OpCtx cx(device, "rt_enc_prep");
+  const float* src[3] = {src0, src1, src2};
+  DevBuf ds[3];
+  for (int l = 0; l < 3; ++l) {
+    ds[l] = upload(src[l], (size_t)n * lv.h[l] * lv.w[l] * src_cs[l]);
+    lv.src[l] = ds[l].as<float>() + src_coff[l];
+    lv.src_cs[l] = src_cs[l];
+  }
+  Level LT;
+  op_flat_level(LT, n, NT, cx.st);
+  DevBuf dv = upload(valid, (size_t)NT), dt = upload(t, (size_t)rows * 256), dtm = upload(tm, (size_t)rows * 256);
+  OpSlot st(amax_t), stm(amax_tm);
+  launch_rt_enc_prep(lv, dv.as<float>(), OpView(dt, 256, 0, 256, &LT, st.ptr()), OpView(dtm, 256, 0, 256, &LT, stm.ptr()), n, cx.st);
+  FFP_HIP(hipStreamSynchronize(cx.st));
+  op_fetch(dt, t, (size_t)rows * 256);
+  op_fetch(dtm, tm, (size_t)rows * 256);
+  st.fetch();
+  stm.fetch();
+  FFP_API_END
+}
+
+int ffp_op_rt_gather(int device, int n, int nt, const float* e, int e_cs, int e_coff, const int32_t* idx, const float* anchors, float* q, int q_cs,
+                     int q_coff, float* anc_out, uint32_t* amax) {
+  FFP_API_BEGIN
+  FFP_CHECK(e && idx && anchors && q && anc_out, FFP_ERR_ARG, "rt_gather: null argument");
+  FFP_CHECK(nt >= 1 && nt <= (1 << 22), FFP_ERR_ARG, "rt_gather: %d tokens", nt);
+  op_check_view4("rt_gather tokens", e_cs, e_coff, 256);
+  op_check_view4("rt_gather queries", q_cs, q_coff, 256);
+  OpCtx cx(device, "rt_gather");
+  Level LT, LQ;
+  op_flat_level(LT, n, nt, cx.st);
+  op_flat_level(LQ, n, RT_NQ, cx.st);
+  const size_t nq = (size_t)n * RT_NQ;
+  DevBuf de = upload(e, (size_t)n * nt * e_cs), di = upload(idx, nq), da = upload(anchors, (size_t)nt * 4), dq = upload(q, nq * q_cs), dan = upload(anc_out, nq * 4);
+  OpSlot slot(amax);
+  // the kernel takes whole 256-channel records: the slices start at the views' pointers
+  TView ve{de.as<float>() + e_coff, F32, e_cs, 0, 256, &LT}, vq{dq.as<float>() + q_coff, F32, q_cs, 0, 256, &LQ};
+  vq.amax = slot.ptr();
+  launch_rt_gather(ve, di.as<int>(), da.as<float>(), nt, n, vq, dan.as<float>(), cx.st);
+  FFP_HIP(hipStreamSynchronize(cx.st));
+  op_fetch(dq, q, nq * q_cs);
+  op_fetch(dan, anc_out, nq * 4);
+  slot.fetch();
+  FFP_API_END
+}
+
+int ffp_op_rt_ref(int device, long long nq, const float* delta, int d_cs, int d_coff, const float* anc, float* ref, int r_cs, int r_coff,
+                  uint32_t* amax) {
+  FFP_API_BEGIN
+  FFP_CHECK(delta && ref, FFP_ERR_ARG, "rt_ref: null argument");
+  op_check_view("rt_ref delta", d_cs, d_coff, 4);
+  op_check_view("rt_ref boxes", r_cs, r_coff, 4);
+  OpCtx cx(device, "rt_ref");
+  Level L;
+  op_flat_level(L, 1, nq, cx.st);
+  DevBuf dd = upload(delta, (size_t)nq * d_cs), dr = upload(ref, (size_t)nq * r_cs), da;
+  if (anc) da = upload(anc, (size_t)nq * 4);
+  OpSlot slot(amax);
+  launch_rt_ref(OpView(dd, d_cs, d_coff, 4, &L), anc ? da.as<float>() : nullptr, OpView(dr, r_cs, r_coff, 4, &L, slot.ptr()), cx.st);
+  FFP_HIP(hipStreamSynchronize(cx.st));
+  op_fetch(dr, ref, (size_t)nq * r_cs);
+  slot.fetch();
+  FFP_API_END
+}
+
+int ffp_op_rt_deform(int device, int n, const int32_t* hs, const int32_t* ws, const float* val, int v_cs, int v_coff, const float* oa, int oa_cs,
+                     int oa_coff, const float* ref, int r_cs, int r_coff, float* y, int y_cs, int y_coff, uint32_t* amax) {
+  FFP_API_BEGIN
+  FFP_CHECK(val && oa && ref && y, FFP_ERR_ARG, "rt_deform: null argument");
+  RtLevels lv{};
+  op_rt_levels("rt_deform", hs, ws, lv);
+  const int NT = lv.start[3];
+  op_check_view("rt_deform values", v_cs, v_coff, 256);
+  op_check_view("rt_deform offsets and weights", oa_cs, oa_coff, 288);
+  op_check_view("rt_deform boxes", r_cs, r_coff, 4);
+  op_check_view("rt_deform output", y_cs, y_coff, 256);
+  OpCtx cx(device, "rt_deform");
+  Level LT, LQ;
+  op_flat_level(LT, n, NT, cx.st);
+  op_flat_level(LQ, n, RT_NQ, cx.st);
+  const size_t nq = (size_t)n * RT_NQ;
+  DevBuf dv = upload(val, (size_t)n * NT * v_cs), doa = upload(oa, nq * oa_cs), dr = upload(ref, nq * r_cs), dy = upload(y, nq * y_cs);
+  OpSlot slot(amax);
+  launch_rt_deform(OpView(dv, v_cs, v_coff, 256, &LT), OpView(doa, oa_cs, oa_coff, 288, &LQ), OpView(dr, r_cs, r_coff, 4, &LQ), lv,
+                   OpView(dy, y_cs, y_coff, 256, &LQ, slot.ptr()), cx.st);
+  FFP_HIP(hipStreamSynchronize(cx.st));
+  op_fetch(dy, y, nq * y_cs);
+  slot.fetch();
+  FFP_API_END
+}
+
+int ffp_op_rt_decode(int device, int n, int nc, const float* ref, int r_cs, int r_coff, const float* scores, int s_cs, int s_coff, float conf,
+                     const float* orig_wh, float* out_raw, float* out_det, int32_t* out_counts) {
+  FFP_API_BEGIN
+  FFP_CHECK(ref && scores && nc >= 1 && nc <= 4096, FFP_ERR_ARG, "rt_decode: bad arguments");
+  FFP_CHECK((out_det != nullptr) == (out_counts != nullptr) && (out_raw || out_det) && (!out_det || orig_wh), FFP_ERR_ARG,
+            "rt_decode: det, counts and orig_wh come together, and something must be asked for");
+  op_check_view("rt_decode boxes", r_cs, r_coff, 4);
+  op_check_view("rt_decode scores", s_cs, s_coff, nc);
+  OpCtx cx(device, "rt_decode");
+  Level LQ;
+  op_flat_level(LQ, n, RT_NQ, cx.st);
+  const size_t nq = (size_t)n * RT_NQ;
+  DevBuf dr = upload(ref, nq * r_cs), ds = upload(scores, nq * s_cs);
+  const TView vr = OpView(dr, r_cs, r_coff, 4, &LQ), vs = OpView(ds, s_cs, s_coff, nc, &LQ);
+  if (out_raw) {
+    DevBuf d_raw = upload(out_raw, nq * (4 + nc));
+    launch_rt_raw(vr, vs, nc, d_raw.as<float>(), cx.st);
+    FFP_HIP(hipStreamSynchronize(cx.st));
+    op_fetch(d_raw, out_raw, nq * (4 + nc));
+  }
+  if (out_det) {
+    DevBuf d_det = upload(out_det, nq * 6), d_wh = upload(orig_wh, (size_t)n * 2), d_counts = upload(out_counts, (size_t)n);
+    launch_rt_post(vr, vs, nc, conf, d_wh.as<float2>(), n, d_det.as<float>(), d_counts.as<int>(), cx.st);
+    FFP_HIP(hipStreamSynchronize(cx.st));
+    op_fetch(d_det, out_det, nq * 6);
+    FFP_HIP(hipMemcpy(out_counts, d_counts.p, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
+  }
+  FFP_API_END
+}
+
+int ffp_op_scrfd_pool(int device, int n, const int32_t* hs, const int32_t* ws, int px_align, int c, int maxpool, int k, const float* x, int x_cs,
+                      int x_coff, float* y, int y_cs, int y_coff) {
+  FFP_API_BEGIN
+  FFP_CHECK(x && y, FFP_ERR_ARG, "scrfd_pool: null argument");
+  FFP_CHECK(maxpool || (k >= 1 && k <= 8), FFP_ERR_ARG, "scrfd_pool: average window %d outside [1, 8]", k);
+  op_check_batch("scrfd_pool", n, hs, ws, px_align);
+  op_check_view("scrfd_pool input", x_cs, x_coff, c);
+  op_check_view("scrfd_pool output", y_cs, y_coff, c);
+  OpCtx cx(device, "scrfd_pool");
+  std::vector<int> ho(n), wo(n);
+  for (int i = 0; i < n; ++i) {
+    ho[i] = maxpool ? (hs[i] - 1) / 2 + 1 : (hs[i] + k - 1) / k;
+    wo[i] = maxpool ? (ws[i] - 1) / 2 + 1 : (ws[i] + k - 1) / k;
+  }
+  Level Li, Lo;
+  Li.build(std::vector<int>(hs, hs + n), std::vector<int>(ws, ws + n), cx.st, px_align);
+  Lo.build(ho, wo, cx.st, px_align);
+  DevBuf dx = op_upload(Li, F32, x, x_cs), dy = op_upload(Lo, F32, y, y_cs);
+  launch_scrfd_pool(OpView(dx, x_cs, x_coff, c, &Li), OpView(dy, y_cs, y_coff, c, &Lo), maxpool ? 1 : 0, k, cx.st);
+  FFP_HIP(hipStreamSynchronize(cx.st));
+  op_download(Lo, F32, dy, y_cs, y);
+  FFP_API_END
+}
+
+int ffp_op_scrfd_post(int device, int n, int net_h, int net_w, int A, const int32_t* strides, int px_align, const float* const* heads,
+                      const int32_t* cs, const int32_t* coff, const float* det_scale, float thresh, float nms_thresh, int cap, float* out,
+                      int32_t* out_counts, float* raw_scores) {
+  FFP_API_BEGIN
+  FFP_CHECK(strides && heads && cs && coff && det_scale && out && out_counts, FFP_ERR_ARG, "scrfd_post: null argument");
+  FFP_CHECK(n >= 1 && n <= 4096 && A >= 1 && A <= 16 && cap >= 1 && cap <= (1 << 20) && px_align >= 1 && px_align <= 4096 && net_h >= 1 && net_w >= 1 &&
+                net_h <= 8192 && net_w <= 8192, FFP_ERR_ARG, "scrfd_post: bad sizes");
+  const bool use_kps = heads[6] != nullptr;
+  const int per_px[3] = {A, 4 * A, 10 * A};
+  for (int kind = 0; kind < 3; ++kind) {
+    for (int l = 0; l < 3; ++l)
+      FFP_CHECK((heads[3 * kind + l] != nullptr) == (kind < 2 || use_kps), FFP_ERR_ARG, "scrfd_post: head %d of level %d missing (kps: all three levels or none)", kind, l);
+    if (kind < 2 || use_kps) op_check_view("scrfd_post head", cs[kind], coff[kind], per_px[kind]);
+  }
+  for (int i = 0; i < n; ++i) FFP_CHECK(det_scale[i] > 0.f, FFP_ERR_ARG, "scrfd_post: det_scale of image %d", i);
+  OpCtx cx(device, "scrfd_post");
+  Level L[3];
+  DevBuf dh[3][3];
+  ScrfdHeads h{};
+  h.A = A;
+  h.a_off[0] = 0;
+  for (int l = 0; l < 3; ++l) {
+    FFP_CHECK(strides[l] >= 1 && net_h % strides[l] == 0 && net_w % strides[l] == 0, FFP_ERR_ARG, "scrfd_post: stride %d does not divide %dx%d", strides[l], net_w, net_h);
+    const int lh = net_h / strides[l], lw = net_w / strides[l];
+    L[l].build(std::vector<int>(n, lh), std::vector<int>(n, lw), cx.st, px_align);
+    for (int kind = 0; kind < 3; ++kind) {
+      if (!heads[3 * kind + l]) continue;
+      dh[kind][l] = op_upload(L[l], F32, heads[3 * kind + l], cs[kind]);
+      h.cs[kind][l] = cs[kind];
+      h.coff[kind][l] = coff[kind];
+    }
+    h.score[l] = dh[0][l].as<float>();
+    h.bbox[l] = dh[1][l].as<float>();
+    h.kps[l] = use_kps ? dh[2][l].as<float>() : nullptr;
+    h.tab[l] = L[l].d_tab.as<int4>();
+    h.stride[l] = strides[l];
+    h.a_off[l + 1] = h.a_off[l] + lh * lw * A;
+  }
+  h.per_img = h.a_off[3];
+  DevBuf d_scale = upload(det_scale, (size_t)n);
+  h.det_scale = d_scale.as<float>();
+  const size_t na = (size_t)n * h.per_img, no = (size_t)n * cap * FFP_DET_STRIDE(5);
+  DevBuf d_cand(sizeof(ScrfdCand) * na), d_counts(sizeof(int) * (size_t)n), d_order(sizeof(int) * na), d_supp(sizeof(int) * na),
+      d_out = upload(out, no), d_out_counts(sizeof(int) * (size_t)n), d_raw;
+  if (raw_scores) {
+    d_raw.alloc(sizeof(float) * na);
+    launch_scrfd_decode(h, n, 0.f, nullptr, nullptr, d_raw.as<float>(), cx.st);
+  }
+  launch_scrfd_decode(h, n, thresh, d_cand.as<ScrfdCand>(), d_counts.as<int>(), nullptr, cx.st);
+  launch_scrfd_nms(d_cand.as<ScrfdCand>(), d_counts.as<int>(), n, h.per_img, d_order.as<int>(), d_supp.as<int>(), nms_thresh, d_out.as<float>(), cap,
+                   d_out_counts.as<int>(), cx.st);
+  FFP_HIP(hipStreamSynchronize(cx.st));
+  op_fetch(d_out, out, no);
+  FFP_HIP(hipMemcpy(out_counts, d_out_counts.p, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
+  if (raw_scores) op_fetch(d_raw, raw_scores, na);
+  FFP_API_END
+}
+
 // tuning hook: average device time (HIP events) of `iters` launches of one dense convolution on synthetic data
 int ffp_op_conv2d_time(int device, int precision, int n, int h, int w, int cin, int cout, int k, int stride, int up, int iters,
                        int dbg_mask, int force_shape, float* out_us) {

@@ -78,16 +78,20 @@ RtdetrEngine::~RtdetrEngine() {
   if (st_) (void)hipStreamDestroy(st_);
 }
 
+std::vector<float> rtdetr_pack_depthwise(const float* w, int C, int taps) {
+  std::vector<float> v((size_t)C * taps);
+  for (int c = 0; c < C; ++c)
+    for (int j = 0; j < taps; ++j) v[(size_t)j * C + c] = w[(size_t)c * taps + j];
+  return v;
+}
+
 const float* RtdetrEngine::dev(const std::string& name) {
   auto it = dev_.find(name);
   if (it == dev_.end()) {
     const HostTensor& h = t(name);
     DevBuf b(h.numel() * 4);
     if (h.dims.size() == 4 && h.dims[1] == 1 && h.dims[0] > 1) {         // depthwise (C, 1, k, k) -> [tap][C]
-      const int C = h.dims[0], kk = h.dims[2] * h.dims[3];
-      std::vector<float> v((size_t)C * kk);
-      for (int c = 0; c < C; ++c)
-        for (int j = 0; j < kk; ++j) v[(size_t)j * C + c] = h.data[(size_t)c * kk + j];
+      const std::vector<float> v = rtdetr_pack_depthwise(h.data, h.dims[0], h.dims[2] * h.dims[3]);
       FFP_HIP(hipMemcpy(b.p, v.data(), v.size() * 4, hipMemcpyHostToDevice));
     } else {
       FFP_HIP(hipMemcpy(b.p, h.data, h.numel() * 4, hipMemcpyHostToDevice));

@@ -33,6 +33,8 @@ void launch_rt_post(const TView& ref, const TView& s, int nc, float conf, const 
 // host tables, constant per imgsz (RTDETRDecoder._generate_anchors, AIFI.build_2d_sincos_position_embedding)
 void rtdetr_anchors(int imgsz, std::vector<float>& anchors, std::vector<float>& valid);
 void rtdetr_pos_embed(int w, int h, std::vector<float>& pos);
+// depthwise weights (C, 1, k, k) -> [tap][C], the layout rt_dwconv reads
+std::vector<float> rtdetr_pack_depthwise(const float* w, int C, int taps);
 
 struct RtdetrPlan : Plan {
   int n = 0, imgsz = 0, NT = 0;

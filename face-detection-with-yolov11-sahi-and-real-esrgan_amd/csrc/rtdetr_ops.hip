@@ -95,8 +95,8 @@ __global__ void rt_add_kernel(const float* __restrict__ a, int a_cs, const float
   raise_slot(amax, m);
 }
 
-// ---- LayerNorm over 256 channels (eps 1e-5); one wave per token, 4 channels per lane. The residual of every post-norm sublayer is
-// already added in the epilogue of the conv that produces x (ConvOp::res1) ------------------------------------------------------------
+// ---- LayerNorm over 256 channels (eps 1e-5, two-pass variance about a corrected mean); one wave per token, 4 channels per lane.
+// The residual of every post-norm sublayer is already added in the epilogue of the conv that produces x (ConvOp::res1) ----------
 __global__ void rt_layernorm_kernel(const float* __restrict__ x, int x_cs, const float* __restrict__ gamma,
                                     const float* __restrict__ beta, float* __restrict__ out, int out_cs, long long npx, unsigned* amax) {
   const long long px = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -107,7 +107,13 @@ __global__ void rt_layernorm_kernel(const float* __restrict__ x, int x_cs, const
     float s = (v.x + v.y) + (v.z + v.w);
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
     const float mean = s * (1.0f / 256.0f);
-    const float d0 = v.x - mean, d1 = v.y - mean, d2 = v.z - mean, d3 = v.w - mean;
+    float d0 = v.x - mean, d1 = v.y - mean, d2 = v.z - mean, d3 = v.w - mean;
+    // the sum of 256 values is rounded at the ulp of the SUM: with |mean| >> std that leaves the mean off by a visible fraction of the std.
+    // The residuals are small, so their mean is accurate: one correction step
+    float e = (d0 + d1) + (d2 + d3);
+    for (int o = 32; o > 0; o >>= 1) e += __shfl_xor(e, o);
+    const float corr = e * (1.0f / 256.0f);
+    d0 -= corr; d1 -= corr; d2 -= corr; d3 -= corr;
     float q = (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
     for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
     const float rs = 1.0f / sqrtf(q * (1.0f / 256.0f) + 1e-5f);

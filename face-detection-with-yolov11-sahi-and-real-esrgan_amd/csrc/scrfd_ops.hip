@@ -1,5 +1,7 @@
 // scrfd_ops.hip — the SCRFD-specific device operators: InsightFace's pre-processing, the ResNet-v1e pools, and the decode / NMS of
 // RetinaFace.detect (insightface/model_zoo/retinaface.py). Vector memory operations and ordinary global atomics only.
+#include <algorithm>
+
 #include "letterbox.hpp"
 #include "scrfd.hpp"
 
@@ -69,7 +71,9 @@ __global__ void scrfd_pool_kernel(const float* __restrict__ in, int in_cs, int i
 void launch_scrfd_pool(const TView& in, const TView& out, int maxpool, int k, hipStream_t st) {
   FFP_CHECK(in.dt == F32 && out.dt == F32 && in.C == out.C && in.lvl->n == out.lvl->n, FFP_ERR_ARG, "scrfd pool: view mismatch");
   const Level& lo = *out.lvl;
-  const dim3 grid(blocks((long long)lo.h[0] * lo.w[0] * in.C, 256), lo.n);
+  long long px = 0;                                  // a ragged batch: the grid covers the largest output image
+  for (int i = 0; i < lo.n; ++i) px = std::max(px, (long long)lo.h[i] * lo.w[i]);
+  const dim3 grid(blocks(px * in.C, 256), lo.n);
   hipLaunchKernelGGL(scrfd_pool_kernel, grid, dim3(256), 0, st, (const float*)in.ptr, in.cs, in.coff, in.lvl->d_tab.as<int4>(), (float*)out.ptr, out.cs,
                      out.coff, lo.d_tab.as<int4>(), in.C, maxpool, k);
   FFP_HIP(hipGetLastError());

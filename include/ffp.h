@@ -396,6 +396,65 @@ int ffp_op_det_post(int device, int n, const int32_t* hs, const int32_t* ws, int
  * patterns (+0.0 above -0.0, which float comparison calls equal). out_idx: [n][300]. */
 int ffp_op_rt_topk(int device, int n, int nt, int nc, const float* scores, int s_cs, int s_coff, int32_t* out_idx);
 
+/* ---- the RT-DETR and SCRFD non-convolution kernels one at a time (csrc/rtdetr_ops.hip, csrc/scrfd_ops.hip), fp32 ---------------------
+ * The rt_* kernels address image i at i * h * w pixels without padding: one (h, w) or token count for the whole batch, host arrays
+ * [n * h * w][cs]. Views are channel slices (cs, coff; multiples of 4) as above and output arrays are in/out. `amax` (NULL: the
+ * kernel gets no slot): the max-|value| slot of the output buffer, in = its initial bit pattern, out = its final one. */
+
+/* depthwise k x k, stride s, pad k / 2 (k5 s1 or k3 s2): y ([n][ho][wo], ho = (h - 1) / s + 1) = act(conv(x) + bias); wt: [c][k][k]
+ * (repacked like the engine's weights), act 0 none / 3 ReLU. */
+int ffp_op_rt_dwconv(int device, int n, int h, int w, int c, int k, int s, int act, const float* x, int x_cs, int x_coff, const float* wt,
+                     const float* bias, float* y, int y_cs, int y_coff, uint32_t* amax);
+/* HGStem's pool: F.pad(x, [0, 1, 0, 1]) then MaxPool2d(2, 1, ceil_mode=True); y has the size of x. */
+int ffp_op_rt_maxpool2(int device, int n, int h, int w, int c, const float* x, int x_cs, int x_coff, float* y, int y_cs, int y_coff, uint32_t* amax);
+/* y[p] = a[p] + b[period ? p % period : p] over npx pixel records; b has period (or npx) records of b_cs. */
+int ffp_op_rt_add(int device, long long npx, int c, const float* a, int a_cs, int a_coff, const float* b, int b_cs, int b_coff, long long period,
+                  float* y, int y_cs, int y_coff, uint32_t* amax);
+/* LayerNorm over 256 channels, eps 1e-5. x = NULL: in place on the slice of y. */
+int ffp_op_rt_layernorm(int device, long long npx, const float* x, int x_cs, int x_coff, const float* gamma, const float* beta, float* y, int y_cs,
+                        int y_coff, uint32_t* amax);
+/* exact (erf) GELU in place on c channels at coff of x. */
+int ffp_op_rt_gelu(int device, long long npx, int c, float* x, int cs, int coff, uint32_t* amax);
+/* 8 heads of 32 over the L tokens of each image: qk view of 512 channels [q 256 | k 256], v view of 256, y view of 256. */
+int ffp_op_rt_attention(int device, int n, int L, const float* qk, int qk_cs, int qk_coff, const float* v, int v_cs, int v_coff, float* y, int y_cs,
+                        int y_coff, uint32_t* amax);
+/* encoder input: three levels of hs[l] x ws[l] pixels with 256 channels at src_coff[l] of records of src_cs[l] -> t [rows][256] tokens
+ * [level 0 | 1 | 2] per image and tm = t where valid[token] != 0, else 0. rows >= n * tokens: the records behind stay untouched. */
+int ffp_op_rt_enc_prep(int device, int n, const int32_t* hs, const int32_t* ws, const float* src0, const float* src1, const float* src2,
+                       const int32_t* src_cs, const int32_t* src_coff, const float* valid, long long rows, float* t, float* tm, uint32_t* amax_t,
+                       uint32_t* amax_tm);
+/* the selected queries: q[i][j] = e[i][clamp(idx[i][j], 0, nt - 1)] (256 channels) and anc_out[i][j] = anchors[that token] (4 values,
+ * copied as they are). idx: [n][300], anchors: [nt][4], anc_out: [n][300][4]. */
+int ffp_op_rt_gather(int device, int n, int nt, const float* e, int e_cs, int e_coff, const int32_t* idx, const float* anchors, float* q, int q_cs,
+                     int q_coff, float* anc_out, uint32_t* amax);
+/* reference boxes over nq queries, 4 channels: anc ([nq][4]) given: ref = sigmoid(delta + anc); NULL: ref = sigmoid(delta +
+ * inverse_sigmoid(ref, 1e-5)) in place. */
+int ffp_op_rt_ref(int device, long long nq, const float* delta, int d_cs, int d_coff, const float* anc, float* ref, int r_cs, int r_coff,
+                  uint32_t* amax);
+/* MSDeformAttn core (8 heads, 3 levels of hs[l] x ws[l], 4 points): val [n][tokens] view of 256, oa [n][300] view of 288 (192 offsets |
+ * 96 weight logits), ref [n][300] view of 4 (cx, cy, w, h) -> y [n][300] view of 256. */
+int ffp_op_rt_deform(int device, int n, const int32_t* hs, const int32_t* ws, const float* val, int v_cs, int v_coff, const float* oa, int oa_cs,
+                     int oa_coff, const float* ref, int r_cs, int r_coff, float* y, int y_cs, int y_coff, uint32_t* amax);
+/* the predictor's outputs from ref ([n][300] view of 4) and class logits (view of nc). out_raw (NULL = skip): [n][300][4 + nc] boxes and
+ * sigmoid scores. out_det / out_counts (both or neither): RTDETRPredictor.postprocess, [n][300][6] rows x1, y1, x2, y2, score, class of
+ * the queries whose best score > conf, in query order, scaled by orig_wh [n][2] = (width, height); rows past out_counts[i] untouched. */
+int ffp_op_rt_decode(int device, int n, int nc, const float* ref, int r_cs, int r_coff, const float* scores, int s_cs, int s_coff, float conf,
+                     const float* orig_wh, float* out_raw, float* out_det, int32_t* out_counts);
+
+/* SCRFD's pools on a ragged batch (px_align as above): maxpool != 0: MaxPool 3x3 / stride 2 / pad 1 (y images of (h - 1) / 2 + 1);
+ * else AveragePool k x k / stride k, ceil_mode, count_include_pad = 0 (y images of ceil(h / k)). */
+int ffp_op_scrfd_pool(int device, int n, const int32_t* hs, const int32_t* ws, int px_align, int c, int maxpool, int k, const float* x, int x_cs,
+                      int x_coff, float* y, int y_cs, int y_coff);
+/* RetinaFace.detect's decode + NMS from head tensors. n images at net size net_h x net_w; level l has (net_h / strides[l]) x
+ * (net_w / strides[l]) pixels with A anchors each. heads: 9 host arrays {score, bbox, kps} x 3 levels (kps NULL for the 6-output
+ * variant), per pixel records of cs[kind] with the A / 4A / 10A values at coff[kind]; scores are logits (the decode applies the sigmoid).
+ * Candidates: score >= thresh; NMS keeps a candidate whose "+1"-convention overlap with every kept one is <= nms_thresh.
+ * out: [n][cap][FFP_DET_STRIDE(5)] in/out; out_counts[i] = faces KEPT for image i, which exceeds cap when the list was cut (only the
+ * first cap rows are written). raw_scores (NULL = skip): [n][anchors per image] the decode's sigmoid of every anchor. */
+int ffp_op_scrfd_post(int device, int n, int net_h, int net_w, int A, const int32_t* strides, int px_align, const float* const* heads,
+                      const int32_t* cs, const int32_t* coff, const float* det_scale, float thresh, float nms_thresh, int cap, float* out,
+                      int32_t* out_counts, float* raw_scores);
+
 /* Tuning hook: mean device time (HIP events, microseconds) of `iters` back-to-back launches of one dense convolution on
  * synthetic data. dbg_mask skips kernel phases (1 stores, 2 MFMAs, 4 chunk refetch, 8 LDS stash) to attribute time —
  * results are then wrong by construction; force_shape pins the workgroup shape (-1: automatic). */
