@@ -123,6 +123,7 @@ _SIGS = {
     "ffp_jpeg_decode_dev": (C.c_int, [C.c_int, _p(C.c_uint8), C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int64]),
     "ffp_jpeg_decode_stats": (C.c_int, [_p(C.c_int64), _p(C.c_int64), _p(C.c_int64)]),
     "ffp_op_conv2d_shape": (C.c_int, [C.c_int]),
+    "ffp_op_conv2d_act_post": (C.c_int, [C.c_int]),
     "ffp_op_conv1x1_up2": (C.c_int, [C.c_int, C.c_int, _p(C.c_float), _p(C.c_float), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_float),
                                      _p(C.c_float), C.c_int, C.c_int, _p(C.c_float)]),
     "ffp_op_conv2d_time": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -1255,6 +1256,11 @@ def op_resize_lanczos4(img: np.ndarray, out_h: int, out_w: int, device: int = 0)
 def op_conv2d_shape(shape: int = -1) -> None:
     """Pin the workgroup shape of the following op_conv2d calls (tests of one kernel variant); -1 restores the automatic choice."""
     _check(lib().ffp_op_conv2d_shape(int(shape)))
+
+
+def op_conv2d_act_post(act: int = 0) -> None:
+    """Activation the following op_conv2d calls apply after the residual term (epilogue contract tests); 0 restores none."""
+    _check(lib().ffp_op_conv2d_act_post(int(act)))
 
 
 def op_conv2d_time(n, h, w, cin, cout, k=3, stride=1, up=False, precision=PREC_F16, iters=50, dbg=0, shape=-1, device=0) -> float:

@@ -938,6 +938,14 @@ int ffp_op_conv2d_shape(int force_shape) {
   return FFP_OK;
 }
 
+static int g_op_conv_act_post = ACT_NONE;
+int ffp_op_conv2d_act_post(int act) {
+  FFP_API_BEGIN
+  FFP_CHECK(act >= ACT_NONE && act <= ACT_RELU, FFP_ERR_ARG, "conv2d_act_post: activation code %d (0..3)", act);
+  g_op_conv_act_post = act;
+  FFP_API_END
+}
+
 int ffp_op_conv2d(int device, int precision, const float* x, int n, int h, int w, int cin, const float* wt, const float* bias, int cout,
                   int k, int stride, int groups, int act, int up, const float* res, float res_scale, float* y) {
   FFP_API_BEGIN
@@ -990,6 +998,7 @@ int ffp_op_conv2d(int device, int precision, const float* x, int n, int h, int w
     }
     if (pc.depthwise()) {
       FFP_CHECK(k == 3 && stride == 1 && !up, FFP_ERR_ARG, "conv2d: depthwise is 3x3 stride 1");
+      FFP_CHECK(g_op_conv_act_post == ACT_NONE, FFP_ERR_ARG, "conv2d: depthwise convs have no post-activation");
       DwConvOp o;
       o.pc = &pc; o.in = vin; o.out = vout; o.out.lvl = &lin; o.act = act;
       if (res) { o.has_res = true; o.res = vres; o.res.lvl = &lin; FFP_CHECK(res_scale == 1.f, FFP_ERR_ARG, "conv2d: depthwise residual has no scale"); }
@@ -999,6 +1008,7 @@ int ffp_op_conv2d(int device, int precision, const float* x, int n, int h, int w
       o.pc = &pc; o.in = vin; o.out = vout; o.stride = stride; o.act = act; o.up = up;
       if (res) { o.has_res1 = true; o.res1 = vres; o.s1 = res_scale; }
       o.force_shape = g_op_conv_shape;
+      o.act_post = g_op_conv_act_post;
       launch_conv(o, st);
     }
     FFP_HIP(hipStreamSynchronize(st));

@@ -156,6 +156,28 @@ __device__ __forceinline__ float apply_act(float v, int act) {
   return v;
 }
 
+// Raw BUFFER loads of conv_mfma, conv_rows and the rows16 family (conv_k3d keeps lambdas of its own: these in their place moved all its streams): the resource base is wave-uniform
+// (readfirstlane'd halves: SGPRs), the per-lane part a 32-bit byte offset; a lane with nothing to read or write uses BUF_OOB, which the range check turns into zeros / a dropped store.
+constexpr unsigned BUF_OOB = 0xFFFFFFFFu;
+__device__ __forceinline__ auto buf_rsrc(const unsigned char* p, unsigned bytes = 0x7FFFFFF0) {
+  const unsigned long long u = reinterpret_cast<unsigned long long>(p);
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
+  return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<unsigned char*>(((unsigned long long)hi << 32) | lo), 0, bytes, 0x00020000);
+}
+typedef decltype(buf_rsrc(nullptr)) buf_rsrc_t;
+__device__ __forceinline__ uint4 buf_load16(buf_rsrc_t rs, unsigned off, int soff = 0) {      // soff: wave-uniform byte offset (an SGPR operand, no VALU)
+  const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs, off, soff, 0);
+  return make_uint4(v[0], v[1], v[2], v[3]);
+}
+// ---- host: what a kernel family's epilogue implements of the ConvOp contract (ops.hpp: act -> v * s1 + res1 -> v * s2 + res2 -> act_post), stated once next
+// to the kernel (true to the kernel text, not to today's callers), and the one check every eligibility predicate starts from
+struct EpiCaps { unsigned acts; bool res, act_post, out_f16, out_f32; };   // acts: bit per Act code applied as `act`; res: res1 / res2 terms; output element types
+constexpr unsigned EPI_ALL_ACTS = 1u << ACT_NONE | 1u << ACT_SILU | 1u << ACT_LRELU | 1u << ACT_RELU;
+inline bool epilogue_fits(int act, bool res, int act_post, DType out, const EpiCaps& caps) {
+  return act >= 0 && act < 32 && (caps.acts >> act & 1u) && (!res || caps.res) && (!act_post || caps.act_post) && (out == F16 ? caps.out_f16 : caps.out_f32);
+}
+inline bool epilogue_fits(const ConvOp& op, const EpiCaps& caps) { return epilogue_fits(op.act, op.has_res1 || op.has_res2, op.act_post, op.out.dt, caps); }
+
 // host side (conv_mfma.hip)
 ConvArgs make_conv_args(const ConvOp& op);
 // k3 s1 fp16 row-reuse kernel (conv_rows.hip)

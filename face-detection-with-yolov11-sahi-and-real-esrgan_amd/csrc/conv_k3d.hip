@@ -479,11 +479,12 @@ bool conv_k3d_enabled() {
   return on;
 }
 
-// what the kernel does not do: fp16 / exact-fp32 arithmetic, upsampled inputs, unaligned outputs, input channel counts that are not
+// what the kernel does not do: fp16 / exact-fp32 arithmetic, fp16 outputs (kEpiK3d), upsampled inputs, unaligned outputs, input channel counts that are not
 // whole 16-channel groups, images whose byte size does not fit the 32-bit offsets of one buffer resource
+static constexpr EpiCaps kEpiK3d{EPI_ALL_ACTS, true, true, false, true};
 unsigned conv_k3d_mask(const ConvOp& op, const ConvArgs& a) {
   const PackedConv& pc = *op.pc;
-  if (!(pc.split && pc.dt == F32 && pc.k == 3 && (op.stride == 1 || op.stride == 2) && !op.up && !op.has_up2 && a.fast_out && a.out_f32 &&
+  if (!(epilogue_fits(op, kEpiK3d) && pc.split && pc.dt == F32 && pc.k == 3 && (op.stride == 1 || op.stride == 2) && !op.up && !op.has_up2 && a.fast_out &&
         pc.cin % 16 == 0 && pc.cin_pad == pc.cin && op.in.lvl->n > 0))
     return 0;
   long long max_px = 0;

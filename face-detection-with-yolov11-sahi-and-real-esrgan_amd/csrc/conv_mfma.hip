@@ -24,9 +24,6 @@
 #ifndef FFP_OCC3
 #define FFP_OCC3 1           // tuning switch: 0 = small-accumulator split shapes stay at two workgroups per CU with two LDS stages
 #endif
-#ifndef FFP_DEEP_OCC1
-#define FFP_DEEP_OCC1 0      // tuning switch: 1 = shapes whose LDS allows one workgroup per CU get 512 registers and a deeper prefetch ring (measured: no gain)
-#endif
 
 namespace ffp {
 
@@ -133,10 +130,8 @@ template <typename T, int KS, int STRIDE, int WM, int WN, int MI, int NIW, int K
   static constexpr int PD_CL = PD_RAW < 0 ? 0 : PD_RAW > 4 ? 4 : PD_RAW;
   static constexpr int PD = PD_CL > NS - 1 ? NS - 1 : PD_CL;
   static constexpr int FRAG_REGS = 4 * (PD + 1) * FPS;
-  // a shape whose LDS footprint allows one workgroup per CU anyway gets the whole 512-register file (launch bound 1 wave
-  // per SIMD) and spends it on prefetch depth: with D = 1 every chunk of an HBM-fed layer exposes a full memory round trip
-  static constexpr int OCC = OCC3 ? 3 : (LDS <= 80 * 1024 || !FFP_DEEP_OCC1) ? 2 : 1;
-  static constexpr int REG_BUDGET = OCC == 3 ? 168 : OCC == 2 ? 256 : 448;
+  static constexpr int OCC = OCC3 ? 3 : 2;
+  static constexpr int REG_BUDGET = OCC == 3 ? 168 : 256;
   static constexpr int DEPTH_RAW = (REG_BUDGET - NIW * MI * 16 - 56 - FRAG_REGS - 3 * (RI + RW)) / (4 * (RI + RW));   // accumulators, fragment ring, ~56 misc, address slots
   static constexpr int DEPTH = DEPTH_RAW < 1 ? 1 : DEPTH_RAW > 4 ? 4 : DEPTH_RAW;
   static_assert(KC % KG == 0 && WM * WN == 4, "geometry");
@@ -191,22 +186,11 @@ __global__ void __launch_bounds__(256, (Geo<T, KS, STRIDE, WM, WN, MI, NIW, KC>:
   const unsigned char* inb = reinterpret_cast<const unsigned char*>(a.in);
   const unsigned char* wb = reinterpret_cast<const unsigned char*>(a.wpk);
 
-  // Global operands are read with raw BUFFER loads: the resource base is wave-uniform (this workgroup's image / pixel run,
-  // the packed weights), the per-lane part a 32-bit byte offset, and an out-of-image / past-the-end slot uses offset
-  // 0xFFFFFFFF, which the hardware range check turns into zeros — conv zero padding without a branch or a select, so the
-  // loads stay straight-line code and hipcc retires them with counted s_waitcnt vmcnt(N).
-  constexpr unsigned OOB = 0xFFFFFFFFu;
-  auto uniform_ptr = [](const unsigned char* q) {
-    const unsigned long long u = reinterpret_cast<unsigned long long>(q);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-    return reinterpret_cast<unsigned char*>(((unsigned long long)hi << 32) | lo);
-  };
-  const auto rs_in = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(const_cast<unsigned char*>(inb) + ((long long)in_base * a.in_cs + a.in_coff) * ES), 0, 0x7FFFFFF0, 0x00020000);
-  const auto rs_w = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(const_cast<unsigned char*>(wb)), 0, 0x7FFFFFF0, 0x00020000);
-  auto bload = [](decltype(rs_in) rs, unsigned off) {
-    const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0);
-    return make_uint4(v[0], v[1], v[2], v[3]);
-  };
+  // Global operands are read with raw BUFFER loads (buf_rsrc / buf_load16, conv_args.hpp) over this workgroup's image / pixel run and
+  // the packed weights: out-of-image / past-the-end slots read zeros through the range check, so the loads stay straight-line code
+  // and hipcc retires them with counted s_waitcnt vmcnt(N).
+  const auto rs_in = buf_rsrc(inb + ((long long)in_base * a.in_cs + a.in_coff) * ES);
+  const auto rs_w = buf_rsrc(wb);
 
   // scaled split: power of two of the activations (max |value| of the input buffer(s) -> [2^13, 2^14) in fp16), per buffer or — with
   // per-image exponent slots — per image: a 3x3 workgroup works on ONE image (its tile's), a 1x1 workgroup on FR 32-pixel fragments
@@ -240,13 +224,13 @@ __global__ void __launch_bounds__(256, (Geo<T, KS, STRIDE, WM, WN, MI, NIW, KC>:
   }
 
   // per-thread staging slots: which vector each of this thread's RI + RW registers carries (chunk independent part)
-  unsigned isrc[RI];           // byte offset of the pixel record relative to the resource base (OOB: zero fill)
+  unsigned isrc[RI];           // byte offset of the pixel record relative to the resource base (BUF_OOB: zero fill)
   int ivec[RI];                // vector index inside the chunk
   float tsc[RI];               // split scale of the slot's pixel (per-image exponent slots: the scale of its fragment's image)
 #pragma unroll
   for (int i = 0; i < RI; ++i) {
     const int idx = tid + i * 256;
-    isrc[i] = OOB; ivec[i] = 0; tsc[i] = tscale;
+    isrc[i] = BUF_OOB; ivec[i] = 0; tsc[i] = tscale;
     if (!STEM && idx < G::NVI) {
       const int hp = idx / VPP;
       if constexpr (SPLIT && KS == 1) {
@@ -274,20 +258,20 @@ __global__ void __launch_bounds__(256, (Geo<T, KS, STRIDE, WM, WN, MI, NIW, KC>:
   // view (through the x2 pixel map) and the offsets into `in` are recomputed per load (one multiply), so that no shape
   // pays registers for the second source
   const unsigned char* upb = a.up_c > 0 ? reinterpret_cast<const unsigned char*>(a.up_src) : wb;
-  const auto rs_up = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(const_cast<unsigned char*>(upb)), 0, 0x7FFFFFF0, 0x00020000);
+  const auto rs_up = buf_rsrc(upb);
   if constexpr (KS == 1) {
     if (a.up_c > 0) {
 #pragma unroll
       for (int i = 0; i < RI; ++i)
-        if (isrc[i] != OOB) isrc[i] = (unsigned)a.up_map[in_base + (tid + i * 256) / VPP] * (unsigned)(a.up_cs * ES);
+        if (isrc[i] != BUF_OOB) isrc[i] = (unsigned)a.up_map[in_base + (tid + i * 256) / VPP] * (unsigned)(a.up_cs * ES);
     }
   }
-  unsigned wsrc[RW];           // byte offset of the fragment row start for k-group 0 (OOB: no such slot)
+  unsigned wsrc[RW];           // byte offset of the fragment row start for k-group 0 (BUF_OOB: no such slot)
   int wkg[RW];
 #pragma unroll
   for (int i = 0; i < RW; ++i) {
     const int idx = tid + i * 256;
-    wsrc[i] = OOB; wkg[i] = 0;
+    wsrc[i] = BUF_OOB; wkg[i] = 0;
     if (idx < G::NVW) {
       const int fl = idx / VPF, l = idx % VPF;
       const int kg = fl % KCG, tap = (fl / KCG) % TAPS, ntl = fl / (KCG * TAPS);
@@ -306,16 +290,16 @@ __global__ void __launch_bounds__(256, (Geo<T, KS, STRIDE, WM, WN, MI, NIW, KC>:
       const int c = c0 + ivec[i] * EPV;
       if constexpr (KS == 1) {
         unsigned so = isrc[i];
-        if (a.up_c > 0 && !from_up && so != OOB) so = (unsigned)(((tid + i * 256) / VPP) * a.in_cs * ES);
-        qi[i] = bload(from_up ? rs_up : rs_in, (so != OOB && c < a.cin) ? so + (unsigned)(c * ES) : OOB);
+        if (a.up_c > 0 && !from_up && so != BUF_OOB) so = (unsigned)(((tid + i * 256) / VPP) * a.in_cs * ES);
+        qi[i] = buf_load16(from_up ? rs_up : rs_in, (so != BUF_OOB && c < a.cin) ? so + (unsigned)(c * ES) : BUF_OOB);
       } else {
-        qi[i] = bload(rs_in, (isrc[i] != OOB && c < a.cin) ? isrc[i] + (unsigned)(c * ES) : OOB);
+        qi[i] = buf_load16(rs_in, (isrc[i] != BUF_OOB && c < a.cin) ? isrc[i] + (unsigned)(c * ES) : BUF_OOB);
       }
     }
     const int cg0 = c0 / KG;
 #pragma unroll
     for (int i = 0; i < RW; ++i)
-      qw[i] = bload(rs_w, (wsrc[i] != OOB && cg0 + wkg[i] < a.ncg) ? wsrc[i] + (unsigned)((cg0 + wkg[i]) * WFRAG) : OOB);
+      qw[i] = buf_load16(rs_w, (wsrc[i] != BUF_OOB && cg0 + wkg[i] < a.ncg) ? wsrc[i] + (unsigned)((cg0 + wkg[i]) * WFRAG) : BUF_OOB);
   };
   auto stash = [&](unsigned char* buf, const uint4 (&qi)[RI], const uint4 (&qw)[RW]) {
 #pragma unroll
@@ -396,8 +380,7 @@ __global__ void __launch_bounds__(256, (Geo<T, KS, STRIDE, WM, WN, MI, NIW, KC>:
         const long long row0 = row_b & ~3ll;                 // dword-aligned like the frame itself
         const int skew = (int)(row_b - row0);
         const long long left = a.st_bytes - row0;
-        const auto rs_f = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(const_cast<unsigned char*>(a.st_frame) + row0), 0,
-                                                            (int)(left < 0x7FFFFFFCll ? left : 0x7FFFFFFCll), 0x00020000);
+        const auto rs_f = buf_rsrc(a.st_frame + row0, (unsigned)(left < 0x7FFFFFFCll ? left : 0x7FFFFFFCll));
         const int r = kb < 3 ? kb : 2;
         unsigned w0[SGW], w1[SGW], w2[SGW];
 #pragma unroll
@@ -406,10 +389,10 @@ __global__ void __launch_bounds__(256, (Geo<T, KS, STRIDE, WM, WN, MI, NIW, KC>:
           const bool inmap = geom(j, q, sy, sx);
           const int ny = 2 * sy - 1 + r;
           const int A = (ny * a.st_W + Lb.x0 + 2 * sx - 1) * 3 + skew;
-          const unsigned base = (inmap && (unsigned)ny < (unsigned)Hn) ? (unsigned)(A & ~3) : OOB;
+          const unsigned base = (inmap && (unsigned)ny < (unsigned)Hn) ? (unsigned)(A & ~3) : BUF_OOB;
           w0[j] = __builtin_amdgcn_raw_buffer_load_b32(rs_f, base, 0, 0);
-          w1[j] = __builtin_amdgcn_raw_buffer_load_b32(rs_f, base == OOB ? OOB : base + 4u, 0, 0);
-          w2[j] = __builtin_amdgcn_raw_buffer_load_b32(rs_f, base == OOB ? OOB : base + 8u, 0, 0);
+          w1[j] = __builtin_amdgcn_raw_buffer_load_b32(rs_f, base == BUF_OOB ? BUF_OOB : base + 4u, 0, 0);
+          w2[j] = __builtin_amdgcn_raw_buffer_load_b32(rs_f, base == BUF_OOB ? BUF_OOB : base + 8u, 0, 0);
         }
 #pragma unroll
         for (int j = 0; j < SGW; ++j) {
@@ -621,8 +604,7 @@ __global__ void __launch_bounds__(256, (Geo<T, KS, STRIDE, WM, WN, MI, NIW, KC>:
     unsigned char* et = smem + wave * (32 * EROW);
     const unsigned char* r1b = a.res1 ? reinterpret_cast<const unsigned char*>(a.res1) + ((long long)out_base * a.r1_cs + a.r1_coff) * ES : wb;
     const unsigned char* r2b = a.res2 ? reinterpret_cast<const unsigned char*>(a.res2) + ((long long)out_base * a.r2_cs + a.r2_coff) * ES : wb;
-    const auto rs_r1 = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(const_cast<unsigned char*>(r1b)), 0, 0x7FFFFFF0, 0x00020000);
-    const auto rs_r2 = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(const_cast<unsigned char*>(r2b)), 0, 0x7FFFFFF0, 0x00020000);
+    const auto rs_r1 = buf_rsrc(r1b), rs_r2 = buf_rsrc(r2b);
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi) {
       const int f = wm * MI + mi;
@@ -649,8 +631,8 @@ __global__ void __launch_bounds__(256, (Geo<T, KS, STRIDE, WM, WN, MI, NIW, KC>:
           oks[it] = oks[it] && nt * 32 + ch0 < a.cout;
           r1v[it] = make_uint4(0u, 0u, 0u, 0u); r2v[it] = r1v[it];
           const unsigned rel_px = (unsigned)(gps[it] - out_base);           // pixel index inside this workgroup's image / run
-          if (a.res1) r1v[it] = bload(rs_r1, oks[it] ? (rel_px * a.r1_cs + nt * 32 + ch0) * ES : OOB);      // uniform branch, branch-free lanes
-          if (a.res2) r2v[it] = bload(rs_r2, oks[it] ? (rel_px * a.r2_cs + nt * 32 + ch0) * ES : OOB);
+          if (a.res1) r1v[it] = buf_load16(rs_r1, oks[it] ? (rel_px * a.r1_cs + nt * 32 + ch0) * ES : BUF_OOB);      // uniform branch, branch-free lanes
+          if (a.res2) r2v[it] = buf_load16(rs_r2, oks[it] ? (rel_px * a.r2_cs + nt * 32 + ch0) * ES : BUF_OOB);
         }
         float oscf[CPL];                                        // output scale of this lane's channels x the fragment's inverse activation scale
 #pragma unroll
@@ -1151,6 +1133,8 @@ void launch_conv(const ConvOp& op, hipStream_t st) {
     FFP_HIP(hipStreamSynchronize(st));           // the plan's tables die with it
     return;
   }
+  const bool f16r = a.force_shape == 9 || a.force_shape == 23 || a.force_shape == 24, frow = a.force_shape >= 6 && a.force_shape <= 8;      // a forced rows shape, like a pw / k3d one, runs the op or is an error
+  FFP_CHECK((!f16r || conv_rows16_eligible(op, a)) && (!frow || conv_rows_eligible(op, a)), FFP_ERR_ARG, "conv %s: rows shape %d cannot run this op", pc.name.c_str(), a.force_shape);
   if (use_rows16(op, a)) {
     if (conv_rows16pc_selected(a)) launch_conv_rows16pc(a, pc, op.out.lvl, st);
     else launch_conv_rows16(a, pc, op.out.lvl, st);

@@ -459,11 +459,12 @@ using Pw21w = PwShape<8, 2, 1, 4>;
 
 void conv_pw_init() { Pw14::init(); Pw22::init(); Pw21::init(); Pw14w::init(); Pw22w::init(); Pw21w::init(); Pw14s::init(); Pw22s::init(); }
 
-// what the kernel does not do: residual inputs, fp16 outputs, input channel counts that are not whole 128-byte lines
+// what the kernel does not do: LReLU, residual inputs, act_post, fp16 outputs (kEpiPw), input channel counts that are not whole 128-byte lines
+static constexpr EpiCaps kEpiPw{1u << ACT_NONE | 1u << ACT_SILU | 1u << ACT_RELU, false, false, false, true};
 static bool pw_common(const ConvOp& op, const ConvArgs& a) {
   const PackedConv& pc = *op.pc;
   if (op.has_up2 && (long long)op.up2.lvl->total_px * op.up2.cs * 4 >= 0x7FFFFFF0ll) return false;      // one buffer resource spans the coarser tensor
-  return pc.split && pc.k == 1 && op.stride == 1 && !op.has_res1 && !op.has_res2 && !op.act_post && a.out_f32 && pc.cin % 32 == 0 &&
+  return epilogue_fits(op, kEpiPw) && pc.split && pc.k == 1 && op.stride == 1 && pc.cin % 32 == 0 &&
          pc.cin_pad == pc.cin && !op.out.lvl->capacity() && a.total_px > 0;
 }
 

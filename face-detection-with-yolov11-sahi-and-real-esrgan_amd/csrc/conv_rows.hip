@@ -232,21 +232,10 @@ __global__ void __launch_bounds__(256, NIW == 1 ? 2 : 1) conv_rows_kernel(const 
   // ---- epilogue: bias + activation, transposed through a wave-private LDS tile into whole-pixel 16-byte stores -------
   constexpr int EROW = G::EROW, CPL = 8, LPP = 4, PPI = 16;
   unsigned char* et = smem + G::XBUF + wave * (32 * EROW);
-  constexpr unsigned OOB = 0xFFFFFFFFu;
-  auto uniform_ptr = [](const unsigned char* q) {
-    const unsigned long long u = reinterpret_cast<unsigned long long>(q);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-    return reinterpret_cast<unsigned char*>(((unsigned long long)hi << 32) | lo);
-  };
   const unsigned char* wb = reinterpret_cast<const unsigned char*>(a.wpk);
   const unsigned char* r1b = a.res1 ? reinterpret_cast<const unsigned char*>(a.res1) + ((long long)out_base * a.r1_cs + a.r1_coff) * 2 : wb;
   const unsigned char* r2b = a.res2 ? reinterpret_cast<const unsigned char*>(a.res2) + ((long long)out_base * a.r2_cs + a.r2_coff) * 2 : wb;
-  const auto rs_r1 = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(r1b), 0, 0x7FFFFFF0, 0x00020000);
-  const auto rs_r2 = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(r2b), 0, 0x7FFFFFF0, 0x00020000);
-  auto bload = [](decltype(rs_r1) rs, unsigned off) {
-    const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0);
-    return make_uint4(v[0], v[1], v[2], v[3]);
-  };
+  const auto rs_r1 = buf_rsrc(r1b), rs_r2 = buf_rsrc(r2b);
 #pragma unroll
   for (int g = 0; g < 2; ++g) {
     const int fi = 2 * kh + g;                       // fragment index inside the wave's 8-row half
@@ -263,8 +252,8 @@ __global__ void __launch_bounds__(256, NIW == 1 ? 2 : 1) conv_rows_kernel(const 
         gps[itr] = out_base + (long long)oy * Wo + ox;
         r1v[itr] = make_uint4(0u, 0u, 0u, 0u); r2v[itr] = r1v[itr];
         const unsigned rel_px = (unsigned)(gps[itr] - out_base);
-        if (a.res1) r1v[itr] = bload(rs_r1, oks[itr] ? (rel_px * a.r1_cs + (nt0 + ni) * 32 + ch0) * 2 : OOB);
-        if (a.res2) r2v[itr] = bload(rs_r2, oks[itr] ? (rel_px * a.r2_cs + (nt0 + ni) * 32 + ch0) * 2 : OOB);
+        if (a.res1) r1v[itr] = buf_load16(rs_r1, oks[itr] ? (rel_px * a.r1_cs + (nt0 + ni) * 32 + ch0) * 2 : BUF_OOB);
+        if (a.res2) r2v[itr] = buf_load16(rs_r2, oks[itr] ? (rel_px * a.r2_cs + (nt0 + ni) * 32 + ch0) * 2 : BUF_OOB);
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
@@ -331,10 +320,11 @@ void conv_rows_init() {
   RowsCfg<1, 2>::init(); RowsCfg<1, 3>::init(); RowsCfg<2, 2>::init();
 }
 
+static constexpr EpiCaps kEpiRows{EPI_ALL_ACTS, true, false, true, false};     // apply_act, res1, res2; no act_post; fp16 outputs
 bool conv_rows_eligible(const ConvOp& op, const ConvArgs& a) {
   const PackedConv& pc = *op.pc;
   if (a.force_shape >= 0 && a.force_shape < 6) return false;        // tuning: a generic shape was asked for
-  return pc.dt == F16 && pc.k == 3 && op.stride == 1 && pc.cin % 32 == 0 && pc.cin >= 64 && pc.cin == pc.cin_pad &&
+  return epilogue_fits(op, kEpiRows) && pc.dt == F16 && pc.k == 3 && op.stride == 1 && pc.cin % 32 == 0 && pc.cin >= 64 && pc.cin == pc.cin_pad &&
          pc.cout % 32 == 0 && pc.cout <= 128 && a.fast_out && a.zeros != nullptr;
 }
 

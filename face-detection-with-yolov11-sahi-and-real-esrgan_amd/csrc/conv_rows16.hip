@@ -70,7 +70,7 @@ __global__ void __launch_bounds__(256, (RES ? 1 : 2)) conv_rows16_kernel(const C
 
   auto sgpr = [](int v) { return __builtin_amdgcn_readfirstlane(v); };
   const unsigned char* wb = reinterpret_cast<const unsigned char*>(a.wpk) + (long long)nt0 * NC * G::W_BYTES;
-  const auto rs_w = r16_rsrc(wb);
+  const auto rs_w = buf_rsrc(wb);
   auto rs_in = rs_w;                                   // rebuilt per item (setup_pf)
   auto rs_wp = rs_w;                                   // the prefetcher's view of the weights (emptied when the stream ends)
 
@@ -83,7 +83,7 @@ __global__ void __launch_bounds__(256, (RES ? 1 : 2)) conv_rows16_kernel(const C
   // so every slot is a whole wave-instruction for every wave: no divergence, no validity tests in the pipeline.
   const bool s9_in = wave == 0;
   const int s9_piece = wave == 0 ? 20 : wave == 1 ? 16 : 17;
-  unsigned isrc[6];        // byte offset of (pixel, slot) of the item being PREFETCHED from its image base; R16_OOB: zeros
+  unsigned isrc[6];        // byte offset of (pixel, slot) of the item being PREFETCHED from its image base; BUF_OOB: zeros
   unsigned idst[6];        // LDS byte offset of that vector inside the stage (item independent)
   unsigned wrel[5];        // weight pieces: byte offset inside a chunk's 18 KiB, also the LDS offset behind IN_BYTES
   unsigned hyx[6];         // the slot's halo pixel and vector slot (slot << 16 | row << 8 | column): item independent, so that an item's set-up is adds and compares
@@ -110,13 +110,13 @@ __global__ void __launch_bounds__(256, (RES ? 1 : 2)) conv_rows16_kernel(const C
     const int oy0 = sgpr(t.y), ox0 = sgpr(t.z), Hi = sgpr(it.y), Wi = sgpr(it.z);
     const int Hv = Hi << a.up, Wv = Wi << a.up;
     const unsigned char* inb = reinterpret_cast<const unsigned char*>(a.in) + ((long long)sgpr(it.x) * a.in_cs + a.in_coff) * 2;
-    rs_in = r16_rsrc(inb);
+    rs_in = buf_rsrc(inb);
 #pragma unroll
     for (int i = 0; i < 6; ++i) {                      // hyx[i]: the slot's halo pixel (row << 8 | column) and vector slot, fixed per lane; 0xFFFF: padding pixel
       const int hy = (int)(hyx[i] >> 8) & 0xFF, hx = (int)hyx[i] & 0xFF, sl = (int)(hyx[i] >> 16) & 3;
       const int iy = oy0 - 1 + hy, ix = ox0 - 1 + hx;
       const bool ok = (hyx[i] & 0xFFFFu) != 0xFFFFu && (unsigned)iy < (unsigned)Hv && (unsigned)ix < (unsigned)Wv;
-      isrc[i] = ok ? (unsigned)(((iy >> a.up) * Wi + (ix >> a.up)) * a.in_cs * 2 + sl * 16) : R16_OOB;
+      isrc[i] = ok ? (unsigned)(((iy >> a.up) * Wi + (ix >> a.up)) * a.in_cs * 2 + sl * 16) : BUF_OOB;
     }
   };
   uint4 ra[NP] = {}, rb[NP] = {};                      // two register sets
@@ -124,16 +124,16 @@ __global__ void __launch_bounds__(256, (RES ? 1 : 2)) conv_rows16_kernel(const C
     if (DBG & 4) return;
     if constexpr (RES) {                               // input pieces only: slots 0..4 as below, slot 5 = input piece 20 for every wave
       const unsigned o = isrc[p];
-      r = r16_bload(rs_in, o != R16_OOB ? o + (unsigned)(pf_c * 64) : R16_OOB);
+      r = buf_load16(rs_in, o != BUF_OOB ? o + (unsigned)(pf_c * 64) : BUF_OOB);
       return;
     }
     if (p < 5) {
-      r = r16_bload(rs_in, isrc[p] != R16_OOB ? isrc[p] + (unsigned)(pf_c * 64) : R16_OOB);
+      r = buf_load16(rs_in, isrc[p] != BUF_OOB ? isrc[p] + (unsigned)(pf_c * 64) : BUF_OOB);
     } else if (p < 9) {
-      r = r16_bload(rs_wp, wrel[p - 5], pf_c * G::W_BYTES);
+      r = buf_load16(rs_wp, wrel[p - 5], pf_c * G::W_BYTES);
     } else {                                           // the mixed slot: wave-uniform choice, no branch
-      const unsigned oi = isrc[5] != R16_OOB ? isrc[5] + (unsigned)(pf_c * 64) : R16_OOB;
-      r = r16_bload(s9_in ? rs_in : rs_wp, s9_in ? oi : wrel[4], s9_in ? 0 : pf_c * G::W_BYTES);
+      const unsigned oi = isrc[5] != BUF_OOB ? isrc[5] + (unsigned)(pf_c * 64) : BUF_OOB;
+      r = buf_load16(s9_in ? rs_in : rs_wp, s9_in ? oi : wrel[4], s9_in ? 0 : pf_c * G::W_BYTES);
     }
   };
   auto piece_stash = [&](unsigned char* sb, int p, const uint4& r) {
@@ -150,7 +150,7 @@ __global__ void __launch_bounds__(256, (RES ? 1 : 2)) conv_rows16_kernel(const C
       if (++pf_item < J) {
         setup_pf(pf_item);
       } else {                                         // stream exhausted: every later request is out of range (zeros, no traffic)
-        rs_in = r16_rsrc(wb, 0);
+        rs_in = buf_rsrc(wb, 0);
         rs_wp = rs_in;
       }
     }
@@ -263,7 +263,7 @@ __global__ void __launch_bounds__(256, (RES ? 1 : 2)) conv_rows16_kernel(const C
     const unsigned char* r1b = a.res1 ? reinterpret_cast<const unsigned char*>(a.res1) + (out_base * a.r1_cs + a.r1_coff) * 2 : wb;
     const unsigned char* r2b = a.res2 ? reinterpret_cast<const unsigned char*>(a.res2) + (out_base * a.r2_cs + a.r2_coff) * 2 : wb;
     unsigned char* ob = reinterpret_cast<unsigned char*>(a.out) + (out_base * a.out_cs + a.out_coff) * 2;
-    const auto rs_r1 = r16_rsrc(r1b), rs_r2 = r16_rsrc(r2b), rs_o = r16_rsrc(ob);
+    const auto rs_r1 = buf_rsrc(r1b), rs_r2 = buf_rsrc(r2b), rs_o = buf_rsrc(ob);
     const int ox = ox0 + pc;
     const int ch0 = nt0 * 32 + 8 * g;
 #pragma unroll
@@ -272,10 +272,10 @@ __global__ void __launch_bounds__(256, (RES ? 1 : 2)) conv_rows16_kernel(const C
       const bool ok = oy < Ho && ox < Wo;
       const unsigned rel_px = (unsigned)(oy * Wo + ox);
       uint4 r1v = make_uint4(0u, 0u, 0u, 0u), r2v = r1v;
-      if (a.res1) r1v = r16_bload(rs_r1, ok ? (rel_px * a.r1_cs + ch0) * 2 : R16_OOB);
-      if (a.res2) r2v = r16_bload(rs_r2, ok ? (rel_px * a.r2_cs + ch0) * 2 : R16_OOB);
+      if (a.res1) r1v = buf_load16(rs_r1, ok ? (rel_px * a.r1_cs + ch0) * 2 : BUF_OOB);
+      if (a.res2) r2v = buf_load16(rs_r2, ok ? (rel_px * a.r2_cs + ch0) * 2 : BUF_OOB);
       const u32x4 ov = r16_finish_px(acc[i][0], acc[i][1], a.act, a.res1 != nullptr, r1v, a.s1, a.res2 != nullptr, r2v, a.s2);
-      __builtin_amdgcn_raw_buffer_store_b128(ov, rs_o, ok ? (rel_px * a.out_cs + ch0) * 2 : R16_OOB, 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b128(ov, rs_o, ok ? (rel_px * a.out_cs + ch0) * 2 : BUF_OOB, 0, 0);
     }
   };
 
@@ -301,7 +301,7 @@ __global__ void __launch_bounds__(256, (RES ? 1 : 2)) conv_rows16_kernel(const C
       uint4 t[8];
 #pragma unroll
       for (int k = 0; k < 8; ++k)
-        if (p0 + 4 * k < n_wp) t[k] = r16_bload(rs_w, (unsigned)lane * 16u, sgpr((p0 + 4 * k) << 10));
+        if (p0 + 4 * k < n_wp) t[k] = buf_load16(rs_w, (unsigned)lane * 16u, sgpr((p0 + 4 * k) << 10));
 #pragma unroll
       for (int k = 0; k < 8; ++k)
         if (p0 + 4 * k < n_wp) *reinterpret_cast<uint4*>(smem + G::RES_W + ((p0 + 4 * k) << 10) + lane * 16) = t[k];
@@ -384,7 +384,7 @@ static bool rows16_resident(const ConvArgs& a) {
 bool conv_rows16_eligible(const ConvOp& op, const ConvArgs& a) {
   const PackedConv& pc = *op.pc;
   if (a.force_shape >= 0 && a.force_shape != 9 && a.force_shape != 23 && a.force_shape != 24) return false;   // tuning: another kernel was asked for
-  return pc.w16.p != nullptr && pc.dt == F16 && pc.k == 3 && op.stride == 1 && pc.cin % 32 == 0 && pc.cin >= 64 && pc.cout % 32 == 0 &&
+  return epilogue_fits(op, kEpiR16) && pc.w16.p != nullptr && pc.dt == F16 && pc.k == 3 && op.stride == 1 && pc.cin % 32 == 0 && pc.cin >= 64 && pc.cout % 32 == 0 &&
          pc.cout <= 128 && a.fast_out && op.out.cs % 8 == 0 && op.out.coff % 8 == 0;
 }
 

@@ -64,7 +64,7 @@ __global__ void __launch_bounds__(512, 2) conv_rows16pc_kernel(const ConvArgs a)
   const int NC = a.cin >> 5;
   const int Q = J * NC;                                // chunks of this workgroup: both roles run exactly Q iterations, one barrier each
   const unsigned char* wb = reinterpret_cast<const unsigned char*>(a.wpk) + (long long)nt0 * NC * G::W_BYTES;
-  const auto rs_w = r16_rsrc(wb);
+  const auto rs_w = buf_rsrc(wb);
   unsigned char* dump = smem + G::DUMP + wave * G::DUMP_W + lane * 16;       // this wave pair's exchange block
 
   if (producer) {
@@ -108,7 +108,7 @@ __global__ void __launch_bounds__(512, 2) conv_rows16pc_kernel(const ConvArgs a)
       const unsigned char* r1b = a.res1 ? reinterpret_cast<const unsigned char*>(a.res1) + (out_base * a.r1_cs + a.r1_coff) * 2 : wb;
       const unsigned char* r2b = a.res2 ? reinterpret_cast<const unsigned char*>(a.res2) + (out_base * a.r2_cs + a.r2_coff) * 2 : wb;
       unsigned char* ob = reinterpret_cast<unsigned char*>(a.out) + (out_base * a.out_cs + a.out_coff) * 2;
-      const auto rs_r1 = r16_rsrc(r1b), rs_r2 = r16_rsrc(r2b), rs_o = r16_rsrc(ob);
+      const auto rs_r1 = buf_rsrc(r1b), rs_r2 = buf_rsrc(r2b), rs_o = buf_rsrc(ob);
       const int ox = ox0 + pc;
       const int ch0 = nt0 * 32 + 8 * g;
 #pragma unroll
@@ -117,10 +117,10 @@ __global__ void __launch_bounds__(512, 2) conv_rows16pc_kernel(const ConvArgs a)
         const bool ok = oy < Ho && ox < Wo;
         const unsigned rel_px = (unsigned)(oy * Wo + ox);
         uint4 r1v = make_uint4(0u, 0u, 0u, 0u), r2v = r1v;
-        if (a.res1) r1v = r16_bload(rs_r1, ok ? (rel_px * a.r1_cs + ch0) * 2 : R16_OOB);
-        if (a.res2) r2v = r16_bload(rs_r2, ok ? (rel_px * a.r2_cs + ch0) * 2 : R16_OOB);
+        if (a.res1) r1v = buf_load16(rs_r1, ok ? (rel_px * a.r1_cs + ch0) * 2 : BUF_OOB);
+        if (a.res2) r2v = buf_load16(rs_r2, ok ? (rel_px * a.r2_cs + ch0) * 2 : BUF_OOB);
         const u32x4 ov = r16_finish_px(acc[i][0], acc[i][1], a.act, a.res1 != nullptr, r1v, a.s1, a.res2 != nullptr, r2v, a.s2);
-        __builtin_amdgcn_raw_buffer_store_b128(ov, rs_o, ok ? (rel_px * a.out_cs + ch0) * 2 : R16_OOB, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(ov, rs_o, ok ? (rel_px * a.out_cs + ch0) * 2 : BUF_OOB, 0, 0);
       }
     };
 

@@ -129,13 +129,12 @@ __global__ void __launch_bounds__(768, 3) conv_trunk_kernel(const TrunkArgs a) {
   const int n_tiles = a.n_tiles_dev ? sload(a.n_tiles_dev, 0) : a.ntiles_host;
   const unsigned total = (unsigned)n_tiles * (unsigned)a.n_blocks;
   if (total == 0) return;
-  constexpr unsigned OOB = 0xFFFFFFFFu;
   constexpr int AUXC = COH ? 16 : 0;                          // sc1 on activation loads / stores of a multi-layer launch
 
   // fragment read offsets (compute wave w: output rows 8w..8w+7): halo rows 8 * wave + r (r = 0..9), column pc + kx, slot g
   unsigned boff[3];
   r16_frag_offsets(8 * (wave & 3), pc, g, boff);
-  unsigned isrc[6];        // loader waves 1..7: byte offset of the lane's 16 bytes of chunk 0 from the image's first pixel record (+ in_coff), or OOB
+  unsigned isrc[6];        // loader waves 1..7: byte offset of the lane's 16 bytes of chunk 0 from the image's first pixel record (+ in_coff), or BUF_OOB
 
   // ---- control (wave 0): the queue, the tile entries and the dependency counters of the next three items -----------------------------------------
   int ck = -1;             // sequence number (within this workgroup) of the CURRENT item (-1: none yet); slot = seq & 3
@@ -298,7 +297,7 @@ __global__ void __launch_bounds__(768, 3) conv_trunk_kernel(const TrunkArgs a) {
       const int sl = (lane & 3) ^ ((hx >> 1) & 2);                   // which holds SOURCE slot (lane % 4) ^ ((hx >> 1) & 2): conflict-free fragment reads
       const int iy = it.y0 - 1 + hy, ix = it.x0 - 1 + hx;
       const bool ok = w8 > 0 && p < G::PIX_PIECES && q < G::HR * G::HC && (unsigned)iy < (unsigned)it.H && (unsigned)ix < (unsigned)it.W;
-      isrc[i] = ok ? (unsigned)((iy * it.W + ix) * cs * 2 + sl * 16) : OOB;
+      isrc[i] = ok ? (unsigned)((iy * it.W + ix) * cs * 2 + sl * 16) : BUF_OOB;
     }
     pix_item = seq;
   };
@@ -324,7 +323,7 @@ __global__ void __launch_bounds__(768, 3) conv_trunk_kernel(const TrunkArgs a) {
     if ((FFP_TRUNK_SKIP & 4)) return;
     const int q = w8 + 8 * j;
     if (q < 18) dma16<false>(rs_w, (unsigned)lane * 16u, (unsigned)(w_soff0 + ((c * 18 + q) << 10)), st + (unsigned)(q << 10));
-    else if (first && q == 23) dma16<false>(rs_b, lane < 8 ? (unsigned)lane * 16u : OOB, 0u, bst);
+    else if (first && q == 23) dma16<false>(rs_b, lane < 8 ? (unsigned)lane * 16u : BUF_OOB, 0u, bst);
   };
   // wait until at most `keep` of this wave's vector-memory operations are outstanding (the youngest ones: a step's pixel pieces are requested
   // last and belong to the step after next — they are NOT waited for at the end of the step that requests them)
@@ -422,7 +421,7 @@ __global__ void __launch_bounds__(768, 3) conv_trunk_kernel(const TrunkArgs a) {
     const float s1 = e.s1, s2 = e.s2;
     const int o_cs = e.o_cs, r1_cs = e.r1_cs, r2_cs = e.r2_cs;
     const bool has1 = e.has1, has2 = e.has2;
-    const auto rs_o = r16_rsrc(e.ob), rs_r1 = r16_rsrc(e.r1b), rs_r2 = r16_rsrc(e.r2b);
+    const auto rs_o = buf_rsrc(e.ob), rs_r1 = buf_rsrc(e.r1b), rs_r2 = buf_rsrc(e.r2b);
     const int ox = it.x0 + pc;
     const int ch0 = it.nb * 32 + 8 * g;
 #pragma unroll
@@ -432,10 +431,10 @@ __global__ void __launch_bounds__(768, 3) conv_trunk_kernel(const TrunkArgs a) {
       const bool ok = oy < it.H && ox < it.W;
       const unsigned rel = (unsigned)(oy * it.W + ox);
       u32x4 r1v = {0u, 0u, 0u, 0u}, r2v = r1v;
-      if (has1) r1v = __builtin_amdgcn_raw_buffer_load_b128(rs_r1, ok ? (rel * r1_cs + ch0) * 2 : OOB, 0, AUXC);
-      if (has2) r2v = __builtin_amdgcn_raw_buffer_load_b128(rs_r2, ok ? (rel * r2_cs + ch0) * 2 : OOB, 0, AUXC);
+      if (has1) r1v = __builtin_amdgcn_raw_buffer_load_b128(rs_r1, ok ? (rel * r1_cs + ch0) * 2 : BUF_OOB, 0, AUXC);
+      if (has2) r2v = __builtin_amdgcn_raw_buffer_load_b128(rs_r2, ok ? (rel * r2_cs + ch0) * 2 : BUF_OOB, 0, AUXC);
       const u32x4 ov = r16_finish_px(acc[i][0], acc[i][1], act, has1, r1v, s1, has2, r2v, s2);
-      __builtin_amdgcn_raw_buffer_store_b128(ov, rs_o, ok ? (rel * o_cs + ch0) * 2 : OOB, 0, AUXC);
+      __builtin_amdgcn_raw_buffer_store_b128(ov, rs_o, ok ? (rel * o_cs + ch0) * 2 : BUF_OOB, 0, AUXC);
     }
   };
   // ---- the epilogue's other form. Global stores issue at ~14 B/clk per CU: an item's 32 KiB cost its compute waves ~4 us with the matrix pipe
@@ -454,7 +453,7 @@ __global__ void __launch_bounds__(768, 3) conv_trunk_kernel(const TrunkArgs a) {
     const LPtr L = layers + it.layer;
     const int o_cs = L->out_cs;
     unsigned char* ob = reinterpret_cast<unsigned char*>(L->out) + ((long long)it.px0 * o_cs + L->out_coff) * 2;
-    const auto rs_o = r16_rsrc(ob);
+    const auto rs_o = buf_rsrc(ob);
     const int ox = it.x0 + pc, ch0 = it.nb * 32 + 8 * g;
     u32x4 d[4];
 #pragma unroll
@@ -463,7 +462,7 @@ __global__ void __launch_bounds__(768, 3) conv_trunk_kernel(const TrunkArgs a) {
     for (int w = 0; w < 4; ++w) {
       const int oy = it.y0 + 8 * w + w8;
       const bool ok = oy < it.H && ox < it.W;
-      __builtin_amdgcn_raw_buffer_store_b128(d[w], rs_o, ok ? ((unsigned)(oy * it.W + ox) * o_cs + ch0) * 2 : OOB, 0, AUXC);
+      __builtin_amdgcn_raw_buffer_store_b128(d[w], rs_o, ok ? ((unsigned)(oy * it.W + ox) * o_cs + ch0) * 2 : BUF_OOB, 0, AUXC);
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");        // the rows are in registers before this wave's next DMA pieces land on them
   };
@@ -704,7 +703,7 @@ bool conv_trunk_layer_ok(const ConvOp& op) {
   const int cpl = 8;
   // one image table serves input, output and residuals: the same Level, or (single-operator hooks) exact-mode levels of identical geometry
   auto same = [](const Level* x, const Level* y) { return x == y || (x && y && !x->capacity() && !y->capacity() && x->n == y->n && x->h == y->h && x->w == y->w && x->off == y->off); };
-  bool ok = pc.w16.p != nullptr && pc.dt == F16 && pc.k == 3 && op.stride == 1 && op.up == 0 && !op.has_up2 && pc.cin % 32 == 0 && pc.cin >= 64 &&
+  bool ok = epilogue_fits(op, kEpiR16) && pc.w16.p != nullptr && pc.dt == F16 && pc.k == 3 && op.stride == 1 && op.up == 0 && !op.has_up2 && pc.cin % 32 == 0 && pc.cin >= 64 &&
             (pc.cout == 32 || pc.cout == 64) && op.in.dt == F16 && op.out.dt == F16 && same(op.in.lvl, op.out.lvl) && op.in.cs % cpl == 0 && op.in.coff % cpl == 0 &&
             op.out.cs % cpl == 0 && op.out.coff % cpl == 0;
   if (op.has_res1) ok = ok && op.res1.dt == F16 && same(op.res1.lvl, op.out.lvl) && op.res1.cs % cpl == 0 && op.res1.coff % cpl == 0;

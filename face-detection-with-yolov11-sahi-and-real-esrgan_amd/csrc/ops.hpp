@@ -13,7 +13,7 @@ struct ConvOp {
   TView in, out;
   int stride = 1;
   int act = ACT_NONE;
-  int act_post = ACT_NONE;   // after the residual terms (ResNet BasicBlock: Relu(Add(conv, identity))); kernels that take no residual refuse it
+  int act_post = ACT_NONE;   // after the residual terms (ResNet BasicBlock: Relu(Add(conv, identity))); kernels whose EpiCaps (conv_args.hpp) lack it are never offered the op
   int up = 0;
   bool has_res1 = false, has_res2 = false;
   TView res1, res2;

@@ -1,6 +1,6 @@
 // ops_misc.hip — the HBM-bound operators around the MFMA convolutions: depthwise 3x3, SPPF pooling, nearest x2,
 // C2PSA attention, LetterBox preprocessing. All work on ragged NHWC batches described by level tables.
-#include "ops.hpp"
+#include "conv_args.hpp"
 #include "letterbox.hpp"
 
 namespace ffp {
@@ -602,9 +602,12 @@ inline unsigned blocks_for(long long n, int bs) { return (unsigned)((n + bs - 1)
 
 }  // namespace
 
+// bias + act_fn (every activation), nothing after it: the image-input kernels; the depthwise kernels add one unscaled residual
+static constexpr EpiCaps kEpiDirect{EPI_ALL_ACTS, false, false, true, true};
+static constexpr EpiCaps kEpiDw{EPI_ALL_ACTS, true, false, true, true};
 bool conv_direct_eligible(const ConvOp& op) {
   const PackedConv& pc = *op.pc;
-  return pc.w_direct.p != nullptr && pc.k == 3 && !op.up && !op.has_res1 && !op.has_res2 && !op.act_post && op.out.dt == pc.dt && op.in.coff == 0 &&
+  return epilogue_fits(op, kEpiDirect) && pc.w_direct.p != nullptr && pc.k == 3 && !op.up && op.out.dt == pc.dt && op.in.coff == 0 &&
          (pc.cout == 16 || pc.cout == 32 || pc.cout == 64) && op.out.cs % 4 == 0 && op.out.coff % 4 == 0 && op.in.cs == (pc.dt == F16 ? 8 : 4);
 }
 
@@ -654,6 +657,8 @@ void launch_dwconv(const DwConvOp& op, hipStream_t st) {
   FFP_CHECK(pc.depthwise() && pc.k == 3, FFP_ERR_ARG, "dwconv %s: expects depthwise 3x3", pc.name.c_str());
   const int C = pc.cout;
   FFP_CHECK(op.out.C == C && op.in.lvl == op.out.lvl, FFP_ERR_ARG, "dwconv %s: view mismatch", pc.name.c_str());
+  FFP_CHECK(epilogue_fits(op.act, op.has_res, ACT_NONE, op.out.dt, kEpiDw) && op.out.dt == op.in.dt && (!op.has_res || op.res.dt == op.in.dt), FFP_ERR_ARG,
+            "dwconv %s: activation %d / element types outside what the depthwise kernels do", pc.name.c_str(), op.act);
   const int grp = op.grp > 0 ? op.grp : C;
   const int gstride = op.grp > 0 ? op.grp_stride : C;
   FFP_CHECK(C % 4 == 0 && grp % 4 == 0 && op.in.cs % 4 == 0 && (op.in.coff + op.grp_off) % 4 == 0 && gstride % 4 == 0 && op.out.cs % 4 == 0 &&

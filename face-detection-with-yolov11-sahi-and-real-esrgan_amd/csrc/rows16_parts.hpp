@@ -1,7 +1,6 @@
 // rows16_parts.hpp — the ONE copy of what conv_rows16_kernel (conv_rows16.hip), conv_rows16pc_kernel (conv_rows16pc.hip) and
-// conv_trunk_kernel (conv_trunk.hip) have in common: geometry, buffer resources, item dealing and the register epilogue of a pixel for
-// all three; the staging lane tables, the prefetch cursor, the fragment offsets and the bias start of the accumulators for the two
-// opt-in kernels. The kernels are bit-identical because they run THIS text, not copies of it. Device-only; every function is a free
+// conv_trunk_kernel (conv_trunk.hip) have in common: geometry, item dealing and the register epilogue of a pixel for all three; the
+// staging lane tables, the prefetch cursor, the fragment offsets and the bias start of the accumulators for the two opt-in kernels. The kernels are bit-identical because they run THIS text, not copies of it. Device-only; every function is a free
 // __forceinline__ function over the caller's own registers (wrapping the lane tables in a struct, or passing kernel arguments by value,
 // changes hipcc's register allocation). conv_rows16_kernel still carries its own text of the second group: there even the free-function
 // form moves the shipped kernel's instruction stream (profiles/rows16_shared_parts_ab.txt), which has to be timed before it may change.
@@ -23,21 +22,6 @@ struct R16Geo {
   static constexpr int NP = 10;                               // wave-pieces per wave and chunk: 5 input, 4 weight, 1 mixed (see r16_piece_fetch)
   static constexpr int TCAP = 40;                             // work items one workgroup walks (descriptor table in LDS)
 };
-
-constexpr unsigned R16_OOB = 0xFFFFFFFFu;                     // buffer offset of a lane with nothing to read or write: zeros / dropped
-
-// raw buffer resource over [p, p + bytes), p made wave-uniform (readfirstlane'd halves: the descriptor lives in SGPRs)
-__device__ __forceinline__ auto r16_rsrc(const unsigned char* p, unsigned bytes = 0x7FFFFFF0) {
-  const unsigned long long u = reinterpret_cast<unsigned long long>(p);
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-  return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<unsigned char*>(((unsigned long long)hi << 32) | lo), 0, bytes, 0x00020000);
-}
-typedef decltype(r16_rsrc(nullptr)) r16_rsrc_t;
-
-__device__ __forceinline__ uint4 r16_bload(r16_rsrc_t rs, unsigned off, int soff = 0) {      // soff: wave-uniform byte offset (an SGPR operand, no VALU)
-  const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs, off, soff, 0);
-  return make_uint4(v[0], v[1], v[2], v[3]);
-}
 
 // ---- this workgroup's items: logical ids first + j * Ws, j < J ---------------------------------------------------------------------
 // Items are dealt so that each XCD (workgroups b, b + 8, ... share one) gets a contiguous run of logical ids (pixel tile x
@@ -93,30 +77,30 @@ __device__ __forceinline__ void r16_stage_tables(int wave, int lane, unsigned (&
 }
 
 // the prefetch cursor moves to item j: its input resource and, per slot, isrc = byte offset of (pixel, slot) from the item's image base; OOB: zeros
-__device__ __forceinline__ void r16_setup_pf(const ConvArgs& a, const int4* desc, int j, const unsigned (&hyx)[6], unsigned (&isrc)[6], r16_rsrc_t& rs_in) {
+__device__ __forceinline__ void r16_setup_pf(const ConvArgs& a, const int4* desc, int j, const unsigned (&hyx)[6], unsigned (&isrc)[6], buf_rsrc_t& rs_in) {
   const int4 t = desc[j * 3], it = desc[j * 3 + 1];
   const int oy0 = __builtin_amdgcn_readfirstlane(t.y), ox0 = __builtin_amdgcn_readfirstlane(t.z);
   const int Hi = __builtin_amdgcn_readfirstlane(it.y), Wi = __builtin_amdgcn_readfirstlane(it.z);
   const int Hv = Hi << a.up, Wv = Wi << a.up;
   const unsigned char* inb = reinterpret_cast<const unsigned char*>(a.in) + ((long long)__builtin_amdgcn_readfirstlane(it.x) * a.in_cs + a.in_coff) * 2;
-  rs_in = r16_rsrc(inb);
+  rs_in = buf_rsrc(inb);
 #pragma unroll
   for (int i = 0; i < 6; ++i) {                      // hyx[i]: fixed per lane; 0xFFFF: padding pixel
     const int hy = (int)(hyx[i] >> 8) & 0xFF, hx = (int)hyx[i] & 0xFF, sl = (int)(hyx[i] >> 16) & 3;
     const int iy = oy0 - 1 + hy, ix = ox0 - 1 + hx;
     const bool ok = (hyx[i] & 0xFFFFu) != 0xFFFFu && (unsigned)iy < (unsigned)Hv && (unsigned)ix < (unsigned)Wv;
-    isrc[i] = ok ? (unsigned)(((iy >> a.up) * Wi + (ix >> a.up)) * a.in_cs * 2 + sl * 16) : R16_OOB;
+    isrc[i] = ok ? (unsigned)(((iy >> a.up) * Wi + (ix >> a.up)) * a.in_cs * 2 + sl * 16) : BUF_OOB;
   }
 }
 // slot p of chunk pf_c of the prefetch cursor's item -> r
-__device__ __forceinline__ void r16_piece_fetch(int p, uint4& r, r16_rsrc_t rs_in, r16_rsrc_t rs_wp, const unsigned (&isrc)[6], const unsigned (&wrel)[5], int pf_c, bool s9_in) {
+__device__ __forceinline__ void r16_piece_fetch(int p, uint4& r, buf_rsrc_t rs_in, buf_rsrc_t rs_wp, const unsigned (&isrc)[6], const unsigned (&wrel)[5], int pf_c, bool s9_in) {
   if (p < 5) {
-    r = r16_bload(rs_in, isrc[p] != R16_OOB ? isrc[p] + (unsigned)(pf_c * 64) : R16_OOB);
+    r = buf_load16(rs_in, isrc[p] != BUF_OOB ? isrc[p] + (unsigned)(pf_c * 64) : BUF_OOB);
   } else if (p < 9) {
-    r = r16_bload(rs_wp, wrel[p - 5], pf_c * R16Geo::W_BYTES);
+    r = buf_load16(rs_wp, wrel[p - 5], pf_c * R16Geo::W_BYTES);
   } else {                                           // the mixed slot: wave-uniform choice, no branch
-    const unsigned oi = isrc[5] != R16_OOB ? isrc[5] + (unsigned)(pf_c * 64) : R16_OOB;
-    r = r16_bload(s9_in ? rs_in : rs_wp, s9_in ? oi : wrel[4], s9_in ? 0 : pf_c * R16Geo::W_BYTES);
+    const unsigned oi = isrc[5] != BUF_OOB ? isrc[5] + (unsigned)(pf_c * 64) : BUF_OOB;
+    r = buf_load16(s9_in ? rs_in : rs_wp, s9_in ? oi : wrel[4], s9_in ? 0 : pf_c * R16Geo::W_BYTES);
   }
 }
 // slot p in r -> the LDS stage at sb
@@ -127,14 +111,14 @@ __device__ __forceinline__ void r16_piece_stash(unsigned char* sb, int p, const 
 }
 // after the last piece of a chunk has been requested: next chunk, next item, or the end of the stream (wb: the weights, any valid base)
 __device__ __forceinline__ void r16_advance_pf(const ConvArgs& a, const int4* desc, int J, int NC, const unsigned char* wb, int& pf_item, int& pf_c,
-                                               const unsigned (&hyx)[6], unsigned (&isrc)[6], r16_rsrc_t& rs_in, r16_rsrc_t& rs_wp) {
+                                               const unsigned (&hyx)[6], unsigned (&isrc)[6], buf_rsrc_t& rs_in, buf_rsrc_t& rs_wp) {
   if (pf_item >= J) return;
   if (++pf_c == NC) {
     pf_c = 0;
     if (++pf_item < J) {
       r16_setup_pf(a, desc, pf_item, hyx, isrc, rs_in);
     } else {                                         // stream exhausted: every later request is out of range (zeros, no traffic)
-      rs_in = r16_rsrc(wb, 0);
+      rs_in = buf_rsrc(wb, 0);
       rs_wp = rs_in;
     }
   }
@@ -158,6 +142,10 @@ template <int ROWS> __device__ __forceinline__ void r16_zero_acc(f32x4 (&acc)[RO
 }
 
 // ---- register epilogue of one pixel: the lane's 8 consecutive channels (two accumulators) -> activation -> v * s1 + res1 -> v * s2 + res2 -> 8 x fp16
+// A deliberately cheaper subset of the ConvOp contract (ops.hpp), bias already in the sums: LReLU as max(x, 0.2 x), SiLU, none — no ReLU arm
+// and no act_post (either would add to the shipped kernels' instruction stream). kEpiR16 says exactly that, and conv_rows16_eligible /
+// conv_trunk_layer_ok start from it: an op outside it runs on conv_rows_kernel or the generic kernel.
+constexpr EpiCaps kEpiR16{1u << ACT_NONE | 1u << ACT_SILU | 1u << ACT_LRELU, true, false, true, false};
 template <class R> __device__ __forceinline__ u32x4 r16_finish_px(const f32x4& acc0, const f32x4& acc1, int act, bool has1, const R& r1v, float s1, bool has2, const R& r2v, float s2) {
   float v[8];
   v[0] = acc0[0]; v[1] = acc0[1]; v[2] = acc0[2]; v[3] = acc0[3];

@@ -344,9 +344,14 @@ int ffp_op_conv1x1_up2(int device, int precision, const float* coarse, const flo
                        const float* wt, const float* bias, int cout, int act, float* y);
 
 /* Tuning / test hook: pin the workgroup shape ffp_op_conv2d uses from now on (process-wide; -1 = automatic, the default).
- * 0..5 generic shapes, 9 conv_rows16, 10..16 the pointwise kernels of conv_pw.hip. A shape that cannot run the op is an error
- * of the following ffp_op_conv2d call. */
+ * 0..5 generic shapes, 6..8 conv_rows, 9 / 23 / 24 the conv_rows16 kernels, 10..16 and 22 the pointwise kernels of conv_pw.hip, 17..21
+ * conv_k3d, 25 conv_trunk. A specialised shape (6 and up) that cannot run the op — its layout, or an activation, residual or
+ * post-activation its epilogue does not implement — is FFP_ERR_ARG of the following ffp_op_conv2d call. */
 int ffp_op_conv2d_shape(int force_shape);
+/* Test hook of the same kind and lifetime: the activation code (0 none, 1 SiLU, 2 LeakyReLU(0.2), 3 ReLU) ffp_op_conv2d applies AFTER the
+ * residual term from now on (ConvOp::act_post; process-wide; 0 = none, the default). Any other code: FFP_ERR_ARG; a depthwise
+ * ffp_op_conv2d call while it is set: FFP_ERR_ARG. */
+int ffp_op_conv2d_act_post(int act);
 
 /* ---- the detector's non-convolution kernels one at a time (operator parity tests) ----------------------------------------
  * A batch is n images of hs[i] x ws[i] pixels; host arrays hold them back to back as [sum hs*ws][cs] fp32 pixel records, and a

@@ -8,7 +8,7 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
-ACTS = {0: lambda t: t, 1: F.silu, 2: lambda t: F.leaky_relu(t, 0.2)}
+ACTS = {0: lambda t: t, 1: F.silu, 2: lambda t: F.leaky_relu(t, 0.2), 3: F.relu}
 
 
 def ref_conv(x, w, b, stride, groups, act, up, res, res_scale, half):
@@ -129,12 +129,14 @@ def test_conv_rows_kernel_random_shapes(gpu_lib):
     folded x2 upsample and the residual epilogue; every case is also run through the generic kernel (force via cin % 32 != 0
     is impossible here, so the comparison is against the PyTorch reference only)."""
     rng = np.random.default_rng(20260101)
-    for it in range(24):
+    for it in range(32):
         n = int(rng.integers(1, 4))
         h, w = int(rng.integers(1, 70)), int(rng.integers(1, 70))
         cin = int(rng.choice([64, 96, 128, 160, 192]))
         cout = int(rng.choice([32, 64, 96, 128]))
         act = int(rng.choice([0, 1, 2]))
+        if it >= 24:
+            act = 3                                 # ReLU: appended cases, the seed's first 24 draws stay what they were
         up = int(rng.integers(0, 2)) if h * w <= 900 else 0
         has_res = bool(rng.integers(0, 2))
         x = rng.standard_normal((n, h, w, cin), dtype=np.float32)
@@ -352,7 +354,9 @@ def test_conv_k3_direct_weight_kernels(gpu_lib, case):
 def test_conv_rows16_weight_resident_form_is_bit_identical(gpu_lib):
     """conv_rows16_kernel<., RES = true> (force_shape 23: one workgroup per CU, the channel block's weights loaded into LDS once per
     workgroup instead of once per tile) and conv_rows16pc_kernel (force_shape 24: producer waves stage and store, consumer waves
-    multiply) against the streaming form (force_shape 9): same MFMAs in the same order -> identical bits; and against the fp16 reference. Ragged sizes, many tiles per workgroup, residual / upsample epilogues, 1..6 chunks."""
+    multiply) against the streaming form (force_shape 9): same MFMAs in the same order -> identical bits; and against the fp16 reference. Ragged sizes, many tiles per workgroup, residual / upsample epilogues, 1..6 chunks.
+    No ReLU case here: the rows16 family does not implement ReLU, so a forced 9 / 23 / 24 with act 3 is the library's argument error
+    (test_conv_epilogue_contract_every_kernel checks that refusal); the ReLU draws are in test_conv_rows_kernel_random_shapes."""
     rng = np.random.default_rng(20261004)
     cases = [(2, 41, 42, 64, 32, 2, 0, False), (1, 70, 33, 96, 32, 2, 0, True), (3, 16, 16, 128, 32, 2, 0, False), (2, 52, 33, 160, 32, 2, 0, True),
              (1, 96, 96, 192, 64, 0, 0, True), (2, 17, 16, 64, 64, 2, 1, False), (1, 1, 1, 64, 32, 2, 0, False), (40, 24, 24, 128, 32, 2, 0, False),
@@ -376,3 +380,79 @@ def test_conv_rows16_weight_resident_form_is_bit_identical(gpu_lib):
             np.testing.assert_allclose(y23, ref_conv(x, wt, b, 1, 1, act, up, res, 0.2, True), rtol=2e-3, atol=2e-3)
     finally:
         gpu_lib.op_conv2d_shape(-1)
+
+
+# ---- the epilogue contract (ConvOp in ops.hpp: act -> v * s1 + res1 -> act_post), kernel family by kernel family -------------------
+# force_shape -> (family, (cin, cout, k, stride) of the smallest row of the family's case table above that the shape can run).
+# Every case runs on two images with a 9 x 17 output: ragged tile edges in both directions.
+EPI_GENERIC = [(s_, 64, 128, 1, 1) for s_ in range(6)] + [(4, 64, 32, 3, 1), (5, 64, 32, 3, 1)] + [(s_, 64, 128, 3, 2) for s_ in (0, 1, 2, 4)]      # CASES
+EPI_ROWS = [(6, 64, 32, 3, 1), (7, 64, 32, 3, 1), (8, 64, 64, 3, 1),                                 # conv_rows (8: two channel tiles per workgroup)
+            (9, 64, 32, 3, 1), (23, 64, 32, 3, 1), (24, 64, 32, 3, 1), (25, 64, 32, 3, 1)]          # conv_rows16, its resident form, conv_rows16pc, conv_trunk
+
+
+def _epi_pw_cases():
+    out = []
+    for shape in sorted(PW_SHAPES):
+        n, h, w, cin, cout, act = min((c for c in PW_CASES if pw_can_run(shape, c[3], c[4])), key=lambda c: c[3] * c[4])
+        out.append((shape, cin, cout, 1, 1))
+    return out
+
+
+def _epi_k3d_cases():
+    out = []
+    for shape, min_tiles in sorted(K3D_SHAPES.items()):
+        n, h, w, cin, cout, stride, act, r = min((c for c in K3D_CASES if -(-c[4] // 32) >= min_tiles), key=lambda c: c[3] * c[4])
+        out.append((shape, cin, cout, 3, stride))
+    return out
+
+
+def test_conv_epilogue_contract_every_kernel(gpu_lib):
+    """act in {none, SiLU, LeakyReLU, ReLU} x residual {none, res1 with scale 0.2} x act_post {none, ReLU after the residual} through every
+    kernel family by its force_shape number. A call either matches the reference (ref_conv, then the post-activation) within this
+    file's tolerance for the precision, or the library refuses it with its argument error; a wrong tensor is the only failure.
+    Standard-normal inputs: a dropped ReLU is an O(1) error on about half the outputs."""
+    P = gpu_lib
+    plan = [("generic", P.PREC_F32, c) for c in EPI_GENERIC] + [("generic", P.PREC_F16, c) for c in EPI_GENERIC] + \
+           [("generic", P.PREC_F32X3, c) for c in EPI_GENERIC] + [("rows", P.PREC_F16, c) for c in EPI_ROWS] + \
+           [("pw", P.PREC_F32X3, c) for c in _epi_pw_cases()] + [("k3d", P.PREC_F32X3, c) for c in _epi_k3d_cases()]
+    tol = {P.PREC_F32: 2e-5, P.PREC_F16: 2e-3, P.PREC_F32X3: 3e-5}
+    rng = np.random.default_rng(20261018)
+    data, wrong, ran, refused = {}, [], 0, 0
+    try:
+        for family, prec, (shape, cin, cout, k, stride) in plan:
+            if family == "generic" and prec == P.PREC_F32X3 and k == 3 and stride == 2 and shape in (0, 1):
+                continue                             # not among the valid ones: the split's wide 3x3 stride-2 stages do not fit the LDS
+            half = prec == P.PREC_F16
+            key = (cin, cout, k, stride, half)
+            if key not in data:                      # inputs and the eight references (act x residual) once per case and rounding
+                hi, wi = (9, 17) if stride == 1 else (17, 33)
+                x = rng.standard_normal((2, hi, wi, cin), dtype=np.float32)
+                wt = (rng.standard_normal((cout, cin, k, k), dtype=np.float32) / np.sqrt(cin * k * k)).astype(np.float32)
+                b = rng.standard_normal(cout, dtype=np.float32) * 0.1
+                res = rng.standard_normal((2, 9, 17, cout), dtype=np.float32)
+                refs = {(act, r): ref_conv(x, wt, b, stride, 1, act, 0, res if r else None, 0.2, half) for act in ACTS for r in (False, True)}
+                data[key] = (x, wt, b, res, refs)
+            x, wt, b, res, refs = data[key]
+            P.op_conv2d_shape(shape)
+            for act in ACTS:
+                for has_res, post in ((False, 0), (True, 0), (True, 3)):
+                    P.op_conv2d_act_post(post)
+                    try:
+                        y = P.op_conv2d(x, wt, b, stride=stride, act=act, res=res if has_res else None, res_scale=0.2 if has_res else 1.0, precision=prec)
+                    except P.FfpError as e:
+                        assert e.code == 1, (family, shape, act, has_res, post, str(e))      # FFP_ERR_ARG: this kernel cannot run the op
+                        refused += 1
+                        continue
+                    ref = ACTS[post](torch.from_numpy(refs[(act, has_res)])).numpy()
+                    ran += 1
+                    if y.shape != ref.shape or not np.allclose(y, ref, rtol=tol[prec], atol=tol[prec]):
+                        wrong.append((family, {P.PREC_F32: "f32", P.PREC_F16: "f16", P.PREC_F32X3: "f32x3"}[prec], shape, f"{cin}->{cout} k{k}s{stride}",
+                                      f"act{act} res{int(has_res)} post{post}", float(np.abs(y - ref).max()) if y.shape == ref.shape else "shape"))
+    finally:
+        P.op_conv2d_shape(-1)
+        P.op_conv2d_act_post(0)
+    print(f"epilogue contract: {ran} calls compared, {refused} refused, {len(wrong)} wrong")
+    for wline in wrong:
+        print("  wrong:", *wline)
+    assert not wrong, wrong
+    assert ran >= 12 * (len(EPI_GENERIC) * 3 - 2)    # the generic kernel refuses nothing
