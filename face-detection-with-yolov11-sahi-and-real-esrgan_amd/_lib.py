@@ -123,6 +123,8 @@ _SIGS = {
     "ffp_jpeg_decode_dev": (C.c_int, [C.c_int, _p(C.c_uint8), C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int64]),
     "ffp_jpeg_decode_stats": (C.c_int, [_p(C.c_int64), _p(C.c_int64), _p(C.c_int64)]),
     "ffp_op_conv2d_shape": (C.c_int, [C.c_int]),
+    "ffp_op_conv2d_shape_name": (C.c_int, [C.c_int, C.c_char_p, C.c_int]),
+    "ffp_op_conv2d_last_variant": (C.c_int, [C.c_char_p, C.c_int]),
     "ffp_op_conv2d_act_post": (C.c_int, [C.c_int]),
     "ffp_op_conv1x1_up2": (C.c_int, [C.c_int, C.c_int, _p(C.c_float), _p(C.c_float), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_float),
                                      _p(C.c_float), C.c_int, C.c_int, _p(C.c_float)]),
@@ -1256,6 +1258,20 @@ def op_resize_lanczos4(img: np.ndarray, out_h: int, out_w: int, device: int = 0)
 def op_conv2d_shape(shape: int = -1) -> None:
     """Pin the workgroup shape of the following op_conv2d calls (tests of one kernel variant); -1 restores the automatic choice."""
     _check(lib().ffp_op_conv2d_shape(int(shape)))
+
+
+def op_conv2d_shape_name(shape: int) -> str:
+    """'<family> <variant suffix>' of a shape number (the table in csrc/conv_route.cpp); FfpError code 1 for a number that is no shape. No device."""
+    out = C.create_string_buffer(64)
+    _check(lib().ffp_op_conv2d_shape_name(int(shape), out, len(out)))
+    return out.value.decode()
+
+
+def op_conv2d_last_variant() -> str:
+    """Variant string of the op the last op_conv2d / op_conv1x1_up2 call of this thread launched ('' if it launched no dense conv)."""
+    out = C.create_string_buffer(64)
+    _check(lib().ffp_op_conv2d_last_variant(out, len(out)))
+    return out.value.decode()
 
 
 def op_conv2d_act_post(act: int = 0) -> None:

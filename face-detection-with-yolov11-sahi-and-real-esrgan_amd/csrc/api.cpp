@@ -5,6 +5,7 @@
 #include <cmath>
 
 #include "coco_eval.hpp"
+#include "conv_route.hpp"
 #include "eval.hpp"
 #include "iqa.hpp"
 #include "jpeg.hpp"
@@ -932,10 +933,28 @@ int ffp_jpeg_decode_stats(int64_t* device_decodes, int64_t* host_fallbacks, int6
   FFP_API_END
 }
 
-static int g_op_conv_shape = -1;
+static int g_op_conv_shape = SHAPE_AUTO;
 int ffp_op_conv2d_shape(int force_shape) {
+  FFP_API_BEGIN
+  FFP_CHECK(force_shape == SHAPE_AUTO || conv_shape_info(force_shape), FFP_ERR_ARG, "conv2d_shape: %d is not a shape number", force_shape);
   g_op_conv_shape = force_shape;
-  return FFP_OK;
+  FFP_API_END
+}
+
+int ffp_op_conv2d_shape_name(int shape, char* out, int cap) {
+  FFP_API_BEGIN
+  const ConvShapeInfo* s = conv_shape_info(shape);
+  FFP_CHECK(s && out && cap > 0, FFP_ERR_ARG, "conv2d_shape_name: %d is not a shape number, or no output buffer", shape);
+  std::snprintf(out, cap, "%s %s", s->family_name, s->suffix);
+  FFP_API_END
+}
+
+static thread_local std::string tl_op_conv_variant;      // conv_variant of the op this thread's last ffp_op_conv2d / ffp_op_conv1x1_up2 launched; empty: none was
+int ffp_op_conv2d_last_variant(char* out, int cap) {
+  FFP_API_BEGIN
+  FFP_CHECK(out && cap > 0, FFP_ERR_ARG, "conv2d_last_variant: no output buffer");
+  std::snprintf(out, cap, "%s", tl_op_conv_variant.c_str());
+  FFP_API_END
 }
 
 static int g_op_conv_act_post = ACT_NONE;
@@ -955,6 +974,7 @@ int ffp_op_conv2d(int device, int precision, const float* x, int n, int h, int w
   FFP_CHECK(hipGetDeviceCount(&ndev) == hipSuccess && device >= 0 && device < ndev, FFP_ERR_HIP, "conv2d: no HIP device %d (no CPU path)", device);
   FFP_HIP(hipSetDevice(device));
   conv_kernels_init();
+  tl_op_conv_variant.clear();
   const DType T = precision == FFP_PREC_F16 ? F16 : F32;
   const bool split = precision == FFP_PREC_F32X3;
   hipStream_t st;
@@ -1010,6 +1030,7 @@ int ffp_op_conv2d(int device, int precision, const float* x, int n, int h, int w
       o.force_shape = g_op_conv_shape;
       o.act_post = g_op_conv_act_post;
       launch_conv(o, st);
+      tl_op_conv_variant = conv_variant(o);
     }
     FFP_HIP(hipStreamSynchronize(st));
     if (T == F32) {
@@ -1036,6 +1057,7 @@ int ffp_op_conv1x1_up2(int device, int precision, const float* coarse, const flo
   FFP_CHECK(hipGetDeviceCount(&ndev) == hipSuccess && device >= 0 && device < ndev, FFP_ERR_HIP, "conv1x1_up2: no HIP device %d (no CPU path)", device);
   FFP_HIP(hipSetDevice(device));
   conv_kernels_init();
+  tl_op_conv_variant.clear();
   hipStream_t st;
   FFP_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
   try {
@@ -1068,6 +1090,7 @@ int ffp_op_conv1x1_up2(int device, int precision, const float* coarse, const flo
     o.has_up2 = true; o.up2 = vco; o.up2_c = c_up; o.up2_map = lf.up2_map(&lc, st);
     o.force_shape = g_op_conv_shape;
     launch_conv(o, st);
+    tl_op_conv_variant = conv_variant(o);
     FFP_HIP(hipStreamSynchronize(st));
     FFP_HIP(hipMemcpy(y, dout.p, pf * cout * 4, hipMemcpyDeviceToHost));
   } catch (...) {
@@ -1755,9 +1778,9 @@ int ffp_op_conv2d_time(int device, int precision, int n, int h, int w, int cin, 
     o.pc = &pc; o.stride = stride; o.act = precision == FFP_PREC_F16 ? ACT_LRELU : ACT_SILU; o.up = up; o.dbg = dbg_mask; o.force_shape = force_shape;   // the activation each precision's network uses
     o.in = TView{din.p, T, pc.cin, 0, pc.cin, &lin};
     o.out = TView{dout.p, T, cout, 0, cout, &lout};
-    // force_shape 25: the fused-body kernel (conv_trunk.hip) on this ONE layer, its plan built once outside the timed launches
+    // SHAPE_TRUNK: the fused-body kernel (conv_trunk.hip) on this ONE layer, its plan built once outside the timed launches
     std::unique_ptr<TrunkPlan> tp;
-    if (force_shape == 25) tp.reset(new TrunkPlan(std::vector<ConvOp>{o}));
+    if (force_shape == SHAPE_TRUNK) tp.reset(new TrunkPlan(std::vector<ConvOp>{o}));
     auto once = [&]() { if (tp) tp->launch(st, dbg_mask); else launch_conv(o, st); };
     for (int i = 0; i < 3; ++i) once();
     hipEvent_t e0, e1;

@@ -2,6 +2,7 @@
 // dispatches to the others), conv_rows.hip, conv_pw.hip, conv_k3d.hip, rtdetr_ops.hip, and — through rows16_parts.hpp — conv_rows16.hip,
 // conv_rows16pc.hip and conv_trunk.hip.
 #pragma once
+#include "conv_route.hpp"
 #include "ops.hpp"
 
 namespace ffp {
@@ -26,7 +27,7 @@ struct ConvArgs {
   float s1, s2;
   int act_post;         // activation applied after the residual terms (SCRFD: Relu(Add(conv, x))); ACT_NONE for every other plan
   int act, out_f32, up, n_nblk, ncg, ntiles32, vec_ok, fast_out;
-  int force_shape;   // tuning only: -1 auto
+  int force_shape;   // ConvOp::force_shape; no kernel and no launcher reads it (the slot keeps the argument block's layout)
   int dbg;   // tuning only (ffp_op_conv2d_time): 1 skip stores, 2 skip MFMAs, 4 skip chunk refetch, 8 skip LDS stash
   const void* up_src;  // 1x1 only: channels [0, up_c) come from this coarser view through up_map (see ConvOp::has_up2)
   const int* up_map;
@@ -178,33 +179,34 @@ inline bool epilogue_fits(int act, bool res, int act_post, DType out, const EpiC
 }
 inline bool epilogue_fits(const ConvOp& op, const EpiCaps& caps) { return epilogue_fits(op.act, op.has_res1 || op.has_res2, op.act_post, op.out.dt, caps); }
 
-// host side (conv_mfma.hip)
+// host side. Which of these kernels runs an op is decided in conv_route.cpp alone: the predicates below say only whether the kernel CAN run the
+// op (at the given shape number) — its layout, geometry and epilogue — and never look at ConvOp::force_shape or the environment.
 ConvArgs make_conv_args(const ConvOp& op);
-// k3 s1 fp16 row-reuse kernel (conv_rows.hip)
-bool conv_rows_eligible(const ConvOp& op, const ConvArgs& a);
-void launch_conv_rows(ConvArgs& a, Level* out_lvl, hipStream_t st);
+// the generic kernel (conv_mfma.hip), shapes SHAPE_WIDE..SHAPE_NARROW1_H: the shapes that fit the op, the heuristic's pick among them
+unsigned conv_generic_mask(const ConvOp& op, const ConvArgs& a);
+int conv_generic_choose(const ConvOp& op, const ConvArgs& a);
+void launch_conv_generic(ConvArgs& a, int shape, const ConvOp& op, hipStream_t st);
+// k3 s1 fp16 row-reuse kernel (conv_rows.hip), shapes SHAPE_ROWS..SHAPE_ROWS_2TILE
+bool conv_rows_eligible(const ConvOp& op, const ConvArgs& a, int shape);
+void launch_conv_rows(ConvArgs& a, int shape, Level* out_lvl, hipStream_t st);
 void conv_rows_init();
-// k3 s1 fp16, second generation on v_mfma_f32_16x16x32_f16 (conv_rows16.hip)
-bool conv_rows16_eligible(const ConvOp& op, const ConvArgs& a);
-void launch_conv_rows16(ConvArgs& a, const PackedConv& pc, Level* out_lvl, hipStream_t st);
+// k3 s1 fp16, second generation on v_mfma_f32_16x16x32_f16 (conv_rows16.hip): SHAPE_ROWS16, and SHAPE_ROWS16_RES with the channel block's weights resident in LDS
+bool conv_rows16_eligible(const ConvOp& op, const ConvArgs& a, int shape);
+void launch_conv_rows16(ConvArgs& a, int shape, const PackedConv& pc, Level* out_lvl, hipStream_t st);
 void conv_rows16_init();
-bool conv_rows16_enabled();     // FFP_ROWS16=0 keeps the first-generation kernel (A/B aid)
 unsigned rows16_grid(int n_tiles, int n_nblk, int min_ws, int tcap, const char* what);      // launch extent 8 x Ws of the item dealing (conv_rows16.hip), checked
-// the same convs with producer / consumer waves (conv_rows16pc.hip): OPT-IN (force_shape 24 or FFP_ROWS16_PC=1; measured 0.73-0.94x); bit-identical results
-bool conv_rows16pc_selected(const ConvArgs& a);
+// the same convs (conv_rows16_eligible) with producer / consumer waves (conv_rows16pc.hip), SHAPE_ROWS16PC: opt-in (measured 0.73-0.94x); bit-identical results
 void launch_conv_rows16pc(ConvArgs& a, const PackedConv& pc, Level* out_lvl, hipStream_t st);
 void conv_rows16pc_init();
-// 1x1 fp32-split convs without LDS staging of the activations (conv_pw.hip): bit s of the mask = force_shape s (10..16) can run this op
+// 1x1 fp32-split convs without LDS staging of the activations (conv_pw.hip): shape_bit(s) of the mask = shape s (SHAPE_PW_*) can run this op
 unsigned conv_pw_mask(const ConvOp& op, const ConvArgs& a);
 void launch_conv_pw(ConvArgs& a, int shape, hipStream_t st);
 void conv_pw_init();
-bool conv_pw_enabled();         // FFP_PW=0 keeps the tuner to the generic shapes (A/B aid)
 
-// 3x3 fp32-split convs, stride 1 and 2, weights straight from L2 into MFMA operand registers (conv_k3d.hip): bit s of the mask =
-// force_shape s (17..21) can run this op; results are bit-identical to the generic kernel's
+// 3x3 fp32-split convs, stride 1 and 2, weights straight from L2 into MFMA operand registers (conv_k3d.hip): shape_bit(s) of the mask =
+// shape s (SHAPE_K3D_*) can run this op; results are bit-identical to the generic kernel's
 unsigned conv_k3d_mask(const ConvOp& op, const ConvArgs& a);
 void launch_conv_k3d(ConvArgs& a, int shape, int stride, Level* out_lvl, hipStream_t st);
 void conv_k3d_init();
-bool conv_k3d_enabled();        // FFP_K3D=0 keeps the tuner to the generic shapes (A/B aid)
 
 }  // namespace ffp

@@ -451,7 +451,7 @@ template <int S, int WM, int WN, int MI, int NIW> struct K3Cfg {
   }
 };
 
-// force_shape 17..21, per stride: {128 px x 128 ch, 128 px x 64 ch, 128 px x 32 ch, 256 px x 128 ch (one workgroup per CU, 512 registers), 256 px x 64 ch}
+// SHAPE_K3D_128 .. SHAPE_K3D_64X256, per stride: {128 px x 128 ch, 128 px x 64 ch, 128 px x 32 ch, 256 px x 128 ch (one workgroup per CU, 512 registers), 256 px x 64 ch}
 template <int S> struct K3Family {
   using V0 = K3Cfg<S, 2, 2, 2, 2>;
   using V1 = K3Cfg<S, 2, 2, 2, 1>;
@@ -461,11 +461,12 @@ template <int S> struct K3Family {
   static void init() { V0::init(); V1::init(); V2::init(); V3::init(); V4::init(); }
   static void launch(ConvArgs& a, int shape, Level* out_lvl, hipStream_t st) {
     switch (shape) {
-      case 17: V0::launch(a, out_lvl, st); break;
-      case 18: V1::launch(a, out_lvl, st); break;
-      case 19: V2::launch(a, out_lvl, st); break;
-      case 20: V3::launch(a, out_lvl, st); break;
-      default: V4::launch(a, out_lvl, st); break;
+      case SHAPE_K3D_128: V0::launch(a, out_lvl, st); break;
+      case SHAPE_K3D_64: V1::launch(a, out_lvl, st); break;
+      case SHAPE_K3D_32: V2::launch(a, out_lvl, st); break;
+      case SHAPE_K3D_128X256: V3::launch(a, out_lvl, st); break;
+      case SHAPE_K3D_64X256: V4::launch(a, out_lvl, st); break;
+      default: fail(FFP_ERR_ARG, "conv_k3d: shape %d", shape);
     }
   }
 };
@@ -473,11 +474,6 @@ template <int S> struct K3Family {
 }  // namespace
 
 void conv_k3d_init() { K3Family<1>::init(); K3Family<2>::init(); }
-
-bool conv_k3d_enabled() {
-  static const bool on = [] { const char* e = getenv("FFP_K3D"); return !(e && e[0] == '0'); }();
-  return on;
-}
 
 // what the kernel does not do: fp16 / exact-fp32 arithmetic, fp16 outputs (kEpiK3d), upsampled inputs, unaligned outputs, input channel counts that are not
 // whole 16-channel groups, images whose byte size does not fit the 32-bit offsets of one buffer resource
@@ -493,9 +489,9 @@ unsigned conv_k3d_mask(const ConvOp& op, const ConvArgs& a) {
   for (int i = 0; i < op.out.lvl->n; ++i) max_opx = std::max(max_opx, (long long)op.out.lvl->h[i] * op.out.lvl->w[i]);
   const long long cs_max = std::max<long long>(op.out.cs, std::max(op.has_res1 ? op.res1.cs : 0, op.has_res2 ? op.res2.cs : 0));
   if (max_px * op.in.cs * 4 >= 0x7FFFFFF0ll || max_opx * cs_max * 4 >= 0x7FFFFFF0ll) return 0;
-  unsigned m = 1u << 19;
-  if (a.ntiles32 >= 2) m |= (1u << 18) | (1u << 21);
-  if (a.ntiles32 >= 3) m |= (1u << 17) | (1u << 20);
+  unsigned m = shape_bit(SHAPE_K3D_32);
+  if (a.ntiles32 >= 2) m |= shape_bit(SHAPE_K3D_64) | shape_bit(SHAPE_K3D_64X256);
+  if (a.ntiles32 >= 3) m |= shape_bit(SHAPE_K3D_128) | shape_bit(SHAPE_K3D_128X256);
   return m;
 }
 

@@ -873,67 +873,59 @@ template <typename T, int KS, int STRIDE> struct Family {
   static unsigned valid_mask(const ConvArgs& a) {
     const bool wide_ok = a.ntiles32 >= 3 && (KS == 1 || STRIDE == 2);
     unsigned m = 0;
-    if (Wide::OK && wide_ok) m |= 1u << 0;
-    if (WideH::OK && wide_ok) m |= 1u << 1;
-    if (Narrow2::OK && a.ntiles32 >= 2) m |= 1u << 2;
-    if (HAS_NH && Narrow2H::OK && a.ntiles32 >= 2) m |= 1u << 3;
-    if (Narrow1::OK) m |= 1u << 4;
-    if (HAS_NH && Narrow1H::OK) m |= 1u << 5;
+    if (Wide::OK && wide_ok) m |= shape_bit(SHAPE_WIDE);
+    if (WideH::OK && wide_ok) m |= shape_bit(SHAPE_WIDE_H);
+    if (Narrow2::OK && a.ntiles32 >= 2) m |= shape_bit(SHAPE_NARROW2);
+    if (HAS_NH && Narrow2H::OK && a.ntiles32 >= 2) m |= shape_bit(SHAPE_NARROW2_H);
+    if (Narrow1::OK) m |= shape_bit(SHAPE_NARROW1);
+    if (HAS_NH && Narrow1H::OK) m |= shape_bit(SHAPE_NARROW1_H);
     return m;
   }
   static int choose(const ConvArgs& a, Level* out_lvl) {
     // candidates in decreasing block size; first pass: shapes that allow two resident workgroups per CU (LDS <= 80 KiB) and fill the chip; second pass: any shape with enough work; else the shape with the most workgroups.
     constexpr long long ENOUGH = 192;     // >= 3/4 of the 256 CUs get a workgroup: measured better than insisting on two for the SR body convs
-    struct Cand { int id; long long n; bool valid; bool occ2; };
-    const bool wide_ok = a.ntiles32 >= 3 && (KS == 1 || STRIDE == 2);
+    struct Cand { int id; long long n; bool occ2; };
     const Cand c[6] = {
-        {0, wgs<Wide>(a, out_lvl), Wide::OK && wide_ok, Wide::LDS <= 80 * 1024},
-        {1, wgs<WideH>(a, out_lvl), WideH::OK && wide_ok, WideH::LDS <= 80 * 1024},
-        {2, wgs<Narrow2>(a, out_lvl), Narrow2::OK && a.ntiles32 >= 2, Narrow2::LDS <= 80 * 1024},
-        {3, wgs<Narrow2H>(a, out_lvl), HAS_NH && Narrow2H::OK && a.ntiles32 >= 2, Narrow2H::LDS <= 80 * 1024},
-        {4, wgs<Narrow1>(a, out_lvl), Narrow1::OK, Narrow1::LDS <= 80 * 1024},
-        {5, wgs<Narrow1H>(a, out_lvl), HAS_NH && Narrow1H::OK, Narrow1H::LDS <= 80 * 1024}};
-    for (const Cand& k : c) if (k.valid && k.occ2 && k.n >= ENOUGH) return k.id;
-    for (const Cand& k : c) if (k.valid && k.n >= ENOUGH) return k.id;
+        {SHAPE_WIDE, wgs<Wide>(a, out_lvl), Wide::LDS <= 80 * 1024},
+        {SHAPE_WIDE_H, wgs<WideH>(a, out_lvl), WideH::LDS <= 80 * 1024},
+        {SHAPE_NARROW2, wgs<Narrow2>(a, out_lvl), Narrow2::LDS <= 80 * 1024},
+        {SHAPE_NARROW2_H, wgs<Narrow2H>(a, out_lvl), Narrow2H::LDS <= 80 * 1024},
+        {SHAPE_NARROW1, wgs<Narrow1>(a, out_lvl), Narrow1::LDS <= 80 * 1024},
+        {SHAPE_NARROW1_H, wgs<Narrow1H>(a, out_lvl), Narrow1H::LDS <= 80 * 1024}};
+    const unsigned valid = valid_mask(a);
+    for (const Cand& k : c) if ((valid & shape_bit(k.id)) && k.occ2 && k.n >= ENOUGH) return k.id;
+    for (const Cand& k : c) if ((valid & shape_bit(k.id)) && k.n >= ENOUGH) return k.id;
     int best = -1;
     long long best_n = -1;
-    for (const Cand& k : c) if (k.valid && k.n > best_n) { best = k.id; best_n = k.n; }
+    for (const Cand& k : c) if ((valid & shape_bit(k.id)) && k.n > best_n) { best = k.id; best_n = k.n; }
     if (best < 0) fail(FFP_ERR_STATE, "conv: no workgroup shape fits");
     return best;
   }
-  static void launch(ConvArgs& a, Level* out_lvl, hipStream_t st) {
-    switch (a.force_shape >= 0 ? a.force_shape : choose(a, out_lvl)) {
-      case 0: Wide::launch(a, out_lvl, st); break;
-      case 1: WideH::launch(a, out_lvl, st); break;
-      case 2: Narrow2::launch(a, out_lvl, st); break;
-      case 3: Narrow2H::launch(a, out_lvl, st); break;
-      case 4: Narrow1::launch(a, out_lvl, st); break;
-      default: Narrow1H::launch(a, out_lvl, st); break;
+  static void launch(ConvArgs& a, int shape, Level* out_lvl, hipStream_t st) {
+    switch (shape) {
+      case SHAPE_WIDE: Wide::launch(a, out_lvl, st); break;
+      case SHAPE_WIDE_H: WideH::launch(a, out_lvl, st); break;
+      case SHAPE_NARROW2: Narrow2::launch(a, out_lvl, st); break;
+      case SHAPE_NARROW2_H: Narrow2H::launch(a, out_lvl, st); break;
+      case SHAPE_NARROW1: Narrow1::launch(a, out_lvl, st); break;
+      case SHAPE_NARROW1_H: Narrow1H::launch(a, out_lvl, st); break;
+      default: fail(FFP_ERR_ARG, "conv: generic shape %d", shape);
     }
   }
 };
 
-static const char* kShapeNames[6] = {"wide", "wideH", "narrow2", "narrow2H", "narrow1", "narrow1H"};
-
-template <typename T> int choose_t(const ConvArgs& a, int k, int stride, Level* out_lvl) {
-  if (k == 1 && stride == 1) return Family<T, 1, 1>::choose(a, out_lvl);
-  if (k == 3 && stride == 1) return Family<T, 3, 1>::choose(a, out_lvl);
-  if (k == 3 && stride == 2) return Family<T, 3, 2>::choose(a, out_lvl);
-  return 4;
-}
-
-template <typename T> unsigned valid_t(const ConvArgs& a, int k, int stride) {
-  if (k == 1 && stride == 1) return Family<T, 1, 1>::valid_mask(a);
-  if (k == 3 && stride == 1) return Family<T, 3, 1>::valid_mask(a);
-  if (k == 3 && stride == 2) return Family<T, 3, 2>::valid_mask(a);
-  return 0;
-}
-
-template <typename T> void launch_t(ConvArgs& a, int k, int stride, Level* out_lvl, hipStream_t st) {
-  if (k == 1 && stride == 1) Family<T, 1, 1>::launch(a, out_lvl, st);
-  else if (k == 3 && stride == 1) Family<T, 3, 1>::launch(a, out_lvl, st);
-  else if (k == 3 && stride == 2) Family<T, 3, 2>::launch(a, out_lvl, st);
-  else fail(FFP_ERR_ARG, "conv: k=%d stride=%d has no kernel", k, stride);
+// (precision, k, stride) of the op -> fn(Family<T, k, stride>{})
+template <typename T> struct TypeTag { using type = T; };
+template <class Fn> auto with_family(const ConvOp& op, Fn&& fn) {
+  const PackedConv& pc = *op.pc;
+  auto by_ks = [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    if (pc.k == 1 && op.stride == 1) return fn(Family<T, 1, 1>{});
+    if (pc.k == 3 && op.stride == 1) return fn(Family<T, 3, 1>{});
+    if (pc.k == 3 && op.stride == 2) return fn(Family<T, 3, 2>{});
+    fail(FFP_ERR_ARG, "conv %s: k=%d stride=%d has no kernel", pc.name.c_str(), pc.k, op.stride);
+  };
+  return pc.dt == F16 ? by_ks(TypeTag<_Float16>{}) : pc.split ? by_ks(TypeTag<X3>{}) : by_ks(TypeTag<float>{});
 }
 
 }  // namespace
@@ -1107,132 +1099,14 @@ ConvArgs make_conv_args(const ConvOp& op) {
   return a;
 }
 
-bool conv_rows16_enabled() {
-  static const bool on = [] { const char* e = getenv("FFP_ROWS16"); return !(e && e[0] == '0'); }();
-  return on;
+unsigned conv_generic_mask(const ConvOp& op, const ConvArgs& a) {
+  return with_family(op, [&](auto f) { return decltype(f)::valid_mask(a); });
 }
-
-bool conv_pw_enabled() {
-  static const bool on = [] { const char* e = getenv("FFP_PW"); return !(e && e[0] == '0'); }();
-  return on;
+int conv_generic_choose(const ConvOp& op, const ConvArgs& a) {
+  return with_family(op, [&](auto f) { return decltype(f)::choose(a, op.out.lvl); });
 }
-
-static bool use_rows16(const ConvOp& op, const ConvArgs& a) {
-  if (!conv_rows16_eligible(op, a)) return false;
-  return a.force_shape == 9 || a.force_shape == 23 || a.force_shape == 24 || (a.force_shape < 0 && conv_rows16_enabled());
-}
-
-void launch_conv(const ConvOp& op, hipStream_t st) {
-  const PackedConv& pc = *op.pc;
-  if (conv_direct_eligible(op)) { launch_conv_direct(op, st); return; }
-  ConvArgs a = make_conv_args(op);
-  if (a.force_shape == 25) {                     // the fused-body kernel on ONE layer (tests, probes): a throw-away single-layer plan
-    FFP_CHECK(conv_trunk_layer_ok(op), FFP_ERR_ARG, "conv %s: not a layer conv_trunk_kernel can run", pc.name.c_str());
-    TrunkPlan tp(std::vector<ConvOp>{op});
-    tp.launch(st, op.dbg);
-    FFP_HIP(hipStreamSynchronize(st));           // the plan's tables die with it
-    return;
-  }
-  const bool f16r = a.force_shape == 9 || a.force_shape == 23 || a.force_shape == 24, frow = a.force_shape >= 6 && a.force_shape <= 8;      // a forced rows shape, like a pw / k3d one, runs the op or is an error
-  FFP_CHECK((!f16r || conv_rows16_eligible(op, a)) && (!frow || conv_rows_eligible(op, a)), FFP_ERR_ARG, "conv %s: rows shape %d cannot run this op", pc.name.c_str(), a.force_shape);
-  if (use_rows16(op, a)) {
-    if (conv_rows16pc_selected(a)) launch_conv_rows16pc(a, pc, op.out.lvl, st);
-    else launch_conv_rows16(a, pc, op.out.lvl, st);
-    FFP_HIP(hipGetLastError());
-    return;
-  }
-  if (conv_rows_eligible(op, a)) { launch_conv_rows(a, op.out.lvl, st); FFP_HIP(hipGetLastError()); return; }
-  if ((a.force_shape >= 10 && a.force_shape <= 16) || a.force_shape == 22) {      // pointwise kernels (conv_pw.hip): only ever picked by measurement (conv_tune) or by hand
-    FFP_CHECK(conv_pw_mask(op, a) & (1u << a.force_shape), FFP_ERR_ARG, "conv %s: pointwise shape %d cannot run this op", pc.name.c_str(), a.force_shape);
-    launch_conv_pw(a, a.force_shape, st);
-    FFP_HIP(hipGetLastError());
-    return;
-  }
-  if (a.force_shape >= 17 && a.force_shape <= 21) {      // direct-weight 3x3 kernels (conv_k3d.hip): picked by measurement (conv_tune) or by hand
-    FFP_CHECK(conv_k3d_mask(op, a) & (1u << a.force_shape), FFP_ERR_ARG, "conv %s: k3d shape %d cannot run this op", pc.name.c_str(), a.force_shape);
-    launch_conv_k3d(a, a.force_shape, op.stride, op.out.lvl, st);
-    FFP_HIP(hipGetLastError());
-    return;
-  }
-  if (pc.dt == F16) launch_t<_Float16>(a, pc.k, op.stride, op.out.lvl, st);
-  else if (pc.split) launch_t<X3>(a, pc.k, op.stride, op.out.lvl, st);
-  else launch_t<float>(a, pc.k, op.stride, op.out.lvl, st);
-  FFP_HIP(hipGetLastError());
-}
-
-std::string conv_variant(const ConvOp& op);
-
-int conv_tune(const ConvOp& op, hipStream_t st) {
-  const PackedConv& pc = *op.pc;
-  if (conv_direct_eligible(op)) return -1;
-  const ConvArgs a = make_conv_args(op);
-  if (use_rows16(op, a) || conv_rows_eligible(op, a)) return -1;
-  const unsigned mask = (pc.dt == F16 ? valid_t<_Float16>(a, pc.k, op.stride) : pc.split ? valid_t<X3>(a, pc.k, op.stride) : valid_t<float>(a, pc.k, op.stride)) |
-                        (conv_pw_enabled() ? conv_pw_mask(op, a) : 0u) | (conv_k3d_enabled() ? conv_k3d_mask(op, a) : 0u);
-  if (__builtin_popcount(mask) < 2) return -1;
-  const int heur = pc.dt == F16 ? choose_t<_Float16>(a, pc.k, op.stride, op.out.lvl)
-                   : pc.split ? choose_t<X3>(a, pc.k, op.stride, op.out.lvl) : choose_t<float>(a, pc.k, op.stride, op.out.lvl);
-  hipEvent_t e0, e1;
-  FFP_HIP(hipEventCreate(&e0));
-  FFP_HIP(hipEventCreate(&e1));
-  auto time_shape = [&](int shape, int iters) {
-    ConvOp o = op;
-    o.force_shape = shape;
-    FFP_HIP(hipEventRecord(e0, st));
-    for (int i = 0; i < iters; ++i) launch_conv(o, st);
-    FFP_HIP(hipEventRecord(e1, st));
-    FFP_HIP(hipEventSynchronize(e1));
-    float ms = 0.f;
-    FFP_HIP(hipEventElapsedTime(&ms, e0, e1));
-    return ms * 1e3f / iters;
-  };
-  float best_t = 0.f, heur_t = 0.f;
-  int best = -1;
-  for (int shape = 0; shape < 23; ++shape) {
-    if (!(mask & (1u << shape))) continue;
-    const float t1 = time_shape(shape, 2);                              // also builds the shape's tile table
-    const int iters = std::min(24, std::max(3, (int)(300.f / std::max(t1, 1.f))));
-    const float t = time_shape(shape, iters);
-    if (shape == heur) heur_t = t;
-    if (best < 0 || t < best_t) { best = shape; best_t = t; }
-    static const bool log = [] { const char* e = getenv("FFP_TUNE_LOG"); return e && e[0] == '1'; }();       // every candidate's time, one line per (layer, shape)
-    if (log) {
-      ConvOp o = op;
-      o.force_shape = shape;
-      fprintf(stderr, "[tune] %-28s %4d->%4d k%d s%d px %9lld  shape %2d %-22s %9.1f us%s\n", pc.name.c_str(), pc.cin_real, pc.cout, pc.k, op.stride,
-              (long long)op.out.lvl->actual_px(), shape, conv_variant(o).c_str(), t, shape == heur ? "  (heuristic)" : "");
-    }
-  }
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  // keep the heuristic's choice unless another shape is clearly (> 3 %) faster: timing noise must not flip plans
-  if (heur_t > 0.f && best_t > 0.97f * heur_t) return heur;
-  return best;
-}
-
-std::string conv_variant(const ConvOp& op) {
-  const PackedConv& pc = *op.pc;
-  if (conv_direct_eligible(op)) return std::string(pc.dt == F32 ? "f32" : "f16") + "_k3_direct";
-  const ConvArgs a = make_conv_args(op);
-  if (use_rows16(op, a)) return conv_rows16pc_selected(a) ? "f16_k3s1_rows16pc" : "f16_k3s1_rows16";
-  if (conv_rows_eligible(op, a)) return "f16_k3s1_rows";
-  if (op.force_shape == 22) return "f32x3_k1s1_pw2x2s";
-  if (op.force_shape >= 10 && op.force_shape <= 16) {
-    static const char* pw[7] = {"f32x3_k1s1_pw1x4", "f32x3_k1s1_pw2x2", "f32x3_k1s1_pw2x1", "f32x3_k1s1_pw1x4w", "f32x3_k1s1_pw2x2w", "f32x3_k1s1_pw2x1w", "f32x3_k1s1_pw1x4s"};
-    return pw[op.force_shape - 10];
-  }
-  if (op.force_shape >= 17 && op.force_shape <= 21) {
-    static const char* k3[5] = {"d128", "d64", "d32", "d128x256", "d64x256"};
-    char b[64];
-    snprintf(b, sizeof(b), "f32x3_k3s%d_%s", op.stride, k3[op.force_shape - 17]);
-    return b;
-  }
-  const int shape = (op.force_shape >= 0 && op.force_shape < 6) ? op.force_shape
-                    : pc.dt == F16 ? choose_t<_Float16>(a, pc.k, op.stride, op.out.lvl)
-                    : pc.split ? choose_t<X3>(a, pc.k, op.stride, op.out.lvl) : choose_t<float>(a, pc.k, op.stride, op.out.lvl);
-  char buf[64];
-  snprintf(buf, sizeof(buf), "%s_k%ds%d_%s", pc.dt == F16 ? "f16" : pc.split ? "f32x3" : "f32", pc.k, op.stride, kShapeNames[shape < 0 ? 4 : shape]);
-  return buf;
+void launch_conv_generic(ConvArgs& a, int shape, const ConvOp& op, hipStream_t st) {
+  with_family(op, [&](auto f) { decltype(f)::launch(a, shape, op.out.lvl, st); });
 }
 
 }  // namespace ffp

@@ -426,8 +426,8 @@ template <int NW, int MI, int NT, int RPMAX> struct PwShape {
   }
 };
 
-// streamed weights: 7 consumer waves + the weight producer. 16: 32 px x 128 channels per wave, any K that is a multiple of 128;
-// 22: 64 px x 64 channels per wave (half the LDS fragment reads per MFMA: the deep 16^2 / 32^2 layers), any K that is a multiple of 64
+// streamed weights: 7 consumer waves + the weight producer. SHAPE_PW_1X4S: 32 px x 128 channels per wave, any K that is a multiple of 128;
+// SHAPE_PW_2X2S: 64 px x 64 channels per wave (half the LDS fragment reads per MFMA: the deep 16^2 / 32^2 layers), any K that is a multiple of 64
 template <int MI_, int NT_, int RP_> struct PwSt {
   static constexpr int NWC = 7, MI = MI_, RP = RP_, NT = NT_, LDS = 2 * NT * 2 * RP * 2048;
   static bool fits(const ConvArgs& a) { return a.ntiles32 % NT == 0 && (a.ncg / 2) % RP == 0; }
@@ -448,10 +448,10 @@ template <int MI_, int NT_, int RP_> struct PwSt {
 using Pw14s = PwSt<1, 4, 4>;
 using Pw22s = PwSt<2, 2, 2>;
 
-using Pw14 = PwShape<4, 1, 4, 4>;      // force_shape 10: 128 px x 128 ch per workgroup, K <= 160
-using Pw22 = PwShape<4, 2, 2, 2>;      // 11: 256 px x 64 ch, K <= 320
-using Pw21 = PwShape<4, 2, 1, 4>;      // 12: 256 px x 32 ch, K <= 640
-using Pw14w = PwShape<8, 1, 4, 4>;     // 13..15: the same per-wave tiles in 8-wave workgroups, twice the K
+using Pw14 = PwShape<4, 1, 4, 4>;      // SHAPE_PW_1X4: 128 px x 128 ch per workgroup, K <= 160
+using Pw22 = PwShape<4, 2, 2, 2>;      // SHAPE_PW_2X2: 256 px x 64 ch, K <= 320
+using Pw21 = PwShape<4, 2, 1, 4>;      // SHAPE_PW_2X1: 256 px x 32 ch, K <= 640
+using Pw14w = PwShape<8, 1, 4, 4>;     // SHAPE_PW_*W: the same per-wave tiles in 8-wave workgroups, twice the K
 using Pw22w = PwShape<8, 2, 2, 2>;
 using Pw21w = PwShape<8, 2, 1, 4>;
 
@@ -471,27 +471,28 @@ static bool pw_common(const ConvOp& op, const ConvArgs& a) {
 unsigned conv_pw_mask(const ConvOp& op, const ConvArgs& a) {
   if (!pw_common(op, a)) return 0;
   unsigned m = 0;
-  if (Pw14::fits(a)) m |= 1u << 10;
-  if (Pw22::fits(a)) m |= 1u << 11;
-  if (Pw21::fits(a)) m |= 1u << 12;
-  if (Pw14w::fits(a)) m |= 1u << 13;
-  if (Pw22w::fits(a)) m |= 1u << 14;
-  if (Pw21w::fits(a)) m |= 1u << 15;
-  if (Pw14s::fits(a)) m |= 1u << 16;
-  if (Pw22s::fits(a)) m |= 1u << 22;
+  if (Pw14::fits(a)) m |= shape_bit(SHAPE_PW_1X4);
+  if (Pw22::fits(a)) m |= shape_bit(SHAPE_PW_2X2);
+  if (Pw21::fits(a)) m |= shape_bit(SHAPE_PW_2X1);
+  if (Pw14w::fits(a)) m |= shape_bit(SHAPE_PW_1X4W);
+  if (Pw22w::fits(a)) m |= shape_bit(SHAPE_PW_2X2W);
+  if (Pw21w::fits(a)) m |= shape_bit(SHAPE_PW_2X1W);
+  if (Pw14s::fits(a)) m |= shape_bit(SHAPE_PW_1X4S);
+  if (Pw22s::fits(a)) m |= shape_bit(SHAPE_PW_2X2S);
   return m;
 }
 
 void launch_conv_pw(ConvArgs& a, int shape, hipStream_t st) {
   switch (shape) {
-    case 10: Pw14::launch(a, st); break;
-    case 11: Pw22::launch(a, st); break;
-    case 12: Pw21::launch(a, st); break;
-    case 13: Pw14w::launch(a, st); break;
-    case 14: Pw22w::launch(a, st); break;
-    case 15: Pw21w::launch(a, st); break;
-    case 22: Pw22s::launch(a, st); break;
-    default: Pw14s::launch(a, st); break;
+    case SHAPE_PW_1X4: Pw14::launch(a, st); break;
+    case SHAPE_PW_2X2: Pw22::launch(a, st); break;
+    case SHAPE_PW_2X1: Pw21::launch(a, st); break;
+    case SHAPE_PW_1X4W: Pw14w::launch(a, st); break;
+    case SHAPE_PW_2X2W: Pw22w::launch(a, st); break;
+    case SHAPE_PW_2X1W: Pw21w::launch(a, st); break;
+    case SHAPE_PW_2X2S: Pw22s::launch(a, st); break;
+    case SHAPE_PW_1X4S: Pw14s::launch(a, st); break;
+    default: fail(FFP_ERR_ARG, "conv_pw: shape %d", shape);
   }
 }
 

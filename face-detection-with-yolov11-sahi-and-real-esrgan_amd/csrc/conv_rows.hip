@@ -321,20 +321,23 @@ void conv_rows_init() {
 }
 
 static constexpr EpiCaps kEpiRows{EPI_ALL_ACTS, true, false, true, false};     // apply_act, res1, res2; no act_post; fp16 outputs
-bool conv_rows_eligible(const ConvOp& op, const ConvArgs& a) {
+bool conv_rows_eligible(const ConvOp& op, const ConvArgs& a, int shape) {
   const PackedConv& pc = *op.pc;
-  if (a.force_shape >= 0 && a.force_shape < 6) return false;        // tuning: a generic shape was asked for
+  if (shape == SHAPE_ROWS_2TILE && a.ntiles32 % 2) return false;     // two channel tiles per workgroup
   return epilogue_fits(op, kEpiRows) && pc.dt == F16 && pc.k == 3 && op.stride == 1 && pc.cin % 32 == 0 && pc.cin >= 64 && pc.cin == pc.cin_pad &&
          pc.cout % 32 == 0 && pc.cout <= 128 && a.fast_out && a.zeros != nullptr;
 }
 
-void launch_conv_rows(ConvArgs& a, Level* out_lvl, hipStream_t st) {
+void launch_conv_rows(ConvArgs& a, int shape, Level* out_lvl, hipStream_t st) {
   // 32 channels per workgroup, two stages = 80 KiB: two workgroups per CU. (A 64-channel workgroup halves the LDS
   // reads per MFMA again but needs 128 accumulator registers + 116 KiB, i.e. one workgroup per CU: measured 1.5x slower
-  // on the 192->64 dense-block conv, as is a third stage at 32 channels. force_shape 7 / 8 keep them reachable for tuning.)
-  if (a.force_shape == 7) RowsCfg<1, 3>::launch(a, out_lvl, st);
-  else if (a.force_shape == 8 && a.ntiles32 % 2 == 0) RowsCfg<2, 2>::launch(a, out_lvl, st);
-  else RowsCfg<1, 2>::launch(a, out_lvl, st);
+  // on the 192->64 dense-block conv, as is a third stage at 32 channels. SHAPE_ROWS_3STAGE / SHAPE_ROWS_2TILE keep them reachable for tuning.)
+  switch (shape) {
+    case SHAPE_ROWS: RowsCfg<1, 2>::launch(a, out_lvl, st); break;
+    case SHAPE_ROWS_3STAGE: RowsCfg<1, 3>::launch(a, out_lvl, st); break;
+    case SHAPE_ROWS_2TILE: RowsCfg<2, 2>::launch(a, out_lvl, st); break;
+    default: fail(FFP_ERR_ARG, "conv_rows: shape %d", shape);
+  }
 }
 
 }  // namespace ffp

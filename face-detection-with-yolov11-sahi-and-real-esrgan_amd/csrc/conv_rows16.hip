@@ -375,15 +375,9 @@ template <int I = 0> void r16_for_mask(int mask, bool res, bool init, const Conv
 
 void conv_rows16_init() { r16_for_mask<>(0, false, true, nullptr, 0, 0, nullptr); }
 
-// the weight-resident form: force_shape 23, or every eligible layer with FFP_ROWS16_RES=1 (A/B aid)
-static bool rows16_resident(const ConvArgs& a) {
-  static const bool env_on = [] { const char* e = getenv("FFP_ROWS16_RES"); return e && e[0] == '1'; }();
-  return (a.force_shape == 23 || (a.force_shape < 0 && env_on)) && (a.cin >> 5) <= R16Lds::RES_MAXC;
-}
-
-bool conv_rows16_eligible(const ConvOp& op, const ConvArgs& a) {
+bool conv_rows16_eligible(const ConvOp& op, const ConvArgs& a, int shape) {
   const PackedConv& pc = *op.pc;
-  if (a.force_shape >= 0 && a.force_shape != 9 && a.force_shape != 23 && a.force_shape != 24) return false;   // tuning: another kernel was asked for
+  if (shape == SHAPE_ROWS16_RES && (a.cin >> 5) > R16Lds::RES_MAXC) return false;      // the weight-resident form: a channel block's weights fit the LDS
   return epilogue_fits(op, kEpiR16) && pc.w16.p != nullptr && pc.dt == F16 && pc.k == 3 && op.stride == 1 && pc.cin % 32 == 0 && pc.cin >= 64 && pc.cout % 32 == 0 &&
          pc.cout <= 128 && a.fast_out && op.out.cs % 8 == 0 && op.out.coff % 8 == 0;
 }
@@ -400,7 +394,7 @@ unsigned rows16_grid(int n_tiles, int n_nblk, int min_ws, int tcap, const char* 
   return (unsigned)(8 * ws);
 }
 
-void launch_conv_rows16(ConvArgs& a, const PackedConv& pc, Level* out_lvl, hipStream_t st) {
+void launch_conv_rows16(ConvArgs& a, int shape, const PackedConv& pc, Level* out_lvl, hipStream_t st) {
   using G = R16Lds;
   static_assert(G::LDS <= 80 * 1024, "rows16 kernel: two workgroups per CU");
   a.wpk = pc.w16.p;
@@ -409,7 +403,7 @@ void launch_conv_rows16(ConvArgs& a, const PackedConv& pc, Level* out_lvl, hipSt
   if (n_tiles == 0) return;
   a.ntiles_host = n_tiles;
   a.n_nblk = a.ntiles32;
-  const bool res = rows16_resident(a);
+  const bool res = shape == SHAPE_ROWS16_RES;
   static const int ws_env = [] { const char* e = getenv("FFP_ROWS16_WS"); return e ? atoi(e) : 0; }();      // experiment: workgroups per XCD (64 = two per CU)
   const unsigned grid = rows16_grid(n_tiles, a.n_nblk, ws_env > 0 ? ws_env : (res ? 32 : 64), G::TCAP, "rows16");      // resident weights: one workgroup per CU
   r16_for_mask<>(a.dbg, res, false, &a, grid, res ? G::res_lds(a.cin >> 5) : G::LDS, st);

@@ -23,7 +23,7 @@
 // hypothesis above is wrong, or incomplete: with the LDS bytes per MFMA unchanged (0.5 KiB of fragment reads + 0.135 KiB of staging
 // writes) a CU with ONE tile in flight is slower than a CU with two whatever the wave roles are. What remains untested is the other
 // half of the idea: consumers with 8 rows each (0.33 KiB of reads per MFMA) fed by LDS-DMA producers (no ds_write_b128 on the shared
-// VGPR -> LDS path). Kept behind force_shape 24 / FFP_ROWS16_PC=1 as the starting point for that.
+// VGPR -> LDS path). Kept behind SHAPE_ROWS16PC / FFP_ROWS16_PC=1 as the starting point for that.
 #include <algorithm>
 #include <cstdlib>
 
@@ -222,12 +222,8 @@ void conv_rows16pc_init() {
   FFP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_rows16pc_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, PCGeo::LDS));
 }
 
-// force_shape 24, or every eligible layer with FFP_ROWS16_PC=1 (A/B aid). NOT the default: measured 0.73-0.94x of conv_rows16_kernel
+// SHAPE_ROWS16PC, or every eligible layer with FFP_ROWS16_PC=1 (A/B aid; conv_route.cpp). NOT the default: measured 0.73-0.94x of conv_rows16_kernel
 // (profiles/r03_rows16_role_split_probe.txt) — with the same LDS traffic per MFMA the role split only halves the tiles in flight per CU.
-bool conv_rows16pc_selected(const ConvArgs& a) {
-  static const bool env_on = [] { const char* e = getenv("FFP_ROWS16_PC"); return e && e[0] == '1'; }();
-  return a.force_shape == 24 || (a.force_shape < 0 && env_on && a.dbg == 0);
-}
 
 void launch_conv_rows16pc(ConvArgs& a, const PackedConv& pc, Level* out_lvl, hipStream_t st) {
   using G = PCGeo;

@@ -1,5 +1,6 @@
 // engine.cpp — plan bookkeeping and conv-kernel profiling.
 #include "engine.hpp"
+#include "conv_route.hpp"
 
 #include <mutex>
 
@@ -210,12 +211,12 @@ void Plan::add_trunk(const std::vector<ConvOp>& ops) {
   for (const ConvOp& op : ops) {
     ConvOp o = op;
     o.flops = conv_flops_of(*op.pc, op.out.lvl->actual_px());
-    o.force_shape = 25;                                   // nothing to tune: the fused launch has one shape
+    o.force_shape = SHAPE_TRUNK;                                   // nothing to tune: the fused launch has one shape
     s.fused.push_back(std::make_shared<ConvOp>(o));
     s.flops += o.flops;
   }
   s.conv = s.fused.front();
-  s.variant = "f16_k3s1_trunk";
+  s.variant = conv_variant(*s.conv);                    // SHAPE_TRUNK routes to the trunk row of the shape table
   s.name = ops.front().pc->name + ".." + ops.back().pc->name;
   s.lane = cur_lane;
   std::shared_ptr<TrunkPlan> tp = s.trunk;

@@ -27,15 +27,16 @@ struct ConvOp {
   const int* up2_map = nullptr;   // device: Level::up2_map of in.lvl over up2.lvl
   double flops = 0;   // 2*MAC, algorithmic (unpadded)
   int dbg = 0;        // tuning only: phase-skip mask (see ConvArgs::dbg)
-  int force_shape = -1;   // tuning only: 0 wide .. 5 narrow1H
+  int force_shape = -1;   // tuning and tests: a ConvShape number (conv_route.hpp) pins the kernel and its workgroup shape; SHAPE_AUTO (-1): conv_route decides
 };
-void launch_conv(const ConvOp& op, hipStream_t st);
+void launch_conv(const ConvOp& op, hipStream_t st);      // on the kernel conv_route (conv_route.hpp) picks
 // image-input 3x3 convs (3 real channels: YOLO stem, ESRGAN conv_first) as a direct VALU kernel (ops_misc.hip)
 bool conv_direct_eligible(const ConvOp& op);
 void launch_conv_direct(const ConvOp& op, hipStream_t st);
 void conv_kernels_init();   // raise dynamic-LDS limits once per process
-// times the valid workgroup shapes of a generic-kernel conv on its own buffers; returns the fastest shape id, or -1 when
-// the op has a single candidate / goes to a specialised kernel (direct stem, row-reuse)
+// times every shape that can run a conv the automatic route gives to the generic kernel — its own shapes and those of conv_pw / conv_k3d
+// (conv_candidates, conv_route.hpp) — on the op's own buffers; returns the fastest shape number, the heuristic's unless another is > 3 % faster,
+// or -1 when the op has a single candidate, goes to a kernel with one shape (direct, rows16, rows) or already has a forced shape
 int conv_tune(const ConvOp& op, hipStream_t st);
 // The image-input conv computed inside the loader of the conv that consumes it (fp32-split plans, YOLO11s: model.0 -> model.1): the
 // stem's output (1 GB per 2-frame group of 4K slices) is neither written nor read back. stem_conv_pack() lays the stem weights out

@@ -343,11 +343,19 @@ int ffp_jpeg_decode_stats(int64_t* device_decodes, int64_t* host_fallbacks, int6
 int ffp_op_conv1x1_up2(int device, int precision, const float* coarse, const float* fine, int n, int h, int w, int c_up, int c_fine,
                        const float* wt, const float* bias, int cout, int act, float* y);
 
-/* Tuning / test hook: pin the workgroup shape ffp_op_conv2d uses from now on (process-wide; -1 = automatic, the default).
- * 0..5 generic shapes, 6..8 conv_rows, 9 / 23 / 24 the conv_rows16 kernels, 10..16 and 22 the pointwise kernels of conv_pw.hip, 17..21
- * conv_k3d, 25 conv_trunk. A specialised shape (6 and up) that cannot run the op — its layout, or an activation, residual or
- * post-activation its epilogue does not implement — is FFP_ERR_ARG of the following ffp_op_conv2d call. */
+/* Tuning / test hook: pin the kernel and workgroup shape ffp_op_conv2d and ffp_op_conv1x1_up2 use from now on (process-wide; -1 =
+ * automatic, the default). The numbers are the ConvShape table of csrc/conv_route.hpp (ffp_op_conv2d_shape_name lists it): 0..5 the
+ * generic kernel, 6..8 conv_rows, 9 / 23 conv_rows16, 24 conv_rows16pc, 10..16 and 22 conv_pw, 17..21 conv_k3d, 25 conv_trunk. A number
+ * that is not in the table is FFP_ERR_ARG here and leaves the setting as it was. A shape that cannot run the op of a following call —
+ * its layout or geometry, or an activation, residual or post-activation its epilogue does not implement — is that call's FFP_ERR_ARG:
+ * a pinned shape runs the op or nothing does. (Image-input convs have one kernel and ignore the setting.) */
 int ffp_op_conv2d_shape(int force_shape);
+/* Test hook, needs no device: "<family> <variant suffix>" of a shape number, e.g. "pw pw2x2w" (the suffix is how the variant strings of
+ * the profile getters end); FFP_ERR_ARG for a number that is not a shape. */
+int ffp_op_conv2d_shape_name(int shape, char* out, int cap);
+/* Test hook: the variant string (as the profile getters report it, e.g. "f16_k3s1_rows16") of the op that the last ffp_op_conv2d or
+ * ffp_op_conv1x1_up2 call of this thread launched; empty after a call that launched no dense conv (an error, a depthwise conv). */
+int ffp_op_conv2d_last_variant(char* out, int cap);
 /* Test hook of the same kind and lifetime: the activation code (0 none, 1 SiLU, 2 LeakyReLU(0.2), 3 ReLU) ffp_op_conv2d applies AFTER the
  * residual term from now on (ConvOp::act_post; process-wide; 0 = none, the default). Any other code: FFP_ERR_ARG; a depthwise
  * ffp_op_conv2d call while it is set: FFP_ERR_ARG. */

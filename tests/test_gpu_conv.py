@@ -1,6 +1,8 @@
 """GPU parity of the MFMA convolution kernels (through the C-ABI ffp_op_conv2d) against a plain PyTorch fp32
 reference of the same op. fp32 mode: exact-f32 MFMA, tolerance = summation-order noise. fp16 mode: operands rounded
 to fp16 on both sides, fp32 accumulate, output rounded to fp16 (tolerance stated per assert)."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -456,3 +458,81 @@ def test_conv_epilogue_contract_every_kernel(gpu_lib):
         print("  wrong:", *wline)
     assert not wrong, wrong
     assert ran >= 12 * (len(EPI_GENERIC) * 3 - 2)    # the generic kernel refuses nothing
+
+
+# ---- conv_route: a forced shape number runs the kernel it names, or is the argument error ------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _route_case(cin, cout, k, stride, half):
+    """Two images with a 9 x 17 output (ragged tile edges both ways), act none, no residual: inputs and the reference, once per case."""
+    rng = np.random.default_rng([20261019, cin, cout, k, stride, int(half)])
+    hi, wi = (9, 17) if stride == 1 else (17, 33)
+    x = rng.standard_normal((2, hi, wi, cin), dtype=np.float32)
+    wt = (rng.standard_normal((cout, cin, k, k), dtype=np.float32) / np.sqrt(cin * k * k)).astype(np.float32)
+    b = rng.standard_normal(cout, dtype=np.float32) * 0.1
+    return x, wt, b, ref_conv(x, wt, b, stride, 1, 0, 0, None, 1.0, half)
+
+
+def _route_run(P, prec, cin, cout, k, stride):
+    """(result, reference, variant of the op that ran) under whatever shape is pinned"""
+    x, wt, b, ref = _route_case(cin, cout, k, stride, prec == P.PREC_F16)
+    y = P.op_conv2d(x, wt, b, stride=stride, act=0, precision=prec)
+    return y, ref, P.op_conv2d_last_variant()
+
+
+def test_conv_forced_shape_runs_the_kernel_it_names(gpu_lib):
+    """Every number of the shape table (ffp_op_conv2d_shape_name) on the smallest case of its family from the lists of the epilogue test:
+    the call is the argument error, or the op that ran reports the table's variant suffix for that number and matches the reference at
+    this file's tolerance for the precision. The generic numbers run in all three precisions, the others in their family's. At least
+    one number per family has to run. Unpinned, the route picks rows16 for the fp16 dense-block conv and a generic shape for a 1x1."""
+    P = gpu_lib
+    tol = {P.PREC_F32: 2e-5, P.PREC_F16: 2e-3, P.PREC_F32X3: 3e-5}
+    lists = {"generic": EPI_GENERIC, "rows": EPI_ROWS, "rows16": EPI_ROWS, "rows16pc": EPI_ROWS, "trunk": EPI_ROWS, "pw": _epi_pw_cases(), "k3d": _epi_k3d_cases()}
+    precs = {"generic": (P.PREC_F32, P.PREC_F16, P.PREC_F32X3), "pw": (P.PREC_F32X3,), "k3d": (P.PREC_F32X3,)}
+    ran = {}
+    try:
+        for shape in range(26):
+            family, suffix = P.op_conv2d_shape_name(shape).split()
+            _, cin, cout, k, stride = min((c for c in lists[family] if c[0] == shape), key=lambda c: c[1] * c[2] * c[3] * c[3])
+            P.op_conv2d_shape(shape)
+            for prec in precs.get(family, (P.PREC_F16,)):
+                try:
+                    y, ref, variant = _route_run(P, prec, cin, cout, k, stride)
+                except P.FfpError as e:
+                    assert e.code == 1, (shape, prec, str(e))
+                    continue
+                assert variant.endswith("_" + suffix), (shape, prec, variant, suffix)
+                np.testing.assert_allclose(y, ref, rtol=tol[prec], atol=tol[prec], err_msg=f"shape {shape} ({variant})")
+                ran.setdefault(family, []).append(shape)
+    finally:
+        P.op_conv2d_shape(-1)
+    assert set(ran) == set(lists), ran
+    # every listed case was picked as one its shape can run (pw_can_run, the k3d tile minimum, the rows tables), so no number may hide behind its family's floor
+    assert sorted({s_ for v in ran.values() for s_ in v}) == list(range(26)), ran
+    assert _route_run(P, P.PREC_F16, 64, 32, 3, 1)[2] == "f16_k3s1_rows16"
+    assert _route_run(P, P.PREC_F32X3, 64, 128, 1, 1)[2].startswith("f32x3_k1s1_")
+
+
+def test_conv_forced_shape_that_cannot_run_the_op_is_refused(gpu_lib):
+    """A number that is no shape is refused by ffp_op_conv2d_shape itself and leaves the knob at -1; a pw / k3d number, or the two-tile rows
+    shape on an odd tile count, on the fp16 dense-block conv is the call's argument error (before conv_route these ran conv_rows_kernel —
+    the last one its <1, 2> configuration — and returned its result: DESIGN.md records that run); so are the fp16 kernels' numbers on an
+    exact-fp32 conv, and the weight-resident rows16 form (23) on 224 input channels, more than its LDS holds (it used to run the streaming form)."""
+    P = gpu_lib
+    try:
+        for bad in (26, 99, -2):
+            with pytest.raises(P.FfpError) as e:
+                P.op_conv2d_shape(bad)
+            assert e.value.code == 1, bad
+            assert _route_run(P, P.PREC_F16, 64, 32, 3, 1)[2] == "f16_k3s1_rows16", bad       # still unpinned
+        for prec, cin, shapes in ((P.PREC_F16, 64, (10, 17, 8)), (P.PREC_F32, 64, (6, 9, 25)), (P.PREC_F16, 224, (23,))):
+            for shape in shapes:
+                P.op_conv2d_shape(shape)
+                with pytest.raises(P.FfpError) as e:
+                    _route_run(P, prec, cin, 32, 3, 1)
+                assert e.value.code == 1, (prec, cin, shape, str(e.value))
+        P.op_conv2d_shape(9)                                  # seven 32-channel chunks: the streaming form runs what the resident form (six at most) refuses
+        y, ref, variant = _route_run(P, P.PREC_F16, 224, 32, 3, 1)
+        assert variant == "f16_k3s1_rows16"
+        np.testing.assert_allclose(y, ref, rtol=2e-3, atol=2e-3)
+    finally:
+        P.op_conv2d_shape(-1)

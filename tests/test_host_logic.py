@@ -31,6 +31,35 @@ def test_every_declared_symbol_is_exported(lib):
     assert lib.ffp_version() >= 200
 
 
+def test_conv_shape_table_through_shape_name(lib):
+    """The shape numbers of csrc/conv_route.hpp, read without a device: exactly 0..25 have a name, '<family> <suffix>' is unique but for
+    the rows configurations (6 / 7 / 8) and the two rows16 forms (9 / 23), whose variant strings have always been shared, and the pw and
+    k3d numbers are the keys of the GPU conv tests' PW_SHAPES and K3D_SHAPES."""
+    import ast
+    names = {}
+    for shape in range(-4, 130):
+        try:
+            names[shape] = tuple(_lib.op_conv2d_shape_name(shape).split())
+        except _lib.FfpError as e:
+            assert e.code == 1, shape
+    assert sorted(names) == list(range(26))
+    for bad in (-2, 26, 99):
+        with pytest.raises(_lib.FfpError) as e:
+            _lib.op_conv2d_shape_name(bad)
+        assert e.value.code == 1
+    assert all(len(v) == 2 for v in names.values()), names
+    groups = {}
+    for shape, v in names.items():
+        groups.setdefault(v, []).append(shape)
+    assert sorted(g for g in groups.values() if len(g) > 1) == [[6, 7, 8], [9, 23]], groups
+    assert groups[("rows", "rows")] == [6, 7, 8] and groups[("rows16", "rows16")] == [9, 23]
+    tree = ast.parse(open(os.path.join(ROOT, "tests", "test_gpu_conv.py")).read())
+    consts = {t.id: ast.literal_eval(n.value) for n in tree.body if isinstance(n, ast.Assign) for t in n.targets
+              if isinstance(t, ast.Name) and t.id in ("PW_SHAPES", "K3D_SHAPES")}
+    assert sorted(consts["PW_SHAPES"]) == sorted(s for s, v in names.items() if v[0] == "pw")
+    assert sorted(consts["K3D_SHAPES"]) == sorted(s for s, v in names.items() if v[0] == "k3d")
+
+
 def test_slice_bboxes_matches_oracle(lib):
     for (H, W, s, o) in [(2160, 3840, 512, 0.2), (4320, 7680, 640, 0.25), (300, 400, 512, 0.2), (513, 1025, 512, 0.0), (1000, 777, 333, 0.37)]:
         assert _lib.slice_bboxes(H, W, s, s, o, o).tolist() == sahi_ref.get_slice_bboxes(H, W, s, s, o, o)
