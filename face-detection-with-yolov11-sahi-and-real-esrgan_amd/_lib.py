@@ -102,6 +102,9 @@ _SIGS = {
     "ffp_sr_mem_bytes": (C.c_int, [C.c_void_p, _p(C.c_uint64), _p(C.c_uint64), _p(C.c_int32)]),
     "ffp_det_mem_bytes": (C.c_int, [C.c_void_p, _p(C.c_uint64), _p(C.c_uint64), _p(C.c_int32)]),
     "ffp_det_set_lanes": (C.c_int, [C.c_void_p, C.c_int]),
+    "ffp_det_set_buffer_reuse": (C.c_int, [C.c_void_p, C.c_int]),
+    "ffp_det_mem_detail": (C.c_int, [C.c_void_p, _p(C.c_uint64), _p(C.c_uint64), _p(C.c_uint64)]),
+    "ffp_det_fill_steps": (C.c_int, [C.c_void_p, _p(C.c_int32), _p(C.c_int32)]),
     "ffp_det_stream_wait_event": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ffp_sr_last_ms": (C.c_int, [C.c_void_p, _p(C.c_float)]),
     "ffp_sr_last_conv_stats": (C.c_int, [C.c_void_p, _p(C.c_double), _p(C.c_float), _p(C.c_int32)]),
@@ -539,6 +542,23 @@ class Detector:
     def set_lanes(self, mode: int):
         """0 (default) one stream; 1 head towers and C3k side convs as parallel graph branches (detector-only deployments)."""
         _check(lib().ffp_det_set_lanes(self._h, int(mode)))
+
+    def set_buffer_reuse(self, mode: int):
+        """0 one allocation per activation tensor; 1 (default) tensors with disjoint lifetimes share bytes; 2 as 1, released ranges are
+        overwritten with 0xFF bytes (diagnostic). Results are bit-identical; the cached plans are dropped."""
+        _check(lib().ffp_det_set_buffer_reuse(self._h, int(mode)))
+
+    def mem_detail(self) -> dict:
+        """Activation storage of the resident plans: bytes held, bytes one allocation per tensor would hold, peak of the bytes live at once."""
+        a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(lib().ffp_det_mem_detail(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return {"activation_bytes": int(a.value), "no_reuse_bytes": int(b.value), "peak_live_bytes": int(c.value)}
+
+    def fill_steps(self) -> dict:
+        """Test hook: 0xFF fill steps in the resident plans, and tensors whose range reached the free list (mode 2: equal and > 0)."""
+        a, b = C.c_int32(0), C.c_int32(0)
+        _check(lib().ffp_det_fill_steps(self._h, C.byref(a), C.byref(b)))
+        return {"fill_steps": int(a.value), "ranges_freed": int(b.value)}
 
     def stream_wait_event(self, hip_event: int):
         """Order the handle's following work behind a hipEvent_t of this process (torch.cuda.Event.cuda_event)."""

@@ -138,9 +138,34 @@ def build_asan(verbose: bool = True) -> str:
     return ASAN_OUT
 
 
+ARENA_OUT = os.path.join(CSRC, "build", "arena_host_check")
+
+
+def build_arena_check(verbose: bool = True) -> str:
+    """Host-only AddressSanitizer + UBSan build of the plans' lifetime pool (csrc/arena.hpp, no HIP in it) with its driver
+    (csrc/arena_host_check.cpp): seeded alloc / release / fork / join sequences against a shadow model."""
+    clang = os.path.join(os.path.dirname(os.path.realpath(_hipcc())), "..", "lib", "llvm", "bin", "clang++")
+    if not os.path.exists(clang):
+        clang = "/opt/rocm/lib/llvm/bin/clang++"
+    os.makedirs(os.path.dirname(ARENA_OUT), exist_ok=True)
+    srcs = [os.path.join(CSRC, "arena_host_check.cpp"), os.path.join(CSRC, "arena.hpp")]
+    if os.path.exists(ARENA_OUT) and os.path.getmtime(ARENA_OUT) > max(os.path.getmtime(s) for s in srcs):
+        return ARENA_OUT
+    cmd = [clang, "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
+           srcs[0], "-o", ARENA_OUT]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(f"sanitizer build failed:\n{r.stdout}\n{r.stderr}")
+    if verbose:
+        print(f"built {ARENA_OUT}")
+    return ARENA_OUT
+
+
 if __name__ == "__main__":
     if "--asan" in sys.argv:
         build_asan()
+    elif "--arena-check" in sys.argv:
+        build_arena_check()
     elif "--variant" in sys.argv:
         build_variant(sys.argv[sys.argv.index("--variant") + 1])
     else:

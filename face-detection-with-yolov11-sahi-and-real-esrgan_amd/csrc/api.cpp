@@ -285,6 +285,15 @@ int ffp_det_set_lanes(ffp_det* d, int mode) {
   FFP_API_END
 }
 
+int ffp_det_set_buffer_reuse(ffp_det* d, int mode) {
+  FFP_API_BEGIN
+  FFP_CHECK(d && mode >= 0 && mode <= 2, FFP_ERR_ARG, "det_set_buffer_reuse: mode %d outside [0,2]", mode);
+  FFP_HIP(hipSetDevice(d->eng.device()));
+  FFP_HIP(hipStreamSynchronize(d->eng.stream()));
+  d->eng.set_buffer_reuse(mode);
+  FFP_API_END
+}
+
 int ffp_det_stream_wait_event(ffp_det* d, void* hip_event) {
   FFP_API_BEGIN
   FFP_CHECK(d && hip_event, FFP_ERR_ARG, "det_stream_wait_event: null argument");
@@ -568,6 +577,25 @@ int ffp_det_mem_bytes(ffp_det* d, uint64_t* out_weight_bytes, uint64_t* out_plan
   if (out_weight_bytes) *out_weight_bytes = d->eng.weight_bytes();
   if (out_plan_bytes) *out_plan_bytes = d->eng.plan_bytes();
   if (out_plans_resident) *out_plans_resident = d->eng.plans_resident();
+  return FFP_OK;
+}
+
+int ffp_det_mem_detail(ffp_det* d, uint64_t* out_activation_bytes, uint64_t* out_no_reuse_bytes, uint64_t* out_peak_live_bytes) {
+  if (!d) return FFP_ERR_ARG;
+  size_t a = 0, n = 0, p = 0;
+  d->eng.mem_detail(&a, &n, &p);
+  if (out_activation_bytes) *out_activation_bytes = a;
+  if (out_no_reuse_bytes) *out_no_reuse_bytes = n;
+  if (out_peak_live_bytes) *out_peak_live_bytes = p;
+  return FFP_OK;
+}
+
+int ffp_det_fill_steps(ffp_det* d, int32_t* out_fill_steps, int32_t* out_ranges_freed) {
+  if (!d) return FFP_ERR_ARG;
+  int f = 0, r = 0;
+  d->eng.fill_counts(&f, &r);
+  if (out_fill_steps) *out_fill_steps = f;
+  if (out_ranges_freed) *out_ranges_freed = r;
   return FFP_OK;
 }
 

@@ -142,9 +142,50 @@ TView Plan::alloc(Level* l, int C, DType dt) {
 void Plan::materialize(TView& v) {
   if (v.ptr) return;
   const size_t nb = (size_t)v.lvl->total_px * v.cs * dsize(v.dt) + 256;   // slack: vector loads of the last record stay in bounds
-  bufs.emplace_back(nb);
-  bytes += nb;
-  v.ptr = bufs.back().p;
+  const int id = pool().alloc(nb);
+  FFP_CHECK(id >= 0, FFP_ERR_HIP, "plan: device block of %zu bytes is not %zu-byte aligned", nb, (size_t)Arena::ALIGN);
+  tensor_key.push_back(v.amax);
+  v.ptr = reinterpret_cast<void*>(arena->addr(id));
+}
+
+Arena& Plan::pool() {
+  if (!arena)
+    arena.reset(new Arena([this](size_t n) { bufs.emplace_back(n); bytes += n; return (uintptr_t)bufs.back().p; }, reuse != 0));
+  return *arena;
+}
+
+void Plan::add_fill(int id) {
+  void* p = reinterpret_cast<void*>(arena->addr(id));
+  const size_t n = arena->tensor(id).span;
+  Step s;
+  s.run = [p, n](hipStream_t q) { FFP_HIP(hipMemsetAsync(p, 0xFF, n, q)); };
+  steps.push_back(std::move(s));
+  ++fill_steps;
+}
+
+void Plan::release(const TView& v) {
+  if (!v.ptr || v.coff != 0 || v.C != v.cs) return;       // a slice, or a view that never got storage: releases nothing
+  int id = -1;
+  for (int i = (int)tensor_key.size() - 1; i >= 0 && id < 0; --i)
+    if (tensor_key[i] == v.amax) id = i;
+  FFP_CHECK(id >= 0 && arena, FFP_ERR_STATE, "plan: release of a view this plan did not allocate");
+  const Arena::Release r = arena->release(id);
+  FFP_CHECK(r != Arena::REJECTED, FFP_ERR_STATE, "plan: tensor released twice");
+  if (r == Arena::FREED) { ++ranges_freed; if (reuse == 2) add_fill(id); }
+}
+
+void Plan::release_since(int first, const std::vector<const unsigned*>& kept) noexcept {
+  if (!arena) return;
+  try {
+    for (int id = first; id < arena->tensors(); ++id) {
+      if (arena->tensor(id).state != 0) continue;
+      bool keep = false;
+      for (const unsigned* k : kept) keep = keep || k == tensor_key[id];
+      if (keep) continue;
+      if (arena->release(id) == Arena::FREED) { ++ranges_freed; if (reuse == 2) add_fill(id); }
+    }
+  } catch (...) {                                         // only an allocation failure of the step list can land here: the tensors stay live
+  }
 }
 
 TView Plan::alloc_virtual(Level* l, int C, DType dt) {
@@ -269,6 +310,7 @@ void Plan::fork(int lane) {
   s.kind = 1; s.lane = lane;
   FFP_HIP(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
   steps.push_back(std::move(s));
+  pool().fork();
 }
 
 void Plan::join(int lane) {
@@ -277,6 +319,13 @@ void Plan::join(int lane) {
   s.kind = 2; s.lane = lane;
   FFP_HIP(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
   steps.push_back(std::move(s));
+  // ranges released while a fork was open become free here, once no lane can still be running a step that uses them
+  std::vector<int> flushed;
+  // (fork and join reach the pool in every plan type, releases or not: an unmatched join is now an error where it used to be a dangling
+  // event wait. Only the YOLO11 plan forks today, and its joins are matched in every lane mode.)
+  FFP_CHECK(pool().join(&flushed), FFP_ERR_STATE, "plan: join without an open fork");
+  ranges_freed += (int)flushed.size();
+  if (reuse == 2) for (int id : flushed) add_fill(id);
 }
 
 // use_lanes = false: every step on `st` in issue order (a valid serialisation: forks / joins only relax the order)

@@ -2,6 +2,7 @@
 #pragma once
 #include <functional>
 
+#include "arena.hpp"
 #include "common.hpp"
 #include "det_post.hpp"
 #include "ops.hpp"
@@ -87,6 +88,35 @@ struct Plan {
   TView alloc(Level* l, int C, DType dt);
   TView alloc_virtual(Level* l, int C, DType dt);        // a view with a max-|value| slot but no storage yet: a tensor that may be fused away
   void materialize(TView& v);                            // ... and its storage, once some kernel turns out to need it
+  // Storage by tensor lifetime (arena.hpp). release(v): no step added after this point reads or writes v; its byte range may back a
+  // tensor allocated later (while a fork is open: after the last open fork has been joined). Only the view alloc / materialize returned
+  // releases anything, a slice does not; a second release of a tensor is FFP_ERR_STATE. Max-|value| slots stay per tensor. A plan that
+  // never releases keeps one block per tensor. `reuse` is set by the owner before the first alloc: 0 release() only closes the lifetime
+  // (one block per tensor: parity oracle and A/B partner), 1 released ranges are handed out again, 2 as 1 and a step appended where a
+  // range becomes free overwrites it with 0xFF bytes (NaN in fp32 and fp16): a step that reads a tensor after its declared end then
+  // reads NaN, reused or not.
+  int reuse = 0;
+  void release(const TView& v);
+  // releases, at scope exit, what was allocated inside the scope, is still live and was not handed out with keep()
+  struct Scope {
+    explicit Scope(Plan& p) : P(p), first(p.pool().tensors()) {}
+    ~Scope() { P.release_since(first, kept); }
+    Scope(const Scope&) = delete;
+    Scope& operator=(const Scope&) = delete;
+    void keep(const TView& v) { kept.push_back(v.amax); }
+    Plan& P;
+    int first;
+    std::vector<const unsigned*> kept;
+  };
+  std::unique_ptr<Arena> arena;                          // created on first use (after the owner has set `reuse`)
+  Arena& pool();
+  std::vector<const unsigned*> tensor_key;               // arena id -> the tensor's max-|value| slot (unique per tensor, shared by its slices)
+  size_t activation_bytes() const { return arena ? arena->held_bytes() : 0; }
+  size_t no_reuse_bytes() const { return arena ? arena->sum_sizes() : 0; }
+  size_t peak_live_bytes() const { return arena ? arena->peak_live_bytes() : 0; }
+  void release_since(int first, const std::vector<const unsigned*>& kept) noexcept;
+  int fill_steps = 0, ranges_freed = 0;                  // steps add_fill appended; tensors whose range reached the free list (any mode)
+  void add_fill(int id);                                 // reuse == 2: the 0xFF fill of a range that has just become free (lane 0)
   void add_conv(const ConvOp& op);
   void add_trunk(const std::vector<ConvOp>& ops);        // the ops as ONE persistent launch (every op: conv_trunk_layer_ok)
   void add(std::function<void(hipStream_t)> f) { Step s; s.run = std::move(f); s.lane = cur_lane; steps.push_back(std::move(s)); }

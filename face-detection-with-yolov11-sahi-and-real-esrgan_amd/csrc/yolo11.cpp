@@ -115,6 +115,7 @@ void DetEngine::build_plan(DetPlan& P, const std::vector<int>& hs, const std::ve
   };
   // Bottleneck(c, c, shortcut, k=(3,3)): out = x + cv2(cv1(x))
   auto bottleneck = [&](const std::string& p, const TView& x, const TView& out, int chid) {
+    Plan::Scope tmp(P);                                 // t
     TView t = P.alloc(x.lvl, chid, T);
     cv(p + ".cv1.conv", x, t, 1, ACT_SILU);
     cv(p + ".cv2.conv", t, out, 1, ACT_SILU, &x);
@@ -122,6 +123,7 @@ void DetEngine::build_plan(DetPlan& P, const std::vector<int>& hs, const std::ve
   // C3k(c, c, n=2) on view b into view mo: cv3(cat(m(cv1(b)), cv2(b)))
   auto c3k = [&](const std::string& p, const TView& b, const TView& mo, int c) {
     const int c_ = c / 2;
+    Plan::Scope tmp(P);                                 // cat2, a0, a1 (released at the join when the side lane is on)
     TView cat2 = P.alloc(b.lvl, 2 * c_, T);
     TView a0 = P.alloc(b.lvl, c_, T), a1 = P.alloc(b.lvl, c_, T);
     const int side = 10;                               // C3k's second branch (one 1x1 conv over b) runs beside the bottleneck chain
@@ -139,6 +141,7 @@ void DetEngine::build_plan(DetPlan& P, const std::vector<int>& hs, const std::ve
   auto c3k2 = [&](const std::string& p, const TView& in, const TView& out, int c2, bool use_c3k, double e, const TView* up2 = nullptr) {
     const int c = (int)(c2 * e);
     use_c3k = use_c3k || force_c3k;
+    Plan::Scope tmp(P);                                 // cat
     TView cat = P.alloc(in.lvl, (2 + reps) * c, T);
     cv(p + ".cv1.conv", in, cat.slice(0, 2 * c), 1, ACT_SILU, nullptr, up2);
     for (int i = 0; i < reps; ++i) {
@@ -154,12 +157,11 @@ void DetEngine::build_plan(DetPlan& P, const std::vector<int>& hs, const std::ve
   const int cin0 = T == F16 ? 8 : 4;
   P.input = TView{};
   P.input.dt = T; P.input.cs = cin0; P.input.C = cin0; P.input.lvl = P.L[0];     // storage only if the stem is not fused (below)
-  TView cat12 = P.alloc(P.L[4], c1024 + c512, T);   // [up(x10) | x6]
-  TView cat15 = P.alloc(P.L[3], c512 + c512, T);    // [up(x13) | x4]
-  TView cat18 = P.alloc(P.L[4], c256 + c512, T);    // [conv17(x16) | x13]
-  TView cat21 = P.alloc(P.L[5], c512 + c1024, T);   // [conv20(x19) | x10]
-  const TView x6 = cat12.slice(c1024, c512), x4 = cat15.slice(c512, c512);
-  const TView x13 = cat18.slice(c256, c512), x10 = cat21.slice(c512, c1024);
+  // Each is allocated where its first slice is written and released behind the C3k2 that reads it whole: the skip tensors x4, x6,
+  // x10 and x13 live in them from the backbone to the neck. Everything else is released behind its last reader (Plan::release,
+  // Plan::Scope for a block's temporaries), so a later tensor may reuse its bytes. Never released: P.input, the tensor the stem launch
+  // writes before execute() (x1, or x0 on the two-kernel path: the tuner's timing launches run after that launch and write every
+  // conv's output) and P.head[l], which decode reads after the plan.
 
   // ---- backbone --------------------------------------------------------------------------------------------------------
   TView x0 = P.alloc_virtual(P.L[1], c64, T);      // stored only if a kernel reads it (not when model.1's loader computes it)
@@ -205,32 +207,47 @@ void DetEngine::build_plan(DetPlan& P, const std::vector<int>& hs, const std::ve
   }
   TView x2 = P.alloc(P.L[2], c256, T);
   c3k2("model.2", x1, x2, c256, false, 0.25);
+  if (!P.fused_stem_conv) P.release(x1);
   TView x3 = P.alloc(P.L[3], c256, T);
   cv("model.3.conv", x2, x3, 2, ACT_SILU);
+  P.release(x2);
+  TView cat15 = P.alloc(P.L[3], c512 + c512, T);    // [up(x13) | x4]
+  const TView x4 = cat15.slice(c512, c512);
   c3k2("model.4", x3, x4, c512, false, 0.25);
+  P.release(x3);
   TView x5 = P.alloc(P.L[4], c512, T);
   cv("model.5.conv", x4, x5, 2, ACT_SILU);
+  TView cat12 = P.alloc(P.L[4], c1024 + c512, T);   // [up(x10) | x6]
+  const TView x6 = cat12.slice(c1024, c512);
   c3k2("model.6", x5, x6, c512, true, 0.5);
+  P.release(x5);
   TView x7 = P.alloc(P.L[5], c1024, T);
   cv("model.7.conv", x6, x7, 2, ACT_SILU);
   TView x8 = P.alloc(P.L[5], c1024, T);
   c3k2("model.8", x7, x8, c1024, true, 0.5);
+  P.release(x7);
+  TView cat21 = P.alloc(P.L[5], c512 + c1024, T);   // [conv20(x19) | x10]
+  const TView x10 = cat21.slice(c512, c1024);
   // SPPF
   {
     const int c_ = c1024 / 2;
     TView cat9 = P.alloc(P.L[5], 4 * c_, T);
     cv("model.9.cv1.conv", x8, cat9.slice(0, c_), 1, ACT_SILU);
+    P.release(x8);
     const TView y0 = cat9.slice(0, c_), y1 = cat9.slice(c_, c_), y2 = cat9.slice(2 * c_, c_), y3 = cat9.slice(3 * c_, c_);
     P.add([y0, y1, y2, y3](hipStream_t s) { launch_sppf_pool(y0, y1, y2, y3, s); });
     TView x9 = P.alloc(P.L[5], c1024, T);
     cv("model.9.cv2.conv", cat9, x9, 1, ACT_SILU);
+    P.release(cat9);
     // C2PSA
     const int h = c1024 / 2, nh = h / 64, hd = h / nh, kd = hd / 2;
     TView pb = P.alloc(P.L[5], 2 * h, T);
     cv("model.10.cv1.conv", x9, pb, 1, ACT_SILU);
+    P.release(x9);
     const TView b = pb.slice(h, h);
     for (int i = 0; i < reps; ++i) {                  // PSABlocks m.0, m.1, ... each in place on b
       const std::string pm = "model.10.m." + std::to_string(i);
+      Plan::Scope tmp(P);                             // qkv, ao, xa, b2, f1
       TView qkv = P.alloc(P.L[5], nh * (2 * kd + hd), T);
       cv(pm + ".attn.qkv.conv", b, qkv, 1, ACT_NONE);
       TView ao = P.alloc(P.L[5], h, T);
@@ -251,6 +268,7 @@ void DetEngine::build_plan(DetPlan& P, const std::vector<int>& hs, const std::ve
       cv(pm + ".ffn.1.conv", f1, b, 1, ACT_NONE, &b2);
     }
     cv("model.10.cv2.conv", pb, x10, 1, ACT_SILU);
+    P.release(pb);
   }
   // ---- neck ------------------------------------------------------------------------------------------------------------
   // Upsample + Concat feed a 1x1 conv only: its loader reads the coarse tensor through the x2 pixel map (no upsampled copy)
@@ -259,7 +277,10 @@ void DetEngine::build_plan(DetPlan& P, const std::vector<int>& hs, const std::ve
     const TView up = cat12.slice(0, c1024);
     P.add([x10, up](hipStream_t s) { launch_upsample2x(x10, up, s); launch_amax_max(up.amax, x10.amax, s, up.amax_n); });
   }
+  TView cat18 = P.alloc(P.L[4], c256 + c512, T);    // [conv17(x16) | x13]
+  const TView x13 = cat18.slice(c256, c512);
   c3k2("model.13", cat12, x13, c512, false, 0.5, fold12 ? &x10 : nullptr);
+  P.release(cat12);
   if (!fold15) {
     const TView up = cat15.slice(0, c512);
     P.add([x13, up](hipStream_t s) { launch_upsample2x(x13, up, s); launch_amax_max(up.amax, x13.amax, s, up.amax_n); });
@@ -276,7 +297,9 @@ void DetEngine::build_plan(DetPlan& P, const std::vector<int>& hs, const std::ve
   // neck, whose stride-16/32 launches (and the towers of levels 1 and 2) leave most of the chip idle on their own.
   auto head_level = [&](int l, const TView& x) {
     Level* lv = P.L[3 + l];
+    Plan::Scope tmp(P);                                 // the towers' temporaries (with lanes on: free once every tower has been joined)
     P.head[l] = P.alloc(lv, head_cs, F32);
+    tmp.keep(P.head[l]);                                // decode reads it after the plan
     const std::string p = "model.23";
     const std::string ls = std::to_string(l);
     TView t1 = P.alloc(lv, c2, T), t2 = P.alloc(lv, c2, T);
@@ -287,6 +310,8 @@ void DetEngine::build_plan(DetPlan& P, const std::vector<int>& hs, const std::ve
     cv(p + ".cv2." + ls + ".0.conv", x, t1, 1, ACT_SILU);
     cv(p + ".cv2." + ls + ".1.conv", t1, t2, 1, ACT_SILU);
     cv(p + ".cv2." + ls + ".2", t2, P.head[l].slice(0, 64), 1, ACT_NONE);
+    P.release(t1);
+    P.release(t2);
     TView d1 = P.alloc(lv, chs[l], T), e1 = P.alloc(lv, c3, T), d2 = P.alloc(lv, c3, T), e2 = P.alloc(lv, c3, T);
     P.cur_lane = tower_lane(2);
     dw(p + ".cv3." + ls + ".0.0.conv", x, d1, ACT_SILU);
@@ -294,6 +319,10 @@ void DetEngine::build_plan(DetPlan& P, const std::vector<int>& hs, const std::ve
     dw(p + ".cv3." + ls + ".1.0.conv", e1, d2, ACT_SILU);
     cv(p + ".cv3." + ls + ".1.1.conv", d2, e2, 1, ACT_SILU);
     cv(p + ".cv3." + ls + ".2", e2, P.head[l].slice(64, nc_), 1, ACT_NONE);
+    P.release(d1);
+    P.release(e1);
+    P.release(d2);
+    P.release(e2);
     if (nk > 0) {
       TView k1 = P.alloc(lv, c4, T), k2 = P.alloc(lv, c4, T);
       P.cur_lane = tower_lane(3);
@@ -307,15 +336,21 @@ void DetEngine::build_plan(DetPlan& P, const std::vector<int>& hs, const std::ve
 
   TView x16 = P.alloc(P.L[3], c256, T);
   c3k2("model.16", cat15, x16, c256, false, 0.5, fold15 ? &x13 : nullptr);
+  P.release(cat15);
   head_level(0, x16);
   cv("model.17.conv", x16, cat18.slice(0, c256), 2, ACT_SILU);
+  P.release(x16);
   TView x19 = P.alloc(P.L[4], c512, T);
   c3k2("model.19", cat18, x19, c512, false, 0.5);
+  P.release(cat18);
   head_level(1, x19);
   cv("model.20.conv", x19, cat21.slice(0, c512), 2, ACT_SILU);
+  P.release(x19);
   TView x22 = P.alloc(P.L[5], c1024, T);
   c3k2("model.22", cat21, x22, c1024, true, 0.5);
+  P.release(cat21);
   head_level(2, x22);
+  P.release(x22);
 
   // ---- Pose head: per level one fp32 record [64 DFL | nc | 3*nkpt] per pixel ---------------------------------------------
   for (int k = 1; k <= 9; ++k)                      // lane 0 continues (decode, NMS) after every tower of every level
@@ -392,6 +427,7 @@ DetPlan* DetEngine::plan_for(const std::vector<TileGeom>& g) {
     while (plans_.size() >= 8 && evict_lru(nullptr)) {}
     std::unique_ptr<DetPlan> p(new DetPlan());
     p->lanes = lanes_;
+    p->reuse = reuse_;
     std::vector<int> hs, ws;
     for (const TileGeom& t : g) { hs.push_back(t.lb.net_h); ws.push_back(t.lb.net_w); }
     build_plan(*p, hs, ws);
@@ -408,6 +444,21 @@ void DetEngine::drop_plans() {
   FFP_HIP(hipSetDevice(device_));
   FFP_HIP(hipStreamSynchronize(st_));
   plans_.clear();
+}
+
+int DetEngine::reuse_env() {
+  // exactly "0", "1" or "2"; anything else (unset, "on", "01") keeps the default, never the large layout by accident
+  static const int m = [] { const char* e = getenv("FFP_DET_ARENA"); return e && e[0] >= '0' && e[0] <= '2' && !e[1] ? e[0] - '0' : 1; }();
+  return m;
+}
+
+void DetEngine::mem_detail(size_t* activation, size_t* no_reuse, size_t* peak_live) const {
+  *activation = *no_reuse = *peak_live = 0;
+  for (const auto& kv : plans_) {
+    *activation += kv.second->activation_bytes();
+    *no_reuse += kv.second->no_reuse_bytes();
+    *peak_live += kv.second->peak_live_bytes();
+  }
 }
 
 size_t DetEngine::plan_bytes() const {

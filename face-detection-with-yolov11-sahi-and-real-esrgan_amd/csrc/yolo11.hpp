@@ -34,6 +34,18 @@ class DetEngine {
   int det_stride() const { return 6 + 3 * nkpt_; }
   // Plan::lanes of every plan built from now on (cached plans are dropped): parallel graph branches for the head towers and C3k
   void set_lanes(int mode) { if (mode != lanes_) { lanes_ = mode; plans_.clear(); } }
+  // Plan::reuse of every plan built from now on (cached plans are dropped): 0 a device block per activation tensor, 1 (default; env
+  // FFP_DET_ARENA sets another default for A/B runs) tensors whose lifetimes do not overlap share bytes, 2 as 1 with released ranges
+  // overwritten by 0xFF bytes. Results are bit-identical in all three.
+  void set_buffer_reuse(int mode) { reuse_ = mode; plans_.clear(); }
+  int buffer_reuse() const { return reuse_; }
+  // summed over the resident plans: bytes held for Plan::alloc tensors, what one block per tensor would hold, and the maximum over
+  // build order of the bytes live at once (the floor of any placement)
+  void mem_detail(size_t* activation, size_t* no_reuse, size_t* peak_live) const;
+  void fill_counts(int* fill_steps, int* ranges_freed) const {     // summed over the resident plans (Plan::fill_steps, ranges_freed)
+    *fill_steps = *ranges_freed = 0;
+    for (const auto& kv : plans_) { *fill_steps += kv.second->fill_steps; *ranges_freed += kv.second->ranges_freed; }
+  }
   int device() const { return device_; }
   hipStream_t stream() const { return st_; }
   int nc() const { return nc_; }
@@ -79,6 +91,8 @@ class DetEngine {
   std::map<std::vector<int>, std::unique_ptr<DetPlan>> plans_;
   std::vector<TileGeom> geom_last_;
   int lanes_ = 0;
+  static int reuse_env();       // FFP_DET_ARENA, or 1
+  int reuse_ = reuse_env();
   unsigned long long use_clock_ = 0;
   size_t weight_bytes_ = 0;
   int device_ = 0, nc_ = 1, nkpt_ = 5;

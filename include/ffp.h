@@ -231,7 +231,27 @@ int ffp_sr_mem_bytes(ffp_sr* s, uint64_t* out_weight_bytes, uint64_t* out_plan_b
  * again (tens of ms: layout, tuning, graph capture). The counterpart of `del model; torch.cuda.empty_cache()` around the reference's modules. */
 int ffp_det_drop_plans(ffp_det* d);
 int ffp_sr_drop_plans(ffp_sr* s);
+/* The detector's plan bytes are the blocks its plans hold, not the sum of its tensors: with buffer reuse on (the default, see
+ * ffp_det_set_buffer_reuse) activation tensors whose lifetimes do not overlap share bytes, and this figure is smaller by what they share. */
 int ffp_det_mem_bytes(ffp_det* d, uint64_t* out_weight_bytes, uint64_t* out_plan_bytes, int32_t* out_plans_resident);
+/* How the activation tensors of the detector's plans are stored. The reference holds one torch module per model
+ * (utils/yolo_wrapper.py:47-61) and leaves activations to torch's caching allocator, which hands a freed tensor's block to the next
+ * one; here a plan's pointers are fixed when it is laid out, so reuse is decided then, from the order the steps are built in.
+ * mode 0: every tensor has its own allocation (parity oracle and A/B partner); 1 (default; env FFP_DET_ARENA=0|1|2 sets another
+ * default): a tensor's bytes go back to the plan's pool behind its last reader and may back a later tensor; 2: as 1, and each
+ * released range is then overwritten with 0xFF bytes (NaN in fp32 and fp16) — a diagnostic: a step that reads a tensor after its
+ * declared end reads NaN, whether or not the range was reused. Results are bit-identical in all modes. Drops the cached plans.
+ * FFP_ERR_ARG for any other mode. */
+int ffp_det_set_buffer_reuse(ffp_det* d, int mode);
+/* Activation storage of the resident detector plans, summed (the part of ffp_det_mem_bytes' plan bytes that torch's caching allocator
+ * would own in the reference, utils/yolo_wrapper.py:47-61): bytes held for activation tensors; what mode 0 would hold (the sum of
+ * every tensor's size); and the maximum, over the order the steps are built in, of the bytes live at once — the floor of any
+ * placement. Any out pointer may be null. */
+int ffp_det_mem_detail(ffp_det* d, uint64_t* out_activation_bytes, uint64_t* out_no_reuse_bytes, uint64_t* out_peak_live_bytes);
+/* (test hook, no counterpart in the reference) Over the resident detector plans: the 0xFF fill steps their step lists hold, and the tensors
+ * whose range reached the free list while they were built. Mode 2 holds exactly one fill per freed range, modes 0 and 1 none — what
+ * makes mode 2 a diagnostic and not a second mode 1. */
+int ffp_det_fill_steps(ffp_det* d, int32_t* out_fill_steps, int32_t* out_ranges_freed);
 /* hipGraph state of the plan the detector's last call ran: 1 replayed a captured graph, 0 not captured yet (first runs of a
  * plan are eager), -1 capture failed and the plan keeps launching eagerly (also reported once on stderr). */
 int ffp_det_graph_status(ffp_det* d, int32_t* out_state);
