@@ -103,6 +103,8 @@ _SIGS = {
     "ffp_det_mem_bytes": (C.c_int, [C.c_void_p, _p(C.c_uint64), _p(C.c_uint64), _p(C.c_int32)]),
     "ffp_det_set_lanes": (C.c_int, [C.c_void_p, C.c_int]),
     "ffp_det_set_buffer_reuse": (C.c_int, [C.c_void_p, C.c_int]),
+    "ffp_det_set_gate": (C.c_int, [C.c_void_p, C.c_int]),
+    "ffp_det_last_active": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ffp_det_mem_detail": (C.c_int, [C.c_void_p, _p(C.c_uint64), _p(C.c_uint64), _p(C.c_uint64)]),
     "ffp_det_fill_steps": (C.c_int, [C.c_void_p, _p(C.c_int32), _p(C.c_int32)]),
     "ffp_det_stream_wait_event": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -547,6 +549,16 @@ class Detector:
         """0 one allocation per activation tensor; 1 (default) tensors with disjoint lifetimes share bytes; 2 as 1, released ranges are
         overwritten with 0xFF bytes (diagnostic). Results are bit-identical; the cached plans are dropped."""
         _check(lib().ffp_det_set_buffer_reuse(self._h, int(mode)))
+
+    def set_gate(self, on: bool):
+        """Skip the box and keypoint towers of items without a class score above conf (default on); bit-identical results; drops the cached plans."""
+        _check(lib().ffp_det_set_gate(self._h, int(on)))
+
+    def last_active(self) -> tuple:
+        """(items whose box and keypoint towers ran, items) of the last inference call."""
+        a, n = C.c_int32(0), C.c_int32(0)
+        _check(lib().ffp_det_last_active(self._h, C.byref(a), C.byref(n)))
+        return int(a.value), int(n.value)
 
     def mem_detail(self) -> dict:
         """Activation storage of the resident plans: bytes held, bytes one allocation per tensor would hold, peak of the bytes live at once."""

@@ -294,6 +294,23 @@ int ffp_det_set_buffer_reuse(ffp_det* d, int mode) {
   FFP_API_END
 }
 
+int ffp_det_set_gate(ffp_det* d, int on) {
+  FFP_API_BEGIN
+  FFP_CHECK(d, FFP_ERR_ARG, "null handle");
+  d->eng.set_gate(on != 0);
+  FFP_API_END
+}
+
+int ffp_det_last_active(ffp_det* d, int32_t* out_active, int32_t* out_items) {
+  FFP_API_BEGIN
+  FFP_CHECK(d && out_active && out_items, FFP_ERR_ARG, "null argument");
+  int a = 0, n = 0;
+  d->eng.last_active(&a, &n);
+  *out_active = a;
+  *out_items = n;
+  FFP_API_END
+}
+
 int ffp_det_stream_wait_event(ffp_det* d, void* hip_event) {
   FFP_API_BEGIN
   FFP_CHECK(d && hip_event, FFP_ERR_ARG, "det_stream_wait_event: null argument");

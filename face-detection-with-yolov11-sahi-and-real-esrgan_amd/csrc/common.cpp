@@ -160,7 +160,34 @@ const int4* Level::tile_table_packed(int th, int* n_launch, const int** d_count,
   return tile_table(-th, n_launch, d_count, st);
 }
 
-const int4* Level::tile_table(int key, int* n_launch, const int** d_count, hipStream_t st) {
+void Level::compact_gated(hipStream_t st) {
+  for (auto& kv : gated) {
+    const TileTab& full = tiles.at(kv.first);
+    gate_compact(full.tab.as<int4>(), full.n, d_tab.as<int4>(), n, kv.first, gate_active, kv.second.tab.as<int4>(), kv.second.d_count.as<int>(), st);
+  }
+}
+
+const int4* Level::tile_table(int key, int* n_launch, const int** d_count, hipStream_t st, const int* gate) {
+  if (gate) {
+    FFP_CHECK(key > 0 && !capacity() && d_count, FFP_ERR_STATE, "level: gated tile tables are for unpacked tables of exact-mode levels");
+    FFP_CHECK(!gate_active || gate_active == gate, FFP_ERR_STATE, "level: a second gate");
+    FFP_CHECK(gate_compact, FFP_ERR_STATE, "level: gated tile table without a compaction launcher");
+    int n_full = 0;
+    const int4* full = tile_table(key, &n_full, nullptr, st);
+    auto it = gated.find(key);
+    if (it == gated.end()) {
+      gate_active = gate;
+      TileTab t;
+      t.cap = n_full;
+      t.tab.alloc(sizeof(int4) * (size_t)n_full);
+      t.d_count.alloc(sizeof(int));
+      it = gated.emplace(key, std::move(t)).first;
+      gate_compact(full, n_full, d_tab.as<int4>(), n, key, gate, it->second.tab.as<int4>(), it->second.d_count.as<int>(), st);
+    }
+    *n_launch = n_full;
+    *d_count = it->second.d_count.as<int>();
+    return it->second.tab.as<int4>();
+  }
   const int th = key < 0 ? -key : key;
   auto it = tiles.find(key);
   if (it == tiles.end()) {

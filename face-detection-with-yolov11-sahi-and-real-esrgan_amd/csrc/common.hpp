@@ -142,7 +142,18 @@ struct Level {
   int64_t actual_px() const { return capacity() ? act_px : real_px; }
   int actual_n() const { return capacity() ? act_n : n; }
   // *n_launch: tiles to launch (capacity mode: the table capacity); *d_count: device count of real tiles (capacity mode) or nullptr
-  const int4* tile_table(int th, int* n_launch, const int** d_count, hipStream_t st);
+  // gate != nullptr (int[n], nonzero = image active, written on the device): the GATED table of that height — the entries of the active images,
+  // compacted on the device in their original order, with their count in device memory (*d_count); *n_launch stays the full table's size, the
+  // kernels bound on the count like on a capacity-mode level. One gate per level. A gated table is compacted when it is created and from then on
+  // by compact_gated(), which the owner runs once per run after the gate has been written and before the first conv that walks such a table.
+  const int4* tile_table(int th, int* n_launch, const int** d_count, hipStream_t st, const int* gate = nullptr);
+  std::map<int, TileTab> gated;   // by tile height; cap = entries of the full table
+  const int* gate_active = nullptr;
+  // the compaction launch (launch_gate_compact, det_post.hpp): set by the owner of the gate before the first gated table is asked for, so that this
+  // file needs no device code: dst = the entries of `src` whose image is active, in their order; *d_count = how many
+  typedef void (*GateCompactFn)(const int4* src, int n_entries, const int4* tab, int n_img, int th, const int* active, int4* dst, int* d_count, hipStream_t st);
+  GateCompactFn gate_compact = nullptr;
+  void compact_gated(hipStream_t st);
   // the same tiles in the PACKED form of conv_trunk.hip, everything a work item needs in one 16-byte load:
   //   {first pixel of the image, y0 | x0 << 16, h | w << 16, tile columns | tile rows << 16 of the image}   (kept under key -th)
   const int4* tile_table_packed(int th, int* n_launch, const int** d_count, hipStream_t st);

@@ -59,6 +59,7 @@ struct ConvArgs {
   int st_W;                          // frame width
   long long st_bytes;                // frame size in bytes, rounded up to whole dwords (range check of the loader's dword reads)
   float st_scale;                    // 1 / (power of two the packed stem weights were multiplied by)
+  const int* gate;                   // ConvOp::gate: the 3x3 launchers pick the gated tile table (no 3x3 kernel reads it); the 1x1 kernels read it per fragment (frag_img)
 };
 
 // (logical workgroup id, number of live workgroups) for a tile kernel; live == 0: this workgroup has nothing to do

@@ -436,7 +436,7 @@ template <int S, int WM, int WN, int MI, int NIW> struct K3Cfg {
   }
   static void launch(ConvArgs& a, Level* out_lvl, hipStream_t st) {
     int n_tiles = 0;
-    a.tiles = out_lvl->tile_table(G::TH, &n_tiles, &a.n_tiles_dev, st);
+    a.tiles = out_lvl->tile_table(G::TH, &n_tiles, &a.n_tiles_dev, st, a.gate);
     if (n_tiles == 0) return;
     a.ntiles_host = n_tiles;
     a.n_nblk = (a.ntiles32 + G::NTB - 1) / G::NTB;

@@ -204,6 +204,18 @@ __global__ void __launch_bounds__(256, (Geo<T, KS, STRIDE, WM, WN, MI, NIW, KC>:
   float f_ts[G::FR], f_ti[G::FR];
 #pragma unroll
   for (int f = 0; f < G::FR; ++f) { f_img[f] = 0; f_end[f] = 0; f_ts[f] = 1.f; f_ti[f] = 1.f; }
+  // gate (ConvArgs::gate, 1x1 only): a fragment whose image is inactive is neither read (its loads go out of range: zeros, no memory traffic)
+  // nor stored nor counted in a max-|value| slot
+  bool f_on[G::FR];
+#pragma unroll
+  for (int f = 0; f < G::FR; ++f) f_on[f] = true;
+  if constexpr (KS == 1) {
+    if (a.gate) {
+      const int nf = (int)(a.total_px >> 5), fb = __builtin_amdgcn_readfirstlane((int)(in_base >> 5));
+#pragma unroll
+      for (int f = 0; f < G::FR; ++f) f_on[f] = sload(a.gate, sload(a.frag_img, 2 * min(fb + f, nf - 1))) != 0;
+    }
+  }
   if constexpr (SPLIT) {
     if (a.amax_in && KS == 3) split_scales(amax_in_bits_s(a, img3), &tscale, &tinv);
     if (a.amax_in && KS == 1 && !a.amax_img) split_scales(amax_in_bits_s(a, 0), &tscale, &tinv);
@@ -245,6 +257,8 @@ __global__ void __launch_bounds__(256, (Geo<T, KS, STRIDE, WM, WN, MI, NIW, KC>:
       if (KS == 1) {
         rel = hp;
         ok = in_base + hp < a.total_px;
+#pragma unroll
+        for (int f = 0; f < G::FR; ++f) if ((hp >> 5) == f && !f_on[f]) ok = false;
       } else {
         const int hy = hp / HW, hx = hp - hy * HW;
         const int iy = iy0 + hy, ix = ix0 + hx;
@@ -516,6 +530,12 @@ __global__ void __launch_bounds__(256, (Geo<T, KS, STRIDE, WM, WN, MI, NIW, KC>:
         for (int f = 0; f < G::FR; ++f)
           if (fw == f) { img_f[mi] = f_img[f]; real_end[mi] = f_end[f]; tinv_f[mi] = f_ti[f]; }
       }
+    }
+    if constexpr (KS == 1) {
+      const int fw = __builtin_amdgcn_readfirstlane(wm * MI + mi);
+#pragma unroll
+      for (int f = 0; f < G::FR; ++f)
+        if (fw == f && !f_on[f]) real_end[mi] = 0;
     }
   }
 
@@ -811,7 +831,7 @@ template <typename T, int KS, int STRIDE, int WM, int WN, int MI, int NIW, int K
       if (KS == 1) {
         n_tiles = (int)((a.total_px + BLOCK_PX - 1) / BLOCK_PX);
       } else {
-        a.tiles = out_lvl->tile_table(G::TH, &n_tiles, &a.n_tiles_dev, st);
+        a.tiles = out_lvl->tile_table(G::TH, &n_tiles, &a.n_tiles_dev, st, a.gate);
       }
       a.n_nblk = (a.ntiles32 * 32 + BLOCK_N - 1) / BLOCK_N;
       const int grid = n_tiles * a.n_nblk;
@@ -1091,6 +1111,13 @@ ConvArgs make_conv_args(const ConvOp& op) {
     FFP_CHECK(!op.has_up2 || (op.in.amax != nullptr) == (op.up2.amax != nullptr), FFP_ERR_STATE, "conv %s: both sources need a max-|value| slot", pc.name.c_str());
   }
   a.ntiles_host = 0;
+  // 3x3: the launcher picks the level's gated tile table. 1x1: the kernels look the image of a 32-pixel fragment up like the per-image exponent
+  // slots do (split plans with one slot per buffer, FFP_AMAX_PER_BUFFER=1, have no such table in conv_pw: their 1x1 convs run ungated)
+  a.gate = op.gate;
+  if (pc.k == 1 && op.gate) {
+    if (pc.split && !a.amax_img) a.gate = nullptr;
+    else a.frag_img = op.out.lvl->frag_img();
+  }
   a.dbg = op.dbg;
   a.force_shape = op.force_shape;
   a.zeros = zero_block();

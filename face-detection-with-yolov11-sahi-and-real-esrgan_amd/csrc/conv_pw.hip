@@ -146,15 +146,29 @@ __global__ void __launch_bounds__((NW + (ST ? 1 : 0)) * 64, 2) conv_pw_kernel(co
 
   // ring slot = one 128-byte line per pixel = k-groups 2*pr and 2*pr + 1: this lane's 2 x 32 bytes of it
   uint4 raw[RP][MI][4];
-  auto issue = [&](uint4 (&q)[MI][4], const Span& sp, const unsigned (&vo)[MI], int pr) {
+  // gate (ConvArgs::gate): a fragment whose image is inactive is neither read (its loads go out of range: zeros, no memory traffic) nor stored
+  // nor counted in a max-|value| slot. on_c / on_n / on_nn: wave-uniform, the fragments of this block, the next one and the one after it.
+  const int nfrag = (int)(a.total_px >> 5);
+  auto frag_of = [&](int pbx, int mi) { return 2 * min((int)(((long long)pbx * BPX) >> 5) + wave * MI + mi, nfrag - 1); };
+  bool on_c[MI], on_n[MI], on_nn[MI];
+#pragma unroll
+  for (int mi = 0; mi < MI; ++mi) {
+    on_c[mi] = on_n[mi] = on_nn[mi] = true;
+    if (a.gate) {
+      on_c[mi] = sload(a.gate, sload(a.frag_img, frag_of(pb_begin, mi))) != 0;
+      on_n[mi] = sload(a.gate, sload(a.frag_img, frag_of(after(pb_begin, 1), mi))) != 0;
+    }
+  }
+  auto issue = [&](uint4 (&q)[MI][4], const Span& sp, const unsigned (&vo)[MI], int pr, bool next_blk) {
     const auto rs = rsrc(sp);
     const int so = pr * 128;
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi) {
-      q[mi][0] = bl(rs, vo[mi], so);
-      q[mi][1] = bl(rs, vo[mi] + 16, so);
-      q[mi][2] = bl(rs, vo[mi] + 64, so);
-      q[mi][3] = bl(rs, vo[mi] + 80, so);
+      const unsigned v = (next_blk ? on_n[mi] : on_c[mi]) ? vo[mi] : PW_OOB;
+      q[mi][0] = bl(rs, v, so);
+      q[mi][1] = bl(rs, v + 16, so);
+      q[mi][2] = bl(rs, v + 64, so);
+      q[mi][3] = bl(rs, v + 80, so);
     }
   };
   // virtual concat [nearest_x2(coarser view) | rest] (ConvOp::has_up2): input channels [0, up_c) of a pixel live in the coarser
@@ -170,7 +184,7 @@ __global__ void __launch_bounds__((NW + (ST ? 1 : 0)) * 64, 2) conv_pw_kernel(co
     }
   };
   // line-load `pr` of a block whose own span / map offsets are (sp_in, vu): pick the side
-  auto fetch = [&](uint4 (&q)[MI][4], const Span& sp_in, const unsigned (&vu)[MI], int pr) {
+  auto fetch = [&](uint4 (&q)[MI][4], const Span& sp_in, const unsigned (&vu)[MI], int pr, bool next_blk) {
     if constexpr (UP) {
       const bool up = pr * 32 < a.up_c;
       Span sp;
@@ -179,9 +193,9 @@ __global__ void __launch_bounds__((NW + (ST ? 1 : 0)) * 64, 2) conv_pw_kernel(co
       unsigned vo[MI];
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi) vo[mi] = up ? vu[mi] : voff[mi];
-      issue(q, sp, vo, pr);
+      issue(q, sp, vo, pr, next_blk);
     } else {
-      issue(q, sp_in, voff, pr);
+      issue(q, sp_in, voff, pr, next_blk);
     }
   };
   auto split8 = [&](const uint4& r0, const uint4& r1, float ts, f16x8& hi, f16x8& lo) {
@@ -202,13 +216,11 @@ __global__ void __launch_bounds__((NW + (ST ? 1 : 0)) * 64, 2) conv_pw_kernel(co
     load_vup(pb, vup_cur);
   }
 #pragma unroll
-  for (int r = 0; r < RP; ++r) fetch(raw[r], rs_cur, vup_cur, r);
+  for (int r = 0; r < RP; ++r) fetch(raw[r], rs_cur, vup_cur, r, false);
   __syncthreads();                             // weights visible; from here on the waves run on their own
 
   // per-image exponent slots: {image, end of its real pixels} of this wave's fragments and the input's max-|value| bits, fetched through
   // the scalar cache TWO blocks (table) / ONE block (slot) ahead, so that the chain table -> slot never sits on the critical path
-  const int nfrag = (int)(a.total_px >> 5);
-  auto frag_of = [&](int pbx, int mi) { return 2 * min((int)(((long long)pbx * BPX) >> 5) + wave * MI + mi, nfrag - 1); };
   int im_n[MI], re_n[MI], im_nn[MI], re_nn[MI];
   unsigned am_n[MI];
 #pragma unroll
@@ -253,7 +265,9 @@ __global__ void __launch_bounds__((NW + (ST ? 1 : 0)) * 64, 2) conv_pw_kernel(co
         am_n[mi] = amax_in_bits_s(a, im_n[mi]);
         im_nn[mi] = sload(a.frag_img, frag_of(after(pb, 2), mi));
         re_nn[mi] = sload(a.frag_img, frag_of(after(pb, 2), mi) + 1);
+        if (a.gate) on_nn[mi] = sload(a.gate, im_nn[mi]) != 0;
       }
+      if (!on_c[mi]) rend_f[mi] = 0;
     }
     const Span rs_next = block_span(a.in, after(pb, 1), a.in_cs, a.in_coff);
     if constexpr (UP) load_vup(after(pb, 1), vup_next);
@@ -296,9 +310,9 @@ __global__ void __launch_bounds__((NW + (ST ? 1 : 0)) * 64, 2) conv_pw_kernel(co
                 unsigned vu[MI];
 #pragma unroll
                 for (int mi = 0; mi < MI; ++mi) vu[mi] = more ? vup_cur[mi] : vup_next[mi];
-                fetch(raw[r], rs_f, vu, prb + r);
+                fetch(raw[r], rs_f, vu, prb + r, !more);
               } else {
-                fetch(raw[r], rs_f, vup_cur, prb + r);
+                fetch(raw[r], rs_f, vup_cur, prb + r, !more);
               }
               __builtin_amdgcn_sched_barrier(0);
             }
@@ -349,7 +363,7 @@ __global__ void __launch_bounds__((NW + (ST ? 1 : 0)) * 64, 2) conv_pw_kernel(co
       const long long px0 = (long long)pb * BPX + (wave * MI + mi) * 32 + 4 * hh;
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt) {
-        const unsigned vo = vout[mi] + cbyte[nt];
+        const unsigned vo = on_c[mi] ? vout[mi] + cbyte[nt] : PW_OOB;
         const float osc = osc_n[nt] * ti_f[mi];
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
@@ -375,6 +389,8 @@ __global__ void __launch_bounds__((NW + (ST ? 1 : 0)) * 64, 2) conv_pw_kernel(co
     }
 #endif
     rs_cur = rs_next;
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi) { on_c[mi] = on_n[mi]; on_n[mi] = on_nn[mi]; }
     if constexpr (UP) {
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi) vup_cur[mi] = vup_next[mi];

@@ -134,6 +134,7 @@ int conv_tune(const ConvOp& op, hipStream_t st) {
   auto time_shape = [&](int shape, int iters) {
     ConvOp o = op;
     o.force_shape = shape;
+    o.gate = nullptr;                      // shapes are chosen on the whole batch
     FFP_HIP(hipEventRecord(e0, st));
     for (int i = 0; i < iters; ++i) launch_conv(o, st);
     FFP_HIP(hipEventRecord(e1, st));

@@ -307,7 +307,7 @@ template <int NIW, int NST> struct RowsCfg {
   }
   static void launch(ConvArgs& a, Level* out_lvl, hipStream_t st) {
     int n_tiles = 0;
-    a.tiles = out_lvl->tile_table(16, &n_tiles, &a.n_tiles_dev, st);
+    a.tiles = out_lvl->tile_table(16, &n_tiles, &a.n_tiles_dev, st, a.gate);
     if (n_tiles == 0) return;
     a.n_nblk = a.ntiles32 / NIW;
     hipLaunchKernelGGL((conv_rows_kernel<NIW, NST>), dim3(n_tiles * a.n_nblk), dim3(256), LDS, st, a);

@@ -399,7 +399,7 @@ void launch_conv_rows16(ConvArgs& a, int shape, const PackedConv& pc, Level* out
   static_assert(G::LDS <= 80 * 1024, "rows16 kernel: two workgroups per CU");
   a.wpk = pc.w16.p;
   int n_tiles = 0;
-  a.tiles = out_lvl->tile_table(16, &n_tiles, &a.n_tiles_dev, st);     // n_tiles: the launch extent (capacity-mode levels: the capacity)
+  a.tiles = out_lvl->tile_table(16, &n_tiles, &a.n_tiles_dev, st, a.gate);     // n_tiles: the launch extent (capacity-mode levels: the capacity)
   if (n_tiles == 0) return;
   a.ntiles_host = n_tiles;
   a.n_nblk = a.ntiles32;

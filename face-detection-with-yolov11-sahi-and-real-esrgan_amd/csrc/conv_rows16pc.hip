@@ -229,7 +229,7 @@ void launch_conv_rows16pc(ConvArgs& a, const PackedConv& pc, Level* out_lvl, hip
   using G = PCGeo;
   a.wpk = pc.w16.p;
   int n_tiles = 0;
-  a.tiles = out_lvl->tile_table(16, &n_tiles, &a.n_tiles_dev, st);
+  a.tiles = out_lvl->tile_table(16, &n_tiles, &a.n_tiles_dev, st, a.gate);
   if (n_tiles == 0) return;
   a.ntiles_host = n_tiles;
   a.n_nblk = a.ntiles32;

@@ -49,6 +49,50 @@ __device__ __forceinline__ float dfl_expect(const float* p) {
   return acc;
 }
 
+// the anchor's best class logit (first of equals) and its index
+__device__ __forceinline__ float best_class(const float* r, int nc, int* bj) {
+  float best = -INFINITY;
+  *bj = 0;
+  for (int c = 0; c < nc; ++c) { const float v = r[64 + c]; if (v > best) { best = v; *bj = c; } }
+  return best;
+}
+
+// one thread per anchor, behind the class towers: active[img] = 1 when the anchor passes decode_kernel's own test (same best_class, sigmoidf_ and
+// sc > conf). An item no anchor of which passes gets nothing out of its box and keypoint towers; the plan then skips them (yolo11.cpp). conf is read
+// from device memory so that a captured launch honours the value of every call.
+__global__ void gate_clear_kernel(int* __restrict__ active, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) active[i] = 0;
+}
+
+__global__ void gate_kernel(const DecodeArgs a, const float* __restrict__ conf, int* __restrict__ active) {
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= a.total_anchors) return;
+  const int img = upper_img(a.anchor_off, a.n_img, g);
+  const AnchorPos ap = locate(a, img, g - a.anchor_off[img]);
+  int bj;
+  const float sc = sigmoidf_(best_class(a.head[ap.lvl] + (size_t)ap.px * a.head_cs, a.nc, &bj));
+  if (sc > *conf) active[img] = 1;
+}
+
+// one thread per entry of a tile table: entries of active images move up by the tiles of the inactive images in front of them
+__global__ void gate_compact_kernel(const int4* __restrict__ src, int n_entries, const int4* __restrict__ tab, int n_img, int th,
+                                    const int* __restrict__ active, int4* __restrict__ dst, int* __restrict__ d_count) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n_entries) return;
+  const int4 t = src[e];
+  int skipped = 0, kept = 0;                  // tiles of inactive images before this entry's image; tiles of active images in the whole table
+  for (int i = 0; i < n_img; ++i) {
+    const int4 im = tab[i];
+    const int cnt = ((im.y + th - 1) / th) * ((im.z + 15) / 16);
+    const bool on = active[i] != 0;
+    if (!on && i < t.x) skipped += cnt;
+    if (on) kept += cnt;
+  }
+  if (active[t.x] != 0) dst[e - skipped] = t;
+  if (e == 0) *d_count = kept;
+}
+
 // one thread per anchor: box (xyxy, net-input pixels), best class score/index; score = -1 when not > conf
 __global__ void decode_kernel(const DecodeArgs a, float conf, float4* __restrict__ boxes, float* __restrict__ scores,
                               int* __restrict__ classes) {
@@ -58,9 +102,8 @@ __global__ void decode_kernel(const DecodeArgs a, float conf, float4* __restrict
   const AnchorPos ap = locate(a, img, g - a.anchor_off[img]);
   const float* r = a.head[ap.lvl] + (size_t)ap.px * a.head_cs;
   const float stride = (float)(8 << ap.lvl);
-  float best = -INFINITY; int bj = 0;
-  for (int c = 0; c < a.nc; ++c) { const float v = r[64 + c]; if (v > best) { best = v; bj = c; } }
-  const float sc = sigmoidf_(best);
+  int bj;
+  const float sc = sigmoidf_(best_class(r, a.nc, &bj));
   float out_s = -1.f;
   float4 bx = make_float4(0.f, 0.f, 0.f, 0.f);
   if (sc > conf) {
@@ -276,6 +319,20 @@ __global__ void truncate_shift_kernel(float* __restrict__ dets, const int* __res
 void launch_decode(const DecodeArgs& a, float conf, float4* boxes, float* scores, int* classes, hipStream_t st) {
   if (a.total_anchors == 0) return;
   hipLaunchKernelGGL(decode_kernel, dim3((a.total_anchors + 255) / 256), dim3(256), 0, st, a, conf, boxes, scores, classes);
+  FFP_HIP(hipGetLastError());
+}
+
+void launch_det_gate(const DecodeArgs& a, const float* conf, int* active, hipStream_t st) {
+  if (a.total_anchors == 0) return;
+  hipLaunchKernelGGL(gate_clear_kernel, dim3((a.n_img + 255) / 256), dim3(256), 0, st, active, a.n_img);      // every run starts with no item active
+  FFP_HIP(hipGetLastError());
+  hipLaunchKernelGGL(gate_kernel, dim3((a.total_anchors + 255) / 256), dim3(256), 0, st, a, conf, active);
+  FFP_HIP(hipGetLastError());
+}
+
+void launch_gate_compact(const int4* src, int n_entries, const int4* tab, int n_img, int th, const int* active, int4* dst, int* d_count, hipStream_t st) {
+  FFP_CHECK(n_entries > 0 && n_img > 0 && th > 0, FFP_ERR_ARG, "gate_compact: empty table");
+  hipLaunchKernelGGL(gate_compact_kernel, dim3((n_entries + 255) / 256), dim3(256), 0, st, src, n_entries, tab, n_img, th, active, dst, d_count);
   FFP_HIP(hipGetLastError());
 }
 

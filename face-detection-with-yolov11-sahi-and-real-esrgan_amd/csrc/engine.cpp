@@ -32,13 +32,14 @@ int ConvProfile::open(hipStream_t st) {
   return slot;
 }
 
-void ConvProfile::close(int slot, hipStream_t st, const std::string& variant, double flops, const std::string& name, double bytes) {
+void ConvProfile::close(int slot, hipStream_t st, const std::string& variant, double flops, const std::string& name, double bytes, const double* share) {
   FFP_HIP(hipEventRecord(ev[slot].second, st));
-  pending.push_back({slot, variant, flops, name, bytes});
+  pending.push_back({slot, variant, flops, name, bytes, share});
 }
 
 void ConvProfile::collect() {
-  for (const Pending& p : pending) {
+  for (Pending& p : pending) {
+    if (p.share) { p.flops *= *p.share; p.bytes *= *p.share; }
     float ms = 0.f;
     FFP_HIP(hipEventElapsedTime(&ms, ev[p.ev].first, ev[p.ev].second));
     Entry& e = table[p.variant];
@@ -371,7 +372,7 @@ void Plan::execute(hipStream_t st, ConvProfile* prof) {
       if (s.is_conv) {
         const int slot = prof->open(st);
         s.run(st);
-        prof->close(slot, st, s.variant, s.actual_flops(), s.name, s.actual_bytes());
+        prof->close(slot, st, s.variant, s.actual_flops(), s.name, s.actual_bytes(), s.share);
       } else {
         s.run(st);
       }

@@ -16,14 +16,16 @@ struct ConvProfile {
   struct Entry { std::string variant; double flops = 0; double ms = 0; int launches = 0; double bytes = 0; };
   bool enabled = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;   // recycled pool
-  struct Pending { int ev; std::string variant; double flops; std::string name; double bytes; };
+  struct Pending { int ev; std::string variant; double flops; std::string name; double bytes; const double* share; };
   std::vector<Entry> detail;                      // one entry per launch of the last call (variant = "<variant> <layer name>")
   std::vector<Pending> pending;
   std::map<std::string, Entry> table;
   ~ConvProfile();
   void begin();                                  // clear the table, start collecting
   int open(hipStream_t st);                      // record a start event, returns slot
-  void close(int slot, hipStream_t st, const std::string& variant, double flops, const std::string& name, double bytes = 0);
+  // share (may be null): read in collect() — the part of the launch's work that was done (gated convs: the active share of the level's pixels,
+  // known only once the stream has drained); flops and bytes are scaled by it, so the per-layer rates describe the work done
+  void close(int slot, hipStream_t st, const std::string& variant, double flops, const std::string& name, double bytes = 0, const double* share = nullptr);
   void collect();                                // after the stream has drained
 };
 
@@ -43,6 +45,7 @@ struct Step {
   double actual_bytes() const;
   std::string variant, name;
   double flops = 0;
+  const double* share = nullptr;     // gated convs: where the owner puts the active share of the level's pixels after a profiled run (ConvProfile::close)
   // lanes: steps of different lanes have no data dependency between a fork and the matching join and may overlap on the device
   // (independent branches of the captured graph). kind 1 = fork: `lane` starts after everything lane 0 has issued so far;
   // kind 2 = join: lane 0 continues after everything `lane` has issued.

@@ -27,6 +27,10 @@ struct ConvOp {
   const int* up2_map = nullptr;   // device: Level::up2_map of in.lvl over up2.lvl
   double flops = 0;   // 2*MAC, algorithmic (unpadded)
   int dbg = 0;        // tuning only: phase-skip mask (see ConvArgs::dbg)
+  // device int[out.lvl->n], nonzero = image active: the conv neither reads nor writes anything of an inactive image and leaves its max-|value|
+  // slot alone. 3x3 convs walk the level's gated tile table (Level::tile_table); 1x1 convs (stride 1, levels aligned to 32 pixels) turn the
+  // loads and stores of an inactive image's 32-pixel fragments into out-of-range buffer accesses. nullptr: every image. The tuner times with nullptr.
+  const int* gate = nullptr;
   int force_shape = -1;   // tuning and tests: a ConvShape number (conv_route.hpp) pins the kernel and its workgroup shape; SHAPE_AUTO (-1): conv_route decides
 };
 void launch_conv(const ConvOp& op, hipStream_t st);      // on the kernel conv_route (conv_route.hpp) picks

@@ -14,6 +14,8 @@ namespace {
 int make_div8(double x) { return (int)std::ceil(x / 8.0) * 8; }
 }  // namespace
 
+static DecodeArgs decode_args(const DetPlan& P, int nc, int nkpt);
+
 void letterbox_geometry(int h, int w, int imgsz, int32_t* o) {
   // Ultralytics LetterBox(new_shape=imgsz, auto=True, scaleup=True, center=True, stride=32); Python round() is
   // round-half-even, as is nearbyint() under the default rounding mode.
@@ -83,7 +85,7 @@ void DetEngine::build_plan(DetPlan& P, const std::vector<int>& hs, const std::ve
   // round 2's one slot per buffer, A/B aid); the 1x1 kernels find a fragment's image through Level::frag_img, hence the 32-pixel alignment
   static const bool per_buffer = [] { const char* e = getenv("FFP_AMAX_PER_BUFFER"); return e && e[0] == '1'; }();
   P.per_image_amax = split_ && !per_buffer;
-  P.px_align = P.per_image_amax ? 32 : 1;
+  P.px_align = (P.per_image_amax || P.gate) ? 32 : 1;        // the gated 1x1 convs find a fragment's image the same way
   for (int l = 0; l < 6; ++l) {
     std::vector<int> h(n), w(n);
     for (int i = 0; i < n; ++i) { h[i] = hs[i] >> l; w[i] = ws[i] >> l; }
@@ -99,14 +101,18 @@ void DetEngine::build_plan(DetPlan& P, const std::vector<int>& hs, const std::ve
   const DType T = dt_;
 
   static const bool fold_up = !getenv("FFP_NO_UPFOLD");
-  auto cv = [&](const std::string& name, const TView& in, const TView& out, int stride, int act, const TView* res = nullptr, const TView* up2 = nullptr) {
+  auto cv = [&](const std::string& name, const TView& in, const TView& out, int stride, int act, const TView* res = nullptr, const TView* up2 = nullptr,
+                const int* gate = nullptr) {
     ConvOp o;
-    o.pc = conv(name); o.in = in; o.out = out; o.stride = stride; o.act = act;
+    o.pc = conv(name); o.in = in; o.out = out; o.stride = stride; o.act = act; o.gate = gate;
+    const double* share = nullptr;
+    for (int l = 0; l < 3; ++l) if (gate && out.lvl == P.L[3 + l]) share = &P.gate_share[l];
     if (res) { o.has_res1 = true; o.res1 = *res; o.s1 = 1.f; }
     if (up2) { o.has_up2 = true; o.up2 = *up2; o.up2_c = up2->C; o.up2_map = in.lvl->up2_map(up2->lvl, st_); }
     FFP_CHECK(o.pc->cin == in.C && o.pc->cout == out.C, FFP_ERR_WEIGHTS, "%s: weights are %d->%d, graph expects %d->%d",
               name.c_str(), o.pc->cin, o.pc->cout, in.C, out.C);
     P.add_conv(o);
+    P.steps.back().share = share;
   };
   auto dw = [&](const std::string& name, const TView& in, const TView& out, int act) {
     DwConvOp o;
@@ -292,69 +298,99 @@ void DetEngine::build_plan(DetPlan& P, const std::vector<int>& hs, const std::ve
   const int c2 = std::max(std::max(16, chs[0] / 4), 64);
   const int c3 = std::max(chs[0], std::min(nc_, 100));
   const int c4 = std::max(chs[0] / 4, nk);
-  // One head level = three independent towers (box, class, keypoints) over one feature map. Each tower is a lane of its own,
-  // forked as soon as the map exists: level 0 (the large one, 1.2 of the head's 2.2 ms per 2-frame group) overlaps the rest of the
-  // neck, whose stride-16/32 launches (and the towers of levels 1 and 2) leave most of the chip idle on their own.
-  auto head_level = [&](int l, const TView& x) {
+  // One head level = three independent towers (box, class, keypoints) over one feature map. decode reads an anchor's box values only when
+  // its best class score passes conf, and NMS reads keypoints only of boxes it keeps: an item (slice) without any such anchor gets nothing
+  // out of its box and keypoint towers. So the class tower of a level is forked as soon as its map exists, the gate (det_post.hip) marks
+  // the items with a passing anchor once all three class towers are done, and the 3x3 convs of the box and keypoint towers of all levels
+  // then walk tile tables that hold the active items only (ConvOp::gate). Exact: with per-image exponent slots an item's bits do not
+  // depend on its batch mates. Each tower is a lane of its own where lanes are on.
+  const std::string hp = "model.23";
+  const int lm = P.lane_mode();
+  auto tower_lane = [&](int l, int k) { return lm == 1 ? 3 * l + k : lm == 2 ? 3 * l + 1 : (lm == 3 && l == 0) ? 1 : 0; };
+  const int* gate = nullptr;
+  if (P.gate) {
+    P.d_active.alloc(sizeof(int) * n);
+    P.d_conf.alloc(sizeof(float));
+    gate = P.d_active.as<int>();
+    for (int l = 3; l < 6; ++l) P.L[l]->gate_compact = &launch_gate_compact;
+  }
+  auto class_tower = [&](int l, const TView& x) {
     Level* lv = P.L[3 + l];
-    Plan::Scope tmp(P);                                 // the towers' temporaries (with lanes on: free once every tower has been joined)
-    P.head[l] = P.alloc(lv, head_cs, F32);
-    tmp.keep(P.head[l]);                                // decode reads it after the plan
-    const std::string p = "model.23";
     const std::string ls = std::to_string(l);
-    TView t1 = P.alloc(lv, c2, T), t2 = P.alloc(lv, c2, T);
-    const int lm = P.lane_mode();
-    auto tower_lane = [&](int k) { return lm == 1 ? 3 * l + k : lm == 2 ? 3 * l + 1 : (lm == 3 && l == 0) ? 1 : 0; };
-    for (int k = 1; k <= 3; ++k) if (lm == 1 || k == 1) P.fork(tower_lane(k));
-    P.cur_lane = tower_lane(1);
-    cv(p + ".cv2." + ls + ".0.conv", x, t1, 1, ACT_SILU);
-    cv(p + ".cv2." + ls + ".1.conv", t1, t2, 1, ACT_SILU);
-    cv(p + ".cv2." + ls + ".2", t2, P.head[l].slice(0, 64), 1, ACT_NONE);
-    P.release(t1);
-    P.release(t2);
+    P.head[l] = P.alloc(lv, head_cs, F32);              // never released: decode reads it after the plan
+    P.fork(tower_lane(l, 2));
     TView d1 = P.alloc(lv, chs[l], T), e1 = P.alloc(lv, c3, T), d2 = P.alloc(lv, c3, T), e2 = P.alloc(lv, c3, T);
-    P.cur_lane = tower_lane(2);
-    dw(p + ".cv3." + ls + ".0.0.conv", x, d1, ACT_SILU);
-    cv(p + ".cv3." + ls + ".0.1.conv", d1, e1, 1, ACT_SILU);
-    dw(p + ".cv3." + ls + ".1.0.conv", e1, d2, ACT_SILU);
-    cv(p + ".cv3." + ls + ".1.1.conv", d2, e2, 1, ACT_SILU);
-    cv(p + ".cv3." + ls + ".2", e2, P.head[l].slice(64, nc_), 1, ACT_NONE);
+    P.cur_lane = tower_lane(l, 2);
+    dw(hp + ".cv3." + ls + ".0.0.conv", x, d1, ACT_SILU);
+    cv(hp + ".cv3." + ls + ".0.1.conv", d1, e1, 1, ACT_SILU);
+    dw(hp + ".cv3." + ls + ".1.0.conv", e1, d2, ACT_SILU);
+    cv(hp + ".cv3." + ls + ".1.1.conv", d2, e2, 1, ACT_SILU);
+    cv(hp + ".cv3." + ls + ".2", e2, P.head[l].slice(64, nc_), 1, ACT_NONE);
     P.release(d1);
     P.release(e1);
     P.release(d2);
     P.release(e2);
+    P.cur_lane = 0;
+  };
+  // the 3x3 convs walk the gated tile tables; the closing 1x1 leaves out the 32-pixel fragments of inactive items, so it reads nothing that
+  // was not written in this run. The head records of a skipped item keep whatever an earlier run left there; nobody reads them.
+  auto box_kpt_towers = [&](int l, const TView& x) {
+    Level* lv = P.L[3 + l];
+    const std::string ls = std::to_string(l);
+    TView t1 = P.alloc(lv, c2, T), t2 = P.alloc(lv, c2, T);
+    P.cur_lane = tower_lane(l, 1);
+    cv(hp + ".cv2." + ls + ".0.conv", x, t1, 1, ACT_SILU, nullptr, nullptr, gate);
+    cv(hp + ".cv2." + ls + ".1.conv", t1, t2, 1, ACT_SILU, nullptr, nullptr, gate);
+    cv(hp + ".cv2." + ls + ".2", t2, P.head[l].slice(0, 64), 1, ACT_NONE, nullptr, nullptr, gate);
+    P.release(t1);
+    P.release(t2);
     if (nk > 0) {
       TView k1 = P.alloc(lv, c4, T), k2 = P.alloc(lv, c4, T);
-      P.cur_lane = tower_lane(3);
-      cv(p + ".cv4." + ls + ".0.conv", x, k1, 1, ACT_SILU);
-      cv(p + ".cv4." + ls + ".1.conv", k1, k2, 1, ACT_SILU);
-      cv(p + ".cv4." + ls + ".2", k2, P.head[l].slice(64 + nc_, nk), 1, ACT_NONE);
+      P.cur_lane = tower_lane(l, 3);
+      cv(hp + ".cv4." + ls + ".0.conv", x, k1, 1, ACT_SILU, nullptr, nullptr, gate);
+      cv(hp + ".cv4." + ls + ".1.conv", k1, k2, 1, ACT_SILU, nullptr, nullptr, gate);
+      cv(hp + ".cv4." + ls + ".2", k2, P.head[l].slice(64 + nc_, nk), 1, ACT_NONE, nullptr, nullptr, gate);
+      P.release(k1);
+      P.release(k2);
     }
     P.cur_lane = 0;
   };
 
-
   TView x16 = P.alloc(P.L[3], c256, T);
   c3k2("model.16", cat15, x16, c256, false, 0.5, fold15 ? &x13 : nullptr);
   P.release(cat15);
-  head_level(0, x16);
+  class_tower(0, x16);
   cv("model.17.conv", x16, cat18.slice(0, c256), 2, ACT_SILU);
-  P.release(x16);
   TView x19 = P.alloc(P.L[4], c512, T);
   c3k2("model.19", cat18, x19, c512, false, 0.5);
   P.release(cat18);
-  head_level(1, x19);
+  class_tower(1, x19);
   cv("model.20.conv", x19, cat21.slice(0, c512), 2, ACT_SILU);
-  P.release(x19);
   TView x22 = P.alloc(P.L[5], c1024, T);
   c3k2("model.22", cat21, x22, c1024, true, 0.5);
   P.release(cat21);
-  head_level(2, x22);
+  class_tower(2, x22);
+  for (int l = 0; l < 3; ++l) P.join(tower_lane(l, 2));
+  if (gate) {
+    DetPlan* pp = &P;
+    const int nc = nc_, nkpt = nkpt_;
+    P.add([pp, nc, nkpt](hipStream_t s) {
+      launch_det_gate(decode_args(*pp, nc, nkpt), pp->d_conf.as<float>(), pp->d_active.as<int>(), s);
+      for (int l = 3; l < 6; ++l) pp->L[l]->compact_gated(s);      // tables the first run's launchers created (they compact what they create)
+    });
+  }
+  // x16, x19 and x22 live until their towers have been issued
+  const TView* xs[3] = {&x16, &x19, &x22};
+  for (int l = 0; l < 3; ++l)
+    for (int k = 1; k <= 3; k += 2) if (lm == 1 || k == 1) P.fork(tower_lane(l, k));
+  for (int l = 0; l < 3; ++l) box_kpt_towers(l, *xs[l]);
+  P.release(x16);
+  P.release(x19);
   P.release(x22);
 
   // ---- Pose head: per level one fp32 record [64 DFL | nc | 3*nkpt] per pixel ---------------------------------------------
-  for (int k = 1; k <= 9; ++k)                      // lane 0 continues (decode, NMS) after every tower of every level
-    if (P.lane_mode() == 1 || (P.lane_mode() == 2 && k % 3 == 1) || (P.lane_mode() == 3 && k == 1)) P.join(k);
+  for (int l = 0; l < 3; ++l)                       // lane 0 continues (decode, NMS) after every tower of every level
+    for (int k = 1; k <= 3; k += 2) if (lm == 1 || k == 1) P.join(tower_lane(l, k));
 
   P.add_amax_reset(st_);      // first step of every run: max-|value| slots back to their static bounds / zero
 
@@ -428,6 +464,7 @@ DetPlan* DetEngine::plan_for(const std::vector<TileGeom>& g) {
     std::unique_ptr<DetPlan> p(new DetPlan());
     p->lanes = lanes_;
     p->reuse = reuse_;
+    p->gate = gate_;
     std::vector<int> hs, ws;
     for (const TileGeom& t : g) { hs.push_back(t.lb.net_h); ws.push_back(t.lb.net_w); }
     build_plan(*p, hs, ws);
@@ -467,7 +504,47 @@ size_t DetEngine::plan_bytes() const {
   return b;
 }
 
-DetPlan* DetEngine::prepare(const uint8_t* d_frame, int H, int W, int chan_order, const int32_t* tiles, int n_tiles, int imgsz) {
+int DetEngine::gate_env() {
+  static const int on = [] { const char* e = getenv("FFP_DET_GATE"); return e && e[0] == '0' && !e[1] ? 0 : 1; }();
+  return on;
+}
+
+void DetEngine::set_gate(bool on) {
+  if (on == gate_) return;
+  gate_ = on;
+  drop_plans();
+}
+
+// the gate's verdict of the run just issued, on its way to the host: valid once the caller has waited for the stream
+void DetEngine::fetch_active(DetPlan* P, int n_tiles) {
+  last_items_ = n_tiles;
+  last_gated_ = P->gate;
+  if (!P->gate) return;
+  h_active_.ensure(sizeof(int) * n_tiles);
+  FFP_HIP(hipMemcpyAsync(h_active_.p, P->d_active.p, sizeof(int) * n_tiles, hipMemcpyDeviceToHost, st_));
+}
+
+// after the stream has drained: per head level, the share of its pixels that belongs to active items
+void DetEngine::set_shares(DetPlan* P) const {
+  if (!P->gate) return;
+  const int* act = static_cast<const int*>(h_active_.p);
+  for (int l = 0; l < 3; ++l) {
+    const Level& lv = *P->L[3 + l];
+    double on = 0, all = 0;
+    for (int i = 0; i < lv.n; ++i) { const double px = (double)lv.h[i] * lv.w[i]; all += px; if (act[i]) on += px; }
+    P->gate_share[l] = all > 0 ? on / all : 1.0;
+  }
+}
+
+void DetEngine::last_active(int* active, int* items) const {
+  *items = last_items_;
+  *active = last_items_;
+  if (!last_gated_) return;
+  *active = 0;
+  for (int i = 0; i < last_items_; ++i) *active += static_cast<const int*>(h_active_.p)[i] != 0;
+}
+
+DetPlan* DetEngine::prepare(const uint8_t* d_frame, int H, int W, int chan_order, const int32_t* tiles, int n_tiles, int imgsz, float conf) {
   FFP_HIP(hipSetDevice(device_));
   geom_last_ = geometry(H, W, tiles, n_tiles, imgsz);
   DetPlan* P = plan_for(geom_last_);
@@ -476,6 +553,8 @@ DetPlan* DetEngine::prepare(const uint8_t* d_frame, int H, int W, int chan_order
   for (int i = 0; i < n_tiles; ++i) { lb[i] = geom_last_[i].lb; di[i] = geom_last_[i].di; }
   FFP_HIP(hipMemcpyAsync(P->d_lb.p, lb.data(), sizeof(LetterboxImg) * n_tiles, hipMemcpyHostToDevice, st_));
   FFP_HIP(hipMemcpyAsync(P->d_imgs.p, di.data(), sizeof(DetImg) * n_tiles, hipMemcpyHostToDevice, st_));
+  // the gate's threshold: uploaded here, outside the captured steps, so that a replayed graph honours the conf of every call
+  if (P->gate) FFP_HIP(hipMemcpyAsync(P->d_conf.p, &conf, sizeof(float), hipMemcpyHostToDevice, st_));
   FFP_HIP(hipStreamSynchronize(st_));   // lb/di are stack vectors
   FFP_HIP(hipEventRecord(ev_[0], st_));
   const int flip = chan_order == FFP_CHAN_AS_BGR ? 1 : 0;
@@ -514,14 +593,15 @@ static DecodeArgs decode_args(const DetPlan& P, int nc, int nkpt) {
 void DetEngine::infer_tiles_dev(const uint8_t* d_frame, int H, int W, int chan_order, const int32_t* tiles, int n_tiles, int imgsz,
                                 float conf, float iou, int max_det, int round_boxes, float* d_out_dets, int32_t* d_out_counts) {
   FFP_CHECK(max_det >= 1 && max_det <= 1024, FFP_ERR_ARG, "max_det %d outside [1,1024]", max_det);
-  DetPlan* P = prepare(d_frame, H, W, chan_order, tiles, n_tiles, imgsz);
+  DetPlan* P = prepare(d_frame, H, W, chan_order, tiles, n_tiles, imgsz, conf);
   const DecodeArgs a = decode_args(*P, nc_, nkpt_);
   launch_decode(a, conf, P->d_boxes.as<float4>(), P->d_scores.as<float>(), P->d_classes.as<int>(), st_);
   launch_nms(a, P->d_boxes.as<float4>(), P->d_scores.as<float>(), P->d_classes.as<int>(), P->d_cand.as<int>(),
              P->d_cscore.as<float>(), P->d_imgs.as<DetImg>(), iou, max_det, round_boxes, det_stride(), d_out_dets, d_out_counts, st_);
   FFP_HIP(hipEventRecord(ev_[3], st_));
+  fetch_active(P, n_tiles);
   FFP_HIP(hipStreamSynchronize(st_));
-  if (prof.enabled) prof.collect();
+  if (prof.enabled) { set_shares(P); prof.collect(); }
   FFP_HIP(hipEventElapsedTime(&last_ms[1], ev_[0], ev_[1]));
   FFP_HIP(hipEventElapsedTime(&last_ms[2], ev_[1], ev_[2]));
   FFP_HIP(hipEventElapsedTime(&last_ms[3], ev_[2], ev_[3]));
@@ -531,7 +611,7 @@ void DetEngine::infer_tiles_dev(const uint8_t* d_frame, int H, int W, int chan_o
 
 void DetEngine::forward_raw(const uint8_t* d_frame, int H, int W, int chan_order, const int32_t* tiles, int n_tiles, int imgsz,
                             float* out_raw, size_t out_cap, int32_t* out_anchor_counts) {
-  DetPlan* P = prepare(d_frame, H, W, chan_order, tiles, n_tiles, imgsz);
+  DetPlan* P = prepare(d_frame, H, W, chan_order, tiles, n_tiles, imgsz, -1.f);      // the raw output needs every anchor: sigmoid > -1, every item active
   const DecodeArgs a = decode_args(*P, nc_, nkpt_);
   const int no = 4 + nc_ + 3 * nkpt_;
   std::vector<long long> off(n_tiles);
@@ -547,8 +627,9 @@ void DetEngine::forward_raw(const uint8_t* d_frame, int H, int W, int chan_order
   FFP_HIP(hipMemcpyAsync(d_off.p, off.data(), sizeof(long long) * n_tiles, hipMemcpyHostToDevice, st_));
   launch_decode_raw(a, d_out.as<float>(), d_off.as<long long>(), st_);
   FFP_HIP(hipMemcpyAsync(out_raw, d_out.p, sizeof(float) * (size_t)tot, hipMemcpyDeviceToHost, st_));
+  fetch_active(P, n_tiles);
   FFP_HIP(hipStreamSynchronize(st_));
-  if (prof.enabled) prof.collect();
+  if (prof.enabled) { set_shares(P); prof.collect(); }
 }
 
 void DetEngine::truncate_shift_dev(float* d_dets, const int32_t* d_counts, int n_tiles, int max_det, int H, int W) {

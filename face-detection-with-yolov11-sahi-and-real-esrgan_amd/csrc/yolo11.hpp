@@ -19,6 +19,11 @@ struct DetPlan : Plan {
   bool fused_stem_conv = false;
   std::string stemconv_variant;
   DevBuf stem_w[2];         // the stem's MFMA fragments per channel order (RGB, BGR frames)
+  // the gate of the box and keypoint towers (build_plan): active[i] != 0 = item i has an anchor whose class score passes *d_conf. Cleared and
+  // written in every run by the gate step behind the class towers, copied to the host behind decode / NMS.
+  bool gate = false;
+  DevBuf d_active, d_conf;
+  double gate_share[3] = {1, 1, 1};      // per head level: active share of its pixels in the last profiled run (Step::share of the gated convs)
 };
 
 struct TileGeom {       // host-side geometry of one crop
@@ -39,6 +44,11 @@ class DetEngine {
   // overwritten by 0xFF bytes. Results are bit-identical in all three.
   void set_buffer_reuse(int mode) { reuse_ = mode; plans_.clear(); }
   int buffer_reuse() const { return reuse_; }
+  // skip the box and keypoint towers of items without a class score above conf (on by default; env FFP_DET_GATE=0 sets the default to off).
+  // Results are bit-identical either way. Cached plans are dropped.
+  void set_gate(bool on);
+  // items whose towers ran in the last infer_tiles_dev / forward_raw call, of how many (gate off: all of them)
+  void last_active(int* active, int* items) const;
   // summed over the resident plans: bytes held for Plan::alloc tensors, what one block per tensor would hold, and the maximum over
   // build order of the bytes live at once (the floor of any placement)
   void mem_detail(size_t* activation, size_t* no_reuse, size_t* peak_live) const;
@@ -84,7 +94,10 @@ class DetEngine {
   DetPlan* plan_for(const std::vector<TileGeom>& g);
   void build_plan(DetPlan& p, const std::vector<int>& hs, const std::vector<int>& ws);
   std::vector<TileGeom> geometry(int H, int W, const int32_t* tiles, int n_tiles, int imgsz) const;
-  DetPlan* prepare(const uint8_t* d_frame, int H, int W, int chan_order, const int32_t* tiles, int n_tiles, int imgsz);
+  // conf: the gate's threshold for this call (what decode will test against; below 0: every item active)
+  DetPlan* prepare(const uint8_t* d_frame, int H, int W, int chan_order, const int32_t* tiles, int n_tiles, int imgsz, float conf);
+  void fetch_active(DetPlan* P, int n_tiles);
+  void set_shares(DetPlan* P) const;
   const PackedConv* conv(const std::string& name) const;
 
   std::map<std::string, PackedConv> convs_;
@@ -93,6 +106,11 @@ class DetEngine {
   int lanes_ = 0;
   static int reuse_env();       // FFP_DET_ARENA, or 1
   int reuse_ = reuse_env();
+  static int gate_env();        // FFP_DET_GATE, or 1
+  bool gate_ = gate_env() != 0;
+  HostPinned h_active_;         // the gate's verdict of the last call
+  bool last_gated_ = false;
+  int last_items_ = 0;
   unsigned long long use_clock_ = 0;
   size_t weight_bytes_ = 0;
   int device_ = 0, nc_ = 1, nkpt_ = 5;

@@ -260,6 +260,15 @@ int ffp_det_graph_status(ffp_det* d, int32_t* out_state);
  * 1: the head's nine towers and C3k's side convs run as parallel graph branches (3-5 % faster when the detector has the device
  * to itself, slower when an enhancer stream runs beside it); 2 / 3: coarser variants for A/B. Drops the cached plans. */
 int ffp_det_set_lanes(ffp_det* d, int mode);
+/* Skip the box and keypoint towers of the pose head for items (slices, the full-frame pass) in which no anchor's class score passes conf
+ * (no counterpart in the reference, whose model.predict at /root/reference/utils/yolo_wrapper.py:74-80 runs every tower on every slice):
+ * decode reads an anchor's box values only when its score passes, NMS reads keypoints only of boxes it keeps, so such an item gets
+ * nothing out of those towers. Results are bit-identical with the gate on and off. on = 1 is the default (env FFP_DET_GATE=0 sets the
+ * default to off). Drops the cached plans. */
+int ffp_det_set_gate(ffp_det* d, int on);
+/* Items whose box and keypoint towers ran in the handle's last inference call, and the items of that call (gate off, and the raw head
+ * output of ffp_det_forward_raw: all of them). */
+int ffp_det_last_active(ffp_det* d, int32_t* out_active, int32_t* out_items);
 /* Stream interop for the multi-GPU exchange (no counterpart in the reference, which is single-device:
  * /root/reference/pipeline_v4_yolo/app_yolo_sahi.py:136): work enqueued on the handle's stream AFTER this call waits for `hip_event`
  * (a hipEvent_t of the same process, e.g. torch.cuda.Event.cuda_event recorded behind the RCCL all-gather of the boxes) — the
