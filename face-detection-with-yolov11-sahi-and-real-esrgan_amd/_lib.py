@@ -147,6 +147,7 @@ _SIGS = {
     "ffp_op_dwconv3x3": (C.c_int, [C.c_int, C.c_int, C.c_int, _p(C.c_int32), _p(C.c_int32), C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int,
                                    C.c_int, C.c_int, C.c_int, _p(C.c_float), _p(C.c_float), C.c_int, _p(C.c_float), C.c_int, C.c_int,
                                    _p(C.c_float), C.c_int, C.c_int]),
+    "ffp_op_cls_tower": (C.c_int, [C.c_int, C.c_int, _p(C.c_int32), _p(C.c_int32), C.c_int, C.c_int, C.c_int] + [_p(C.c_float)] * 13 + [C.c_int, C.c_int, _p(C.c_int64)]),
     "ffp_op_det_post": (C.c_int, [C.c_int, C.c_int, _p(C.c_int32), _p(C.c_int32), C.c_int, C.c_int, C.c_int, _p(C.c_float), _p(C.c_float),
                                   _p(C.c_float), _p(C.c_float), _p(C.c_int32), C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                   _p(C.c_float), _p(C.c_float), _p(C.c_int32)]),
@@ -849,6 +850,25 @@ def op_psa_attention(qkv, nh: int, q_coff: int, out, o_coff: int, px_align: int 
     _op_same_batch(hs, ws, hs2, ws2, "psa_attention")
     _check(lib().ffp_op_psa_attention(device, precision, len(hs), _ip(hs), _ip(ws), px_align, nh, _fp(qf), qcs, q_coff, _fp(of), ocs, o_coff))
     return _op_unpack(of, hs, ws)
+
+
+def op_cls_tower(x, dw0, pw0, dw1, pw1, fin, head, head_coff: int, px_align: int = 32, want_e1: bool = True, device: int = 0):
+    """The fused class tower (ffp_op_cls_tower). x / head: per image (h, w, cin) / (h, w, head_cs) arrays; dw0 .. fin: (weight, bias) pairs.
+    -> (e1 per image (h, w, 128) or None, head per image with the logits in channels [head_coff, head_coff + nc), the number of 32-bit words
+    that changed in the device buffers' padding pixels: between the aligned images and behind the last one)."""
+    hs, ws = [int(a.shape[0]) for a in x], [int(a.shape[1]) for a in x]
+    cin, nc, hcs = int(x[0].shape[2]), int(fin[0].shape[0]), int(head[0].shape[2])
+    xf = np.ascontiguousarray(np.concatenate([np.asarray(a, np.float32).reshape(-1, cin) for a in x]))
+    hf = np.ascontiguousarray(np.concatenate([np.asarray(a, np.float32).reshape(-1, hcs) for a in head]))
+    e1 = np.zeros((xf.shape[0], 128), np.float32) if want_e1 else None
+    f32 = lambda a: np.ascontiguousarray(a, np.float32)
+    ws_ = [f32(a) for pair in (dw0, pw0, dw1, pw1, fin) for a in pair]
+    stray = C.c_int64(-1)
+    _check(lib().ffp_op_cls_tower(device, len(hs), _ip(np.asarray(hs, np.int32)), _ip(np.asarray(ws, np.int32)), px_align, cin, nc, _fp(xf),
+                                  *[_fp(a) for a in ws_], _fp(e1) if want_e1 else None, _fp(hf), hcs, head_coff, C.byref(stray)))
+    cut = np.cumsum([0] + [h * w for h, w in zip(hs, ws)])
+    split = lambda a, c: [a[cut[i]:cut[i + 1]].reshape(hs[i], ws[i], c) for i in range(len(hs))]
+    return (split(e1, 128) if want_e1 else None), split(hf, hcs), int(stray.value)
 
 
 def op_dwconv3x3(x, c: int, x_coff: int, w: np.ndarray, b: Optional[np.ndarray], y, y_coff: int, act: int = 0, grp: int = 0, grp_stride: int = 0,

@@ -15,7 +15,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libffp.so")
-SOURCES = ["common.cpp", "weights.cpp", "engine.cpp", "conv_route.cpp", "conv_mfma.hip", "conv_rows.hip", "conv_rows16.hip", "conv_rows16pc.hip", "conv_trunk.hip", "conv_pw.hip", "conv_k3d.hip", "ops_misc.hip", "det_post.hip", "merge.hip", "eval.hip", "coco_eval.hip", "iqa.hip", "jpeg.hip", "jpeg_huff.hip", "jpeg_dec.cpp",
+SOURCES = ["common.cpp", "weights.cpp", "engine.cpp", "conv_route.cpp", "conv_mfma.hip", "conv_rows.hip", "conv_rows16.hip", "conv_rows16pc.hip", "conv_trunk.hip", "conv_pw.hip", "conv_k3d.hip", "conv_dwpw.hip", "ops_misc.hip", "det_post.hip", "merge.hip", "eval.hip", "coco_eval.hip", "iqa.hip", "jpeg.hip", "jpeg_huff.hip", "jpeg_dec.cpp",
            "sr_ops.hip", "resize.hip", "yolo11.cpp", "rrdb.cpp", "onnx_graph.cpp", "scrfd_ops.hip", "scrfd.cpp", "rtdetr_ops.hip", "rtdetr.cpp", "api.cpp"]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-result",
          "-ffp-contract=off"]
@@ -161,11 +161,36 @@ def build_arena_check(verbose: bool = True) -> str:
     return ARENA_OUT
 
 
+DW_BOUND_OUT = os.path.join(CSRC, "build", "dw_bound_host_check")
+
+
+def build_dw_bound_check(verbose: bool = True) -> str:
+    """Host-only AddressSanitizer + UBSan build of the depthwise-fused loader's exponent arithmetic (csrc/dw_bound.hpp, plain C++ shared with
+    the kernel) with its driver (csrc/dw_bound_host_check.cpp)."""
+    clang = os.path.join(os.path.dirname(os.path.realpath(_hipcc())), "..", "lib", "llvm", "bin", "clang++")
+    if not os.path.exists(clang):
+        clang = "/opt/rocm/lib/llvm/bin/clang++"
+    os.makedirs(os.path.dirname(DW_BOUND_OUT), exist_ok=True)
+    srcs = [os.path.join(CSRC, "dw_bound_host_check.cpp"), os.path.join(CSRC, "dw_bound.hpp")]
+    if os.path.exists(DW_BOUND_OUT) and os.path.getmtime(DW_BOUND_OUT) > max(os.path.getmtime(s) for s in srcs):
+        return DW_BOUND_OUT
+    cmd = [clang, "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
+           srcs[0], "-o", DW_BOUND_OUT]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(f"sanitizer build failed:\n{r.stdout}\n{r.stderr}")
+    if verbose:
+        print(f"built {DW_BOUND_OUT}")
+    return DW_BOUND_OUT
+
+
 if __name__ == "__main__":
     if "--asan" in sys.argv:
         build_asan()
     elif "--arena-check" in sys.argv:
         build_arena_check()
+    elif "--dw-bound-check" in sys.argv:
+        build_dw_bound_check()
     elif "--variant" in sys.argv:
         build_variant(sys.argv[sys.argv.index("--variant") + 1])
     else:

@@ -1328,6 +1328,96 @@ int ffp_op_dwconv3x3(int device, int precision, int n, const int32_t* hs, const 
   FFP_API_END
 }
 
+int ffp_op_cls_tower(int device, int n, const int32_t* hs, const int32_t* ws, int px_align, int cin, int nc, const float* x, const float* dw0_w,
+                     const float* dw0_b, const float* pw0_w, const float* pw0_b, const float* dw1_w, const float* dw1_b, const float* pw1_w,
+                     const float* pw1_b, const float* fin_w, const float* fin_b, float* e1, float* head, int head_cs, int head_coff, int64_t* stray) {
+  FFP_API_BEGIN
+  FFP_CHECK(x && dw0_w && dw0_b && pw0_w && pw0_b && dw1_w && dw1_b && pw1_w && pw1_b && fin_w && fin_b && head, FFP_ERR_ARG, "cls_tower: null argument");
+  op_check_batch("cls_tower", n, hs, ws, px_align);
+  FFP_CHECK(px_align % 32 == 0 && cin > 0 && cin % 16 == 0 && cin <= 4096 && nc >= 1 && nc <= 256, FFP_ERR_ARG, "cls_tower: px_align %d must be a multiple of 32, cin %d a multiple of 16, nc %d in [1, 256]", px_align, cin, nc);
+  op_check_view("cls_tower head", head_cs, head_coff, nc);
+  OpCtx cx(device, "cls_tower");
+  conv_kernels_init();
+  const int C3 = 128;
+  PackedConv dw0, pw0, dw1, pw1, fin;
+  pack_conv(dw0, "cv3.0.0", dw0_w, dw0_b, cin, cin, 3, cin, F32, cx.st, false);
+  pack_conv(pw0, "cv3.0.1", pw0_w, pw0_b, C3, cin, 1, 1, F32, cx.st, true);
+  pack_conv(dw1, "cv3.1.0", dw1_w, dw1_b, C3, C3, 3, C3, F32, cx.st, false);
+  pack_conv(pw1, "cv3.1.1", pw1_w, pw1_b, C3, C3, 1, 1, F32, cx.st, true);
+  pack_conv(fin, "cv3.2", fin_w, fin_b, nc, C3, 1, 1, F32, cx.st, true);
+  DenseF32 dense;
+  dense.w.alloc(sizeof(float) * nc * C3);
+  dense.b.alloc(sizeof(float) * nc);
+  FFP_HIP(hipMemcpy(dense.w.p, fin_w, sizeof(float) * nc * C3, hipMemcpyHostToDevice));
+  FFP_HIP(hipMemcpy(dense.b.p, fin_b, sizeof(float) * nc, hipMemcpyHostToDevice));
+  Level L;
+  L.build(std::vector<int>(hs, hs + n), std::vector<int>(ws, ws + n), cx.st, px_align);
+  DevBuf dx = op_upload(L, F32, x, cin), dhead = op_upload(L, F32, head, head_cs);
+  FFP_HIP(hipMemset(static_cast<char*>(dhead.p) + (size_t)L.total_px * head_cs * 4, 0xFF, 256));      // the slack behind the records: a known pattern too (stray)
+  DevBuf de1((size_t)L.total_px * C3 * 4 + 256), de2((size_t)L.total_px * C3 * 4 + 256);
+  FFP_HIP(hipMemset(de1.p, 0xFF, de1.n));      // NaN: padding pixels are never written
+  FFP_HIP(hipMemset(de2.p, 0xFF, de2.n));
+  // a max-|value| slot per (tensor, image): x's from the data, the others raised by their producers
+  std::vector<unsigned> slots(3 * (size_t)n, 0u);
+  {
+    size_t sp = 0;
+    for (int i = 0; i < n; ++i) {
+      const size_t np = (size_t)hs[i] * ws[i] * cin;
+      float m = 0.f;
+      for (size_t k = 0; k < np; ++k) m = std::max(m, std::fabs(x[sp + k]));
+      std::memcpy(&slots[i], &m, 4);
+      sp += np;
+    }
+  }
+  DevBuf dslots(slots.size() * 4);
+  FFP_HIP(hipMemcpy(dslots.p, slots.data(), slots.size() * 4, hipMemcpyHostToDevice));
+  auto view = [&](void* p, int cs, int coff, int c, int slot) {
+    TView v{p, F32, cs, coff, c, &L};
+    if (slot >= 0) { v.amax = dslots.as<unsigned>() + (size_t)slot * n; v.amax_n = n; }
+    return v;
+  };
+  const bool fuse_fin = nc <= 4;
+  ConvOp t1, t2;
+  t1.pc = &pw0; t1.dw = &dw0; t1.dw_act = ACT_SILU; t1.act = ACT_SILU;
+  t1.in = view(dx.p, cin, 0, cin, 0); t1.out = view(de1.p, C3, 0, C3, 1);
+  t2.pc = &pw1; t2.dw = &dw1; t2.dw_act = ACT_SILU; t2.act = ACT_SILU;
+  t2.in = t1.out; t2.out = view(fuse_fin ? nullptr : de2.p, C3, 0, C3, 2);
+  const TView logits = view(dhead.p, head_cs, head_coff, nc, -1);
+  if (fuse_fin) { t2.fin = &fin; t2.fin_w = &dense; t2.fin_out = logits; }
+  launch_conv(t1, cx.st);
+  launch_conv(t2, cx.st);
+  if (!fuse_fin) {
+    ConvOp t3;
+    t3.pc = &fin; t3.in = t2.out; t3.out = logits; t3.act = ACT_NONE;
+    launch_conv(t3, cx.st);
+  }
+  FFP_HIP(hipStreamSynchronize(cx.st));
+  op_download(L, F32, dhead, head_cs, head);
+  if (e1) op_download(L, F32, de1, C3, e1);
+  if (stray) {
+    // pixels that belong to no image (behind each aligned image, and the slack behind the buffer) must still hold what went up: 0xFF bytes in e1 / e2,
+    // op_upload's NaN in the head record
+    const float nanv = std::nanf("");
+    unsigned nan_bits;
+    std::memcpy(&nan_bits, &nanv, 4);
+    auto changed = [&](const DevBuf& b, int cs, unsigned want, unsigned want_slack) {
+      std::vector<unsigned> h(b.n / 4);
+      FFP_HIP(hipMemcpy(h.data(), b.p, h.size() * 4, hipMemcpyDeviceToHost));
+      int64_t bad = 0;
+      for (int i = 0; i < n; ++i) {
+        const size_t p0 = (size_t)(L.off[i] + (int64_t)hs[i] * ws[i]) * cs, p1 = (size_t)(i + 1 < n ? L.off[i + 1] : L.total_px) * cs;
+        for (size_t k = p0; k < p1; ++k) bad += h[k] != want;
+      }
+      for (size_t k = (size_t)L.total_px * cs; k < h.size(); ++k) bad += h[k] != want_slack;
+      return bad;
+    };
+    *stray = changed(de1, C3, 0xFFFFFFFFu, 0xFFFFFFFFu) + changed(de2, C3, 0xFFFFFFFFu, 0xFFFFFFFFu);
+    // nc > 4: the head record is written by the plain 1x1 conv, and the flat-pixel 1x1 kernels compute padding pixels like any pixel (common.hpp, Level::build)
+    if (fuse_fin) *stray += changed(dhead, head_cs, nan_bits, 0xFFFFFFFFu);
+  }
+  FFP_API_END
+}
+
 int ffp_op_det_post(int device, int n, const int32_t* hs, const int32_t* ws, int px_align, int nc, int nkpt, const float* head8, const float* head16,
                     const float* head32, const float* gain_pad, const int32_t* rects, float conf, float iou, int max_det, int round_boxes,
                     int shift, int full_h, int full_w, float* out_raw, float* out_dets, int32_t* out_counts) {

@@ -3,6 +3,7 @@
 // conv_rows16pc.hip and conv_trunk.hip.
 #pragma once
 #include "conv_route.hpp"
+#include "dw_bound.hpp"
 #include "ops.hpp"
 
 namespace ffp {
@@ -128,10 +129,7 @@ __device__ __forceinline__ unsigned amax_in_bits_s(const ConvArgs& a, int img) {
 
 // activation scale of the split and its inverse from a max-|value| bit pattern: 2^(13 - e) puts the largest value in [2^13, 2^14)
 __device__ __forceinline__ void split_scales(unsigned amax_bits, float* t, float* tinv) {
-  const unsigned eb = (amax_bits >> 23) & 0xFFu;
-  const bool ok = eb >= 14u && eb < 255u;         // zero / denormal-tiny / inf / nan tensors: unscaled
-  *t = ok ? __uint_as_float((267u - eb) << 23) : 1.f;
-  *tinv = ok ? __uint_as_float((eb - 13u) << 23) : 1.f;
+  split_scales_hd(amax_bits, t, tinv);            // dw_bound.hpp: the one text of this step, host and device (dw_bound_host_check.cpp runs it on the CPU)
 }
 
 // (x0, x1) * t -> packed fp16 pair hi = RN(x * t) and packed fp16 pair lo = RN(x * t - hi), t a power of two: the operand split of
@@ -147,6 +145,15 @@ __device__ __forceinline__ void split_pair(float x0, float x1, float t, unsigned
   asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(l) : "v"(x1), "v"(t), "v"(h));
   hi = h;
   lo = l;
+}
+
+// the activations with IEEE expf and divide: the depthwise and image-input kernels (ops_misc.hip) and the depthwise sums conv_dwpw.hip computes in
+// its loader, which must have the bits dwconv3x3_col_kernel stores
+__device__ __forceinline__ float act_fn(float v, int act) {
+  if (act == ACT_SILU) return v / (1.0f + expf(-v));
+  if (act == ACT_LRELU) return v >= 0.f ? v : v * 0.2f;
+  if (act == ACT_RELU) return fmaxf(v, 0.f);
+  return v;
 }
 
 __device__ __forceinline__ float apply_act(float v, int act) {
@@ -203,6 +210,12 @@ void conv_rows16pc_init();
 unsigned conv_pw_mask(const ConvOp& op, const ConvArgs& a);
 void launch_conv_pw(ConvArgs& a, int shape, hipStream_t st);
 void conv_pw_init();
+
+// a depthwise 3x3 + activation inside the loader of a 1x1 fp32-split conv to 128 channels, optionally with a closing 1x1 to <= 4 channels in the
+// epilogue (conv_dwpw.hip, ConvOp::dw / ConvOp::fin): one shape (SHAPE_DWPW). The launcher builds its own argument block from the op.
+bool conv_dwpw_eligible(const ConvOp& op, bool need_storage = true);      // need_storage = false: views without storage yet (a plan asking before it allocates)
+void launch_conv_dwpw(const ConvOp& op, hipStream_t st);
+void conv_dwpw_init();
 
 // 3x3 fp32-split convs, stride 1 and 2, weights straight from L2 into MFMA operand registers (conv_k3d.hip): shape_bit(s) of the mask =
 // shape s (SHAPE_K3D_*) can run this op; results are bit-identical to the generic kernel's

@@ -1035,6 +1035,7 @@ void conv_kernels_init() {
   conv_trunk_init();
   conv_pw_init();
   conv_k3d_init();
+  conv_dwpw_init();
   Family<float, 1, 1>::init(); Family<float, 3, 1>::init(); Family<float, 3, 2>::init();
   Family<_Float16, 1, 1>::init(); Family<_Float16, 3, 1>::init(); Family<_Float16, 3, 2>::init();
   Family<X3, 1, 1>::init(); Family<X3, 3, 1>::init(); Family<X3, 3, 2>::init();

@@ -27,11 +27,13 @@ constexpr ConvShapeInfo kShapes[SHAPE_COUNT] = {
     {SHAPE_PW_2X2S, F::PW, "pw", "pw2x2s"},              {SHAPE_ROWS16_RES, F::ROWS16, "rows16", "rows16"},
     {SHAPE_ROWS16PC, F::ROWS16PC, "rows16pc", "rows16pc"}, {SHAPE_TRUNK, F::TRUNK, "trunk", "trunk"},
 };
+constexpr ConvShapeInfo kDwPw{SHAPE_DWPW, F::DWPW, "dwpw", "dw3"};
 constexpr bool table_in_order() {
   for (int i = 0; i < SHAPE_COUNT; ++i) if (kShapes[i].shape != i) return false;
   return true;
 }
 static_assert(table_in_order(), "conv shape table: row i holds shape i");
+static_assert(SHAPE_COUNT <= 32 && SHAPE_DWPW >= 32, "forceable shapes fit a 32-bit candidate mask; route-only numbers lie above them");
 
 bool env_is(const char* name, char c) {
   const char* e = getenv(name);
@@ -53,6 +55,7 @@ bool family_runs(ConvFamily family, int shape, const ConvOp& op, const ConvArgs&
     case F::PW: return conv_pw_mask(op, a) & shape_bit(shape);
     case F::K3D: return conv_k3d_mask(op, a) & shape_bit(shape);
     case F::TRUNK: return conv_trunk_layer_ok(op);
+    case F::DWPW: return conv_dwpw_eligible(op);
     case F::DIRECT: break;
   }
   return false;
@@ -65,9 +68,15 @@ const ConvShapeInfo* conv_shape_info(int shape) {
   return &kShapes[shape];
 }
 
-ConvArgs conv_route_args(const ConvOp& op) { return conv_direct_eligible(op) ? ConvArgs{} : make_conv_args(op); }
+const ConvShapeInfo* conv_route_info(int shape) { return shape == SHAPE_DWPW ? &kDwPw : conv_shape_info(shape); }
+
+ConvArgs conv_route_args(const ConvOp& op) { return op.dw || conv_direct_eligible(op) ? ConvArgs{} : make_conv_args(op); }      // the depthwise-fused launcher builds its own block
 
 ConvRoute conv_route(const ConvOp& op, const ConvArgs& a) {
+  if (op.dw) {      // one kernel, one shape: nothing else computes the depthwise conv on the way in
+    FFP_CHECK((op.force_shape < 0 || op.force_shape == SHAPE_DWPW) && conv_dwpw_eligible(op), FFP_ERR_ARG, "conv %s: the depthwise-fused kernel cannot run this op", op.pc->name.c_str());
+    return {F::DWPW, SHAPE_DWPW};
+  }
   if (conv_direct_eligible(op)) return {F::DIRECT, SHAPE_AUTO};
   if (op.force_shape >= 0) {
     const ConvShapeInfo* s = conv_shape_info(op.force_shape);
@@ -101,6 +110,7 @@ void launch_conv(const ConvOp& op, hipStream_t st) {
     case F::ROWS16PC: launch_conv_rows16pc(a, *op.pc, op.out.lvl, st); break;
     case F::PW: launch_conv_pw(a, r.shape, st); break;
     case F::K3D: launch_conv_k3d(a, r.shape, op.stride, op.out.lvl, st); break;
+    case F::DWPW: launch_conv_dwpw(op, st); break;
     case F::TRUNK: {                               // the fused-body kernel on ONE layer (tests, probes): a throw-away single-layer plan
       TrunkPlan tp(std::vector<ConvOp>{op});
       tp.launch(st, op.dbg);
@@ -116,7 +126,7 @@ std::string conv_variant(const ConvOp& op) {
   const ConvRoute r = conv_route(op, conv_route_args(op));
   if (r.family == F::DIRECT) return std::string(pc.dt == F32 ? "f32" : "f16") + "_k3_direct";
   char buf[64];
-  snprintf(buf, sizeof(buf), "%s_k%ds%d_%s", pc.dt == F16 ? "f16" : pc.split ? "f32x3" : "f32", pc.k, op.stride, conv_shape_info(r.shape)->suffix);
+  snprintf(buf, sizeof(buf), "%s_k%ds%d_%s", pc.dt == F16 ? "f16" : pc.split ? "f32x3" : "f32", pc.k, op.stride, conv_route_info(r.shape)->suffix);
   return buf;
 }
 

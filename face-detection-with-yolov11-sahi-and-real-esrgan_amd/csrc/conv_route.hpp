@@ -20,18 +20,21 @@ enum ConvShape : int {
   SHAPE_ROWS16_RES = 23,                                                                             // conv_rows16_kernel, weights resident in LDS
   SHAPE_ROWS16PC = 24,                                                                               // conv_rows16pc_kernel
   SHAPE_TRUNK = 25,                                                                                  // conv_trunk_kernel on one layer
-  SHAPE_COUNT
+  SHAPE_COUNT,                                                                                       // the numbers above: what ConvOp::force_shape and ffp_op_conv2d_shape take
+  SHAPE_DWPW = 64                                                                                    // conv_dwpw_kernel: only ever the route of an op with ConvOp::dw set, never forced onto another; 64: out of reach of the numbers appended above (static_assert in conv_route.cpp)
 };
 constexpr unsigned shape_bit(int shape) { return 1u << shape; }      // candidate masks: bit s = shape s
 
-enum class ConvFamily { DIRECT, GENERIC, ROWS, ROWS16, ROWS16PC, PW, K3D, TRUNK };
+enum class ConvFamily { DIRECT, GENERIC, ROWS, ROWS16, ROWS16PC, PW, K3D, TRUNK, DWPW };
 
 // One row per shape number. A step's variant string is "<precision>_k<k>s<stride>_<suffix>" (conv_variant): bench.py parses it and
 // profiles/*pmc_traffic.json is keyed by it, so 6 / 7 / 8 all say "rows" and 9 / 23 both say "rows16", as they always have.
 struct ConvShapeInfo { int shape; ConvFamily family; const char* family_name; const char* suffix; };
-const ConvShapeInfo* conv_shape_info(int shape);      // nullptr: not a shape number
+const ConvShapeInfo* conv_shape_info(int shape);      // nullptr: not a shape number an op can be forced to (0 .. SHAPE_COUNT - 1)
+const ConvShapeInfo* conv_route_info(int shape);      // ... and SHAPE_DWPW: every number conv_route returns
 
 // The kernel that runs `op`, and the shape number it runs at (DIRECT: SHAPE_AUTO, the image-input kernel has one shape).
+//   op.dw set: the depthwise-fused 1x1 kernel (SHAPE_DWPW) or FFP_ERR_ARG; the plan asks conv_dwpw_eligible before it builds such an op.
 //   force_shape < 0: direct -> rows16 (rows16pc / its resident form by switch) -> rows -> the generic kernel at its heuristic's shape.
 //     pw and k3d shapes are only ever picked by measurement: conv_candidates() offers them to conv_tune.
 //   force_shape >= 0: that shape's family at that shape, or FFP_ERR_ARG when the number is no shape or the family cannot run the op; only

@@ -69,7 +69,7 @@ Level* Plan::add_level_capacity(int cap_n, int64_t cap_px, int cap_t16, hipStrea
 
 double Step::actual_flops() const {
   if (!is_conv) return 0;
-  if (!trunk) return conv_flops_of(*conv->pc, conv->out.lvl->actual_px());
+  if (!trunk) return conv_flops_of(*conv->pc, conv->out.lvl->actual_px()) + (conv->fin ? conv_flops_of(*conv->fin, conv->out.lvl->actual_px()) : 0.0);
   double f = 0;
   for (const auto& c : fused) f += conv_flops_of(*c->pc, c->out.lvl->actual_px());
   return f;
@@ -80,6 +80,9 @@ static double conv_bytes_of(const ConvOp& c) {
   const double opx = (double)c.out.lvl->actual_px(), ipx = (double)c.in.lvl->actual_px();
   const double ie = (double)dsize(c.in.dt), oe = (double)dsize(c.out.dt);
   double b = opx * pc.cout * oe;
+  // depthwise-fused ops (ConvOp::dw / fin): the input once, what is stored (the closing conv's channels instead of this conv's), every weight once
+  if (c.fin) b = opx * c.fin->cout * 4.0 + (double)c.fin->cout * c.fin->cin_real * 4.0 + 4.0 * c.fin->cout;
+  if (c.dw) b += 10.0 * c.dw->cout * 4.0;
   if (c.has_up2) b += (double)c.up2.lvl->actual_px() * c.up2_c * (double)dsize(c.up2.dt) + ipx * (pc.cin_real - c.up2_c) * ie;
   else b += ipx * pc.cin_real * ie;
   if (c.has_res1) b += opx * pc.cout * (double)dsize(c.res1.dt);
@@ -232,10 +235,10 @@ void Plan::add_amax_reset(hipStream_t st) {
 void Plan::add_conv(const ConvOp& op) {
   Step s;
   ConvOp o = op;
-  o.flops = conv_flops_of(*op.pc, op.out.lvl->actual_px());
+  o.flops = conv_flops_of(*op.pc, op.out.lvl->actual_px()) + (op.fin ? conv_flops_of(*op.fin, op.out.lvl->actual_px()) : 0.0);
   s.is_conv = true;
   s.variant = conv_variant(o);
-  s.name = op.pc->name;
+  s.name = op.label.empty() ? op.pc->name : op.label;
   s.flops = o.flops;
   s.conv = std::make_shared<ConvOp>(o);
   std::shared_ptr<ConvOp> cp = s.conv;

@@ -5,6 +5,9 @@
 
 namespace ffp {
 
+// the closing 1x1 of ConvOp::fin as plain fp32 [cout][cin] + bias[cout] on the device (the packed fragments are of no use to a dot product)
+struct DenseF32 { DevBuf w, b; };
+
 // Dense convolution k in {1,3}, stride in {1,2}, pad k/2, as an implicit GEMM on MFMA (conv_mfma.hip).
 //   out = epilogue( conv(in) + bias ),   epilogue: act, then optional  v = v*s1 + res1,  v = v*s2 + res2, then act_post
 // `up` = 1 reads the input through a nearest x2 upsample (ESRGAN conv_up1/2). Depthwise convs go to DwConvOp.
@@ -31,6 +34,16 @@ struct ConvOp {
   // slot alone. 3x3 convs walk the level's gated tile table (Level::tile_table); 1x1 convs (stride 1, levels aligned to 32 pixels) turn the
   // loads and stores of an inactive image's 32-pixel fragments into out-of-range buffer accesses. nullptr: every image. The tuner times with nullptr.
   const int* gate = nullptr;
+  // A depthwise 3x3 conv + activation computed inside this 1x1 conv's loader (conv_dwpw.hip, YOLO11 class tower): `in` is the depthwise conv's
+  // input and carries its max-|value| slot; the depthwise output is never stored, its split exponent comes from a bound (dw_bound.hpp).
+  const PackedConv* dw = nullptr;
+  int dw_act = ACT_NONE;
+  // ... and a closing 1x1 conv to at most 4 channels (no activation) in its epilogue, as fp32 dot products in a fixed order: `out` then has no
+  // storage (Plan::alloc_virtual: level and channel count only) and no slot is raised; the results go to `fin_out`.
+  const PackedConv* fin = nullptr;      // its name, shape and FLOPs
+  const DenseF32* fin_w = nullptr;      // its values
+  TView fin_out;
+  std::string label;                    // step / profile name of an op that stands for more than its own conv (empty: pc->name)
   int force_shape = -1;   // tuning and tests: a ConvShape number (conv_route.hpp) pins the kernel and its workgroup shape; SHAPE_AUTO (-1): conv_route decides
 };
 void launch_conv(const ConvOp& op, hipStream_t st);      // on the kernel conv_route (conv_route.hpp) picks

@@ -10,13 +10,6 @@ namespace {
 template <typename T> __device__ __forceinline__ float ldf(const T* p) { return (float)*p; }
 template <typename T> __device__ __forceinline__ void stf(T* p, float v) { *p = (T)v; }
 
-__device__ __forceinline__ float act_fn(float v, int act) {
-  if (act == ACT_SILU) return v / (1.0f + expf(-v));
-  if (act == ACT_LRELU) return v >= 0.f ? v : v * 0.2f;
-  if (act == ACT_RELU) return fmaxf(v, 0.f);
-  return v;
-}
-
 // locate the image containing flat pixel `gp` (tables are tiny: linear scan from a per-thread guess is fine, binary here)
 __device__ __forceinline__ int find_img(const int4* tab, int n, long long gp) {
   int lo = 0, hi = n - 1;

@@ -1,6 +1,8 @@
 // weights.cpp — FFPW parsing + MFMA-fragment weight packing (host side).
 #include "weights.hpp"
 
+#include "dw_bound.hpp"
+
 #include <algorithm>
 #include <cmath>
 
@@ -90,6 +92,7 @@ void pack_conv(PackedConv& pc, const std::string& name, const float* w, const fl
     for (int c = 0; c < cout; ++c)
       for (int t = 0; t < taps; ++t) hw[(size_t)t * cout + c] = w[(size_t)c * taps + t];
     pc.cin_pad = cin; pc.ncg = 0;
+    dw_weight_norms(w, b, cout, taps, &pc.dw_l1, &pc.dw_bmax);
     pc.w.alloc(hw.size() * 4);
     FFP_HIP(hipMemcpyAsync(pc.w.p, hw.data(), hw.size() * 4, hipMemcpyHostToDevice, st));
     FFP_HIP(hipStreamSynchronize(st));

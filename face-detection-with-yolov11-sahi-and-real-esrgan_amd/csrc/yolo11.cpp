@@ -5,6 +5,8 @@
 // channel slices of the consumer's buffer; Upsample is a copy into such a slice.
 #include "yolo11.hpp"
 
+#include "conv_args.hpp"
+
 #include <cmath>
 #include <cstdlib>
 
@@ -61,6 +63,20 @@ DetEngine::DetEngine(const void* weights, size_t nbytes, int arch, int nc, int n
   FFP_CHECK(conv("model.23.cv3.0.2")->cout == nc_ && conv("model.23.cv4.0.2")->cout == 3 * nkpt_, FFP_ERR_WEIGHTS,
             "head shapes (%d classes, %d kpt values) differ from nc=%d nkpt=%d", conv("model.23.cv3.0.2")->cout,
             conv("model.23.cv4.0.2")->cout, nc_, nkpt_);
+  if (split_ && nc_ <= 4 && conv("model.23.cv3.0.1.1.conv")->cout == 128)      // where a plan can fuse the class tower (build_plan)
+    for (int l = 0; l < 3; ++l) {
+      const std::string nm = "model.23.cv3." + std::to_string(l) + ".2";
+      if (!wf.has(nm + ".weight") || !wf.has(nm + ".bias")) continue;
+      const HostTensor& w = wf.get(nm + ".weight");
+      const HostTensor& b = wf.get(nm + ".bias");
+      DenseF32& d = dense_[nm];
+      d.w.alloc(w.numel() * 4);
+      d.b.alloc(b.numel() * 4);
+      FFP_HIP(hipMemcpyAsync(d.w.p, w.data, w.numel() * 4, hipMemcpyHostToDevice, st_));
+      FFP_HIP(hipMemcpyAsync(d.b.p, b.data, b.numel() * 4, hipMemcpyHostToDevice, st_));
+      FFP_HIP(hipStreamSynchronize(st_));
+      weight_bytes_ += d.w.n + d.b.n;
+    }
   for (const auto& kv : convs_) weight_bytes_ += kv.second.w.n + kv.second.w16.n + kv.second.bias.n + kv.second.w_direct.n + kv.second.oscale.n;
 }
 
@@ -319,7 +335,42 @@ void DetEngine::build_plan(DetPlan& P, const std::vector<int>& hs, const std::ve
     const std::string ls = std::to_string(l);
     P.head[l] = P.alloc(lv, head_cs, F32);              // never released: decode reads it after the plan
     P.fork(tower_lane(l, 2));
-    TView d1 = P.alloc(lv, chs[l], T), e1 = P.alloc(lv, c3, T), d2 = P.alloc(lv, c3, T), e2 = P.alloc(lv, c3, T);
+    // Two launches instead of five (conv_dwpw.hip): each depthwise conv runs inside the loader of the 1x1 conv behind it, and with nc <= 4 the closing 1x1
+    // inside the second one's epilogue; d1, d2 and e2 are never stored. A never-stored tensor has no max-|value| slot: its split takes its exponent from a
+    // per-image bound (dw_bound.hpp). FFP_CLS_FUSE=0: the five ops. Read per plan, so that one process can build both.
+    const char* fuse_env = getenv("FFP_CLS_FUSE");
+    const std::string n0 = hp + ".cv3." + ls + ".0", n1 = hp + ".cv3." + ls + ".1", n2 = hp + ".cv3." + ls + ".2";
+    // e1 and e2 start without storage: the fused ops are described first and the kernel is asked (its layout, and that x, e1 and the head record each fit
+    // one buffer resource: a level past 2 GiB, e.g. 5-frame groups at imgsz 1024, does not); a level it cannot run gets the five ops below, unchanged
+    TView e1 = P.alloc_virtual(lv, c3, T), e2 = P.alloc_virtual(lv, c3, T);
+    bool fused = false;
+    if (split_ && P.per_image_amax && !(fuse_env && fuse_env[0] == '0' && !fuse_env[1]) && chs[l] % 16 == 0 && c3 == 128) {
+      const bool fin = dense_.count(n2) != 0;
+      ConvOp t1, t2;
+      t1.pc = conv(n0 + ".1.conv"); t1.dw = conv(n0 + ".0.conv"); t1.dw_act = ACT_SILU;
+      t1.in = x; t1.out = e1; t1.act = ACT_SILU; t1.label = n0;
+      t2.pc = conv(n1 + ".1.conv"); t2.dw = conv(n1 + ".0.conv"); t2.dw_act = ACT_SILU;
+      t2.in = e1; t2.out = e2; t2.act = ACT_SILU; t2.label = fin ? n1 + "+2" : n1;
+      if (fin) { t2.fin = conv(n2); t2.fin_w = &dense_.at(n2); t2.fin_out = P.head[l].slice(64, nc_); }
+      if (conv_dwpw_eligible(t1, false) && conv_dwpw_eligible(t2, false)) {
+        fused = true;
+        P.materialize(e1);
+        if (!fin) P.materialize(e2);
+        t1.out = e1; t2.in = e1; t2.out = e2;
+        P.cur_lane = tower_lane(l, 2);
+        P.add_conv(t1);
+        P.add_conv(t2);
+        if (!fin) cv(n2, e2, P.head[l].slice(64, nc_), 1, ACT_NONE);
+        P.release(e1);
+        if (!fin) P.release(e2);
+        P.cur_lane = 0;
+      }
+    }
+    if (fused) return;
+    TView d1 = P.alloc(lv, chs[l], T);
+    P.materialize(e1);
+    TView d2 = P.alloc(lv, c3, T);
+    P.materialize(e2);
     P.cur_lane = tower_lane(l, 2);
     dw(hp + ".cv3." + ls + ".0.0.conv", x, d1, ACT_SILU);
     cv(hp + ".cv3." + ls + ".0.1.conv", d1, e1, 1, ACT_SILU);

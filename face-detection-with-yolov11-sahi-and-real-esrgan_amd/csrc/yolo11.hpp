@@ -101,6 +101,7 @@ class DetEngine {
   const PackedConv* conv(const std::string& name) const;
 
   std::map<std::string, PackedConv> convs_;
+  std::map<std::string, DenseF32> dense_;      // model.23.cv3.<l>.2 as plain fp32 (nc <= 4): the closing conv of the fused class tower (conv_dwpw.hip)
   std::map<std::vector<int>, std::unique_ptr<DetPlan>> plans_;
   std::vector<TileGeom> geom_last_;
   int lanes_ = 0;

@@ -422,6 +422,19 @@ int ffp_op_dwconv3x3(int device, int precision, int n, const int32_t* hs, const 
                      int x_coff, int grp, int grp_stride, int grp_off, const float* wt, const float* bias, int act, const float* res, int r_cs,
                      int r_coff, float* y, int y_cs, int y_coff);
 
+/* The YOLO11 class tower of one head level as the detector's fp32-split plan runs it fused (conv_dwpw.hip): two launches,
+ *   e1 = SiLU(pw0(SiLU(dw0(x))))   and   logits = fin(SiLU(pw1(SiLU(dw1(e1))))),
+ * each depthwise 3x3 inside the loader of the 1x1 behind it; with nc <= 4 the closing 1x1 runs in the second launch's epilogue, with nc > 4 as
+ * the conv it is in the unfused plan. x: [pixels][cin] (cin a multiple of 16), dw0: [cin][3][3] + [cin], pw0: [128][cin] + [128], dw1: [128][3][3]
+ * + [128], pw1: [128][128] + [128], fin: [nc][128] + [nc]. px_align must be a multiple of 32 (one split exponent per image). e1 (NULL = skip):
+ * [pixels][128] out. head: [pixels][head_cs] in/out, the logits go to channels [head_coff, head_coff + nc). stray (NULL = skip): the number of
+ * 32-bit words that changed in the padding pixels between the aligned images and behind the last one (e1, the stored second tensor when nc > 4,
+ * and, with nc <= 4, the head record): the device buffers go up with a known pattern there and are read back whole. With nc > 4 the head record
+ * is written by the plain 1x1 conv, whose flat-pixel kernels compute padding pixels like any pixel; it is then left out of the count. */
+int ffp_op_cls_tower(int device, int n, const int32_t* hs, const int32_t* ws, int px_align, int cin, int nc, const float* x, const float* dw0_w,
+                     const float* dw0_b, const float* pw0_w, const float* pw0_b, const float* dw1_w, const float* dw1_b, const float* pw1_w,
+                     const float* pw1_b, const float* fin_w, const float* fin_b, float* e1, float* head, int head_cs, int head_coff, int64_t* stray);
+
 /* Pose-head post-processing on given head tensors. hs / ws: net input size per image (multiples of 32); head8 / head16 / head32:
  * [sum (hs/s)*(ws/s)][64 + nc + 3*nkpt] fp32 records (64 DFL logits | class logits | keypoint raws). gain_pad [n][3] = gain,
  * pad_x, pad_y and rects [n][4] = crop width, crop height, x0, y0: the un-letterboxing geometry of each image.

@@ -22,11 +22,21 @@ tot_ms = tot_b = 0
 rows = []
 for x in det:
     variant, name = x["name"].split(" ", 1)
-    if "+" in name:         # model.0 computed in model.1's loader: reads the u8 network image, writes model.1's output; nothing in between
+    if "+" in name and name.startswith("model.0."):         # model.0 computed in model.1's loader: reads the u8 network image, writes model.1's output; nothing in between
         w0, w1 = Wd["model.0.conv.weight"], Wd["model.1.conv.weight"]
         px1 = x["flops"] / (2.0 * (w0.shape[1] * 9 * w0.shape[0] * 4 + w1.shape[1] * 9 * w1.shape[0]))
         by = px1 * 16 * 3 + px1 * w1.shape[0] * 4
         rows.append((x["ms"], name, variant, 3, w1.shape[0], 3, by))
+        tot_ms += x["ms"]; tot_b += by
+        continue
+    if name + ".weight" not in Wd:      # fused class-tower step "model.23.cv3.<l>.0" / ".1" / ".1+2": depthwise 3x3 in the loader of the 1x1 behind it (+ the closing 1x1)
+        stem, tail = name.rsplit(".", 1)
+        w = Wd[f"{stem}.{tail[0]}.1.conv.weight"]
+        fin = Wd[f"{stem}.2.weight"] if tail.endswith("+2") else None
+        cout, cin = w.shape[0], w.shape[1]
+        px = x["flops"] / (2.0 * (cin * cout + (cout * fin.shape[0] if fin is not None else 0)))
+        by = px * cin * 4 + px * (fin.shape[0] if fin is not None else cout) * 4      # the input once, what is stored
+        rows.append((x["ms"], name, variant, cin, fin.shape[0] if fin is not None else cout, 1, by))
         tot_ms += x["ms"]; tot_b += by
         continue
     w = Wd[name + ".weight"]
