@@ -148,6 +148,10 @@ _SIGS = {
                                    C.c_int, C.c_int, C.c_int, _p(C.c_float), _p(C.c_float), C.c_int, _p(C.c_float), C.c_int, C.c_int,
                                    _p(C.c_float), C.c_int, C.c_int]),
     "ffp_op_cls_tower": (C.c_int, [C.c_int, C.c_int, _p(C.c_int32), _p(C.c_int32), C.c_int, C.c_int, C.c_int] + [_p(C.c_float)] * 13 + [C.c_int, C.c_int, _p(C.c_int64)]),
+    "ffp_op_conv2d_views": (C.c_int, [C.c_int, C.c_int, C.c_int, _p(C.c_int32), _p(C.c_int32), C.c_int, _p(C.c_float), C.c_int, C.c_int, C.c_int,
+                                      _p(C.c_float), _p(C.c_float), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_float), C.c_int,
+                                      C.c_int, C.c_float, _p(C.c_float), C.c_int, C.c_int, C.c_float, _p(C.c_float), C.c_int, C.c_int, C.c_int,
+                                      _p(C.c_uint32), _p(C.c_int32), _p(C.c_int32), _p(C.c_int64)]),
     "ffp_op_det_post": (C.c_int, [C.c_int, C.c_int, _p(C.c_int32), _p(C.c_int32), C.c_int, C.c_int, C.c_int, _p(C.c_float), _p(C.c_float),
                                   _p(C.c_float), _p(C.c_float), _p(C.c_int32), C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                   _p(C.c_float), _p(C.c_float), _p(C.c_int32)]),
@@ -800,7 +804,16 @@ def op_variant(family: int, variant=0) -> None:
     _check(lib().ffp_op_variant(int(family), v))
 
 
-def _op_pack(imgs: Sequence[np.ndarray]):
+class OpBatch:
+    """A ragged batch packed once (the images' pixel records back to back), to be passed in place of the list of images to several operator calls."""
+
+    def __init__(self, imgs: Sequence[np.ndarray]):
+        self.flat, self.hs, self.ws, self.cs = _op_pack(imgs)
+
+
+def _op_pack(imgs):
+    if isinstance(imgs, OpBatch):
+        return imgs.flat, imgs.hs, imgs.ws, imgs.cs
     imgs = [np.asarray(a, np.float32) for a in imgs]
     if not imgs or any(a.ndim != 3 or a.shape[2] != imgs[0].shape[2] for a in imgs):
         raise ValueError("a batch is a non-empty list of (h, w, cs) arrays with one record size")
@@ -891,6 +904,54 @@ def op_dwconv3x3(x, c: int, x_coff: int, w: np.ndarray, b: Optional[np.ndarray],
     _check(lib().ffp_op_dwconv3x3(device, precision, len(hs), _ip(hs), _ip(ws), px_align, c, _fp(xf), xcs, x_coff, grp, grp_stride, grp_off, _fp(w),
                                   _fp(bb) if bb is not None else None, act, _fp(rf) if rf is not None else None, rcs, r_coff, _fp(yf), ycs, y_coff))
     return _op_unpack(yf, hs, ws)
+
+
+def op_conv2d_views(x, x_coff: int, w: np.ndarray, b: Optional[np.ndarray], y, y_coff: int, stride: int = 1, act: int = 0, act_post: int = 0,
+                    up: bool = False, res1=None, r1_coff: int = 0, s1: float = 1.0, res2=None, r2_coff: int = 0, s2: float = 1.0, px_align: int = 32,
+                    per_image_amax: bool = False, amax_out=None, gate=None, gate_prev=None, precision: int = PREC_F32, device: int = 0):
+    """One dense conv on the operands the plans give it (ffp_op_conv2d_views). x: per image (h, w, x_cs) arrays, read at channels
+    [x_coff, x_coff + cin); w: (cout, cin, k, k); y / res1 / res2: per image arrays of the OUTPUT sizes, the conv writes y[..., y_coff : y_coff + cout].
+    x, y, res1 and res2 may be OpBatch objects (packed once, reused over calls). amax_out: initial bit patterns of the output's max-|value| slots (n with per_image_amax, else 1; default zeros); gate / gate_prev: per image
+    0 / 1. -> (y per image, final slot bit patterns, elements changed where the conv may not write)."""
+    xf, hs, ws, xcs = _op_pack(x)
+    yf, hs2, ws2, ycs = _op_pack(y)
+    if isinstance(y, OpBatch):
+        yf = yf.copy()                     # in/out: the packed batch stays what it was
+    w = np.ascontiguousarray(w, np.float32)
+    if w.ndim != 4 or w.shape[2] != w.shape[3]:
+        raise ValueError(f"conv2d_views: weights {w.shape}, expected (cout, cin, k, k)")
+    cout, cin, k = int(w.shape[0]), int(w.shape[1]), int(w.shape[2])
+    bb = np.ascontiguousarray(b, np.float32) if b is not None else None
+    if bb is not None and bb.shape != (cout,):
+        raise ValueError(f"conv2d_views: bias {bb.shape}, expected {(cout,)}")
+    n = len(hs)
+    sc = 2 if up else 1
+    pad = k // 2
+    _op_same_batch((hs * sc + 2 * pad - k) // stride + 1, (ws * sc + 2 * pad - k) // stride + 1, hs2, ws2, "conv2d_views output")
+    rf = [None, None]
+    rcs = [0, 0]
+    for i, r in enumerate((res1, res2)):
+        if r is not None:
+            rf[i], hs3, ws3, rcs[i] = _op_pack(r)
+            _op_same_batch(hs2, ws2, hs3, ws3, "conv2d_views residual")
+    ns = n if per_image_amax else 1
+    slots = np.zeros(ns, np.uint32) if amax_out is None else np.ascontiguousarray(amax_out, np.uint32).copy()
+    if slots.shape != (ns,):
+        raise ValueError(f"conv2d_views: {slots.shape} output slots, expected {(ns,)}")
+    g = [None, None]
+    for i, m in enumerate((gate, gate_prev)):
+        if m is not None:
+            g[i] = np.ascontiguousarray(m, np.int32)
+            if g[i].shape != (n,):
+                raise ValueError(f"conv2d_views: gate {g[i].shape}, expected {(n,)}")
+    stray = C.c_int64(-1)
+    opt = lambda a: _fp(a) if a is not None else None
+    _check(lib().ffp_op_conv2d_views(device, precision, n, _ip(hs), _ip(ws), px_align, _fp(xf), xcs, x_coff, cin, _fp(w), opt(bb), cout, k, stride, act,
+                                     act_post, int(bool(up)), opt(rf[0]), rcs[0], r1_coff, s1, opt(rf[1]), rcs[1], r2_coff, s2, _fp(yf), ycs, y_coff,
+                                     int(bool(per_image_amax)), _up(slots), _ip(g[0]) if g[0] is not None else None,
+                                     _ip(g[1]) if g[1] is not None else None, C.byref(stray)))
+    cut = np.cumsum([0] + [int(h) * int(w_) for h, w_ in zip(hs2, ws2)])
+    return [yf[cut[i]:cut[i + 1]].reshape(int(hs2[i]), int(ws2[i]), ycs) for i in range(n)], slots, int(stray.value)
 
 
 def op_det_post(heads, nc: int, nkpt: int, geom, conf: float = 0.25, iou: float = 0.7, max_det: int = 300, round_boxes: bool = False,

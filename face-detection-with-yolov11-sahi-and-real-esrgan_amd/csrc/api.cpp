@@ -6,6 +6,7 @@
 
 #include "coco_eval.hpp"
 #include "conv_route.hpp"
+#include "det_post.hpp"
 #include "eval.hpp"
 #include "iqa.hpp"
 #include "jpeg.hpp"
@@ -1414,6 +1415,138 @@ int ffp_op_cls_tower(int device, int n, const int32_t* hs, const int32_t* ws, in
     *stray = changed(de1, C3, 0xFFFFFFFFu, 0xFFFFFFFFu) + changed(de2, C3, 0xFFFFFFFFu, 0xFFFFFFFFu);
     // nc > 4: the head record is written by the plain 1x1 conv, and the flat-pixel 1x1 kernels compute padding pixels like any pixel (common.hpp, Level::build)
     if (fuse_fin) *stray += changed(dhead, head_cs, nan_bits, 0xFFFFFFFFu);
+  }
+  FFP_API_END
+}
+
+// A dense conv the way the plans run it (tests/test_gpu_conv_views.py): ragged batch, levels built with `px_align`, every operand a channel slice of a
+// wider record, up to two residual terms, one max-|value| slot per buffer or per image, and the gate. hs / ws are the INPUT image sizes; y, res1 and
+// res2 hold the output level's images. y is in/out. *stray: what changed where the conv may not write — bytes among the 256 behind y's records, and elements
+// of y's padding pixels (a 1x1 conv computes the padding pixels of its own slice like any pixel: those channels are left out of the count, except behind an
+// image that is inactive under the final gate).
+int ffp_op_conv2d_views(int device, int precision, int n, const int32_t* hs, const int32_t* ws, int px_align, const float* x, int x_cs, int x_coff,
+                        int cin, const float* wt, const float* bias, int cout, int k, int stride, int act, int act_post, int up, const float* res1,
+                        int r1_cs, int r1_coff, float s1, const float* res2, int r2_cs, int r2_coff, float s2, float* y, int y_cs, int y_coff,
+                        int per_image_amax, uint32_t* amax_out, const int32_t* gate, const int32_t* gate_prev, int64_t* stray) {
+  FFP_API_BEGIN
+  FFP_CHECK(x && wt && y && amax_out && cin > 0 && cout > 0, FFP_ERR_ARG, "conv2d_views: null argument or no channels");
+  FFP_CHECK(precision == FFP_PREC_F32 || precision == FFP_PREC_F16 || precision == FFP_PREC_F32X3, FFP_ERR_ARG, "conv2d_views: precision %d", precision);
+  FFP_CHECK((k == 1 || k == 3) && (stride == 1 || stride == 2) && (up == 0 || up == 1) && (per_image_amax == 0 || per_image_amax == 1), FFP_ERR_ARG,
+            "conv2d_views: k in {1,3}, stride in {1,2}, up and per_image_amax in {0,1}");
+  FFP_CHECK(act >= ACT_NONE && act <= ACT_RELU && act_post >= ACT_NONE && act_post <= ACT_RELU, FFP_ERR_ARG, "conv2d_views: activation codes %d / %d (0..3)", act, act_post);
+  FFP_CHECK(!gate_prev || gate, FFP_ERR_ARG, "conv2d_views: gate_prev without gate");
+  op_check_batch("conv2d_views", n, hs, ws, px_align);
+  const DType T = precision == FFP_PREC_F16 ? F16 : F32;
+  const int epv = 16 / (int)dsize(T);
+  const int cin_s = (cin + epv - 1) / epv * epv;       // the packed conv's input channels: padded to 16 bytes (an image-input conv reads 3 of 4)
+  op_check_view("conv2d_views input", x_cs, x_coff, cin_s);
+  FFP_CHECK(x_cs % epv == 0 && x_coff % epv == 0, FFP_ERR_ARG, "conv2d_views: input view not 16-byte aligned (cs=%d coff=%d)", x_cs, x_coff);
+  op_check_view("conv2d_views output", y_cs, y_coff, cout);
+  if (res1) op_check_view("conv2d_views res1", r1_cs, r1_coff, cout);
+  if (res2) op_check_view("conv2d_views res2", r2_cs, r2_coff, cout);
+  std::vector<int> hi(hs, hs + n), wi(ws, ws + n), ho(n), wo(n);
+  for (int i = 0; i < n; ++i) {
+    const int hv = up ? hi[i] * 2 : hi[i], wv = up ? wi[i] * 2 : wi[i];
+    ho[i] = (hv + 2 * (k / 2) - k) / stride + 1;
+    wo[i] = (wv + 2 * (k / 2) - k) / stride + 1;
+  }
+  OpCtx cx(device, "conv2d_views");
+  conv_kernels_init();
+  tl_op_conv_variant.clear();
+  PackedConv pc;
+  pack_conv(pc, "op", wt, bias, cout, cin, k, 1, T, cx.st, precision == FFP_PREC_F32X3);
+  FFP_CHECK(pc.cin == cin_s, FFP_ERR_STATE, "conv2d_views: packed conv reads %d channels, expected %d", pc.cin, cin_s);
+  Level lin, lout;
+  lin.build(hi, wi, cx.st, px_align);
+  lout.build(ho, wo, cx.st, px_align);
+  lout.gate_compact = &launch_gate_compact;
+  const size_t esz = dsize(T), ybytes = (size_t)lout.total_px * y_cs * esz;
+  DevBuf din = op_upload(lin, T, x, x_cs), dout, dr1, dr2;
+  if (res1) dr1 = op_upload(lout, T, res1, r1_cs);
+  if (res2) dr2 = op_upload(lout, T, res2, r2_cs);
+  // max-|value| slots: [0, ns) the input's — from the data, per image over the view's own channels, NaN (an inactive image on its way up) left out —
+  // and [ns, 2 ns) the output's, which start from the caller's bit patterns
+  const int ns = per_image_amax ? n : 1;
+  std::vector<unsigned> slots(2 * (size_t)ns, 0u);
+  {
+    size_t sp = 0;
+    for (int i = 0; i < n; ++i) {
+      const size_t np = (size_t)hi[i] * wi[i];
+      float m = 0.f;
+      for (size_t p = 0; p < np; ++p)
+        for (int c = 0; c < cin; ++c) m = std::max(m, std::fabs(x[(sp + p) * x_cs + x_coff + c]));
+      unsigned b;
+      std::memcpy(&b, &m, 4);
+      slots[per_image_amax ? i : 0] = std::max(slots[per_image_amax ? i : 0], b);
+      sp += np;
+    }
+  }
+  DevBuf dslots(slots.size() * 4), dgate;
+  auto upload_outputs = [&]() {      // padding pixels go up as NaN (op_upload), the slack behind the records as 0xFF bytes
+    dout = op_upload(lout, T, y, y_cs);
+    FFP_HIP(hipMemset(static_cast<char*>(dout.p) + ybytes, 0xFF, 256));
+    std::copy(amax_out, amax_out + ns, slots.begin() + ns);
+    FFP_HIP(hipMemcpy(dslots.p, slots.data(), slots.size() * 4, hipMemcpyHostToDevice));
+  };
+  upload_outputs();
+  if (gate) dgate = upload(gate_prev ? gate_prev : gate, (size_t)n);
+  auto view = [&](void* p, int cs, int coff, int c, Level* L, int slot) {
+    TView v{p, T, cs, coff, c, L};
+    if (slot >= 0) { v.amax = dslots.as<unsigned>() + (size_t)slot * ns; v.amax_n = ns; }
+    return v;
+  };
+  ConvOp o;
+  o.pc = &pc; o.stride = stride; o.act = act; o.act_post = act_post; o.up = up;
+  o.in = view(din.p, x_cs, x_coff, cin_s, &lin, 0);
+  auto bind_out = [&]() {      // dout is a new allocation after every upload
+    o.out = view(dout.p, y_cs, y_coff, cout, &lout, 1);
+  };
+  bind_out();
+  if (res1) { o.has_res1 = true; o.res1 = view(dr1.p, r1_cs, r1_coff, cout, &lout, -1); o.s1 = s1; }
+  if (res2) { o.has_res2 = true; o.res2 = view(dr2.p, r2_cs, r2_coff, cout, &lout, -1); o.s2 = s2; }
+  if (gate) o.gate = dgate.as<int>();
+  o.force_shape = g_op_conv_shape;
+  launch_conv(o, cx.st);
+  tl_op_conv_variant = conv_variant(o);
+  FFP_HIP(hipStreamSynchronize(cx.st));
+  if (gate_prev) {      // what a captured plan does between two runs with different gates: same tables, same launches, the mask rewritten and the gated tables compacted again
+    upload_outputs();
+    bind_out();
+    FFP_HIP(hipMemcpy(dgate.p, gate, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
+    lout.compact_gated(cx.st);
+    launch_conv(o, cx.st);
+    FFP_HIP(hipStreamSynchronize(cx.st));
+  }
+  // one copy of the whole buffer back: the images' records for the caller, the rest for the stray count
+  std::vector<unsigned char> now(ybytes + 256);
+  FFP_HIP(hipMemcpy(now.data(), dout.p, now.size(), hipMemcpyDeviceToHost));
+  {
+    size_t sp = 0;
+    for (int i = 0; i < n; ++i) {
+      const size_t ne = (size_t)ho[i] * wo[i] * y_cs, e0 = (size_t)lout.off[i] * y_cs;
+      if (T == F32) std::memcpy(y + sp, &now[e0 * 4], ne * 4);
+      else for (size_t e = 0; e < ne; ++e) y[sp + e] = (float)reinterpret_cast<const _Float16*>(now.data())[e0 + e];
+      sp += ne;
+    }
+  }
+  FFP_HIP(hipMemcpy(slots.data(), dslots.p, slots.size() * 4, hipMemcpyDeviceToHost));
+  std::copy(slots.begin() + ns, slots.end(), amax_out);
+  if (stray) {
+    volatile float nanv = std::nanf("");            // (volatile: the conversion op_upload ran, not a folded constant)
+    const float nanf32 = nanv;
+    const _Float16 nanf16 = (_Float16)nanf32;      // what op_upload stored in a padding pixel
+    const void* want_pad = T == F32 ? static_cast<const void*>(&nanf32) : static_cast<const void*>(&nanf16);
+    int64_t bad = 0;
+    for (int i = 0; i < n; ++i) {
+      const size_t p0 = (size_t)(lout.off[i] + (int64_t)ho[i] * wo[i]), p1 = (size_t)(i + 1 < n ? lout.off[i + 1] : lout.total_px);
+      for (size_t p = p0; p < p1; ++p)
+        for (int c = 0; c < y_cs; ++c) {
+          if (k == 1 && c >= y_coff && c < y_coff + cout && (!gate || gate[i])) continue;      // (behind an inactive image they are nobody's to write)
+          bad += std::memcmp(&now[(p * y_cs + c) * esz], want_pad, esz) != 0;
+        }
+    }
+    for (size_t e = ybytes; e < now.size(); ++e) bad += now[e] != 0xFF;
+    *stray = bad;
   }
   FFP_API_END
 }

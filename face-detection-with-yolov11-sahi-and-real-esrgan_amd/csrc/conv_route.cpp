@@ -77,7 +77,10 @@ ConvRoute conv_route(const ConvOp& op, const ConvArgs& a) {
     FFP_CHECK((op.force_shape < 0 || op.force_shape == SHAPE_DWPW) && conv_dwpw_eligible(op), FFP_ERR_ARG, "conv %s: the depthwise-fused kernel cannot run this op", op.pc->name.c_str());
     return {F::DWPW, SHAPE_DWPW};
   }
-  if (conv_direct_eligible(op)) return {F::DIRECT, SHAPE_AUTO};
+  if (conv_direct_eligible(op)) {      // the flat-pixel VALU kernel knows no gate: a gated image-input conv is refused, not computed on every image
+    FFP_CHECK(!op.gate, FFP_ERR_ARG, "conv %s: the image-input kernel cannot honour a gate", op.pc->name.c_str());
+    return {F::DIRECT, SHAPE_AUTO};
+  }
   if (op.force_shape >= 0) {
     const ConvShapeInfo* s = conv_shape_info(op.force_shape);
     FFP_CHECK(s, FFP_ERR_ARG, "conv %s: %d is not a shape number", op.pc->name.c_str(), op.force_shape);

@@ -703,7 +703,8 @@ bool conv_trunk_layer_ok(const ConvOp& op) {
   const int cpl = 8;
   // one image table serves input, output and residuals: the same Level, or (single-operator hooks) exact-mode levels of identical geometry
   auto same = [](const Level* x, const Level* y) { return x == y || (x && y && !x->capacity() && !y->capacity() && x->n == y->n && x->h == y->h && x->w == y->w && x->off == y->off); };
-  bool ok = epilogue_fits(op, kEpiR16) && pc.w16.p != nullptr && pc.dt == F16 && pc.k == 3 && op.stride == 1 && op.up == 0 && !op.has_up2 && pc.cin % 32 == 0 && pc.cin >= 64 &&
+  // no gate: the fused launch walks the level's packed tile table, which has no gated form — a gated op is refused, not computed on every image
+  bool ok = !op.gate && epilogue_fits(op, kEpiR16) && pc.w16.p != nullptr && pc.dt == F16 && pc.k == 3 && op.stride == 1 && op.up == 0 && !op.has_up2 && pc.cin % 32 == 0 && pc.cin >= 64 &&
             (pc.cout == 32 || pc.cout == 64) && op.in.dt == F16 && op.out.dt == F16 && same(op.in.lvl, op.out.lvl) && op.in.cs % cpl == 0 && op.in.coff % cpl == 0 &&
             op.out.cs % cpl == 0 && op.out.coff % cpl == 0;
   if (op.has_res1) ok = ok && op.res1.dt == F16 && same(op.res1.lvl, op.out.lvl) && op.res1.cs % cpl == 0 && op.res1.coff % cpl == 0;

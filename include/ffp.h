@@ -435,6 +435,23 @@ int ffp_op_cls_tower(int device, int n, const int32_t* hs, const int32_t* ws, in
                      const float* dw0_b, const float* pw0_w, const float* pw0_b, const float* dw1_w, const float* dw1_b, const float* pw1_w,
                      const float* pw1_b, const float* fin_w, const float* fin_b, float* e1, float* head, int head_cs, int head_coff, int64_t* stray);
 
+/* One dense conv (k in {1,3}, stride in {1,2}, pad k/2, optional nearest x2 `up` in front) on the operands the plans give it:
+ *   y = act_post( (act(conv(x) + bias) * s1 + res1) * s2 + res2 )
+ * hs / ws: INPUT image sizes of a ragged batch; the output level is derived per image and both levels are built with px_align. x: channels
+ * [x_coff, x_coff + cin) of records of x_cs; y (in/out: the caller's contents go up first), res1 and res2 (NULL = none) hold the output level's
+ * images as slices of records of y_cs / r1_cs / r2_cs. wt: [cout][cin][k][k], bias: [cout] or NULL. The kernel is the one ffp_op_conv2d_shape
+ * pins (ffp_op_conv2d_last_variant names it). per_image_amax = 1: n max-|value| slots per tensor (one split exponent per image), else one; the
+ * input's are filled from the data, amax_out (n or 1 values, in/out) carries the output slots' initial and final bit patterns.
+ * gate (NULL = every image): int32[n], nonzero = active (ConvOp::gate). gate_prev (only with gate): the op runs once under gate_prev, then y and
+ * the output slots go up again, the device mask is overwritten with gate, the level's gated tile tables are compacted again and the op runs a
+ * second time — two runs of one captured plan. stray (NULL = skip): the number of bytes that changed among the 256 behind y's records plus the
+ * number of elements that changed in y's padding pixels (of a 1x1 conv: outside its own slice, whose padding pixels the flat-pixel kernels compute like any pixel;
+ * behind an image that is inactive under gate they count too). */
+int ffp_op_conv2d_views(int device, int precision, int n, const int32_t* hs, const int32_t* ws, int px_align, const float* x, int x_cs, int x_coff,
+                        int cin, const float* wt, const float* bias, int cout, int k, int stride, int act, int act_post, int up, const float* res1,
+                        int r1_cs, int r1_coff, float s1, const float* res2, int r2_cs, int r2_coff, float s2, float* y, int y_cs, int y_coff,
+                        int per_image_amax, uint32_t* amax_out, const int32_t* gate, const int32_t* gate_prev, int64_t* stray);
+
 /* Pose-head post-processing on given head tensors. hs / ws: net input size per image (multiples of 32); head8 / head16 / head32:
  * [sum (hs/s)*(ws/s)][64 + nc + 3*nkpt] fp32 records (64 DFL logits | class logits | keypoint raws). gain_pad [n][3] = gain,
  * pad_x, pad_y and rects [n][4] = crop width, crop height, x0, y0: the un-letterboxing geometry of each image.

@@ -516,7 +516,9 @@ def test_conv_forced_shape_that_cannot_run_the_op_is_refused(gpu_lib):
     """A number that is no shape is refused by ffp_op_conv2d_shape itself and leaves the knob at -1; a pw / k3d number, or the two-tile rows
     shape on an odd tile count, on the fp16 dense-block conv is the call's argument error (before conv_route these ran conv_rows_kernel —
     the last one its <1, 2> configuration — and returned its result: DESIGN.md records that run); so are the fp16 kernels' numbers on an
-    exact-fp32 conv, and the weight-resident rows16 form (23) on 224 input channels, more than its LDS holds (it used to run the streaming form)."""
+    exact-fp32 conv, and the weight-resident rows16 form (23) on 224 input channels, more than its LDS holds (it used to run the streaming form).
+    A gated op (ConvOp::gate, through ffp_op_conv2d_views) is refused by the two kernels that cannot skip an image: the fused-body kernel (25) and the
+    image-input kernel; ungated, both run it."""
     P = gpu_lib
     try:
         for bad in (26, 99, -2):
@@ -530,6 +532,24 @@ def test_conv_forced_shape_that_cannot_run_the_op_is_refused(gpu_lib):
                 with pytest.raises(P.FfpError) as e:
                     _route_run(P, prec, cin, 32, 3, 1)
                 assert e.value.code == 1, (prec, cin, shape, str(e.value))
+        # ConvOp::gate (ops.hpp: nothing of an inactive image is read or written): the fused-body kernel (25) walks a packed tile table that has no gated
+        # form, and the image-input VALU kernel walks flat pixels — both used to compute every image of a gated op; now they are the argument error
+        z = lambda h, w, c: [np.zeros((h, w, c), np.float32)] * 2
+        w64, w3 = np.zeros((32, 64, 3, 3), np.float32), np.zeros((32, 3, 3, 3), np.float32)
+        P.op_conv2d_shape(25)
+        y, _, _ = P.op_conv2d_views(z(9, 17, 64), 0, w64, None, z(9, 17, 32), 0, precision=P.PREC_F16)      # ungated: runs
+        assert P.op_conv2d_last_variant() == "f16_k3s1_trunk"
+        with pytest.raises(P.FfpError) as e:
+            P.op_conv2d_views(z(9, 17, 64), 0, w64, None, z(9, 17, 32), 0, gate=[1, 0], precision=P.PREC_F16)
+        assert e.value.code == 1, str(e.value)
+        P.op_conv2d_shape(-1)
+        for prec in (P.PREC_F32, P.PREC_F16):
+            cs = 8 if prec == P.PREC_F16 else 4
+            P.op_conv2d_views(z(9, 17, cs), 0, w3, None, z(9, 17, 32), 0, precision=prec)
+            assert P.op_conv2d_last_variant().endswith("_k3_direct")
+            with pytest.raises(P.FfpError) as e:
+                P.op_conv2d_views(z(9, 17, cs), 0, w3, None, z(9, 17, 32), 0, gate=[1, 0], precision=prec)
+            assert e.value.code == 1, str(e.value)
         P.op_conv2d_shape(9)                                  # seven 32-channel chunks: the streaming form runs what the resident form (six at most) refuses
         y, ref, variant = _route_run(P, P.PREC_F16, 224, 32, 3, 1)
         assert variant == "f16_k3s1_rows16"

@@ -117,6 +117,16 @@ def test_operator_entry_points_check_arguments_before_touching_the_device(lib):
                                  [(1, 0, 0, 64, 64, 0, 0)], max_det=2000),
         lambda: _lib.op_rt_topk(np.zeros((1, 299, 4), np.float32)),
         lambda: _lib.op_rt_topk(np.zeros((1, 300, 4), np.float32), nc=4, s_coff=1),
+        lambda: _lib.op_conv2d_views(z(4, 4, 64), 8, np.zeros((32, 64, 1, 1)), None, z(4, 4, 32), 0),                    # input slice past the record
+        lambda: _lib.op_conv2d_views(z(4, 4, 72), 2, np.zeros((32, 64, 1, 1)), None, z(4, 4, 32), 0),                    # input slice not 16-byte aligned
+        lambda: _lib.op_conv2d_views(z(4, 4, 64), 0, np.zeros((32, 64, 1, 1)), None, z(4, 4, 40), 16),                   # output slice past the record
+        lambda: _lib.op_conv2d_views(z(4, 4, 64), 0, np.zeros((32, 64, 1, 1)), None, z(4, 4, 32), 0, res1=z(4, 4, 32), r1_coff=8),
+        lambda: _lib.op_conv2d_views(z(4, 4, 64), 0, np.zeros((32, 64, 1, 1)), None, z(4, 4, 32), 0, res2=z(4, 4, 16)),
+        lambda: _lib.op_conv2d_views(z(4, 4, 64), 0, np.zeros((32, 64, 1, 1)), None, z(4, 4, 32), 0, gate_prev=[1]),     # gate_prev without gate
+        lambda: _lib.op_conv2d_views(z(4, 4, 64), 0, np.zeros((32, 64, 1, 1)), None, z(4, 4, 32), 0, act=4),
+        lambda: _lib.op_conv2d_views(z(4, 4, 64), 0, np.zeros((32, 64, 1, 1)), None, z(4, 4, 32), 0, act_post=-1),
+        lambda: _lib.op_conv2d_views(z(4, 4, 64), 0, np.zeros((32, 64, 1, 1)), None, z(4, 4, 32), 0, precision=7),
+        lambda: _lib.op_conv2d_views(z(4, 4, 64), 0, np.zeros((32, 64, 1, 1)), None, z(4, 4, 32), 0, px_align=0),
         lambda: _lib.op_variant(_lib.OP_SPPF, 3),
         lambda: _lib.op_variant(3, 1),
     ]
@@ -130,6 +140,9 @@ def test_operator_entry_points_check_arguments_before_touching_the_device(lib):
         assert "no HIP device" in str(e.value)
         with pytest.raises(_lib.FfpError) as e:
             _lib.op_rt_topk(np.zeros((1, 300, 4), np.float32))
+        assert "no HIP device" in str(e.value)
+        with pytest.raises(_lib.FfpError) as e:
+            _lib.op_conv2d_views(z(4, 4, 64), 0, np.zeros((32, 64, 1, 1)), None, z(4, 4, 32), 0, gate=[1], gate_prev=[0])
         assert "no HIP device" in str(e.value)
 
 
@@ -329,3 +342,22 @@ def test_bench_dump_outputs_reads_the_last_batch_and_keeps_the_budget(tmp_path):
         assert n <= 200_000
         picks.append(np.load(tmp_path / f"small{k}" / "enhanced_crop_index.npy").tolist())
     assert 0 < len(picks[0]) < 6 and picks[0] == picks[1]
+
+
+def test_conv_views_plan_bookkeeping():
+    """tests/test_gpu_conv_views.py, the part that needs no device: which shape a case of its plan can run, from the Python predicates alone — every
+    pw / k3d case is one its shape can run, the head slices have pw shapes to run on, and the block-walk batches (and the prefix of them each shape runs
+    on) give every conv_pw workgroup its three pixel blocks."""
+    import test_gpu_conv_views as V
+    from test_gpu_conv import K3D_SHAPES, PW_SHAPES, _epi_k3d_cases, _epi_pw_cases, pw_can_run
+    for shape, cin, cout, k, stride in _epi_pw_cases():
+        assert pw_can_run(shape, cin, cout) and k == 1 and cin % 32 == 0
+    for shape, cin, cout, k, stride in _epi_k3d_cases():
+        assert -(-cout // 32) >= K3D_SHAPES[shape] and (cin + V.X_PAD) % 4 == 0
+    assert [s_ for s_ in sorted(PW_SHAPES) if pw_can_run(s_, 64, 15)] == [12, 15] == [s_ for s_ in sorted(PW_SHAPES) if pw_can_run(s_, 64, 1)]
+    for cin, cout in V.WALK_CASES:
+        sizes = V._walk_sizes(cin, cout)
+        shapes = [s_ for s_ in sorted(PW_SHAPES) if pw_can_run(s_, cin, cout)]
+        assert len(shapes) >= 5 and all(V._pw_blocks_per_workgroup(s_, V._aligned_px(sizes), cout) >= 3 for s_ in shapes)
+        assert all(V._pw_blocks_per_workgroup(s_, V._aligned_px(sizes[:V._walk_prefix(s_, sizes, cout)]), cout) >= 3 for s_ in shapes)
+    assert len(V._walk_sizes(64, 64)) == 60 and len(V._walk_sizes(96, 128)) == 31
