@@ -167,6 +167,7 @@ _SIGS = {
     "ffp_op_rt_ref": (C.c_int, [C.c_int, C.c_longlong, _p(C.c_float), C.c_int, C.c_int, _p(C.c_float), _p(C.c_float), C.c_int, C.c_int, _p(C.c_uint32)]),
     "ffp_op_rt_deform": (C.c_int, [C.c_int, C.c_int, _p(C.c_int32), _p(C.c_int32), _p(C.c_float), C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, _p(C.c_uint32)]),
     "ffp_op_rt_decode": (C.c_int, [C.c_int, C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, C.c_float, _p(C.c_float), _p(C.c_float), _p(C.c_float), _p(C.c_int32)]),
+    "ffp_op_rt_post_tiles": (C.c_int, [C.c_int, C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, C.c_float, _p(C.c_int32), C.c_int, C.c_int, C.c_int, _p(C.c_float), _p(C.c_int32)]),
     "ffp_op_scrfd_pool": (C.c_int, [C.c_int, C.c_int, _p(C.c_int32), _p(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int]),
     "ffp_op_scrfd_post": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_int32), C.c_int, _p(_p(C.c_float)), _p(C.c_int32), _p(C.c_int32), _p(C.c_float), C.c_float, C.c_float, C.c_int, _p(C.c_float), _p(C.c_int32), _p(C.c_float)]),
     "ffp_op_resize_lanczos4": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
@@ -183,6 +184,14 @@ _SIGS = {
     "ffp_rtdetr_destroy": (None, [C.c_void_p]),
     "ffp_rtdetr_predict": (C.c_int, [C.c_void_p, _p(C.c_void_p), _p(C.c_int32), C.c_int, C.c_int, C.c_float, _p(C.c_float), _p(C.c_int32)]),
     "ffp_rtdetr_forward_raw": (C.c_int, [C.c_void_p, _p(C.c_void_p), _p(C.c_int32), C.c_int, C.c_int, _p(C.c_float), _p(C.c_int32)]),
+    "ffp_rtdetr_infer_tiles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _p(C.c_int32), C.c_int, C.c_int, C.c_float, C.c_int, C.c_int,
+                                         _p(C.c_float), _p(C.c_int32)]),
+    "ffp_rtdetr_infer_tiles_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _p(C.c_int32), C.c_int, C.c_int, C.c_float, C.c_int,
+                                             C.c_int, C.c_void_p, C.c_void_p]),
+    "ffp_rtdetr_sliced_predict": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int,
+                                            C.c_float, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _p(C.c_float), C.c_int, _p(C.c_int32)]),
+    "ffp_rtdetr_mem_bytes": (C.c_int, [C.c_void_p, _p(C.c_uint64), _p(C.c_int32)]),
+    "ffp_rtdetr_drop_plans": (C.c_int, [C.c_void_p]),
     "ffp_rtdetr_info": (C.c_int, [C.c_void_p, _p(C.c_int32), _p(C.c_double), _p(C.c_int32)]),
     "ffp_rtdetr_set_profile": (C.c_int, [C.c_void_p, C.c_int]),
     "ffp_rtdetr_profile_count": (C.c_int, [C.c_void_p, _p(C.c_int32)]),
@@ -441,6 +450,46 @@ class RTDETRDetector:
         topk = np.zeros((n, self.NQ), np.int32)
         _check(lib().ffp_rtdetr_forward_raw(self._h, ptrs, _ip(hw), n, imgsz, _fp(out), _ip(topk)))
         return out, topk
+
+    TILE_MODES = {"local": 0, "sahi": 1}         # FFP_RT_TILES_LOCAL, FFP_RT_TILES_SAHI
+
+    def infer_tiles(self, frame: np.ndarray, tiles: Sequence[Sequence[int]], imgsz: int = 640, conf: float = 0.25, mode: str = "local",
+                    chan_order: int = CHAN_AS_BGR, max_batch: int = 0) -> List[np.ndarray]:
+        """Tiles [x0, y0, x1, y1] of one frame, each stretched to imgsz -> per tile (k, 6) float32 rows in query order. mode "local": tile-local
+        pixels, predict()'s rows of the crop; "sahi": clipped against the frame, invalid boxes dropped, shifted to frame pixels (float boxes).
+        max_batch: items per network batch (0: FFP_RT_TILES_DEFAULT_BATCH)."""
+        f = _as_frame(frame)
+        t = np.ascontiguousarray(np.asarray(tiles, np.int32).reshape(-1, 4))
+        n = t.shape[0]
+        dets = np.zeros((max(n, 1), self.NQ, 6), np.float32)
+        counts = np.zeros(max(n, 1), np.int32)
+        _check(lib().ffp_rtdetr_infer_tiles(self._h, f.ctypes.data, f.shape[0], f.shape[1], chan_order, _ip(t), n, imgsz, conf, self.TILE_MODES[mode],
+                                            max_batch, _fp(dets), _ip(counts)))
+        return [dets[i, :counts[i]].copy() for i in range(n)]
+
+    def sliced_predict(self, frame: np.ndarray, slice_h: int, slice_w: int, overlap_h: float = 0.2, overlap_w: float = 0.2,
+                       perform_standard_pred: bool = True, imgsz: int = 640, conf: float = 0.25, pp_type: str = "GREEDYNMM", pp_metric: str = "IOS",
+                       pp_thr: float = 0.5, class_agnostic: bool = False, chan_order: int = CHAN_AS_BGR, max_batch: int = 0, cap: int = 0) -> np.ndarray:
+        """Fused get_sliced_prediction -> (k, 6) float32 rows {x1, y1, x2, y2, score, cls} in frame pixels (float boxes, sahi's rules)."""
+        f = _as_frame(frame)
+        H, W = f.shape[:2]
+        if cap <= 0:
+            cap = (len(slice_bboxes(H, W, slice_h, slice_w, overlap_h, overlap_w)) + 1) * self.NQ
+        out = np.zeros((cap, 6), np.float32)
+        n = C.c_int32(0)
+        _check(lib().ffp_rtdetr_sliced_predict(self._h, f.ctypes.data, H, W, chan_order, slice_h, slice_w, overlap_h, overlap_w,
+                                               int(perform_standard_pred), imgsz, conf, max_batch, PP_TYPES[pp_type], METRICS[pp_metric], float(pp_thr),
+                                               int(class_agnostic), _fp(out), cap, C.byref(n)))
+        return out[:n.value].copy()
+
+    def mem_bytes(self) -> dict:
+        """Device bytes held by the resident plans' activations, and how many plans are resident."""
+        b, n = C.c_uint64(0), C.c_int32(0)
+        _check(lib().ffp_rtdetr_mem_bytes(self._h, C.byref(b), C.byref(n)))
+        return {"plans": int(b.value), "plans_resident": int(n.value)}
+
+    def drop_plans(self):
+        _check(lib().ffp_rtdetr_drop_plans(self._h))
 
 
 class Detector:
@@ -1158,6 +1207,23 @@ def op_rt_decode(ref, r_coff: int, scores, s_coff: int, nc: int, conf: Optional[
                                   _fp(wh) if wh is not None else None, _fp(o_raw) if o_raw is not None else None,
                                   _fp(o_det) if o_det is not None else None, _ip(cnt) if cnt is not None else None))
     return o_raw, o_det, cnt
+
+
+def op_rt_post_tiles(ref, r_coff: int, scores, s_coff: int, nc: int, conf: float, tiles, full_shape, mode: str, det=None, device: int = 0):
+    """ref (n, 300, cs) slice of 4, scores (n, 300, cs') slice of nc logits, tiles (n, 4) x0, y0, x1, y1, full_shape (h, w), mode "local" |
+    "sahi". det: (n, 300, 6) array to fill (default zeros). Returns (det, counts)."""
+    ref, scores = _f32(ref), _f32(scores)
+    n = ref.shape[0]
+    t = np.ascontiguousarray(np.asarray(tiles, np.int32).reshape(-1, 4))
+    if ref.shape[:2] != (n, 300) or scores.shape[:2] != (n, 300) or t.shape[0] != n:
+        raise ValueError("rt_post_tiles: shapes")
+    o = _f32(det).copy() if det is not None else np.zeros((n, 300, 6), np.float32)
+    if o.shape != (n, 300, 6):
+        raise ValueError("rt_post_tiles: output shape")
+    cnt = np.full(n, -1, np.int32)
+    _check(lib().ffp_op_rt_post_tiles(device, n, nc, _fp(ref), ref.shape[2], r_coff, _fp(scores), scores.shape[2], s_coff, float(conf), _ip(t),
+                                      int(full_shape[0]), int(full_shape[1]), RTDETRDetector.TILE_MODES[mode], _fp(o), _ip(cnt)))
+    return o, cnt
 
 
 def op_scrfd_pool(x, c: int, x_coff: int, y, y_coff: int, maxpool: bool, k: int = 2, px_align: int = 1, device: int = 0) -> List[np.ndarray]:

@@ -42,7 +42,8 @@ class PostprocessPredictions:
                 res.append(p0)
                 continue
             first = p0          # merged box: union, max score, category (and keypoints) of the higher-scored source
-            m = ObjectPrediction(bbox=[int(r[0]), int(r[1]), int(r[2]), int(r[3])] if float(r[0]).is_integer() else r[:4].tolist(),
+            # int boxes (the YOLO wrapper truncates) stay ints; float boxes (RT-DETR) stay floats even where one corner is a whole number
+            m = ObjectPrediction(bbox=[int(v) for v in r[:4]] if all(float(v).is_integer() for v in r[:4]) else r[:4].tolist(),
                                  score=float(r[4]), category_id=first.category.id, category_name=first.category.name,
                                  shift_amount=first.bbox.shift_amount, full_shape=first.full_shape)
             if hasattr(first, "keypoints"):

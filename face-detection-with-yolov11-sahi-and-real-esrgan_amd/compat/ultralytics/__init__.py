@@ -160,6 +160,20 @@ else:
                 self._save(out)
             return out
 
+        def predict_tiles(self, frame, tiles, conf=0.25, imgsz=640, rgb=False, max_batch=0):
+            """Not part of Ultralytics: the crops [x0, y0, x1, y1] of one frame as network batches (ffp_rtdetr_infer_tiles, tile-local rows),
+            per tile the list predict() returns for that crop. rgb: the frame is RGB (sahi's arrays), as if every crop were passed flipped."""
+            from ffp_amd import _lib
+            if frame.dtype != np.uint8 or frame.ndim != 3 or frame.shape[2] != 3:
+                raise ValueError(f"RTDETR.predict_tiles: expected an HxWx3 uint8 frame, got {frame.dtype} {frame.shape}")
+            rows = self._det(_lib.PREC_F32).infer_tiles(frame, tiles, int(imgsz), float(conf), "local",
+                                                        _lib.CHAN_AS_RGB if rgb else _lib.CHAN_AS_BGR, max_batch)
+            out = []
+            for k, ((x0, y0, x1, y1), d) in enumerate(zip(tiles, rows)):
+                crop = frame[y0:y1, x0:x1, ::-1] if rgb else frame[y0:y1, x0:x1]
+                out.append([Results(crop, f"image{k}.jpg", self.names, d)])
+            return out
+
         def _save(self, results):
             """save=True: each image with its boxes and 'name score' labels written to runs/detect/predict, predict2, ... (a new directory
             per call, as Ultralytics' increment_path), named after the source file. Drawn with the cv2 shim, so the labels are not

@@ -1923,6 +1923,28 @@ int ffp_op_rt_decode(int device, int n, int nc, const float* ref, int r_cs, int 
   FFP_API_END
 }
 
+int ffp_op_rt_post_tiles(int device, int n, int nc, const float* ref, int r_cs, int r_coff, const float* scores, int s_cs, int s_coff, float conf,
+                         const int32_t* tiles_xyxy, int full_h, int full_w, int mode, float* out_dets, int32_t* out_counts) {
+  FFP_API_BEGIN
+  FFP_CHECK(ref && scores && tiles_xyxy && out_dets && out_counts && nc >= 1 && nc <= 4096, FFP_ERR_ARG, "rt_post_tiles: bad arguments");
+  FFP_CHECK(full_h > 0 && full_w > 0 && (mode == FFP_RT_TILES_LOCAL || mode == FFP_RT_TILES_SAHI), FFP_ERR_ARG,
+            "rt_post_tiles: full shape %d x %d, mode %d", full_w, full_h, mode);
+  op_check_view("rt_post_tiles boxes", r_cs, r_coff, 4);
+  op_check_view("rt_post_tiles scores", s_cs, s_coff, nc);
+  OpCtx cx(device, "rt_post_tiles");
+  Level LQ;
+  op_flat_level(LQ, n, RT_NQ, cx.st);
+  const size_t nq = (size_t)n * RT_NQ;
+  DevBuf dr = upload(ref, nq * r_cs), ds = upload(scores, nq * s_cs), dt = upload(tiles_xyxy, (size_t)n * 4);
+  DevBuf d_det = upload(out_dets, nq * 6), d_counts = upload(out_counts, (size_t)n);
+  launch_rt_post_tiles(OpView(dr, r_cs, r_coff, 4, &LQ), OpView(ds, s_cs, s_coff, nc, &LQ), nc, conf, dt.as<int4>(), n, full_h, full_w, mode,
+                       d_det.as<float>(), d_counts.as<int>(), cx.st);
+  FFP_HIP(hipStreamSynchronize(cx.st));
+  op_fetch(d_det, out_dets, nq * 6);
+  FFP_HIP(hipMemcpy(out_counts, d_counts.p, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost));
+  FFP_API_END
+}
+
 int ffp_op_scrfd_pool(int device, int n, const int32_t* hs, const int32_t* ws, int px_align, int c, int maxpool, int k, const float* x, int x_cs,
                       int x_coff, float* y, int y_cs, int y_coff) {
   FFP_API_BEGIN
@@ -2196,6 +2218,53 @@ int ffp_rtdetr_forward_raw(ffp_rtdetr* r, const uint8_t* const* frames, const in
   FFP_API_BEGIN
   FFP_CHECK(r && frames && hw && out, FFP_ERR_ARG, "null argument");
   r->eng.forward_raw(frames, hw, n, imgsz, out, out_topk);
+  FFP_API_END
+}
+
+// sahi.predict.get_sliced_prediction over sahi.models.ultralytics (model_type "rtdetr"): the slices of a frame as network batches
+int ffp_rtdetr_infer_tiles(ffp_rtdetr* r, const uint8_t* frame, int H, int W, int chan_order, const int32_t* tiles, int n_tiles, int imgsz,
+                           float conf, int mode, int max_batch, float* out_dets, int32_t* out_counts) {
+  FFP_API_BEGIN
+  FFP_CHECK(r && out_dets && out_counts, FFP_ERR_ARG, "null argument");
+  r->eng.infer_tiles(frame, H, W, chan_order, tiles, n_tiles, imgsz, conf, mode, max_batch, out_dets, out_counts);
+  FFP_API_END
+}
+
+int ffp_rtdetr_infer_tiles_dev(ffp_rtdetr* r, const uint8_t* d_frame, int H, int W, int chan_order, const int32_t* tiles, int n_tiles, int imgsz,
+                               float conf, int mode, int max_batch, float* d_out_dets, int32_t* d_out_counts) {
+  FFP_API_BEGIN
+  FFP_CHECK(r && d_frame && d_out_dets && d_out_counts, FFP_ERR_ARG, "null argument");
+  r->eng.infer_tiles_dev(d_frame, H, W, chan_order, tiles, n_tiles, imgsz, conf, mode, max_batch, d_out_dets, d_out_counts);
+  FFP_API_END
+}
+
+int ffp_rtdetr_sliced_predict(ffp_rtdetr* r, const uint8_t* frame, int H, int W, int chan_order, int slice_h, int slice_w, float oh, float ow,
+                              int perform_standard_pred, int imgsz, float conf, int max_batch, int pp_type, int pp_metric, double pp_thr,
+                              int class_agnostic, float* out, int cap, int32_t* out_n) {
+  FFP_API_BEGIN
+  FFP_CHECK(r && frame && out && out_n && cap > 0, FFP_ERR_ARG, "null argument");
+  FFP_CHECK(H > 0 && W > 0, FFP_ERR_ARG, "frame is empty");
+  std::vector<int32_t> items = slice_bboxes(H, W, slice_h, slice_w, oh, ow);
+  if (items.size() / 4 > 1 && perform_standard_pred) items.insert(items.end(), {0, 0, W, H});   // sahi/predict.py: the full-frame pass
+  r->eng.sliced_predict(frame, H, W, chan_order, items, imgsz, conf, max_batch, pp_type, pp_metric, pp_thr, class_agnostic, out, cap, out_n);
+  FFP_API_END
+}
+
+int ffp_rtdetr_mem_bytes(ffp_rtdetr* r, uint64_t* out_plan_bytes, int32_t* out_plans_resident) {
+  FFP_API_BEGIN
+  FFP_CHECK(r, FFP_ERR_ARG, "null handle");
+  size_t b = 0;
+  int n = 0;
+  r->eng.mem_bytes(&b, &n);
+  if (out_plan_bytes) *out_plan_bytes = b;
+  if (out_plans_resident) *out_plans_resident = n;
+  FFP_API_END
+}
+
+int ffp_rtdetr_drop_plans(ffp_rtdetr* r) {
+  FFP_API_BEGIN
+  FFP_CHECK(r, FFP_ERR_ARG, "null handle");
+  r->eng.drop_plans();
   FFP_API_END
 }
 

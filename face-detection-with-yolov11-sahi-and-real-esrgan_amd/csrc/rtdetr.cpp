@@ -380,11 +380,15 @@ RtdetrPlan* RtdetrEngine::plan_for(int n, int imgsz) {
   return it->second.get();
 }
 
-RtdetrPlan* RtdetrEngine::prepare(const uint8_t* const* frames, const int32_t* hw, int n, int imgsz) {
-  FFP_CHECK(frames && hw && n > 0, FFP_ERR_ARG, "rtdetr: empty batch");
+static void check_imgsz(int imgsz) {
   FFP_CHECK(imgsz >= 32 && imgsz % 32 == 0 && imgsz <= 4096, FFP_ERR_ARG, "rtdetr: imgsz %d must be a multiple of 32 in [32, 4096]", imgsz);
   FFP_CHECK((imgsz / 8) * (imgsz / 8) + (imgsz / 16) * (imgsz / 16) + (imgsz / 32) * (imgsz / 32) >= RT_NQ, FFP_ERR_ARG,
             "rtdetr: imgsz %d gives fewer encoder tokens than the decoder's %d queries", imgsz, RT_NQ);
+}
+
+RtdetrPlan* RtdetrEngine::prepare(const uint8_t* const* frames, const int32_t* hw, int n, int imgsz) {
+  FFP_CHECK(frames && hw && n > 0, FFP_ERR_ARG, "rtdetr: empty batch");
+  check_imgsz(imgsz);
   int Wmax = 0;
   long long rows = 0;
   for (int i = 0; i < n; ++i) {
@@ -460,6 +464,130 @@ void RtdetrEngine::forward_raw(const uint8_t* const* frames, const int32_t* hw, 
   launch_rt_raw(P->ref, P->scores, nc_, P->d_raw.as<float>(), st_);
   FFP_HIP(hipMemcpyAsync(out, P->d_raw.p, sizeof(float) * (size_t)n * RT_NQ * (4 + nc_), hipMemcpyDeviceToHost, st_));
   if (topk) FFP_HIP(hipMemcpyAsync(topk, P->d_idx.p, sizeof(int) * (size_t)n * RT_NQ, hipMemcpyDeviceToHost, st_));
+  FFP_HIP(hipStreamSynchronize(st_));
+}
+
+// ---- tiles of one frame (sahi's get_sliced_prediction over an Ultralytics RT-DETR model) ---------------------------------------------
+
+std::vector<int> RtdetrEngine::chunk_sizes(int n, int max_batch) {
+  if (max_batch <= 0) max_batch = RT_TILES_DEFAULT_BATCH;
+  const int chunks = (n + max_batch - 1) / max_batch;
+  std::vector<int> v(chunks, chunks ? n / chunks : 0);
+  for (int i = 0; i < (chunks ? n % chunks : 0); ++i) ++v[i];      // 61 at 16: 16, 15, 15, 15
+  return v;
+}
+
+void RtdetrEngine::mem_bytes(size_t* plans, int* resident) const {
+  size_t b = 0;
+  for (const auto& kv : plans_) b += kv.second->bytes;
+  *plans = b;
+  *resident = (int)plans_.size();
+}
+
+void RtdetrEngine::drop_plans() {
+  FFP_HIP(hipSetDevice(device_));
+  FFP_HIP(hipStreamSynchronize(st_));
+  plans_.clear();
+}
+
+void RtdetrEngine::upload_frame(const uint8_t* frame, int H, int W) {
+  FFP_CHECK(frame && H > 0 && W > 0, FFP_ERR_ARG, "rtdetr: frame is null or empty");
+  FFP_HIP(hipSetDevice(device_));
+  const size_t nb = (size_t)H * W * 3;
+  frame_.ensure(nb);
+  FFP_HIP(hipMemcpyAsync(frame_.p, frame, nb, hipMemcpyHostToDevice, st_));
+}
+
+// everything on st_, nothing waited for: the caller drains the stream (h_lb_ and the caller's `tiles` are read by the copies until then)
+void RtdetrEngine::enqueue_tiles(const uint8_t* d_frame, int H, int W, int chan_order, const int32_t* tiles, int n_tiles, int imgsz, float conf,
+                                 int mode, int max_batch, float* d_out, int32_t* d_counts) {
+  FFP_CHECK(d_frame && H > 0 && W > 0 && d_out && d_counts, FFP_ERR_ARG, "rtdetr: tiles need a frame and outputs");
+  FFP_CHECK(tiles && n_tiles > 0, FFP_ERR_ARG, "rtdetr: no tile to run (n_tiles %d)", n_tiles);
+  FFP_CHECK(n_tiles <= 65536, FFP_ERR_ARG, "rtdetr: %d tiles exceed 65536", n_tiles);
+  FFP_CHECK(chan_order == FFP_CHAN_AS_BGR || chan_order == FFP_CHAN_AS_RGB, FFP_ERR_ARG, "rtdetr: chan_order %d", chan_order);
+  FFP_CHECK(mode == FFP_RT_TILES_LOCAL || mode == FFP_RT_TILES_SAHI, FFP_ERR_ARG, "rtdetr: tile mode %d (FFP_RT_TILES_LOCAL or FFP_RT_TILES_SAHI)", mode);
+  check_imgsz(imgsz);
+  h_lb_.resize(n_tiles);
+  for (int i = 0; i < n_tiles; ++i) {
+    const int32_t* t = tiles + 4 * i;
+    FFP_CHECK(t[0] >= 0 && t[1] >= 0 && t[2] > t[0] && t[3] > t[1] && t[2] <= W && t[3] <= H, FFP_ERR_ARG,
+              "rtdetr: tile %d [%d, %d, %d, %d] is empty, inverted or outside the %d x %d frame", i, t[0], t[1], t[2], t[3], W, H);
+    LetterboxImg& L = h_lb_[i];
+    L.x0 = t[0]; L.y0 = t[1]; L.sw = t[2] - t[0]; L.sh = t[3] - t[1];
+    L.new_w = imgsz; L.new_h = imgsz; L.top = 0; L.left = 0; L.net_h = imgsz; L.net_w = imgsz;    // the stretch prepare() builds
+  }
+  FFP_HIP(hipSetDevice(device_));
+  tiles_lb_.ensure(sizeof(LetterboxImg) * n_tiles);
+  tiles_xy_.ensure(sizeof(int4) * n_tiles);
+  FFP_HIP(hipMemcpyAsync(tiles_lb_.p, h_lb_.data(), sizeof(LetterboxImg) * n_tiles, hipMemcpyHostToDevice, st_));
+  FFP_HIP(hipMemcpyAsync(tiles_xy_.p, tiles, sizeof(int4) * n_tiles, hipMemcpyHostToDevice, st_));
+  const int flip = chan_order == FFP_CHAN_AS_BGR ? 1 : 0;
+  int off = 0;
+  for (int m : chunk_sizes(n_tiles, max_batch)) {
+    RtdetrPlan* P = plan_for(m, imgsz);        // an eviction waits for the stream first
+    FFP_HIP(hipMemcpyAsync(P->d_lb.p, tiles_lb_.as<LetterboxImg>() + off, sizeof(LetterboxImg) * m, hipMemcpyDeviceToDevice, st_));
+    launch_letterbox(d_frame, H, W, flip, P->d_lb, P->input, st_);
+    P->execute(st_, nullptr);
+    // straight into the call-wide buffers at the chunk's tile offset: nothing to copy between the chunks and the merge
+    launch_rt_post_tiles(P->ref, P->scores, nc_, conf, tiles_xy_.as<int4>() + off, m, H, W, mode, d_out + (size_t)off * RT_NQ * 6, d_counts + off, st_);
+    last_conv_flops = P->conv_flops;
+    last_graph_state = P->graph_state();
+    off += m;
+  }
+}
+
+void RtdetrEngine::infer_tiles_dev(const uint8_t* d_frame, int H, int W, int chan_order, const int32_t* tiles, int n_tiles, int imgsz, float conf,
+                                   int mode, int max_batch, float* d_out, int32_t* d_counts) {
+  enqueue_tiles(d_frame, H, W, chan_order, tiles, n_tiles, imgsz, conf, mode, max_batch, d_out, d_counts);
+  FFP_HIP(hipStreamSynchronize(st_));
+}
+
+void RtdetrEngine::infer_tiles(const uint8_t* frame, int H, int W, int chan_order, const int32_t* tiles, int n_tiles, int imgsz, float conf, int mode,
+                               int max_batch, float* out, int32_t* counts) {
+  FFP_CHECK(out && counts, FFP_ERR_ARG, "rtdetr: null output");
+  FFP_CHECK(n_tiles > 0 && n_tiles <= 65536, FFP_ERR_ARG, "rtdetr: no tile to run, or too many (n_tiles %d)", n_tiles);
+  upload_frame(frame, H, W);
+  const size_t nd = sizeof(float) * (size_t)n_tiles * RT_NQ * 6;
+  tile_dets_.ensure(nd);
+  tile_counts_.ensure(sizeof(int) * n_tiles);
+  FFP_HIP(hipMemsetAsync(tile_dets_.p, 0, nd, st_));       // rows past a tile's count read as zeros
+  enqueue_tiles(frame_.as<uint8_t>(), H, W, chan_order, tiles, n_tiles, imgsz, conf, mode, max_batch, tile_dets_.as<float>(), tile_counts_.as<int>());
+  FFP_HIP(hipMemcpyAsync(out, tile_dets_.p, nd, hipMemcpyDeviceToHost, st_));
+  FFP_HIP(hipMemcpyAsync(counts, tile_counts_.p, sizeof(int) * n_tiles, hipMemcpyDeviceToHost, st_));
+  FFP_HIP(hipStreamSynchronize(st_));
+}
+
+void RtdetrEngine::sliced_predict(const uint8_t* frame, int H, int W, int chan_order, const std::vector<int32_t>& items, int imgsz, float conf,
+                                  int max_batch, int pp_type, int pp_metric, double pp_thr, int class_agnostic, float* out, int cap, int32_t* out_n) {
+  FFP_CHECK(out && out_n && cap > 0, FFP_ERR_ARG, "rtdetr: sliced_predict needs an output of cap > 0 rows");
+  const int n_tiles = (int)items.size() / 4;
+  FFP_CHECK(n_tiles > 0 && n_tiles <= 65536, FFP_ERR_ARG, "rtdetr: no tile to run, or too many (n_tiles %d)", n_tiles);
+  upload_frame(frame, H, W);
+  tile_dets_.ensure(sizeof(float) * (size_t)n_tiles * RT_NQ * 6);
+  tile_counts_.ensure(sizeof(int) * n_tiles);
+  enqueue_tiles(frame_.as<uint8_t>(), H, W, chan_order, items.data(), n_tiles, imgsz, conf, FFP_RT_TILES_SAHI, max_batch, tile_dets_.as<float>(),
+                tile_counts_.as<int>());
+  const int n_max = n_tiles * RT_NQ;
+  rows_.ensure(sizeof(float) * (size_t)n_max * 6);
+  rows_n_.ensure(sizeof(int));
+  rows_prefix_.ensure(sizeof(int) * (n_tiles + 1));
+  merged_.ensure(sizeof(float) * (size_t)cap * 6);
+  merged_n_.ensure(sizeof(int));
+  launch_compact_rows(tile_dets_.as<float>(), tile_counts_.as<int>(), n_tiles, RT_NQ, 6, rows_.as<float>(), rows_n_.as<int>(), rows_prefix_.as<int>(), st_);
+  int rows = 0;                              // the merge's grid follows the row count: one small read back between the two halves
+  FFP_HIP(hipMemcpyAsync(&rows, rows_n_.p, sizeof(int), hipMemcpyDeviceToHost, st_));
+  FFP_HIP(hipStreamSynchronize(st_));
+  FFP_CHECK(rows >= 0 && rows <= n_max, FFP_ERR_STATE, "rtdetr: %d rows from %d tiles", rows, n_tiles);
+  // one slice: its rows as they are, in query order, like the other engines' fused calls; with more tiles sahi post-processes a list of two or more
+  if (n_tiles > 1 && rows > 1) run_merge(merge_work_, rows_.as<float>(), rows_n_.as<int>(), rows, 6, pp_type, pp_metric, pp_thr, class_agnostic, merged_.as<float>(),
+                          nullptr, merged_n_.as<int>(), cap, st_);
+  else run_merge_passthrough(rows_.as<float>(), rows_n_.as<int>(), 6, merged_.as<float>(), nullptr, merged_n_.as<int>(), cap, st_);   // sahi/predict.py: a list of one is kept
+  int k = 0;
+  FFP_HIP(hipMemcpyAsync(&k, merged_n_.p, sizeof(int), hipMemcpyDeviceToHost, st_));
+  FFP_HIP(hipStreamSynchronize(st_));
+  *out_n = k;
+  FFP_CHECK(k <= cap, FFP_ERR_ARG, "rtdetr: sliced_predict: %d merged detections exceed the output capacity %d (nothing was dropped silently: call again with cap >= %d)", k, cap, k);
+  FFP_HIP(hipMemcpyAsync(out, merged_.p, sizeof(float) * (size_t)k * 6, hipMemcpyDeviceToHost, st_));
   FFP_HIP(hipStreamSynchronize(st_));
 }
 

@@ -431,6 +431,52 @@ __global__ __launch_bounds__(1024) void rt_post_kernel(const float* __restrict__
   if (t == 0) counts[im] = tot;
 }
 
+// rt_post for tiles of one frame: workgroup b handles batch item b of the chunk, whose tile is tiles[b] = {x0, y0, x1, y1} in frame pixels.
+// FFP_RT_TILES_LOCAL writes rt_post's crop-local rows. FFP_RT_TILES_SAHI restates what sahi's Ultralytics wrapper and ObjectAnnotation do
+// to such a row with float boxes: clip the crop-local box against the FULL frame shape, drop it unless x1 < x2 and y1 < y2, then shift it by
+// the tile origin (get_shifted_object_prediction: no second clip). Every step is one rounded fp32 operation (no contraction of the
+// scale-then-shift into an FMA), so a float32 numpy restatement gives the same bits. Rows stay in query order.
+__global__ __launch_bounds__(1024) void rt_post_tiles_kernel(const float* __restrict__ ref, int ref_cs, const float* __restrict__ s, int s_cs, int nc,
+                                                             float conf, const int4* __restrict__ tiles, float full_w, float full_h, int mode,
+                                                             float* __restrict__ det, int* __restrict__ counts) {
+  __shared__ int scan[1024];
+  const int im = blockIdx.x, t = threadIdx.x;
+  const long long qi = (long long)im * RT_NQ + t;
+  float best = 0.f, x1 = 0.f, y1 = 0.f, x2 = 0.f, y2 = 0.f;
+  int cls = 0;
+  bool keep = false;
+  if (t < RT_NQ) {
+    const float* p = s + qi * s_cs;
+    best = sigm(p[0]);
+    for (int c = 1; c < nc; ++c) {
+      const float v = sigm(p[c]);
+      if (v > best) { best = v; cls = c; }
+    }
+    keep = best > conf;
+  }
+  if (keep) {
+    const int4 tl = tiles[im];
+    const float w = (float)(tl.z - tl.x), h = (float)(tl.w - tl.y);
+    const float cx = ref[qi * ref_cs], cy = ref[qi * ref_cs + 1], dw = ref[qi * ref_cs + 2] / 2, dh = ref[qi * ref_cs + 3] / 2;
+    x1 = __fmul_rn(__fsub_rn(cx, dw), w); y1 = __fmul_rn(__fsub_rn(cy, dh), h);
+    x2 = __fmul_rn(__fadd_rn(cx, dw), w); y2 = __fmul_rn(__fadd_rn(cy, dh), h);
+    if (mode == 1) {
+      x1 = fmaxf(x1, 0.f); y1 = fmaxf(y1, 0.f);
+      x2 = fminf(x2, full_w); y2 = fminf(y2, full_h);
+      keep = x1 < x2 && y1 < y2;
+      const float sx = (float)tl.x, sy = (float)tl.y;
+      x1 = __fadd_rn(x1, sx); x2 = __fadd_rn(x2, sx); y1 = __fadd_rn(y1, sy); y2 = __fadd_rn(y2, sy);
+    }
+  }
+  int tot;
+  const int pos = block_excl_scan(keep ? 1 : 0, scan, &tot);
+  if (keep) {
+    float* d = det + ((long long)im * RT_NQ + pos) * 6;
+    d[0] = x1; d[1] = y1; d[2] = x2; d[3] = y2; d[4] = best; d[5] = (float)cls;
+  }
+  if (t == 0) counts[im] = tot;
+}
+
 unsigned nblk(long long n, int b) { return (unsigned)((n + b - 1) / b); }
 
 }  // namespace
@@ -532,6 +578,14 @@ void launch_rt_raw(const TView& ref, const TView& s, int nc, float* raw, hipStre
 void launch_rt_post(const TView& ref, const TView& s, int nc, float conf, const float2* orig_wh, int n, float* det, int* counts, hipStream_t st) {
   hipLaunchKernelGGL(rt_post_kernel, dim3(n), dim3(1024), 0, st, (const float*)ref.ptr + ref.coff, ref.cs, (const float*)s.ptr + s.coff, s.cs, nc, conf,
                      orig_wh, det, counts);
+  FFP_HIP(hipGetLastError());
+}
+
+void launch_rt_post_tiles(const TView& ref, const TView& s, int nc, float conf, const int4* tiles_xyxy, int n, int full_h, int full_w, int mode,
+                          float* det, int* counts, hipStream_t st) {
+  FFP_CHECK(mode == 0 || mode == 1, FFP_ERR_ARG, "rt_post_tiles: mode %d (FFP_RT_TILES_LOCAL or FFP_RT_TILES_SAHI)", mode);
+  hipLaunchKernelGGL(rt_post_tiles_kernel, dim3(n), dim3(1024), 0, st, (const float*)ref.ptr + ref.coff, ref.cs, (const float*)s.ptr + s.coff, s.cs, nc,
+                     conf, tiles_xyxy, (float)full_w, (float)full_h, mode, det, counts);
   FFP_HIP(hipGetLastError());
 }
 

@@ -512,6 +512,14 @@ int ffp_op_rt_deform(int device, int n, const int32_t* hs, const int32_t* ws, co
  * the queries whose best score > conf, in query order, scaled by orig_wh [n][2] = (width, height); rows past out_counts[i] untouched. */
 int ffp_op_rt_decode(int device, int n, int nc, const float* ref, int r_cs, int r_coff, const float* scores, int s_cs, int s_coff, float conf,
                      const float* orig_wh, float* out_raw, float* out_det, int32_t* out_counts);
+/* rt_post_tiles: the same selection for n tiles of one full_h x full_w frame, tiles_xyxy [n][4] = x0, y0, x1, y1 in frame pixels (the scale
+ * is the tile's width and height). mode FFP_RT_TILES_LOCAL: crop-local rows, as ffp_op_rt_decode. mode FFP_RT_TILES_SAHI: what sahi 0.11.x
+ * UltralyticsDetectionModel._create_object_prediction_list_from_original_predictions, ObjectAnnotation and get_shifted_object_prediction do
+ * to such a row, with float boxes: x1 = max(x1, 0), y1 = max(y1, 0), x2 = min(x2, full_w), y2 = min(y2, full_h) (the crop-local box against
+ * the FULL shape), the row dropped unless x1 < x2 and y1 < y2, then + x0 / + y0 with no second clip. Every step is one float32 operation.
+ * out_dets [n][300][6] in/out (rows past out_counts[i] untouched), out_counts [n]; rows in query order. */
+int ffp_op_rt_post_tiles(int device, int n, int nc, const float* ref, int r_cs, int r_coff, const float* scores, int s_cs, int s_coff, float conf,
+                         const int32_t* tiles_xyxy, int full_h, int full_w, int mode, float* out_dets, int32_t* out_counts);
 
 /* SCRFD's pools on a ragged batch (px_align as above): maxpool != 0: MaxPool 3x3 / stride 2 / pad 1 (y images of (h - 1) / 2 + 1);
  * else AveragePool k x k / stride k, ceil_mode, count_include_pad = 0 (y images of ceil(h / k)). */
@@ -640,6 +648,41 @@ int ffp_rtdetr_info(ffp_rtdetr* r, int32_t* out_nc, double* out_last_conv_flops,
 int ffp_rtdetr_set_profile(ffp_rtdetr* r, int on);
 int ffp_rtdetr_profile_count(ffp_rtdetr* r, int32_t* out_n);
 int ffp_rtdetr_profile_get(ffp_rtdetr* r, int i, char* name, int name_cap, float* out_ms);
+
+/* Sliced prediction. Upstream sahi was not available to run against: the box rules below restate sahi 0.11.x from its source, and only
+ * synthetic weights have been run. */
+#define FFP_RT_TILES_LOCAL 0 /* rows in tile-local pixels, exactly ffp_rtdetr_predict's rows of the host crop */
+#define FFP_RT_TILES_SAHI 1  /* rows as sahi's ObjectPrediction list holds them: clipped against the full shape, invalid ones dropped, shifted */
+/* Items per network batch when max_batch <= 0: the fastest measured size whose plans stay under 8 GB (tools/rtdetr_sliced_probe.py on an
+ * MI355X, profiles/rtdetr_sliced_mi355x.json: 61 tiles of a 2160 x 3840 frame at imgsz 640, FFP_PREC_F32 / F32X3 ms per frame and bytes held
+ * by the two plans: 4: 144.0 / 102.6 ms, 2.4 GB; 8: 109.7 / 66.8 ms, 5.1 GB; 16: 88.8 / 48.5 ms, 10.5 GB; 32: 78.9 / 40.0 ms, 20.7 GB).
+ * A caller with the memory to spare passes 16 or 32. */
+#define FFP_RT_TILES_DEFAULT_BATCH 8
+/* n_tiles crops [x0, y0, x1, y1] (frame pixels) of one H x W x 3 uint8 frame, each stretched to imgsz x imgsz exactly as
+ * ffp_rtdetr_predict stretches an image, so a tile's rows in FFP_RT_TILES_LOCAL equal ffp_rtdetr_predict on the host crop (bit for bit in
+ * FFP_PREC_F32). The frame goes up once. Tiles run in ceil(n_tiles / max_batch) chunks of sizes as even as possible (61 at 16: 16, 15, 15,
+ * 15; at the default 8: 8, 8, 8, 8, 8, 7, 7, 7), one plan per chunk size. chan_order as for the YOLO detector (sahi hands RGB arrays: FFP_CHAN_AS_RGB). mode: see
+ * ffp_op_rt_post_tiles. A tile that is empty, inverted or reaches outside the frame is FFP_ERR_ARG naming the tile.
+ * out_dets: [n_tiles][300][6] {x1, y1, x2, y2, score, cls}, query order; out_counts [n_tiles].
+ * (sahi.predict.get_sliced_prediction's loop of get_prediction(slice) -> UltralyticsDetectionModel.perform_inference ->
+ * model(image[:, :, ::-1], imgsz=..., conf=...), sahi/models/ultralytics.py, and the conversion behind it in FFP_RT_TILES_SAHI) */
+int ffp_rtdetr_infer_tiles(ffp_rtdetr* r, const uint8_t* frame_hwc, int H, int W, int chan_order, const int32_t* tiles_xyxy, int n_tiles,
+                           int imgsz, float conf, int mode, int max_batch, float* out_dets, int32_t* out_counts);
+/* the same with the frame and both outputs on the device (tiles_xyxy stays a host pointer); work is enqueued on the engine's stream and the
+ * call returns after that stream has drained, as ffp_det_infer_tiles_dev does */
+int ffp_rtdetr_infer_tiles_dev(ffp_rtdetr* r, const uint8_t* d_frame_hwc, int H, int W, int chan_order, const int32_t* tiles_xyxy, int n_tiles,
+                               int imgsz, float conf, int mode, int max_batch, float* d_out_dets, int32_t* d_out_counts);
+/* sahi.predict.get_sliced_prediction(image, RTDetrDetectionModel, slice_height, slice_width, overlap ratios, perform_standard_pred,
+ * postprocess_type / match_metric / match_threshold / class_agnostic) in one call: the grid of ffp_slice_bboxes, plus the full frame when
+ * there is more than one slice and perform_standard_pred != 0 (sahi/predict.py), ffp_rtdetr_infer_tiles in FFP_RT_TILES_SAHI, rows in
+ * tile order then query order (the order the Python loop appends ObjectPredictions), then the merge of ffp_merge (skipped for one row or
+ * fewer). pp_type: FFP_PP_NMS or FFP_PP_GREEDYNMM. out: [cap][6]; more than cap merged rows is FFP_ERR_ARG with *out_n = the full count. */
+int ffp_rtdetr_sliced_predict(ffp_rtdetr* r, const uint8_t* frame_hwc, int H, int W, int chan_order, int slice_h, int slice_w,
+                              float overlap_h_ratio, float overlap_w_ratio, int perform_standard_pred, int imgsz, float conf, int max_batch,
+                              int pp_type, int pp_metric, double pp_thr, int class_agnostic, float* out, int cap, int32_t* out_n);
+/* device bytes held by the resident plans' activations and how many plans are resident (at most 4); ffp_rtdetr_drop_plans releases them */
+int ffp_rtdetr_mem_bytes(ffp_rtdetr* r, uint64_t* out_plan_bytes, int32_t* out_plans_resident);
+int ffp_rtdetr_drop_plans(ffp_rtdetr* r);
 
 /* ---------------------------------------------------------------------------------------------------------
  * No-reference image quality: NIQE — replaces pyiqa.create_metric('niqe', device=...) and the call of the metric on an image
