@@ -176,6 +176,20 @@ _SIGS = {
     "ffp_scrfd_describe": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
     "ffp_scrfd_infer_tiles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _p(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_float,
                                         C.c_float, _p(C.c_float), C.c_int, _p(C.c_int32)]),
+    "ffp_scrfd_infer_tiles_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _p(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_float,
+                                           C.c_float, C.c_float, C.c_int, C.c_int, _p(C.c_float), C.c_int, _p(C.c_int32)]),
+    "ffp_scrfd_infer_tiles_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _p(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_float,
+                                            C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "ffp_scrfd_sliced_predict": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int,
+                                           C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
+                                           _p(C.c_float), C.c_int, _p(C.c_int32)]),
+    "ffp_scrfd_sliced_predict_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int,
+                                               C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
+                                               C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "ffp_scrfd_mem_bytes": (C.c_int, [C.c_void_p, _p(C.c_uint64), _p(C.c_int32)]),
+    "ffp_scrfd_drop_plans": (C.c_int, [C.c_void_p]),
+    "ffp_op_scrfd_sahi_rows": (C.c_int, [C.c_int, C.c_int, C.c_int, _p(C.c_int32), C.c_int, C.c_int, C.c_float, _p(C.c_float), _p(C.c_int32),
+                                         _p(C.c_int32)]),
     "ffp_scrfd_forward_raw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _p(C.c_int32), C.c_int, C.c_int, C.c_int, _p(C.c_float),
                                         C.c_size_t, _p(C.c_int64)]),
     "ffp_scrfd_info": (C.c_int, [C.c_void_p, _p(C.c_int32), _p(C.c_double)]),
@@ -338,22 +352,87 @@ class FaceDetector:
         _check(lib().ffp_scrfd_info(self._h, None, C.byref(f)))
         return float(f.value)
 
+    TILE_MODES = {"local": 0, "sahi": 1}         # FFP_SCRFD_TILES_LOCAL, FFP_SCRFD_TILES_SAHI
+
     def infer_tiles(self, frame: np.ndarray, tiles: Sequence[Sequence[int]], det_size=(640, 640), det_thresh: float = 0.5,
-                    nms_thresh: float = 0.4, chan_order: int = CHAN_AS_BGR, cap: int = 1024) -> List[np.ndarray]:
-        """-> per tile (n_i, 21) float32 rows [x1,y1,x2,y2,score,0, 5 x (x,y,1)] in tile-local pixels (not truncated)."""
+                    nms_thresh: float = 0.4, chan_order: int = CHAN_AS_BGR, cap: int = 1024, *, conf: Optional[float] = None, mode: str = "local",
+                    max_batch: int = 0) -> List[np.ndarray]:
+        """-> per tile (n_i, 21) float32 rows [x1,y1,x2,y2,score,0, 5 x (x,y,1)] in tile-local pixels (not truncated).
+        mode "sahi" (ffp_scrfd_infer_tiles_ex): rows with score < conf (default det_thresh) skipped, boxes int-truncated, clipped against the
+        frame and shifted to frame pixels with their keypoints; a box whose far corner is negative raises FfpError, as the reference raises.
+        max_batch: items per network batch (0: all tiles in one; < 0: FFP_SCRFD_TILES_DEFAULT_BATCH)."""
         f = _as_frame(frame)
         t = np.ascontiguousarray(np.asarray(tiles, np.int32).reshape(-1, 4))
         n = t.shape[0]
+        plain = conf is None and mode == "local" and max_batch == 0
         while True:
-            dets = np.zeros((n, cap, self.STRIDE), np.float32)
-            counts = np.zeros(n, np.int32)
-            rc = lib().ffp_scrfd_infer_tiles(self._h, f.ctypes.data, f.shape[0], f.shape[1], chan_order, _ip(t), n, int(det_size[0]),
-                                             int(det_size[1]), det_thresh, nms_thresh, _fp(dets), cap, _ip(counts))
+            dets = np.zeros((max(n, 1), cap, self.STRIDE), np.float32)
+            counts = np.zeros(max(n, 1), np.int32)
+            if plain:
+                rc = lib().ffp_scrfd_infer_tiles(self._h, f.ctypes.data, f.shape[0], f.shape[1], chan_order, _ip(t), n, int(det_size[0]),
+                                                 int(det_size[1]), det_thresh, nms_thresh, _fp(dets), cap, _ip(counts))
+            else:
+                rc = lib().ffp_scrfd_infer_tiles_ex(self._h, f.ctypes.data, f.shape[0], f.shape[1], chan_order, _ip(t), n, int(det_size[0]),
+                                                    int(det_size[1]), det_thresh, nms_thresh, det_thresh if conf is None else conf,
+                                                    self.TILE_MODES[mode], max_batch, _fp(dets), cap, _ip(counts))
             if rc != 0 and int(counts.max(initial=0)) > cap:
                 cap = int(counts.max())                # out_counts are not capped: retry once with room for every face
                 continue
             _check(rc)
             return [dets[i, :counts[i]].copy() for i in range(n)]
+
+    def infer_tiles_dev(self, d_frame: int, H: int, W: int, tiles: Sequence[Sequence[int]], d_out: int, cap: int, d_counts: int, det_size=(640, 640),
+                        det_thresh: float = 0.5, nms_thresh: float = 0.4, chan_order: int = CHAN_AS_BGR, conf: Optional[float] = None,
+                        mode: str = "local", max_batch: int = 0):
+        """infer_tiles with the frame (H x W x 3 uint8), d_out [n][cap][21] float32 and d_counts [n] int32 given as device pointers
+        (ffp_scrfd_infer_tiles_dev). Returns after the engine's stream has drained."""
+        t = np.ascontiguousarray(np.asarray(tiles, np.int32).reshape(-1, 4))
+        _check(lib().ffp_scrfd_infer_tiles_dev(self._h, d_frame, H, W, chan_order, _ip(t), t.shape[0], int(det_size[0]), int(det_size[1]), det_thresh,
+                                               nms_thresh, det_thresh if conf is None else conf, self.TILE_MODES[mode], max_batch, d_out, cap,
+                                               d_counts))
+
+    def _sliced_args(self, H, W, slice_h, slice_w, overlap_h, overlap_w, perform_standard_pred, det_size, det_thresh, nms_thresh, conf, max_batch,
+                     tile_cap, pp_type, pp_metric, pp_thr, class_agnostic, chan_order):
+        return (H, W, chan_order, slice_h, slice_w, overlap_h, overlap_w, int(perform_standard_pred), int(det_size[0]), int(det_size[1]), det_thresh,
+                nms_thresh, det_thresh if conf is None else conf, max_batch, tile_cap, PP_TYPES[pp_type], METRICS[pp_metric], float(pp_thr),
+                int(class_agnostic))
+
+    def sliced_predict(self, frame: np.ndarray, slice_h: int, slice_w: int, overlap_h: float = 0.2, overlap_w: float = 0.2,
+                       perform_standard_pred: bool = True, det_size=(640, 640), det_thresh: float = 0.5, nms_thresh: float = 0.4,
+                       conf: Optional[float] = None, pp_type: str = "GREEDYNMM", pp_metric: str = "IOS", pp_thr: float = 0.5,
+                       class_agnostic: bool = False, chan_order: int = CHAN_AS_BGR, max_batch: int = -1, tile_cap: int = 1024, cap: int = 4096) -> np.ndarray:
+        """Fused get_sliced_prediction over InsightFaceDetectionModel (ffp_scrfd_sliced_predict) -> (k, 21) float32 rows in frame pixels: integer
+        boxes stored as floats, score, 0, and the keypoints of the higher-scored source row. conf: the wrapper's confidence_threshold (default
+        det_thresh). max_batch: items per network batch (0: all in one; < 0: FFP_SCRFD_TILES_DEFAULT_BATCH)."""
+        f = _as_frame(frame)
+        H, W = f.shape[:2]
+        out = np.zeros((cap, self.STRIDE), np.float32)
+        n = C.c_int32(0)
+        _check(lib().ffp_scrfd_sliced_predict(self._h, f.ctypes.data, *self._sliced_args(H, W, slice_h, slice_w, overlap_h, overlap_w, perform_standard_pred,
+                                                                                         det_size, det_thresh, nms_thresh, conf, max_batch, tile_cap, pp_type,
+                                                                                         pp_metric, pp_thr, class_agnostic, chan_order),
+                                              _fp(out), cap, C.byref(n)))
+        return out[:n.value].copy()
+
+    def sliced_predict_dev(self, d_frame: int, H: int, W: int, d_out: int, cap: int, d_out_n: int, slice_h: int, slice_w: int, overlap_h: float = 0.2,
+                           overlap_w: float = 0.2, perform_standard_pred: bool = True, det_size=(640, 640), det_thresh: float = 0.5,
+                           nms_thresh: float = 0.4, conf: Optional[float] = None, pp_type: str = "GREEDYNMM", pp_metric: str = "IOS", pp_thr: float = 0.5,
+                           class_agnostic: bool = False, chan_order: int = CHAN_AS_BGR, max_batch: int = -1, tile_cap: int = 1024):
+        """sliced_predict with the frame, d_out [cap][21] float32 and d_out_n [1] int32 given as device pointers (ffp_scrfd_sliced_predict_dev).
+        *d_out_n is the untruncated merged count: above cap the result has overflowed (the rule of ffp_merge_dev)."""
+        _check(lib().ffp_scrfd_sliced_predict_dev(self._h, d_frame, *self._sliced_args(H, W, slice_h, slice_w, overlap_h, overlap_w, perform_standard_pred,
+                                                                                       det_size, det_thresh, nms_thresh, conf, max_batch, tile_cap, pp_type,
+                                                                                       pp_metric, pp_thr, class_agnostic, chan_order),
+                                                  d_out, cap, d_out_n))
+
+    def mem_bytes(self) -> dict:
+        """Device bytes held by the resident plans, and how many plans are resident."""
+        b, n = C.c_uint64(0), C.c_int32(0)
+        _check(lib().ffp_scrfd_mem_bytes(self._h, C.byref(b), C.byref(n)))
+        return {"plans": int(b.value), "plans_resident": int(n.value)}
+
+    def drop_plans(self):
+        _check(lib().ffp_scrfd_drop_plans(self._h))
 
     def forward_raw(self, frame: np.ndarray, tiles: Sequence[Sequence[int]], det_size=(640, 640),
                     chan_order: int = CHAN_AS_BGR) -> List[List[np.ndarray]]:
@@ -1268,6 +1347,24 @@ def op_scrfd_post(net_hw, A: int, score, bbox, kps, coffs, det_scale, thresh: fl
     _check(lib().ffp_op_scrfd_post(device, n, net_h, net_w, A, _ip(st), px_align, ptrs, _ip(cs), _ip(co), _fp(ds), thresh, nms_thresh, o.shape[1], _fp(o),
                                    _ip(cnt), _fp(rs) if rs is not None else None))
     return (o, cnt, rs) if raw_scores else (o, cnt)
+
+
+def op_scrfd_sahi_rows(dets: np.ndarray, counts, tiles, full_shape, conf: float, device: int = 0):
+    """ffp_op_scrfd_sahi_rows on dets (n, cap, 21) / counts (n) / tiles (n, 4) of a full_shape = (h, w) frame -> (dets, counts, bad): copies
+    after the kernel, bad = None or the first (tile, row) whose far corner is negative after the clip (the C entry returns FFP_ERR_ARG there)."""
+    d = np.ascontiguousarray(dets, np.float32).copy()
+    n, cap = d.shape[0], d.shape[1]
+    if d.ndim != 3 or d.shape[2] != FaceDetector.STRIDE:
+        raise ValueError(f"dets must be (n, cap, {FaceDetector.STRIDE})")
+    c = np.ascontiguousarray(counts, np.int32).copy()
+    t = np.ascontiguousarray(np.asarray(tiles, np.int32).reshape(-1, 4))
+    if c.shape != (n,) or t.shape != (n, 4):
+        raise ValueError("counts / tiles do not match dets")
+    bad = C.c_int32(-1)
+    rc = lib().ffp_op_scrfd_sahi_rows(device, n, cap, _ip(t), int(full_shape[0]), int(full_shape[1]), conf, _fp(d), _ip(c), C.byref(bad))
+    if rc != 0 and bad.value < 0:
+        _check(rc)
+    return d, c, (None if bad.value < 0 else (bad.value // cap, bad.value % cap))
 
 
 def jpeg_encode(img: np.ndarray, quality: int = 95, bgr: bool = False, device: int = 0) -> bytes:

@@ -73,6 +73,14 @@ std::vector<int32_t> slice_bboxes(int H, int W, int sh, int sw, float oh, float 
   return out;
 }
 
+// the items of get_sliced_prediction: the slice grid, then the full frame when there is more than one slice and it is asked for
+std::vector<int32_t> sliced_items(int H, int W, int slice_h, int slice_w, float oh, float ow, int perform_standard_pred) {
+  FFP_CHECK(H > 0 && W > 0, FFP_ERR_ARG, "frame is empty");
+  std::vector<int32_t> items = slice_bboxes(H, W, slice_h, slice_w, oh, ow);
+  if (items.size() / 4 > 1 && perform_standard_pred) items.insert(items.end(), {0, 0, W, H});   // sahi/predict.py: the full-frame pass
+  return items;
+}
+
 void upload_frame(DetEngine& e, const uint8_t* frame, int H, int W) {
   FFP_CHECK(frame && H > 0 && W > 0, FFP_ERR_ARG, "frame is null or empty");
   FFP_HIP(hipSetDevice(e.device()));
@@ -2027,6 +2035,30 @@ int ffp_op_scrfd_post(int device, int n, int net_h, int net_w, int A, const int3
   FFP_API_END
 }
 
+int ffp_op_scrfd_sahi_rows(int device, int n_tiles, int cap, const int32_t* tiles_xyxy, int full_h, int full_w, float conf, float* dets,
+                           int32_t* counts, int32_t* out_bad) {
+  FFP_API_BEGIN
+  FFP_CHECK(tiles_xyxy && dets && counts, FFP_ERR_ARG, "scrfd_sahi_rows: null argument");
+  FFP_CHECK(n_tiles >= 1 && n_tiles <= 65536 && cap >= 1 && cap <= (1 << 20) && (long long)n_tiles * cap < (1 << 24) && full_h >= 1 && full_w >= 1, FFP_ERR_ARG,
+            "scrfd_sahi_rows: bad sizes");
+  if (out_bad) *out_bad = -1;
+  OpCtx cx(device, "scrfd_sahi_rows");
+  const size_t nd = (size_t)n_tiles * cap * FFP_DET_STRIDE(5);
+  DevBuf dd = upload(dets, nd), dc = upload(counts, (size_t)n_tiles), dt = upload(tiles_xyxy, (size_t)n_tiles * 4), de(sizeof(unsigned));
+  launch_scrfd_sahi_rows(dd.as<float>(), dc.as<int>(), dt.as<int4>(), n_tiles, cap, conf, full_h, full_w, de.as<unsigned>(), cx.st);
+  FFP_HIP(hipStreamSynchronize(cx.st));
+  op_fetch(dd, dets, nd);
+  FFP_HIP(hipMemcpy(counts, dc.p, sizeof(int) * (size_t)n_tiles, hipMemcpyDeviceToHost));
+  unsigned bad = SCRFD_NO_BAD_ROW;
+  FFP_HIP(hipMemcpy(&bad, de.p, sizeof(unsigned), hipMemcpyDeviceToHost));
+  if (bad != SCRFD_NO_BAD_ROW) {
+    if (out_bad) *out_bad = (int32_t)bad;
+    FFP_CHECK(false, FFP_ERR_ARG, "scrfd_sahi_rows: tile %d row %d: Box coords [minx, miny, maxx, maxy] cannot be negative", (int)(bad / (unsigned)cap),
+              (int)(bad % (unsigned)cap));
+  }
+  FFP_API_END
+}
+
 // tuning hook: average device time (HIP events) of `iters` launches of one dense convolution on synthetic data
 int ffp_op_conv2d_time(int device, int precision, int n, int h, int w, int cin, int cout, int k, int stride, int up, int iters,
                        int dbg_mask, int force_shape, float* out_us) {
@@ -2166,6 +2198,65 @@ int ffp_scrfd_infer_tiles(ffp_scrfd* s, const uint8_t* frame, int H, int W, int 
   FFP_API_BEGIN
   FFP_CHECK(s, FFP_ERR_ARG, "null handle");
   s->eng.infer_tiles(frame, H, W, chan_order, tiles, n_tiles, det_w, det_h, det_thresh, nms_thresh, out_dets, cap, out_counts);
+  FFP_API_END
+}
+
+// the batched detector call behind InsightFaceDetectionModel.perform_inference_batch, in bounded chunks, and (FFP_SCRFD_TILES_SAHI) the
+// per-face Python behind it: utils/insightface_wrapper.py:83-86, sahi/annotation.py and get_shifted_object_prediction
+int ffp_scrfd_infer_tiles_ex(ffp_scrfd* s, const uint8_t* frame, int H, int W, int chan_order, const int32_t* tiles, int n_tiles, int det_w, int det_h,
+                             float det_thresh, float nms_thresh, float conf, int mode, int max_batch, float* out_dets, int cap, int32_t* out_counts) {
+  FFP_API_BEGIN
+  FFP_CHECK(s, FFP_ERR_ARG, "null handle");
+  s->eng.infer_tiles_ex(frame, H, W, chan_order, tiles, n_tiles, det_w, det_h, det_thresh, nms_thresh, conf, mode, max_batch, out_dets, cap, out_counts);
+  FFP_API_END
+}
+
+int ffp_scrfd_infer_tiles_dev(ffp_scrfd* s, const uint8_t* d_frame, int H, int W, int chan_order, const int32_t* tiles, int n_tiles, int det_w,
+                              int det_h, float det_thresh, float nms_thresh, float conf, int mode, int max_batch, float* d_out_dets, int cap,
+                              int32_t* d_out_counts) {
+  FFP_API_BEGIN
+  FFP_CHECK(s, FFP_ERR_ARG, "null handle");
+  s->eng.infer_tiles_dev(d_frame, H, W, chan_order, tiles, n_tiles, det_w, det_h, det_thresh, nms_thresh, conf, mode, max_batch, d_out_dets, cap,
+                         d_out_counts);
+  FFP_API_END
+}
+
+// sahi.predict.get_sliced_prediction over InsightFaceDetectionModel (pipeline_v1_detection_first/app_v1.py's detector stage) in one call
+int ffp_scrfd_sliced_predict(ffp_scrfd* s, const uint8_t* frame, int H, int W, int chan_order, int slice_h, int slice_w, float oh, float ow,
+                             int perform_standard_pred, int det_w, int det_h, float det_thresh, float nms_thresh, float conf, int max_batch,
+                             int tile_cap, int pp_type, int pp_metric, double pp_thr, int class_agnostic, float* out, int cap, int32_t* out_n) {
+  FFP_API_BEGIN
+  FFP_CHECK(s && frame && out && out_n && cap > 0, FFP_ERR_ARG, "null argument");
+  s->eng.sliced_predict(frame, H, W, chan_order, sliced_items(H, W, slice_h, slice_w, oh, ow, perform_standard_pred), det_w, det_h, det_thresh,
+                        nms_thresh, conf, max_batch, tile_cap, pp_type, pp_metric, pp_thr, class_agnostic, out, cap, out_n);
+  FFP_API_END
+}
+
+int ffp_scrfd_sliced_predict_dev(ffp_scrfd* s, const uint8_t* d_frame, int H, int W, int chan_order, int slice_h, int slice_w, float oh, float ow,
+                                 int perform_standard_pred, int det_w, int det_h, float det_thresh, float nms_thresh, float conf, int max_batch,
+                                 int tile_cap, int pp_type, int pp_metric, double pp_thr, int class_agnostic, float* d_out, int cap, int32_t* d_out_n) {
+  FFP_API_BEGIN
+  FFP_CHECK(s && d_frame && d_out && d_out_n && cap > 0, FFP_ERR_ARG, "null argument");
+  s->eng.sliced_predict_dev(d_frame, H, W, chan_order, sliced_items(H, W, slice_h, slice_w, oh, ow, perform_standard_pred), det_w, det_h, det_thresh,
+                            nms_thresh, conf, max_batch, tile_cap, pp_type, pp_metric, pp_thr, class_agnostic, d_out, cap, d_out_n);
+  FFP_API_END
+}
+
+int ffp_scrfd_mem_bytes(ffp_scrfd* s, uint64_t* out_plan_bytes, int32_t* out_plans_resident) {
+  FFP_API_BEGIN
+  FFP_CHECK(s, FFP_ERR_ARG, "null handle");
+  size_t b = 0;
+  int n = 0;
+  s->eng.mem_bytes(&b, &n);
+  if (out_plan_bytes) *out_plan_bytes = b;
+  if (out_plans_resident) *out_plans_resident = n;
+  FFP_API_END
+}
+
+int ffp_scrfd_drop_plans(ffp_scrfd* s) {
+  FFP_API_BEGIN
+  FFP_CHECK(s, FFP_ERR_ARG, "null handle");
+  s->eng.drop_plans();
   FFP_API_END
 }
 

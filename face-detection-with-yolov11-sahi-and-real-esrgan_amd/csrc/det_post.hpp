@@ -40,8 +40,11 @@ struct MergeWork {            // device scratch, grown on demand
 };
 // d_rows: device [*d_n][stride] (first six x1,y1,x2,y2,score,class), *d_n <= n_max (grid bound).
 // d_out: device [cap][stride]; d_out_src [cap] (may be null): index of the source row of each output; d_out_n[1].
+// Rows from clip_first_row on carry sahi's full_shape (the full-frame prediction, which is not shifted and keeps it): a GREEDYNMM union
+// kept by such a row is clipped to x2 <= clip_w, y2 <= clip_h after every merge, as ObjectAnnotation clips it. Default: no such row.
 void run_merge(MergeWork& w, const float* d_rows, const int* d_n, int n_max, int stride, int type, int metric, double thr,
-               int class_agnostic, float* d_out, int* d_out_src, int* d_out_n, int cap, hipStream_t st);
+               int class_agnostic, float* d_out, int* d_out_src, int* d_out_n, int cap, hipStream_t st, int clip_first_row = 0x7fffffff,
+               int clip_w = 0, int clip_h = 0);
 void run_merge_passthrough(const float* d_rows, const int* d_n, int stride, float* d_out, int* d_out_src, int* d_out_n, int cap,
                            hipStream_t st);
 // gather fixed-cap per-slice detections [n_slices][max_det][stride] into a compact row list (slice order, then kept

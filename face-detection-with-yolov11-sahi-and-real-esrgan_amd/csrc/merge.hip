@@ -131,11 +131,14 @@ __device__ __forceinline__ bool has_match_f64(const double* c, const float4& o, 
   return v > thr;
 }
 
+// CLIP: some rows carry sahi's full_shape (run_merge's clip_first_row); without it the kernel is the plain sweep
+template <bool CLIP>
 __global__ void __launch_bounds__(64) merge_sweep_kernel(const float4* __restrict__ sbox, const float* __restrict__ sscore,
                                                          const int* __restrict__ d_n, int nws, int type, int metric, double thr,
                                                          const unsigned long long* __restrict__ mask, float4* __restrict__ kbox,
                                                          float* __restrict__ kscore, int* __restrict__ ksrc,
-                                                         int* __restrict__ d_k) {
+                                                         int* __restrict__ d_k, const int* __restrict__ order, int clip_first_row,
+                                                         double clip_w, double clip_h) {
   extern __shared__ unsigned long long alive[];
   const int n = *d_n;
   const int lane = threadIdx.x;
@@ -154,6 +157,9 @@ __global__ void __launch_bounds__(64) merge_sweep_kernel(const float4* __restric
     cur[0] = bi.x; cur[1] = bi.y; cur[2] = bi.z; cur[3] = bi.w;
     float cscore = sscore[i];
     int csrc = i;
+    // a keeper that carries a full_shape (sahi's full-frame prediction): merge_object_prediction_pair builds the union as an
+    // ObjectPrediction with that shape, which clips it, and the next has_match sees the clipped box
+    const bool clip = CLIP && order[i] >= clip_first_row;
     const int w0 = i >> 6;
     for (int base = w0; base < nw; base += 64) {
       const int w = base + lane;
@@ -180,6 +186,7 @@ __global__ void __launch_bounds__(64) merge_sweep_kernel(const float4* __restric
             if (has_match_f64(cur, bj, metric, thr)) {
               cur[0] = fmin(cur[0], (double)bj.x); cur[1] = fmin(cur[1], (double)bj.y);
               cur[2] = fmax(cur[2], (double)bj.z); cur[3] = fmax(cur[3], (double)bj.w);
+              if (clip) { cur[2] = fmin(cur[2], clip_w); cur[3] = fmin(cur[3], clip_h); }
               const float sj = sscore[j];
               if (!(cscore > sj)) csrc = j;
               cscore = fmaxf(cscore, sj);
@@ -241,7 +248,7 @@ void launch_compact_rows(const float* d_dets, const int* d_counts, int n_slices,
 }
 
 void run_merge(MergeWork& w, const float* d_rows, const int* d_n, int n_max, int stride, int type, int metric, double thr,
-               int class_agnostic, float* d_out, int* d_out_src, int* d_out_n, int cap, hipStream_t st) {
+               int class_agnostic, float* d_out, int* d_out_src, int* d_out_n, int cap, hipStream_t st, int clip_first_row, int clip_w, int clip_h) {
   FFP_CHECK(type == FFP_PP_NMS || type == FFP_PP_GREEDYNMM, FFP_ERR_ARG, "merge: postprocess type %d not implemented", type);
   FFP_CHECK(metric == FFP_METRIC_IOU || metric == FFP_METRIC_IOS, FFP_ERR_ARG, "merge: metric %d", metric);
   FFP_CHECK(n_max < (1 << 24), FFP_ERR_ARG, "merge: %d boxes exceed 2^24", n_max);
@@ -264,9 +271,10 @@ void run_merge(MergeWork& w, const float* d_rows, const int* d_n, int n_max, int
                      w.keys.as<unsigned long long>(), w.order.as<int>(), w.sbox.as<float4>(), w.sscore.as<float>(), w.scat.as<int>());
   hipLaunchKernelGGL(merge_mask_kernel, dim3(nws, nws), dim3(64), 0, st, w.sbox.as<float4>(), w.scat.as<int>(), d_n, nws, metric,
                      (float)thr, class_agnostic, w.mask.as<unsigned long long>());
-  hipLaunchKernelGGL(merge_sweep_kernel, dim3(1), dim3(64), sizeof(unsigned long long) * (size_t)nws, st, w.sbox.as<float4>(),
+  const auto sweep = clip_first_row != 0x7fffffff ? merge_sweep_kernel<true> : merge_sweep_kernel<false>;
+  hipLaunchKernelGGL(sweep, dim3(1), dim3(64), sizeof(unsigned long long) * (size_t)nws, st, w.sbox.as<float4>(),
                      w.sscore.as<float>(), d_n, nws, type, metric, thr, w.mask.as<unsigned long long>(), w.kbox.as<float4>(),
-                     w.kscore.as<float>(), w.ksrc.as<int>(), w.dk.as<int>());
+                     w.kscore.as<float>(), w.ksrc.as<int>(), w.dk.as<int>(), w.order.as<int>(), clip_first_row, (double)clip_w, (double)clip_h);
   hipLaunchKernelGGL(merge_emit_kernel, dim3((n_max + 255) / 256), dim3(256), 0, st, d_rows, stride, w.order.as<int>(),
                      w.kbox.as<float4>(), w.kscore.as<float>(), w.ksrc.as<int>(), w.dk.as<int>(), cap, d_out, d_out_src, d_out_n);
   FFP_HIP(hipGetLastError());

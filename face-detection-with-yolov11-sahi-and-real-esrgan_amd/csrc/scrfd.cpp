@@ -153,32 +153,44 @@ ScrfdPlan* ScrfdEngine::prepare(const uint8_t* frame, int H, int W, int chan_ord
   FFP_CHECK(det_w % 32 == 0 && det_h % 32 == 0 && det_w >= 32 && det_h >= 32, FFP_ERR_ARG, "scrfd: det size %dx%d must be multiples of 32", det_w, det_h);
   FFP_HIP(hipSetDevice(device_));
   ScrfdPlan* P = plan_for(n_tiles, det_w, det_h);
-  const int nw_ = P->low.det_w, nh_ = P->low.det_h;     // a fixed input size of the file wins
-  std::vector<LetterboxImg> lb(n_tiles);
-  std::vector<float> sc(n_tiles);
+  tile_geometry(*P, H, W, tiles, n_tiles);
+  upload_frame(frame, H, W);
+  run_chunk(P, frame_.as<uint8_t>(), W, chan_order, 0, n_tiles);
+  FFP_HIP(hipStreamSynchronize(st_));
+  return P;
+}
+
+void ScrfdEngine::tile_geometry(const ScrfdPlan& first, int H, int W, const int32_t* tiles, int n_tiles) {
+  const int nw_ = first.low.det_w, nh_ = first.low.det_h;     // a fixed input size of the file wins
+  h_lb_.resize(n_tiles);
+  h_scale_.resize(n_tiles);
   for (int i = 0; i < n_tiles; ++i) {
     const int x0 = tiles[4 * i], y0 = tiles[4 * i + 1], x1 = tiles[4 * i + 2], y1 = tiles[4 * i + 3];
     FFP_CHECK(x0 >= 0 && y0 >= 0 && x1 <= W && y1 <= H && x1 > x0 && y1 > y0, FFP_ERR_ARG, "tile %d [%d,%d,%d,%d] outside %dx%d frame", i, x0, y0,
               x1, y1, W, H);
-    LetterboxImg& L = lb[i];
+    LetterboxImg& L = h_lb_[i];
     L.x0 = x0; L.y0 = y0; L.sw = x1 - x0; L.sh = y1 - y0;
-    scrfd_geometry(L.sh, L.sw, nw_, nh_, &L.new_w, &L.new_h, &sc[i]);
+    scrfd_geometry(L.sh, L.sw, nw_, nh_, &L.new_w, &L.new_h, &h_scale_[i]);
     FFP_CHECK(L.new_w > 0 && L.new_h > 0, FFP_ERR_ARG, "tile %d (%dx%d) resizes to %dx%d at net size %dx%d (cv2.resize would raise)", i, L.sw, L.sh,
               L.new_w, L.new_h, nw_, nh_);
     L.top = 0; L.left = 0; L.net_h = nh_; L.net_w = nw_;
   }
+}
+
+void ScrfdEngine::upload_frame(const uint8_t* frame, int H, int W) {
   const size_t fb = (size_t)H * W * 3;
   frame_.ensure(fb);
   FFP_HIP(hipMemcpyAsync(frame_.p, frame, fb, hipMemcpyHostToDevice, st_));
-  FFP_HIP(hipMemcpyAsync(P->d_lb.p, lb.data(), sizeof(LetterboxImg) * n_tiles, hipMemcpyHostToDevice, st_));
-  FFP_HIP(hipMemcpyAsync(P->d_scale.p, sc.data(), sizeof(float) * n_tiles, hipMemcpyHostToDevice, st_));
+}
+
+void ScrfdEngine::run_chunk(ScrfdPlan* P, const uint8_t* d_frame, int W, int chan_order, int off, int m) {
+  FFP_HIP(hipMemcpyAsync(P->d_lb.p, h_lb_.data() + off, sizeof(LetterboxImg) * m, hipMemcpyHostToDevice, st_));
+  FFP_HIP(hipMemcpyAsync(P->d_scale.p, h_scale_.data() + off, sizeof(float) * m, hipMemcpyHostToDevice, st_));
   const int flip = chan_order == FFP_CHAN_AS_BGR ? 1 : 0;
-  launch_scrfd_preproc(frame_.as<uint8_t>(), W, flip, P->d_lb.as<LetterboxImg>(), P->views[P->low.input_buf], st_);
+  launch_scrfd_preproc(d_frame, W, flip, P->d_lb.as<LetterboxImg>(), P->views[P->low.input_buf], st_);
   P->execute(st_, nullptr);
   last_conv_flops = P->conv_flops;
   last_graph_state = P->graph_state();
-  FFP_HIP(hipStreamSynchronize(st_));       // lb / sc are stack vectors
-  return P;
 }
 
 void ScrfdEngine::infer_tiles(const uint8_t* frame, int H, int W, int chan_order, const int32_t* tiles, int n_tiles, int det_w, int det_h,
@@ -242,6 +254,158 @@ void ScrfdEngine::forward_raw(const uint8_t* frame, int H, int W, int chan_order
       o += out_sizes[k];
     }
   }
+}
+
+// ---- tiles of one frame in chunks, and sahi's get_sliced_prediction over InsightFaceDetectionModel in one call ------------------------
+
+std::vector<int> ScrfdEngine::chunk_sizes(int n, int max_batch) {
+  if (max_batch < 0) max_batch = SCRFD_TILES_DEFAULT_BATCH;
+  if (max_batch == 0 || max_batch > n) max_batch = n;
+  const int chunks = max_batch ? (n + max_batch - 1) / max_batch : 0;
+  std::vector<int> v(chunks, chunks ? n / chunks : 0);
+  for (int i = 0; i < (chunks ? n % chunks : 0); ++i) ++v[i];      // 13 at 5: 5, 4, 4
+  return v;
+}
+
+void ScrfdEngine::mem_bytes(size_t* plans, int* resident) const {
+  *plans = plan_bytes();
+  *resident = (int)plans_.size();
+}
+
+void ScrfdEngine::drop_plans() {
+  FFP_HIP(hipSetDevice(device_));
+  FFP_HIP(hipStreamSynchronize(st_));
+  plans_.clear();
+}
+
+void ScrfdEngine::enqueue_tiles(const uint8_t* d_frame, int H, int W, int chan_order, const int32_t* tiles, int n_tiles, int det_w, int det_h,
+                                float det_thresh, float nms_thresh, float conf, int mode, int max_batch, float* d_out, int cap, int32_t* d_out_counts) {
+  FFP_CHECK(d_frame && H > 0 && W > 0 && tiles && n_tiles > 0, FFP_ERR_ARG, "scrfd: empty frame or tile list");
+  FFP_CHECK(d_out && d_out_counts && cap >= 1, FFP_ERR_ARG, "scrfd: cap must be >= 1 and outputs non-null");
+  FFP_CHECK((long long)n_tiles * cap < (1ll << 31) / FFP_DET_STRIDE(5), FFP_ERR_ARG, "scrfd: %d tiles of %d rows", n_tiles, cap);
+  FFP_CHECK(det_w % 32 == 0 && det_h % 32 == 0 && det_w >= 32 && det_h >= 32, FFP_ERR_ARG, "scrfd: det size %dx%d must be multiples of 32", det_w, det_h);
+  FFP_CHECK(chan_order == FFP_CHAN_AS_BGR || chan_order == FFP_CHAN_AS_RGB, FFP_ERR_ARG, "scrfd: chan_order %d", chan_order);
+  FFP_CHECK(mode == FFP_SCRFD_TILES_LOCAL || mode == FFP_SCRFD_TILES_SAHI, FFP_ERR_ARG, "scrfd: tile mode %d (FFP_SCRFD_TILES_LOCAL or FFP_SCRFD_TILES_SAHI)",
+            mode);
+  FFP_HIP(hipSetDevice(device_));
+  const std::vector<int> chunks = chunk_sizes(n_tiles, max_batch);
+  tile_geometry(*plan_for(chunks[0], det_w, det_h), H, W, tiles, n_tiles);
+  int off = 0;
+  for (int m : chunks) {
+    ScrfdPlan* P = plan_for(m, det_w, det_h);        // an eviction waits for the stream first
+    run_chunk(P, d_frame, W, chan_order, off, m);
+    const ScrfdHeads& h = P->heads;
+    launch_scrfd_decode(h, m, det_thresh, P->d_cand.as<ScrfdCand>(), P->d_counts.as<int>(), nullptr, st_);
+    // straight into the call-wide buffers at the chunk's tile offset
+    launch_scrfd_nms(P->d_cand.as<ScrfdCand>(), P->d_counts.as<int>(), m, h.per_img, P->d_order.as<int>(), P->d_supp.as<int>(), nms_thresh,
+                     d_out + (size_t)off * cap * FFP_DET_STRIDE(5), cap, d_out_counts + off, st_);
+    off += m;
+  }
+  h_counts_.assign(n_tiles, 0);                       // the NMS counts (not capped), before the SAHI rule rewrites them
+  FFP_HIP(hipMemcpyAsync(h_counts_.data(), d_out_counts, sizeof(int) * n_tiles, hipMemcpyDeviceToHost, st_));
+  h_err_ = SCRFD_NO_BAD_ROW;
+  if (mode == FFP_SCRFD_TILES_SAHI) {
+    tiles_xy_.ensure(sizeof(int4) * n_tiles);
+    err_.ensure(sizeof(unsigned));
+    FFP_HIP(hipMemcpyAsync(tiles_xy_.p, tiles, sizeof(int4) * n_tiles, hipMemcpyHostToDevice, st_));
+    launch_scrfd_sahi_rows(d_out, d_out_counts, tiles_xy_.as<int4>(), n_tiles, cap, conf, H, W, err_.as<unsigned>(), st_);
+    FFP_HIP(hipMemcpyAsync(&h_err_, err_.p, sizeof(unsigned), hipMemcpyDeviceToHost, st_));
+  }
+}
+
+void ScrfdEngine::check_tiles(int n_tiles, int cap, int mode) {
+  for (int i = 0; i < n_tiles; ++i)
+    FFP_CHECK(h_counts_[i] <= cap, FFP_ERR_ARG, "scrfd: tile %d kept %d faces, the output holds %d per tile", i, h_counts_[i], cap);
+  if (mode == FFP_SCRFD_TILES_SAHI && h_err_ != SCRFD_NO_BAD_ROW)
+    FFP_CHECK(false, FFP_ERR_ARG, "scrfd: tile %d row %d: Box coords [minx, miny, maxx, maxy] cannot be negative (the box's far corner is negative after "
+              "the clip; sahi's BoundingBox raises here and the frame fails)", (int)(h_err_ / (unsigned)cap), (int)(h_err_ % (unsigned)cap));
+}
+
+void ScrfdEngine::infer_tiles_dev(const uint8_t* d_frame, int H, int W, int chan_order, const int32_t* tiles, int n_tiles, int det_w, int det_h,
+                                  float det_thresh, float nms_thresh, float conf, int mode, int max_batch, float* d_out, int cap, int32_t* d_out_counts) {
+  enqueue_tiles(d_frame, H, W, chan_order, tiles, n_tiles, det_w, det_h, det_thresh, nms_thresh, conf, mode, max_batch, d_out, cap, d_out_counts);
+  FFP_HIP(hipStreamSynchronize(st_));
+  check_tiles(n_tiles, cap, mode);
+}
+
+void ScrfdEngine::infer_tiles_ex(const uint8_t* frame, int H, int W, int chan_order, const int32_t* tiles, int n_tiles, int det_w, int det_h,
+                                 float det_thresh, float nms_thresh, float conf, int mode, int max_batch, float* out, int cap, int32_t* out_counts) {
+  FFP_CHECK(frame && H > 0 && W > 0 && tiles && n_tiles > 0, FFP_ERR_ARG, "scrfd: empty frame or tile list");
+  FFP_CHECK(cap >= 1 && out && out_counts, FFP_ERR_ARG, "scrfd: cap must be >= 1 and outputs non-null");
+  FFP_CHECK((long long)n_tiles * cap < (1ll << 31) / FFP_DET_STRIDE(5), FFP_ERR_ARG, "scrfd: %d tiles of %d rows", n_tiles, cap);
+  FFP_HIP(hipSetDevice(device_));
+  upload_frame(frame, H, W);
+  const size_t ob = sizeof(float) * (size_t)n_tiles * cap * FFP_DET_STRIDE(5);
+  tile_dets_.ensure(ob);
+  tile_counts_.ensure(sizeof(int) * n_tiles);
+  FFP_HIP(hipMemsetAsync(tile_dets_.p, 0, ob, st_));       // rows past a tile's count read as zeros
+  enqueue_tiles(frame_.as<uint8_t>(), H, W, chan_order, tiles, n_tiles, det_w, det_h, det_thresh, nms_thresh, conf, mode, max_batch,
+                tile_dets_.as<float>(), cap, tile_counts_.as<int>());
+  FFP_HIP(hipMemcpyAsync(out, tile_dets_.p, ob, hipMemcpyDeviceToHost, st_));
+  FFP_HIP(hipMemcpyAsync(out_counts, tile_counts_.p, sizeof(int) * n_tiles, hipMemcpyDeviceToHost, st_));
+  FFP_HIP(hipStreamSynchronize(st_));
+  for (int i = 0; i < n_tiles; ++i)
+    if (h_counts_[i] > cap) {            // the caller sizes its retry by the NMS counts (not capped), as with infer_tiles
+      std::copy(h_counts_.begin(), h_counts_.end(), out_counts);
+      break;
+    }
+  check_tiles(n_tiles, cap, mode);
+}
+
+void ScrfdEngine::merge_tiles(int n_tiles, int tile_cap, bool full_last, int H, int W, int pp_type, int pp_metric, double pp_thr, int class_agnostic,
+                              float* d_out, int cap, int32_t* d_out_n) {
+  constexpr int S = FFP_DET_STRIDE(5);
+  const int n_max = n_tiles * tile_cap;
+  rows_.ensure(sizeof(float) * (size_t)n_max * S);
+  rows_n_.ensure(sizeof(int));
+  rows_prefix_.ensure(sizeof(int) * (n_tiles + 1));
+  launch_compact_rows(tile_dets_.as<float>(), tile_counts_.as<int>(), n_tiles, tile_cap, S, rows_.as<float>(), rows_n_.as<int>(), rows_prefix_.as<int>(), st_);
+  int rows = 0, full_first = 0;              // the merge's grid follows the row count: one small read back between the two halves
+  FFP_HIP(hipMemcpyAsync(&rows, rows_n_.p, sizeof(int), hipMemcpyDeviceToHost, st_));
+  FFP_HIP(hipMemcpyAsync(&full_first, rows_prefix_.as<int>() + (n_tiles - 1), sizeof(int), hipMemcpyDeviceToHost, st_));
+  FFP_HIP(hipStreamSynchronize(st_));
+  check_tiles(n_tiles, tile_cap, FFP_SCRFD_TILES_SAHI);
+  FFP_CHECK(rows >= 0 && rows <= n_max, FFP_ERR_STATE, "scrfd: %d rows from %d tiles", rows, n_tiles);
+  // one slice: its rows as they are, in score order; with more tiles sahi post-processes a list of two or more (sahi/predict.py)
+  // the full-frame prediction is the one sahi does not shift, so it keeps its full_shape: a union it keeps is clipped to the frame
+  if (n_tiles > 1 && rows > 1) run_merge(merge_work_, rows_.as<float>(), rows_n_.as<int>(), rows, S, pp_type, pp_metric, pp_thr, class_agnostic, d_out, nullptr,
+                                         d_out_n, cap, st_, full_last ? full_first : 0x7fffffff, W, H);
+  else run_merge_passthrough(rows_.as<float>(), rows_n_.as<int>(), S, d_out, nullptr, d_out_n, cap, st_);
+}
+
+void ScrfdEngine::sliced_predict_dev(const uint8_t* d_frame, int H, int W, int chan_order, const std::vector<int32_t>& items, int det_w, int det_h,
+                                     float det_thresh, float nms_thresh, float conf, int max_batch, int tile_cap, int pp_type, int pp_metric,
+                                     double pp_thr, int class_agnostic, float* d_out, int cap, int32_t* d_out_n) {
+  FFP_CHECK(d_out && d_out_n && cap > 0 && tile_cap > 0, FFP_ERR_ARG, "scrfd: sliced_predict needs an output of cap > 0 rows and tile_cap > 0");
+  const int n_tiles = (int)items.size() / 4;
+  FFP_CHECK(n_tiles > 0 && (long long)n_tiles * tile_cap < (1 << 24), FFP_ERR_ARG, "scrfd: no tile to run, or too many rows (%d tiles of %d)", n_tiles, tile_cap);
+  FFP_HIP(hipSetDevice(device_));
+  tile_dets_.ensure(sizeof(float) * (size_t)n_tiles * tile_cap * FFP_DET_STRIDE(5));
+  tile_counts_.ensure(sizeof(int) * n_tiles);
+  enqueue_tiles(d_frame, H, W, chan_order, items.data(), n_tiles, det_w, det_h, det_thresh, nms_thresh, conf, FFP_SCRFD_TILES_SAHI, max_batch,
+                tile_dets_.as<float>(), tile_cap, tile_counts_.as<int>());
+  const int32_t* last = items.data() + 4 * (n_tiles - 1);          // more than one slice: none of them is the whole frame
+  const bool full_last = n_tiles > 1 && last[0] == 0 && last[1] == 0 && last[2] == W && last[3] == H;
+  merge_tiles(n_tiles, tile_cap, full_last, H, W, pp_type, pp_metric, pp_thr, class_agnostic, d_out, cap, d_out_n);
+  FFP_HIP(hipStreamSynchronize(st_));
+}
+
+void ScrfdEngine::sliced_predict(const uint8_t* frame, int H, int W, int chan_order, const std::vector<int32_t>& items, int det_w, int det_h,
+                                 float det_thresh, float nms_thresh, float conf, int max_batch, int tile_cap, int pp_type, int pp_metric, double pp_thr,
+                                 int class_agnostic, float* out, int cap, int32_t* out_n) {
+  FFP_CHECK(frame && H > 0 && W > 0 && out && out_n && cap > 0, FFP_ERR_ARG, "scrfd: sliced_predict needs a frame and an output of cap > 0 rows");
+  constexpr int S = FFP_DET_STRIDE(5);
+  FFP_HIP(hipSetDevice(device_));
+  upload_frame(frame, H, W);
+  merged_.ensure(sizeof(float) * (size_t)cap * S);
+  merged_n_.ensure(sizeof(int));
+  sliced_predict_dev(frame_.as<uint8_t>(), H, W, chan_order, items, det_w, det_h, det_thresh, nms_thresh, conf, max_batch, tile_cap, pp_type, pp_metric,
+                     pp_thr, class_agnostic, merged_.as<float>(), cap, merged_n_.as<int>());
+  int k = 0;
+  FFP_HIP(hipMemcpy(&k, merged_n_.p, sizeof(int), hipMemcpyDeviceToHost));
+  *out_n = k;
+  FFP_CHECK(k <= cap, FFP_ERR_ARG, "scrfd: sliced_predict: %d merged detections exceed the output capacity %d (nothing was dropped silently: call again with cap >= %d)", k, cap, k);
+  FFP_HIP(hipMemcpy(out, merged_.p, sizeof(float) * (size_t)k * S, hipMemcpyDeviceToHost));
 }
 
 }  // namespace ffp

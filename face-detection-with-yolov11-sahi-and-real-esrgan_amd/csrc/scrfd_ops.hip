@@ -1,6 +1,7 @@
 // scrfd_ops.hip — the SCRFD-specific device operators: InsightFace's pre-processing, the ResNet-v1e pools, and the decode / NMS of
 // RetinaFace.detect (insightface/model_zoo/retinaface.py). Vector memory operations and ordinary global atomics only.
 #include <algorithm>
+#include <climits>
 
 #include "letterbox.hpp"
 #include "scrfd.hpp"
@@ -187,6 +188,82 @@ __global__ void __launch_bounds__(256) scrfd_nms_kernel(const ScrfdCand* __restr
 void launch_scrfd_nms(const ScrfdCand* cand, const int* counts, int n_img, int per_img, int* order, int* supp, float thresh, float* out, int cap,
                       int* out_counts, hipStream_t st) {
   hipLaunchKernelGGL(scrfd_nms_kernel, dim3(n_img), dim3(256), 0, st, cand, counts, per_img, order, supp, thresh, out, cap, out_counts);
+  FFP_HIP(hipGetLastError());
+}
+
+// numpy's float32 -> int conversion of face.bbox.astype(int): toward zero. A NaN is negative there (the smallest integer), and a value
+// outside int32 is pinned to its end of the range: the clip that follows brings both back into the frame or flags them.
+__device__ __forceinline__ int scrfd_trunc(float v) {
+  if (!(v == v)) return INT_MIN;
+  return (int)fminf(fmaxf(v, -2147483648.0f), 2147483520.0f);
+}
+
+constexpr int SCRFD_ROW = FFP_DET_STRIDE(5);
+
+// utils/insightface_wrapper.py's conversion, sahi's ObjectAnnotation / BoundingBox and get_shifted_object_prediction on the rows of one
+// tile per workgroup, in place: rows with score < conf skipped, the box int-truncated and clipped (x1, y1 >= 0, x2 <= full_w,
+// y2 <= full_h: the crop-local box against the FULL frame), a box with x2 < 0 or y2 < 0 reported through *err (the smallest
+// tile * cap + row wins; the reference raises there) and left out, then the tile origin added to the box (integers) and to the
+// keypoints (floats). Survivors keep their order and move to the front; the rows they vacate are zeroed; counts[tile] is rewritten.
+// Rounds of 256 rows: every row of a round sits in registers before the first survivor of that round is stored, and a survivor never
+// moves past its own place, so compacting in place reads nothing that was already overwritten.
+__global__ void __launch_bounds__(256) scrfd_sahi_rows_kernel(float* __restrict__ dets, int* __restrict__ counts, const int4* __restrict__ tiles,
+                                                              int cap, float conf, int full_h, int full_w, unsigned* __restrict__ err) {
+  const int tile = blockIdx.x;
+  const int n = min(counts[tile], cap);
+  float* base = dets + (size_t)tile * cap * SCRFD_ROW;
+  const int4 t = tiles[tile];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __shared__ int wave_kept[4];
+  __syncthreads();                      // counts[tile] is read by every thread before thread 0 rewrites it
+  int kept = 0;
+  for (int r0 = 0; r0 < n; r0 += 256) {
+    const int r = r0 + (int)threadIdx.x;
+    float row[SCRFD_ROW];
+    bool keep = false;
+    if (r < n) {
+      const float* src = base + (size_t)r * SCRFD_ROW;
+#pragma unroll
+      for (int i = 0; i < SCRFD_ROW; ++i) row[i] = src[i];
+      if (!(row[4] < conf)) {
+        const int x1 = max(scrfd_trunc(row[0]), 0), y1 = max(scrfd_trunc(row[1]), 0);
+        const int x2 = min(scrfd_trunc(row[2]), full_w), y2 = min(scrfd_trunc(row[3]), full_h);
+        if (x2 < 0 || y2 < 0) {
+          atomicMin(err, (unsigned)(tile * cap + r));
+        } else {
+          keep = true;
+          row[0] = (float)((long long)x1 + t.x); row[1] = (float)((long long)y1 + t.y);
+          row[2] = (float)(x2 + t.x); row[3] = (float)(y2 + t.y);
+#pragma unroll
+          for (int k = 0; k < 5; ++k) { row[6 + 3 * k] += (float)t.x; row[7 + 3 * k] += (float)t.y; }
+        }
+      }
+    }
+    const unsigned long long m = __ballot(keep);
+    if (lane == 0) wave_kept[wave] = __popcll(m);
+    __syncthreads();
+    int at = kept + __popcll(m & ((1ull << lane) - 1ull)), round = 0;
+    for (int w = 0; w < 4; ++w) {
+      if (w < wave) at += wave_kept[w];
+      round += wave_kept[w];
+    }
+    if (keep) {
+      float* dst = base + (size_t)at * SCRFD_ROW;
+#pragma unroll
+      for (int i = 0; i < SCRFD_ROW; ++i) dst[i] = row[i];
+    }
+    kept += round;
+    __syncthreads();                    // wave_kept is rewritten by the next round
+  }
+  for (int e = kept * SCRFD_ROW + (int)threadIdx.x; e < n * SCRFD_ROW; e += 256) base[e] = 0.f;
+  if (threadIdx.x == 0) counts[tile] = kept;
+}
+
+void launch_scrfd_sahi_rows(float* dets, int* counts, const int4* tiles_xyxy, int n_tiles, int cap, float conf, int full_h, int full_w, unsigned* err,
+                            hipStream_t st) {
+  FFP_CHECK(n_tiles >= 1 && cap >= 1 && (long long)n_tiles * cap < (1ll << 31), FFP_ERR_ARG, "scrfd sahi rows: %d tiles of %d rows", n_tiles, cap);
+  FFP_HIP(hipMemsetAsync(err, 0xff, sizeof(unsigned), st));      // SCRFD_NO_BAD_ROW
+  hipLaunchKernelGGL(scrfd_sahi_rows_kernel, dim3(n_tiles), dim3(256), 0, st, dets, counts, tiles_xyxy, cap, conf, full_h, full_w, err);
   FFP_HIP(hipGetLastError());
 }
 

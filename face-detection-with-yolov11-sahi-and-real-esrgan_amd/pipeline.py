@@ -270,22 +270,9 @@ def frame_major(g, gc, world: int, n_frames: int, per: int):
     return g2, gc2
 
 
-class FramePipeline:
-    """One rank's share of the pipeline. `torch` is imported lazily: it provides device tensors and the collective."""
-
-    def __init__(self, det_weights, sr_weights, cfg: PipeConfig, arch: str = "s", device: int = 0,
-                 det_precision: int = _lib.PREC_F32, sr_half: bool = True, rank: int = 0, world: int = 1):
-        import torch
-        self.torch = torch
-        self.cfg, self.rank, self.world, self.device = cfg, rank, world, device
-        self.dev = torch.device("cuda", device)
-        self.det = _lib.Detector(det_weights, arch=arch, device=device, precision=det_precision)
-        self.sr = _lib.Enhancer(sr_weights, 4, 23, device=device, half=sr_half) if (cfg.sr_crops > 0 and sr_weights is not None) else None
-        if self.sr is None:
-            self.det.set_lanes(1)       # detection only (BASELINE config 2): nothing runs beside the detector, let its branches overlap
-        self.stride = self.det.stride
-        self._bufs = {}
-        self._layouts = {}
+class CropEnhancerMixin:
+    """The device-resident crop stage the pipelines share: scratch tensors by name and Real-ESRGAN on crops of a resident BGR frame.
+    The class using it sets self.torch, self.dev, self.cfg, self.sr (an `_lib.Enhancer`) and self._bufs = {}."""
 
     def _buf(self, name, shape, dtype):
         t = self._bufs.get(name)
@@ -314,6 +301,35 @@ class FramePipeline:
             if w > 0 and h > 0:
                 tot += (h * scale * w * scale * 3 + 15) // 16 * 16
         return tot
+
+    def enhance_crops(self, d_frame_bgr, H: int, W: int, boxes: np.ndarray, wait: bool = True, slot: int = 0):
+        """Real-ESRGAN x4 on crops of a resident BGR frame. Returns (uint8 cuda tensor with all outputs, offsets).
+        wait=False enqueues on the enhancer's stream and returns; call wait_sr() before reading the tensor."""
+        tot = self.sr_out_bytes(boxes, H, W, self.sr.scale)
+        out = self._bytes(f"sr_out{slot}", tot)
+        offs = self.sr.enhance_crops_dev([d_frame_bgr.data_ptr()], H, W, boxes, out.data_ptr(), tot, None, self.cfg.sr_tile, self.cfg.sr_tile_pad, wait)
+        return out, offs
+
+    def wait_sr(self):
+        _lib._check(_lib.lib().ffp_sr_wait(self.sr.handle))
+
+
+class FramePipeline(CropEnhancerMixin):
+    """One rank's share of the pipeline. `torch` is imported lazily: it provides device tensors and the collective."""
+
+    def __init__(self, det_weights, sr_weights, cfg: PipeConfig, arch: str = "s", device: int = 0,
+                 det_precision: int = _lib.PREC_F32, sr_half: bool = True, rank: int = 0, world: int = 1):
+        import torch
+        self.torch = torch
+        self.cfg, self.rank, self.world, self.device = cfg, rank, world, device
+        self.dev = torch.device("cuda", device)
+        self.det = _lib.Detector(det_weights, arch=arch, device=device, precision=det_precision)
+        self.sr = _lib.Enhancer(sr_weights, 4, 23, device=device, half=sr_half) if (cfg.sr_crops > 0 and sr_weights is not None) else None
+        if self.sr is None:
+            self.det.set_lanes(1)       # detection only (BASELINE config 2): nothing runs beside the detector, let its branches overlap
+        self.stride = self.det.stride
+        self._bufs = {}
+        self._layouts = {}
 
     def merged_count(self, outn) -> int:
         """Host value of merge_frame's count; raises when the frame produced more merged detections than merge_cap rows."""
@@ -399,14 +415,6 @@ class FramePipeline:
                                              cfg.merge_cap, outn.data_ptr()))
         return out, outn
 
-    def enhance_crops(self, d_frame_bgr, H: int, W: int, boxes: np.ndarray, wait: bool = True, slot: int = 0):
-        """Real-ESRGAN x4 on crops of a resident BGR frame. Returns (uint8 cuda tensor with all outputs, offsets).
-        wait=False enqueues on the enhancer's stream and returns; call wait_sr() before reading the tensor."""
-        tot = self.sr_out_bytes(boxes, H, W, self.sr.scale)
-        out = self._bytes(f"sr_out{slot}", tot)
-        offs = self.sr.enhance_crops_dev([d_frame_bgr.data_ptr()], H, W, boxes, out.data_ptr(), tot, None, self.cfg.sr_tile, self.cfg.sr_tile_pad, wait)
-        return out, offs
-
     def enhance_crops_multi(self, d_frames, H: int, W: int, boxes_per_frame, slot: int = 0):
         """Crops of several resident frames as ONE ragged SR batch (async; wait_sr() before reading)."""
         boxes = np.ascontiguousarray(np.concatenate(boxes_per_frame, 0), np.int32)
@@ -437,5 +445,55 @@ class FramePipeline:
         rows, n = self.merge_frame_of(dets, counts, L, 0, gathered)
         return enh, rows, n
 
-    def wait_sr(self):
-        _lib._check(_lib.lib().ffp_sr_wait(self.sr.handle))
+
+class DetectionFirstPipeline(CropEnhancerMixin):
+    """pipeline_v1_detection_first/app_v1.py on one GPU with nothing going through the host between the stages: a resident BGR frame
+    (e.g. from ffp_jpeg_decode_dev) -> ffp_scrfd_sliced_predict_dev (InsightFace SCRFD over SAHI's slices, the wrapper's conversion and the
+    merge) -> face crops -> Real-ESRGAN x4. Single rank, one frame per call.
+
+    The reference hands sahi's RGB array to RetinaFace's swapRB blob, so the network sees BGR planes; a BGR-resident frame reproduces that
+    with no flip (FFP_CHAN_AS_RGB), which is what detect() passes: cfg.chan_order is not consulted. cfg.conf is both FaceAnalysis' det_thresh
+    and the wrapper's confidence_threshold, as InsightFaceDetectionModel.load_model sets them; cfg.imgsz / iou / max_det are YOLO's and unused."""
+
+    TILE_CAP = 1024       # faces per item, the cap FaceDetector.infer_tiles starts from
+
+    def __init__(self, onnx, sr_weights, cfg: PipeConfig, device: int = 0, det_precision: int = _lib.PREC_F32, sr_half: bool = True,
+                 det_size=(640, 640), nms_thresh: float = 0.4, max_batch: int = 0):
+        import torch
+        self.torch = torch
+        self.cfg, self.device = cfg, device
+        self.dev = torch.device("cuda", device)
+        self.det = _lib.FaceDetector(onnx, device=device, precision=det_precision)
+        self.sr = _lib.Enhancer(sr_weights, 4, 23, device=device, half=sr_half) if (cfg.sr_crops > 0 and sr_weights is not None) else None
+        self.det_size, self.nms_thresh, self.max_batch = (int(det_size[0]), int(det_size[1])), float(nms_thresh), int(max_batch)
+        self.stride = _lib.FaceDetector.STRIDE
+        self._bufs = {}
+
+    def detect(self, d_frame_bgr, H: int, W: int):
+        """d_frame_bgr: uint8 cuda tensor (H, W, 3), BGR. Returns (rows [merge_cap][21] float32 cuda tensor, count): the merged detections of
+        the frame in SAHI's output order; raises when there are more than cfg.merge_cap, or where the reference raises on a negative box."""
+        cfg = self.cfg
+        self._hw = (H, W)
+        out = self._buf("merged", (cfg.merge_cap, self.stride), self.torch.float32)
+        outn = self._buf("merged_n", (1,), self.torch.int32)
+        self.det.sliced_predict_dev(d_frame_bgr.data_ptr(), H, W, out.data_ptr(), cfg.merge_cap, outn.data_ptr(), cfg.slice_h, cfg.slice_w,
+                                    cfg.overlap, cfg.overlap, cfg.perform_standard_pred, self.det_size, cfg.conf, self.nms_thresh, cfg.conf,
+                                    cfg.pp_type, cfg.pp_metric, cfg.pp_thr, cfg.class_agnostic, _lib.CHAN_AS_RGB, self.max_batch, self.TILE_CAP)
+        n = int(outn.item())
+        if n > cfg.merge_cap:
+            raise _lib.FfpError(1, f"{n} merged detections exceed merge_cap={cfg.merge_cap}: raise PipeConfig.merge_cap")
+        return out, n
+
+    def crop_boxes(self, rows, H: Optional[int] = None, W: Optional[int] = None) -> np.ndarray:
+        """Host int32 [k][4] boxes of merged rows (a cuda tensor or an array of the first `count` rows), clamped to the frame (the last
+        detect()'s when H, W are not given), empty ones dropped, at most cfg.sr_crops: utils/visualization.py's save_face_crops in detection order."""
+        H, W = (self._hw[0] if H is None else H), (self._hw[1] if W is None else W)
+        r = rows.detach().cpu().numpy() if hasattr(rows, "detach") else np.asarray(rows)
+        out = []
+        for x1, y1, x2, y2 in r[:, :4].astype(np.int64):
+            x1, y1, x2, y2 = max(0, x1), max(0, y1), min(W, x2), min(H, y2)
+            if x2 > x1 and y2 > y1:
+                out.append((x1, y1, x2, y2))
+        if self.cfg.sr_crops > 0:
+            out = out[:self.cfg.sr_crops]
+        return np.asarray(out, np.int32).reshape(-1, 4)

@@ -534,6 +534,18 @@ int ffp_op_scrfd_pool(int device, int n, const int32_t* hs, const int32_t* ws, i
 int ffp_op_scrfd_post(int device, int n, int net_h, int net_w, int A, const int32_t* strides, int px_align, const float* const* heads,
                       const int32_t* cs, const int32_t* coff, const float* det_scale, float thresh, float nms_thresh, int cap, float* out,
                       int32_t* out_counts, float* raw_scores);
+/* scrfd_sahi_rows alone: what utils/insightface_wrapper.py's conversion, sahi's ObjectAnnotation / BoundingBox and
+ * get_shifted_object_prediction do to the rows of n_tiles tiles {x0, y0, x1, y1} of a full_h x full_w frame, per row and in this order:
+ * (1) skipped when score < conf (strict, float32); (2) x1, y1, x2, y2 = (int) of the float32 value, toward zero (face.bbox.astype(int));
+ * (3) x1 = max(x1, 0), y1 = max(y1, 0), x2 = min(x2, full_w), y2 = min(y2, full_h): the crop-local box against the FULL frame;
+ * (4) x2 < 0 or y2 < 0 now: the reference raises "Box coords [minx, miny, maxx, maxy] cannot be negative" and the frame fails; here the
+ * smallest tile * cap + row of such a box goes to *out_bad (-1: none) and the call returns FFP_ERR_ARG naming tile and row; (5) the tile
+ * origin added to the box (integers) and to the five keypoints' x, y (floats); boxes with x1 >= x2 are kept, as the reference keeps them;
+ * (6) survivors stay in their tile's order at the front of the tile. dets [n_tiles][cap][FFP_DET_STRIDE(5)] and counts [n_tiles] in/out:
+ * counts above cap are read as cap; rows the survivors vacate (from the new count up to the old one) are zeroed, rows at or past the old
+ * count are untouched. After an error return the outputs hold the other rows' results with the offending rows left out. */
+int ffp_op_scrfd_sahi_rows(int device, int n_tiles, int cap, const int32_t* tiles_xyxy, int full_h, int full_w, float conf, float* dets,
+                           int32_t* counts, int32_t* out_bad);
 
 /* Tuning hook: mean device time (HIP events, microseconds) of `iters` back-to-back launches of one dense convolution on
  * synthetic data. dbg_mask skips kernel phases (1 stores, 2 MFMAs, 4 chunk refetch, 8 LDS stash) to attribute time —
@@ -606,6 +618,62 @@ int ffp_scrfd_describe(const void* onnx_bytes, size_t nbytes, int n, int det_w, 
 int ffp_scrfd_infer_tiles(ffp_scrfd* s, const uint8_t* frame_hwc, int H, int W, int chan_order, const int32_t* tiles_xyxy,
                           int n_tiles, int det_w, int det_h, float det_thresh, float nms_thresh, float* out_dets, int cap,
                           int32_t* out_counts);
+
+/* Sliced prediction. Upstream sahi and insightface were not available to run against: the rules below restate
+ * utils/insightface_wrapper.py and sahi 0.11.x from their source, and only synthetic weights have been run (not the real det_10g.onnx). */
+#define FFP_SCRFD_TILES_LOCAL 0 /* rows in tile-local float pixels, exactly ffp_scrfd_infer_tiles' rows */
+#define FFP_SCRFD_TILES_SAHI 1  /* rows as sahi's ObjectPrediction list holds them after the wrapper: see ffp_op_scrfd_sahi_rows */
+/* Items per network batch where a caller of the entries below passes max_batch < 0: the fastest measured size whose plans stay under 8 GB,
+ * the rule of FFP_RT_TILES_DEFAULT_BATCH (tools/scrfd_sliced_probe.py on an MI355X, profiles/scrfd_sliced_mi355x.json: 61 items of a
+ * 2160 x 3840 frame at 512 / 0.2, det size 640, the full-size synthetic model; FFP_PREC_F32 / F32X3 ms per frame of ffp_scrfd_sliced_predict
+ * and the bytes held by the plans: 8: 47.4 / 37.4 ms, 2.1 GB; 16: 42.5 / 32.9 ms, 4.3 GB; 32: 40.6 / 30.0 ms, 8.4 GB; 0, i.e. one batch of
+ * 61: 38.8 / 28.2 ms, 8.4 GB; min..max spread under 1 ms each. The Python path, get_sliced_prediction with InsightFaceDetectionModel on
+ * the same commit in FFP_PREC_F32: median 123 to 138 ms, 77 to 203 ms over 40 samples). A caller with the memory to spare passes 32 or 0.
+ * max_batch == 0 keeps ffp_scrfd_infer_tiles' behaviour: every tile in one batch. */
+#define FFP_SCRFD_TILES_DEFAULT_BATCH 16
+/* ffp_scrfd_infer_tiles with two additions. (1) Tiles run in ceil(n_tiles / max_batch) chunks of sizes as even as possible (13 at 5: 5, 4, 4),
+ * one plan per chunk size, each chunk's decode and NMS writing its slice of the output; the engine scales every image by itself, so a
+ * tile's rows do not depend on its batch mates in either precision. (2) mode FFP_SCRFD_TILES_SAHI applies ffp_op_scrfd_sahi_rows at `conf`
+ * (the wrapper's confidence_threshold; the network's own filter stays score >= det_thresh) with the frame as the full shape.
+ * out_dets: [n_tiles][cap][FFP_DET_STRIDE(5)], rows past out_counts[i] zero; out_counts [n_tiles]. A tile whose NMS keeps more than cap
+ * faces is FFP_ERR_ARG with the uncapped NMS counts in out_counts; a negative far corner in SAHI mode is FFP_ERR_ARG naming tile and row.
+ * (InsightFaceDetectionModel.perform_inference_batch -> FaceAnalysis.detect_tiles, and in SAHI mode the per-face Python behind it:
+ * utils/insightface_wrapper.py:83-86 `score < confidence_threshold` / `face.bbox.astype(int)`, sahi/annotation.py ObjectAnnotation and
+ * BoundingBox, sahi/prediction.py get_shifted_object_prediction) */
+int ffp_scrfd_infer_tiles_ex(ffp_scrfd* s, const uint8_t* frame_hwc, int H, int W, int chan_order, const int32_t* tiles_xyxy, int n_tiles,
+                             int det_w, int det_h, float det_thresh, float nms_thresh, float conf, int mode, int max_batch, float* out_dets,
+                             int cap, int32_t* out_counts);
+/* the same with the frame and both outputs on the device (tiles_xyxy stays a host pointer): a frame decoded by ffp_jpeg_decode_dev stays
+ * where it is. Work is enqueued on the engine's stream and the call returns after that stream has drained, as ffp_det_infer_tiles_dev
+ * does. Rows past a tile's count are untouched (LOCAL) or zero up to the tile's NMS count (SAHI). Errors as above.
+ * (replaces the host round trip between cv2.imread / sahi's slice_image and FaceAnalysis.get, app_v1.py's detector stage) */
+int ffp_scrfd_infer_tiles_dev(ffp_scrfd* s, const uint8_t* d_frame_hwc, int H, int W, int chan_order, const int32_t* tiles_xyxy, int n_tiles,
+                              int det_w, int det_h, float det_thresh, float nms_thresh, float conf, int mode, int max_batch,
+                              float* d_out_dets, int cap, int32_t* d_out_counts);
+/* sahi.predict.get_sliced_prediction(image, InsightFaceDetectionModel, slice_height, slice_width, overlap ratios, perform_standard_pred,
+ * postprocess_type / match_metric / match_threshold / class_agnostic) in one call (pipeline_v1_detection_first/app_v1.py's detector
+ * stage): the grid of ffp_slice_bboxes, plus the full frame when there is more than one slice and perform_standard_pred != 0,
+ * ffp_scrfd_infer_tiles_ex in FFP_SCRFD_TILES_SAHI with at most tile_cap faces per item, rows in tile order then score order (the order
+ * the Python loop appends ObjectPredictions), then the merge of ffp_merge when there is more than one item and more than one row. Rows
+ * keep FFP_DET_STRIDE(5): a merged detection carries the keypoints of its higher-scored source (ffp_merge), shifted to frame pixels.
+ * out: [cap][FFP_DET_STRIDE(5)]; more than cap merged rows is FFP_ERR_ARG with *out_n = the full count. A box whose far corner is
+ * negative after the clip fails the frame with FFP_ERR_ARG, as the reference's exception does. */
+int ffp_scrfd_sliced_predict(ffp_scrfd* s, const uint8_t* frame_hwc, int H, int W, int chan_order, int slice_h, int slice_w,
+                             float overlap_h_ratio, float overlap_w_ratio, int perform_standard_pred, int det_w, int det_h, float det_thresh,
+                             float nms_thresh, float conf, int max_batch, int tile_cap, int pp_type, int pp_metric, double pp_thr,
+                             int class_agnostic, float* out, int cap, int32_t* out_n);
+/* the same with the frame, d_out [cap][FFP_DET_STRIDE(5)] and d_out_n[1] on the device; returns after the engine's stream has drained.
+ * *d_out_n receives the UNTRUNCATED number of merged detections: when it exceeds cap only the first cap rows were written and the caller
+ * must treat the result as overflowed (the rule of ffp_merge_dev).
+ * (replaces the same call, between ffp_jpeg_decode_dev and ffp_sr_enhance_crops_dev with nothing going through the host) */
+int ffp_scrfd_sliced_predict_dev(ffp_scrfd* s, const uint8_t* d_frame_hwc, int H, int W, int chan_order, int slice_h, int slice_w,
+                                 float overlap_h_ratio, float overlap_w_ratio, int perform_standard_pred, int det_w, int det_h,
+                                 float det_thresh, float nms_thresh, float conf, int max_batch, int tile_cap, int pp_type, int pp_metric,
+                                 double pp_thr, int class_agnostic, float* d_out, int cap, int32_t* d_out_n);
+/* device bytes held by the resident plans (activations and candidate lists) and how many plans are resident (at most 8);
+ * ffp_scrfd_drop_plans releases them (no counterpart in the reference: onnxruntime owns its arena) */
+int ffp_scrfd_mem_bytes(ffp_scrfd* s, uint64_t* out_plan_bytes, int32_t* out_plans_resident);
+int ffp_scrfd_drop_plans(ffp_scrfd* s);
 
 /* The graph outputs of every crop (net_outs of RetinaFace.forward), for parity tests: per crop, per output in file order,
  * anchors x values floats in the graph's (Transpose + Reshape) order; scores are the sigmoid values the decode thresholds.
