@@ -138,6 +138,7 @@ _SIGS = {
     "ffp_op_conv2d": (C.c_int, [C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_float), _p(C.c_float), C.c_int,
                                 C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_float), C.c_float, _p(C.c_float)]),
     "ffp_op_variant": (C.c_int, [C.c_int, C.c_int]),
+    "ffp_op_cls_tower_variant": (C.c_int, [C.c_int, C.c_int]),
     "ffp_op_sppf_pool": (C.c_int, [C.c_int, C.c_int, C.c_int, _p(C.c_int32), _p(C.c_int32), C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int,
                                    _p(C.c_float), C.c_int, C.c_int, C.c_int, C.c_int]),
     "ffp_op_upsample2x": (C.c_int, [C.c_int, C.c_int, C.c_int, _p(C.c_int32), _p(C.c_int32), C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int,
@@ -922,13 +923,21 @@ def op_conv2d(x: np.ndarray, w: np.ndarray, b: Optional[np.ndarray], stride: int
 # per image, holding WHOLE pixel records; the operator reads / writes the channel slice the offsets name. Output buffers are passed in
 # (`y`, same list form) and come back with the slice written and every other value as it went in.
 OP_SPPF, OP_ATTENTION, OP_DWCONV = 0, 1, 2
-OP_VARIANTS = {OP_SPPF: {"lds": 1, "direct": 2}, OP_ATTENTION: {"mfma": 1, "valu": 2}, OP_DWCONV: {"col": 1, "strip": 2}}
+OP_CLS_TOWER = "cls_tower"      # op_cls_tower: the variant is a tile height, with a workgroup cap beside it (ffp_op_cls_tower_variant)
+OP_VARIANTS = {OP_SPPF: {"lds": 1, "direct": 2}, OP_ATTENTION: {"mfma": 1, "valu": 2}, OP_DWCONV: {"col": 1, "strip": 2},
+               OP_CLS_TOWER: {"rows16": 16, "rows8": 8}}
 
 
-def op_variant(family: int, variant=0) -> None:
-    """Pin the kernel the following op_sppf_pool / op_psa_attention / op_dwconv3x3 calls launch (a name of OP_VARIANTS[family], or 0 / None
-    for the automatic choice)."""
+def op_variant(family, variant=0, wg_cap: int = 0) -> None:
+    """Pin the kernel the following op_sppf_pool / op_psa_attention / op_dwconv3x3 / op_cls_tower calls launch (a name of OP_VARIANTS[family],
+    or 0 / None for the automatic choice). OP_CLS_TOWER: the tile height, and with wg_cap > 0 at most that many workgroups, so that a small
+    batch walks its tiles persistently."""
     v = OP_VARIANTS[family][variant] if isinstance(variant, str) else int(variant or 0)
+    if family == OP_CLS_TOWER:
+        _check(lib().ffp_op_cls_tower_variant(v, int(wg_cap)))
+        return
+    if wg_cap:
+        raise ValueError("wg_cap is for OP_CLS_TOWER")
     _check(lib().ffp_op_variant(int(family), v))
 
 

@@ -1167,6 +1167,13 @@ int ffp_op_variant(int family, int variant) {
   g_op_variant[family] = variant;
   FFP_API_END
 }
+static int g_op_cls_tower_force = 0;      // ConvOp::dwpw_force of ffp_op_cls_tower's two launches
+int ffp_op_cls_tower_variant(int rows, int wg_cap) {
+  FFP_API_BEGIN
+  FFP_CHECK((rows == 0 || rows == 8 || rows == 16) && wg_cap >= 0 && wg_cap <= 65535, FFP_ERR_ARG, "op_cls_tower_variant: rows %d (0, 8, 16) / workgroup cap %d", rows, wg_cap);
+  g_op_cls_tower_force = (rows == 16 ? 1 : rows == 8 ? 2 : 0) | wg_cap << 2;
+  FFP_API_END
+}
 
 namespace {
 
@@ -1393,6 +1400,7 @@ int ffp_op_cls_tower(int device, int n, const int32_t* hs, const int32_t* ws, in
   t2.in = t1.out; t2.out = view(fuse_fin ? nullptr : de2.p, C3, 0, C3, 2);
   const TView logits = view(dhead.p, head_cs, head_coff, nc, -1);
   if (fuse_fin) { t2.fin = &fin; t2.fin_w = &dense; t2.fin_out = logits; }
+  t1.dwpw_force = t2.dwpw_force = g_op_cls_tower_force;
   launch_conv(t1, cx.st);
   launch_conv(t2, cx.st);
   if (!fuse_fin) {

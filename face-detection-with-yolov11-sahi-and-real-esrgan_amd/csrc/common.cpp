@@ -160,11 +160,24 @@ const int4* Level::tile_table_packed(int th, int* n_launch, const int** d_count,
   return tile_table(-th, n_launch, d_count, st);
 }
 
-void Level::compact_gated(hipStream_t st) {
-  for (auto& kv : gated) {
-    const TileTab& full = tiles.at(kv.first);
-    gate_compact(full.tab.as<int4>(), full.n, d_tab.as<int4>(), n, kv.first, gate_active, kv.second.tab.as<int4>(), kv.second.d_count.as<int>(), st);
+static GateTab gate_tab(Level& L, int key) {
+  const TileTab& full = L.tiles.at(key);
+  TileTab& g = L.gated.at(key);
+  Level::GateIdx& ix = L.gate_idx.at(key);
+  return GateTab{full.tab.as<int4>(), ix.first.as<int>(), L.gate_active, g.tab.as<int4>(), ix.start.as<int>(), g.d_count.as<int>(), full.n, L.n};
+}
+
+void Level::compact_gated(Level* const* levels, int n_levels, hipStream_t st) {
+  std::vector<GateTab> tabs;
+  GateCompactFn fn = nullptr;
+  for (int l = 0; l < n_levels; ++l) {
+    Level& L = *levels[l];
+    if (L.gated.empty()) continue;
+    FFP_CHECK(L.gate_compact && (!fn || fn == L.gate_compact), FFP_ERR_STATE, "level: gated tile tables without one compaction launcher");
+    fn = L.gate_compact;
+    for (auto& kv : L.gated) tabs.push_back(gate_tab(L, kv.first));
   }
+  if (!tabs.empty()) fn(tabs.data(), (int)tabs.size(), st);
 }
 
 const int4* Level::tile_table(int key, int* n_launch, const int** d_count, hipStream_t st, const int* gate) {
@@ -173,7 +186,7 @@ const int4* Level::tile_table(int key, int* n_launch, const int** d_count, hipSt
     FFP_CHECK(!gate_active || gate_active == gate, FFP_ERR_STATE, "level: a second gate");
     FFP_CHECK(gate_compact, FFP_ERR_STATE, "level: gated tile table without a compaction launcher");
     int n_full = 0;
-    const int4* full = tile_table(key, &n_full, nullptr, st);
+    (void)tile_table(key, &n_full, nullptr, st);      // the full table: built on first use
     auto it = gated.find(key);
     if (it == gated.end()) {
       gate_active = gate;
@@ -182,7 +195,23 @@ const int4* Level::tile_table(int key, int* n_launch, const int** d_count, hipSt
       t.tab.alloc(sizeof(int4) * (size_t)n_full);
       t.d_count.alloc(sizeof(int));
       it = gated.emplace(key, std::move(t)).first;
-      gate_compact(full, n_full, d_tab.as<int4>(), n, key, gate, it->second.tab.as<int4>(), it->second.d_count.as<int>(), st);
+      // the table was built in image order: image i's entries start where the tiles of the images before it end
+      std::vector<int> first((size_t)n + 1);
+      long long e = 0;
+      for (int i = 0; i < n; ++i) {
+        first[i] = (int)e;
+        e += (long long)((h[i] + key - 1) / key) * ((w[i] + 15) / 16);
+      }
+      first[n] = (int)e;
+      FFP_CHECK(e == n_full, FFP_ERR_STATE, "level: the images hold %lld tiles of height %d, the table %d", e, key, n_full);
+      GateIdx ix;
+      ix.first.alloc(sizeof(int) * first.size());
+      ix.start.alloc(sizeof(int) * (size_t)n);
+      FFP_HIP(hipMemcpyAsync(ix.first.p, first.data(), sizeof(int) * first.size(), hipMemcpyHostToDevice, st));
+      FFP_HIP(hipStreamSynchronize(st));
+      gate_idx.emplace(key, std::move(ix));
+      const GateTab gt = gate_tab(*this, key);
+      gate_compact(&gt, 1, st);
     }
     *n_launch = n_full;
     *d_count = it->second.d_count.as<int>();

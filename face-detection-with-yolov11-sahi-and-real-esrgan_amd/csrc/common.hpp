@@ -108,6 +108,17 @@ struct TileTab {
   int cap = 0;       // capacity mode: table capacity == launch extent
 };
 
+// one gated tile table as its compaction sees it (Level::compact_gated, det_post.hip)
+struct GateTab {
+  const int4* src;        // the full table
+  const int* first;       // [n_img + 1] first entry of each image in src; first[n_img] = n_entries
+  const int* active;      // [n_img] the gate
+  int4* dst;              // the compacted table
+  int* start;             // [n_img] scratch: first entry of each image in dst
+  int* d_count;           // entries of dst
+  int n_entries, n_img;
+};
+
 struct Level {
   int n = 0;
   std::vector<int> h, w;
@@ -148,12 +159,18 @@ struct Level {
   // by compact_gated(), which the owner runs once per run after the gate has been written and before the first conv that walks such a table.
   const int4* tile_table(int th, int* n_launch, const int** d_count, hipStream_t st, const int* gate = nullptr);
   std::map<int, TileTab> gated;   // by tile height; cap = entries of the full table
+  // per gated table: first[i] = index of image i's first entry in the full table, first[n] = its size (tables are built in image order; uploaded once,
+  // when the gated table is created), and start[i] = where image i's entries begin in the compacted table (written on the device by every compaction)
+  struct GateIdx { DevBuf first, start; };
+  std::map<int, GateIdx> gate_idx;
   const int* gate_active = nullptr;
-  // the compaction launch (launch_gate_compact, det_post.hpp): set by the owner of the gate before the first gated table is asked for, so that this
-  // file needs no device code: dst = the entries of `src` whose image is active, in their order; *d_count = how many
-  typedef void (*GateCompactFn)(const int4* src, int n_entries, const int4* tab, int n_img, int th, const int* active, int4* dst, int* d_count, hipStream_t st);
+  // the compaction launches (launch_gate_compact, det_post.hpp): set by the owner of the gate before the first gated table is asked for, so that this
+  // file needs no device code: for each table, dst = the entries of `src` whose image is active, in their order; *d_count = how many
+  typedef void (*GateCompactFn)(const GateTab* tabs, int n_tabs, hipStream_t st);
   GateCompactFn gate_compact = nullptr;
-  void compact_gated(hipStream_t st);
+  void compact_gated(hipStream_t st) { Level* me = this; compact_gated(&me, 1, st); }
+  // every gated table of several levels (each with its own gate) in one pair of launches
+  static void compact_gated(Level* const* levels, int n_levels, hipStream_t st);
   // the same tiles in the PACKED form of conv_trunk.hip, everything a work item needs in one 16-byte load:
   //   {first pixel of the image, y0 | x0 << 16, h | w << 16, tile columns | tile rows << 16 of the image}   (kept under key -th)
   const int4* tile_table_packed(int th, int* n_launch, const int** d_count, hipStream_t st);

@@ -75,22 +75,43 @@ __global__ void gate_kernel(const DecodeArgs a, const float* __restrict__ conf, 
   if (sc > *conf) active[img] = 1;
 }
 
-// one thread per entry of a tile table: entries of active images move up by the tiles of the inactive images in front of them
-__global__ void gate_compact_kernel(const int4* __restrict__ src, int n_entries, const int4* __restrict__ tab, int n_img, int th,
-                                    const int* __restrict__ active, int4* __restrict__ dst, int* __restrict__ d_count) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= n_entries) return;
-  const int4 t = src[e];
-  int skipped = 0, kept = 0;                  // tiles of inactive images before this entry's image; tiles of active images in the whole table
-  for (int i = 0; i < n_img; ++i) {
-    const int4 im = tab[i];
-    const int cnt = ((im.y + th - 1) / th) * ((im.z + 15) / 16);
-    const bool on = active[i] != 0;
-    if (!on && i < t.x) skipped += cnt;
-    if (on) kept += cnt;
+// Compaction of gated tile tables, two launches for up to GATE_TABS tables. Tables are built in image order, so image i's entries are
+// first[i] .. first[i + 1] - 1 of the full table and keep their order behind the entries of the active images before them.
+constexpr int GATE_TABS = 8;
+struct GateTabs { GateTab t[GATE_TABS]; };
+
+// workgroup b = table b: start[i] = entries of the active images before image i (an exclusive prefix over all n_img images, 256 at a time with a
+// carry), *d_count = entries of all active images
+__global__ void __launch_bounds__(256) gate_scan_kernel(const GateTabs tabs) {
+  const GateTab& g = tabs.t[blockIdx.x];
+  __shared__ int sums[256];
+  const int tid = threadIdx.x;
+  int carry = 0;
+  for (int base = 0; base < g.n_img; base += 256) {
+    const int i = base + tid;
+    const int cnt = (i < g.n_img && g.active[i] != 0) ? g.first[i + 1] - g.first[i] : 0;
+    sums[tid] = cnt;
+    __syncthreads();
+    for (int d = 1; d < 256; d <<= 1) {      // inclusive scan
+      const int v = tid >= d ? sums[tid - d] : 0;
+      __syncthreads();
+      sums[tid] += v;
+      __syncthreads();
+    }
+    if (i < g.n_img) g.start[i] = carry + sums[tid] - cnt;
+    carry += sums[255];
+    __syncthreads();                          // sums is rewritten by the next round
   }
-  if (active[t.x] != 0) dst[e - skipped] = t;
-  if (e == 0) *d_count = kept;
+  if (tid == 0) *g.d_count = carry;
+}
+
+// blockIdx.y = table, one thread per entry of the full table: entry e of an active image i goes to start[i] + (e - first[i])
+__global__ void __launch_bounds__(256) gate_scatter_kernel(const GateTabs tabs) {
+  const GateTab& g = tabs.t[blockIdx.y];
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= g.n_entries) return;
+  const int4 t = g.src[e];
+  if (g.active[t.x] != 0) g.dst[g.start[t.x] + (e - g.first[t.x])] = t;
 }
 
 // one thread per anchor: box (xyxy, net-input pixels), best class score/index; score = -1 when not > conf
@@ -330,10 +351,21 @@ void launch_det_gate(const DecodeArgs& a, const float* conf, int* active, hipStr
   FFP_HIP(hipGetLastError());
 }
 
-void launch_gate_compact(const int4* src, int n_entries, const int4* tab, int n_img, int th, const int* active, int4* dst, int* d_count, hipStream_t st) {
-  FFP_CHECK(n_entries > 0 && n_img > 0 && th > 0, FFP_ERR_ARG, "gate_compact: empty table");
-  hipLaunchKernelGGL(gate_compact_kernel, dim3((n_entries + 255) / 256), dim3(256), 0, st, src, n_entries, tab, n_img, th, active, dst, d_count);
-  FFP_HIP(hipGetLastError());
+void launch_gate_compact(const GateTab* tabs, int n_tabs, hipStream_t st) {
+  for (int b = 0; b < n_tabs; b += GATE_TABS) {      // one pair of launches per GATE_TABS tables
+    const int nb = std::min(GATE_TABS, n_tabs - b);
+    GateTabs a{};
+    int most = 0;
+    for (int k = 0; k < nb; ++k) {
+      const GateTab& g = tabs[b + k];
+      FFP_CHECK(g.src && g.first && g.active && g.dst && g.start && g.d_count && g.n_entries > 0 && g.n_img > 0, FFP_ERR_ARG, "gate_compact: empty table");
+      a.t[k] = g;
+      most = std::max(most, g.n_entries);
+    }
+    hipLaunchKernelGGL(gate_scan_kernel, dim3(nb), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(gate_scatter_kernel, dim3((most + 255) / 256, nb), dim3(256), 0, st, a);
+    FFP_HIP(hipGetLastError());
+  }
 }
 
 void launch_decode_raw(const DecodeArgs& a, float* out, const long long* out_off, hipStream_t st) {

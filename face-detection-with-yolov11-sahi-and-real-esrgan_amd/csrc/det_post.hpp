@@ -24,9 +24,9 @@ struct DetImg {
 void launch_decode(const DecodeArgs& a, float conf, float4* boxes, float* scores, int* classes, hipStream_t st);
 // active[img] = whether image img has an anchor that launch_decode would let through at *conf (device float): cleared, then set, by two launches
 void launch_det_gate(const DecodeArgs& a, const float* conf, int* active, hipStream_t st);
-// dst = the entries of `src` (Level::tile_table, unpacked form) whose image is active, in their order; *d_count = how many. `tab` = the level's image
-// table, th = the tile height of `src` (Level::gate_compact)
-void launch_gate_compact(const int4* src, int n_entries, const int4* tab, int n_img, int th, const int* active, int4* dst, int* d_count, hipStream_t st);
+// for each of the n_tabs gated tables (Level::tile_table, unpacked form): dst = the entries of src whose image is active, in their order; *d_count =
+// how many. A scan over the images and a scatter over the entries, one pair of launches for every 8 tables (Level::gate_compact)
+void launch_gate_compact(const GateTab* tabs, int n_tabs, hipStream_t st);
 void launch_decode_raw(const DecodeArgs& a, float* out, const long long* out_off, hipStream_t st);
 void launch_nms(const DecodeArgs& a, const float4* boxes, const float* scores, const int* classes, int* cand, float* cscore,
                 const DetImg* imgs, float iou_thr, int max_det, int round_boxes, int det_stride, float* out_dets,

@@ -44,6 +44,7 @@ struct ConvOp {
   const DenseF32* fin_w = nullptr;      // its values
   TView fin_out;
   std::string label;                    // step / profile name of an op that stands for more than its own conv (empty: pc->name)
+  int dwpw_force = 0;     // tests of the depthwise-fused kernel: tile height (0 the launcher's choice, 1 = 16 rows, 2 = 8 rows) | workgroup cap << 2 (0: none)
   int force_shape = -1;   // tuning and tests: a ConvShape number (conv_route.hpp) pins the kernel and its workgroup shape; SHAPE_AUTO (-1): conv_route decides
 };
 void launch_conv(const ConvOp& op, hipStream_t st);      // on the kernel conv_route (conv_route.hpp) picks

@@ -427,7 +427,7 @@ void DetEngine::build_plan(DetPlan& P, const std::vector<int>& hs, const std::ve
     const int nc = nc_, nkpt = nkpt_;
     P.add([pp, nc, nkpt](hipStream_t s) {
       launch_det_gate(decode_args(*pp, nc, nkpt), pp->d_conf.as<float>(), pp->d_active.as<int>(), s);
-      for (int l = 3; l < 6; ++l) pp->L[l]->compact_gated(s);      // tables the first run's launchers created (they compact what they create)
+      Level::compact_gated(&pp->L[3], 3, s);      // tables the first run's launchers created (they compact what they create): one scan and one scatter for all of them
     });
   }
   // x16, x19 and x22 live until their towers have been issued

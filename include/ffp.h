@@ -401,6 +401,9 @@ int ffp_op_conv2d_act_post(int act);
  * ffp_op_dwconv3x3 (family 2: 1 column walk, 2 strip) launches from now on (process-wide; 0 = the automatic choice, the default).
  * A variant that cannot run the op is an error of the following op call. Engines are not affected. */
 int ffp_op_variant(int family, int variant);
+/* Test hook of ffp_op_cls_tower: rows = 16 or 8 pins the tile height of its two launches (0: the launcher's choice from the batch's shapes),
+ * wg_cap > 0 launches at most that many workgroups, so that a small batch walks its tiles persistently (0: no cap). Process-wide. */
+int ffp_op_cls_tower_variant(int rows, int wg_cap);
 
 /* SPPF: y1, y2, y3 = three chained MaxPool2d(5, 1, 2) of x, written to the slices y*_coff of one buffer y. */
 int ffp_op_sppf_pool(int device, int precision, int n, const int32_t* hs, const int32_t* ws, int px_align, int c, const float* x, int x_cs,
