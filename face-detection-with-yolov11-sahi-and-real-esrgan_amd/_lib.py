@@ -123,6 +123,12 @@ _SIGS = {
     "ffp_jpeg_encode_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _p(C.c_uint8), C.c_int64, _p(C.c_int64)]),
     "ffp_jpeg_encode_batch_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, _p(C.c_int64), _p(C.c_int32), _p(C.c_int32), _p(C.c_int64), C.c_int, C.c_int, _p(C.c_uint8),
                                             C.c_int64, _p(C.c_int64)]),
+    "ffp_png_bound": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "ffp_png_segment_bytes": (C.c_int, []),
+    "ffp_png_encode": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_uint8), C.c_int64, _p(C.c_int64)]),
+    "ffp_png_encode_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _p(C.c_uint8), C.c_int64, _p(C.c_int64)]),
+    "ffp_png_encode_batch_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, _p(C.c_int64), _p(C.c_int32), _p(C.c_int32), _p(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_int,
+                                           _p(C.c_uint8), C.c_int64, _p(C.c_int64)]),
     "ffp_jpeg_info": (C.c_int, [_p(C.c_uint8), C.c_int64, _p(C.c_int32), _p(C.c_int32), _p(C.c_int32)]),
     "ffp_jpeg_decode": (C.c_int, [C.c_int, _p(C.c_uint8), C.c_int64, C.c_int, _p(C.c_uint8), C.c_int64]),
     "ffp_jpeg_decode_dev": (C.c_int, [C.c_int, _p(C.c_uint8), C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int64]),
@@ -1406,6 +1412,69 @@ def jpeg_encode_batch_dev(d_base: int, offsets, hs, ws, quality: int = 95, bgr: 
     oo = np.zeros(n + 1, np.int64)
     _check(lib().ffp_jpeg_encode_batch_dev(device, C.c_void_p(d_base), n, offsets.ctypes.data_as(_p(C.c_int64)), hs.ctypes.data_as(_p(C.c_int32)),
                                            ws.ctypes.data_as(_p(C.c_int32)), None, int(bgr), quality, out.ctypes.data_as(_p(C.c_uint8)), cap, oo.ctypes.data_as(_p(C.c_int64))))
+    return [out[oo[i]:oo[i + 1]].tobytes() for i in range(n)]
+
+
+def png_bound(h: int, w: int, channels: int = 3, bit_depth: int = 8) -> int:
+    """Worst-case size of the PNG file of an h x w image (every segment stored)."""
+    n = lib().ffp_png_bound(h, w, channels, bit_depth)
+    if n < 0:
+        raise FfpError(1, lib().ffp_last_error().decode("utf-8", "replace"))
+    return int(n)
+
+
+def png_segment_bytes() -> int:
+    """Bytes of filtered stream one workgroup compresses on its own (one deflate block, one IDAT chunk)."""
+    return int(lib().ffp_png_segment_bytes())
+
+
+def _png_geometry(img: np.ndarray):
+    if img.dtype not in (np.uint8, np.uint16) or img.ndim not in (2, 3) or (img.ndim == 3 and img.shape[2] not in (1, 3, 4)):
+        raise ValueError(f"png_encode: uint8 or uint16 of shape (H, W), (H, W, 1), (H, W, 3) or (H, W, 4), not {img.dtype} {img.shape}")
+    return img.shape[0], img.shape[1], (1 if img.ndim == 2 else img.shape[2]), 8 * img.dtype.itemsize
+
+
+def png_encode(img: np.ndarray, level: int = 1, bgr: bool = False, device: int = 0, cap: int = None) -> bytes:
+    """PNG file of a gray, RGB(A) or BGR(A) uint8 / uint16 image, filtered, compressed and checksummed on the GPU (csrc/png.hip).
+    level 0: stored blocks; every level >= 1 is the one device compressor. cap: output capacity, the worst case by default."""
+    img = np.ascontiguousarray(img)
+    h, w, ch, depth = _png_geometry(img)
+    cap = png_bound(h, w, ch, depth) if cap is None else int(cap)
+    out = np.empty(max(cap, 1), np.uint8)
+    n = C.c_int64(0)
+    rc = lib().ffp_png_encode(device, C.c_void_p(img.ctypes.data), h, w, ch, depth, int(bgr), level, out.ctypes.data_as(_p(C.c_uint8)), cap, C.byref(n))
+    if rc != 0:
+        e = FfpError(rc, lib().ffp_last_error().decode("utf-8", "replace"))
+        e.needed = n.value                                   # the size the file has, when the capacity was the trouble
+        raise e
+    return out[:n.value].tobytes()
+
+
+def png_encode_dev(d_ptr: int, h: int, w: int, channels: int = 3, bit_depth: int = 8, row_stride: int = None, level: int = 1, bgr: bool = True,
+                   device: int = 0) -> bytes:
+    """Same for an image already in device memory (pointer + row pitch in bytes): only the file crosses PCIe."""
+    if row_stride is None:
+        row_stride = w * channels * (bit_depth // 8)
+    cap = png_bound(h, w, channels, bit_depth)
+    out = np.empty(cap, np.uint8)
+    n = C.c_int64(0)
+    _check(lib().ffp_png_encode_dev(device, C.c_void_p(d_ptr), h, w, channels, bit_depth, row_stride, int(bgr), level, out.ctypes.data_as(_p(C.c_uint8)), cap,
+                                    C.byref(n)))
+    return out[:n.value].tobytes()
+
+
+def png_encode_batch_dev(d_base: int, offsets, hs, ws, channels: int = 3, bit_depth: int = 8, strides=None, level: int = 1, bgr: bool = True, device: int = 0):
+    """n device-resident images (d_base + offsets[i] bytes, hs[i] x ws[i], row pitch strides[i] or packed) -> list of PNG files, one pass."""
+    offsets = np.ascontiguousarray(offsets, np.int64)
+    hs, ws = np.ascontiguousarray(hs, np.int32), np.ascontiguousarray(ws, np.int32)
+    n = len(offsets)
+    st = None if strides is None else np.ascontiguousarray(strides, np.int64)
+    cap = sum(png_bound(int(h), int(w), channels, bit_depth) for h, w in zip(hs, ws))
+    out = np.empty(max(cap, 1), np.uint8)
+    oo = np.zeros(n + 1, np.int64)
+    _check(lib().ffp_png_encode_batch_dev(device, C.c_void_p(d_base), n, offsets.ctypes.data_as(_p(C.c_int64)), hs.ctypes.data_as(_p(C.c_int32)),
+                                          ws.ctypes.data_as(_p(C.c_int32)), None if st is None else st.ctypes.data_as(_p(C.c_int64)), channels, bit_depth,
+                                          int(bgr), level, out.ctypes.data_as(_p(C.c_uint8)), cap, oo.ctypes.data_as(_p(C.c_int64))))
     return [out[oo[i]:oo[i + 1]].tobytes() for i in range(n)]
 
 

@@ -7,7 +7,10 @@ not OpenCV's glyphs) for pipeline_v3_RTDETR/inference.py; utils.visualization of
 
 `.jpg` files go through this build's JPEG codec on the GPU (csrc/jpeg.hip: ffp_jpeg_decode / ffp_jpeg_encode) whenever a device is
 visible; its output is byte-identical (files) and pixel-identical (decoded arrays) to the libjpeg-turbo inside OpenCV and Pillow
-(tests/test_gpu_jpeg.py) for YCbCr / grayscale baseline files, so the choice changes the time, not one bit of the result. Files the
+(tests/test_gpu_jpeg.py) for YCbCr / grayscale baseline files, so the choice changes the time, not one bit of the result. `.png`
+files are written by the device encoder too (csrc/png.hip: ffp_png_encode; uint8 / uint16, gray, BGR or BGRA): other bytes than
+libpng's, the same pixels (tests/test_gpu_png.py), 10 to 100 times sooner than Pillow at compress_level=1 (profiles/png_encode_mi355x.json);
+reading PNG stays with Pillow. Files the
 device codec does not read (progressive, RGB-coded with Adobe transform 0 or R/G/B component ids) and machines without a GPU use
 Pillow, and say so once on stderr. Like `cv2.imread`, `imread` applies the EXIF orientation tag (not with IMREAD_UNCHANGED).
 """
@@ -44,7 +47,7 @@ else:
     COLOR_BGR2RGB, COLOR_RGB2BGR = 4, 4
     INTER_NEAREST, INTER_LINEAR, INTER_CUBIC, INTER_AREA, INTER_LANCZOS4 = 0, 1, 2, 3, 4
 
-    _state = {"gpu": None, "told": False}
+    _state = {"gpu": None, "told": False, "told_png": False}
 
     def _gpu_codec():
         if _state["gpu"] is None:
@@ -59,6 +62,14 @@ else:
         if not _state["told"]:
             _state["told"] = True
             print(f"cv2 shim: JPEG through Pillow ({why}); same bytes, host speed", file=sys.stderr)
+
+    def _tell_png(why):
+        if not _state["told_png"]:
+            _state["told_png"] = True
+            print(f"cv2 shim: PNG through Pillow ({why}); same pixels, host speed", file=sys.stderr)
+
+    def _is_png(path):
+        return os.path.splitext(str(path))[1].lower() == ".png"
 
     def _is_jpeg(path):
         return os.path.splitext(str(path))[1].lower() in (".jpg", ".jpeg")
@@ -111,14 +122,25 @@ else:
             return None
 
     def imwrite(path, img, params=None):
-        """JPEG quality from [IMWRITE_JPEG_QUALITY, q] (OpenCV default 95). Returns success like OpenCV."""
+        """JPEG quality from [IMWRITE_JPEG_QUALITY, q] (OpenCV default 95); [IMWRITE_PNG_COMPRESSION, 0] gives stored blocks, every
+        other level the device's one compressor. Returns success like OpenCV."""
         try:
-            q = 95
+            q, png_level = 95, 1
             if params:
                 for k, v in zip(params[0::2], params[1::2]):
                     if k == IMWRITE_JPEG_QUALITY:
                         q = int(v)
+                    elif k == IMWRITE_PNG_COMPRESSION:
+                        png_level = int(v)
             a = np.ascontiguousarray(img)
+            if _is_png(path) and a.dtype in (np.uint8, np.uint16) and a.size > 0 and (a.ndim == 2 or (a.ndim == 3 and a.shape[2] in (1, 3, 4))):
+                codec = _gpu_codec()
+                if codec:
+                    data = codec.png_encode(a, 0 if png_level == 0 else 1, bgr=True)
+                    with open(path, "wb") as fh:
+                        fh.write(data)
+                    return True
+                _tell_png("no GPU visible")
             if _is_jpeg(path) and a.ndim == 3 and a.shape[2] == 3 and a.dtype == np.uint8:
                 codec = _gpu_codec()
                 if codec:

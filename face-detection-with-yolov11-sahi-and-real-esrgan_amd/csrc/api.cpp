@@ -10,6 +10,7 @@
 #include "eval.hpp"
 #include "iqa.hpp"
 #include "jpeg.hpp"
+#include "png.hpp"
 #include "sr_ops.hpp"
 #include "scrfd.hpp"
 #include "rtdetr.hpp"
@@ -984,6 +985,93 @@ int ffp_jpeg_decode_stats(int64_t* device_decodes, int64_t* host_fallbacks, int6
   if (device_decodes) *device_decodes = a;
   if (host_fallbacks) *host_fallbacks = b;
   if (extra_sync_rounds) *extra_sync_rounds = c;
+  FFP_API_END
+}
+
+// ---- PNG at the file boundaries (png.hip) -----------------------------------------------------------------------------------------
+int64_t ffp_png_bound(int h, int w, int channels, int bit_depth) {
+  try {
+    return png_bound(h, w, channels, bit_depth);
+  } catch (const ffp::Error& e) {
+    ffp::set_last_error(e.what());
+    return -1;
+  }
+}
+
+int ffp_png_segment_bytes(void) { return kPngSegmentBytes; }
+
+// the three entries below: device chosen, arguments checked, one launch sequence on an I/O stream; out_offsets is filled before the
+// capacity is judged
+static void png_encode_any(int device, const void* d_base, int n, const int64_t* offsets, const int32_t* hs, const int32_t* ws, const int64_t* strides, int channels,
+                           int bit_depth, int bgr, int level, uint8_t* out, int64_t cap, int64_t* out_offsets) {
+  FFP_CHECK(n >= 0 && out_offsets && (n == 0 || (d_base && offsets && hs && ws)), FFP_ERR_ARG, "png_encode: bad arguments");
+  FFP_CHECK((channels == 1 || channels == 3 || channels == 4) && (bit_depth == 8 || bit_depth == 16), FFP_ERR_ARG,
+            "png_encode: %d channels of %d bits (gray, RGB or RGBA at depth 8 or 16 are written)", channels, bit_depth);
+  int ndev = 0;
+  FFP_CHECK(hipGetDeviceCount(&ndev) == hipSuccess && device >= 0 && device < ndev, FFP_ERR_HIP, "png_encode: no HIP device %d (no CPU path)", device);
+  FFP_HIP(hipSetDevice(device));
+  std::vector<PngSrc> src((size_t)n);
+  for (int i = 0; i < n; ++i)
+    src[i] = PngSrc{(const unsigned char*)d_base + offsets[i], hs[i], ws[i], strides ? strides[i] : (long long)ws[i] * channels * (bit_depth / 8)};
+  std::vector<long long> off((size_t)n + 1, 0);
+  hipStream_t st;
+  st = io_stream();
+  long long total = 0;
+  try {
+    total = png_encode_batch_device(src.data(), n, channels, bit_depth, bgr, level, off.data(), out, cap, st);
+  } catch (...) {
+    (void)hipStreamDestroy(st);
+    throw;
+  }
+  (void)hipStreamDestroy(st);
+  for (int i = 0; i <= n; ++i) out_offsets[i] = off[i];
+  FFP_CHECK(out && cap >= total, FFP_ERR_ARG, "png_encode: output buffer too small (%lld bytes needed)", total);
+}
+
+int ffp_png_encode_batch_dev(int device, const void* d_base, int n, const int64_t* offsets, const int32_t* hs, const int32_t* ws, const int64_t* strides,
+                             int channels, int bit_depth, int bgr, int level, uint8_t* out, int64_t cap, int64_t* out_offsets) {
+  FFP_API_BEGIN
+  png_encode_any(device, d_base, n, offsets, hs, ws, strides, channels, bit_depth, bgr, level, out, cap, out_offsets);
+  FFP_API_END
+}
+
+int ffp_png_encode_dev(int device, const void* d_img, int h, int w, int channels, int bit_depth, int64_t row_stride, int bgr, int level, uint8_t* out, int64_t cap,
+                       int64_t* out_size) {
+  FFP_API_BEGIN
+  FFP_CHECK(out_size, FFP_ERR_ARG, "png_encode: out_size is null");
+  const int64_t zero = 0;
+  const int32_t hh = h, ww = w;
+  int64_t oo[2] = {0, 0};
+  try {
+    png_encode_any(device, d_img, 1, &zero, &hh, &ww, &row_stride, channels, bit_depth, bgr, level, out, cap, oo);
+  } catch (...) {
+    *out_size = oo[1];
+    throw;
+  }
+  *out_size = oo[1];
+  FFP_API_END
+}
+
+int ffp_png_encode(int device, const void* img, int h, int w, int channels, int bit_depth, int bgr, int level, uint8_t* out, int64_t cap, int64_t* out_size) {
+  FFP_API_BEGIN
+  FFP_CHECK(img && h > 0 && w > 0 && out_size, FFP_ERR_ARG, "png_encode: bad arguments");
+  FFP_CHECK((channels == 1 || channels == 3 || channels == 4) && (bit_depth == 8 || bit_depth == 16), FFP_ERR_ARG,
+            "png_encode: %d channels of %d bits (gray, RGB or RGBA at depth 8 or 16 are written)", channels, bit_depth);
+  int ndev = 0;
+  FFP_CHECK(hipGetDeviceCount(&ndev) == hipSuccess && device >= 0 && device < ndev, FFP_ERR_HIP, "png_encode: no HIP device %d (no CPU path)", device);
+  FFP_HIP(hipSetDevice(device));
+  const int64_t row = (int64_t)w * channels * (bit_depth / 8), zero = 0;
+  DevBuf d((size_t)h * (size_t)row);
+  FFP_HIP(hipMemcpy(d.p, img, (size_t)h * (size_t)row, hipMemcpyHostToDevice));
+  const int32_t hh = h, ww = w;
+  int64_t oo[2] = {0, 0};
+  try {
+    png_encode_any(device, d.p, 1, &zero, &hh, &ww, &row, channels, bit_depth, bgr, level, out, cap, oo);
+  } catch (...) {
+    *out_size = oo[1];
+    throw;
+  }
+  *out_size = oo[1];
   FFP_API_END
 }
 

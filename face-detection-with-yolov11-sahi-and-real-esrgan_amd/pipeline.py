@@ -313,6 +313,13 @@ class CropEnhancerMixin:
     def wait_sr(self):
         _lib._check(_lib.lib().ffp_sr_wait(self.sr.handle))
 
+    def encode_png(self, d_img, H: int, W: int, channels: int = 3, level: int = 1) -> bytes:
+        """A resident BGR(A) / gray uint8 or uint16 image (a frame, or an SR output inside enhance_crops' tensor: pass the slice that starts
+        at its offset) leaves the device as a finished PNG file (csrc/png.hip): only the file crosses PCIe. Work queued on other
+        streams that writes d_img must have finished (wait_sr())."""
+        depth = 8 * d_img.element_size()
+        return _lib.png_encode_dev(d_img.data_ptr(), H, W, channels, depth, W * channels * (depth // 8), level=level, bgr=True, device=self.dev.index or 0)
+
 
 class FramePipeline(CropEnhancerMixin):
     """One rank's share of the pipeline. `torch` is imported lazily: it provides device tensors and the collective."""

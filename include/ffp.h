@@ -365,6 +365,34 @@ int ffp_jpeg_decode_dev(int device, const uint8_t* data, int64_t n, int bgr, uin
  * files decoded on the device, files that fell back to the host decoder, extra synchronisation rounds (beyond the one queued blindly). */
 int ffp_jpeg_decode_stats(int64_t* device_decodes, int64_t* host_fallbacks, int64_t* extra_sync_rounds);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * PNG at the file boundaries (encoding only; reading PNG stays with the host)
+ * ------------------------------------------------------------------------------------------------------- */
+
+/* Replaces `cv2.imwrite(path, img)` for .png paths (/root/reference/pipeline_v1_detection_first/app_v1.py:39, app_sahi_detection.py:31,
+ * app_enhancer.py:43 and pipeline_v2_enhancement_first/app_v2.py:82 `visual_*.png`; app_v2.py:105-106 the enhanced frame;
+ * utils/enhancer.py:273-278 enhanced crops whose path is not .jpg; the 16-bit results of RealESRGANer.enhance). The file is written on
+ * the device and only the file crosses PCIe: signature, IHDR, IDAT..., IEND; colour type gray (channels 1), RGB (3) or RGBA (4) at
+ * bit_depth 8 or 16 (samples in host byte order in memory, big-endian in the file); no interlace, palette or ancillary chunk. bgr = 1:
+ * the image is BGR(A), OpenCV's order. One filter byte per row by libpng's minimum sum of absolute differences (signed bytes; ties to the
+ * lowest type). One zlib stream: the filtered bytes are cut into segments of ffp_png_segment_bytes() bytes, each compressed on its own
+ * (LZ77 inside the segment; fixed or dynamic Huffman code, whichever is smaller; stored when it does not shrink) into one IDAT chunk,
+ * every segment but the last ending with an empty stored block; the Adler-32 is a last 4-byte IDAT. level 0: stored blocks
+ * throughout; every level >= 1 is the same one compressor. The contract is what a PNG reader decodes, not libpng's bytes; the same
+ * pixels always give the same file. ffp_png_bound: worst-case file size (-1 for a geometry that is not written). *out_size is set also
+ * when cap is too small (FFP_ERR_ARG, call again). _dev: the image is in device memory (row pitch in bytes). */
+int64_t ffp_png_bound(int h, int w, int channels, int bit_depth);
+int ffp_png_segment_bytes(void);
+int ffp_png_encode(int device, const void* img, int h, int w, int channels, int bit_depth, int bgr, int level, uint8_t* out, int64_t cap, int64_t* out_size);
+int ffp_png_encode_dev(int device, const void* d_img, int h, int w, int channels, int bit_depth, int64_t row_stride, int bgr, int level, uint8_t* out, int64_t cap,
+                       int64_t* out_size);
+/* The per-crop `cv2.imwrite` loop of enhance_face_crops_batch (/root/reference/utils/enhancer.py:344-391) for .png outputs as ONE pass,
+ * with the layout of ffp_jpeg_encode_batch_dev: image i is hs[i] x ws[i] at d_base + offsets[i] bytes (row pitch strides[i], or the
+ * packed row when strides is NULL); file i is out[out_offsets[i] .. out_offsets[i+1]) (n+1 entries, filled even when cap is too small:
+ * FFP_ERR_ARG). File i is byte for byte what ffp_png_encode_dev writes for image i. */
+int ffp_png_encode_batch_dev(int device, const void* d_base, int n, const int64_t* offsets, const int32_t* hs, const int32_t* ws, const int64_t* strides,
+                             int channels, int bit_depth, int bgr, int level, uint8_t* out, int64_t cap, int64_t* out_offsets);
+
 /* 1x1 conv over the virtual concat [nearest_x2(coarse) | fine] (the YOLO neck's Upsample + Concat + C3k2.cv1 without
  * materialising the upsampled tensor: /root/reference's model graph via ultralytics' yolo11-pose.yaml layers 11-13 and 14-16).
  * coarse: [n][h/2][w/2][c_up] (c_up a multiple of 64), fine: [n][h][w][c_fine]; wt: [cout][c_up + c_fine] (input channel
