@@ -47,6 +47,7 @@ _SIGS = {
     "ffp_version": (C.c_int, []),
     "ffp_device_count": (C.c_int, [_p(C.c_int)]),
     "ffp_slice_bboxes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _p(C.c_int32), C.c_int, _p(C.c_int32)]),
+    "ffp_tile_chunks": (C.c_int, [C.c_int, C.c_int, _p(C.c_int32), C.c_int, _p(C.c_int32)]),
     "ffp_letterbox_geometry": (C.c_int, [C.c_int, C.c_int, C.c_int, _p(C.c_int32)]),
     "ffp_det_create": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_void_p)]),
     "ffp_det_destroy": (None, [C.c_void_p]),
@@ -288,6 +289,17 @@ def slice_bboxes(H: int, W: int, slice_h: int, slice_w: int, overlap_h: float = 
     return out
 
 
+def tile_chunks(n: int, max_batch: int) -> List[int]:
+    """The sizes of the network batches n tiles run in at a positive max_batch (ffp_tile_chunks)."""
+    out, k = np.zeros(max(n, 1), np.int32), C.c_int32(0)               # never more chunks than items
+    _check(lib().ffp_tile_chunks(n, max_batch, _ip(out), len(out), C.byref(k)))
+    return out[:k.value].tolist()
+
+
+def _as_tiles(tiles) -> np.ndarray:
+    return np.ascontiguousarray(np.asarray(tiles, np.int32).reshape(-1, 4))
+
+
 def letterbox_geometry(h: int, w: int, imgsz: int) -> Tuple[int, int, int, int, int, int]:
     out = np.zeros(6, np.int32)
     _check(lib().ffp_letterbox_geometry(h, w, imgsz, _ip(out)))
@@ -369,7 +381,7 @@ class FaceDetector:
         frame and shifted to frame pixels with their keypoints; a box whose far corner is negative raises FfpError, as the reference raises.
         max_batch: items per network batch (0: all tiles in one; < 0: FFP_SCRFD_TILES_DEFAULT_BATCH)."""
         f = _as_frame(frame)
-        t = np.ascontiguousarray(np.asarray(tiles, np.int32).reshape(-1, 4))
+        t = _as_tiles(tiles)
         n = t.shape[0]
         plain = conf is None and mode == "local" and max_batch == 0
         while True:
@@ -393,7 +405,7 @@ class FaceDetector:
                         mode: str = "local", max_batch: int = 0):
         """infer_tiles with the frame (H x W x 3 uint8), d_out [n][cap][21] float32 and d_counts [n] int32 given as device pointers
         (ffp_scrfd_infer_tiles_dev). Returns after the engine's stream has drained."""
-        t = np.ascontiguousarray(np.asarray(tiles, np.int32).reshape(-1, 4))
+        t = _as_tiles(tiles)
         _check(lib().ffp_scrfd_infer_tiles_dev(self._h, d_frame, H, W, chan_order, _ip(t), t.shape[0], int(det_size[0]), int(det_size[1]), det_thresh,
                                                nms_thresh, det_thresh if conf is None else conf, self.TILE_MODES[mode], max_batch, d_out, cap,
                                                d_counts))
@@ -445,7 +457,7 @@ class FaceDetector:
                     chan_order: int = CHAN_AS_BGR) -> List[List[np.ndarray]]:
         """-> per tile the graph outputs in file order, each (anchors, values) float32 (scores after the sigmoid)."""
         f = _as_frame(frame)
-        t = np.ascontiguousarray(np.asarray(tiles, np.int32).reshape(-1, 4))
+        t = _as_tiles(tiles)
         n = t.shape[0]
         W, H = int(det_size[0]), int(det_size[1])
         per = sum((H // s) * (W // s) * 2 * v for s in (8, 16, 32) for v in (1, 4, 10))
@@ -545,7 +557,7 @@ class RTDETRDetector:
         pixels, predict()'s rows of the crop; "sahi": clipped against the frame, invalid boxes dropped, shifted to frame pixels (float boxes).
         max_batch: items per network batch (0: FFP_RT_TILES_DEFAULT_BATCH)."""
         f = _as_frame(frame)
-        t = np.ascontiguousarray(np.asarray(tiles, np.int32).reshape(-1, 4))
+        t = _as_tiles(tiles)
         n = t.shape[0]
         dets = np.zeros((max(n, 1), self.NQ, 6), np.float32)
         counts = np.zeros(max(n, 1), np.int32)
@@ -611,7 +623,7 @@ class Detector:
                     max_det: int = 300, chan_order: int = CHAN_AS_BGR, round_boxes: bool = False) -> List[np.ndarray]:
         """-> per tile (n_i, 6+3*nkpt) float32 rows [x1,y1,x2,y2,score,cls,kpts] in tile-local pixels (not truncated)."""
         f = _as_frame(frame)
-        t = np.ascontiguousarray(np.asarray(tiles, np.int32).reshape(-1, 4))
+        t = _as_tiles(tiles)
         n = t.shape[0]
         dets = np.zeros((n, max_det, self.stride), np.float32)
         counts = np.zeros(n, np.int32)
@@ -623,7 +635,7 @@ class Detector:
                     chan_order: int = CHAN_AS_BGR) -> List[np.ndarray]:
         """-> per tile the (4+nc+3*nkpt, A) inference-mode head output."""
         f = _as_frame(frame)
-        t = np.ascontiguousarray(np.asarray(tiles, np.int32).reshape(-1, 4))
+        t = _as_tiles(tiles)
         n = t.shape[0]
         no = 4 + self.nc + 3 * self.nkpt
         cap = 0
@@ -1308,7 +1320,7 @@ def op_rt_post_tiles(ref, r_coff: int, scores, s_coff: int, nc: int, conf: float
     "sahi". det: (n, 300, 6) array to fill (default zeros). Returns (det, counts)."""
     ref, scores = _f32(ref), _f32(scores)
     n = ref.shape[0]
-    t = np.ascontiguousarray(np.asarray(tiles, np.int32).reshape(-1, 4))
+    t = _as_tiles(tiles)
     if ref.shape[:2] != (n, 300) or scores.shape[:2] != (n, 300) or t.shape[0] != n:
         raise ValueError("rt_post_tiles: shapes")
     o = _f32(det).copy() if det is not None else np.zeros((n, 300, 6), np.float32)
@@ -1372,7 +1384,7 @@ def op_scrfd_sahi_rows(dets: np.ndarray, counts, tiles, full_shape, conf: float,
     if d.ndim != 3 or d.shape[2] != FaceDetector.STRIDE:
         raise ValueError(f"dets must be (n, cap, {FaceDetector.STRIDE})")
     c = np.ascontiguousarray(counts, np.int32).copy()
-    t = np.ascontiguousarray(np.asarray(tiles, np.int32).reshape(-1, 4))
+    t = _as_tiles(tiles)
     if c.shape != (n,) or t.shape != (n, 4):
         raise ValueError("counts / tiles do not match dets")
     bad = C.c_int32(-1)

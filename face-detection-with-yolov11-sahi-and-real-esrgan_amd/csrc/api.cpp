@@ -13,6 +13,7 @@
 #include "png.hpp"
 #include "sr_ops.hpp"
 #include "scrfd.hpp"
+#include "sliced.hpp"
 #include "rtdetr.hpp"
 #include "yolo11.hpp"
 
@@ -48,46 +49,9 @@ void check_offsets(const int64_t* off, int n, const char* what) {
   for (int i = 0; i < n; ++i) FFP_CHECK(off[i + 1] >= off[i], FFP_ERR_ARG, "%s offsets must not decrease (image %d)", what, i);
 }
 
-std::vector<int32_t> slice_bboxes(int H, int W, int sh, int sw, float oh, float ow) {
-  // sahi.slicing.get_slice_bboxes
-  FFP_CHECK(H > 0 && W > 0 && sh > 0 && sw > 0, FFP_ERR_ARG, "slice_bboxes: sizes must be positive");
-  FFP_CHECK(oh >= 0.f && oh < 1.f && ow >= 0.f && ow < 1.f, FFP_ERR_ARG, "slice_bboxes: overlap ratio must be in [0,1)");
-  std::vector<int32_t> out;
-  int y_max = 0, y_min = 0;
-  const int y_overlap = (int)((double)oh * sh), x_overlap = (int)((double)ow * sw);
-  while (y_max < H) {
-    int x_min = 0, x_max = 0;
-    y_max = y_min + sh;
-    while (x_max < W) {
-      x_max = x_min + sw;
-      if (y_max > H || x_max > W) {
-        const int xmax = std::min(W, x_max), ymax = std::min(H, y_max);
-        const int xmin = std::max(0, xmax - sw), ymin = std::max(0, ymax - sh);
-        out.insert(out.end(), {xmin, ymin, xmax, ymax});
-      } else {
-        out.insert(out.end(), {x_min, y_min, x_max, y_max});
-      }
-      x_min = x_max - x_overlap;
-    }
-    y_min = y_max - y_overlap;
-  }
-  return out;
-}
-
-// the items of get_sliced_prediction: the slice grid, then the full frame when there is more than one slice and it is asked for
-std::vector<int32_t> sliced_items(int H, int W, int slice_h, int slice_w, float oh, float ow, int perform_standard_pred) {
-  FFP_CHECK(H > 0 && W > 0, FFP_ERR_ARG, "frame is empty");
-  std::vector<int32_t> items = slice_bboxes(H, W, slice_h, slice_w, oh, ow);
-  if (items.size() / 4 > 1 && perform_standard_pred) items.insert(items.end(), {0, 0, W, H});   // sahi/predict.py: the full-frame pass
-  return items;
-}
-
 void upload_frame(DetEngine& e, const uint8_t* frame, int H, int W) {
-  FFP_CHECK(frame && H > 0 && W > 0, FFP_ERR_ARG, "frame is null or empty");
   FFP_HIP(hipSetDevice(e.device()));
-  const size_t nb = (size_t)H * W * 3;
-  e.scratch_frame.ensure(nb);
-  FFP_HIP(hipMemcpyAsync(e.scratch_frame.p, frame, nb, hipMemcpyHostToDevice, e.stream()));
+  ffp::upload_frame(e.scratch_frame, frame, H, W, e.stream());
 }
 
 // the host side of a Lanczos4 resize: tables built here, uploaded on `st` into `tab` (the host copy must outlive the upload)
@@ -124,6 +88,15 @@ int ffp_slice_bboxes(int H, int W, int sh, int sw, float oh, float ow, int32_t* 
   const int n = (int)b.size() / 4;
   *out_n = n;
   if (out_xyxy && cap > 0) std::memcpy(out_xyxy, b.data(), sizeof(int32_t) * 4 * (size_t)std::min(n, cap));
+  FFP_API_END
+}
+
+int ffp_tile_chunks(int n, int max_batch, int32_t* out, int cap, int32_t* out_n) {
+  FFP_API_BEGIN
+  FFP_CHECK(out_n, FFP_ERR_ARG, "null output");
+  const std::vector<int> c = even_chunks(n, max_batch);
+  *out_n = (int)c.size();
+  if (out && cap > 0) std::copy(c.begin(), c.begin() + std::min((int)c.size(), cap), out);
   FFP_API_END
 }
 
@@ -232,9 +205,7 @@ static void stage(DetEngine& e, const uint8_t* d_frame, int H, int W, int chan_o
                   int perform_standard_pred, int imgsz, float conf, float iou, int max_det, int round_boxes, int rank, int world,
                   float* d_dets, int32_t* d_counts, int* n_local, int* n_total) {
   FFP_CHECK(world >= 1 && rank >= 0 && rank < world, FFP_ERR_ARG, "rank %d of %d", rank, world);
-  std::vector<int32_t> items = slice_bboxes(H, W, slice_h, slice_w, oh, ow);
-  const int n_slices = (int)items.size() / 4;
-  if (n_slices > 1 && perform_standard_pred) items.insert(items.end(), {0, 0, W, H});   // docs sahi/predict.py:301-314
+  const std::vector<int32_t> items = sliced_items(H, W, slice_h, slice_w, oh, ow, perform_standard_pred);
   const int total = (int)items.size() / 4;
   const int per = (total + world - 1) / world;
   const int lo = std::min(rank * per, total), hi = std::min(lo + per, total);
@@ -253,23 +224,17 @@ int ffp_sliced_predict(ffp_det* d, const uint8_t* frame, int H, int W, int chan_
   FFP_CHECK(d && out && out_n && cap > 0, FFP_ERR_ARG, "null argument");
   DetEngine& e = d->eng;
   upload_frame(e, frame, H, W);
-  const std::vector<int32_t> sl = slice_bboxes(H, W, slice_h, slice_w, oh, ow);
-  const int total = (int)sl.size() / 4 + ((sl.size() / 4 > 1 && perform_standard_pred) ? 1 : 0);
+  const int total = (int)sliced_items(H, W, slice_h, slice_w, oh, ow, perform_standard_pred).size() / 4;
   const int stride = e.det_stride();
   e.scratch_dets.ensure(sizeof(float) * (size_t)total * max_det * stride);
   e.scratch_counts.ensure(sizeof(int32_t) * total);
   int nl = 0, nt = 0;
   stage(e, e.scratch_frame.as<uint8_t>(), H, W, chan_order, slice_h, slice_w, oh, ow, perform_standard_pred, imgsz, conf, iou, max_det,
         round_boxes, 0, 1, e.scratch_dets.as<float>(), e.scratch_counts.as<int32_t>(), &nl, &nt);
-  e.scratch_out.ensure(sizeof(float) * (size_t)cap * stride);
-  e.scratch_outn.ensure(sizeof(int));
+  e.tail.reserve(cap, stride);
   e.merge_dev(e.scratch_dets.as<float>(), e.scratch_counts.as<int32_t>(), total, max_det, pp_type, pp_metric, pp_thr, class_agnostic,
-              e.scratch_out.as<float>(), nullptr, cap, e.scratch_outn.as<int32_t>());
-  int k = 0;
-  FFP_HIP(hipMemcpy(&k, e.scratch_outn.p, sizeof(int), hipMemcpyDeviceToHost));
-  *out_n = k;
-  FFP_CHECK(k <= cap, FFP_ERR_ARG, "sliced_predict: %d merged detections exceed the output capacity %d (nothing was dropped silently: call again with cap >= %d)", k, cap, k);
-  FFP_HIP(hipMemcpy(out, e.scratch_out.p, sizeof(float) * (size_t)k * stride, hipMemcpyDeviceToHost));
+              e.tail.merged.as<float>(), nullptr, cap, e.tail.merged_n.as<int32_t>());
+  e.tail.fetch(out, cap, stride, out_n, "sliced_predict", nullptr);      // merge_dev has drained the stream
   FFP_API_END
 }
 
@@ -2430,10 +2395,8 @@ int ffp_rtdetr_sliced_predict(ffp_rtdetr* r, const uint8_t* frame, int H, int W,
                               int class_agnostic, float* out, int cap, int32_t* out_n) {
   FFP_API_BEGIN
   FFP_CHECK(r && frame && out && out_n && cap > 0, FFP_ERR_ARG, "null argument");
-  FFP_CHECK(H > 0 && W > 0, FFP_ERR_ARG, "frame is empty");
-  std::vector<int32_t> items = slice_bboxes(H, W, slice_h, slice_w, oh, ow);
-  if (items.size() / 4 > 1 && perform_standard_pred) items.insert(items.end(), {0, 0, W, H});   // sahi/predict.py: the full-frame pass
-  r->eng.sliced_predict(frame, H, W, chan_order, items, imgsz, conf, max_batch, pp_type, pp_metric, pp_thr, class_agnostic, out, cap, out_n);
+  r->eng.sliced_predict(frame, H, W, chan_order, sliced_items(H, W, slice_h, slice_w, oh, ow, perform_standard_pred), imgsz, conf, max_batch, pp_type,
+                        pp_metric, pp_thr, class_agnostic, out, cap, out_n);
   FFP_API_END
 }
 

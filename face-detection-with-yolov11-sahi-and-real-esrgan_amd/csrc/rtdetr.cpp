@@ -469,14 +469,6 @@ void RtdetrEngine::forward_raw(const uint8_t* const* frames, const int32_t* hw, 
 
 // ---- tiles of one frame (sahi's get_sliced_prediction over an Ultralytics RT-DETR model) ---------------------------------------------
 
-std::vector<int> RtdetrEngine::chunk_sizes(int n, int max_batch) {
-  if (max_batch <= 0) max_batch = RT_TILES_DEFAULT_BATCH;
-  const int chunks = (n + max_batch - 1) / max_batch;
-  std::vector<int> v(chunks, chunks ? n / chunks : 0);
-  for (int i = 0; i < (chunks ? n % chunks : 0); ++i) ++v[i];      // 61 at 16: 16, 15, 15, 15
-  return v;
-}
-
 void RtdetrEngine::mem_bytes(size_t* plans, int* resident) const {
   size_t b = 0;
   for (const auto& kv : plans_) b += kv.second->bytes;
@@ -488,14 +480,6 @@ void RtdetrEngine::drop_plans() {
   FFP_HIP(hipSetDevice(device_));
   FFP_HIP(hipStreamSynchronize(st_));
   plans_.clear();
-}
-
-void RtdetrEngine::upload_frame(const uint8_t* frame, int H, int W) {
-  FFP_CHECK(frame && H > 0 && W > 0, FFP_ERR_ARG, "rtdetr: frame is null or empty");
-  FFP_HIP(hipSetDevice(device_));
-  const size_t nb = (size_t)H * W * 3;
-  frame_.ensure(nb);
-  FFP_HIP(hipMemcpyAsync(frame_.p, frame, nb, hipMemcpyHostToDevice, st_));
 }
 
 // everything on st_, nothing waited for: the caller drains the stream (h_lb_ and the caller's `tiles` are read by the copies until then)
@@ -523,7 +507,8 @@ void RtdetrEngine::enqueue_tiles(const uint8_t* d_frame, int H, int W, int chan_
   FFP_HIP(hipMemcpyAsync(tiles_xy_.p, tiles, sizeof(int4) * n_tiles, hipMemcpyHostToDevice, st_));
   const int flip = chan_order == FFP_CHAN_AS_BGR ? 1 : 0;
   int off = 0;
-  for (int m : chunk_sizes(n_tiles, max_batch)) {
+  if (max_batch <= 0) max_batch = RT_TILES_DEFAULT_BATCH;      // this engine's sentinel: no positive size asks for the default
+  for (int m : even_chunks(n_tiles, max_batch)) {
     RtdetrPlan* P = plan_for(m, imgsz);        // an eviction waits for the stream first
     FFP_HIP(hipMemcpyAsync(P->d_lb.p, tiles_lb_.as<LetterboxImg>() + off, sizeof(LetterboxImg) * m, hipMemcpyDeviceToDevice, st_));
     launch_letterbox(d_frame, H, W, flip, P->d_lb, P->input, st_);
@@ -546,7 +531,8 @@ void RtdetrEngine::infer_tiles(const uint8_t* frame, int H, int W, int chan_orde
                                int max_batch, float* out, int32_t* counts) {
   FFP_CHECK(out && counts, FFP_ERR_ARG, "rtdetr: null output");
   FFP_CHECK(n_tiles > 0 && n_tiles <= 65536, FFP_ERR_ARG, "rtdetr: no tile to run, or too many (n_tiles %d)", n_tiles);
-  upload_frame(frame, H, W);
+  FFP_HIP(hipSetDevice(device_));
+  upload_frame(frame_, frame, H, W, st_);
   const size_t nd = sizeof(float) * (size_t)n_tiles * RT_NQ * 6;
   tile_dets_.ensure(nd);
   tile_counts_.ensure(sizeof(int) * n_tiles);
@@ -562,33 +548,22 @@ void RtdetrEngine::sliced_predict(const uint8_t* frame, int H, int W, int chan_o
   FFP_CHECK(out && out_n && cap > 0, FFP_ERR_ARG, "rtdetr: sliced_predict needs an output of cap > 0 rows");
   const int n_tiles = (int)items.size() / 4;
   FFP_CHECK(n_tiles > 0 && n_tiles <= 65536, FFP_ERR_ARG, "rtdetr: no tile to run, or too many (n_tiles %d)", n_tiles);
-  upload_frame(frame, H, W);
+  FFP_HIP(hipSetDevice(device_));
+  upload_frame(frame_, frame, H, W, st_);
   tile_dets_.ensure(sizeof(float) * (size_t)n_tiles * RT_NQ * 6);
   tile_counts_.ensure(sizeof(int) * n_tiles);
   enqueue_tiles(frame_.as<uint8_t>(), H, W, chan_order, items.data(), n_tiles, imgsz, conf, FFP_RT_TILES_SAHI, max_batch, tile_dets_.as<float>(),
                 tile_counts_.as<int>());
   const int n_max = n_tiles * RT_NQ;
-  rows_.ensure(sizeof(float) * (size_t)n_max * 6);
-  rows_n_.ensure(sizeof(int));
-  rows_prefix_.ensure(sizeof(int) * (n_tiles + 1));
-  merged_.ensure(sizeof(float) * (size_t)cap * 6);
-  merged_n_.ensure(sizeof(int));
-  launch_compact_rows(tile_dets_.as<float>(), tile_counts_.as<int>(), n_tiles, RT_NQ, 6, rows_.as<float>(), rows_n_.as<int>(), rows_prefix_.as<int>(), st_);
+  tail_.reserve(cap, 6);
+  tail_.compact(tile_dets_.as<float>(), tile_counts_.as<int>(), n_tiles, RT_NQ, 6, st_);
   int rows = 0;                              // the merge's grid follows the row count: one small read back between the two halves
-  FFP_HIP(hipMemcpyAsync(&rows, rows_n_.p, sizeof(int), hipMemcpyDeviceToHost, st_));
+  FFP_HIP(hipMemcpyAsync(&rows, tail_.rows_n.p, sizeof(int), hipMemcpyDeviceToHost, st_));
   FFP_HIP(hipStreamSynchronize(st_));
   FFP_CHECK(rows >= 0 && rows <= n_max, FFP_ERR_STATE, "rtdetr: %d rows from %d tiles", rows, n_tiles);
   // one slice: its rows as they are, in query order, like the other engines' fused calls; with more tiles sahi post-processes a list of two or more
-  if (n_tiles > 1 && rows > 1) run_merge(merge_work_, rows_.as<float>(), rows_n_.as<int>(), rows, 6, pp_type, pp_metric, pp_thr, class_agnostic, merged_.as<float>(),
-                          nullptr, merged_n_.as<int>(), cap, st_);
-  else run_merge_passthrough(rows_.as<float>(), rows_n_.as<int>(), 6, merged_.as<float>(), nullptr, merged_n_.as<int>(), cap, st_);   // sahi/predict.py: a list of one is kept
-  int k = 0;
-  FFP_HIP(hipMemcpyAsync(&k, merged_n_.p, sizeof(int), hipMemcpyDeviceToHost, st_));
-  FFP_HIP(hipStreamSynchronize(st_));
-  *out_n = k;
-  FFP_CHECK(k <= cap, FFP_ERR_ARG, "rtdetr: sliced_predict: %d merged detections exceed the output capacity %d (nothing was dropped silently: call again with cap >= %d)", k, cap, k);
-  FFP_HIP(hipMemcpyAsync(out, merged_.p, sizeof(float) * (size_t)k * 6, hipMemcpyDeviceToHost, st_));
-  FFP_HIP(hipStreamSynchronize(st_));
+  tail_.merge(MergeRule::TwoOrMore, rows, pp_type, pp_metric, pp_thr, class_agnostic, tail_.merged.as<float>(), nullptr, tail_.merged_n.as<int>(), cap, st_);
+  tail_.fetch(out, cap, 6, out_n, "rtdetr: sliced_predict", st_);      // the merge is still in flight: both copies on st_, each waited for
 }
 
 }  // namespace ffp

@@ -1,8 +1,8 @@
 // rtdetr.hpp — Ultralytics RT-DETR-l (rtdetr-l.yaml, eval path) as a plan of HIP launches: every conv and every Linear over tokens on the
 // shared conv kernels, everything else (LayerNorm, softmax, attention, top-k, deformable sampling) in rtdetr_ops.hip, fp32.
 #pragma once
-#include "det_post.hpp"
 #include "engine.hpp"
+#include "sliced.hpp"
 
 namespace ffp {
 
@@ -71,7 +71,6 @@ class RtdetrEngine {
   // tile order then query order into the SAHI merge. out [cap][6]; *out_n is the merged count even when it exceeds cap (FFP_ERR_ARG then).
   void sliced_predict(const uint8_t* frame, int H, int W, int chan_order, const std::vector<int32_t>& items, int imgsz, float conf, int max_batch,
                       int pp_type, int pp_metric, double pp_thr, int class_agnostic, float* out, int cap, int32_t* out_n);
-  static std::vector<int> chunk_sizes(int n, int max_batch);
   void mem_bytes(size_t* plans, int* resident) const;
   void drop_plans();
   // profile: the next calls run their plan eagerly with a pair of events around every launch (no hipGraph); profile_ms holds the last call's
@@ -82,7 +81,6 @@ class RtdetrEngine {
   int last_graph_state = 0;
 
  private:
-  void upload_frame(const uint8_t* frame, int H, int W);
   void enqueue_tiles(const uint8_t* d_frame, int H, int W, int chan_order, const int32_t* tiles, int n_tiles, int imgsz, float conf, int mode,
                      int max_batch, float* d_out, int32_t* d_counts);
   RtdetrPlan* prepare(const uint8_t* const* frames, const int32_t* hw, int n, int imgsz);
@@ -104,8 +102,8 @@ class RtdetrEngine {
   DevBuf frame_;
   // the tile path: per-call tables (host copies live until the stream has drained) and the fused call's scratch
   std::vector<LetterboxImg> h_lb_;
-  DevBuf tiles_lb_, tiles_xy_, tile_dets_, tile_counts_, rows_, rows_n_, rows_prefix_, merged_, merged_n_;
-  MergeWork merge_work_;
+  DevBuf tiles_lb_, tiles_xy_, tile_dets_, tile_counts_;
+  SlicedTail tail_;
 };
 
 }  // namespace ffp

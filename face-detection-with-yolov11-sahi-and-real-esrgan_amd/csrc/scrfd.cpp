@@ -154,7 +154,7 @@ ScrfdPlan* ScrfdEngine::prepare(const uint8_t* frame, int H, int W, int chan_ord
   FFP_HIP(hipSetDevice(device_));
   ScrfdPlan* P = plan_for(n_tiles, det_w, det_h);
   tile_geometry(*P, H, W, tiles, n_tiles);
-  upload_frame(frame, H, W);
+  upload_frame(frame_, frame, H, W, st_);
   run_chunk(P, frame_.as<uint8_t>(), W, chan_order, 0, n_tiles);
   FFP_HIP(hipStreamSynchronize(st_));
   return P;
@@ -175,12 +175,6 @@ void ScrfdEngine::tile_geometry(const ScrfdPlan& first, int H, int W, const int3
               L.new_w, L.new_h, nw_, nh_);
     L.top = 0; L.left = 0; L.net_h = nh_; L.net_w = nw_;
   }
-}
-
-void ScrfdEngine::upload_frame(const uint8_t* frame, int H, int W) {
-  const size_t fb = (size_t)H * W * 3;
-  frame_.ensure(fb);
-  FFP_HIP(hipMemcpyAsync(frame_.p, frame, fb, hipMemcpyHostToDevice, st_));
 }
 
 void ScrfdEngine::run_chunk(ScrfdPlan* P, const uint8_t* d_frame, int W, int chan_order, int off, int m) {
@@ -258,15 +252,6 @@ void ScrfdEngine::forward_raw(const uint8_t* frame, int H, int W, int chan_order
 
 // ---- tiles of one frame in chunks, and sahi's get_sliced_prediction over InsightFaceDetectionModel in one call ------------------------
 
-std::vector<int> ScrfdEngine::chunk_sizes(int n, int max_batch) {
-  if (max_batch < 0) max_batch = SCRFD_TILES_DEFAULT_BATCH;
-  if (max_batch == 0 || max_batch > n) max_batch = n;
-  const int chunks = max_batch ? (n + max_batch - 1) / max_batch : 0;
-  std::vector<int> v(chunks, chunks ? n / chunks : 0);
-  for (int i = 0; i < (chunks ? n % chunks : 0); ++i) ++v[i];      // 13 at 5: 5, 4, 4
-  return v;
-}
-
 void ScrfdEngine::mem_bytes(size_t* plans, int* resident) const {
   *plans = plan_bytes();
   *resident = (int)plans_.size();
@@ -288,7 +273,9 @@ void ScrfdEngine::enqueue_tiles(const uint8_t* d_frame, int H, int W, int chan_o
   FFP_CHECK(mode == FFP_SCRFD_TILES_LOCAL || mode == FFP_SCRFD_TILES_SAHI, FFP_ERR_ARG, "scrfd: tile mode %d (FFP_SCRFD_TILES_LOCAL or FFP_SCRFD_TILES_SAHI)",
             mode);
   FFP_HIP(hipSetDevice(device_));
-  const std::vector<int> chunks = chunk_sizes(n_tiles, max_batch);
+  // this engine's sentinels: below 0 asks for the default, 0 (or more than there are) for one batch, as infer_tiles runs them
+  max_batch = max_batch < 0 ? SCRFD_TILES_DEFAULT_BATCH : max_batch == 0 || max_batch > n_tiles ? n_tiles : max_batch;
+  const std::vector<int> chunks = even_chunks(n_tiles, max_batch);      // 13 at 5: 5, 4, 4
   tile_geometry(*plan_for(chunks[0], det_w, det_h), H, W, tiles, n_tiles);
   int off = 0;
   for (int m : chunks) {
@@ -334,7 +321,7 @@ void ScrfdEngine::infer_tiles_ex(const uint8_t* frame, int H, int W, int chan_or
   FFP_CHECK(cap >= 1 && out && out_counts, FFP_ERR_ARG, "scrfd: cap must be >= 1 and outputs non-null");
   FFP_CHECK((long long)n_tiles * cap < (1ll << 31) / FFP_DET_STRIDE(5), FFP_ERR_ARG, "scrfd: %d tiles of %d rows", n_tiles, cap);
   FFP_HIP(hipSetDevice(device_));
-  upload_frame(frame, H, W);
+  upload_frame(frame_, frame, H, W, st_);
   const size_t ob = sizeof(float) * (size_t)n_tiles * cap * FFP_DET_STRIDE(5);
   tile_dets_.ensure(ob);
   tile_counts_.ensure(sizeof(int) * n_tiles);
@@ -356,21 +343,17 @@ void ScrfdEngine::merge_tiles(int n_tiles, int tile_cap, bool full_last, int H, 
                               float* d_out, int cap, int32_t* d_out_n) {
   constexpr int S = FFP_DET_STRIDE(5);
   const int n_max = n_tiles * tile_cap;
-  rows_.ensure(sizeof(float) * (size_t)n_max * S);
-  rows_n_.ensure(sizeof(int));
-  rows_prefix_.ensure(sizeof(int) * (n_tiles + 1));
-  launch_compact_rows(tile_dets_.as<float>(), tile_counts_.as<int>(), n_tiles, tile_cap, S, rows_.as<float>(), rows_n_.as<int>(), rows_prefix_.as<int>(), st_);
+  tail_.compact(tile_dets_.as<float>(), tile_counts_.as<int>(), n_tiles, tile_cap, S, st_);
   int rows = 0, full_first = 0;              // the merge's grid follows the row count: one small read back between the two halves
-  FFP_HIP(hipMemcpyAsync(&rows, rows_n_.p, sizeof(int), hipMemcpyDeviceToHost, st_));
-  FFP_HIP(hipMemcpyAsync(&full_first, rows_prefix_.as<int>() + (n_tiles - 1), sizeof(int), hipMemcpyDeviceToHost, st_));
+  FFP_HIP(hipMemcpyAsync(&rows, tail_.rows_n.p, sizeof(int), hipMemcpyDeviceToHost, st_));
+  FFP_HIP(hipMemcpyAsync(&full_first, tail_.prefix.as<int>() + (n_tiles - 1), sizeof(int), hipMemcpyDeviceToHost, st_));
   FFP_HIP(hipStreamSynchronize(st_));
   check_tiles(n_tiles, tile_cap, FFP_SCRFD_TILES_SAHI);
   FFP_CHECK(rows >= 0 && rows <= n_max, FFP_ERR_STATE, "scrfd: %d rows from %d tiles", rows, n_tiles);
   // one slice: its rows as they are, in score order; with more tiles sahi post-processes a list of two or more (sahi/predict.py)
   // the full-frame prediction is the one sahi does not shift, so it keeps its full_shape: a union it keeps is clipped to the frame
-  if (n_tiles > 1 && rows > 1) run_merge(merge_work_, rows_.as<float>(), rows_n_.as<int>(), rows, S, pp_type, pp_metric, pp_thr, class_agnostic, d_out, nullptr,
-                                         d_out_n, cap, st_, full_last ? full_first : 0x7fffffff, W, H);
-  else run_merge_passthrough(rows_.as<float>(), rows_n_.as<int>(), S, d_out, nullptr, d_out_n, cap, st_);
+  tail_.merge(MergeRule::TwoOrMore, rows, pp_type, pp_metric, pp_thr, class_agnostic, d_out, nullptr, d_out_n, cap, st_,
+              full_last ? full_first : 0x7fffffff, W, H);
 }
 
 void ScrfdEngine::sliced_predict_dev(const uint8_t* d_frame, int H, int W, int chan_order, const std::vector<int32_t>& items, int det_w, int det_h,
@@ -396,16 +379,11 @@ void ScrfdEngine::sliced_predict(const uint8_t* frame, int H, int W, int chan_or
   FFP_CHECK(frame && H > 0 && W > 0 && out && out_n && cap > 0, FFP_ERR_ARG, "scrfd: sliced_predict needs a frame and an output of cap > 0 rows");
   constexpr int S = FFP_DET_STRIDE(5);
   FFP_HIP(hipSetDevice(device_));
-  upload_frame(frame, H, W);
-  merged_.ensure(sizeof(float) * (size_t)cap * S);
-  merged_n_.ensure(sizeof(int));
+  upload_frame(frame_, frame, H, W, st_);
+  tail_.reserve(cap, S);
   sliced_predict_dev(frame_.as<uint8_t>(), H, W, chan_order, items, det_w, det_h, det_thresh, nms_thresh, conf, max_batch, tile_cap, pp_type, pp_metric,
-                     pp_thr, class_agnostic, merged_.as<float>(), cap, merged_n_.as<int>());
-  int k = 0;
-  FFP_HIP(hipMemcpy(&k, merged_n_.p, sizeof(int), hipMemcpyDeviceToHost));
-  *out_n = k;
-  FFP_CHECK(k <= cap, FFP_ERR_ARG, "scrfd: sliced_predict: %d merged detections exceed the output capacity %d (nothing was dropped silently: call again with cap >= %d)", k, cap, k);
-  FFP_HIP(hipMemcpy(out, merged_.p, sizeof(float) * (size_t)k * S, hipMemcpyDeviceToHost));
+                     pp_thr, class_agnostic, tail_.merged.as<float>(), cap, tail_.merged_n.as<int>());
+  tail_.fetch(out, cap, S, out_n, "scrfd: sliced_predict", nullptr);      // sliced_predict_dev has drained the stream
 }
 
 }  // namespace ffp

@@ -1,8 +1,8 @@
 // scrfd.hpp — the face detector of InsightFace's model packs (SCRFD, det_*.onnx behind insightface.app.FaceAnalysis) as a plan
 // of HIP launches: the ONNX graph is lowered on the host (onnx_graph.hpp) onto the shared conv kernels plus scrfd_ops.hip.
 #pragma once
-#include "det_post.hpp"
 #include "engine.hpp"
+#include "sliced.hpp"
 #include "onnx_graph.hpp"
 
 namespace ffp {
@@ -85,7 +85,6 @@ class ScrfdEngine {
   void sliced_predict_dev(const uint8_t* d_frame, int H, int W, int chan_order, const std::vector<int32_t>& items, int det_w, int det_h,
                           float det_thresh, float nms_thresh, float conf, int max_batch, int tile_cap, int pp_type, int pp_metric, double pp_thr,
                           int class_agnostic, float* d_out, int cap, int32_t* d_out_n);
-  static std::vector<int> chunk_sizes(int n, int max_batch);
   void mem_bytes(size_t* plans, int* resident) const;
   void drop_plans();
   double last_conv_flops = 0;
@@ -94,7 +93,6 @@ class ScrfdEngine {
 
  private:
   ScrfdPlan* prepare(const uint8_t* frame, int H, int W, int chan_order, const int32_t* tiles, int n_tiles, int det_w, int det_h);
-  void upload_frame(const uint8_t* frame, int H, int W);
   // the geometry of every tile into h_lb_ / h_scale_ at the net size `first` was lowered for
   void tile_geometry(const ScrfdPlan& first, int H, int W, const int32_t* tiles, int n_tiles);
   // tiles [off, off + m) through P, nothing waited for: the tables, the pre-processing and the plan
@@ -122,8 +120,8 @@ class ScrfdEngine {
   std::vector<float> h_scale_;
   std::vector<int32_t> h_counts_;
   unsigned h_err_ = SCRFD_NO_BAD_ROW;
-  DevBuf tiles_xy_, err_, tile_dets_, tile_counts_, rows_, rows_n_, rows_prefix_, merged_, merged_n_;
-  MergeWork merge_work_;
+  DevBuf tiles_xy_, err_, tile_dets_, tile_counts_;
+  SlicedTail tail_;
 };
 
 }  // namespace ffp

@@ -693,15 +693,10 @@ void DetEngine::merge_dev(const float* d_dets, const int32_t* d_counts, int n_sl
                           int class_agnostic, float* d_out, int32_t* d_out_src, int cap, int32_t* d_out_n) {
   FFP_HIP(hipSetDevice(device_));
   const int stride = det_stride();
-  const int n_max = n_slices * max_det;
-  scratch_rows.ensure(sizeof(float) * (size_t)n_max * stride);
-  scratch_n.ensure(sizeof(int));
-  scratch_prefix.ensure(sizeof(int) * (n_slices + 1));
   FFP_HIP(hipEventRecord(ev_[4], st_));
-  launch_compact_rows(d_dets, d_counts, n_slices, max_det, stride, scratch_rows.as<float>(), scratch_n.as<int>(),
-                      scratch_prefix.as<int>(), st_);
-  run_merge(merge_work, scratch_rows.as<float>(), scratch_n.as<int>(), n_max, stride, type, metric, thr, class_agnostic, d_out,
-            d_out_src, d_out_n, cap, st_);
+  tail.compact(d_dets, d_counts, n_slices, max_det, stride, st_);
+  // always the merge, over the grid bound: no read back of the row count between the two (the benchmarked ffp_merge_dev path)
+  tail.merge(MergeRule::Always, n_slices * max_det, type, metric, thr, class_agnostic, d_out, d_out_src, d_out_n, cap, st_);
   FFP_HIP(hipEventRecord(ev_[5], st_));
   FFP_HIP(hipStreamSynchronize(st_));
   FFP_HIP(hipEventElapsedTime(&last_ms[4], ev_[4], ev_[5]));

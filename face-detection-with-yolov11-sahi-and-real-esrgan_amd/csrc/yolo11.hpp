@@ -1,6 +1,7 @@
 // yolo11.hpp — the detector engine: YOLO11{n,s}-pose laid out as a plan of HIP launches per ragged batch shape.
 #pragma once
 #include "engine.hpp"
+#include "sliced.hpp"
 
 namespace ffp {
 
@@ -80,9 +81,8 @@ class DetEngine {
                  int class_agnostic, float* d_out, int32_t* d_out_src, int cap, int32_t* d_out_n);
 
   // scratch the API layer may use (grown on demand)
-  DevBuf scratch_frame, scratch_dets, scratch_counts, scratch_rows, scratch_n, scratch_prefix, scratch_out, scratch_outn,
-      scratch_src;
-  MergeWork merge_work;
+  DevBuf scratch_frame, scratch_dets, scratch_counts, scratch_src;
+  SlicedTail tail;
   ConvProfile prof;
   float last_ms[5] = {0, 0, 0, 0, 0};
   double last_conv_flops = 0;

@@ -68,6 +68,12 @@ int ffp_device_count(int* out_n);
 int ffp_slice_bboxes(int image_h, int image_w, int slice_h, int slice_w, float overlap_h_ratio, float overlap_w_ratio,
                      int32_t* out_xyxy, int cap, int32_t* out_n);
 
+/* How the tile entry points (ffp_rtdetr_infer_tiles, ffp_scrfd_infer_tiles_ex, the sliced predictions) split n items into network batches
+ * of at most max_batch >= 1 (a positive number: each engine resolves its own "default" / "one batch" values first): ceil(n / max_batch)
+ * chunks whose sizes differ by at most one, the larger ones first (61 at 16: 16, 15, 15, 15). Writes up to cap sizes; *out_n = number of
+ * chunks (may exceed cap, in which case only cap sizes were written). n < 0 or max_batch < 1 is FFP_ERR_ARG. */
+int ffp_tile_chunks(int n, int max_batch, int32_t* out, int cap, int32_t* out_n);
+
 /* Ultralytics LetterBox(new_shape=imgsz, auto=True, stride=32) geometry for one (h,w) source:
  * out[6] = {new_w, new_h, top, bottom, left, right}.  (inside YOLO.predict, utils/yolo_wrapper.py:74-80) */
 int ffp_letterbox_geometry(int h, int w, int imgsz, int32_t* out6);

@@ -75,6 +75,26 @@ def test_letterbox_geometry_matches_oracle(lib):
         assert _lib.letterbox_geometry(h, w, s) == ultra_post.letterbox_geometry(h, w, s), (h, w, s)
 
 
+def test_tile_chunks_are_even_and_larger_first(lib):
+    """ffp_tile_chunks, the one statement of how the tile entry points split n items at a positive max_batch: the shapes the engine
+    comments and the GPU tests name, then the rule itself (ceil(n / m) chunks, sizes within one of each other, not increasing)."""
+    for (n, m), want in {(61, 16): [16, 15, 15, 15], (13, 5): [5, 4, 4], (7, 3): [3, 2, 2], (61, 8): [8, 8, 8, 8, 8, 7, 7, 7], (5, 8): [5],
+                         (0, 4): []}.items():
+        assert _lib.tile_chunks(n, m) == want, (n, m)
+    for n in range(1, 71):
+        for m in range(1, 21):
+            c = _lib.tile_chunks(n, m)
+            assert len(c) == -(-n // m) and sum(c) == n and max(c) <= m and max(c) - min(c) <= 1 and c == sorted(c, reverse=True), (n, m, c)
+    k = C.c_int32(-1)
+    first = np.zeros(2, np.int32)                                       # fewer than there are: cap sizes written, the full count returned
+    assert lib.ffp_tile_chunks(61, 16, first.ctypes.data_as(C.POINTER(C.c_int32)), 2, C.byref(k)) == 0
+    assert k.value == 4 and first.tolist() == [16, 15]
+    for n, m in ((5, 0), (5, -1), (-1, 4)):
+        with pytest.raises(_lib.FfpError) as e:
+            _lib.tile_chunks(n, m)
+        assert e.value.code == 1, (n, m)
+
+
 def test_compute_calls_fail_loudly_without_gpu(lib):
     if _lib.device_count() > 0:
         pytest.skip("a GPU is visible")

@@ -33,14 +33,9 @@ H, W, SLICE, OVERLAP, IMGSZ, CONF = 2160, 3840, 512, 0.2, 640, 0.25
 LIMIT = 8 * 1000 ** 3
 
 
-def chunk_sizes(n, max_batch):
-    chunks = -(-n // max_batch)
-    return [n // chunks + (1 if i < n % chunks else 0) for i in range(chunks)]
-
-
 def by_crops(det, crops, max_batch):
     out, o = [], 0
-    for m in chunk_sizes(len(crops), max_batch):
+    for m in _lib.tile_chunks(len(crops), max_batch):
         out += det.predict(crops[o:o + m], IMGSZ, CONF)
         o += m
     return out
@@ -82,7 +77,7 @@ def main():
                 t = time.perf_counter()
                 by_crops(det, crops, mb)
                 tb.append((time.perf_counter() - t) * 1e3)
-            run = {"precision": prec_name, "max_batch": mb, "chunks": chunk_sizes(len(tiles), mb), "plan_bytes": mem["plans"],
+            run = {"precision": prec_name, "max_batch": mb, "chunks": _lib.tile_chunks(len(tiles), mb), "plan_bytes": mem["plans"],
                    "plans_resident": mem["plans_resident"], "graph_state": det.info()["graph_state"], "detections": int(sum(len(r) for r in ra)),
                    "tiles_equal_host_crops": bool(same), "infer_tiles": summary(ta), "host_crops_predict": summary(tb)}
             res["runs"].append(run)

@@ -52,12 +52,6 @@ def step(name, seconds):
         faulthandler.cancel_dump_traceback_later()
 
 
-def chunk_sizes(n, max_batch):
-    max_batch = n if max_batch <= 0 or max_batch > n else max_batch
-    chunks = -(-n // max_batch)
-    return [n // chunks + (1 if i < n % chunks else 0) for i in range(chunks)]
-
-
 def summary(samples):
     return {"median_ms": round(statistics.median(samples), 3), "min_ms": round(min(samples), 3), "max_ms": round(max(samples), 3),
             "samples_ms": [round(s, 3) for s in samples]}
@@ -148,7 +142,7 @@ def main():
                         t = time.perf_counter()
                         python_path()
                         tb.append((time.perf_counter() - t) * 1e3)
-            run = {"precision": prec_name, "max_batch": mb, "chunks": chunk_sizes(n_items, mb), "plan_bytes": mem["plans"],
+            run = {"precision": prec_name, "max_batch": mb, "chunks": _lib.tile_chunks(n_items, mb or n_items), "plan_bytes": mem["plans"],
                    "plans_resident": mem["plans_resident"], "detections": int(len(ra)), "sliced_predict": summary(ta)}
             if tb:
                 same = len(py) == len(ra) and all([float(v) for v in p.bbox.to_xyxy()] == [float(v) for v in r[:4]] for p, r in zip(py, ra))
