@@ -138,50 +138,39 @@ def build_asan(verbose: bool = True) -> str:
     return ASAN_OUT
 
 
-ARENA_OUT = os.path.join(CSRC, "build", "arena_host_check")
+def _build_host_check(out: str, driver: str, headers: list, verbose: bool) -> str:
+    """One stand-alone driver (own main, no HIP) built with the host compiler under AddressSanitizer + UBSan into csrc/build/<out>."""
+    clang = os.path.join(os.path.dirname(os.path.realpath(_hipcc())), "..", "lib", "llvm", "bin", "clang++")
+    if not os.path.exists(clang):
+        clang = "/opt/rocm/lib/llvm/bin/clang++"
+    out = os.path.join(CSRC, "build", out)
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    srcs = [os.path.join(CSRC, f) for f in [driver, *headers]]
+    if os.path.exists(out) and os.path.getmtime(out) > max(os.path.getmtime(s) for s in srcs):
+        return out
+    cmd = [clang, "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
+           srcs[0], "-o", out]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(f"sanitizer build failed:\n{r.stdout}\n{r.stderr}")
+    if verbose:
+        print(f"built {out}")
+    return out
 
 
 def build_arena_check(verbose: bool = True) -> str:
-    """Host-only AddressSanitizer + UBSan build of the plans' lifetime pool (csrc/arena.hpp, no HIP in it) with its driver
-    (csrc/arena_host_check.cpp): seeded alloc / release / fork / join sequences against a shadow model."""
-    clang = os.path.join(os.path.dirname(os.path.realpath(_hipcc())), "..", "lib", "llvm", "bin", "clang++")
-    if not os.path.exists(clang):
-        clang = "/opt/rocm/lib/llvm/bin/clang++"
-    os.makedirs(os.path.dirname(ARENA_OUT), exist_ok=True)
-    srcs = [os.path.join(CSRC, "arena_host_check.cpp"), os.path.join(CSRC, "arena.hpp")]
-    if os.path.exists(ARENA_OUT) and os.path.getmtime(ARENA_OUT) > max(os.path.getmtime(s) for s in srcs):
-        return ARENA_OUT
-    cmd = [clang, "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
-           srcs[0], "-o", ARENA_OUT]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError(f"sanitizer build failed:\n{r.stdout}\n{r.stderr}")
-    if verbose:
-        print(f"built {ARENA_OUT}")
-    return ARENA_OUT
-
-
-DW_BOUND_OUT = os.path.join(CSRC, "build", "dw_bound_host_check")
+    """The plans' lifetime pool (csrc/arena.hpp, no HIP in it): seeded alloc / release / fork / join sequences against a shadow model."""
+    return _build_host_check("arena_host_check", "arena_host_check.cpp", ["arena.hpp"], verbose)
 
 
 def build_dw_bound_check(verbose: bool = True) -> str:
-    """Host-only AddressSanitizer + UBSan build of the depthwise-fused loader's exponent arithmetic (csrc/dw_bound.hpp, plain C++ shared with
-    the kernel) with its driver (csrc/dw_bound_host_check.cpp)."""
-    clang = os.path.join(os.path.dirname(os.path.realpath(_hipcc())), "..", "lib", "llvm", "bin", "clang++")
-    if not os.path.exists(clang):
-        clang = "/opt/rocm/lib/llvm/bin/clang++"
-    os.makedirs(os.path.dirname(DW_BOUND_OUT), exist_ok=True)
-    srcs = [os.path.join(CSRC, "dw_bound_host_check.cpp"), os.path.join(CSRC, "dw_bound.hpp")]
-    if os.path.exists(DW_BOUND_OUT) and os.path.getmtime(DW_BOUND_OUT) > max(os.path.getmtime(s) for s in srcs):
-        return DW_BOUND_OUT
-    cmd = [clang, "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
-           srcs[0], "-o", DW_BOUND_OUT]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError(f"sanitizer build failed:\n{r.stdout}\n{r.stderr}")
-    if verbose:
-        print(f"built {DW_BOUND_OUT}")
-    return DW_BOUND_OUT
+    """The depthwise-fused loader's exponent arithmetic (csrc/dw_bound.hpp, plain C++ shared with the kernel)."""
+    return _build_host_check("dw_bound_host_check", "dw_bound_host_check.cpp", ["dw_bound.hpp"], verbose)
+
+
+def build_plan_cache_check(verbose: bool = True) -> str:
+    """The engines' plan cache (csrc/plan_cache.hpp, no HIP in it): seeded get / find / touch / clear sequences against a shadow model."""
+    return _build_host_check("plan_cache_host_check", "plan_cache_host_check.cpp", ["plan_cache.hpp"], verbose)
 
 
 if __name__ == "__main__":
@@ -191,6 +180,8 @@ if __name__ == "__main__":
         build_arena_check()
     elif "--dw-bound-check" in sys.argv:
         build_dw_bound_check()
+    elif "--plan-cache-check" in sys.argv:
+        build_plan_cache_check()
     elif "--variant" in sys.argv:
         build_variant(sys.argv[sys.argv.index("--variant") + 1])
     else:

@@ -302,4 +302,10 @@ hipStream_t create_engine_stream(const char* env_name) {
   return st;
 }
 
+size_t det_plan_budget() {
+  // at least one byte: FFP_DET_PLAN_GIB=0 keeps only the plan in use, it does not lift the budget (PlanCache reads 0 as "none")
+  static const size_t budget = [] { const char* e = getenv("FFP_DET_PLAN_GIB"); const double g = e ? atof(e) : 64.0; return std::max<size_t>(1, (size_t)(g * (1ull << 30))); }();
+  return budget;
+}
+
 }  // namespace ffp

@@ -21,6 +21,9 @@ namespace ffp {
 // kernels (hipExtStreamCreateWithCUMask) — a spatial split of the card between the detector and the enhancer.
 hipStream_t create_engine_stream(const char* env_name);
 
+// Byte budget of the resident plans of one YOLO11 or SCRFD handle (PlanCache's max_bytes): env FFP_DET_PLAN_GIB, default 64, read once per process.
+size_t det_plan_budget();
+
 
 // ---- errors ---------------------------------------------------------------------------------------------
 struct Error : std::runtime_error {

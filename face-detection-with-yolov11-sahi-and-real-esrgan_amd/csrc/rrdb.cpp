@@ -40,30 +40,14 @@ SrEngine::SrEngine(const void* weights, size_t nbytes, int scale, int num_block,
 void SrEngine::set_fused_body(bool on) {
   on = on && dt_ == F16;
   if (on == fused_body_) return;
-  FFP_HIP(hipSetDevice(device_));
-  if (pending_) wait_done();
-  FFP_HIP(hipStreamSynchronize(st_));
   plans_.clear();
   fused_body_ = on;
-}
-
-void SrEngine::drop_plans() {
-  FFP_HIP(hipSetDevice(device_));
-  if (pending_) wait_done();
-  FFP_HIP(hipStreamSynchronize(st_));
-  plans_.clear();
-}
-
-size_t SrEngine::plan_bytes() const {
-  size_t b = 0;
-  for (const auto& kv : plans_) b += kv.second->bytes;
-  return b;
 }
 
 SrEngine::~SrEngine() {
   (void)hipSetDevice(device_);
   if (st_) (void)hipStreamSynchronize(st_);
-  plans_.clear();
+  plans_.clear_nothrow();
   convs_.clear();
   for (auto& e : ev_) (void)hipEventDestroy(e);
   if (st_) (void)hipStreamDestroy(st_);
@@ -165,24 +149,18 @@ SrPlan::~SrPlan() {
 SrPlan& SrEngine::plan_for(long long t16) {
   // smallest resident plan that holds the batch; else a new one at the next capacity bucket (least recently used one evicted)
   SrPlan* best = nullptr;
-  for (auto& kv : plans_)
-    if (kv.first >= t16 && (!best || kv.first < best->cap_t16)) best = kv.second.get();
-  if (!best) {
-    const int cap = capacity_bucket(t16);
-    if (plans_.size() >= 4) {
-      auto victim = plans_.begin();
-      for (auto it = plans_.begin(); it != plans_.end(); ++it)
-        if (it->second->last_use < victim->second->last_use) victim = it;
-      plans_.erase(victim);
-    }
+  plans_.for_each([&](SrPlan& p) { if (p.cap_t16 >= t16 && (!best || p.cap_t16 < best->cap_t16)) best = &p; });
+  if (best) {
+    plans_.touch(*best);
+    return *best;
+  }
+  const int cap = capacity_bucket(t16);
+  return plans_.get(cap, [&] {
     std::unique_ptr<SrPlan> p(new SrPlan());
     build_plan(*p, cap);
     ++plans_built;
-    best = p.get();
-    plans_.emplace(cap, std::move(p));
-  }
-  best->last_use = ++use_clock_;
-  return *best;
+    return p;
+  });
 }
 
 void SrEngine::wait_done() {

@@ -72,7 +72,7 @@ RtdetrEngine::RtdetrEngine(const void* weights, size_t nbytes, int device, int p
 RtdetrEngine::~RtdetrEngine() {
   (void)hipSetDevice(device_);
   if (st_) (void)hipStreamSynchronize(st_);
-  plans_.clear();
+  plans_.clear_nothrow();
   convs_.clear();
   dev_.clear();
   if (st_) (void)hipStreamDestroy(st_);
@@ -360,24 +360,13 @@ void RtdetrEngine::build_plan(RtdetrPlan& P) {
 }
 
 RtdetrPlan* RtdetrEngine::plan_for(int n, int imgsz) {
-  const std::vector<int> key = {n, imgsz};
-  auto it = plans_.find(key);
-  if (it == plans_.end()) {
-    while (plans_.size() >= 4) {               // least recently used first
-      auto victim = plans_.begin();
-      for (auto jt = plans_.begin(); jt != plans_.end(); ++jt)
-        if (jt->second->last_use < victim->second->last_use) victim = jt;
-      FFP_HIP(hipStreamSynchronize(st_));
-      plans_.erase(victim);
-    }
+  return &plans_.get({n, imgsz}, [&] {
     std::unique_ptr<RtdetrPlan> p(new RtdetrPlan());
     p->n = n;
     p->imgsz = imgsz;
     build_plan(*p);
-    it = plans_.emplace(key, std::move(p)).first;
-  }
-  it->second->last_use = ++use_clock_;
-  return it->second.get();
+    return p;
+  });
 }
 
 static void check_imgsz(int imgsz) {
@@ -468,19 +457,6 @@ void RtdetrEngine::forward_raw(const uint8_t* const* frames, const int32_t* hw, 
 }
 
 // ---- tiles of one frame (sahi's get_sliced_prediction over an Ultralytics RT-DETR model) ---------------------------------------------
-
-void RtdetrEngine::mem_bytes(size_t* plans, int* resident) const {
-  size_t b = 0;
-  for (const auto& kv : plans_) b += kv.second->bytes;
-  *plans = b;
-  *resident = (int)plans_.size();
-}
-
-void RtdetrEngine::drop_plans() {
-  FFP_HIP(hipSetDevice(device_));
-  FFP_HIP(hipStreamSynchronize(st_));
-  plans_.clear();
-}
 
 // everything on st_, nothing waited for: the caller drains the stream (h_lb_ and the caller's `tiles` are read by the copies until then)
 void RtdetrEngine::enqueue_tiles(const uint8_t* d_frame, int H, int W, int chan_order, const int32_t* tiles, int n_tiles, int imgsz, float conf,

@@ -2,6 +2,7 @@
 // shared conv kernels, everything else (LayerNorm, softmax, attention, top-k, deformable sampling) in rtdetr_ops.hip, fp32.
 #pragma once
 #include "engine.hpp"
+#include "plan_cache.hpp"
 #include "sliced.hpp"
 
 namespace ffp {
@@ -45,7 +46,6 @@ std::vector<float> rtdetr_pack_depthwise(const float* w, int C, int taps);
 struct RtdetrPlan : Plan {
   int n = 0, imgsz = 0, NT = 0;
   void add_named(const std::string& name, std::function<void(hipStream_t)> f) { add(std::move(f)); steps.back().name = name; }
-  unsigned long long last_use = 0;
   TView input, ref, scores;
   DevBuf d_lb, d_wh, d_anchors, d_valid, d_pos, d_keys, d_idx, d_anc, d_raw, d_det, d_counts;
 };
@@ -71,8 +71,8 @@ class RtdetrEngine {
   // tile order then query order into the SAHI merge. out [cap][6]; *out_n is the merged count even when it exceeds cap (FFP_ERR_ARG then).
   void sliced_predict(const uint8_t* frame, int H, int W, int chan_order, const std::vector<int32_t>& items, int imgsz, float conf, int max_batch,
                       int pp_type, int pp_metric, double pp_thr, int class_agnostic, float* out, int cap, int32_t* out_n);
-  void mem_bytes(size_t* plans, int* resident) const;
-  void drop_plans();
+  void mem_bytes(size_t* plans, int* resident) const { *plans = plans_.bytes(); *resident = (int)plans_.size(); }
+  void drop_plans() { plans_.clear(); }      // waits for the stream first
   // profile: the next calls run their plan eagerly with a pair of events around every launch (no hipGraph); profile_ms holds the last call's
   // {"<kernel> <layer>", ms} per launch in issue order
   bool profile = false;
@@ -94,8 +94,7 @@ class RtdetrEngine {
   WeightFile wf_;
   std::map<std::string, std::unique_ptr<PackedConv>> convs_;
   std::map<std::string, DevBuf> dev_;
-  std::map<std::vector<int>, std::unique_ptr<RtdetrPlan>> plans_;
-  unsigned long long use_clock_ = 0;
+  PlanCache<std::vector<int>, RtdetrPlan> plans_{4, 0, [this] { FFP_HIP(hipSetDevice(device_)); FFP_HIP(hipStreamSynchronize(st_)); }};
   int device_ = 0, nc_ = 0;
   bool split_ = false;
   hipStream_t st_ = nullptr;

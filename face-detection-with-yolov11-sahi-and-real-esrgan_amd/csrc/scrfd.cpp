@@ -36,14 +36,8 @@ ScrfdEngine::ScrfdEngine(const void* onnx_bytes, size_t nbytes, int n, int devic
 ScrfdEngine::~ScrfdEngine() {
   (void)hipSetDevice(device_);
   if (st_) (void)hipStreamSynchronize(st_);
-  plans_.clear();
+  plans_.clear_nothrow();
   if (st_) (void)hipStreamDestroy(st_);
-}
-
-size_t ScrfdEngine::plan_bytes() const {
-  size_t b = 0;
-  for (const auto& kv : plans_) b += kv.second->bytes;
-  return b;
 }
 
 void ScrfdEngine::build_plan(ScrfdPlan& P, int n, int det_w, int det_h) {
@@ -122,30 +116,11 @@ void ScrfdEngine::build_plan(ScrfdPlan& P, int n, int det_w, int det_h) {
 }
 
 ScrfdPlan* ScrfdEngine::plan_for(int n, int det_w, int det_h) {
-  const std::vector<int> key = {n, det_w, det_h};
-  auto it = plans_.find(key);
-  if (it == plans_.end()) {
-    // least recently used plans go first, beyond 8 plans or beyond the byte budget (as DetEngine::plan_for)
-    static const size_t budget = [] { const char* e = getenv("FFP_DET_PLAN_GIB"); const double g = e ? atof(e) : 64.0; return (size_t)(g * (1ull << 30)); }();
-    auto evict_lru = [&](const ScrfdPlan* keep) {
-      auto victim = plans_.end();
-      for (auto jt = plans_.begin(); jt != plans_.end(); ++jt)
-        if (jt->second.get() != keep && (victim == plans_.end() || jt->second->last_use < victim->second->last_use)) victim = jt;
-      if (victim == plans_.end()) return false;
-      FFP_HIP(hipStreamSynchronize(st_));
-      plans_.erase(victim);
-      return true;
-    };
-    while (plans_.size() >= 8 && evict_lru(nullptr)) {}
+  return &plans_.get({n, det_w, det_h}, [&] {
     std::unique_ptr<ScrfdPlan> p(new ScrfdPlan());
     build_plan(*p, n, det_w, det_h);
-    const ScrfdPlan* fresh = p.get();
-    plans_.emplace(key, std::move(p));
-    while (plan_bytes() > budget && evict_lru(fresh)) {}
-    it = plans_.find(key);
-  }
-  it->second->last_use = ++use_clock_;
-  return it->second.get();
+    return p;
+  });
 }
 
 ScrfdPlan* ScrfdEngine::prepare(const uint8_t* frame, int H, int W, int chan_order, const int32_t* tiles, int n_tiles, int det_w, int det_h) {
@@ -251,17 +226,6 @@ void ScrfdEngine::forward_raw(const uint8_t* frame, int H, int W, int chan_order
 }
 
 // ---- tiles of one frame in chunks, and sahi's get_sliced_prediction over InsightFaceDetectionModel in one call ------------------------
-
-void ScrfdEngine::mem_bytes(size_t* plans, int* resident) const {
-  *plans = plan_bytes();
-  *resident = (int)plans_.size();
-}
-
-void ScrfdEngine::drop_plans() {
-  FFP_HIP(hipSetDevice(device_));
-  FFP_HIP(hipStreamSynchronize(st_));
-  plans_.clear();
-}
 
 void ScrfdEngine::enqueue_tiles(const uint8_t* d_frame, int H, int W, int chan_order, const int32_t* tiles, int n_tiles, int det_w, int det_h,
                                 float det_thresh, float nms_thresh, float conf, int mode, int max_batch, float* d_out, int cap, int32_t* d_out_counts) {

@@ -2,6 +2,7 @@
 // of HIP launches: the ONNX graph is lowered on the host (onnx_graph.hpp) onto the shared conv kernels plus scrfd_ops.hip.
 #pragma once
 #include "engine.hpp"
+#include "plan_cache.hpp"
 #include "sliced.hpp"
 #include "onnx_graph.hpp"
 
@@ -46,7 +47,6 @@ void launch_scrfd_sahi_rows(float* dets, int* counts, const int4* tiles_xyxy, in
 void scrfd_geometry(int h, int w, int net_w, int net_h, int* new_w, int* new_h, float* det_scale);
 
 struct ScrfdPlan : Plan {
-  unsigned long long last_use = 0;
   onnx::Lowered low;
   std::vector<TView> views;                // by lowered buffer
   std::vector<std::unique_ptr<PackedConv>> convs;
@@ -85,11 +85,11 @@ class ScrfdEngine {
   void sliced_predict_dev(const uint8_t* d_frame, int H, int W, int chan_order, const std::vector<int32_t>& items, int det_w, int det_h,
                           float det_thresh, float nms_thresh, float conf, int max_batch, int tile_cap, int pp_type, int pp_metric, double pp_thr,
                           int class_agnostic, float* d_out, int cap, int32_t* d_out_n);
-  void mem_bytes(size_t* plans, int* resident) const;
-  void drop_plans();
+  void mem_bytes(size_t* plans, int* resident) const { *plans = plans_.bytes(); *resident = (int)plans_.size(); }
+  void drop_plans() { plans_.clear(); }      // waits for the stream first
   double last_conv_flops = 0;
   int last_graph_state = 0;
-  size_t plan_bytes() const;
+  size_t plan_bytes() const { return plans_.bytes(); }
 
  private:
   ScrfdPlan* prepare(const uint8_t* frame, int H, int W, int chan_order, const int32_t* tiles, int n_tiles, int det_w, int det_h);
@@ -109,8 +109,7 @@ class ScrfdEngine {
   void build_plan(ScrfdPlan& P, int n, int det_w, int det_h);
 
   onnx::Graph graph_;
-  std::map<std::vector<int>, std::unique_ptr<ScrfdPlan>> plans_;
-  unsigned long long use_clock_ = 0;
+  PlanCache<std::vector<int>, ScrfdPlan> plans_{8, det_plan_budget(), [this] { FFP_HIP(hipSetDevice(device_)); FFP_HIP(hipStreamSynchronize(st_)); }};
   int device_ = 0;
   bool split_ = false;
   hipStream_t st_ = nullptr;

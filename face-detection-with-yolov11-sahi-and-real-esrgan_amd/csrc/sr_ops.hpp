@@ -1,6 +1,7 @@
 // sr_ops.hpp — Real-ESRGAN pre/post kernels (sr_ops.hip) and the SR engine (rrdb.cpp).
 #pragma once
 #include "engine.hpp"
+#include "plan_cache.hpp"
 
 namespace ffp {
 
@@ -71,7 +72,6 @@ struct SrPlan : Plan {
   int cap_t16 = 0;
   void* stage = nullptr;   // pinned staging of the per-batch tile descriptors
   size_t stage_bytes = 0;
-  unsigned long long last_use = 0;
   ~SrPlan();
 };
 
@@ -97,8 +97,8 @@ class SrEngine {
   // results either way. Default: fused in fp16 unless FFP_TRUNK=0. Changing it drops the resident plans.
   void set_fused_body(bool on);
   bool fused_body() const { return fused_body_; }
-  void drop_plans();            // release every resident plan (waits for the batch in flight and the stream first)
-  size_t plan_bytes() const;    // device memory held by the resident plans (activations, tables), without the packed weights
+  void drop_plans() { plans_.clear(); }      // release every resident plan (waits for the batch in flight and the stream first)
+  size_t plan_bytes() const { return plans_.bytes(); }      // device memory held by the resident plans (activations, tables), without the packed weights
   size_t weight_bytes() const { return weight_bytes_; }
   int plans_resident() const { return (int)plans_.size(); }
 
@@ -115,10 +115,10 @@ class SrEngine {
   struct TileDesc { SrSrc src; SrDst dst; int h, w; };
   void build_plan(SrPlan& P, int cap_t16);
   SrPlan& plan_for(long long t16);
-  unsigned long long use_clock_ = 0;
   const PackedConv* conv(const std::string& name) const;
   std::map<std::string, PackedConv> convs_;
-  std::map<int, std::unique_ptr<SrPlan>> plans_;      // keyed by capacity
+  // keyed by capacity; at most 4 buckets
+  PlanCache<int, SrPlan> plans_{4, 0, [this] { FFP_HIP(hipSetDevice(device_)); if (pending_) wait_done(); FFP_HIP(hipStreamSynchronize(st_)); }};
   int scale_ = 4, num_block_ = 23, device_ = 0;
   DType dt_ = F16;
   hipStream_t st_ = nullptr;

@@ -83,7 +83,7 @@ DetEngine::DetEngine(const void* weights, size_t nbytes, int arch, int nc, int n
 DetEngine::~DetEngine() {
   (void)hipSetDevice(device_);
   if (st_) (void)hipStreamSynchronize(st_);
-  plans_.clear();
+  plans_.clear_nothrow();
   convs_.clear();
   for (auto& e : ev_) (void)hipEventDestroy(e);
   if (st_) (void)hipStreamDestroy(st_);
@@ -497,21 +497,8 @@ DetPlan* DetEngine::plan_for(const std::vector<TileGeom>& g) {
   std::vector<int> key;
   key.reserve(g.size() * 2);
   for (const TileGeom& t : g) { key.push_back(t.lb.net_h); key.push_back(t.lb.net_w); }
-  auto it = plans_.find(key);
-  if (it == plans_.end()) {
-    // bound the cache by count and by bytes: least recently used plans go first (a caller alternating between image_size 512 and 1024, or
-    // between group sizes, keeps what it uses; round 3 dropped everything at the ninth plan and never looked at bytes)
-    static const size_t budget = [] { const char* e = getenv("FFP_DET_PLAN_GIB"); const double g = e ? atof(e) : 64.0; return (size_t)(g * (1ull << 30)); }();
-    auto evict_lru = [&](const DetPlan* keep) {
-      auto victim = plans_.end();
-      for (auto jt = plans_.begin(); jt != plans_.end(); ++jt)
-        if (jt->second.get() != keep && (victim == plans_.end() || jt->second->last_use < victim->second->last_use)) victim = jt;
-      if (victim == plans_.end()) return false;
-      FFP_HIP(hipStreamSynchronize(st_));
-      plans_.erase(victim);
-      return true;
-    };
-    while (plans_.size() >= 8 && evict_lru(nullptr)) {}
+  // bounded by count and by bytes (a caller alternating between image_size 512 and 1024, or between group sizes, keeps what it uses)
+  return &plans_.get(key, [&] {
     std::unique_ptr<DetPlan> p(new DetPlan());
     p->lanes = lanes_;
     p->reuse = reuse_;
@@ -519,19 +506,8 @@ DetPlan* DetEngine::plan_for(const std::vector<TileGeom>& g) {
     std::vector<int> hs, ws;
     for (const TileGeom& t : g) { hs.push_back(t.lb.net_h); ws.push_back(t.lb.net_w); }
     build_plan(*p, hs, ws);
-    const DetPlan* fresh = p.get();
-    it = plans_.emplace(key, std::move(p)).first;
-    while (plan_bytes() > budget && evict_lru(fresh)) {}
-    it = plans_.find(key);
-  }
-  it->second->last_use = ++use_clock_;
-  return it->second.get();
-}
-
-void DetEngine::drop_plans() {
-  FFP_HIP(hipSetDevice(device_));
-  FFP_HIP(hipStreamSynchronize(st_));
-  plans_.clear();
+    return p;
+  });
 }
 
 int DetEngine::reuse_env() {
@@ -542,17 +518,11 @@ int DetEngine::reuse_env() {
 
 void DetEngine::mem_detail(size_t* activation, size_t* no_reuse, size_t* peak_live) const {
   *activation = *no_reuse = *peak_live = 0;
-  for (const auto& kv : plans_) {
-    *activation += kv.second->activation_bytes();
-    *no_reuse += kv.second->no_reuse_bytes();
-    *peak_live += kv.second->peak_live_bytes();
-  }
-}
-
-size_t DetEngine::plan_bytes() const {
-  size_t b = 0;
-  for (const auto& kv : plans_) b += kv.second->bytes;
-  return b;
+  plans_.for_each([&](const DetPlan& p) {
+    *activation += p.activation_bytes();
+    *no_reuse += p.no_reuse_bytes();
+    *peak_live += p.peak_live_bytes();
+  });
 }
 
 int DetEngine::gate_env() {
@@ -562,8 +532,8 @@ int DetEngine::gate_env() {
 
 void DetEngine::set_gate(bool on) {
   if (on == gate_) return;
-  gate_ = on;
   drop_plans();
+  gate_ = on;
 }
 
 // the gate's verdict of the run just issued, on its way to the host: valid once the caller has waited for the stream

@@ -1,12 +1,12 @@
 // yolo11.hpp — the detector engine: YOLO11{n,s}-pose laid out as a plan of HIP launches per ragged batch shape.
 #pragma once
 #include "engine.hpp"
+#include "plan_cache.hpp"
 #include "sliced.hpp"
 
 namespace ffp {
 
 struct DetPlan : Plan {
-  unsigned long long last_use = 0;
   Level* L[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // strides 1,2,4,8,16,32
   TView input;
   TView head[3];
@@ -39,11 +39,11 @@ class DetEngine {
 
   int det_stride() const { return 6 + 3 * nkpt_; }
   // Plan::lanes of every plan built from now on (cached plans are dropped): parallel graph branches for the head towers and C3k
-  void set_lanes(int mode) { if (mode != lanes_) { lanes_ = mode; plans_.clear(); } }
+  void set_lanes(int mode) { if (mode != lanes_) { plans_.clear(); lanes_ = mode; } }
   // Plan::reuse of every plan built from now on (cached plans are dropped): 0 a device block per activation tensor, 1 (default; env
   // FFP_DET_ARENA sets another default for A/B runs) tensors whose lifetimes do not overlap share bytes, 2 as 1 with released ranges
   // overwritten by 0xFF bytes. Results are bit-identical in all three.
-  void set_buffer_reuse(int mode) { reuse_ = mode; plans_.clear(); }
+  void set_buffer_reuse(int mode) { plans_.clear(); reuse_ = mode; }
   int buffer_reuse() const { return reuse_; }
   // skip the box and keypoint towers of items without a class score above conf (on by default; env FFP_DET_GATE=0 sets the default to off).
   // Results are bit-identical either way. Cached plans are dropped.
@@ -55,16 +55,16 @@ class DetEngine {
   void mem_detail(size_t* activation, size_t* no_reuse, size_t* peak_live) const;
   void fill_counts(int* fill_steps, int* ranges_freed) const {     // summed over the resident plans (Plan::fill_steps, ranges_freed)
     *fill_steps = *ranges_freed = 0;
-    for (const auto& kv : plans_) { *fill_steps += kv.second->fill_steps; *ranges_freed += kv.second->ranges_freed; }
+    plans_.for_each([&](const DetPlan& p) { *fill_steps += p.fill_steps; *ranges_freed += p.ranges_freed; });
   }
   int device() const { return device_; }
   hipStream_t stream() const { return st_; }
   int nc() const { return nc_; }
   int nkpt() const { return nkpt_; }
   // device memory: resident plans (activations + tables; one plan per batch shape, least recently used ones are dropped beyond 8 plans or
-  // beyond the byte budget — env FFP_DET_PLAN_GIB, default 64) and the packed weights
-  size_t plan_bytes() const;
-  void drop_plans();            // release every resident plan (the next call lays its plan out again); waits for the stream first
+  // beyond det_plan_budget(), plan_cache.hpp) and the packed weights
+  size_t plan_bytes() const { return plans_.bytes(); }
+  void drop_plans() { plans_.clear(); }      // release every resident plan (the next call lays its plan out again); waits for the stream first
   size_t weight_bytes() const { return weight_bytes_; }
   int plans_resident() const { return (int)plans_.size(); }
 
@@ -102,7 +102,7 @@ class DetEngine {
 
   std::map<std::string, PackedConv> convs_;
   std::map<std::string, DenseF32> dense_;      // model.23.cv3.<l>.2 as plain fp32 (nc <= 4): the closing conv of the fused class tower (conv_dwpw.hip)
-  std::map<std::vector<int>, std::unique_ptr<DetPlan>> plans_;
+  PlanCache<std::vector<int>, DetPlan> plans_{8, det_plan_budget(), [this] { FFP_HIP(hipSetDevice(device_)); FFP_HIP(hipStreamSynchronize(st_)); }};
   std::vector<TileGeom> geom_last_;
   int lanes_ = 0;
   static int reuse_env();       // FFP_DET_ARENA, or 1
@@ -112,7 +112,6 @@ class DetEngine {
   HostPinned h_active_;         // the gate's verdict of the last call
   bool last_gated_ = false;
   int last_items_ = 0;
-  unsigned long long use_clock_ = 0;
   size_t weight_bytes_ = 0;
   int device_ = 0, nc_ = 1, nkpt_ = 5;
   char scale_ = 's';

@@ -121,6 +121,35 @@ def test_memory_figures(gpu_lib, frame, scale):
     det.close()
 
 
+def test_ninth_plan_evicts_the_least_recently_used(gpu_lib, frame):
+    """A handle keeps at most 8 plans, least recently used first out (csrc/plan_cache.hpp). Batches of k = 1..9 copies of one tile are nine
+    plans of nine different sizes b_k, so the byte sum of the resident plans tells which ones they are."""
+    det = _detector(gpu_lib, "n", "f32")
+    run = lambda k: det.forward_raw(frame, [TILES[0]] * k, 64)
+    plans = lambda: det.mem_bytes()["plans"]
+    b = {}
+    for k in range(1, 10):
+        det.drop_plans()
+        raw = run(k)
+        b[k] = plans()
+        if k == 2:
+            first2 = raw
+    assert len(set(b.values())) == 9 and min(b.values()) > 0, b
+    det.drop_plans()
+    for k in range(1, 9):
+        run(k)
+    assert det.mem_bytes()["plans_resident"] == 8 and plans() == sum(b[k] for k in range(1, 9))
+    run(1)                                                                 # a hit: builds nothing, makes k = 1 the most recently used
+    assert det.mem_bytes()["plans_resident"] == 8 and plans() == sum(b[k] for k in range(1, 9))
+    run(9)                                                                 # k = 2 goes, not k = 1
+    assert det.mem_bytes()["plans_resident"] == 8 and plans() == sum(b.values()) - b[2], (plans(), b)
+    again2 = run(2)                                                        # laid out again; k = 3 goes
+    assert det.mem_bytes()["plans_resident"] == 8 and plans() == sum(b.values()) - b[3], (plans(), b)
+    for x, y in zip(again2, first2):
+        assert x.shape == y.shape and np.array_equal(x, y)
+    det.close()
+
+
 @pytest.mark.parametrize("lanes", [0, 1])
 def test_mode_2_appends_one_fill_per_freed_range(gpu_lib, frame, lanes):
     """Mode 2 is only a diagnostic if the fills are really in the step list: one per range that reached the free list (with lanes, at the

@@ -246,3 +246,24 @@ def test_device_variant_and_chunk_plans(gpu_lib, w1, frame, tl, conf, local):
     assert d.mem_bytes()["plans_resident"] == 2
     d.drop_plans()
     assert d.mem_bytes() == {"plans": 0, "plans_resident": 0}
+
+
+def test_fifth_plan_evicts_the_least_recently_used(gpu_lib, w1, frame, tl):
+    """At most 4 plans per handle, least recently used first out (csrc/plan_cache.hpp): batches of n = 1..5 images at imgsz 128 (the smallest
+    multiple of 32 with 300 encoder tokens: 256 + 64 + 16) are five plans; b_n is what the n-th adds to the resident bytes."""
+    d = gpu_lib.RTDETRDetector(w1, precision=gpu_lib.PREC_F32)
+    imgs = T.crops(frame, tl)
+    total, b = [0], {}
+    for n in range(1, 6):
+        d.predict(imgs[:n], 128, 0.5)
+        total.append(d.mem_bytes()["plans"])
+        if n <= 4:
+            assert d.mem_bytes()["plans_resident"] == n
+            b[n] = total[n] - total[n - 1]
+    assert d.mem_bytes()["plans_resident"] == 4                            # n = 1 went
+    assert 0 < b[1] < b[2] < b[3] < b[4], b
+    d.predict(imgs[:1], 128, 0.5)                                          # so this lays n = 1 out again, and n = 2 goes
+    mb = d.mem_bytes()
+    assert mb["plans_resident"] == 4 and mb["plans"] - total[5] == b[1] - b[2], (mb, total, b)
+    d.drop_plans()
+    assert d.mem_bytes() == {"plans": 0, "plans_resident": 0}

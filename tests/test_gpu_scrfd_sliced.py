@@ -330,3 +330,31 @@ def test_mem_bytes_and_drop_plans(gpu_lib, model, frames):
     d.drop_plans()
     assert d.mem_bytes() == {"plans": 0, "plans_resident": 0}
     assert np.array_equal(d.sliced_predict(frames["b"], SL, SL, OV, OV, True, DET, THR, NMS, THR, max_batch=3), first)
+
+
+def test_ninth_plan_evicts_the_least_recently_used(gpu_lib, model, frames):
+    """At most 8 plans per handle, least recently used first out (csrc/plan_cache.hpp): batches of n = 1..9 tiles are nine plans of nine
+    different sizes b_n, so the byte sum of the resident plans tells which ones they are."""
+    d = gpu_lib.FaceDetector(model[0], precision=gpu_lib.PREC_F32)
+    f = frames["a"]
+    items = _items(gpu_lib, f)
+    run = lambda n: d.infer_tiles(f, items[:n], DET, THR, NMS)
+    b = {}
+    for n in range(1, 10):
+        d.drop_plans()
+        rows = run(n)
+        b[n] = d.mem_bytes()["plans"]
+        if n == 2:
+            first2 = rows
+    assert len(set(b.values())) == 9 and min(b.values()) > 0, b
+    d.drop_plans()
+    for n in range(1, 9):
+        run(n)
+    assert d.mem_bytes() == {"plans": sum(b[n] for n in range(1, 9)), "plans_resident": 8}
+    run(1)                                                                 # a hit: n = 1 becomes the most recently used
+    assert d.mem_bytes() == {"plans": sum(b[n] for n in range(1, 9)), "plans_resident": 8}
+    run(9)                                                                 # n = 2 goes, not n = 1
+    assert d.mem_bytes() == {"plans": sum(b.values()) - b[2], "plans_resident": 8}
+    again2 = run(2)                                                        # laid out again; n = 3 goes
+    assert d.mem_bytes() == {"plans": sum(b.values()) - b[3], "plans_resident": 8}
+    _same(again2, first2)

@@ -157,3 +157,22 @@ def test_varying_crop_multisets_reuse_one_plan(ctx):
             plans_after_warm = st["plans_built"]
     assert plans_after_warm == 1
     assert graphs >= 17                                                # eager only while the plan is being tuned / captured
+
+
+def test_fifth_capacity_bucket_evicts_the_least_recently_used(ctx):
+    """At most 4 capacity plans per handle, least recently used first out (csrc/plan_cache.hpp). Five images whose 16x16-tile counts fall
+    into the buckets 64, 96, 128, 192 and 256 build five plans; the first one goes, and the first image then runs in the 96 bucket."""
+    from ffp_amd import synth
+    enh = ctx["lib"].Enhancer(ctx["W4"], 4, 23, half=True)
+    big = synth.synthetic_frame(200, 248, seed=44, n_blobs=12)[..., ::-1]
+    sizes = [(40, 40), (113, 129), (129, 161), (161, 193), (193, 241)]     # 3*3 = 9, 8*9 = 72, 9*11 = 99, 11*13 = 143, 13*16 = 208 tiles
+    imgs = [np.ascontiguousarray(big[:h, :w]) for h, w in sizes]
+    first = None
+    for k, im in enumerate(imgs):
+        out = enh.enhance(im)
+        first = out if k == 0 else first
+        assert enh.plan_state()["plans_built"] == k + 1
+        assert enh.mem_bytes()["plans_resident"] == min(k + 1, 4)
+    again = enh.enhance(imgs[0])
+    assert enh.plan_state()["plans_built"] == 5 and enh.mem_bytes()["plans_resident"] == 4
+    assert np.array_equal(again, first)
