@@ -1,0 +1,164 @@
+// api_codec.cpp — the C-ABI of libffp.so, part three of four (see api.cpp): JPEG and PNG at the file boundaries. They take a device number, not a handle.
+#include "api_util.hpp"
+#include "jpeg.hpp"
+#include "png.hpp"
+
+using namespace ffp;
+
+extern "C" {
+
+// ---- JPEG at the file boundaries -----------------------------------------------------------------------------
+// Every entry runs on a stream of its own of the I/O kind (api_util.hpp, ScopedStream::Io).
+int ffp_jpeg_encode_dev(int device, const uint8_t* d_img, int h, int w, int64_t row_stride, int bgr, int quality, uint8_t* out, int64_t cap, int64_t* out_size) {
+  FFP_API_BEGIN
+  FFP_CHECK(out_size, FFP_ERR_ARG, "jpeg_encode: out_size is null");
+  ScopedStream cx(device, "jpeg_encode", ScopedStream::Io);
+  const long long n = jpeg_encode_device(d_img, h, w, row_stride, bgr, quality, out, cap, cx.st);
+  *out_size = n < 0 ? -n : n;
+  FFP_CHECK(n >= 0, FFP_ERR_ARG, "jpeg_encode: output buffer too small (%lld bytes needed)", -n);
+  FFP_API_END
+}
+
+int ffp_jpeg_encode_batch_dev(int device, const uint8_t* d_base, int n, const int64_t* offsets, const int32_t* hs, const int32_t* ws, const int64_t* strides,
+                              int bgr, int quality, uint8_t* out, int64_t cap, int64_t* out_offsets) {
+  FFP_API_BEGIN
+  FFP_CHECK(n >= 0 && out_offsets && (n == 0 || (d_base && offsets && hs && ws)), FFP_ERR_ARG, "jpeg_encode_batch: bad arguments");
+  ScopedStream cx(device, "jpeg_encode_batch", ScopedStream::Io);
+  std::vector<JpegSrc> src((size_t)n);
+  for (int i = 0; i < n; ++i) src[i] = JpegSrc{d_base + offsets[i], hs[i], ws[i], strides ? strides[i] : (long long)ws[i] * 3};
+  std::vector<std::vector<unsigned char>> files;
+  jpeg_encode_batch_device(src.data(), n, bgr, quality, files, cx.st);
+  int64_t pos = 0;
+  for (int i = 0; i < n; ++i) { out_offsets[i] = pos; pos += (int64_t)files[i].size(); }
+  out_offsets[n] = pos;
+  FFP_CHECK(out && cap >= pos, FFP_ERR_ARG, "jpeg_encode_batch: output buffer too small (%lld bytes needed)", (long long)pos);
+  for (int i = 0; i < n; ++i) std::memcpy(out + out_offsets[i], files[i].data(), files[i].size());
+  FFP_API_END
+}
+
+int ffp_jpeg_encode(int device, const uint8_t* img, int h, int w, int bgr, int quality, uint8_t* out, int64_t cap, int64_t* out_size) {
+  FFP_API_BEGIN
+  FFP_CHECK(img && h > 0 && w > 0 && out_size, FFP_ERR_ARG, "jpeg_encode: bad arguments");
+  ScopedStream cx(device, "jpeg_encode", ScopedStream::Io);
+  DevBuf d((size_t)h * w * 3);
+  FFP_HIP(hipMemcpy(d.p, img, (size_t)h * w * 3, hipMemcpyHostToDevice));
+  const long long n = jpeg_encode_device(d.as<unsigned char>(), h, w, (long long)w * 3, bgr, quality, out, cap, cx.st);
+  *out_size = n < 0 ? -n : n;
+  FFP_CHECK(n >= 0, FFP_ERR_ARG, "jpeg_encode: output buffer too small (%lld bytes needed)", -n);
+  FFP_API_END
+}
+
+int ffp_jpeg_info(const uint8_t* data, int64_t n, int32_t* out_h, int32_t* out_w, int32_t* out_ncomp) {
+  FFP_API_BEGIN
+  FFP_CHECK(data && out_h && out_w, FFP_ERR_ARG, "jpeg_info: null argument");
+  JpegScan s;
+  jpeg_entropy_decode(data, n, s, true);
+  *out_h = s.h; *out_w = s.w;
+  if (out_ncomp) *out_ncomp = s.ncomp;
+  FFP_API_END
+}
+
+int ffp_jpeg_decode_dev(int device, const uint8_t* data, int64_t n, int bgr, uint8_t* d_out, int64_t row_stride, int64_t cap) {
+  FFP_API_BEGIN
+  FFP_CHECK(data && d_out, FFP_ERR_ARG, "jpeg_decode: null argument");
+  ScopedStream cx(device, "jpeg_decode", ScopedStream::Io);
+  jpeg_decode_to_device(data, n, d_out, row_stride, cap, bgr, cx.st, nullptr, nullptr);
+  FFP_API_END
+}
+
+int ffp_jpeg_decode(int device, const uint8_t* data, int64_t n, int bgr, uint8_t* out, int64_t cap) {
+  FFP_API_BEGIN
+  FFP_CHECK(data && out, FFP_ERR_ARG, "jpeg_decode: null argument");
+  ScopedStream cx(device, "jpeg_decode", ScopedStream::Io);
+  JpegScan s;
+  jpeg_entropy_decode(data, n, s, true);
+  const size_t bytes = (size_t)s.h * s.w * 3;
+  FFP_CHECK(cap >= (int64_t)bytes, FFP_ERR_ARG, "jpeg_decode: output buffer too small for %dx%d", s.w, s.h);
+  DevBuf d(bytes);
+  jpeg_decode_to_device(data, n, d.as<unsigned char>(), 0, (long long)bytes, bgr, cx.st, nullptr, nullptr);
+  FFP_HIP(hipMemcpy(out, d.p, bytes, hipMemcpyDeviceToHost));
+  FFP_API_END
+}
+
+int ffp_jpeg_decode_stats(int64_t* device_decodes, int64_t* host_fallbacks, int64_t* extra_sync_rounds) {
+  FFP_API_BEGIN
+  long long a = 0, b = 0, c = 0;
+  jpeg_huff_stats(&a, &b, &c);
+  if (device_decodes) *device_decodes = a;
+  if (host_fallbacks) *host_fallbacks = b;
+  if (extra_sync_rounds) *extra_sync_rounds = c;
+  FFP_API_END
+}
+
+// ---- PNG at the file boundaries (png.hip) -----------------------------------------------------------------------------------------
+int64_t ffp_png_bound(int h, int w, int channels, int bit_depth) {
+  try {
+    return png_bound(h, w, channels, bit_depth);
+  } catch (const ffp::Error& e) {
+    ffp::set_last_error(e.what());
+    return -1;
+  }
+}
+
+int ffp_png_segment_bytes(void) { return kPngSegmentBytes; }
+
+// the three entries below: arguments checked, device chosen, one launch sequence on an I/O stream; out_offsets is filled before the
+// capacity is judged. on_host: `base` is host memory (one image, n == 1) and goes up first.
+static void png_encode_any(int device, const void* base, bool on_host, int n, const int64_t* offsets, const int32_t* hs, const int32_t* ws, const int64_t* strides,
+                           int channels, int bit_depth, int bgr, int level, uint8_t* out, int64_t cap, int64_t* out_offsets) {
+  FFP_CHECK(n >= 0 && out_offsets && (n == 0 || (base && offsets && hs && ws)), FFP_ERR_ARG, "png_encode: bad arguments");
+  FFP_CHECK((channels == 1 || channels == 3 || channels == 4) && (bit_depth == 8 || bit_depth == 16), FFP_ERR_ARG,
+            "png_encode: %d channels of %d bits (gray, RGB or RGBA at depth 8 or 16 are written)", channels, bit_depth);
+  ScopedStream cx(device, "png_encode", ScopedStream::Io);
+  DevBuf up;
+  if (on_host) {
+    up = upload(static_cast<const unsigned char*>(base), (size_t)hs[0] * (size_t)strides[0]);
+    base = up.p;
+  }
+  std::vector<PngSrc> src((size_t)n);
+  for (int i = 0; i < n; ++i)
+    src[i] = PngSrc{(const unsigned char*)base + offsets[i], hs[i], ws[i], strides ? strides[i] : (long long)ws[i] * channels * (bit_depth / 8)};
+  std::vector<long long> off((size_t)n + 1, 0);
+  const long long total = png_encode_batch_device(src.data(), n, channels, bit_depth, bgr, level, off.data(), out, cap, cx.st);
+  for (int i = 0; i <= n; ++i) out_offsets[i] = off[i];
+  FFP_CHECK(out && cap >= total, FFP_ERR_ARG, "png_encode: output buffer too small (%lld bytes needed)", total);
+}
+
+// one image: *out_size is the file's size also when the capacity was the trouble
+static void png_encode_one(int device, const void* img, bool on_host, int h, int w, int channels, int bit_depth, int64_t row_stride, int bgr, int level, uint8_t* out,
+                           int64_t cap, int64_t* out_size) {
+  const int64_t zero = 0;
+  const int32_t hh = h, ww = w;
+  int64_t oo[2] = {0, 0};
+  try {
+    png_encode_any(device, img, on_host, 1, &zero, &hh, &ww, &row_stride, channels, bit_depth, bgr, level, out, cap, oo);
+  } catch (...) {
+    *out_size = oo[1];
+    throw;
+  }
+  *out_size = oo[1];
+}
+
+int ffp_png_encode_batch_dev(int device, const void* d_base, int n, const int64_t* offsets, const int32_t* hs, const int32_t* ws, const int64_t* strides,
+                             int channels, int bit_depth, int bgr, int level, uint8_t* out, int64_t cap, int64_t* out_offsets) {
+  FFP_API_BEGIN
+  png_encode_any(device, d_base, false, n, offsets, hs, ws, strides, channels, bit_depth, bgr, level, out, cap, out_offsets);
+  FFP_API_END
+}
+
+int ffp_png_encode_dev(int device, const void* d_img, int h, int w, int channels, int bit_depth, int64_t row_stride, int bgr, int level, uint8_t* out, int64_t cap,
+                       int64_t* out_size) {
+  FFP_API_BEGIN
+  FFP_CHECK(out_size, FFP_ERR_ARG, "png_encode: out_size is null");
+  png_encode_one(device, d_img, false, h, w, channels, bit_depth, row_stride, bgr, level, out, cap, out_size);
+  FFP_API_END
+}
+
+int ffp_png_encode(int device, const void* img, int h, int w, int channels, int bit_depth, int bgr, int level, uint8_t* out, int64_t cap, int64_t* out_size) {
+  FFP_API_BEGIN
+  FFP_CHECK(img && h > 0 && w > 0 && out_size, FFP_ERR_ARG, "png_encode: bad arguments");
+  png_encode_one(device, img, true, h, w, channels, bit_depth, (int64_t)w * channels * (bit_depth / 8), bgr, level, out, cap, out_size);
+  FFP_API_END
+}
+
+}  // extern "C"

@@ -3,6 +3,7 @@
 
 #include <algorithm>
 
+#include "api_util.hpp"
 #include "conv_args.hpp"
 #include "engine.hpp"
 #include "trunk.hpp"
@@ -141,9 +142,7 @@ int conv_tune(const ConvOp& op, hipStream_t st) {
   const unsigned mask = conv_candidates(op, a);
   if (__builtin_popcount(mask) < 2) return -1;
   const int heur = r.shape;
-  hipEvent_t e0, e1;
-  FFP_HIP(hipEventCreate(&e0));
-  FFP_HIP(hipEventCreate(&e1));
+  ScopedEvent e0, e1;
   auto time_shape = [&](int shape, int iters) {
     ConvOp o = op;
     o.force_shape = shape;
@@ -173,8 +172,6 @@ int conv_tune(const ConvOp& op, hipStream_t st) {
               (long long)op.out.lvl->actual_px(), shape, conv_variant(o).c_str(), t, shape == heur ? "  (heuristic)" : "");
     }
   }
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
   // keep the heuristic's choice unless another shape is clearly (> 3 %) faster: timing noise must not flip plans
   if (heur_t > 0.f && best_t > 0.97f * heur_t) return heur;
   return best;

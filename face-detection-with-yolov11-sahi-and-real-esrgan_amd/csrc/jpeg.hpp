@@ -64,7 +64,7 @@ void jpeg_huff_note_fallback();
 // dequantisation + integer IDCT + upsampling + colour conversion into d_out (h x w x 3 uint8, row pitch `stride`, RGB or BGR);
 // upload: the coefficients are in s.coef (host decoder) and go to the device first. Queues on `st`, no synchronisation.
 void jpeg_reconstruct_device(const JpegScan& s, JpegDecodeWs& ws, unsigned char* d_out, long long stride, int bgr, hipStream_t st, bool upload);
-// header -> workspace -> entropy decode -> reconstruction, for a stream of `n` bytes (the three entry points of api.cpp share it)
+// header -> workspace -> entropy decode -> reconstruction, for a stream of `n` bytes (the decoding entry points of api_codec.cpp share it)
 void jpeg_decode_to_device(const unsigned char* data, long long n, unsigned char* d_out, long long stride, long long cap, int bgr, hipStream_t st, int* out_h, int* out_w);
 
 }  // namespace ffp

@@ -11,6 +11,15 @@
 
 namespace ffp {
 
+void resize_lanczos4_dev(const void* d_src, int h, int w, int cn, int wide, int out_h, int out_w, void* d_dst, DevBuf& tab,
+                         std::vector<uint8_t>& host_tab, hipStream_t st) {
+  host_tab.resize(lanczos4_table_bytes(out_h, out_w));
+  lanczos4_pack(lanczos4_axis(w, out_w), lanczos4_axis(h, out_h), wide, host_tab.data());
+  tab.ensure(host_tab.size());
+  FFP_HIP(hipMemcpyAsync(tab.p, host_tab.data(), host_tab.size(), hipMemcpyHostToDevice, st));
+  launch_resize_lanczos4(d_src, h, w, cn, wide, tab.p, out_h, out_w, d_dst, st);
+}
+
 SrEngine::SrEngine(const void* weights, size_t nbytes, int scale, int num_block, int device, int half) {
   FFP_CHECK(scale == 4 || scale == 2, FFP_ERR_ARG, "scale must be 4 or 2");
   FFP_CHECK(num_block >= 1 && num_block <= 64, FFP_ERR_ARG, "num_block");

@@ -8,6 +8,8 @@
 
 #include <cmath>
 
+#include "api_util.hpp"
+
 namespace ffp {
 
 namespace {
@@ -408,17 +410,14 @@ RtdetrPlan* RtdetrEngine::prepare(const uint8_t* const* frames, const int32_t* h
   if (profile) {
     if (P->runs == 0) P->execute(st_, nullptr);           // the first run tunes the convs and builds lazily created tables
     profile_ms.clear();
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
+    std::vector<std::pair<ScopedEvent, ScopedEvent>> ev;
     std::vector<std::string> names;
     for (Step& s : P->steps) {
       if (s.kind != 0) continue;
-      hipEvent_t a, b;
-      FFP_HIP(hipEventCreate(&a));
-      FFP_HIP(hipEventCreate(&b));
-      FFP_HIP(hipEventRecord(a, st_));
+      ev.emplace_back();
+      FFP_HIP(hipEventRecord(ev.back().first, st_));
       s.run(st_);
-      FFP_HIP(hipEventRecord(b, st_));
-      ev.emplace_back(a, b);
+      FFP_HIP(hipEventRecord(ev.back().second, st_));
       names.push_back(s.is_conv ? "conv " + s.variant + " " + s.name : s.name.empty() ? std::string("amax_init") : s.name);
     }
     FFP_HIP(hipStreamSynchronize(st_));
@@ -426,8 +425,6 @@ RtdetrPlan* RtdetrEngine::prepare(const uint8_t* const* frames, const int32_t* h
       float ms = 0.f;
       FFP_HIP(hipEventElapsedTime(&ms, ev[i].first, ev[i].second));
       profile_ms.emplace_back(names[i], ms);
-      (void)hipEventDestroy(ev[i].first);
-      (void)hipEventDestroy(ev[i].second);
     }
   } else {
     P->execute(st_, nullptr);

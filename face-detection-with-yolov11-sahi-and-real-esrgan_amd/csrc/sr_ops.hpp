@@ -53,6 +53,9 @@ size_t lanczos4_table_bytes(int out_h, int out_w);
 void lanczos4_pack(const Lanczos4Axis& ax, const Lanczos4Axis& ay, int wide, void* host_tab);
 void launch_resize_lanczos4(const void* d_src, int h, int w, int cn, int wide, const void* d_tab, int out_h, int out_w, void* d_dst,
                             hipStream_t st);
+// the host side of a Lanczos4 resize (rrdb.cpp): tables built here, uploaded on `st` into `tab` (the host copy must outlive the upload)
+void resize_lanczos4_dev(const void* d_src, int h, int w, int cn, int wide, int out_h, int out_w, void* d_dst, DevBuf& tab,
+                         std::vector<uint8_t>& host_tab, hipStream_t st);
 // the 'cv2' alpha upsampler: cv2.resize(alpha / range, (out_w, out_h), INTER_LINEAR) in float32, quantised to rint(a * range)
 // into channel 3 of a 4-channel canvas of 8-bit (dst_wide 0) or 16-bit elements; src is the 4-channel input
 void launch_alpha_linear(const void* d_src, int h, int w, int src_wide, float range, int out_h, int out_w, void* d_dst, int dst_wide,

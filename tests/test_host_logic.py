@@ -107,6 +107,30 @@ def test_compute_calls_fail_loudly_without_gpu(lib):
         _lib.Enhancer({"conv_first.weight": np.zeros((64, 3, 3, 3), np.float32)})
     with pytest.raises(_lib.FfpError):
         _lib.op_conv2d(np.zeros((1, 4, 4, 4), np.float32), np.zeros((4, 4, 1, 1), np.float32), None)
+    # every family of entries that takes a device number: arguments that are valid up to the device check -> FFP_ERR_HIP (2), said in one way
+    f32 = lambda *s: np.zeros(s, np.float32)
+    u8 = C.POINTER(C.c_uint8)
+    raw = np.zeros(64, np.uint8)              # ffp_jpeg_decode looks at the device before it looks at the bytes
+    calls = {
+        "merge": lambda: _lib.merge(f32(3, 6)),
+        "eval_wider_pr": lambda: _lib.eval_wider_pr([np.zeros((1, 5))], [np.zeros((1, 4))], [np.ones(1, np.uint8)], thresh_num=4),
+        "eval_dual_match": lambda: _lib.eval_dual_match([np.zeros((1, 5))], [np.zeros((1, 4))], [np.ones(1, np.uint8)]),
+        "eval_coco_bbox": lambda: _lib.eval_coco_bbox(np.zeros((0, 7)), [0, 0], np.zeros((0, 8)), [0, 0], 1, 1, [0.5], [0.0], [[0.0, 1e10]], [100]),
+        "jpeg_encode": lambda: _lib.jpeg_encode(np.zeros((8, 8, 3), np.uint8)),
+        "jpeg_decode": lambda: _lib._check(lib.ffp_jpeg_decode(0, raw.ctypes.data_as(u8), raw.size, 0, np.zeros(192, np.uint8).ctypes.data_as(u8), 192)),
+        "png_encode": lambda: _lib.png_encode(np.zeros((8, 8, 3), np.uint8)),
+        "conv2d": lambda: _lib.op_conv2d(f32(1, 4, 4, 4), f32(4, 4, 1, 1), None),
+        "conv1x1_up2": lambda: _lib.op_conv1x1_up2(f32(1, 2, 2, 4), f32(1, 4, 4, 4), f32(8, 8), f32(8)),
+        "conv2d_time": lambda: _lib.op_conv2d_time(1, 8, 8, 16, 16, iters=1),
+        "resize_lanczos4": lambda: _lib.op_resize_lanczos4(np.zeros((4, 4, 3), np.uint8), 6, 5),
+        "upsample2x": lambda: _lib.op_upsample2x([f32(2, 2, 8)], 8, 0, [f32(4, 4, 8)], 0),
+        "rt_gelu": lambda: _lib.op_rt_gelu(f32(4, 8), 8, 0),
+    }
+    for name, call in calls.items():
+        with pytest.raises(_lib.FfpError) as e:
+            call()
+        assert e.value.code == 2 and "no HIP device" in str(e.value), (name, str(e.value))
+        assert f"{name}: no HIP device 0 (no CPU path)" in str(e.value), (name, str(e.value))
 
 
 def test_bad_arguments_are_reported(lib):
