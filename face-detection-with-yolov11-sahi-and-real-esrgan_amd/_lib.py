@@ -179,6 +179,12 @@ _SIGS = {
     "ffp_op_scrfd_pool": (C.c_int, [C.c_int, C.c_int, _p(C.c_int32), _p(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int]),
     "ffp_op_scrfd_post": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_int32), C.c_int, _p(_p(C.c_float)), _p(C.c_int32), _p(C.c_int32), _p(C.c_float), C.c_float, C.c_float, C.c_int, _p(C.c_float), _p(C.c_int32), _p(C.c_float)]),
     "ffp_op_resize_lanczos4": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "ffp_op_image_input": (C.c_int, [C.c_int, C.c_int, C.c_int, _p(C.c_uint8), C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_int32), C.c_int, C.c_int,
+                                     _p(C.c_float), _p(C.c_int32), _p(C.c_int32)]),
+    "ffp_op_stem": (C.c_int, [C.c_int, C.c_int, C.c_int, _p(C.c_uint8), C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_int32), C.c_int, _p(C.c_float),
+                              _p(C.c_float), C.c_int, C.c_int, C.c_int, _p(C.c_float)]),
+    "ffp_op_stem_conv": (C.c_int, [C.c_int, _p(C.c_uint8), C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_int32), C.c_int, _p(C.c_float), _p(C.c_float),
+                                   C.c_int, _p(C.c_float), _p(C.c_float), _p(C.c_float)]),
     "ffp_scrfd_create": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, _p(C.c_void_p)]),
     "ffp_scrfd_destroy": (None, [C.c_void_p]),
     "ffp_scrfd_describe": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
@@ -1392,6 +1398,68 @@ def op_scrfd_sahi_rows(dets: np.ndarray, counts, tiles, full_shape, conf: float,
     if rc != 0 and bad.value < 0:
         _check(rc)
     return d, c, (None if bad.value < 0 else (bad.value // cap, bad.value % cap))
+
+
+IMAGE_YOLO, IMAGE_RTDETR, IMAGE_SCRFD = 0, 1, 2      # ffp_op_image_input kind
+
+
+def _u8p(a: np.ndarray):
+    return a.ctypes.data_as(_p(C.c_uint8))
+
+
+def op_image_input(kind: int, frame: np.ndarray, boxes, size, chan_order: int = CHAN_AS_BGR, precision: int = PREC_F32,
+                   device: int = 0) -> List[np.ndarray]:
+    """The network image of every box {x0, y0, x1, y1} of an H x W x 3 uint8 frame, as the image-input kernel of `kind` writes it
+    (ffp_op_image_input): one (net_h, net_w, 4 or 8) float32 array of whole pixel records per box. size: imgsz, or (det_w, det_h) for
+    IMAGE_SCRFD."""
+    f, t = _as_frame(frame), _as_tiles(boxes)
+    a, b = (int(size[0]), int(size[1])) if kind == IMAGE_SCRFD else (int(size), int(size))
+    n = t.shape[0]
+    cs = 8 if precision == PREC_F16 and kind != IMAGE_SCRFD else 4
+    out = np.zeros((max(n * a * b, 1), cs), np.float32)
+    hs, ws = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+    _check(lib().ffp_op_image_input(device, kind, precision, _u8p(f), f.shape[0], f.shape[1], chan_order, n, _ip(t), a, b, _fp(out), _ip(hs), _ip(ws)))
+    return _op_unpack(out, hs[:n], ws[:n])
+
+
+def _stem_out_sizes(t: np.ndarray, imgsz: int, stride: int):
+    hs, ws = [], []
+    for x0, y0, x1, y1 in t.tolist():
+        nw, nh, top, bottom, left, right = letterbox_geometry(y1 - y0, x1 - x0, imgsz)
+        hs.append((nh + top + bottom - 1) // stride + 1)
+        ws.append((nw + left + right - 1) // stride + 1)
+    return hs, ws
+
+
+def op_stem(frame: np.ndarray, boxes, imgsz: int, w, bias, fused: bool, stride: int = 2, act: int = 1, chan_order: int = CHAN_AS_BGR,
+            precision: int = PREC_F32, device: int = 0) -> List[np.ndarray]:
+    """The image-input 3x3 conv (w (cout, 3, 3, 3), bias (cout,)) on the YOLO letterbox of every box (ffp_op_stem): fused False = the
+    letterbox kernel and the direct conv kernel, True = the one kernel that reads the frame. One (ho, wo, cout) float32 array per box."""
+    f, t, w, bias = _as_frame(frame), _as_tiles(boxes), _f32(w), _f32(bias)
+    if w.ndim != 4 or w.shape[1:] != (3, 3, 3) or bias.shape != (w.shape[0],):
+        raise ValueError("stem: w must be (cout, 3, 3, 3) and bias (cout,)")
+    n, cout = t.shape[0], int(w.shape[0])
+    side = (int(imgsz) - 1) // max(int(stride), 1) + 1
+    out = np.zeros((max(n * side * side, 1), cout), np.float32)
+    _check(lib().ffp_op_stem(device, precision, int(bool(fused)), _u8p(f), f.shape[0], f.shape[1], chan_order, n, _ip(t), int(imgsz), _fp(w), _fp(bias),
+                             cout, int(stride), int(act), _fp(out)))
+    return _op_unpack(out, *_stem_out_sizes(t, int(imgsz), int(stride)))
+
+
+def op_stem_conv(frame: np.ndarray, boxes, imgsz: int, stem_w, stem_b, conv_w, conv_b, chan_order: int = CHAN_AS_BGR, device: int = 0) -> List[np.ndarray]:
+    """model.0 inside model.1's loader (ffp_op_stem_conv, PREC_F32X3): stem_w (c, 3, 3, 3) with c 16 or 32, conv_w (2c, c, 3, 3), both stride 2 and
+    SiLU. One (net_h / 4, net_w / 4, 2c) float32 array per box."""
+    f, t = _as_frame(frame), _as_tiles(boxes)
+    sw, sb, cw, cb = _f32(stem_w), _f32(stem_b), _f32(conv_w), _f32(conv_b)
+    c = int(sw.shape[0])
+    if sw.ndim != 4 or sw.shape[1:] != (3, 3, 3) or sb.shape != (c,) or cw.shape != (2 * c, c, 3, 3) or cb.shape != (2 * c,):
+        raise ValueError("stem_conv: stem_w (c, 3, 3, 3), stem_b (c,), conv_w (2c, c, 3, 3), conv_b (2c,)")
+    n = t.shape[0]
+    side = (int(imgsz) + 3) // 4
+    out = np.zeros((max(n * side * side, 1), 2 * c), np.float32)
+    _check(lib().ffp_op_stem_conv(device, _u8p(f), f.shape[0], f.shape[1], chan_order, n, _ip(t), int(imgsz), _fp(sw), _fp(sb), c, _fp(cw), _fp(cb),
+                                  _fp(out)))
+    return _op_unpack(out, *_stem_out_sizes(t, int(imgsz), 4))
 
 
 def jpeg_encode(img: np.ndarray, quality: int = 95, bgr: bool = False, device: int = 0) -> bytes:

@@ -8,6 +8,7 @@
 #include "rtdetr.hpp"
 #include "scrfd.hpp"
 #include "sr_ops.hpp"
+#include "yolo11.hpp"
 
 using namespace ffp;
 
@@ -1057,6 +1058,173 @@ int ffp_op_scrfd_sahi_rows(int device, int n_tiles, int cap, const int32_t* tile
     FFP_CHECK(false, FFP_ERR_ARG, "scrfd_sahi_rows: tile %d row %d: Box coords [minx, miny, maxx, maxy] cannot be negative", (int)(bad / (unsigned)cap),
               (int)(bad % (unsigned)cap));
   }
+  FFP_API_END
+}
+
+// ---- single-operator entry points of the image-input kernels (tests/test_gpu_image_input.py) -----------------------------------------
+// The frame is H x W x 3 u8 on the host, the items are boxes {x0, y0, x1, y1} of it; their LetterboxImg records come from the functions
+// the engines call (det_tile_geometry, rtdetr_tile_records, scrfd_tile_records), so a geometry mistake shows as well. Outputs hold the
+// items back to back; every output buffer goes up as 0xFF bytes (NaN), so a pixel no kernel wrote comes back as NaN.
+namespace {
+
+void op_check_frame(const char* what, const uint8_t* frame, int H, int W, int chan_order, int n, const int32_t* boxes) {
+  FFP_CHECK(frame && boxes, FFP_ERR_ARG, "%s: null frame or boxes", what);
+  FFP_CHECK(H >= 1 && W >= 1 && H <= 16384 && W <= 16384 && n >= 1 && n <= 4096, FFP_ERR_ARG, "%s: %d boxes of a %d x %d frame", what, n, W, H);
+  FFP_CHECK(chan_order == FFP_CHAN_AS_BGR || chan_order == FFP_CHAN_AS_RGB, FFP_ERR_ARG, "%s: chan_order %d", what, chan_order);
+}
+
+// the frame on the device; the 256 bytes behind it are 0xFF, so a kernel that used a byte past the frame would not match a reference that never saw one
+DevBuf op_upload_frame(const uint8_t* frame, int H, int W) {
+  const size_t nb = (size_t)H * W * 3;
+  DevBuf b(nb + 256);
+  FFP_HIP(hipMemcpy(b.p, frame, nb, hipMemcpyHostToDevice));
+  FFP_HIP(hipMemset(static_cast<char*>(b.p) + nb, 0xFF, 256));
+  return b;
+}
+
+DevBuf op_nan_buffer(size_t bytes) {
+  DevBuf b(bytes + 256);
+  FFP_HIP(hipMemset(b.p, 0xFF, b.n));
+  return b;
+}
+
+std::vector<LetterboxImg> op_det_records(int H, int W, const int32_t* boxes, int n, int imgsz) {
+  FFP_CHECK(imgsz > 0, FFP_ERR_ARG, "imgsz %d must be a multiple of 32 in [32,4096]", imgsz);      // (0 would ask det_tile_geometry for the first box's own size)
+  const std::vector<TileGeom> g = det_tile_geometry(H, W, boxes, n, imgsz);
+  std::vector<LetterboxImg> lb(n);
+  for (int i = 0; i < n; ++i) lb[i] = g[i].lb;
+  return lb;
+}
+
+}  // namespace
+
+int ffp_op_image_input(int device, int kind, int precision, const uint8_t* frame, int H, int W, int chan_order, int n, const int32_t* boxes_xyxy,
+                       int size_a, int size_b, float* out, int32_t* out_hs, int32_t* out_ws) {
+  FFP_API_BEGIN
+  FFP_CHECK(out && out_hs && out_ws, FFP_ERR_ARG, "image_input: null output");
+  op_check_frame("image_input", frame, H, W, chan_order, n, boxes_xyxy);
+  FFP_CHECK(kind >= 0 && kind <= 2, FFP_ERR_ARG, "image_input: kind %d (0 YOLO letterbox, 1 RT-DETR stretch, 2 SCRFD)", kind);
+  const DType T = op_dtype("image_input", precision);
+  FFP_CHECK(kind != 2 || T == F32, FFP_ERR_ARG, "image_input: the SCRFD pre-processing writes fp32 only");
+  std::vector<LetterboxImg> lb;
+  std::vector<float> scale;
+  if (kind == 0) {
+    lb = op_det_records(H, W, boxes_xyxy, n, size_a);
+  } else if (kind == 1) {
+    FFP_CHECK(size_a >= 32 && size_a % 32 == 0 && size_a <= 4096, FFP_ERR_ARG, "image_input: imgsz %d must be a multiple of 32 in [32, 4096]", size_a);
+    rtdetr_tile_records(H, W, boxes_xyxy, n, size_a, lb);
+  } else {
+    FFP_CHECK(size_a % 32 == 0 && size_b % 32 == 0 && size_a >= 32 && size_b >= 32 && size_a <= 4096 && size_b <= 4096, FFP_ERR_ARG,
+              "image_input: det size %dx%d must be multiples of 32 in [32, 4096]", size_a, size_b);
+    scrfd_tile_records(size_a, size_b, H, W, boxes_xyxy, n, lb, scale);
+  }
+  std::vector<int> hs(n), ws(n);
+  for (int i = 0; i < n; ++i) { hs[i] = lb[i].net_h; ws[i] = lb[i].net_w; }
+  ScopedStream cx(device, "image_input");
+  const int cs = T == F16 ? 8 : 4;
+  Level L;
+  L.build(hs, ws, cx.st);
+  DevBuf d_frame = op_upload_frame(frame, H, W), d_imgs = upload(lb.data(), lb.size()), dout = op_nan_buffer((size_t)L.total_px * cs * dsize(T));
+  const TView vout{dout.p, T, cs, 0, cs, &L};
+  const int flip = chan_order == FFP_CHAN_AS_BGR ? 1 : 0;
+  if (kind == 2) launch_scrfd_preproc(d_frame.as<uint8_t>(), W, flip, d_imgs.as<LetterboxImg>(), vout, cx.st);
+  else launch_letterbox(d_frame.as<uint8_t>(), H, W, flip, d_imgs, vout, cx.st);
+  FFP_HIP(hipStreamSynchronize(cx.st));
+  op_download(L, T, dout, cs, out);
+  std::copy(hs.begin(), hs.end(), out_hs);
+  std::copy(ws.begin(), ws.end(), out_ws);
+  FFP_API_END
+}
+
+int ffp_op_stem(int device, int precision, int fused, const uint8_t* frame, int H, int W, int chan_order, int n, const int32_t* boxes_xyxy, int imgsz,
+                const float* w, const float* bias, int cout, int stride, int act, float* out) {
+  FFP_API_BEGIN
+  FFP_CHECK(w && bias && out, FFP_ERR_ARG, "stem: null argument");
+  op_check_frame("stem", frame, H, W, chan_order, n, boxes_xyxy);
+  FFP_CHECK((fused == 0 || fused == 1) && (cout == 16 || cout == 32 || cout == 64) && (stride == 1 || stride == 2) && act >= ACT_NONE && act <= ACT_RELU,
+            FFP_ERR_ARG, "stem: fused %d (0, 1), cout %d (16, 32, 64), stride %d (1, 2), activation code %d (0..3)", fused, cout, stride, act);
+  const DType T = op_dtype("stem", precision);
+  const std::vector<LetterboxImg> lb = op_det_records(H, W, boxes_xyxy, n, imgsz);
+  std::vector<int> hi(n), wi(n), ho(n), wo(n);
+  for (int i = 0; i < n; ++i) {
+    hi[i] = lb[i].net_h; wi[i] = lb[i].net_w;
+    ho[i] = (hi[i] - 1) / stride + 1; wo[i] = (wi[i] - 1) / stride + 1;
+  }
+  ScopedStream cx(device, "stem");
+  PackedConv pc;
+  pack_conv(pc, "op_stem", w, bias, cout, 3, 3, 1, T, cx.st, false);
+  Level lin, lout;
+  lin.build(hi, wi, cx.st);
+  lout.build(ho, wo, cx.st);
+  const int cin0 = T == F16 ? 8 : 4;
+  DevBuf d_frame = op_upload_frame(frame, H, W), d_imgs = upload(lb.data(), lb.size()), din,
+         dout = op_nan_buffer((size_t)lout.total_px * cout * dsize(T));
+  if (!fused) din = op_nan_buffer((size_t)lin.total_px * cin0 * dsize(T));
+  ConvOp o;
+  o.pc = &pc; o.stride = stride; o.act = act;
+  o.in = TView{din.p, T, cin0, 0, cin0, &lin};      // fused: the level and the channel padding only
+  o.out = TView{dout.p, T, cout, 0, cout, &lout};
+  const int flip = chan_order == FFP_CHAN_AS_BGR ? 1 : 0;
+  if (fused) {
+    launch_stem_from_frame(d_frame.as<uint8_t>(), H, W, flip, d_imgs, o, cx.st);
+  } else {
+    launch_letterbox(d_frame.as<uint8_t>(), H, W, flip, d_imgs, o.in, cx.st);
+    launch_conv_direct(o, cx.st);
+  }
+  FFP_HIP(hipStreamSynchronize(cx.st));
+  op_download(lout, T, dout, cout, out);
+  FFP_API_END
+}
+
+int ffp_op_stem_conv(int device, const uint8_t* frame, int H, int W, int chan_order, int n, const int32_t* boxes_xyxy, int imgsz, const float* stem_w,
+                     const float* stem_b, int stem_cout, const float* conv_w, const float* conv_b, float* out) {
+  FFP_API_BEGIN
+  FFP_CHECK(stem_w && stem_b && conv_w && conv_b && out, FFP_ERR_ARG, "stem_conv: null argument");
+  op_check_frame("stem_conv", frame, H, W, chan_order, n, boxes_xyxy);
+  FFP_CHECK(stem_cout == 16 || stem_cout == 32, FFP_ERR_ARG, "stem_conv: %d stem channels (16 or 32: the loader holds one or two 16-channel chunks)", stem_cout);
+  const std::vector<LetterboxImg> lb = op_det_records(H, W, boxes_xyxy, n, imgsz);
+  std::vector<int> h0(n), w0(n), h1(n), w1(n), h2(n), w2(n);
+  for (int i = 0; i < n; ++i) {
+    h0[i] = lb[i].net_h; w0[i] = lb[i].net_w;
+    h1[i] = (h0[i] - 1) / 2 + 1; w1[i] = (w0[i] - 1) / 2 + 1;
+    h2[i] = (h1[i] - 1) / 2 + 1; w2[i] = (w1[i] - 1) / 2 + 1;
+  }
+  ScopedStream cx(device, "stem_conv");
+  conv_kernels_init();
+  const int cc = 2 * stem_cout;
+  PackedConv ps, pc;
+  pack_conv(ps, "model.0.conv", stem_w, stem_b, stem_cout, 3, 3, 1, F32, cx.st, true);
+  pack_conv(pc, "model.1.conv", conv_w, conv_b, cc, stem_cout, 3, 1, F32, cx.st, true);
+  // as a split plan lays it out: levels aligned to 32 pixels, one max-|value| slot per (buffer, image); the stem output's slots hold the bound the
+  // plan knows from the weights alone, the conv output's start at zero
+  Level L0, L1, L2;
+  L0.build(h0, w0, cx.st, 32);
+  L1.build(h1, w1, cx.st, 32);
+  L2.build(h2, w2, cx.st, 32);
+  std::vector<unsigned> slots(2 * (size_t)n, 0u);
+  {
+    const float bound = std::max(ps.out_bound, 0.3f);
+    unsigned b;
+    std::memcpy(&b, &bound, 4);
+    std::fill(slots.begin(), slots.begin() + n, b);
+  }
+  DevBuf d_frame = op_upload_frame(frame, H, W), d_imgs = upload(lb.data(), lb.size()), dslots = upload(slots.data(), slots.size()),
+         dout = op_nan_buffer((size_t)L2.total_px * cc * 4), d_stem_w;
+  ConvOp stem, conv;
+  stem.pc = &ps; stem.stride = 2; stem.act = ACT_SILU;
+  stem.in = TView{nullptr, F32, 4, 0, 4, &L0};
+  stem.out = TView{nullptr, F32, stem_cout, 0, stem_cout, &L1};      // never stored
+  stem.out.amax = dslots.as<unsigned>(); stem.out.amax_n = n;
+  conv.pc = &pc; conv.stride = 2; conv.act = ACT_SILU;
+  conv.in = stem.out;
+  conv.out = TView{dout.p, F32, cc, 0, cc, &L2};
+  conv.out.amax = dslots.as<unsigned>() + n; conv.out.amax_n = n;
+  FFP_CHECK(stem_conv_eligible(stem, conv), FFP_ERR_ARG, "stem_conv: the stem-fused loader refuses this pair of convs");
+  const int flip = chan_order == FFP_CHAN_AS_BGR ? 1 : 0;
+  stem_conv_pack(stem, flip, d_stem_w, cx.st);
+  launch_stem_conv(d_frame.as<uint8_t>(), H, W, d_imgs, d_stem_w, stem, conv, cx.st);
+  FFP_HIP(hipStreamSynchronize(cx.st));
+  op_download(L2, F32, dout, cc, out);
   FFP_API_END
 }
 

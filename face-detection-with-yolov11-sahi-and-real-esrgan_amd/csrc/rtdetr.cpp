@@ -377,6 +377,23 @@ static void check_imgsz(int imgsz) {
             "rtdetr: imgsz %d gives fewer encoder tokens than the decoder's %d queries", imgsz, RT_NQ);
 }
 
+LetterboxImg rtdetr_stretch(int x0, int y0, int sw, int sh, int imgsz) {
+  LetterboxImg L;
+  L.x0 = x0; L.y0 = y0; L.sw = sw; L.sh = sh;
+  L.new_w = imgsz; L.new_h = imgsz; L.top = 0; L.left = 0; L.net_h = imgsz; L.net_w = imgsz;    // LetterBox(scale_fill=True): a stretch
+  return L;
+}
+
+void rtdetr_tile_records(int H, int W, const int32_t* tiles, int n_tiles, int imgsz, std::vector<LetterboxImg>& lb) {
+  lb.resize(n_tiles);
+  for (int i = 0; i < n_tiles; ++i) {
+    const int32_t* t = tiles + 4 * i;
+    FFP_CHECK(t[0] >= 0 && t[1] >= 0 && t[2] > t[0] && t[3] > t[1] && t[2] <= W && t[3] <= H, FFP_ERR_ARG,
+              "rtdetr: tile %d [%d, %d, %d, %d] is empty, inverted or outside the %d x %d frame", i, t[0], t[1], t[2], t[3], W, H);
+    lb[i] = rtdetr_stretch(t[0], t[1], t[2] - t[0], t[3] - t[1], imgsz);      // the stretch prepare() builds
+  }
+}
+
 RtdetrPlan* RtdetrEngine::prepare(const uint8_t* const* frames, const int32_t* hw, int n, int imgsz) {
   FFP_CHECK(frames && hw && n > 0, FFP_ERR_ARG, "rtdetr: empty batch");
   check_imgsz(imgsz);
@@ -398,9 +415,7 @@ RtdetrPlan* RtdetrEngine::prepare(const uint8_t* const* frames, const int32_t* h
     const int h = hw[2 * i], w = hw[2 * i + 1];
     FFP_HIP(hipMemcpy2DAsync((uint8_t*)frame_.p + (size_t)y * Wmax * 3, (size_t)Wmax * 3, frames[i], (size_t)w * 3, (size_t)w * 3, h,
                              hipMemcpyHostToDevice, st_));
-    LetterboxImg& L = lb[i];
-    L.x0 = 0; L.y0 = (int)y; L.sw = w; L.sh = h;
-    L.new_w = imgsz; L.new_h = imgsz; L.top = 0; L.left = 0; L.net_h = imgsz; L.net_w = imgsz;    // LetterBox(scale_fill=True): a stretch
+    lb[i] = rtdetr_stretch(0, (int)y, w, h, imgsz);
     wh[i] = make_float2((float)w, (float)h);
     y += h;
   }
@@ -464,15 +479,7 @@ void RtdetrEngine::enqueue_tiles(const uint8_t* d_frame, int H, int W, int chan_
   FFP_CHECK(chan_order == FFP_CHAN_AS_BGR || chan_order == FFP_CHAN_AS_RGB, FFP_ERR_ARG, "rtdetr: chan_order %d", chan_order);
   FFP_CHECK(mode == FFP_RT_TILES_LOCAL || mode == FFP_RT_TILES_SAHI, FFP_ERR_ARG, "rtdetr: tile mode %d (FFP_RT_TILES_LOCAL or FFP_RT_TILES_SAHI)", mode);
   check_imgsz(imgsz);
-  h_lb_.resize(n_tiles);
-  for (int i = 0; i < n_tiles; ++i) {
-    const int32_t* t = tiles + 4 * i;
-    FFP_CHECK(t[0] >= 0 && t[1] >= 0 && t[2] > t[0] && t[3] > t[1] && t[2] <= W && t[3] <= H, FFP_ERR_ARG,
-              "rtdetr: tile %d [%d, %d, %d, %d] is empty, inverted or outside the %d x %d frame", i, t[0], t[1], t[2], t[3], W, H);
-    LetterboxImg& L = h_lb_[i];
-    L.x0 = t[0]; L.y0 = t[1]; L.sw = t[2] - t[0]; L.sh = t[3] - t[1];
-    L.new_w = imgsz; L.new_h = imgsz; L.top = 0; L.left = 0; L.net_h = imgsz; L.net_w = imgsz;    // the stretch prepare() builds
-  }
+  rtdetr_tile_records(H, W, tiles, n_tiles, imgsz, h_lb_);
   FFP_HIP(hipSetDevice(device_));
   tiles_lb_.ensure(sizeof(LetterboxImg) * n_tiles);
   tiles_xy_.ensure(sizeof(int4) * n_tiles);

@@ -43,6 +43,12 @@ void rtdetr_pos_embed(int w, int h, std::vector<float>& pos);
 // depthwise weights (C, 1, k, k) -> [tap][C], the layout rt_dwconv reads
 std::vector<float> rtdetr_pack_depthwise(const float* w, int C, int taps);
 
+// the letterbox record of one source rectangle: LetterBox(imgsz, auto=False, scale_fill=True), a stretch to imgsz x imgsz without padding
+LetterboxImg rtdetr_stretch(int x0, int y0, int sw, int sh, int imgsz);
+// ... of every tile {x0, y0, x1, y1} of an H x W frame (an empty, inverted or outside tile is FFP_ERR_ARG): what the sliced path runs and what
+// ffp_op_image_input hands letterbox_kernel
+void rtdetr_tile_records(int H, int W, const int32_t* tiles, int n_tiles, int imgsz, std::vector<LetterboxImg>& lb);
+
 struct RtdetrPlan : Plan {
   int n = 0, imgsz = 0, NT = 0;
   void add_named(const std::string& name, std::function<void(hipStream_t)> f) { add(std::move(f)); steps.back().name = name; }

@@ -135,21 +135,24 @@ ScrfdPlan* ScrfdEngine::prepare(const uint8_t* frame, int H, int W, int chan_ord
   return P;
 }
 
-void ScrfdEngine::tile_geometry(const ScrfdPlan& first, int H, int W, const int32_t* tiles, int n_tiles) {
-  const int nw_ = first.low.det_w, nh_ = first.low.det_h;     // a fixed input size of the file wins
-  h_lb_.resize(n_tiles);
-  h_scale_.resize(n_tiles);
+void scrfd_tile_records(int net_w, int net_h, int H, int W, const int32_t* tiles, int n_tiles, std::vector<LetterboxImg>& lb, std::vector<float>& scale) {
+  lb.resize(n_tiles);
+  scale.resize(n_tiles);
   for (int i = 0; i < n_tiles; ++i) {
     const int x0 = tiles[4 * i], y0 = tiles[4 * i + 1], x1 = tiles[4 * i + 2], y1 = tiles[4 * i + 3];
     FFP_CHECK(x0 >= 0 && y0 >= 0 && x1 <= W && y1 <= H && x1 > x0 && y1 > y0, FFP_ERR_ARG, "tile %d [%d,%d,%d,%d] outside %dx%d frame", i, x0, y0,
               x1, y1, W, H);
-    LetterboxImg& L = h_lb_[i];
+    LetterboxImg& L = lb[i];
     L.x0 = x0; L.y0 = y0; L.sw = x1 - x0; L.sh = y1 - y0;
-    scrfd_geometry(L.sh, L.sw, nw_, nh_, &L.new_w, &L.new_h, &h_scale_[i]);
+    scrfd_geometry(L.sh, L.sw, net_w, net_h, &L.new_w, &L.new_h, &scale[i]);
     FFP_CHECK(L.new_w > 0 && L.new_h > 0, FFP_ERR_ARG, "tile %d (%dx%d) resizes to %dx%d at net size %dx%d (cv2.resize would raise)", i, L.sw, L.sh,
-              L.new_w, L.new_h, nw_, nh_);
-    L.top = 0; L.left = 0; L.net_h = nh_; L.net_w = nw_;
+              L.new_w, L.new_h, net_w, net_h);
+    L.top = 0; L.left = 0; L.net_h = net_h; L.net_w = net_w;
   }
+}
+
+void ScrfdEngine::tile_geometry(const ScrfdPlan& first, int H, int W, const int32_t* tiles, int n_tiles) {
+  scrfd_tile_records(first.low.det_w, first.low.det_h, H, W, tiles, n_tiles, h_lb_, h_scale_);     // a fixed input size of the file wins
 }
 
 void ScrfdEngine::run_chunk(ScrfdPlan* P, const uint8_t* d_frame, int W, int chan_order, int off, int m) {

@@ -46,6 +46,10 @@ void launch_scrfd_sahi_rows(float* dets, int* counts, const int4* tiles_xyxy, in
 // RetinaFace.detect geometry of one (h, w) crop at net size (W, H): {new_w, new_h}; det_scale = float32(new_h / h). new_w or new_h may be 0.
 void scrfd_geometry(int h, int w, int net_w, int net_h, int* new_w, int* new_h, float* det_scale);
 
+// the record (picture at the top-left of a net_w x net_h canvas) and det_scale of every tile {x0, y0, x1, y1} of an H x W frame; a tile outside the
+// frame, or one that resizes to nothing, is FFP_ERR_ARG: what the engine runs and what ffp_op_image_input hands scrfd_preproc_kernel
+void scrfd_tile_records(int net_w, int net_h, int H, int W, const int32_t* tiles, int n_tiles, std::vector<LetterboxImg>& lb, std::vector<float>& scale);
+
 struct ScrfdPlan : Plan {
   onnx::Lowered low;
   std::vector<TView> views;                // by lowered buffer

@@ -465,7 +465,7 @@ void DetEngine::build_plan(DetPlan& P, const std::vector<int>& hs, const std::ve
   P.d_imgs.alloc(sizeof(DetImg) * n);
 }
 
-std::vector<TileGeom> DetEngine::geometry(int H, int W, const int32_t* tiles, int n_tiles, int imgsz) const {
+std::vector<TileGeom> det_tile_geometry(int H, int W, const int32_t* tiles, int n_tiles, int imgsz) {
   FFP_CHECK(H > 0 && W > 0 && n_tiles > 0 && tiles, FFP_ERR_ARG, "empty frame or tile list");
   std::vector<TileGeom> g(n_tiles);
   for (int i = 0; i < n_tiles; ++i) {
@@ -478,6 +478,7 @@ std::vector<TileGeom> DetEngine::geometry(int H, int W, const int32_t* tiles, in
     FFP_CHECK(sz % 32 == 0 && sz >= 32 && sz <= 4096, FFP_ERR_ARG, "imgsz %d must be a multiple of 32 in [32,4096]", sz);
     int32_t lg[6];
     letterbox_geometry(sh, sw, sz, lg);
+    FFP_CHECK(lg[0] > 0 && lg[1] > 0, FFP_ERR_ARG, "tile %d (%dx%d) resizes to %dx%d at imgsz %d (cv2.resize would raise)", i, sw, sh, lg[0], lg[1], sz);
     TileGeom& t = g[i];
     t.lb.x0 = x0; t.lb.y0 = y0; t.lb.sw = sw; t.lb.sh = sh;
     t.lb.new_w = lg[0]; t.lb.new_h = lg[1]; t.lb.top = lg[2]; t.lb.left = lg[4];
@@ -567,7 +568,7 @@ void DetEngine::last_active(int* active, int* items) const {
 
 DetPlan* DetEngine::prepare(const uint8_t* d_frame, int H, int W, int chan_order, const int32_t* tiles, int n_tiles, int imgsz, float conf) {
   FFP_HIP(hipSetDevice(device_));
-  geom_last_ = geometry(H, W, tiles, n_tiles, imgsz);
+  geom_last_ = det_tile_geometry(H, W, tiles, n_tiles, imgsz);
   DetPlan* P = plan_for(geom_last_);
   std::vector<LetterboxImg> lb(n_tiles);
   std::vector<DetImg> di(n_tiles);

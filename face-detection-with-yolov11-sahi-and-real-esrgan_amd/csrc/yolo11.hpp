@@ -93,7 +93,6 @@ class DetEngine {
  private:
   DetPlan* plan_for(const std::vector<TileGeom>& g);
   void build_plan(DetPlan& p, const std::vector<int>& hs, const std::vector<int>& ws);
-  std::vector<TileGeom> geometry(int H, int W, const int32_t* tiles, int n_tiles, int imgsz) const;
   // conf: the gate's threshold for this call (what decode will test against; below 0: every item active)
   DetPlan* prepare(const uint8_t* d_frame, int H, int W, int chan_order, const int32_t* tiles, int n_tiles, int imgsz, float conf);
   void fetch_active(DetPlan* P, int n_tiles);
@@ -121,5 +120,8 @@ class DetEngine {
 };
 
 void letterbox_geometry(int h, int w, int imgsz, int32_t* out6);
+// the letterbox record and the decode's gain / pad of every tile {x0, y0, x1, y1} of an H x W frame (imgsz <= 0: the first tile's long side rounded up
+// to 32): what DetEngine runs, and what ffp_op_image_input / ffp_op_stem / ffp_op_stem_conv hand the image-input kernels
+std::vector<TileGeom> det_tile_geometry(int H, int W, const int32_t* tiles, int n_tiles, int imgsz);
 
 }  // namespace ffp

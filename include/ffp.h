@@ -584,6 +584,28 @@ int ffp_op_scrfd_post(int device, int n, int net_h, int net_w, int A, const int3
 int ffp_op_scrfd_sahi_rows(int device, int n_tiles, int cap, const int32_t* tiles_xyxy, int full_h, int full_w, float conf, float* dets,
                            int32_t* counts, int32_t* out_bad);
 
+/* Tests only: the image-input kernels alone. frame: H x W x 3 u8 on the host; the n items are boxes {x0, y0, x1, y1} of it, turned into
+ * letterbox records by the code the engines run (a box outside the frame, or a size that is no multiple of 32, is FFP_ERR_ARG). chan_order as
+ * for the detectors. Every output holds the items back to back and goes up as NaN, so a pixel no kernel wrote comes back as NaN.
+ *
+ * ffp_op_image_input: kind 0 = the YOLO letterbox at imgsz size_a (pad 114, / 255), 1 = the RT-DETR stretch to size_a x size_a (/ 255),
+ * 2 = SCRFD at det size size_a x size_b (w x h): picture at the top-left, pad 0, (v - 127.5) / 128, FFP_PREC_F32 only. out: whole pixel
+ * records as float32, pad channels included — 4 per pixel, 8 for kinds 0 and 1 in FFP_PREC_F16 (values rounded to fp16 by the kernel) — sized
+ * for n * size_a * size_a (kind 2: n * size_a * size_b) pixels; out_hs / out_ws [n]: the network size of every item. */
+int ffp_op_image_input(int device, int kind, int precision, const uint8_t* frame, int H, int W, int chan_order, int n, const int32_t* boxes_xyxy,
+                       int size_a, int size_b, float* out, int32_t* out_hs, int32_t* out_ws);
+/* The image-input 3x3 conv (w [cout][3][3][3], bias [cout], cout 16 / 32 / 64, stride 1 or 2, pad 1, activation code act) on the YOLO
+ * letterbox of every item at imgsz: fused 0 = letterbox kernel, then the direct conv kernel; 1 = the one kernel that reads the frame through
+ * the letterbox arithmetic. FFP_PREC_F32 or FFP_PREC_F16. out: [sum ho * wo][cout] float32, ho = (net_h - 1) / stride + 1. */
+int ffp_op_stem(int device, int precision, int fused, const uint8_t* frame, int H, int W, int chan_order, int n, const int32_t* boxes_xyxy, int imgsz,
+                const float* w, const float* bias, int cout, int stride, int act, float* out);
+/* model.0 computed inside model.1's loader (FFP_PREC_F32X3): stem 3x3 stride 2 SiLU to stem_cout (16 or 32) channels, then conv_w
+ * [2 * stem_cout][stem_cout][3][3] stride 2 SiLU, laid out as a split plan lays it out (levels aligned to 32 pixels, one max-|value| slot per
+ * image, the stem output's from the weight bound). out: [sum (net_h / 4) * (net_w / 4)][2 * stem_cout]. A pair of convs the loader
+ * refuses is FFP_ERR_ARG; nothing else ever runs in its place. */
+int ffp_op_stem_conv(int device, const uint8_t* frame, int H, int W, int chan_order, int n, const int32_t* boxes_xyxy, int imgsz, const float* stem_w,
+                     const float* stem_b, int stem_cout, const float* conv_w, const float* conv_b, float* out);
+
 /* Tuning hook: mean device time (HIP events, microseconds) of `iters` back-to-back launches of one dense convolution on
  * synthetic data. dbg_mask skips kernel phases (1 stores, 2 MFMAs, 4 chunk refetch, 8 LDS stash) to attribute time —
  * results are then wrong by construction; force_shape pins the workgroup shape (-1: automatic). */

@@ -23,6 +23,22 @@ def _round_half_even_short(x: np.ndarray) -> np.ndarray:
     return np.clip(np.rint(x), -32768, 32767).astype(np.int32)
 
 
+def linear_axis(n_dst: int, n_src: int, scale: float, zero_frac_at_border: bool):
+    """Per destination index of one axis of the 8-bit INTER_LINEAR resize: (first source index, 11-bit weight of it, weight of the next one)."""
+    d = np.arange(n_dst, dtype=np.float64)
+    f = ((d + 0.5) * scale - 0.5).astype(np.float32)
+    s = np.floor(f).astype(np.int64)
+    f = (f - s.astype(np.float32)).astype(np.float32)
+    if zero_frac_at_border:                    # x axis: fx = 0 when the tap would leave the row
+        lo = s < 0
+        f[lo] = 0; s[lo] = 0
+        hi = s >= n_src - 1
+        f[hi] = 0; s[hi] = n_src - 1
+    c0 = _round_half_even_short((np.float32(1.0) - f) * np.float32(_COEF_ONE))
+    c1 = _round_half_even_short(f * np.float32(_COEF_ONE))
+    return s, c0, c1
+
+
 def resize_linear_u8(src: np.ndarray, dw: int, dh: int) -> np.ndarray:
     """cv2.resize(src, (dw, dh), interpolation=INTER_LINEAR) for uint8 HWC, restating OpenCV's fixed-point path:
     11-bit coefficients (saturate_cast<short>(c * 2048)), horizontal pass in int32, vertical pass
@@ -30,24 +46,10 @@ def resize_linear_u8(src: np.ndarray, dw: int, dh: int) -> np.ndarray:
     sh, sw = src.shape[:2]
     if (sw, sh) == (dw, dh):
         return src.copy()
-    scale_x, scale_y = sw / dw, sh / dh          # double, = 1 / inv_scale
-
-    def axis(n_dst, n_src, scale, zero_frac_at_border):
-        d = np.arange(n_dst, dtype=np.float64)
-        f = ((d + 0.5) * scale - 0.5).astype(np.float32)
-        s = np.floor(f).astype(np.int64)
-        f = (f - s.astype(np.float32)).astype(np.float32)
-        if zero_frac_at_border:                    # x axis: fx = 0 when the tap would leave the row
-            lo = s < 0
-            f[lo] = 0; s[lo] = 0
-            hi = s >= n_src - 1
-            f[hi] = 0; s[hi] = n_src - 1
-        c0 = _round_half_even_short((np.float32(1.0) - f) * np.float32(_COEF_ONE))
-        c1 = _round_half_even_short(f * np.float32(_COEF_ONE))
-        return s, c0, c1
-
-    sx, ax0, ax1 = axis(dw, sw, scale_x, True)
-    sy, by0, by1 = axis(dh, sh, scale_y, False)
+    # cv2 forms the scale as 1. / inv_scale with inv_scale = (double)dsize / ssize (imgproc/resize.cpp, cv::resize): not always the double sw / dw
+    scale_x, scale_y = 1.0 / (dw / sw), 1.0 / (dh / sh)
+    sx, ax0, ax1 = linear_axis(dw, sw, scale_x, True)
+    sy, by0, by1 = linear_axis(dh, sh, scale_y, False)
     sx1 = np.minimum(sx + 1, sw - 1)
     s32 = src.astype(np.int32)
     rows = s32[:, sx, :] * ax0[None, :, None] + s32[:, sx1, :] * ax1[None, :, None]   # (sh, dw, C)

@@ -125,6 +125,9 @@ def test_compute_calls_fail_loudly_without_gpu(lib):
         "resize_lanczos4": lambda: _lib.op_resize_lanczos4(np.zeros((4, 4, 3), np.uint8), 6, 5),
         "upsample2x": lambda: _lib.op_upsample2x([f32(2, 2, 8)], 8, 0, [f32(4, 4, 8)], 0),
         "rt_gelu": lambda: _lib.op_rt_gelu(f32(4, 8), 8, 0),
+        "image_input": lambda: _lib.op_image_input(_lib.IMAGE_YOLO, np.zeros((40, 40, 3), np.uint8), [(0, 0, 32, 32)], 32),
+        "stem": lambda: _lib.op_stem(np.zeros((40, 40, 3), np.uint8), [(0, 0, 32, 32)], 32, f32(16, 3, 3, 3), f32(16), True),
+        "stem_conv": lambda: _lib.op_stem_conv(np.zeros((40, 40, 3), np.uint8), [(0, 0, 32, 32)], 32, f32(16, 3, 3, 3), f32(16), f32(32, 16, 3, 3), f32(32)),
     }
     for name, call in calls.items():
         with pytest.raises(_lib.FfpError) as e:
@@ -174,6 +177,53 @@ def test_operator_entry_points_check_arguments_before_touching_the_device(lib):
         lambda: _lib.op_variant(_lib.OP_SPPF, 3),
         lambda: _lib.op_variant(3, 1),
     ]
+    # the image-input entries: frame 40 x 48 (h x w), one good box; each call is wrong in one way
+    fr, box, f32 = np.zeros((40, 48, 3), np.uint8), [(0, 0, 32, 32)], lambda *s: np.zeros(s, np.float32)
+    sw, sb, cw, cb = f32(16, 3, 3, 3), f32(16), f32(32, 16, 3, 3), f32(32)
+    l, u8p, ip, fp = _lib.lib(), _lib._u8p, _lib._ip, _lib._fp
+    t, o, hw = np.asarray(box, np.int32), f32(32 * 32 * 32), np.zeros(2, np.int32)
+    bad += [
+        lambda: _lib.op_image_input(_lib.IMAGE_YOLO, fr, [(0, 0, 49, 32)], 32),                  # box outside the frame
+        lambda: _lib.op_image_input(_lib.IMAGE_RTDETR, fr, [(0, 9, 48, 41)], 32),
+        lambda: _lib.op_image_input(_lib.IMAGE_SCRFD, fr, [(-1, 0, 32, 32)], (32, 32)),
+        lambda: _lib.op_image_input(_lib.IMAGE_YOLO, fr, [(8, 8, 8, 32)], 32),                   # empty box
+        lambda: _lib.op_image_input(_lib.IMAGE_YOLO, fr, box, 40),                               # imgsz not a multiple of 32
+        lambda: _lib.op_image_input(_lib.IMAGE_RTDETR, fr, box, 48),
+        lambda: _lib.op_image_input(_lib.IMAGE_SCRFD, fr, box, (64, 40)),
+        lambda: _lib.op_image_input(_lib.IMAGE_YOLO, fr, box, 0),
+        lambda: _lib.op_image_input(3, fr, box, 32),                                             # kind out of range
+        lambda: _lib.op_image_input(-1, fr, box, 32),
+        lambda: _lib.op_image_input(_lib.IMAGE_SCRFD, fr, box, (32, 32), precision=_lib.PREC_F16),
+        lambda: _lib.op_image_input(_lib.IMAGE_YOLO, fr, box, 32, precision=_lib.PREC_F32X3),
+        lambda: _lib.op_image_input(_lib.IMAGE_YOLO, fr, box, 32, chan_order=2),
+        lambda: _lib.op_image_input(_lib.IMAGE_YOLO, fr, np.zeros((0, 4), np.int32), 32),        # n <= 0
+        lambda: _lib.op_image_input(_lib.IMAGE_YOLO, np.zeros((4, 80, 3), np.uint8), [(0, 0, 80, 1)], 32),      # round(32 / 80) = 0 rows: cv2.resize would raise
+        lambda: _lib.op_image_input(_lib.IMAGE_SCRFD, fr, [(0, 0, 1, 40)], (32, 32)),
+        lambda: _lib._check(l.ffp_op_image_input(0, 0, 0, None, 40, 48, 0, 1, ip(t), 32, 32, fp(o), ip(hw), ip(hw))),     # null pointers
+        lambda: _lib._check(l.ffp_op_image_input(0, 0, 0, u8p(fr), 40, 48, 0, 1, None, 32, 32, fp(o), ip(hw), ip(hw))),
+        lambda: _lib._check(l.ffp_op_image_input(0, 0, 0, u8p(fr), 40, 48, 0, 1, ip(t), 32, 32, None, ip(hw), ip(hw))),
+        lambda: _lib._check(l.ffp_op_image_input(0, 0, 0, u8p(fr), 40, 48, 0, 1, ip(t), 32, 32, fp(o), None, ip(hw))),
+        lambda: _lib._check(l.ffp_op_image_input(0, 0, 0, u8p(fr), 40, 48, 0, -1, ip(t), 32, 32, fp(o), ip(hw), ip(hw))),
+        lambda: _lib.op_stem(fr, [(0, 0, 49, 32)], 32, sw, sb, True),
+        lambda: _lib.op_stem(fr, box, 48, sw, sb, False),
+        lambda: _lib.op_stem(fr, box, 32, f32(24, 3, 3, 3), f32(24), True),                      # cout outside 16 / 32 / 64
+        lambda: _lib.op_stem(fr, box, 32, sw, sb, True, stride=3),
+        lambda: _lib.op_stem(fr, box, 32, sw, sb, True, act=4),
+        lambda: _lib.op_stem(fr, box, 32, sw, sb, True, precision=_lib.PREC_F32X3),
+        lambda: _lib.op_stem(fr, np.zeros((0, 4), np.int32), 32, sw, sb, True),
+        lambda: _lib._check(l.ffp_op_stem(0, 0, 2, u8p(fr), 40, 48, 0, 1, ip(t), 32, fp(sw), fp(sb), 16, 2, 1, fp(o))),       # fused is 0 or 1
+        lambda: _lib._check(l.ffp_op_stem(0, 0, 1, None, 40, 48, 0, 1, ip(t), 32, fp(sw), fp(sb), 16, 2, 1, fp(o))),
+        lambda: _lib._check(l.ffp_op_stem(0, 0, 1, u8p(fr), 40, 48, 0, 1, ip(t), 32, None, fp(sb), 16, 2, 1, fp(o))),
+        lambda: _lib._check(l.ffp_op_stem(0, 0, 1, u8p(fr), 40, 48, 0, 1, ip(t), 32, fp(sw), None, 16, 2, 1, fp(o))),
+        lambda: _lib._check(l.ffp_op_stem(0, 0, 1, u8p(fr), 40, 48, 0, 1, ip(t), 32, fp(sw), fp(sb), 16, 2, 1, None)),
+        lambda: _lib.op_stem_conv(fr, [(0, 0, 32, 41)], 32, sw, sb, cw, cb),
+        lambda: _lib.op_stem_conv(fr, box, 33, sw, sb, cw, cb),
+        lambda: _lib.op_stem_conv(fr, box, 32, f32(64, 3, 3, 3), f32(64), f32(128, 64, 3, 3), f32(128)),      # the loader holds one or two 16-channel chunks
+        lambda: _lib.op_stem_conv(fr, np.zeros((0, 4), np.int32), 32, sw, sb, cw, cb),
+        lambda: _lib.op_stem_conv(fr, box, 32, sw, sb, cw, cb, chan_order=-1),
+        lambda: _lib._check(l.ffp_op_stem_conv(0, u8p(fr), 40, 48, 0, 1, ip(t), 32, fp(sw), fp(sb), 16, None, fp(cb), fp(o))),
+        lambda: _lib._check(l.ffp_op_stem_conv(0, u8p(fr), 40, 48, 0, 1, ip(t), 32, fp(sw), fp(sb), 16, fp(cw), fp(cb), None)),
+    ]
     for i, f in enumerate(bad):
         with pytest.raises(_lib.FfpError) as e:
             f()
@@ -188,6 +238,11 @@ def test_operator_entry_points_check_arguments_before_touching_the_device(lib):
         with pytest.raises(_lib.FfpError) as e:
             _lib.op_conv2d_views(z(4, 4, 64), 0, np.zeros((32, 64, 1, 1)), None, z(4, 4, 32), 0, gate=[1], gate_prev=[0])
         assert "no HIP device" in str(e.value)
+        for call in (lambda: _lib.op_image_input(_lib.IMAGE_SCRFD, fr, box, (64, 32)), lambda: _lib.op_stem(fr, box, 32, sw, sb, False),
+                     lambda: _lib.op_stem_conv(fr, box, 32, sw, sb, cw, cb)):
+            with pytest.raises(_lib.FfpError) as e:
+                call()
+            assert e.value.code == 2 and "no HIP device" in str(e.value)
 
 
 def test_weights_container_roundtrip():
