@@ -46,6 +46,7 @@ _SIGS = {
     "ffp_last_error": (C.c_char_p, []),
     "ffp_version": (C.c_int, []),
     "ffp_device_count": (C.c_int, [_p(C.c_int)]),
+    "ffp_switches": (C.c_int, [C.c_char_p, C.c_size_t]),
     "ffp_slice_bboxes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _p(C.c_int32), C.c_int, _p(C.c_int32)]),
     "ffp_tile_chunks": (C.c_int, [C.c_int, C.c_int, _p(C.c_int32), C.c_int, _p(C.c_int32)]),
     "ffp_letterbox_geometry": (C.c_int, [C.c_int, C.c_int, C.c_int, _p(C.c_int32)]),
@@ -277,6 +278,20 @@ def device_count() -> int:
     n = C.c_int(0)
     _check(lib().ffp_device_count(C.byref(n)))
     return n.value
+
+
+def switches() -> dict:
+    """The library's environment switches as this process reads them (csrc/switches.hpp), by name:
+    {"value", "source" ("env" | "default"), "when" ("once" | "live"), "accepts", "effect"}. Needs no device.
+    FfpError(FFP_ERR_ARG) names the variable whose value its rule refuses."""
+    buf = C.create_string_buffer(1 << 16)
+    _check(lib().ffp_switches(buf, len(buf)))
+    out = {}
+    for line in buf.value.decode("utf-8").splitlines():
+        head, source, when, accepts, effect = line.split("\t")
+        name, value = head.split("=", 1)
+        out[name] = {"value": value, "source": source, "when": when, "accepts": accepts, "effect": effect}
+    return out
 
 
 def _fp(a: np.ndarray):

@@ -174,6 +174,12 @@ def build_plan_cache_check(verbose: bool = True) -> str:
     return _build_host_check("plan_cache_host_check", "plan_cache_host_check.cpp", ["plan_cache.hpp"], verbose)
 
 
+def build_switches_check(verbose: bool = True) -> str:
+    """The environment-switch table (csrc/switches.hpp, no HIP in it): every row's accepted and refused values, read-once against live rows, the
+    unknown-name warning."""
+    return _build_host_check("switches_host_check", "switches_host_check.cpp", ["switches.hpp"], verbose)
+
+
 if __name__ == "__main__":
     if "--asan" in sys.argv:
         build_asan()
@@ -183,6 +189,8 @@ if __name__ == "__main__":
         build_dw_bound_check()
     elif "--plan-cache-check" in sys.argv:
         build_plan_cache_check()
+    elif "--switches-check" in sys.argv:
+        build_switches_check()
     elif "--variant" in sys.argv:
         build_variant(sys.argv[sys.argv.index("--variant") + 1])
     else:

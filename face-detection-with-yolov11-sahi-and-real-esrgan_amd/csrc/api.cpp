@@ -42,6 +42,14 @@ int ffp_device_count(int* out_n) {
   FFP_API_END
 }
 
+int ffp_switches(char* out, size_t cap) {
+  FFP_API_BEGIN
+  const std::string text = ffp::switches_report(ffp::sw_live());
+  FFP_CHECK(out && cap > text.size(), FFP_ERR_ARG, "ffp_switches: the report needs %zu bytes", text.size() + 1);
+  memcpy(out, text.c_str(), text.size() + 1);
+  FFP_API_END
+}
+
 int ffp_slice_bboxes(int H, int W, int sh, int sw, float oh, float ow, int32_t* out_xyxy, int cap, int32_t* out_n) {
   FFP_API_BEGIN
   FFP_CHECK(out_n, FFP_ERR_ARG, "null output");

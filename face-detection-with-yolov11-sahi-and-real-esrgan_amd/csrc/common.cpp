@@ -276,11 +276,10 @@ const int* Level::up2_map(const Level* src, hipStream_t st) {
 
 namespace ffp {
 
-hipStream_t create_engine_stream(const char* env_name) {
+hipStream_t create_engine_stream(const CuRange& mask_range) {
   hipStream_t st = nullptr;
-  const char* e = env_name ? getenv(env_name) : nullptr;
-  int lo = 0, hi = 0;
-  if (e && sscanf(e, "%d-%d", &lo, &hi) == 2 && lo >= 0 && hi > lo && hi <= 32) {
+  const int lo = mask_range.lo, hi = mask_range.hi;
+  if (hi > lo) {
     hipDeviceProp_t prop;
     int dev = 0;
     FFP_HIP(hipGetDevice(&dev));
@@ -289,8 +288,7 @@ hipStream_t create_engine_stream(const char* env_name) {
     std::vector<uint32_t> mask((ncu + 31) / 32, 0u);
     // bit i of the mask = CU i in the runtime's enumeration; both plausible enumerations (XCD-major, CU-major) are covered by setting the
     // range in every group of 32 AND the matching interleaved positions is not possible at once: FFP_CU_MASK_ORDER=1 selects CU-major
-    const char* ord = getenv("FFP_CU_MASK_ORDER");
-    const bool cu_major = ord && ord[0] == '1';
+    const bool cu_major = sw().cu_mask_order;
     for (int i = 0; i < ncu; ++i) {
       const int cu_in_xcd = cu_major ? i / 8 : i % 32;
       if (cu_in_xcd >= lo && cu_in_xcd < hi) mask[i / 32] |= 1u << (i % 32);
@@ -300,12 +298,6 @@ hipStream_t create_engine_stream(const char* env_name) {
   }
   FFP_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
   return st;
-}
-
-size_t det_plan_budget() {
-  // at least one byte: FFP_DET_PLAN_GIB=0 keeps only the plan in use, it does not lift the budget (PlanCache reads 0 as "none")
-  static const size_t budget = [] { const char* e = getenv("FFP_DET_PLAN_GIB"); const double g = e ? atof(e) : 64.0; return std::max<size_t>(1, (size_t)(g * (1ull << 30))); }();
-  return budget;
 }
 
 }  // namespace ffp

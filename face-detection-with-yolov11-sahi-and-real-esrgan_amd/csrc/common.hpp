@@ -14,15 +14,13 @@
 #include <vector>
 
 #include "../../include/ffp.h"
+#include "switches.hpp"
 
 namespace ffp {
 
-// An engine's stream. env `name` (FFP_DET_CU_MASK / FFP_SR_CU_MASK, experiment): "lo-hi" = only CUs lo..hi-1 of EVERY XCD run this stream's
+// An engine's stream. mask (sw().det_cu_mask / sw().sr_cu_mask, experiment): "lo-hi" = only CUs lo..hi-1 of EVERY XCD run this stream's
 // kernels (hipExtStreamCreateWithCUMask) — a spatial split of the card between the detector and the enhancer.
-hipStream_t create_engine_stream(const char* env_name);
-
-// Byte budget of the resident plans of one YOLO11 or SCRFD handle (PlanCache's max_bytes): env FFP_DET_PLAN_GIB, default 64, read once per process.
-size_t det_plan_budget();
+hipStream_t create_engine_stream(const CuRange& mask);
 
 
 // ---- errors ---------------------------------------------------------------------------------------------
@@ -32,6 +30,11 @@ struct Error : std::runtime_error {
 };
 void set_last_error(const std::string& m);
 [[noreturn]] void fail(int code, const char* fmt, ...);
+
+// The environment switches (switches.hpp: the table, the value rules, when each row is read). A value outside its rule is FFP_ERR_ARG from every call
+// that reads a switch, for as long as the environment stays that way.
+inline const Switches& sw() try { return switches_once(); } catch (const SwitchError& e) { throw Error(FFP_ERR_ARG, e.what()); }
+inline Switches sw_live() try { return switches_now(); } catch (const SwitchError& e) { throw Error(FFP_ERR_ARG, e.what()); }      // LIVE rows read again
 
 #define FFP_HIP(expr)                                                                              \
   do {                                                                                             \
@@ -67,7 +70,7 @@ struct DevBuf {
     if (bytes == 0) bytes = 16;
     // FFP_ALLOC_FLAGS (experiment): 3 = hipDeviceMallocUncached for buffers of at least 1 MiB (activations, tables; MTYPE_UC: nothing of them is ever dirty in
     // an L2, so a kernel boundary has nothing to write back — for this stream or for the one running beside it), 1 = hipDeviceMallocFinegrained
-    static const int flags = [] { const char* e = getenv("FFP_ALLOC_FLAGS"); return e ? atoi(e) : 0; }();
+    const int flags = sw().alloc_flags;
     if (flags && bytes >= (1u << 20)) FFP_HIP(hipExtMallocWithFlags(&p, bytes, (unsigned)flags));
     else FFP_HIP(hipMalloc(&p, bytes));
     n = bytes;

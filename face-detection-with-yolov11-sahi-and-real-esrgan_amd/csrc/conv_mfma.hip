@@ -12,6 +12,8 @@
 // blockIdx is remapped so that the n-blocks of one pixel tile and neighbouring tiles share an XCD (L2 reuse of the
 // input tile); the mapping only affects speed.
 #include <cstdlib>
+#include <map>
+#include <mutex>
 #include <type_traits>
 
 #include "conv_args.hpp"
@@ -950,19 +952,6 @@ template <class Fn> auto with_family(const ConvOp& op, Fn&& fn) {
 
 }  // namespace
 
-// 256 zero bytes per device: where the LDS-DMA loader of conv_rows.hip reads conv zero padding from
-static const void* zero_block() {
-  static std::map<int, DevBuf> blocks;
-  int dev = 0;
-  FFP_HIP(hipGetDevice(&dev));
-  auto it = blocks.find(dev);
-  if (it == blocks.end()) {
-    DevBuf b(256);
-    FFP_HIP(hipMemset(b.p, 0, 256));
-    it = blocks.emplace(dev, std::move(b)).first;
-  }
-  return it->second.p;
-}
 
 // ---- stem fused into the first MFMA conv (conv_mfma_kernel<X3, 3, 2, 4, 1, 1, 2, 16, true>) ------------------------------------
 namespace {
@@ -992,8 +981,7 @@ __global__ void stem_pack_kernel(const float* __restrict__ w, int cout, int flip
 bool stem_conv_eligible(const ConvOp& stem, const ConvOp& conv) {
   const PackedConv& ps = *stem.pc;
   const PackedConv& pc = *conv.pc;
-  static const bool off = [] { const char* e = getenv("FFP_NO_STEM_FUSE"); return e && e[0] == '1'; }();
-  return !off && conv_direct_eligible(stem) && ps.dt == F32 && stem.stride == 2 && stem.act == ACT_SILU && (ps.cout == 32 || ps.cout == 16) && ps.w_direct.p != nullptr &&
+  return !sw().no_stem_fuse && conv_direct_eligible(stem) && ps.dt == F32 && stem.stride == 2 && stem.act == ACT_SILU && (ps.cout == 32 || ps.cout == 16) && ps.w_direct.p != nullptr &&
          pc.split && pc.dt == F32 && pc.k == 3 && conv.stride == 2 && pc.cin == ps.cout && pc.cout_pad == 2 * ps.cout && !conv.up && !conv.has_res1 && !conv.has_res2 &&
          !conv.has_up2 && conv.in.lvl == stem.out.lvl && conv.in.amax != nullptr && !conv.out.lvl->capacity();
 }
@@ -1025,10 +1013,17 @@ void launch_stem_conv(const uint8_t* d_frame, int H, int W, const DevBuf& d_imgs
   FFP_HIP(hipGetLastError());
 }
 
-void conv_kernels_init() {
-  (void)zero_block();
-  static bool done = false;
-  if (done) return;
+// What the conv kernels need once per DEVICE, under one lock: their dynamic-LDS limits raised (hipFuncSetAttribute on every instantiation) and 256 zero
+// bytes, where the LDS-DMA loader of conv_rows.hip reads conv zero padding from. The current device's record is made the first time it is asked for
+// (std::map: a record's address holds while others are added).
+static const void* conv_device_zeros() {
+  static std::mutex mu;
+  static std::map<int, DevBuf> zeros;
+  int dev = 0;
+  FFP_HIP(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = zeros.find(dev);
+  if (it != zeros.end()) return it->second.p;
   conv_rows_init();
   conv_rows16_init();
   conv_rows16pc_init();
@@ -1041,8 +1036,12 @@ void conv_kernels_init() {
   Family<X3, 1, 1>::init(); Family<X3, 3, 1>::init(); Family<X3, 3, 2>::init();
   FFP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_kernel<X3, 3, 2, 4, 1, 1, 2, 16, true>), hipFuncAttributeMaxDynamicSharedMemorySize, StemG::LDS));
   FFP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_kernel<X3, 3, 2, 4, 1, 1, 1, 16, true>), hipFuncAttributeMaxDynamicSharedMemorySize, StemGn::LDS));
-  done = true;
+  DevBuf b(256);
+  FFP_HIP(hipMemset(b.p, 0, 256));
+  return zeros.emplace(dev, std::move(b)).first->second.p;      // last: a device whose set-up threw has no record and is set up again
 }
+
+void conv_kernels_init() { (void)conv_device_zeros(); }
 
 ConvArgs make_conv_args(const ConvOp& op) {
   const PackedConv& pc = *op.pc;
@@ -1121,7 +1120,7 @@ ConvArgs make_conv_args(const ConvOp& op) {
   }
   a.dbg = op.dbg;
   a.force_shape = op.force_shape;
-  a.zeros = zero_block();
+  a.zeros = conv_device_zeros();
   if (pc.k == 1) FFP_CHECK(!op.out.lvl->capacity(), FFP_ERR_ARG, "conv %s: 1x1 convs are not built for capacity-mode levels", pc.name.c_str());
   if (pc.k == 1) FFP_CHECK(op.in.lvl->total_px == op.out.lvl->total_px, FFP_ERR_ARG, "conv %s: 1x1 levels differ", pc.name.c_str());
   return a;

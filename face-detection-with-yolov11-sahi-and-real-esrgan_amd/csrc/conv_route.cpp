@@ -36,16 +36,6 @@ constexpr bool table_in_order() {
 static_assert(table_in_order(), "conv shape table: row i holds shape i");
 static_assert(SHAPE_COUNT <= 32 && SHAPE_DWPW >= 32, "forceable shapes fit a 32-bit candidate mask; route-only numbers lie above them");
 
-bool env_is(const char* name, char c) {
-  const char* e = getenv(name);
-  return e && e[0] == c;
-}
-struct Switches { bool rows16, rows16_res, rows16_pc, pw, k3d; };
-const Switches& switches() {      // A/B aids: read at the first routed conv of the process
-  static const Switches s{!env_is("FFP_ROWS16", '0'), env_is("FFP_ROWS16_RES", '1'), env_is("FFP_ROWS16_PC", '1'), !env_is("FFP_PW", '0'), !env_is("FFP_K3D", '0')};
-  return s;
-}
-
 // can `family` run the op at `shape` (a number of that family)
 bool family_runs(ConvFamily family, int shape, const ConvOp& op, const ConvArgs& a) {
   switch (family) {
@@ -88,10 +78,9 @@ ConvRoute conv_route(const ConvOp& op, const ConvArgs& a) {
     FFP_CHECK(family_runs(s->family, s->shape, op, a), FFP_ERR_ARG, "conv %s: %s shape %d cannot run this op", op.pc->name.c_str(), s->family_name, s->shape);
     return {s->family, s->shape};
   }
-  const Switches& sw = switches();
-  if (sw.rows16 && conv_rows16_eligible(op, a, SHAPE_ROWS16)) {
-    if (sw.rows16_pc && a.dbg == 0) return {F::ROWS16PC, SHAPE_ROWS16PC};
-    if (sw.rows16_res && conv_rows16_eligible(op, a, SHAPE_ROWS16_RES)) return {F::ROWS16, SHAPE_ROWS16_RES};
+  if (sw().rows16 && conv_rows16_eligible(op, a, SHAPE_ROWS16)) {
+    if (sw().rows16_pc && a.dbg == 0) return {F::ROWS16PC, SHAPE_ROWS16PC};
+    if (sw().rows16_res && conv_rows16_eligible(op, a, SHAPE_ROWS16_RES)) return {F::ROWS16, SHAPE_ROWS16_RES};
     return {F::ROWS16, SHAPE_ROWS16};
   }
   if (conv_rows_eligible(op, a, SHAPE_ROWS)) return {F::ROWS, SHAPE_ROWS};
@@ -99,8 +88,7 @@ ConvRoute conv_route(const ConvOp& op, const ConvArgs& a) {
 }
 
 unsigned conv_candidates(const ConvOp& op, const ConvArgs& a) {
-  const Switches& sw = switches();
-  return conv_generic_mask(op, a) | (sw.pw ? conv_pw_mask(op, a) : 0u) | (sw.k3d ? conv_k3d_mask(op, a) : 0u);
+  return conv_generic_mask(op, a) | (sw().pw ? conv_pw_mask(op, a) : 0u) | (sw().k3d ? conv_k3d_mask(op, a) : 0u);
 }
 
 void launch_conv(const ConvOp& op, hipStream_t st) {
@@ -164,8 +152,7 @@ int conv_tune(const ConvOp& op, hipStream_t st) {
     const float t = time_shape(shape, iters);
     if (shape == heur) heur_t = t;
     if (best < 0 || t < best_t) { best = shape; best_t = t; }
-    static const bool log = [] { const char* e = getenv("FFP_TUNE_LOG"); return e && e[0] == '1'; }();       // every candidate's time, one line per (layer, shape)
-    if (log) {
+    if (sw().tune_log) {      // every candidate's time, one line per (layer, shape)
       ConvOp o = op;
       o.force_shape = shape;
       fprintf(stderr, "[tune] %-28s %4d->%4d k%d s%d px %9lld  shape %2d %-22s %9.1f us%s\n", pc.name.c_str(), pc.cin_real, pc.cout, pc.k, op.stride,

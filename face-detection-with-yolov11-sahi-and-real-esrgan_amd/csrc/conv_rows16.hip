@@ -404,7 +404,7 @@ void launch_conv_rows16(ConvArgs& a, int shape, const PackedConv& pc, Level* out
   a.ntiles_host = n_tiles;
   a.n_nblk = a.ntiles32;
   const bool res = shape == SHAPE_ROWS16_RES;
-  static const int ws_env = [] { const char* e = getenv("FFP_ROWS16_WS"); return e ? atoi(e) : 0; }();      // experiment: workgroups per XCD (64 = two per CU)
+  const int ws_env = sw().rows16_ws;      // experiment: workgroups per XCD (64 = two per CU)
   const unsigned grid = rows16_grid(n_tiles, a.n_nblk, ws_env > 0 ? ws_env : (res ? 32 : 64), G::TCAP, "rows16");      // resident weights: one workgroup per CU
   r16_for_mask<>(a.dbg, res, false, &a, grid, res ? G::res_lds(a.cin >> 5) : G::LDS, st);
 }

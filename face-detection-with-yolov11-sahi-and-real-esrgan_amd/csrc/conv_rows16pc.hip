@@ -234,7 +234,7 @@ void launch_conv_rows16pc(ConvArgs& a, const PackedConv& pc, Level* out_lvl, hip
   a.ntiles_host = n_tiles;
   a.n_nblk = a.ntiles32;
   const unsigned grid = rows16_grid(n_tiles, a.n_nblk, 32, G::TCAP, "rows16pc");          // 8 x 32 workgroups: one per CU
-  static const int ns = [] { const char* e = getenv("FFP_ROWS16_PC_SETS"); return e ? atoi(e) : 2; }();       // 4 sets (five chunks ahead) measured SLOWER than 2: 0.68-0.85x vs 0.78-0.95x of conv_rows16_kernel
+  const int ns = sw().rows16_pc_sets;       // 4 sets (five chunks ahead) measured SLOWER than 2: 0.68-0.85x vs 0.78-0.95x of conv_rows16_kernel
   if (ns == 2) hipLaunchKernelGGL(conv_rows16pc_kernel<2>, dim3(grid), dim3(512), G::LDS, st, a);
   else hipLaunchKernelGGL(conv_rows16pc_kernel<4>, dim3(grid), dim3(512), G::LDS, st, a);
 }

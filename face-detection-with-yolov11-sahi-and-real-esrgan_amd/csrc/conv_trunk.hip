@@ -691,13 +691,6 @@ void conv_trunk_init() {
   FFP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_trunk_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, TG::LDS));
 }
 
-bool conv_trunk_enabled() {
-  // opt-in (FFP_TRUNK=1 or ffp_sr_set_fused_body): measured on MI355X it is bit-identical to, and 6 % slower than, the per-layer launches at 320 crops
-  // and 2x slower at 32 (profiles/r04_sr_batch_sweep.txt) — the shipped default stays the faster path
-  static const bool on = [] { const char* e = getenv("FFP_TRUNK"); return e && e[0] == '1'; }();
-  return on;
-}
-
 bool conv_trunk_layer_ok(const ConvOp& op) {
   const PackedConv& pc = *op.pc;
   const int cpl = 8;
@@ -755,7 +748,7 @@ void TrunkPlan::launch(hipStream_t st, int dbg) {
   a.queue = sync.as<unsigned>();
   a.done = sync.as<unsigned>() + 16;
   a.dbg = dbg;
-  static const bool dump = [] { const char* e = getenv("FFP_TRUNK_DUMP"); return e && e[0] == '1'; }();
+  const bool dump = sw().trunk_dump;
   // one workgroup per CU; capacity-mode levels launch for the capacity (workgroups beyond the batch's items find the queue empty)
   const long long items = (long long)n_tiles * n_blocks;
   const unsigned grid = (unsigned)std::min<long long>(256, items);

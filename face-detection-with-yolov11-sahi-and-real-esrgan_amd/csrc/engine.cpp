@@ -298,11 +298,6 @@ Plan::~Plan() {
   for (hipStream_t q : lane_streams) (void)hipStreamDestroy(q);
 }
 
-int Plan::lanes_env() {
-  static const int m = [] { const char* e = getenv("FFP_LANES"); return e ? atoi(e) : -1; }();
-  return m;
-}
-
 void Plan::fork(int lane) {
   if (!lanes_enabled() || lane <= 0) return;
   while ((int)lane_streams.size() < lane) {
@@ -346,15 +341,9 @@ void Plan::run_steps(hipStream_t st, bool use_lanes) {
   }
 }
 
-static bool graphs_enabled() {
-  static const bool on = [] { const char* e = getenv("FFP_NO_GRAPH"); return !(e && e[0] == '1'); }();
-  return on;
-}
-
 void Plan::tune(hipStream_t st) {
   tuned = true;
-  static const bool off = [] { const char* e = getenv("FFP_NO_TUNE"); return e && e[0] == '1'; }();
-  if (off) return;
+  if (sw().no_tune) return;
   for (Step& s : steps) {
     if (!s.is_conv || s.trunk || s.conv->force_shape >= 0) continue;
     const int best = conv_tune(*s.conv, st);
@@ -382,7 +371,7 @@ void Plan::execute(hipStream_t st, ConvProfile* prof) {
     }
     return;
   }
-  if (runs > 0 && graph_ok && graphs_enabled()) {
+  if (runs > 0 && graph_ok && !sw().no_graph) {
     if (!gexec) {
       // first eager run has built every lazily created table; capture the identical sequence now
       CaptureExclusive only_me;

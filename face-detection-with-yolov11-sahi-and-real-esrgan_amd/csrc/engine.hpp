@@ -130,8 +130,7 @@ struct Plan {
   // own lane (detector-only deployments), 2 one lane per head level, 3 head level 0 only. The owner sets it before building;
   // env FFP_LANES overrides it for A/B runs.
   int lanes = 0;
-  static int lanes_env();                                // FFP_LANES or -1
-  int lane_mode() const { return lanes_env() >= 0 ? lanes_env() : lanes; }
+  int lane_mode() const { return sw().lanes >= 0 ? sw().lanes : lanes; }
   bool lanes_enabled() const { return lane_mode() != 0; }
   void fork(int lane);                                   // no-op when lanes are disabled (the steps then run in issue order on lane 0)
   void join(int lane);

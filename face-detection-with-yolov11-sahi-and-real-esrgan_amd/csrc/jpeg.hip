@@ -746,12 +746,6 @@ void jpeg_reconstruct_device(const JpegScan& s, JpegDecodeWs& ws, unsigned char*
   FFP_HIP(hipGetLastError());
 }
 
-// FFP_JPEG_HOST_HUFFMAN=1: entropy decoding on the host for every file (round-2 behaviour; A/B and the fallback's own tests)
-static bool host_huffman_forced() {
-  static const bool v = [] { const char* e = std::getenv("FFP_JPEG_HOST_HUFFMAN"); return e && e[0] == '1'; }();
-  return v;
-}
-
 void jpeg_decode_to_device(const unsigned char* data, long long n, unsigned char* d_out, long long stride, long long cap, int bgr, hipStream_t st, int* out_h, int* out_w) {
   JpegScan s;
   JpegHead head;
@@ -764,7 +758,7 @@ void jpeg_decode_to_device(const unsigned char* data, long long n, unsigned char
   try {
     ws->ensure(s);
     bool done = false;
-    if (!host_huffman_forced()) {
+    if (!sw().jpeg_host_huffman) {      // FFP_JPEG_HOST_HUFFMAN=1: entropy decoding on the host for every file (round-2 behaviour; A/B and the fallback's own tests)
       // the whole decode is queued in one go — entropy decoding (jpeg_huff.hip) and reconstruction — and checked after ONE synchronisation
       if (jpeg_huff_decode_async(data, n, s, head, *ws, st)) {
         jpeg_reconstruct_device(s, *ws, d_out, stride, bgr, st, false);

@@ -51,7 +51,7 @@ void launch_conv(const ConvOp& op, hipStream_t st);      // on the kernel conv_r
 // image-input 3x3 convs (3 real channels: YOLO stem, ESRGAN conv_first) as a direct VALU kernel (ops_misc.hip)
 bool conv_direct_eligible(const ConvOp& op);
 void launch_conv_direct(const ConvOp& op, hipStream_t st);
-void conv_kernels_init();   // raise dynamic-LDS limits once per process
+void conv_kernels_init();   // raise dynamic-LDS limits and make the zero block, once per device (the current one)
 // times every shape that can run a conv the automatic route gives to the generic kernel — its own shapes and those of conv_pw / conv_k3d
 // (conv_candidates, conv_route.hpp) — on the op's own buffers; returns the fastest shape number, the heuristic's unless another is > 3 % faster,
 // or -1 when the op has a single candidate, goes to a kernel with one shape (direct, rows16, rows) or already has a forced shape

@@ -658,7 +658,7 @@ void launch_dwconv(const DwConvOp& op, hipStream_t st) {
                 op.out.coff % 4 == 0 && (!op.has_res || (op.res.cs % 4 == 0 && op.res.coff % 4 == 0)),
             FFP_ERR_ARG, "dwconv %s: channel counts/offsets must be multiples of 4", pc.name.c_str());
   const int4* tab = op.out.lvl->d_tab.as<int4>();
-  static const bool col_walk = [] { const char* e = getenv("FFP_DW_STRIP"); return !(e && e[0] == '1'); }();      // FFP_DW_STRIP=1: the strip kernel (A/B aid)
+  const bool col_walk = !sw().dw_strip;      // FFP_DW_STRIP=1: the strip kernel (A/B aid)
   const int amax_img = op.out.amax && op.out.amax_n > 1 ? 1 : 0;
   FFP_CHECK(op.force >= 0 && op.force <= 2, FFP_ERR_ARG, "dwconv: unknown kernel variant %d", op.force);
   FFP_CHECK(op.force != 1 || !op.out.lvl->capacity(), FFP_ERR_ARG, "dwconv: the column-walk kernel needs an exact-mode level");
@@ -770,7 +770,7 @@ void launch_psa_attention(const TView& qkv, const TView& out, int nh, int kd, in
   int nmax = 0;
   for (int i = 0; i < qkv.lvl->n; ++i) nmax = std::max(nmax, qkv.lvl->h[i] * qkv.lvl->w[i]);
   const float scale = 1.0f / sqrtf((float)kd);
-  static const bool valu = [] { const char* e = getenv("FFP_ATTN_VALU"); return e && e[0] == '1'; }();
+  const bool valu = sw().attn_valu;
   const bool aligned = qkv.cs % 4 == 0 && qkv.coff % 4 == 0 && out.cs % 4 == 0 && out.coff % 4 == 0;
   FFP_CHECK(force >= 0 && force <= 2, FFP_ERR_ARG, "psa attention: unknown kernel variant %d", force);
   FFP_CHECK(force != 1 || aligned, FFP_ERR_ARG, "psa attention: the MFMA kernel needs views aligned to 4 channels");

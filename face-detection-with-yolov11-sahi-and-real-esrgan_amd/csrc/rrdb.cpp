@@ -28,7 +28,7 @@ SrEngine::SrEngine(const void* weights, size_t nbytes, int scale, int num_block,
   FFP_CHECK(device >= 0 && device < ndev, FFP_ERR_ARG, "device %d of %d", device, ndev);
   scale_ = scale; num_block_ = num_block; device_ = device; dt_ = half ? F16 : F32;
   FFP_HIP(hipSetDevice(device_));
-  st_ = create_engine_stream("FFP_SR_CU_MASK");
+  st_ = create_engine_stream(sw().sr_cu_mask);
   for (auto& e : ev_) FFP_HIP(hipEventCreate(&e));
   conv_kernels_init();
   WeightFile wf;
@@ -42,7 +42,9 @@ SrEngine::SrEngine(const void* weights, size_t nbytes, int scale, int num_block,
   const int cin_first = 3 * (scale_ == 2 ? 4 : 1);
   FFP_CHECK(conv("conv_first")->cin_real == cin_first && conv("conv_first")->cout == 64, FFP_ERR_WEIGHTS,
             "conv_first is %d->%d, scale %d expects %d->64", conv("conv_first")->cin_real, conv("conv_first")->cout, scale_, cin_first);
-  fused_body_ = dt_ == F16 && conv_trunk_enabled();
+  // opt-in (FFP_TRUNK=1 or ffp_sr_set_fused_body): measured on MI355X it is bit-identical to, and 6 % slower than, the per-layer launches at 320 crops
+  // and 2x slower at 32 (profiles/r04_sr_batch_sweep.txt) — the shipped default stays the faster path
+  fused_body_ = dt_ == F16 && sw().trunk;
   for (const auto& kv : convs_) weight_bytes_ += kv.second.w.n + kv.second.w16.n + kv.second.bias.n + kv.second.w_direct.n;
 }
 

@@ -29,7 +29,7 @@ ScrfdEngine::ScrfdEngine(const void* onnx_bytes, size_t nbytes, int n, int devic
   device_ = device;
   split_ = precision == FFP_PREC_F32X3;
   FFP_HIP(hipSetDevice(device_));
-  st_ = create_engine_stream("FFP_DET_CU_MASK");
+  st_ = create_engine_stream(sw().det_cu_mask);
   conv_kernels_init();
 }
 

@@ -113,7 +113,7 @@ class ScrfdEngine {
   void build_plan(ScrfdPlan& P, int n, int det_w, int det_h);
 
   onnx::Graph graph_;
-  PlanCache<std::vector<int>, ScrfdPlan> plans_{8, det_plan_budget(), [this] { FFP_HIP(hipSetDevice(device_)); FFP_HIP(hipStreamSynchronize(st_)); }};
+  PlanCache<std::vector<int>, ScrfdPlan> plans_{8, sw().det_plan_bytes(), [this] { FFP_HIP(hipSetDevice(device_)); FFP_HIP(hipStreamSynchronize(st_)); }};
   int device_ = 0;
   bool split_ = false;
   hipStream_t st_ = nullptr;

@@ -97,7 +97,7 @@ class SrEngine {
   void enhance_dev(const uint8_t* d_in, uint8_t* d_out, const std::vector<SrImage>& imgs, int tile, int tile_pad, int pre_pad, bool wait = true);
   void wait_done();
   // the body (every conv of the residual dense blocks) as ONE persistent launch (conv_trunk.hip) or one launch per layer; bit-identical
-  // results either way. Default: fused in fp16 unless FFP_TRUNK=0. Changing it drops the resident plans.
+  // results either way. Default: per-layer launches; FFP_TRUNK=1 makes the fused launch the default of fp16 handles. Changing it drops the resident plans.
   void set_fused_body(bool on);
   bool fused_body() const { return fused_body_; }
   void drop_plans() { plans_.clear(); }      // release every resident plan (waits for the batch in flight and the stream first)

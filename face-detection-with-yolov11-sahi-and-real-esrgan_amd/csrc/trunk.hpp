@@ -44,7 +44,6 @@ struct TrunkPlan {
 };
 
 bool conv_trunk_layer_ok(const ConvOp& op);     // the conv can be a layer of a fused run (3x3 s1 fp16, cin % 32 == 0, cout 32 or 64, one level)
-bool conv_trunk_enabled();                      // FFP_TRUNK=0: one launch per layer (A/B aid, and the fused launch's parity oracle)
 void conv_trunk_init();
 
 }  // namespace ffp

@@ -43,7 +43,7 @@ DetEngine::DetEngine(const void* weights, size_t nbytes, int arch, int nc, int n
   device_ = device; nc_ = nc; nkpt_ = nkpt; scale_ = (char)arch; dt_ = precision == FFP_PREC_F16 ? F16 : F32;
   split_ = precision == FFP_PREC_F32X3;
   FFP_HIP(hipSetDevice(device_));
-  st_ = create_engine_stream("FFP_DET_CU_MASK");
+  st_ = create_engine_stream(sw().det_cu_mask);
   for (auto& e : ev_) FFP_HIP(hipEventCreate(&e));
   conv_kernels_init();
   WeightFile wf;
@@ -99,8 +99,7 @@ void DetEngine::build_plan(DetPlan& P, const std::vector<int>& hs, const std::ve
   const int n = (int)hs.size();
   // scaled split: a max-|value| slot per (buffer, image), so that an item's bits do not depend on its batch mates (FFP_AMAX_PER_BUFFER=1:
   // round 2's one slot per buffer, A/B aid); the 1x1 kernels find a fragment's image through Level::frag_img, hence the 32-pixel alignment
-  static const bool per_buffer = [] { const char* e = getenv("FFP_AMAX_PER_BUFFER"); return e && e[0] == '1'; }();
-  P.per_image_amax = split_ && !per_buffer;
+  P.per_image_amax = split_ && !sw().amax_per_buffer;
   P.px_align = (P.per_image_amax || P.gate) ? 32 : 1;        // the gated 1x1 convs find a fragment's image the same way
   for (int l = 0; l < 6; ++l) {
     std::vector<int> h(n), w(n);
@@ -116,7 +115,7 @@ void DetEngine::build_plan(DetPlan& P, const std::vector<int>& hs, const std::ve
   const int c64 = ch(64), c128 = ch(128), c256 = ch(256), c512 = ch(512), c1024 = ch(1024);
   const DType T = dt_;
 
-  static const bool fold_up = !getenv("FFP_NO_UPFOLD");
+  const bool fold_up = !sw().no_upfold;
   auto cv = [&](const std::string& name, const TView& in, const TView& out, int stride, int act, const TView* res = nullptr, const TView* up2 = nullptr,
                 const int* gate = nullptr) {
     ConvOp o;
@@ -196,7 +195,7 @@ void DetEngine::build_plan(DetPlan& P, const std::vector<int>& hs, const std::ve
     m1.pc = conv("model.1.conv"); m1.in = x0; m1.out = x1; m1.stride = 2; m1.act = ACT_SILU;
     FFP_CHECK(m1.pc->cin == x0.C && m1.pc->cout == x1.C, FFP_ERR_WEIGHTS, "model.1.conv: weights are %d->%d, graph expects %d->%d", m1.pc->cin,
               m1.pc->cout, x0.C, x1.C);
-    const bool direct = conv_direct_eligible(o) && !getenv("FFP_NO_FUSED_STEM");
+    const bool direct = conv_direct_eligible(o) && !sw().no_fused_stem;
     // the image-input conv's output bound is known from the weights alone (inputs in [0, 1], |SiLU(v)| <= max(|v|, 0.279)), so the
     // first MFMA conv finds its input's exponent without a pass over the data
     P.set_amax_bound(x0, std::max(o.pc->out_bound, 0.3f));
@@ -338,13 +337,13 @@ void DetEngine::build_plan(DetPlan& P, const std::vector<int>& hs, const std::ve
     // Two launches instead of five (conv_dwpw.hip): each depthwise conv runs inside the loader of the 1x1 conv behind it, and with nc <= 4 the closing 1x1
     // inside the second one's epilogue; d1, d2 and e2 are never stored. A never-stored tensor has no max-|value| slot: its split takes its exponent from a
     // per-image bound (dw_bound.hpp). FFP_CLS_FUSE=0: the five ops. Read per plan, so that one process can build both.
-    const char* fuse_env = getenv("FFP_CLS_FUSE");
+    const bool cls_fuse = sw_live().cls_fuse;
     const std::string n0 = hp + ".cv3." + ls + ".0", n1 = hp + ".cv3." + ls + ".1", n2 = hp + ".cv3." + ls + ".2";
     // e1 and e2 start without storage: the fused ops are described first and the kernel is asked (its layout, and that x, e1 and the head record each fit
     // one buffer resource: a level past 2 GiB, e.g. 5-frame groups at imgsz 1024, does not); a level it cannot run gets the five ops below, unchanged
     TView e1 = P.alloc_virtual(lv, c3, T), e2 = P.alloc_virtual(lv, c3, T);
     bool fused = false;
-    if (split_ && P.per_image_amax && !(fuse_env && fuse_env[0] == '0' && !fuse_env[1]) && chs[l] % 16 == 0 && c3 == 128) {
+    if (split_ && P.per_image_amax && cls_fuse && chs[l] % 16 == 0 && c3 == 128) {
       const bool fin = dense_.count(n2) != 0;
       ConvOp t1, t2;
       t1.pc = conv(n0 + ".1.conv"); t1.dw = conv(n0 + ".0.conv"); t1.dw_act = ACT_SILU;
@@ -511,12 +510,6 @@ DetPlan* DetEngine::plan_for(const std::vector<TileGeom>& g) {
   });
 }
 
-int DetEngine::reuse_env() {
-  // exactly "0", "1" or "2"; anything else (unset, "on", "01") keeps the default, never the large layout by accident
-  static const int m = [] { const char* e = getenv("FFP_DET_ARENA"); return e && e[0] >= '0' && e[0] <= '2' && !e[1] ? e[0] - '0' : 1; }();
-  return m;
-}
-
 void DetEngine::mem_detail(size_t* activation, size_t* no_reuse, size_t* peak_live) const {
   *activation = *no_reuse = *peak_live = 0;
   plans_.for_each([&](const DetPlan& p) {
@@ -524,11 +517,6 @@ void DetEngine::mem_detail(size_t* activation, size_t* no_reuse, size_t* peak_li
     *no_reuse += p.no_reuse_bytes();
     *peak_live += p.peak_live_bytes();
   });
-}
-
-int DetEngine::gate_env() {
-  static const int on = [] { const char* e = getenv("FFP_DET_GATE"); return e && e[0] == '0' && !e[1] ? 0 : 1; }();
-  return on;
 }
 
 void DetEngine::set_gate(bool on) {

@@ -62,7 +62,7 @@ class DetEngine {
   int nc() const { return nc_; }
   int nkpt() const { return nkpt_; }
   // device memory: resident plans (activations + tables; one plan per batch shape, least recently used ones are dropped beyond 8 plans or
-  // beyond det_plan_budget(), plan_cache.hpp) and the packed weights
+  // beyond sw().det_plan_bytes(), plan_cache.hpp) and the packed weights
   size_t plan_bytes() const { return plans_.bytes(); }
   void drop_plans() { plans_.clear(); }      // release every resident plan (the next call lays its plan out again); waits for the stream first
   size_t weight_bytes() const { return weight_bytes_; }
@@ -101,13 +101,11 @@ class DetEngine {
 
   std::map<std::string, PackedConv> convs_;
   std::map<std::string, DenseF32> dense_;      // model.23.cv3.<l>.2 as plain fp32 (nc <= 4): the closing conv of the fused class tower (conv_dwpw.hip)
-  PlanCache<std::vector<int>, DetPlan> plans_{8, det_plan_budget(), [this] { FFP_HIP(hipSetDevice(device_)); FFP_HIP(hipStreamSynchronize(st_)); }};
+  PlanCache<std::vector<int>, DetPlan> plans_{8, sw().det_plan_bytes(), [this] { FFP_HIP(hipSetDevice(device_)); FFP_HIP(hipStreamSynchronize(st_)); }};
   std::vector<TileGeom> geom_last_;
   int lanes_ = 0;
-  static int reuse_env();       // FFP_DET_ARENA, or 1
-  int reuse_ = reuse_env();
-  static int gate_env();        // FFP_DET_GATE, or 1
-  bool gate_ = gate_env() != 0;
+  int reuse_ = sw().det_arena;      // FFP_DET_ARENA, or 1
+  bool gate_ = sw().det_gate;       // FFP_DET_GATE, or on
   HostPinned h_active_;         // the gate's verdict of the last call
   bool last_gated_ = false;
   int last_items_ = 0;

@@ -57,6 +57,11 @@ const char* ffp_last_error(void);
 int ffp_version(void);
 /* number of visible HIP devices (0 and FFP_OK when none) */
 int ffp_device_count(int* out_n);
+/* The environment switches of this process (csrc/switches.hpp), one line per switch, NUL-terminated:
+ *   NAME=effective value <tab> env|default <tab> once|live <tab> accepted values <tab> effect
+ * Needs no device. A variable whose value its rule refuses is FFP_ERR_ARG here and from every other call that reads a switch;
+ * FFP_ERR_ARG also when cap is too small (the message says how many bytes are needed). */
+int ffp_switches(char* out, size_t cap);
 
 /* ---------------------------------------------------------------------------------------------------------
  * host logic
