@@ -135,6 +135,11 @@ _SIGS = {
     "ffp_jpeg_decode": (C.c_int, [C.c_int, _p(C.c_uint8), C.c_int64, C.c_int, _p(C.c_uint8), C.c_int64]),
     "ffp_jpeg_decode_dev": (C.c_int, [C.c_int, _p(C.c_uint8), C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int64]),
     "ffp_jpeg_decode_stats": (C.c_int, [_p(C.c_int64), _p(C.c_int64), _p(C.c_int64)]),
+    "ffp_png_info": (C.c_int, [_p(C.c_uint8), C.c_int64, _p(C.c_int32), _p(C.c_int32), _p(C.c_int32), _p(C.c_int32)]),
+    "ffp_png_decode": (C.c_int, [C.c_int, _p(C.c_uint8), C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int64]),
+    "ffp_png_decode_dev": (C.c_int, [C.c_int, _p(C.c_uint8), C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64]),
+    "ffp_png_decode_stats": (C.c_int, [_p(C.c_int64), _p(C.c_int64)]),
+    "ffp_png_unfilter_geometry": (C.c_int, [_p(C.c_int32), _p(C.c_int32)]),
     "ffp_op_conv2d_shape": (C.c_int, [C.c_int]),
     "ffp_op_conv2d_shape_name": (C.c_int, [C.c_int, C.c_char_p, C.c_int]),
     "ffp_op_conv2d_last_variant": (C.c_int, [C.c_char_p, C.c_int]),
@@ -1603,6 +1608,82 @@ def jpeg_decode_stats():
     a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
     _check(lib().ffp_jpeg_decode_stats(C.byref(a), C.byref(b), C.byref(c)))
     return a.value, b.value, c.value
+
+
+FFP_ERR_ARG = 1              # include/ffp.h
+FFP_PNG_DEC_SERIAL = 1
+
+
+def png_info(data: bytes):
+    """(height, width, channels, bit depth) from the IHDR of a PNG file; FfpError(FFP_ERR_ARG) names the field of a file that is not decoded
+    (palette, sub-byte depth, gray with alpha, interlace). No device."""
+    buf = np.frombuffer(data, np.uint8)
+    h, w, ch, bd = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    _check(lib().ffp_png_info(buf.ctypes.data_as(_p(C.c_uint8)), len(buf), C.byref(h), C.byref(w), C.byref(ch), C.byref(bd)))
+    return h.value, w.value, ch.value, bd.value
+
+
+def png_decode(data: bytes, bgr: bool = False, flags: int = 0, device: int = 0) -> np.ndarray:
+    """PNG file -> (h, w) or (h, w, channels) uint8 / uint16, what cv2.imread(path, IMREAD_UNCHANGED) gives (bgr=True). A file whose IDAT chunks
+    inflate one by one (every file png_encode writes) is inflated on the GPU, one wavefront per chunk; others on the host (csrc/png_dec.hip).
+    flags=FFP_PNG_DEC_SERIAL: the host inflate for every file."""
+    h, w, ch, bd = png_info(data)
+    buf = np.frombuffer(data, np.uint8)
+    out = np.empty((h, w, ch), np.uint8 if bd == 8 else np.uint16)
+    _check(lib().ffp_png_decode(device, buf.ctypes.data_as(_p(C.c_uint8)), len(buf), int(bgr), int(flags), C.c_void_p(out.ctypes.data), out.nbytes))
+    return out[..., 0] if ch == 1 else out
+
+
+def png_decode_dev(data: bytes, d_ptr: int, row_stride: int, cap: int, bgr: bool = True, flags: int = 0, device: int = 0):
+    """Same into device memory (pointer, row pitch and capacity in bytes; pitch 0 = packed rows); returns (h, w, channels, bit depth)."""
+    info = png_info(data)
+    buf = np.frombuffer(data, np.uint8)
+    _check(lib().ffp_png_decode_dev(device, buf.ctypes.data_as(_p(C.c_uint8)), len(buf), int(bgr), int(flags), C.c_void_p(d_ptr), row_stride, cap))
+    return info
+
+
+def png_decode_stats():
+    """(files inflated on the device, files inflated on the host) since load"""
+    a, b = C.c_int64(0), C.c_int64(0)
+    _check(lib().ffp_png_decode_stats(C.byref(a), C.byref(b)))
+    return a.value, b.value
+
+
+def png_unfilter_geometry():
+    """(rows one workgroup pass of the unfilter kernel covers, pixels of one of its steps): test hook"""
+    r, c = C.c_int32(0), C.c_int32(0)
+    _check(lib().ffp_png_unfilter_geometry(C.byref(r), C.byref(c)))
+    return r.value, c.value
+
+
+def _png_has_trns(data: bytes) -> bool:
+    """a tRNS chunk among the chunks in front of the first IDAT (where the format puts it): a walk by chunk lengths, not a byte search"""
+    pos = 8
+    while pos + 12 <= len(data):
+        n = int.from_bytes(data[pos:pos + 4], "big")
+        typ = data[pos + 4:pos + 8]
+        if typ == b"tRNS":
+            return True
+        if typ in (b"IDAT", b"IEND"):
+            return False
+        pos += 12 + n
+    return False
+
+
+def png_read_rgb8(data: bytes, bgr: bool):
+    """What np.asarray(Image.open(...).convert("RGB")) gives ([..., ::-1] of it when bgr) for an 8-bit gray, RGB or RGBA file, decoded by png_decode: gray
+    replicated to three channels, alpha dropped. Both routes of the decoder beat Pillow on every measured frame (profiles/png_decode_mi355x.json), so every
+    such file comes here. None when the file stays with Pillow: 16-bit, a geometry png_info refuses, a tRNS chunk, or any error of the decoder."""
+    try:
+        _, _, ch, depth = png_info(data)
+        if depth != 8 or _png_has_trns(data):
+            return None
+        a = png_decode(data, bgr=bgr)
+    except Exception:        # noqa: BLE001 — Pillow decides, and reports what is wrong with the file
+        return None
+    if ch == 1:
+        return np.repeat(a[..., None], 3, axis=2)
+    return np.ascontiguousarray(a[..., :3]) if ch == 4 else a
 
 
 def _ragged(rows, width, dtype):

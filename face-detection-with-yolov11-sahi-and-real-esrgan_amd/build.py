@@ -15,7 +15,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libffp.so")
-SOURCES = ["common.cpp", "weights.cpp", "engine.cpp", "conv_route.cpp", "conv_mfma.hip", "conv_rows.hip", "conv_rows16.hip", "conv_rows16pc.hip", "conv_trunk.hip", "conv_pw.hip", "conv_k3d.hip", "conv_dwpw.hip", "ops_misc.hip", "det_post.hip", "merge.hip", "eval.hip", "coco_eval.hip", "iqa.hip", "jpeg.hip", "jpeg_huff.hip", "jpeg_dec.cpp", "png.hip",
+SOURCES = ["common.cpp", "weights.cpp", "engine.cpp", "conv_route.cpp", "conv_mfma.hip", "conv_rows.hip", "conv_rows16.hip", "conv_rows16pc.hip", "conv_trunk.hip", "conv_pw.hip", "conv_k3d.hip", "conv_dwpw.hip", "ops_misc.hip", "det_post.hip", "merge.hip", "eval.hip", "coco_eval.hip", "iqa.hip", "jpeg.hip", "jpeg_huff.hip", "jpeg_dec.cpp", "png.hip", "png_dec.cpp", "png_dec.hip",
            "sr_ops.hip", "resize.hip", "yolo11.cpp", "rrdb.cpp", "onnx_graph.cpp", "scrfd_ops.hip", "scrfd.cpp", "rtdetr_ops.hip", "rtdetr.cpp", "sliced.cpp", "api.cpp",
            "api_eval.cpp", "api_codec.cpp", "api_ops.cpp"]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-result",
@@ -35,10 +35,18 @@ def _newest_header() -> float:
     return max(os.path.getmtime(h) for h in hs)
 
 
+def _obj_base(src: str) -> str:
+    """Object file stem of a source: its own stem, with the extension added where a .cpp and a .hip share one (png_dec.cpp, png_dec.hip)."""
+    stem, ext = os.path.splitext(src)
+    if sum(1 for s in SOURCES if os.path.splitext(s)[0] == stem) > 1:
+        stem += "_" + ext.lstrip(".")
+    return stem
+
+
 def _compile(src: str, force: bool) -> str:
     bdir = os.path.join(CSRC, "build")
     os.makedirs(bdir, exist_ok=True)
-    obj = os.path.join(bdir, os.path.splitext(src)[0] + ".o")
+    obj = os.path.join(bdir, _obj_base(src) + ".o")
     spath = os.path.join(CSRC, src)
     if not force and os.path.exists(obj) and os.path.getmtime(obj) > max(os.path.getmtime(spath), _newest_header()):
         return obj
@@ -96,7 +104,7 @@ def build_variant(name: str, verbose: bool = True) -> str:
     bdir = os.path.join(CSRC, "build")
     objs = []
     for s_ in SOURCES:
-        base = os.path.splitext(s_)[0]
+        base = _obj_base(s_)
         if s_ in srcs:
             obj = os.path.join(bdir, f"{base}.{name}.o")
             cmd = [_hipcc(), *FLAGS, *defs, "-c", os.path.join(CSRC, s_), "-o", obj]
@@ -115,13 +123,13 @@ def build_variant(name: str, verbose: bool = True) -> str:
     return out
 
 
-ASAN_SOURCES = ["common.cpp", "weights.cpp", "jpeg_dec.cpp", "onnx_graph.cpp", "asan_host_check.cpp"]
+ASAN_SOURCES = ["common.cpp", "weights.cpp", "jpeg_dec.cpp", "png_dec.cpp", "onnx_graph.cpp", "asan_host_check.cpp"]
 ASAN_OUT = os.path.join(CSRC, "build", "asan_host_check")
 
 
 def build_asan(verbose: bool = True) -> str:
     """Host-only AddressSanitizer + UBSan build of the parsers of untrusted bytes (FFPW containers, JPEG markers and Huffman
-    tables) with their robustness driver (csrc/asan_host_check.cpp). No device code; runs on a CPU-only box."""
+    tables, PNG chunks and the inflate core the PNG kernel shares) with their robustness driver (csrc/asan_host_check.cpp). No device code; runs on a CPU-only box."""
     clang = os.path.join(os.path.dirname(os.path.realpath(_hipcc())), "..", "lib", "llvm", "bin", "clang++")
     if not os.path.exists(clang):
         clang = "/opt/rocm/lib/llvm/bin/clang++"

@@ -10,7 +10,8 @@ visible; its output is byte-identical (files) and pixel-identical (decoded array
 (tests/test_gpu_jpeg.py) for YCbCr / grayscale baseline files, so the choice changes the time, not one bit of the result. `.png`
 files are written by the device encoder too (csrc/png.hip: ffp_png_encode; uint8 / uint16, gray, BGR or BGRA): other bytes than
 libpng's, the same pixels (tests/test_gpu_png.py), 10 to 100 times sooner than Pillow at compress_level=1 (profiles/png_encode_mi355x.json);
-reading PNG stays with Pillow. Files the
+8-bit gray / RGB / RGBA `.png` files are read by the device decoder (csrc/png_dec.hip: ffp_png_decode) and come back as Pillow's
+`convert("RGB")` gives them; 16-bit, palette, tRNS, gray+alpha and interlaced files stay with Pillow (profiles/png_decode_mi355x.json). Files the
 device codec does not read (progressive, RGB-coded with Adobe transform 0 or R/G/B component ids) and machines without a GPU use
 Pillow, and say so once on stderr. Like `cv2.imread`, `imread` applies the EXIF orientation tag (not with IMREAD_UNCHANGED).
 """
@@ -117,6 +118,13 @@ else:
                         _tell(str(e))
                 else:
                     _tell("no GPU visible")
+            elif _is_png(path):
+                codec = _gpu_codec()
+                if codec:
+                    with open(path, "rb") as fh:
+                        a = codec.png_read_rgb8(fh.read(), bgr=True)      # None: the file stays with Pillow (16-bit, palette, tRNS, a route left to Pillow)
+                    if a is not None:
+                        return _oriented(a, o)
             return _oriented(np.asarray(Image.open(path).convert("RGB"))[..., ::-1], o)
         except Exception:
             return None

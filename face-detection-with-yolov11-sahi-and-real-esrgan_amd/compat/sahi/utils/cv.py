@@ -38,4 +38,19 @@ def read_image_as_array(image) -> np.ndarray:
                         return _lib.jpeg_decode(fh.read(), bgr=False)
         except Exception:        # noqa: BLE001 — progressive / CMYK / truncated files: PIL decides
             pass
+    if isinstance(image, str) and image.lower().endswith(".png"):
+        # 8-bit gray / RGB / RGBA files go through this build's decoder (_lib.png_read_rgb8): the ones its encoder wrote (the enhanced frame of
+        # pipeline_v2_enhancement_first/app_v2.py:104-112) are inflated on the GPU, others on the host, all unfiltered on the GPU; every other file stays with PIL
+        try:
+            from ffp_amd import _lib
+            if _lib.device_count() > 0:
+                with Image.open(image) as im:
+                    plain = im.getexif().get(0x0112, 1) in (0, 1)
+                if plain:
+                    with open(image, "rb") as fh:
+                        a = _lib.png_read_rgb8(fh.read(), bgr=False)
+                    if a is not None:
+                        return a
+        except Exception:        # noqa: BLE001 — PIL decides
+            pass
     return np.asarray(read_image_as_pil(image))

@@ -2,6 +2,7 @@
 #include "api_util.hpp"
 #include "jpeg.hpp"
 #include "png.hpp"
+#include "png_dec.hpp"
 
 using namespace ffp;
 
@@ -158,6 +159,60 @@ int ffp_png_encode(int device, const void* img, int h, int w, int channels, int 
   FFP_API_BEGIN
   FFP_CHECK(img && h > 0 && w > 0 && out_size, FFP_ERR_ARG, "png_encode: bad arguments");
   png_encode_one(device, img, true, h, w, channels, bit_depth, (int64_t)w * channels * (bit_depth / 8), bgr, level, out, cap, out_size);
+  FFP_API_END
+}
+
+// ---- reading PNG (png_dec.cpp, png_dec.hip) -----------------------------------------------------------------------------------------
+int ffp_png_info(const uint8_t* data, int64_t n, int32_t* h, int32_t* w, int32_t* channels, int32_t* bit_depth) {
+  FFP_API_BEGIN
+  FFP_CHECK(data && h && w, FFP_ERR_ARG, "png_info: null argument");
+  PngFile f;
+  png_parse(data, n, f, true);
+  *h = f.h; *w = f.w;
+  if (channels) *channels = f.channels;
+  if (bit_depth) *bit_depth = f.bit_depth;
+  FFP_API_END
+}
+
+int ffp_png_decode_dev(int device, const uint8_t* data, int64_t n, int bgr, int flags, void* d_out, int64_t row_stride, int64_t cap) {
+  FFP_API_BEGIN
+  FFP_CHECK(data && d_out, FFP_ERR_ARG, "png_decode: null argument");
+  PngFile f;
+  png_parse(data, n, f, false);                          // every refusal of the file's layout comes before the device is touched
+  ScopedStream cx(device, "png_decode", ScopedStream::Io);
+  png_decode_to_device(data, n, f, bgr, flags, d_out, row_stride, cap, cx.st);
+  FFP_API_END
+}
+
+int ffp_png_decode(int device, const uint8_t* data, int64_t n, int bgr, int flags, void* out, int64_t cap) {
+  FFP_API_BEGIN
+  FFP_CHECK(data && out, FFP_ERR_ARG, "png_decode: null argument");
+  PngFile f;
+  png_parse(data, n, f, false);
+  const long long bytes = (long long)f.h * f.row_bytes();
+  FFP_CHECK(cap >= bytes, FFP_ERR_ARG, "png_decode: output buffer too small for %d x %d x %d at %d bits (%lld bytes needed)", f.w, f.h, f.channels, f.bit_depth, bytes);
+  ScopedStream cx(device, "png_decode", ScopedStream::Io);
+  DevBuf d((size_t)bytes);
+  png_decode_to_device(data, n, f, bgr, flags, d.p, 0, bytes, cx.st);
+  FFP_HIP(hipMemcpy(out, d.p, (size_t)bytes, hipMemcpyDeviceToHost));
+  FFP_API_END
+}
+
+int ffp_png_decode_stats(int64_t* parallel_decodes, int64_t* serial_decodes) {
+  FFP_API_BEGIN
+  long long a = 0, b = 0;
+  png_decode_stats(&a, &b);
+  if (parallel_decodes) *parallel_decodes = a;
+  if (serial_decodes) *serial_decodes = b;
+  FFP_API_END
+}
+
+int ffp_png_unfilter_geometry(int32_t* rows_per_group, int32_t* cols_per_step) {
+  FFP_API_BEGIN
+  int r = 0, c = 0;
+  png_unfilter_geometry(&r, &c);
+  if (rows_per_group) *rows_per_group = r;
+  if (cols_per_step) *cols_per_step = c;
   FFP_API_END
 }
 

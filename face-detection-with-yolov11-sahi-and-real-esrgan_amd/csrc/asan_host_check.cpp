@@ -8,7 +8,11 @@
 // and expects each call to either succeed or throw ffp::Error — any out-of-bounds access, overflow or undefined shift aborts the
 // process through the sanitizer runtime. ONNX models (onnx_graph.cpp) are parsed and lowered (SCRFD subset) under the same cases:
 // every truncation of the first 4 KiB and at a stride through the body, and seeded byte / bit mutations.
-// Usage: asan_host_check jpeg <file>... ffpw <file>... onnx <file>...
+// PNG files (png_dec.cpp; the inflate core of png_inflate.hpp, the code png_inflate_kernel compiles): each file is parsed, inflated serially and span by
+// span under the kernel's rules (length, Adler-32 and the verdict "segmented" / "serial" are printed), then truncated at every length of the first 4 KiB
+// and at a stride through the body, and hit by seeded byte / bit mutations, raw and inside chunk payloads with the CRCs made right again. `pngbad` files
+// must be refused; the reason is printed.
+// Usage: asan_host_check jpeg <file>... ffpw <file>... onnx <file>... png <file>... pngbad <file>...
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -18,6 +22,7 @@
 
 #include "jpeg.hpp"
 #include "onnx_graph.hpp"
+#include "png_dec.hpp"
 #include "weights.hpp"
 
 using namespace ffp;
@@ -225,19 +230,131 @@ static void onnx_cases(const Bytes& good, unsigned seed) {
   }
 }
 
+// ---- png: the chunk walk (png_dec.cpp) and the inflate core the kernel compiles too (png_inflate.hpp) -------------------------------------------
+static unsigned png_crc(const unsigned char* p, size_t n) {
+  unsigned c = 0xFFFFFFFFu;
+  for (size_t k = 0; k < n; ++k) {
+    c ^= p[k];
+    for (int b = 0; b < 8; ++b) c = (c >> 1) ^ (0xEDB88320u & (0u - (c & 1u)));
+  }
+  return ~c;
+}
+struct PngChunk { Bytes type, payload; };
+static std::vector<PngChunk> png_chunks(const Bytes& b) {          // of a file the parser accepted
+  std::vector<PngChunk> out;
+  size_t pos = 8;
+  while (pos + 12 <= b.size()) {
+    const size_t len = ((size_t)b[pos] << 24) | ((size_t)b[pos + 1] << 16) | ((size_t)b[pos + 2] << 8) | b[pos + 3];
+    if (len > b.size() - pos - 12) break;
+    out.push_back(PngChunk{Bytes(b.begin() + pos + 4, b.begin() + pos + 8), Bytes(b.begin() + pos + 8, b.begin() + pos + 8 + len)});
+    pos += 12 + len;
+  }
+  return out;
+}
+static Bytes png_join(const Bytes& sig, const std::vector<PngChunk>& ch) {   // lengths and CRCs made right again
+  Bytes o(sig.begin(), sig.begin() + 8);
+  for (const PngChunk& c : ch) {
+    const unsigned len = (unsigned)c.payload.size();
+    for (int s = 24; s >= 0; s -= 8) o.push_back((unsigned char)(len >> s));
+    Bytes body(c.type);
+    body.insert(body.end(), c.payload.begin(), c.payload.end());
+    o.insert(o.end(), body.begin(), body.end());
+    const unsigned crc = png_crc(body.data(), body.size());
+    for (int s = 24; s >= 0; s -= 8) o.push_back((unsigned char)(crc >> s));
+  }
+  return o;
+}
+
+// Both routes over one file: the spans one by one under the kernel's rules, and the joined stream. 1 accepted, 0 rejected (why: the serial route's
+// message). The routes must agree wherever the span route accepts: exit 3 otherwise.
+static int try_png(const Bytes& b, const char* print_as, std::string* why = nullptr) {
+  std::unique_ptr<unsigned char[]> d(new unsigned char[b.size() ? b.size() : 1]);      // exact-size copy: a redzone right behind it
+  if (!b.empty()) memcpy(d.get(), b.data(), b.size());
+  try {
+    PngFile f;
+    png_parse(d.get(), (long long)b.size(), f, false);
+    if (f.filtered_len() > (64ll << 20)) { ++g_rejected; if (why) *why = "too large for the driver"; return 0; }      // a mutated IHDR must not exhaust the host
+    const size_t want = (size_t)f.filtered_len();
+    std::unique_ptr<unsigned char[]> a(new unsigned char[want]), s(new unsigned char[want]);
+    unsigned adler = 0;
+    const unsigned char* tail = d.get() + f.idat.back().off;
+    bool seg = png_spans_self_contained(d.get(), f, a.get(), &adler);
+    if (seg) {
+      const unsigned stored = ((unsigned)tail[0] << 24) | ((unsigned)tail[1] << 16) | ((unsigned)tail[2] << 8) | tail[3];
+      seg = stored == adler;
+    }
+    png_inflate_serial(d.get(), f, s.get());
+    if (seg && memcmp(a.get(), s.get(), want) != 0) { fprintf(stderr, "png: the span route and the serial route disagree\n"); exit(3); }
+    if (print_as) printf("png %s: length %zu adler %08x verdict %s\n", print_as, want, png_adler32(s.get(), want), seg ? "segmented" : "serial");
+    ++g_ok;
+    return 1;
+  } catch (const Error& e) {
+    if (why) *why = e.what();
+    ++g_rejected;
+    return 0;
+  }
+}
+
+static void png_cases(const Bytes& good, const char* path, unsigned seed) {
+  if (!try_png(good, path)) { fprintf(stderr, "a valid file was rejected\n"); exit(3); }
+  const size_t he = good.size() < 4096 ? good.size() : 4096;
+  for (size_t n = 0; n <= he; ++n) try_png(Bytes(good.begin(), good.begin() + n), nullptr);
+  for (size_t n = he; n < good.size(); n += 1 + (good.size() - he) / 97) try_png(Bytes(good.begin(), good.begin() + n), nullptr);
+  const std::vector<PngChunk> ch = png_chunks(good);
+  std::mt19937 rng(seed);
+  for (int it = 0; it < 3000; ++it) {
+    if (it % 3 == 0) {                                       // raw hits: mostly the chunk walk and the CRCs answer
+      Bytes m = good;
+      const int k = 1 + (int)(rng() % 4);
+      for (int q = 0; q < k; ++q) {
+        const size_t pos = rng() % m.size();
+        if (rng() % 2) m[pos] = (unsigned char)rng(); else m[pos] ^= (unsigned char)(1u << (rng() % 8));
+      }
+      try_png(m, nullptr);
+      continue;
+    }
+    std::vector<PngChunk> c = ch;                            // hits inside payloads with the CRCs made right: the header checks and the inflate core answer
+    const int k = 1 + (int)(rng() % 3);
+    for (int q = 0; q < k; ++q) {
+      PngChunk& t = c[rng() % c.size()];
+      if (t.payload.empty()) continue;
+      const size_t pos = (rng() % 4 == 0) ? rng() % (t.payload.size() < 16 ? t.payload.size() : 16) : rng() % t.payload.size();   // extra weight on block headers
+      switch (rng() % 5) {
+        case 0: t.payload[pos] = (unsigned char)rng(); break;
+        case 1: t.payload[pos] ^= (unsigned char)(1u << (rng() % 8)); break;
+        case 2: t.payload[pos] = 0xFF; break;
+        case 3: t.payload[pos] = 0; break;
+        default: t.payload.resize(pos); break;               // a chunk cut short
+      }
+    }
+    try_png(png_join(good, c), nullptr);
+  }
+}
+
+// files that must be refused: prints the reason
+static void png_bad_case(const Bytes& bad, const char* path) {
+  std::string why;
+  if (try_png(bad, nullptr, &why)) { fprintf(stderr, "png %s: an invalid file was accepted\n", path); exit(3); }
+  printf("png %s: rejected: %s\n", path, why.c_str());
+}
+
 int main(int argc, char** argv) {
-  enum { NONE, JPEG, FFPW, ONNX } mode = NONE;
+  enum { NONE, JPEG, FFPW, ONNX, PNG, PNGBAD } mode = NONE;
   unsigned seed = 1;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
     if (a == "jpeg") { mode = JPEG; continue; }
     if (a == "ffpw") { mode = FFPW; continue; }
     if (a == "onnx") { mode = ONNX; continue; }
+    if (a == "png") { mode = PNG; continue; }
+    if (a == "pngbad") { mode = PNGBAD; continue; }
     const Bytes b = slurp(argv[i]);
-    if (mode == JPEG) jpeg_cases(b, seed++);
+    if (mode == PNG) png_cases(b, argv[i], seed++);
+    else if (mode == PNGBAD) png_bad_case(b, argv[i]);
+    else if (mode == JPEG) jpeg_cases(b, seed++);
     else if (mode == FFPW) ffpw_cases(b, seed++);
     else if (mode == ONNX) onnx_cases(b, seed++);
-    else { fprintf(stderr, "usage: %s jpeg <file>... ffpw <file>... onnx <file>...\n", argv[0]); return 2; }
+    else { fprintf(stderr, "usage: %s jpeg <file>... ffpw <file>... onnx <file>... png <file>... pngbad <file>...\n", argv[0]); return 2; }
   }
   printf("asan_host_check: %lld inputs parsed, %lld rejected, no sanitizer report\n", g_ok, g_rejected);
   return 0;

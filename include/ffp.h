@@ -377,7 +377,7 @@ int ffp_jpeg_decode_dev(int device, const uint8_t* data, int64_t n, int bgr, uin
 int ffp_jpeg_decode_stats(int64_t* device_decodes, int64_t* host_fallbacks, int64_t* extra_sync_rounds);
 
 /* ---------------------------------------------------------------------------------------------------------
- * PNG at the file boundaries (encoding only; reading PNG stays with the host)
+ * PNG at the file boundaries (written and read on the device; palette, sub-byte, gray+alpha and interlaced files stay with the host)
  * ------------------------------------------------------------------------------------------------------- */
 
 /* Replaces `cv2.imwrite(path, img)` for .png paths (/root/reference/pipeline_v1_detection_first/app_v1.py:39, app_sahi_detection.py:31,
@@ -403,6 +403,28 @@ int ffp_png_encode_dev(int device, const void* d_img, int h, int w, int channels
  * FFP_ERR_ARG). File i is byte for byte what ffp_png_encode_dev writes for image i. */
 int ffp_png_encode_batch_dev(int device, const void* d_base, int n, const int64_t* offsets, const int32_t* hs, const int32_t* ws, const int64_t* strides,
                              int channels, int bit_depth, int bgr, int level, uint8_t* out, int64_t cap, int64_t* out_offsets);
+
+/* Reading PNG (csrc/png_dec.cpp, png_dec.hip): replaces `cv2.imread(path)` for .png paths (the reference's utils/enhancer.py:254 and
+ * utils/visualization.py:95,198) and the read behind `get_sliced_prediction(image=temp_enhanced_path)`
+ * (pipeline_v2_enhancement_first/app_v2.py:112). Decoded: colour types 0, 2 and 6 (gray, RGB, RGBA) at bit depth 8 or 16, not interlaced,
+ * h, w >= 1; palette, sub-byte depths, gray with alpha, interlace and a file without IDAT are FFP_ERR_ARG naming the field, before
+ * anything is launched. Ancillary chunks (tRNS, gAMA, iCCP, eXIf, ...) are skipped unread. Output: h x w x channels samples of the
+ * file's depth (uint8, or uint16 in host byte order), what IMREAD_UNCHANGED gives; the first three channels are BGR when bgr = 1. cap too
+ * small is FFP_ERR_ARG. A file whose IDAT chunks each inflate on their own (every file ffp_png_encode* writes: one deflate segment per
+ * IDAT, the Adler-32 in a last 4-byte IDAT) is inflated on the device, one wavefront per IDAT; the verdict is taken per file from the
+ * bytes alone (every chunk decodes by itself, uses exactly its bytes, no match reaches before its own output, the lengths add up and the
+ * Adler-32 matches), never from a marker. Every other file is inflated on the host by the same code and unfiltered on the device.
+ * flags: FFP_PNG_DEC_SERIAL forces the host inflate for every file (A/B partner, parity oracle). A wrong CRC (IHDR, IDAT, IEND), a wrong
+ * Adler-32, a stream that ends early and one that ends late are FFP_ERR_ARG with the message saying which. ffp_png_info: header only,
+ * no device. _dev: the frame stays in device memory (row pitch in bytes, 0 = packed) for the ffp_*_dev entries.
+ * ffp_png_decode_stats: files decoded by each route since the library was loaded. ffp_png_unfilter_geometry: test hook, the rows one
+ * workgroup pass covers and the pixels of one of its steps. */
+#define FFP_PNG_DEC_SERIAL 1
+int ffp_png_info(const uint8_t* data, int64_t n, int32_t* h, int32_t* w, int32_t* channels, int32_t* bit_depth);
+int ffp_png_decode(int device, const uint8_t* data, int64_t n, int bgr, int flags, void* out, int64_t cap);
+int ffp_png_decode_dev(int device, const uint8_t* data, int64_t n, int bgr, int flags, void* d_out, int64_t row_stride, int64_t cap);
+int ffp_png_decode_stats(int64_t* parallel_decodes, int64_t* serial_decodes);
+int ffp_png_unfilter_geometry(int32_t* rows_per_group, int32_t* cols_per_step);
 
 /* 1x1 conv over the virtual concat [nearest_x2(coarse) | fine] (the YOLO neck's Upsample + Concat + C3k2.cv1 without
  * materialising the upsampled tensor: /root/reference's model graph via ultralytics' yolo11-pose.yaml layers 11-13 and 14-16).
