@@ -135,6 +135,11 @@ _SIGS = {
     "ffp_jpeg_decode": (C.c_int, [C.c_int, _p(C.c_uint8), C.c_int64, C.c_int, _p(C.c_uint8), C.c_int64]),
     "ffp_jpeg_decode_dev": (C.c_int, [C.c_int, _p(C.c_uint8), C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int64]),
     "ffp_jpeg_decode_stats": (C.c_int, [_p(C.c_int64), _p(C.c_int64), _p(C.c_int64)]),
+    "ffp_jpeg_decode_batch_dev": (C.c_int, [C.c_int, C.c_int, _p(C.c_void_p), _p(C.c_int64), C.c_int, C.c_void_p, _p(C.c_int64), _p(C.c_int64), C.c_int64,
+                                            _p(C.c_int32), _p(C.c_int32), _p(C.c_int32)]),
+    "ffp_jpeg_decode_batch": (C.c_int, [C.c_int, C.c_int, _p(C.c_void_p), _p(C.c_int64), C.c_int, _p(C.c_void_p), _p(C.c_int64), _p(C.c_int32), _p(C.c_int32),
+                                        _p(C.c_int32)]),
+    "ffp_jpeg_decode_batch_stats": (C.c_int, [_p(C.c_int64), _p(C.c_int64), _p(C.c_int64)]),
     "ffp_png_info": (C.c_int, [_p(C.c_uint8), C.c_int64, _p(C.c_int32), _p(C.c_int32), _p(C.c_int32), _p(C.c_int32)]),
     "ffp_png_decode": (C.c_int, [C.c_int, _p(C.c_uint8), C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int64]),
     "ffp_png_decode_dev": (C.c_int, [C.c_int, _p(C.c_uint8), C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64]),
@@ -1601,6 +1606,74 @@ def jpeg_decode_dev(data: bytes, d_ptr: int, row_stride: int, cap: int, bgr: boo
     buf = np.frombuffer(data, np.uint8)
     _check(lib().ffp_jpeg_decode_dev(device, buf.ctypes.data_as(_p(C.c_uint8)), len(buf), int(bgr), C.c_void_p(d_ptr), row_stride, cap))
     return h, w
+
+
+def _file_table(datas):
+    """n byte strings as the (pointer array, sizes, keep-alive list) the batch entries take"""
+    bufs = [np.frombuffer(bytes(d), np.uint8) if len(d) else np.zeros(0, np.uint8) for d in datas]
+    ptrs = (C.c_void_p * max(len(bufs), 1))(*[b.ctypes.data if b.size else None for b in bufs])
+    sizes = np.asarray([b.size for b in bufs], np.int64).reshape(-1)
+    return ptrs, sizes, bufs
+
+
+def jpeg_decode_batch_dev(datas, d_base: int, offsets, strides, cap: int, bgr: bool = True, device: int = 0):
+    """n JPEG streams -> n images in device memory in ONE pass (ffp_jpeg_decode_batch_dev): image i at d_base + offsets[i], row pitch strides[i]
+    (None: packed). Returns (hs, ws, status) as int32 arrays; status 0: decoded on the device, 1: by the host decoder, < 0: minus the error code
+    of a file that was not decoded (its region is untouched)."""
+    n = len(datas)
+    ptrs, sizes, keep = _file_table(datas)
+    offsets = np.ascontiguousarray(np.asarray(offsets, np.int64).reshape(-1))
+    if len(offsets) != n:
+        raise ValueError("jpeg_decode_batch_dev: one offset per file")
+    st = None if strides is None else np.ascontiguousarray(np.asarray(strides, np.int64).reshape(-1))
+    if st is not None and len(st) != n:
+        raise ValueError("jpeg_decode_batch_dev: one row pitch per file")
+    hs, ws, status = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+    i64 = lambda a: a.ctypes.data_as(_p(C.c_int64))
+    i32 = lambda a: a.ctypes.data_as(_p(C.c_int32))
+    _check(lib().ffp_jpeg_decode_batch_dev(device, n, ptrs, i64(np.ascontiguousarray(sizes)) if n else i64(np.zeros(1, np.int64)), int(bgr), C.c_void_p(d_base),
+                                           i64(offsets) if n else i64(np.zeros(1, np.int64)), None if st is None else i64(st), cap, i32(hs), i32(ws), i32(status)))
+    del keep
+    return hs[:n], ws[:n], status[:n]
+
+
+def jpeg_decode_batch(datas, bgr: bool = False, device: int = 0):
+    """n JPEG streams in ONE pass -> a list with, per file, the h x w x 3 uint8 array or the FfpError that says why it was not decoded."""
+    n = len(datas)
+    if n == 0:
+        _check(lib().ffp_jpeg_decode_batch(device, 0, None, None, int(bgr), None, None, None, None, None))
+        return []
+    ptrs, sizes, keep = _file_table(datas)
+    res, outs = [], []
+    for d in datas:
+        try:
+            h, w, _ = jpeg_info(d)
+            outs.append(np.empty((h, w, 3), np.uint8))
+        except FfpError:
+            outs.append(np.empty((0, 0, 3), np.uint8))
+    optrs = (C.c_void_p * n)(*[o.ctypes.data if o.size else None for o in outs])
+    caps = np.asarray([o.size for o in outs], np.int64)
+    hs, ws, status = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+    _check(lib().ffp_jpeg_decode_batch(device, n, ptrs, sizes.ctypes.data_as(_p(C.c_int64)), int(bgr), optrs, caps.ctypes.data_as(_p(C.c_int64)),
+                                       hs.ctypes.data_as(_p(C.c_int32)), ws.ctypes.data_as(_p(C.c_int32)), status.ctypes.data_as(_p(C.c_int32))))
+    for i in range(n):
+        if status[i] >= 0:
+            res.append(outs[i])
+        else:
+            try:                                   # the file's own message: what the single-file call says about it
+                jpeg_info(datas[i])
+                res.append(FfpError(int(-status[i]), f"jpeg_decode_batch: file {i} was not decoded"))
+            except FfpError as e:
+                res.append(e)
+    del keep
+    return res
+
+
+def jpeg_decode_batch_stats():
+    """(batches since load, kernel launches of the latest batch, stream synchronisations of the latest batch)"""
+    a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    _check(lib().ffp_jpeg_decode_batch_stats(C.byref(a), C.byref(b), C.byref(c)))
+    return a.value, b.value, c.value
 
 
 def jpeg_decode_stats():

@@ -188,6 +188,11 @@ def build_switches_check(verbose: bool = True) -> str:
     return _build_host_check("switches_host_check", "switches_host_check.cpp", ["switches.hpp"], verbose)
 
 
+def build_jpeg_batch_plan_check(verbose: bool = True) -> str:
+    """The layout of a batch of JPEG decodes (csrc/jpeg_batch_plan.hpp, no HIP in it): seeded header sets, every range in bounds and disjoint."""
+    return _build_host_check("jpeg_batch_plan_host_check", "jpeg_batch_plan_host_check.cpp", ["jpeg_batch_plan.hpp"], verbose)
+
+
 if __name__ == "__main__":
     if "--asan" in sys.argv:
         build_asan()
@@ -199,6 +204,8 @@ if __name__ == "__main__":
         build_plan_cache_check()
     elif "--switches-check" in sys.argv:
         build_switches_check()
+    elif "--jpeg-batch-plan-check" in sys.argv:
+        build_jpeg_batch_plan_check()
     elif "--variant" in sys.argv:
         build_variant(sys.argv[sys.argv.index("--variant") + 1])
     else:

@@ -231,6 +231,77 @@ class FaceEnhancer:
                 "is_loaded": self.upsampler is not None, "backend": f"libffp {_lib.lib().ffp_version()}", "cuda_available": self.device == "cuda"}
 
 
+# The crops directory from file to file on the device (decode batch -> SR on the atlas -> encode batch) is taken from this many JPEG crops
+# on. Set by measurement (tools/jpeg_batch_probe.py -> profiles/jpeg_decode_batch_mi355x.json, "crops_dir"): the smallest measured count at
+# which the new route's slowest sample is below the per-file-read route's fastest (4 files: the directory in 4.9..6.1 ms against 9.1..10.2 ms,
+# the decode alone in 0.61..0.76 ms against 2.2..2.4 ms; one file is a tie in the decode, 0.57..0.62 ms against 0.56..0.61 ms). None would mean
+# that no such count was measured, and keep the old route.
+BATCH_ROUTE_MIN_FILES = 4
+ATLAS_MAX_WIDTH = 2048
+
+
+def pack_atlas(sizes, max_width):
+    """Shelf packing of images [(h, w), ...] in their order: -> (H, W, [(x, y), ...]). An image goes behind its predecessor on the current
+    shelf while it fits into max_width, else it opens a new shelf below; an image wider than max_width gets a shelf of its own (and W
+    grows to it). Deterministic, no overlap, everything inside H x W."""
+    pos, x, y, shelf_h, W = [], 0, 0, 0, 0
+    for h, w in sizes:
+        h, w = int(h), int(w)
+        if x > 0 and x + w > max_width:
+            y += shelf_h
+            x, shelf_h = 0, 0
+        pos.append((x, y))
+        x += w
+        shelf_h = max(shelf_h, h)
+        W = max(W, x)
+    return y + shelf_h, W, pos
+
+
+def _crops_dir_on_device(crops_dir, files, enhancer):
+    """The batch route of enhance_face_crops_batch: {file name: ((w, h), (W, H), bytes of the enhanced .jpg)} for the JPEG crops it
+    could take — read once, decoded in ONE pass into a BGR atlas in device memory (ffp_jpeg_decode_batch_dev), enhanced there
+    (ffp_sr_enhance_crops_dev with the enhancer's tile), encoded in ONE pass (ffp_jpeg_encode_batch_dev, quality 95). Only the files go up
+    and only the enhanced files come down. Every other file, and every failure, is left to the per-file loop."""
+    import torch
+    sr = enhancer.upsampler._sr
+    if enhancer.scale != sr.scale or enhancer.upsampler.scale != sr.scale:      # a resize behind the net: the per-file path knows how
+        return {}
+    names, datas, sizes = [], [], []
+    for f in files:
+        if not f.lower().endswith((".jpg", ".jpeg")):
+            continue
+        try:
+            with open(os.path.join(crops_dir, f), "rb") as fh:
+                data = fh.read()
+            h, w, _ = _lib.jpeg_info(data)
+        except Exception:
+            continue
+        if h < 4 or w < 4:
+            continue
+        names.append(f); datas.append(data); sizes.append((h, w))
+    if not names:
+        return {}
+    H, W, pos = pack_atlas(sizes, ATLAS_MAX_WIDTH)
+    pitch = W * 3
+    dev = torch.device("cuda", sr.device)
+    atlas = torch.zeros(H * pitch, dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize(dev)
+    hs, ws, status = _lib.jpeg_decode_batch_dev(datas, atlas.data_ptr(), [y * pitch + x * 3 for x, y in pos], [pitch] * len(names), H * pitch,
+                                                bgr=True, device=sr.device)
+    keep = [i for i in range(len(names)) if status[i] >= 0 and (int(hs[i]), int(ws[i])) == sizes[i]]
+    if not keep:
+        return {}
+    s = sr.scale
+    boxes = np.asarray([[pos[i][0], pos[i][1], pos[i][0] + sizes[i][1], pos[i][1] + sizes[i][0]] for i in keep], np.int32)
+    cap = int(sum((sizes[i][0] * s * sizes[i][1] * s * 3 + 15) // 16 * 16 for i in keep))
+    out = torch.empty(cap + 64, dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize(dev)
+    offs = sr.enhance_crops_dev([atlas.data_ptr()], H, W, boxes, out.data_ptr(), cap, None, enhancer.tile, 10, True)
+    blobs = _lib.jpeg_encode_batch_dev(out.data_ptr(), offs[:len(keep)], [sizes[i][0] * s for i in keep], [sizes[i][1] * s for i in keep], 95, bgr=True,
+                                       device=sr.device)
+    return {names[i]: ((sizes[i][1], sizes[i][0]), (sizes[i][1] * s, sizes[i][0] * s), blob) for i, blob in zip(keep, blobs)}
+
+
 def enhance_face_crops_batch(crops_dir, enhancer, prefix="enhanced", progress_callback=None):
     results = {"enhanced_files": [], "failed_files": [], "enhancement_info": [],
                "statistics": {"total_files": 0, "successful": 0, "failed": 0, "total_time": 0}}
@@ -241,12 +312,19 @@ def enhance_face_crops_batch(crops_dir, enhancer, prefix="enhanced", progress_ca
     files = [f for f in os.listdir(crops_dir) if f.lower().endswith((".png", ".jpg", ".jpeg", ".bmp", ".tiff"))]
     results["statistics"]["total_files"] = len(files)
     t0 = time.time()
-    batched = {}
-    if type(enhancer) is FaceEnhancer and len(files) > 1:
+    batched, on_device = {}, {}
+    n_jpeg = sum(1 for f in files if f.lower().endswith((".jpg", ".jpeg")))
+    if type(enhancer) is FaceEnhancer and enhancer.upsampler is not None and BATCH_ROUTE_MIN_FILES is not None and n_jpeg >= BATCH_ROUTE_MIN_FILES:
+        try:
+            on_device = _crops_dir_on_device(crops_dir, files, enhancer)
+        except Exception:
+            on_device = {}
+    rest = [f for f in files if f not in on_device]
+    if type(enhancer) is FaceEnhancer and len(rest) > 1:
         # every readable crop through ONE ragged GPU batch (same bytes as the per-file loop below, which still runs for whatever the batch
         # could not take: unreadable files, failures, an enhancer subclass with its own enhance_face_crop)
         try:
-            imgs = [(f, _imread_bgr(os.path.join(crops_dir, f))) for f in files]
+            imgs = [(f, _imread_bgr(os.path.join(crops_dir, f))) for f in rest]
             outs = enhancer.enhance_images([im for _, im in imgs if im is not None])
             it = iter(outs)
             for f, im in imgs:
@@ -265,7 +343,18 @@ def enhance_face_crops_batch(crops_dir, enhancer, prefix="enhanced", progress_ca
             except Exception:
                 pass
         ok, info = False, None
-        if f in batched:
+        if f in on_device:
+            (ow, oh), (ew, eh), blob = on_device[f]
+            info = {"original_path": os.path.join(crops_dir, f), "output_path": dst, "original_size": (ow, oh), "enhanced_size": (ew, eh),
+                    "scale_factor": enhancer.scale, "success": False}
+            try:
+                os.makedirs(os.path.dirname(dst) or ".", exist_ok=True)
+                with open(dst, "wb") as fh:
+                    fh.write(blob)
+                ok = info["success"] = True
+            except Exception:
+                ok = False
+        elif f in batched:
             im, o = batched[f]
             info = {"original_path": os.path.join(crops_dir, f), "output_path": dst, "original_size": (im.shape[1], im.shape[0]),
                     "enhanced_size": (o.shape[1], o.shape[0]), "scale_factor": enhancer.scale, "success": False}

@@ -91,6 +91,65 @@ int ffp_jpeg_decode_stats(int64_t* device_decodes, int64_t* host_fallbacks, int6
   FFP_API_END
 }
 
+// n files in one pass (jpeg_huff.hip, jpeg_decode_batch_to_device). The call succeeds when its arguments were valid; what became of file i is status[i],
+// and ffp_last_error names the first file that failed.
+int ffp_jpeg_decode_batch_dev(int device, int n, const uint8_t* const* datas, const int64_t* sizes, int bgr, uint8_t* d_base, const int64_t* offsets,
+                              const int64_t* strides, int64_t cap, int32_t* hs, int32_t* ws, int32_t* status) {
+  FFP_API_BEGIN
+  FFP_CHECK(n >= 0 && (n == 0 || (datas && sizes && d_base && offsets && hs && ws && status)), FFP_ERR_ARG, "jpeg_decode_batch: bad arguments");
+  if (n > 0) {
+    ScopedStream cx(device, "jpeg_decode_batch", ScopedStream::Io);
+    static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(int) == sizeof(int32_t), "the ABI's integer types are the library's");
+    std::string first;
+    jpeg_decode_batch_to_device(n, datas, reinterpret_cast<const long long*>(sizes), bgr, d_base, reinterpret_cast<const long long*>(offsets),
+                                reinterpret_cast<const long long*>(strides), cap, hs, ws, status, &first, cx.st);
+    if (!first.empty()) set_last_error("jpeg_decode_batch: " + first);
+  }
+  FFP_API_END
+}
+
+int ffp_jpeg_decode_batch(int device, int n, const uint8_t* const* datas, const int64_t* sizes, int bgr, uint8_t* const* outs, const int64_t* caps, int32_t* hs,
+                          int32_t* ws, int32_t* status) {
+  FFP_API_BEGIN
+  FFP_CHECK(n >= 0 && (n == 0 || (datas && sizes && outs && caps && hs && ws && status)), FFP_ERR_ARG, "jpeg_decode_batch: bad arguments");
+  if (n > 0) {
+    // the headers first: the images are packed into one device buffer, 256-byte aligned; an unreadable file gets an empty region
+    std::vector<long long> off((size_t)n, 0);
+    long long total = 0;
+    for (int i = 0; i < n; ++i) {
+      off[i] = total;
+      JpegScan s;
+      try {
+        FFP_CHECK(datas[i] && sizes[i] > 0, FFP_ERR_ARG, "jpeg_decode_batch: no data");
+        jpeg_entropy_decode(datas[i], sizes[i], s, true);
+      } catch (const ffp::Error&) {
+        continue;                                            // the batch call reports it in status[i]
+      }
+      const long long bytes = (long long)s.h * s.w * 3;
+      FFP_CHECK(outs[i] && caps[i] >= bytes, FFP_ERR_ARG, "jpeg_decode_batch: output buffer %d too small for %dx%d", i, s.w, s.h);
+      total += (bytes + 255) / 256 * 256;
+    }
+    ScopedStream cx(device, "jpeg_decode_batch", ScopedStream::Io);
+    DevBuf d((size_t)std::max<long long>(total, 16));
+    std::string first;
+    jpeg_decode_batch_to_device(n, datas, reinterpret_cast<const long long*>(sizes), bgr, d.as<unsigned char>(), off.data(), nullptr, total, hs, ws, status, &first, cx.st);
+    for (int i = 0; i < n; ++i)
+      if (status[i] >= 0) FFP_HIP(hipMemcpy(outs[i], d.as<unsigned char>() + off[i], (size_t)hs[i] * ws[i] * 3, hipMemcpyDeviceToHost));
+    if (!first.empty()) set_last_error("jpeg_decode_batch: " + first);
+  }
+  FFP_API_END
+}
+
+int ffp_jpeg_decode_batch_stats(int64_t* batches, int64_t* launches_last_batch, int64_t* syncs_last_batch) {
+  FFP_API_BEGIN
+  long long a = 0, b = 0, c = 0;
+  jpeg_batch_stats(&a, &b, &c);
+  if (batches) *batches = a;
+  if (launches_last_batch) *launches_last_batch = b;
+  if (syncs_last_batch) *syncs_last_batch = c;
+  FFP_API_END
+}
+
 // ---- PNG at the file boundaries (png.hip) -----------------------------------------------------------------------------------------
 int64_t ffp_png_bound(int h, int w, int channels, int bit_depth) {
   try {

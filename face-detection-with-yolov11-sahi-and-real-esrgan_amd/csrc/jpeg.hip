@@ -18,6 +18,7 @@
 #include <cstdlib>
 
 #include "jpeg.hpp"
+#include "jpeg_batch_plan.hpp"
 
 namespace ffp {
 
@@ -588,20 +589,13 @@ __device__ __forceinline__ void idct8(int (&v)[8], bool first) {
 // One launch covers the components of the scan: workgroups [wg0[c], wg0[c + 1]) work on component c.
 struct IdctComp { const short* coef; unsigned char* plane; const unsigned short* qt; int n_blocks, blocks_x, wg0; };
 struct IdctArgs { IdctComp c[3]; int ncomp; };
-__global__ void __launch_bounds__(64) jpeg_idct_kernel(const IdctArgs A) {
+// blocks b0 .. b0 + 7 of one component: shared by the single-file kernel and the batch kernel
+__device__ __forceinline__ void idct_blocks(const short* __restrict__ coef, unsigned char* __restrict__ plane, const unsigned short* __restrict__ qt, int n_blocks, int blocks_x, int b0) {
   __shared__ int ws[8][64];
-  int ci = 0;
-  if (A.ncomp > 1 && (int)blockIdx.x >= A.c[1].wg0) ci = 1;
-  if (A.ncomp > 2 && (int)blockIdx.x >= A.c[2].wg0) ci = 2;
-  const short* __restrict__ coef = ci == 0 ? A.c[0].coef : ci == 1 ? A.c[1].coef : A.c[2].coef;
-  unsigned char* __restrict__ plane = ci == 0 ? A.c[0].plane : ci == 1 ? A.c[1].plane : A.c[2].plane;
-  const unsigned short* __restrict__ qt = ci == 0 ? A.c[0].qt : ci == 1 ? A.c[1].qt : A.c[2].qt;
-  const int n_blocks = ci == 0 ? A.c[0].n_blocks : ci == 1 ? A.c[1].n_blocks : A.c[2].n_blocks;
-  const int blocks_x = ci == 0 ? A.c[0].blocks_x : ci == 1 ? A.c[1].blocks_x : A.c[2].blocks_x;
-  const int wg0 = ci == 0 ? A.c[0].wg0 : ci == 1 ? A.c[1].wg0 : A.c[2].wg0;
   const int lb = threadIdx.x >> 3, idx = threadIdx.x & 7;
-  const int b = ((int)blockIdx.x - wg0) * 8 + lb;
+  const int b = b0 + lb;
   int v[8];
+
   if (b < n_blocks) {
 #pragma unroll
     for (int r = 0; r < 8; ++r) v[r] = (int)coef[(size_t)b * 64 + r * 8 + idx] * (int)qt[r * 8 + idx];
@@ -625,13 +619,23 @@ __global__ void __launch_bounds__(64) jpeg_idct_kernel(const IdctArgs A) {
     *reinterpret_cast<uint2*>(dst) = make_uint2(lo, hi);
   }
 }
+__global__ void __launch_bounds__(64) jpeg_idct_kernel(const IdctArgs A) {
+  int ci = 0;
+  if (A.ncomp > 1 && (int)blockIdx.x >= A.c[1].wg0) ci = 1;
+  if (A.ncomp > 2 && (int)blockIdx.x >= A.c[2].wg0) ci = 2;
+  const short* __restrict__ coef = ci == 0 ? A.c[0].coef : ci == 1 ? A.c[1].coef : A.c[2].coef;
+  unsigned char* __restrict__ plane = ci == 0 ? A.c[0].plane : ci == 1 ? A.c[1].plane : A.c[2].plane;
+  const unsigned short* __restrict__ qt = ci == 0 ? A.c[0].qt : ci == 1 ? A.c[1].qt : A.c[2].qt;
+  const int n_blocks = ci == 0 ? A.c[0].n_blocks : ci == 1 ? A.c[1].n_blocks : A.c[2].n_blocks;
+  const int blocks_x = ci == 0 ? A.c[0].blocks_x : ci == 1 ? A.c[1].blocks_x : A.c[2].blocks_x;
+  const int wg0 = ci == 0 ? A.c[0].wg0 : ci == 1 ? A.c[1].wg0 : A.c[2].wg0;
+  idct_blocks(coef, plane, qt, n_blocks, blocks_x, ((int)blockIdx.x - wg0) * 8);
+}
 
 // one thread per output pixel: chroma through libjpeg's "fancy" triangle upsampling (jdsample.c; replication when the component is
 // at most 2 samples wide), then jdcolor.c YCbCr -> RGB
-__global__ void jpeg_colour_kernel(const unsigned char* __restrict__ py, const unsigned char* __restrict__ pcb, const unsigned char* __restrict__ pcr, int h, int w,
-                                   int pitch_y, int pitch_c, int ch, int cw, int hsub, int vsub, int ncomp, int bgr, long long stride, unsigned char* __restrict__ out) {
-  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-  if (x >= w) return;
+__device__ __forceinline__ void colour_pixel(const unsigned char* __restrict__ py, const unsigned char* __restrict__ pcb, const unsigned char* __restrict__ pcr, int x, int y,
+                                             int pitch_y, int pitch_c, int ch, int cw, int hsub, int vsub, int ncomp, int bgr, long long stride, unsigned char* __restrict__ out) {
   const int Y = py[(size_t)y * pitch_y + x];
   int r, g, b;
   if (ncomp == 1) {
@@ -663,6 +667,33 @@ __global__ void jpeg_colour_kernel(const unsigned char* __restrict__ py, const u
   }
   unsigned char* o = out + (size_t)y * stride + (size_t)x * 3;
   o[0] = (unsigned char)(bgr ? b : r); o[1] = (unsigned char)g; o[2] = (unsigned char)(bgr ? r : b);
+}
+__global__ void jpeg_colour_kernel(const unsigned char* __restrict__ py, const unsigned char* __restrict__ pcb, const unsigned char* __restrict__ pcr, int h, int w,
+                                   int pitch_y, int pitch_c, int ch, int cw, int hsub, int vsub, int ncomp, int bgr, long long stride, unsigned char* __restrict__ out) {
+  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+  if (x >= w) return;
+  colour_pixel(py, pcb, pcr, x, y, pitch_y, pitch_c, ch, cw, hsub, vsub, ncomp, bgr, stride, out);
+}
+
+// ---- the same two stages for a batch: a workgroup finds its descriptor (sorted by wg0) by bisection ------------------------------------
+template <class D>
+__device__ __forceinline__ int find_desc(const D* d, int n, int wg) {
+  int lo = 0, hi = n;                            // the last descriptor with wg0 <= wg
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (d[mid].wg0 <= wg) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+__global__ void __launch_bounds__(64) jpeg_idct_batch_kernel(const JpegBatchIdct* __restrict__ D, int n) {
+  const JpegBatchIdct d = D[find_desc(D, n, (int)blockIdx.x)];
+  idct_blocks(d.coef, d.plane, d.qt, d.n_blocks, d.blocks_x, ((int)blockIdx.x - d.wg0) * 8);
+}
+__global__ void __launch_bounds__(64) jpeg_colour_batch_kernel(const JpegBatchColour* __restrict__ D, int n, int bgr) {
+  const JpegBatchColour d = D[find_desc(D, n, (int)blockIdx.x)];
+  const int r = (int)blockIdx.x - d.wg0, y = r / d.wgs_x, x = (r - y * d.wgs_x) * 64 + (int)threadIdx.x;
+  if (x >= d.w || y >= d.h) return;
+  colour_pixel(d.py, d.pcb, d.pcr, x, y, d.pitch_y, d.pitch_c, d.ch, d.cw, d.hsub, d.vsub, d.ncomp, bgr, d.stride, d.out);
 }
 
 }  // namespace
@@ -743,6 +774,13 @@ void jpeg_reconstruct_device(const JpegScan& s, JpegDecodeWs& ws, unsigned char*
   hipLaunchKernelGGL(jpeg_colour_kernel, dim3((s.w + 255) / 256, s.h), dim3(256), 0, st, ws.plane[0].as<unsigned char>(),
                      s.ncomp == 3 ? ws.plane[1].as<unsigned char>() : nullptr, s.ncomp == 3 ? ws.plane[2].as<unsigned char>() : nullptr, s.h, s.w,
                      s.comp[0].blocks_x * 8, s.ncomp == 3 ? s.comp[1].blocks_x * 8 : 0, ch, cw, hsub, vsub, s.ncomp, bgr, stride, d_out);
+  FFP_HIP(hipGetLastError());
+}
+
+void jpeg_batch_reconstruct(const JpegBatchIdct* d_idct, int n_idct, int n_idct_wg, const JpegBatchColour* d_colour, int n_img, int n_px_wg, int bgr, hipStream_t st) {
+  static_assert(jbp::IDCT_BLOCKS == 8 && jbp::PX_THREADS == 64, "the planner counts workgroups of these kernels");
+  hipLaunchKernelGGL(jpeg_idct_batch_kernel, dim3(n_idct_wg), dim3(64), 0, st, d_idct, n_idct);
+  hipLaunchKernelGGL(jpeg_colour_batch_kernel, dim3(n_px_wg), dim3(64), 0, st, d_colour, n_img, bgr);
   FFP_HIP(hipGetLastError());
 }
 

@@ -67,4 +67,24 @@ void jpeg_reconstruct_device(const JpegScan& s, JpegDecodeWs& ws, unsigned char*
 // header -> workspace -> entropy decode -> reconstruction, for a stream of `n` bytes (the decoding entry points of api_codec.cpp share it)
 void jpeg_decode_to_device(const unsigned char* data, long long n, unsigned char* d_out, long long stride, long long cap, int bgr, hipStream_t st, int* out_h, int* out_w);
 
+// ---- a batch of files in one pass (jpeg_huff.hip; the layout: jpeg_batch_plan.hpp) ------------------------------------------------------
+// Reconstruction of a batch: per-component and per-image descriptors in device memory, sorted by their first workgroup (wg0), so that a
+// workgroup finds its own by bisection. One launch per stage, whatever the number of images (jpeg.hip).
+struct JpegBatchIdct { const short* coef; unsigned char* plane; const unsigned short* qt; int n_blocks, blocks_x, wg0, pad; };
+struct JpegBatchColour {
+  const unsigned char *py, *pcb, *pcr;
+  unsigned char* out;
+  long long stride;
+  int h, w, pitch_y, pitch_c, ch, cw, hsub, vsub, ncomp, wg0, wgs_x, pad;
+};
+void jpeg_batch_reconstruct(const JpegBatchIdct* d_idct, int n_idct, int n_idct_wg, const JpegBatchColour* d_colour, int n_img, int n_px_wg, int bgr, hipStream_t st);
+// n files -> n images at d_base + offsets[i] (row pitch strides[i], 0 or strides == nullptr: packed). status[i]: 0 decoded on the device,
+// 1 by the host decoder, < 0 the FFP_ERR_* of a file that was not decoded (its region is untouched). A fixed number of launches, ONE upload,
+// ONE memset, ONE download and TWO stream synchronisations per sub-batch, whatever n is; a file whose stream needs further rounds of
+// synchronisation adds rounds for the sub-batch, a flagged file goes to the host decoder alone. Throws FFP_ERR_ARG, before anything is
+// queued, when a readable file's region does not lie inside cap. first_error: "file <i>: <why>" of the first file that failed, or empty.
+void jpeg_decode_batch_to_device(int n, const unsigned char* const* datas, const long long* sizes, int bgr, unsigned char* d_base, const long long* offsets,
+                                 const long long* strides, long long cap, int* hs, int* ws, int* status, std::string* first_error, hipStream_t st);
+void jpeg_batch_stats(long long* batches, long long* launches_last_batch, long long* syncs_last_batch);
+
 }  // namespace ffp

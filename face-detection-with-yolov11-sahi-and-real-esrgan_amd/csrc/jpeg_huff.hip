@@ -24,8 +24,13 @@
 #include <atomic>
 #include <cstddef>
 #include <cstring>
+#include <map>
+#include <mutex>
+#include <string>
+#include <vector>
 
 #include "jpeg.hpp"
+#include "jpeg_batch_plan.hpp"
 
 namespace ffp {
 
@@ -36,6 +41,7 @@ constexpr int NT = 128;                         // subsequences per workgroup
 constexpr int FB = 10;                          // index bits of the fast table
 constexpr int TILE = 1024;                      // bytes per unstuffing tile (256 threads x 4 bytes)
 constexpr int LDS_WORDS = NT * SUB_BITS / 32 + 8;
+static_assert(SUB_BITS == jbp::SUB_BITS && NT == jbp::NT && TILE == jbp::TILE && LDS_WORDS == jbp::LDS_WORDS, "jpeg_batch_plan.hpp sizes the batch by these");
 
 __constant__ unsigned char kZig[64] = {0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
                                        35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
@@ -90,8 +96,10 @@ struct Bufs {
 __device__ __forceinline__ bool is_rst(unsigned b) { return b >= 0xD0u && b <= 0xD7u; }
 
 // ---- 1. unstuffing ---------------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) jh_end_kernel(Bufs b, HuffParams P) {
-  const int i0 = (blockIdx.x * 256 + threadIdx.x) * 4;
+// Every stage is a body that takes its workgroup's index `blk` INSIDE the file, so that the single-file kernels (blk = blockIdx.x) and the
+// batch kernels further down (blk = blockIdx.x - the file's first workgroup) run the same code.
+__device__ __forceinline__ void jh_end_body(const Bufs& b, const HuffParams& P, int blk) {
+  const int i0 = (blk * 256 + threadIdx.x) * 4;
   for (int i = i0; i < min(i0 + 4, P.n_raw); ++i) {
     if (b.raw[i] != 0xFF) continue;
     if (i + 1 >= P.n_raw) { atomicMin(&b.scal->end, i); continue; }          // a dangling 0xFF: the host decoder stops there too
@@ -99,6 +107,7 @@ __global__ void __launch_bounds__(256) jh_end_kernel(Bufs b, HuffParams P) {
     if (!(m == 0 || m == 0xFF || is_rst(m))) atomicMin(&b.scal->end, i);
   }
 }
+__global__ void __launch_bounds__(256) jh_end_kernel(Bufs b, HuffParams P) { jh_end_body(b, P, (int)blockIdx.x); }
 
 // byte i < end of the raw stream: kept in the clean stream? an RSTn code byte?
 __device__ __forceinline__ void classify(const unsigned char* raw, int i, int n, bool* keep, bool* rst) {
@@ -112,12 +121,12 @@ __device__ __forceinline__ void classify(const unsigned char* raw, int i, int n,
   }
 }
 
-__global__ void __launch_bounds__(256) jh_count_kernel(Bufs b, HuffParams P) {
+__device__ __forceinline__ void jh_count_body(const Bufs& b, const HuffParams& P, int blk) {
   __shared__ unsigned s_keep, s_rst;
   if (threadIdx.x == 0) { s_keep = 0; s_rst = 0; }
   __syncthreads();
   const int end = b.scal->end;
-  const int i0 = blockIdx.x * TILE + threadIdx.x * 4;
+  const int i0 = blk * TILE + threadIdx.x * 4;
   unsigned k = 0, r = 0;
   for (int i = i0; i < min(i0 + 4, end); ++i) {
     bool keep, rst;
@@ -127,8 +136,9 @@ __global__ void __launch_bounds__(256) jh_count_kernel(Bufs b, HuffParams P) {
   if (k) atomicAdd(&s_keep, k);
   if (r) atomicAdd(&s_rst, r);
   __syncthreads();
-  if (threadIdx.x == 0) b.tile_cnt[blockIdx.x] = (unsigned long long)s_keep | ((unsigned long long)s_rst << 32);
+  if (threadIdx.x == 0) b.tile_cnt[blk] = (unsigned long long)s_keep | ((unsigned long long)s_rst << 32);
 }
+__global__ void __launch_bounds__(256) jh_count_kernel(Bufs b, HuffParams P) { jh_count_body(b, P, (int)blockIdx.x); }
 
 // exclusive scan of n 64-bit values by one workgroup of 1024 threads (each thread a contiguous run); returns the total
 __device__ unsigned long long block_scan_u64(unsigned long long* v, int n) {
@@ -151,7 +161,7 @@ __device__ unsigned long long block_scan_u64(unsigned long long* v, int n) {
   return total;
 }
 
-__global__ void __launch_bounds__(1024) jh_scan_tiles_kernel(Bufs b, HuffParams P, int n_tiles, int n_seg_expected) {
+__device__ __forceinline__ void jh_scan_tiles_body(const Bufs& b, const HuffParams& P, int n_tiles, int n_seg_expected) {
   const unsigned long long total = block_scan_u64(b.tile_cnt, n_tiles);
   if (threadIdx.x == 0) {
     const int kept = (int)(unsigned)total, n_seg = (int)(total >> 32) + 1;
@@ -161,11 +171,12 @@ __global__ void __launch_bounds__(1024) jh_scan_tiles_kernel(Bufs b, HuffParams 
     b.seg_start[min(n_seg, P.seg_cap)] = kept;
   }
 }
+__global__ void __launch_bounds__(1024) jh_scan_tiles_kernel(Bufs b, HuffParams P, int n_tiles, int n_seg_expected) { jh_scan_tiles_body(b, P, n_tiles, n_seg_expected); }
 
-__global__ void __launch_bounds__(256) jh_scatter_kernel(Bufs b, HuffParams P) {
+__device__ __forceinline__ void jh_scatter_body(const Bufs& b, const HuffParams& P, int blk) {
   __shared__ unsigned s_k[256], s_r[256];
   const int end = b.scal->end, tid = threadIdx.x;
-  const int i0 = blockIdx.x * TILE + tid * 4;
+  const int i0 = blk * TILE + tid * 4;
   bool keep[4], rst[4];
   unsigned k = 0, r = 0;
 #pragma unroll
@@ -182,7 +193,7 @@ __global__ void __launch_bounds__(256) jh_scatter_kernel(Bufs b, HuffParams P) {
     s_k[tid] += ak; s_r[tid] += ar;
     __syncthreads();
   }
-  const unsigned long long base = b.tile_cnt[blockIdx.x];
+  const unsigned long long base = b.tile_cnt[blk];
   unsigned ko = (unsigned)base + s_k[tid] - k, ro = (unsigned)(base >> 32) + s_r[tid] - r;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
@@ -190,9 +201,10 @@ __global__ void __launch_bounds__(256) jh_scatter_kernel(Bufs b, HuffParams P) {
     if (rst[j]) { ++ro; if ((int)ro < P.seg_cap) b.seg_start[ro] = (int)ko; }       // segment `ro` starts where the marker stood
   }
 }
+__global__ void __launch_bounds__(256) jh_scatter_kernel(Bufs b, HuffParams P) { jh_scatter_body(b, P, (int)blockIdx.x); }
 
 // ---- subsequence layout ------------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(1024) jh_segs_kernel(Bufs b, HuffParams P, unsigned long long* tmp) {
+__device__ __forceinline__ void jh_segs_body(const Bufs& b, const HuffParams& P, unsigned long long* tmp) {
   const int n_seg = b.scal->n_seg, total_clean = b.scal->total_clean;
   for (int k = threadIdx.x; k < n_seg; k += 1024) {
     const long long bits = (long long)(b.seg_start[k + 1] - b.seg_start[k]) * 8;
@@ -222,16 +234,17 @@ __global__ void __launch_bounds__(1024) jh_segs_kernel(Bufs b, HuffParams P, uns
     b.sub_start[t] = (unsigned)b.seg_start[lo] * 8u + (unsigned)(t - (int)tmp[lo]) * SUB_BITS;
   }
 }
+__global__ void __launch_bounds__(1024) jh_segs_kernel(Bufs b, HuffParams P, unsigned long long* tmp) { jh_segs_body(b, P, tmp); }
 
 // ---- tables --------------------------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) jh_tables_kernel(const HuffSpecDev* spec, HuffTabDev* tabs, Bufs b, HuffParams P) {
+__device__ __forceinline__ void jh_tables_body(const HuffSpecDev* spec, HuffTabDev* tabs, const Bufs& b, const HuffParams& P, int blk) {
   __shared__ int s_min[17], s_ptr[17], s_max[17];
-  if (blockIdx.x == 0 && threadIdx.x == 0) {     // the scalars of this decode
+  if (blk == 0 && threadIdx.x == 0) {     // the scalars of this decode
     b.scal->end = P.n_raw; b.scal->total_clean = 0; b.scal->n_seg = 1; b.scal->T = 0; b.scal->changed = 0; b.scal->err = 0;
     b.seg_start[0] = 0;
   }
-  const HuffSpecDev& sp = spec[blockIdx.x];
-  HuffTabDev& t = tabs[blockIdx.x];
+  const HuffSpecDev& sp = spec[blk];
+  HuffTabDev& t = tabs[blk];
   if (threadIdx.x == 0) {
     int code = 0, k = 0;
     for (int l = 1; l <= 16; ++l) {
@@ -254,6 +267,7 @@ __global__ void __launch_bounds__(256) jh_tables_kernel(const HuffSpecDev* spec,
     t.lut[e] = v;
   }
 }
+__global__ void __launch_bounds__(256) jh_tables_kernel(const HuffSpecDev* spec, HuffTabDev* tabs, Bufs b, HuffParams P) { jh_tables_body(spec, tabs, b, P, (int)blockIdx.x); }
 
 // ---- the decoding loop -----------------------------------------------------------------------------------------------------------------------
 struct HuffLds {
@@ -356,12 +370,12 @@ __device__ __forceinline__ void decode_run(const HuffLds& L, unsigned bit0, cons
 struct SubCtx { int t, seg; bool active, head; unsigned sub_start, sub_end, seg_end, bit0; };
 
 // fills the workgroup's LDS (tables + its part of the stream) and the thread's subsequence
-__device__ __forceinline__ SubCtx stage(const Bufs& b, HuffLds& L) {
+__device__ __forceinline__ SubCtx stage(const Bufs& b, HuffLds& L, int blk) {
   const int T = b.scal->T, tid = threadIdx.x;
   SubCtx x;
-  x.t = blockIdx.x * NT + tid;
+  x.t = blk * NT + tid;
   x.active = x.t < T;
-  const int t0 = blockIdx.x * NT;
+  const int t0 = blk * NT;
   const unsigned start0 = b.sub_start[min(t0, T - 1)];
   x.bit0 = start0 & ~31u;
   x.seg = 0; x.head = false; x.sub_start = x.sub_end = x.seg_end = 0;
@@ -383,10 +397,8 @@ __device__ __forceinline__ SubCtx stage(const Bufs& b, HuffLds& L) {
 
 // 2./3. synchronisation. FIRST: cold start; otherwise continue from the stored states with the predecessor WORKGROUP's last exit state.
 template <bool FIRST>
-__global__ void __launch_bounds__(NT) jh_sync_kernel(Bufs b, HuffParams P) {
-  __shared__ HuffLds L;
-  if (blockIdx.x * NT >= b.scal->T) return;
-  const SubCtx x = stage(b, L);
+__device__ __forceinline__ void jh_sync_body(const Bufs& b, const HuffParams& P, HuffLds& L, int blk) {
+  const SubCtx x = stage(b, L, blk);
   const int tid = threadIdx.x;
   unsigned long long entry = 0, exit_ = 0, exit_at_load = 0;
   int4 cnt = make_int4(0, 0, 0, 0);
@@ -428,9 +440,15 @@ __global__ void __launch_bounds__(NT) jh_sync_kernel(Bufs b, HuffParams P) {
     if (!FIRST && exit_ != exit_at_load && (tid == NT - 1 || x.t == b.scal->T - 1)) atomicOr(&b.scal->changed, 1);
   }
 }
+template <bool FIRST>
+__global__ void __launch_bounds__(NT) jh_sync_kernel(Bufs b, HuffParams P) {
+  __shared__ HuffLds L;
+  if (blockIdx.x * NT >= b.scal->T) return;
+  jh_sync_body<FIRST>(b, P, L, (int)blockIdx.x);
+}
 
 // 4. exclusive segmented scan over the subsequences: one workgroup, every thread a contiguous run
-__global__ void __launch_bounds__(1024) jh_prefix_kernel(Bufs b) {
+__device__ __forceinline__ void jh_prefix_body(const Bufs& b) {
   __shared__ int4 s_sum[1024];
   __shared__ int s_flag[1024];
   const int T = b.scal->T, tid = threadIdx.x, per = (T + 1023) / 1024, lo = min(tid * per, T), hi = min(lo + per, T);
@@ -461,12 +479,11 @@ __global__ void __launch_bounds__(1024) jh_prefix_kernel(Bufs b) {
     run = add(run, b.cnt[t]);
   }
 }
+__global__ void __launch_bounds__(1024) jh_prefix_kernel(Bufs b) { jh_prefix_body(b); }
 
 // 5. the coefficients
-__global__ void __launch_bounds__(NT) jh_write_kernel(Bufs b, HuffParams P) {
-  __shared__ HuffLds L;
-  if (blockIdx.x * NT >= b.scal->T) return;
-  const SubCtx x = stage(b, L);
+__device__ __forceinline__ void jh_write_body(const Bufs& b, const HuffParams& P, HuffLds& L, int blk) {
+  const SubCtx x = stage(b, L, blk);
   if (!x.active) return;
   const unsigned long long en = b.entry[x.t];
   unsigned p = (unsigned)(en >> 16);
@@ -481,6 +498,11 @@ __global__ void __launch_bounds__(NT) jh_write_kernel(Bufs b, HuffParams P) {
     if (g0 + pre.x + cnt.x != g_end || c != 0 || z != 0 || x.seg_end - p >= 8u) e |= E_COUNT;
   }
   if (e) atomicOr(&b.scal->err, e);
+}
+__global__ void __launch_bounds__(NT) jh_write_kernel(Bufs b, HuffParams P) {
+  __shared__ HuffLds L;
+  if (blockIdx.x * NT >= b.scal->T) return;
+  jh_write_body(b, P, L, (int)blockIdx.x);
 }
 
 std::atomic<long long> g_stat_device{0}, g_stat_fallback{0}, g_stat_rounds{0};
@@ -625,6 +647,326 @@ int jpeg_huff_finish(const JpegScan& s, JpegDecodeWs& ws, hipStream_t st) {
   if (sc->err) return 0;
   g_stat_device.fetch_add(1);
   return rc;
+}
+
+
+// ---- a batch of files in one pass ----------------------------------------------------------------------------------------------------------
+// Every file owns whole workgroups and whole unstuffing tiles (jpeg_batch_plan.hpp), and a descriptor in device memory with what the
+// single-file kernels get as arguments. The stage bodies above run unchanged; only where b, P and `blk` come from differs. Because a file's
+// first subsequence is a segment head (its entry state is exact and it adopts nobody's exit state) and b.exit_ is the file's own array,
+// nothing travels from one file's last subsequence into the next file's first.
+namespace {
+
+struct BatchFile {
+  Bufs b;
+  HuffParams P;
+  unsigned long long* tmp;
+  const HuffSpecDev* spec;
+  HuffTabDev* tabs;
+  int wg0, tile0, n_tiles, n_seg_expected;
+};
+
+__global__ void __launch_bounds__(256) jhb_tables_kernel(const BatchFile* __restrict__ F) {
+  const BatchFile& f = F[blockIdx.x / 6];
+  jh_tables_body(f.spec, f.tabs, f.b, f.P, (int)(blockIdx.x % 6));
+}
+__global__ void __launch_bounds__(256) jhb_end_kernel(const BatchFile* __restrict__ F, const int* __restrict__ tile_file) {
+  const BatchFile& f = F[tile_file[blockIdx.x]];
+  jh_end_body(f.b, f.P, (int)blockIdx.x - f.tile0);
+}
+__global__ void __launch_bounds__(256) jhb_count_kernel(const BatchFile* __restrict__ F, const int* __restrict__ tile_file) {
+  const BatchFile& f = F[tile_file[blockIdx.x]];
+  jh_count_body(f.b, f.P, (int)blockIdx.x - f.tile0);
+}
+__global__ void __launch_bounds__(1024) jhb_scan_tiles_kernel(const BatchFile* __restrict__ F) {
+  const BatchFile& f = F[blockIdx.x];
+  jh_scan_tiles_body(f.b, f.P, f.n_tiles, f.n_seg_expected);
+}
+__global__ void __launch_bounds__(256) jhb_scatter_kernel(const BatchFile* __restrict__ F, const int* __restrict__ tile_file) {
+  const BatchFile& f = F[tile_file[blockIdx.x]];
+  jh_scatter_body(f.b, f.P, (int)blockIdx.x - f.tile0);
+}
+__global__ void __launch_bounds__(1024) jhb_segs_kernel(const BatchFile* __restrict__ F) {
+  const BatchFile& f = F[blockIdx.x];
+  jh_segs_body(f.b, f.P, f.tmp);
+}
+__global__ void __launch_bounds__(1024) jhb_prefix_kernel(const BatchFile* __restrict__ F) { jh_prefix_body(F[blockIdx.x].b); }
+
+// the decoding loop indexes P by the block of the MCU: the file's copy goes to LDS next to its tables
+__device__ __forceinline__ void load_params(const BatchFile& f, HuffParams& sP) {
+  static_assert(sizeof(HuffParams) % 4 == 0 && sizeof(HuffParams) / 4 <= NT, "one word per thread");
+  if (threadIdx.x < sizeof(HuffParams) / 4) reinterpret_cast<int*>(&sP)[threadIdx.x] = reinterpret_cast<const int*>(&f.P)[threadIdx.x];
+  __syncthreads();
+}
+template <bool FIRST>
+__global__ void __launch_bounds__(NT) jhb_sync_kernel(const BatchFile* __restrict__ F, const int* __restrict__ wg_file) {
+  __shared__ HuffLds L;
+  __shared__ HuffParams sP;
+  const BatchFile& f = F[wg_file[blockIdx.x]];
+  const int blk = (int)blockIdx.x - f.wg0;
+  const Bufs b = f.b;
+  if (blk * NT >= b.scal->T) return;
+  load_params(f, sP);
+  jh_sync_body<FIRST>(b, sP, L, blk);
+}
+__global__ void __launch_bounds__(NT) jhb_write_kernel(const BatchFile* __restrict__ F, const int* __restrict__ wg_file) {
+  __shared__ HuffLds L;
+  __shared__ HuffParams sP;
+  const BatchFile& f = F[wg_file[blockIdx.x]];
+  const int blk = (int)blockIdx.x - f.wg0;
+  const Bufs b = f.b;
+  if (blk * NT >= b.scal->T) return;
+  load_params(f, sP);
+  jh_write_body(b, sP, L, blk);
+}
+
+struct BatchWs { HostPinned stage; DevBuf up, work, coef; };
+std::mutex g_batch_mu;                           // one batch at a time per process: the workspaces below are shared
+std::map<int, BatchWs*> g_batch_ws;              // per device, never freed (as the pooled single-file workspaces)
+std::atomic<long long> g_batch_count{0}, g_batch_launches{0}, g_batch_syncs{0};
+
+struct BatchCounters { long long launches = 0, syncs = 0; };
+
+// the host decoder for one file of a batch (what jpeg_decode_to_device does when the device decoder gave up)
+void host_decode_one(const unsigned char* data, long long n, JpegScan& s, unsigned char* d_out, long long stride, int bgr, hipStream_t st, BatchCounters& k) {
+  JpegDecodeWs* ws = jpeg_ws_acquire();
+  try {
+    ws->ensure_host(s);
+    jpeg_entropy_decode(data, n, s, false);
+    jpeg_reconstruct_device(s, *ws, d_out, stride, bgr, st, true);
+    FFP_HIP(hipStreamSynchronize(st));
+    k.launches += 2; k.syncs += 1;
+  } catch (...) {
+    jpeg_ws_release(ws);
+    throw;
+  }
+  jpeg_ws_release(ws);
+}
+
+}  // namespace
+
+void jpeg_batch_stats(long long* batches, long long* launches_last_batch, long long* syncs_last_batch) {
+  if (batches) *batches = g_batch_count.load();
+  if (launches_last_batch) *launches_last_batch = g_batch_launches.load();
+  if (syncs_last_batch) *syncs_last_batch = g_batch_syncs.load();
+}
+
+void jpeg_decode_batch_to_device(int n, const unsigned char* const* datas, const long long* sizes, int bgr, unsigned char* d_base, const long long* offsets,
+                                 const long long* strides, long long cap, int* hs, int* ws, int* status, std::string* first_error, hipStream_t st) {
+  if (first_error) first_error->clear();
+  if (n <= 0) return;
+  auto note = [&](int i, int code, const char* why) {
+    status[i] = -code;
+    if (first_error && first_error->empty()) *first_error = "file " + std::to_string(i) + ": " + why;
+  };
+  // 1. the markers of every file; an unreadable one keeps its status and is not looked at again
+  std::vector<JpegScan> scans((size_t)n);
+  std::vector<JpegHead> heads((size_t)n);
+  std::vector<unsigned char> readable((size_t)n, 0);
+  std::vector<long long> stride((size_t)n, 0);
+  for (int i = 0; i < n; ++i) {
+    hs[i] = ws[i] = 0; status[i] = 0;
+    try {
+      FFP_CHECK(datas[i] && sizes[i] > 0, FFP_ERR_ARG, "jpeg_decode_batch: no data");
+      jpeg_entropy_decode(datas[i], sizes[i], scans[i], true, &heads[i]);
+      hs[i] = scans[i].h; ws[i] = scans[i].w;
+      readable[i] = 1;
+    } catch (const Error& e) {
+      note(i, e.code, e.what());
+    }
+  }
+  // 2. every readable file's region inside cap, before anything is queued
+  for (int i = 0; i < n; ++i) {
+    if (!readable[i]) continue;
+    const JpegScan& s = scans[i];
+    stride[i] = strides && strides[i] ? strides[i] : (long long)s.w * 3;
+    FFP_CHECK(offsets[i] >= 0 && stride[i] >= (long long)s.w * 3 && offsets[i] <= cap && stride[i] * (s.h - 1) + (long long)s.w * 3 <= cap - offsets[i], FFP_ERR_ARG,
+              "jpeg_decode_batch: image %d (%dx%d at offset %lld, row pitch %lld) does not lie inside the %lld bytes of the output", i, s.w, s.h, offsets[i], stride[i], cap);
+  }
+  // 3. the layout
+  std::vector<jbp::FileIn> in((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    if (!readable[i]) continue;
+    const JpegScan& s = scans[i];
+    jbp::FileIn& f = in[i];
+    f.n_raw = sizes[i] - heads[i].data_off; f.h = s.h; f.w = s.w; f.ncomp = s.ncomp; f.dri = heads[i].dri;
+    for (int c = 0; c < s.ncomp; ++c) { f.hs[c] = s.comp[c].hs; f.vs[c] = s.comp[c].vs; f.blocks_x[c] = s.comp[c].blocks_x; f.blocks_y[c] = s.comp[c].blocks_y; }
+  }
+  const bool host_only = sw().jpeg_host_huffman;
+  std::vector<unsigned char> for_device = readable;
+  if (host_only) std::fill(for_device.begin(), for_device.end(), 0);
+  const jbp::Sizes sz{(long long)sizeof(BatchFile), (long long)sizeof(JpegBatchIdct), (long long)sizeof(JpegBatchColour), (long long)sizeof(HuffTabDev),
+                      (long long)sizeof(HuffSpecDev), (long long)sizeof(Scal)};
+  const jbp::Plan plan = jbp::plan_batch(in.data(), for_device.data(), n, sz);
+
+  std::lock_guard<std::mutex> lock(g_batch_mu);
+  BatchCounters k;
+  std::vector<unsigned char> to_host((size_t)n, 0);
+  for (int i = 0; i < n; ++i) to_host[i] = readable[i] && plan.files[i].sub < 0;
+  int dev = 0;
+  FFP_HIP(hipGetDevice(&dev));
+  BatchWs*& Wp = g_batch_ws[dev];
+  if (!Wp) Wp = new BatchWs();
+  BatchWs& W = *Wp;
+
+  for (const jbp::SubPlan& S : plan.subs) {
+    const int m = (int)S.files.size();
+    const size_t scal_host = (size_t)jbp::align_up(S.up_bytes);
+    W.stage.ensure(scal_host + (size_t)S.scal.bytes);
+    if ((size_t)S.up_bytes > W.up.n) W.up.alloc((size_t)S.up_bytes * 5 / 4);
+    if ((size_t)S.work_bytes > W.work.n) W.work.alloc((size_t)S.work_bytes * 5 / 4);
+    if ((size_t)S.coef_bytes > W.coef.n) W.coef.alloc((size_t)S.coef_bytes * 5 / 4);
+    unsigned char* hp = static_cast<unsigned char*>(W.stage.p);
+    unsigned char* up = W.up.as<unsigned char>();
+    unsigned char* work = W.work.as<unsigned char>();
+    unsigned char* coef = W.coef.as<unsigned char>();
+    std::memset(hp, 0, (size_t)S.spec.off + (size_t)S.spec.bytes);          // the tables; the raw bytes behind them are copied in below
+    BatchFile* hF = reinterpret_cast<BatchFile*>(hp + S.desc.off);
+    int* h_wg_file = reinterpret_cast<int*>(hp + S.wg_file.off);
+    int* h_tile_file = reinterpret_cast<int*>(hp + S.tile_file.off);
+    JpegBatchIdct* hI = reinterpret_cast<JpegBatchIdct*>(hp + S.idct.off);
+    JpegBatchColour* hC = reinterpret_cast<JpegBatchColour*>(hp + S.colour.off);
+    unsigned short* hQ = reinterpret_cast<unsigned short*>(hp + S.qt.off);
+    HuffSpecDev* hS = reinterpret_cast<HuffSpecDev*>(hp + S.spec.off);
+    for (int j = 0; j < m; ++j) {
+      const int i = S.files[j];
+      const jbp::FilePlan& p = plan.files[i];
+      const JpegScan& s = scans[i];
+      const JpegHead& head = heads[i];
+      BatchFile& f = hF[j];
+      HuffParams& P = f.P;
+      P.ncomp = s.ncomp;
+      for (int c = 0; c < s.ncomp; ++c) {
+        P.hs[c] = s.comp[c].hs; P.vs[c] = s.comp[c].vs; P.blocks_x[c] = s.comp[c].blocks_x;
+        for (int dy = 0; dy < s.comp[c].vs; ++dy)
+          for (int dx = 0; dx < s.comp[c].hs; ++dx) { P.blk_comp[P.bpm] = c; P.blk_dx[P.bpm] = dx; P.blk_dy[P.bpm] = dy; ++P.bpm; }       // the planner admitted bpm <= 6
+        P.coef[c] = reinterpret_cast<short*>(coef + p.coef[c].off);
+      }
+      P.mcus_x = p.mcus_x; P.total_mcus = p.total_mcus; P.dri = head.dri; P.n_raw = (int)in[i].n_raw;
+      P.seg_cap = p.seg_cap; P.t_cap = p.t_cap;
+      Bufs& b = f.b;
+      b.raw = up + p.raw.off; b.clean = work + p.clean.off;
+      b.tile_cnt = reinterpret_cast<unsigned long long*>(work + p.tile_cnt.off);
+      b.seg_start = reinterpret_cast<int*>(work + p.seg_start.off); b.first_sub = reinterpret_cast<int*>(work + p.first_sub.off);
+      b.sub_start = reinterpret_cast<unsigned*>(work + p.sub_start.off); b.sub_seg = reinterpret_cast<int*>(work + p.sub_seg.off);
+      b.entry = reinterpret_cast<unsigned long long*>(work + p.entry.off); b.exit_ = reinterpret_cast<unsigned long long*>(work + p.exit_.off);
+      b.cnt = reinterpret_cast<int4*>(work + p.cnt.off); b.pref = reinterpret_cast<int4*>(work + p.pref.off);
+      b.tabs = reinterpret_cast<const HuffTabDev*>(work + p.tabs.off); b.scal = reinterpret_cast<Scal*>(work + p.scal.off);
+      f.tmp = reinterpret_cast<unsigned long long*>(work + p.tmp.off);
+      f.spec = reinterpret_cast<const HuffSpecDev*>(up + S.spec.off) + (size_t)j * 6;
+      f.tabs = reinterpret_cast<HuffTabDev*>(work + p.tabs.off);
+      f.wg0 = p.wg0; f.tile0 = p.tile0; f.n_tiles = p.n_tiles; f.n_seg_expected = p.n_seg_expected;
+      std::fill(h_wg_file + p.wg0, h_wg_file + p.wg0 + p.n_wg, j);
+      std::fill(h_tile_file + p.tile0, h_tile_file + p.tile0 + p.n_tiles, j);
+      std::memcpy(hQ + (size_t)j * 256, s.qt, sizeof(unsigned short) * 256);
+      for (int c = 0; c < s.ncomp; ++c) {
+        for (int t = 0; t < 2; ++t) {
+          const JpegHuffSpec& sp = t ? head.ac[s.comp[c].ta] : head.dc[s.comp[c].td];
+          std::memcpy(hS[(size_t)j * 6 + c * 2 + t].bits, sp.bits, 16);
+          std::memcpy(hS[(size_t)j * 6 + c * 2 + t].vals, sp.vals, (size_t)sp.n);
+        }
+        hI[p.idct_slot0 + c] = JpegBatchIdct{P.coef[c], work + p.plane[c].off, reinterpret_cast<const unsigned short*>(up + S.qt.off) + (size_t)j * 256 + 64 * s.comp[c].tq,
+                                             s.comp[c].blocks_x * s.comp[c].blocks_y, s.comp[c].blocks_x, p.idct_wg0[c], 0};
+      }
+      const int hsub = s.ncomp == 3 ? s.hmax : 1, vsub = s.ncomp == 3 ? s.vmax : 1;
+      JpegBatchColour& cd = hC[j];
+      cd.py = work + p.plane[0].off;
+      cd.pcb = s.ncomp == 3 ? work + p.plane[1].off : nullptr;
+      cd.pcr = s.ncomp == 3 ? work + p.plane[2].off : nullptr;
+      cd.out = d_base + offsets[i]; cd.stride = stride[i];
+      cd.h = s.h; cd.w = s.w; cd.pitch_y = s.comp[0].blocks_x * 8; cd.pitch_c = s.ncomp == 3 ? s.comp[1].blocks_x * 8 : 0;
+      cd.ch = (s.h + vsub - 1) / vsub; cd.cw = (s.w + hsub - 1) / hsub; cd.hsub = hsub; cd.vsub = vsub; cd.ncomp = s.ncomp;
+      cd.wg0 = p.px_wg0; cd.wgs_x = p.px_wgs_x; cd.pad = 0;
+      std::memcpy(hp + p.raw.off, datas[i] + head.data_off, (size_t)in[i].n_raw);
+    }
+    const BatchFile* dF = reinterpret_cast<const BatchFile*>(up + S.desc.off);
+    const int* d_wg_file = reinterpret_cast<const int*>(up + S.wg_file.off);
+    const int* d_tile_file = reinterpret_cast<const int*>(up + S.tile_file.off);
+    Scal* h_scal = reinterpret_cast<Scal*>(hp + scal_host);
+    auto download = [&]() {
+      FFP_HIP(hipMemcpyAsync(h_scal, work + S.scal.off, (size_t)S.scal.bytes, hipMemcpyDeviceToHost, st));
+      FFP_HIP(hipStreamSynchronize(st));
+      k.syncs += 1;
+    };
+    auto scan_and_write = [&]() {
+      hipLaunchKernelGGL(jhb_prefix_kernel, dim3(m), dim3(1024), 0, st, dF);
+      hipLaunchKernelGGL(jhb_write_kernel, dim3(S.n_wg), dim3(NT), 0, st, dF, d_wg_file);
+      k.launches += 2;
+    };
+    auto reconstruct = [&]() {
+      jpeg_batch_reconstruct(reinterpret_cast<const JpegBatchIdct*>(up + S.idct.off), S.n_idct, S.n_idct_wg, reinterpret_cast<const JpegBatchColour*>(up + S.colour.off), m,
+                             S.n_px_wg, bgr, st);
+      k.launches += 2;
+    };
+    FFP_HIP(hipMemcpyAsync(up, hp, (size_t)S.up_bytes, hipMemcpyHostToDevice, st));
+    FFP_HIP(hipMemsetAsync(coef, 0, (size_t)S.coef_bytes, st));
+    hipLaunchKernelGGL(jhb_tables_kernel, dim3(m * 6), dim3(256), 0, st, dF);
+    hipLaunchKernelGGL(jhb_end_kernel, dim3(S.n_tiles), dim3(256), 0, st, dF, d_tile_file);
+    hipLaunchKernelGGL(jhb_count_kernel, dim3(S.n_tiles), dim3(256), 0, st, dF, d_tile_file);
+    hipLaunchKernelGGL(jhb_scan_tiles_kernel, dim3(m), dim3(1024), 0, st, dF);
+    hipLaunchKernelGGL(jhb_scatter_kernel, dim3(S.n_tiles), dim3(256), 0, st, dF, d_tile_file);
+    hipLaunchKernelGGL(jhb_segs_kernel, dim3(m), dim3(1024), 0, st, dF);
+    hipLaunchKernelGGL(jhb_sync_kernel<true>, dim3(S.n_wg), dim3(NT), 0, st, dF, d_wg_file);
+    hipLaunchKernelGGL(jhb_sync_kernel<false>, dim3(S.n_wg), dim3(NT), 0, st, dF, d_wg_file);
+    k.launches += 8;
+    scan_and_write();
+    FFP_HIP(hipGetLastError());
+    // Unlike the single-file path, the reconstruction is NOT queued blindly: it writes into the caller's memory, and the region of a file
+    // that is not decoded in the end (flagged here, then refused by the host decoder too) has to stay untouched. So the scalars come down
+    // first, and the two reconstruction launches follow with the flagged files blanked out: two synchronisations per sub-batch, always.
+    download();
+    std::vector<int> sticky((size_t)m, 0);
+    bool more = false;
+    for (int j = 0; j < m; ++j) {
+      sticky[j] = h_scal[j].err & (E_SEGS | E_CAP);
+      if (h_scal[j].changed && !sticky[j]) more = true;
+    }
+    if (more) {
+      // some workgroup's last exit state moved in the round that was queued blindly: rounds for the sub-batch until none moves, then the
+      // scan and the write pass again, for all files (the ones that did not move get the same coefficients again)
+      int rounds = 0;
+      const int limit = S.n_wg + 2;
+      do {
+        FFP_HIP(hipMemset2DAsync(work + S.scal.off + offsetof(Scal, changed), sizeof(Scal), 0, sizeof(int), (size_t)m, st));
+        hipLaunchKernelGGL(jhb_sync_kernel<false>, dim3(S.n_wg), dim3(NT), 0, st, dF, d_wg_file);
+        k.launches += 1;
+        download();
+        g_stat_rounds.fetch_add(1);
+        more = false;
+        for (int j = 0; j < m; ++j) more = more || (h_scal[j].changed && !sticky[j]);
+      } while (more && ++rounds < limit);
+      for (int j = 0; j < m; ++j)
+        if (h_scal[j].changed) sticky[j] |= E_CAP;                             // did not settle: the host decoder
+      FFP_HIP(hipMemset2DAsync(work + S.scal.off + offsetof(Scal, err), sizeof(Scal), 0, sizeof(int), (size_t)m, st));     // flags of the premature write pass
+      FFP_HIP(hipMemsetAsync(coef, 0, (size_t)S.coef_bytes, st));
+      scan_and_write();
+      download();
+    }
+    // files whose flags are set leave the batch: blank out their colour descriptors (h = 0: no pixel is written), the rest is reconstructed
+    bool any_bad = false;
+    for (int j = 0; j < m; ++j)
+      if (h_scal[j].err | sticky[j]) { hC[j].h = 0; to_host[S.files[j]] = 1; any_bad = true; }
+    if (any_bad) FFP_HIP(hipMemcpyAsync(up + S.colour.off, hC, (size_t)S.colour.bytes, hipMemcpyHostToDevice, st));
+    reconstruct();
+    FFP_HIP(hipStreamSynchronize(st));
+    k.syncs += 1;
+    for (int j = 0; j < m; ++j)
+      if (!to_host[S.files[j]]) g_stat_device.fetch_add(1);
+  }
+  // 4. the host decoder, file by file, for what the device decoder did not take or gave up on
+  for (int i = 0; i < n; ++i) {
+    if (!to_host[i]) continue;
+    if (!host_only) jpeg_huff_note_fallback();
+    try {
+      host_decode_one(datas[i], sizes[i], scans[i], d_base + offsets[i], stride[i], bgr, st, k);
+      status[i] = 1;
+    } catch (const Error& e) {
+      note(i, e.code, e.what());
+    }
+  }
+  g_batch_count.fetch_add(1);
+  g_batch_launches.store(k.launches);
+  g_batch_syncs.store(k.syncs);
 }
 
 }  // namespace ffp

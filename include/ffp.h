@@ -375,6 +375,24 @@ int ffp_jpeg_decode_dev(int device, const uint8_t* data, int64_t n, int bgr, uin
  * decoded again by the host decoder (FFP_JPEG_HOST_HUFFMAN=1 forces it for every file). Counters since the library was loaded:
  * files decoded on the device, files that fell back to the host decoder, extra synchronisation rounds (beyond the one queued blindly). */
 int ffp_jpeg_decode_stats(int64_t* device_decodes, int64_t* host_fallbacks, int64_t* extra_sync_rounds);
+/* The read side of the per-crop loop of enhance_face_crops_batch (/root/reference/utils/enhancer.py:344-391: one cv2.imread per crop,
+ * utils/enhancer.py:254) as ONE pass: n JPEG files -> n images in device memory. File i is datas[i][0 .. sizes[i]); image i is written at
+ * d_base + offsets[i] with row pitch strides[i] bytes (NULL or 0: packed, ws[i]*3). hs/ws (out, n entries) are filled from the headers.
+ * status (out, n entries): 0 decoded on the device, 1 decoded by the host decoder, < 0 minus the FFP_ERR_* of a file that was not decoded
+ * (progressive, arithmetic, not a JPEG, damaged beyond the host decoder): its region is left untouched. The call returns FFP_OK when the
+ * arguments were valid, even if files failed; ffp_last_error then names the first failed index and why. A null array, n < 0, or a readable
+ * file's region that does not lie inside cap: FFP_ERR_ARG before anything is launched. n == 0: FFP_OK. The number of kernel launches and
+ * stream synchronisations does not depend on n (csrc/jpeg_batch_plan.hpp: every file owns whole workgroups; one upload, one memset, one
+ * launch per stage, one download of all files' scalars); batches whose streams would pass 256 MiB are cut into sub-batches.
+ * ffp_jpeg_decode_batch: the same into n host buffers of caps[i] bytes (a readable file whose buffer is too small: FFP_ERR_ARG).
+ * ffp_jpeg_decode_stats keeps counting files; FFP_JPEG_HOST_HUFFMAN=1 sends every file of a batch to the host decoder.
+ * ffp_jpeg_decode_batch_stats: batches since load, kernel launches and stream synchronisations of the latest one. */
+int ffp_jpeg_decode_batch_dev(int device, int n, const uint8_t* const* datas, const int64_t* sizes, int bgr,
+                              uint8_t* d_base, const int64_t* offsets, const int64_t* strides, int64_t cap,
+                              int32_t* hs, int32_t* ws, int32_t* status);
+int ffp_jpeg_decode_batch(int device, int n, const uint8_t* const* datas, const int64_t* sizes, int bgr,
+                          uint8_t* const* outs, const int64_t* caps, int32_t* hs, int32_t* ws, int32_t* status);
+int ffp_jpeg_decode_batch_stats(int64_t* batches, int64_t* launches_last_batch, int64_t* syncs_last_batch);
 
 /* ---------------------------------------------------------------------------------------------------------
  * PNG at the file boundaries (written and read on the device; palette, sub-byte, gray+alpha and interlaced files stay with the host)
