@@ -63,7 +63,7 @@ int ffp_jpeg_decode_dev(int device, const uint8_t* data, int64_t n, int bgr, uin
   FFP_API_BEGIN
   FFP_CHECK(data && d_out, FFP_ERR_ARG, "jpeg_decode: null argument");
   ScopedStream cx(device, "jpeg_decode", ScopedStream::Io);
-  jpeg_decode_to_device(data, n, d_out, row_stride, cap, bgr, cx.st, nullptr, nullptr);
+  jpeg_decode_to_device(data, n, d_out, row_stride, cap, bgr, cx.st);
   FFP_API_END
 }
 
@@ -76,7 +76,7 @@ int ffp_jpeg_decode(int device, const uint8_t* data, int64_t n, int bgr, uint8_t
   const size_t bytes = (size_t)s.h * s.w * 3;
   FFP_CHECK(cap >= (int64_t)bytes, FFP_ERR_ARG, "jpeg_decode: output buffer too small for %dx%d", s.w, s.h);
   DevBuf d(bytes);
-  jpeg_decode_to_device(data, n, d.as<unsigned char>(), 0, (long long)bytes, bgr, cx.st, nullptr, nullptr);
+  jpeg_decode_to_device(data, n, d.as<unsigned char>(), 0, (long long)bytes, bgr, cx.st);
   FFP_HIP(hipMemcpy(out, d.p, bytes, hipMemcpyDeviceToHost));
   FFP_API_END
 }
@@ -92,18 +92,30 @@ int ffp_jpeg_decode_stats(int64_t* device_decodes, int64_t* host_fallbacks, int6
 }
 
 // n files in one pass (jpeg_huff.hip, jpeg_decode_batch_to_device). The call succeeds when its arguments were valid; what became of file i is status[i],
-// and ffp_last_error names the first file that failed.
+// and ffp_last_error names the first file that failed. What only a batch entry reports is done here, after the routine the single-file entries share:
+// the batch counters, and that name.
+static void decode_batch(int n, const uint8_t* const* datas, const int64_t* sizes, int bgr, uint8_t* d_base, const long long* offsets, const int64_t* strides,
+                         int64_t cap, int32_t* hs, int32_t* ws, int32_t* status, hipStream_t st) {
+  static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(int) == sizeof(int32_t), "the ABI's integer types are the library's");
+  std::vector<std::string> why((size_t)n);
+  JpegBatchCost cost;
+  jpeg_decode_batch_to_device(n, datas, reinterpret_cast<const long long*>(sizes), bgr, d_base, offsets, reinterpret_cast<const long long*>(strides), cap, hs, ws, status,
+                              why.data(), &cost, st);
+  jpeg_batch_note(cost);
+  for (int i = 0; i < n; ++i)
+    if (status[i] < 0) {
+      set_last_error("jpeg_decode_batch: file " + std::to_string(i) + ": " + why[(size_t)i]);
+      break;
+    }
+}
+
 int ffp_jpeg_decode_batch_dev(int device, int n, const uint8_t* const* datas, const int64_t* sizes, int bgr, uint8_t* d_base, const int64_t* offsets,
                               const int64_t* strides, int64_t cap, int32_t* hs, int32_t* ws, int32_t* status) {
   FFP_API_BEGIN
   FFP_CHECK(n >= 0 && (n == 0 || (datas && sizes && d_base && offsets && hs && ws && status)), FFP_ERR_ARG, "jpeg_decode_batch: bad arguments");
   if (n > 0) {
     ScopedStream cx(device, "jpeg_decode_batch", ScopedStream::Io);
-    static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(int) == sizeof(int32_t), "the ABI's integer types are the library's");
-    std::string first;
-    jpeg_decode_batch_to_device(n, datas, reinterpret_cast<const long long*>(sizes), bgr, d_base, reinterpret_cast<const long long*>(offsets),
-                                reinterpret_cast<const long long*>(strides), cap, hs, ws, status, &first, cx.st);
-    if (!first.empty()) set_last_error("jpeg_decode_batch: " + first);
+    decode_batch(n, datas, sizes, bgr, d_base, reinterpret_cast<const long long*>(offsets), strides, cap, hs, ws, status, cx.st);
   }
   FFP_API_END
 }
@@ -131,11 +143,9 @@ int ffp_jpeg_decode_batch(int device, int n, const uint8_t* const* datas, const 
     }
     ScopedStream cx(device, "jpeg_decode_batch", ScopedStream::Io);
     DevBuf d((size_t)std::max<long long>(total, 16));
-    std::string first;
-    jpeg_decode_batch_to_device(n, datas, reinterpret_cast<const long long*>(sizes), bgr, d.as<unsigned char>(), off.data(), nullptr, total, hs, ws, status, &first, cx.st);
+    decode_batch(n, datas, sizes, bgr, d.as<unsigned char>(), off.data(), nullptr, total, hs, ws, status, cx.st);
     for (int i = 0; i < n; ++i)
       if (status[i] >= 0) FFP_HIP(hipMemcpy(outs[i], d.as<unsigned char>() + off[i], (size_t)hs[i] * ws[i] * 3, hipMemcpyDeviceToHost));
-    if (!first.empty()) set_last_error("jpeg_decode_batch: " + first);
   }
   FFP_API_END
 }

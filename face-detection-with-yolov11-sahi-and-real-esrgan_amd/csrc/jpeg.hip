@@ -589,7 +589,7 @@ __device__ __forceinline__ void idct8(int (&v)[8], bool first) {
 // One launch covers the components of the scan: workgroups [wg0[c], wg0[c + 1]) work on component c.
 struct IdctComp { const short* coef; unsigned char* plane; const unsigned short* qt; int n_blocks, blocks_x, wg0; };
 struct IdctArgs { IdctComp c[3]; int ncomp; };
-// blocks b0 .. b0 + 7 of one component: shared by the single-file kernel and the batch kernel
+// blocks b0 .. b0 + 7 of one component: shared by the host decoder's kernel (one file, arguments by value) and the batch kernel
 __device__ __forceinline__ void idct_blocks(const short* __restrict__ coef, unsigned char* __restrict__ plane, const unsigned short* __restrict__ qt, int n_blocks, int blocks_x, int b0) {
   __shared__ int ws[8][64];
   const int lb = threadIdx.x >> 3, idx = threadIdx.x & 7;
@@ -709,8 +709,7 @@ void JpegDecodeWs::ensure(const JpegScan& s) {
     }
     off[c + 1] = off[c] + ((nb * 64 * sizeof(short) + 255) & ~(size_t)255);
   }
-  coef_bytes = off[s.ncomp];
-  if (coef_bytes > coef_all.n) coef_all.alloc(coef_bytes * 5 / 4);
+  if (off[s.ncomp] > coef_all.n) coef_all.alloc(off[s.ncomp] * 5 / 4);
   for (int c = 0; c < s.ncomp; ++c) dev[c] = reinterpret_cast<short*>(static_cast<unsigned char*>(coef_all.p) + off[c]);
 }
 
@@ -755,7 +754,7 @@ void jpeg_ws_release(JpegDecodeWs* ws) {
   if (cur != owner) (void)hipSetDevice(cur);
 }
 
-void jpeg_reconstruct_device(const JpegScan& s, JpegDecodeWs& ws, unsigned char* d_out, long long stride, int bgr, hipStream_t st, bool upload) {
+void jpeg_reconstruct_device(const JpegScan& s, JpegDecodeWs& ws, unsigned char* d_out, long long stride, int bgr, hipStream_t st) {
   FFP_HIP(hipMemcpyAsync(ws.qt.p, s.qt, sizeof(unsigned short) * 64 * 4, hipMemcpyHostToDevice, st));
   IdctArgs A;
   A.ncomp = s.ncomp;
@@ -764,7 +763,7 @@ void jpeg_reconstruct_device(const JpegScan& s, JpegDecodeWs& ws, unsigned char*
   for (int c = 0; c < s.ncomp; ++c) {
     const JpegComp& cp = s.comp[c];
     const int nb = cp.blocks_x * cp.blocks_y;
-    if (upload) FFP_HIP(hipMemcpyAsync(ws.dev[c], s.coef[c], (size_t)nb * 64 * sizeof(short), hipMemcpyHostToDevice, st));
+    FFP_HIP(hipMemcpyAsync(ws.dev[c], s.coef[c], (size_t)nb * 64 * sizeof(short), hipMemcpyHostToDevice, st));
     A.c[c] = IdctComp{ws.dev[c], ws.plane[c].as<unsigned char>(), ws.qt.as<unsigned short>() + 64 * cp.tq, nb, cp.blocks_x, wg};
     wg += (nb + 7) / 8;
   }
@@ -784,43 +783,20 @@ void jpeg_batch_reconstruct(const JpegBatchIdct* d_idct, int n_idct, int n_idct_
   FFP_HIP(hipGetLastError());
 }
 
-void jpeg_decode_to_device(const unsigned char* data, long long n, unsigned char* d_out, long long stride, long long cap, int bgr, hipStream_t st, int* out_h, int* out_w) {
+// One file is a batch of one, as jpeg_encode_device is of jpeg_encode_batch_device. The header is read here first, so that whatever the
+// markers refuse, and a buffer that is too small, fail as a single file's always did, with nothing queued; what can come back in `status` is
+// then only the host decoder's refusal of a damaged stream, and it is thrown as it was recorded.
+void jpeg_decode_to_device(const unsigned char* data, long long n, unsigned char* d_out, long long stride, long long cap, int bgr, hipStream_t st) {
   JpegScan s;
-  JpegHead head;
-  jpeg_entropy_decode(data, n, s, true, &head);
-  if (out_h) *out_h = s.h;
-  if (out_w) *out_w = s.w;
+  jpeg_entropy_decode(data, n, s, true);
   if (stride == 0) stride = (long long)s.w * 3;
   FFP_CHECK(stride >= (long long)s.w * 3 && cap >= stride * (s.h - 1) + (long long)s.w * 3, FFP_ERR_ARG, "jpeg_decode: output buffer too small for %dx%d", s.w, s.h);
-  JpegDecodeWs* ws = jpeg_ws_acquire();
-  try {
-    ws->ensure(s);
-    bool done = false;
-    if (!sw().jpeg_host_huffman) {      // FFP_JPEG_HOST_HUFFMAN=1: entropy decoding on the host for every file (round-2 behaviour; A/B and the fallback's own tests)
-      // the whole decode is queued in one go — entropy decoding (jpeg_huff.hip) and reconstruction — and checked after ONE synchronisation
-      if (jpeg_huff_decode_async(data, n, s, head, *ws, st)) {
-        jpeg_reconstruct_device(s, *ws, d_out, stride, bgr, st, false);
-        FFP_HIP(hipStreamSynchronize(st));
-        const int rc = jpeg_huff_finish(s, *ws, st);
-        if (rc == 2) {
-          jpeg_reconstruct_device(s, *ws, d_out, stride, bgr, st, false);
-          FFP_HIP(hipStreamSynchronize(st));
-        }
-        done = rc != 0;
-      }
-      if (!done) jpeg_huff_note_fallback();
-    }
-    if (!done) {                                 // the host decoder: libjpeg's behaviour on damaged streams, and its error reports
-      ws->ensure_host(s);
-      jpeg_entropy_decode(data, n, s, false);
-      jpeg_reconstruct_device(s, *ws, d_out, stride, bgr, st, true);
-      FFP_HIP(hipStreamSynchronize(st));         // the staging planes go back to the pool after this
-    }
-  } catch (...) {
-    jpeg_ws_release(ws);
-    throw;
-  }
-  jpeg_ws_release(ws);
+  const long long offset = 0;
+  int h = 0, w = 0, status = 0;
+  std::string why;
+  jpeg_decode_batch_to_device(1, &data, &n, bgr, d_out, &offset, &stride, cap, &h, &w, &status, &why, nullptr, st);
+  if (status < 0) throw Error(-status, why);
 }
 
 }  // namespace ffp
+

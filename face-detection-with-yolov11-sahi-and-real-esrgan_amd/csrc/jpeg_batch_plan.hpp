@@ -1,6 +1,7 @@
 // jpeg_batch_plan.hpp — where everything of a BATCH of JPEG decodes lives (jpeg_huff.hip / jpeg.hip, jpeg_decode_batch_to_device): plain C++,
 // no HIP, because every number here is computed from the headers of untrusted files and is checked on the CPU under sanitizers
-// (csrc/jpeg_batch_plan_host_check.cpp, tests/test_jpeg_batch_host.py).
+// (csrc/jpeg_batch_plan_host_check.cpp, tests/test_jpeg_batch_host.py). A single file (ffp_jpeg_decode*) is a batch of one, so this is also
+// the only place where the buffers of a frame's decode are sized.
 //
 // A batch is cut into SUB-BATCHES of consecutive eligible files; one sub-batch is one launch sequence. Inside a sub-batch every file owns
 //   * whole workgroups of the subsequence kernels (jh_sync / jh_write): [wg0, wg0 + n_wg), n_wg = ceil(t_cap / NT),

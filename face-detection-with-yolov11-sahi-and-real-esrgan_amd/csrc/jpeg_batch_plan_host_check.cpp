@@ -173,6 +173,27 @@ int main() {
     std::vector<FileIn> big{image(64, 64, 3, 2, 2, 0, STREAM_LIMIT - CLEAN_PAD - ALIGN), image(64, 64, 3, 2, 2, 0, STREAM_LIMIT - CLEAN_PAD), image(8, 8, 1, 1, 1, 0, 10)};
     EXPECT(check(big, nullptr, "one huge file") == 2, "a file just under the limit is a sub-batch of its own, one at the limit goes to the host");
   }
+  // plans of exactly one file: what every single-file decode (ffp_jpeg_decode*) runs on — the planner sizes the buffers of a frame
+  {
+    struct One { const char* name; FileIn f; bool admitted; };
+    const One ones[] = {
+        {"one 1x1", image(1, 1, 3, 2, 2, 0, 3), true},
+        {"one 4K 4:2:0", image(2160, 3840, 3, 2, 2, 0, 1100000), true},
+        {"one 16K", image(8640, 15360, 3, 2, 2, 0, 30ll << 20), true},
+        {"one with dri 1", image(47, 60, 3, 2, 1, 1, 4000), true},
+        {"one under the limit", image(64, 64, 3, 2, 2, 0, STREAM_LIMIT - CLEAN_PAD - ALIGN), true},
+        {"one whose padded stream reaches the limit", image(64, 64, 3, 2, 2, 0, STREAM_LIMIT - CLEAN_PAD), false},
+        {"one at the limit", image(64, 64, 3, 2, 2, 0, STREAM_LIMIT), false},
+    };
+    for (const One& o : ones) {
+      const std::vector<FileIn> v{o.f};
+      const int subs = check(v, nullptr, o.name);
+      const Plan P = plan_batch(v.data(), nullptr, 1, kSizes);
+      EXPECT(subs == (o.admitted ? 1 : 0) && P.subs.size() == (size_t)subs && P.files[0].sub == (o.admitted ? 0 : -1), "%s: %d sub-batches, file in sub %d", o.name, subs,
+             P.files[0].sub);
+      if (o.admitted) EXPECT(P.subs[0].files.size() == 1 && P.subs[0].files[0] == 0 && P.files[0].slot == 0 && P.files[0].wg0 == 0 && P.files[0].tile0 == 0, "%s: slot", o.name);
+    }
+  }
   // seeded sets: plausible crops mixed with headers that claim nonsense, and unreadable files in between
   std::mt19937 rng(20240607u);
   for (int round = 0; round < 300; ++round) {

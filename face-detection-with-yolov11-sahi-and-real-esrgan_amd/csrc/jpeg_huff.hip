@@ -8,23 +8,24 @@
 //   1. unstuff: find the end of the entropy-coded data (first marker that is not RSTn), drop the 0x00 after every 0xFF and the RSTn
 //      markers themselves (flags -> scan over 1 KiB tiles -> scatter); the clean offsets of the RSTn markers start the restart
 //      SEGMENTS, whose first decoder state is known exactly, as is the one at the start of the scan;
-//   2. sync (jh_sync_kernel<true>): every thread decodes its subsequence from a cold state, then, per workgroup, threads adopt their
+//   2. sync (jhb_sync_kernel<true>): every thread decodes its subsequence from a cold state, then, per workgroup, threads adopt their
 //      predecessor's exit state as entry state and decode again until nothing changes any more (a thread whose entry did not change
 //      keeps its result, so after the first pass only the few not-yet-synchronised threads work);
-//   3. the same across workgroups (jh_sync_kernel<false>, repeated until no workgroup's last exit state changed: normally once);
+//   3. the same across workgroups (jhb_sync_kernel<false>, repeated until no workgroup's last exit state changed: normally once);
 //   4. an exclusive segmented scan over the subsequences of (blocks completed, sum of DC differences per component) gives every
 //      thread its first block's index and the DC predictors at its entry;
-//   5. write (jh_write_kernel): decode once more from the now exact entry states and store the quantised coefficients, natural order,
-//      into the planes jpeg_idct_kernel (jpeg.hip) reads.
+//   5. write (jhb_write_kernel): decode once more from the now exact entry states and store the quantised coefficients, natural order,
+//      into the planes jpeg_idct_batch_kernel (jpeg.hip) reads.
 // Semantics are those of jpeg_dec.cpp (jdhuff.c); anything that decoder would treat specially — a bad code, a DC category above 11,
 // a coefficient index past 63, a segment that does not hold exactly its MCUs, markers out of place — raises a flag instead, and
-// jpeg_decode_to_device repeats the decode with the host decoder, which reproduces libjpeg's behaviour on damaged streams.
+// jpeg_decode_batch_to_device repeats the file's decode with the host decoder, which reproduces libjpeg's behaviour on damaged streams.
+// There is ONE orchestration, for n files (jpeg_decode_batch_to_device, at the end of this file; the layout: jpeg_batch_plan.hpp); a single
+// file (jpeg_decode_to_device, jpeg.hip) is a batch of one.
 // Parallel Huffman decoding by self-synchronisation: Klein & Wiseman 2003; for JPEG on GPUs: Weissenberger & Schmidt 2021.
 #include <algorithm>
 #include <atomic>
 #include <cstddef>
 #include <cstring>
-#include <map>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -61,7 +62,7 @@ struct Scal {                                   // scalars the kernels hand to e
   int total_clean;                              // bytes of the unstuffed stream
   int n_seg;                                    // restart segments
   int T;                                        // subsequences
-  int changed;                                  // a workgroup's last exit state changed in the latest jh_sync_kernel<false>
+  int changed;                                  // a workgroup's last exit state changed in the latest jhb_sync_kernel<false>
   int err;                                      // bit mask, see the E_ constants
   int pad[2];
 };
@@ -96,8 +97,8 @@ struct Bufs {
 __device__ __forceinline__ bool is_rst(unsigned b) { return b >= 0xD0u && b <= 0xD7u; }
 
 // ---- 1. unstuffing ---------------------------------------------------------------------------------------------------------------------
-// Every stage is a body that takes its workgroup's index `blk` INSIDE the file, so that the single-file kernels (blk = blockIdx.x) and the
-// batch kernels further down (blk = blockIdx.x - the file's first workgroup) run the same code.
+// Every stage is a body that takes its workgroup's index `blk` INSIDE the file; the kernels further down look the file up and pass
+// blk = blockIdx.x - the file's first workgroup (or tile).
 __device__ __forceinline__ void jh_end_body(const Bufs& b, const HuffParams& P, int blk) {
   const int i0 = (blk * 256 + threadIdx.x) * 4;
   for (int i = i0; i < min(i0 + 4, P.n_raw); ++i) {
@@ -107,7 +108,6 @@ __device__ __forceinline__ void jh_end_body(const Bufs& b, const HuffParams& P, 
     if (!(m == 0 || m == 0xFF || is_rst(m))) atomicMin(&b.scal->end, i);
   }
 }
-__global__ void __launch_bounds__(256) jh_end_kernel(Bufs b, HuffParams P) { jh_end_body(b, P, (int)blockIdx.x); }
 
 // byte i < end of the raw stream: kept in the clean stream? an RSTn code byte?
 __device__ __forceinline__ void classify(const unsigned char* raw, int i, int n, bool* keep, bool* rst) {
@@ -138,7 +138,6 @@ __device__ __forceinline__ void jh_count_body(const Bufs& b, const HuffParams& P
   __syncthreads();
   if (threadIdx.x == 0) b.tile_cnt[blk] = (unsigned long long)s_keep | ((unsigned long long)s_rst << 32);
 }
-__global__ void __launch_bounds__(256) jh_count_kernel(Bufs b, HuffParams P) { jh_count_body(b, P, (int)blockIdx.x); }
 
 // exclusive scan of n 64-bit values by one workgroup of 1024 threads (each thread a contiguous run); returns the total
 __device__ unsigned long long block_scan_u64(unsigned long long* v, int n) {
@@ -171,7 +170,6 @@ __device__ __forceinline__ void jh_scan_tiles_body(const Bufs& b, const HuffPara
     b.seg_start[min(n_seg, P.seg_cap)] = kept;
   }
 }
-__global__ void __launch_bounds__(1024) jh_scan_tiles_kernel(Bufs b, HuffParams P, int n_tiles, int n_seg_expected) { jh_scan_tiles_body(b, P, n_tiles, n_seg_expected); }
 
 __device__ __forceinline__ void jh_scatter_body(const Bufs& b, const HuffParams& P, int blk) {
   __shared__ unsigned s_k[256], s_r[256];
@@ -201,7 +199,6 @@ __device__ __forceinline__ void jh_scatter_body(const Bufs& b, const HuffParams&
     if (rst[j]) { ++ro; if ((int)ro < P.seg_cap) b.seg_start[ro] = (int)ko; }       // segment `ro` starts where the marker stood
   }
 }
-__global__ void __launch_bounds__(256) jh_scatter_kernel(Bufs b, HuffParams P) { jh_scatter_body(b, P, (int)blockIdx.x); }
 
 // ---- subsequence layout ------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void jh_segs_body(const Bufs& b, const HuffParams& P, unsigned long long* tmp) {
@@ -234,7 +231,6 @@ __device__ __forceinline__ void jh_segs_body(const Bufs& b, const HuffParams& P,
     b.sub_start[t] = (unsigned)b.seg_start[lo] * 8u + (unsigned)(t - (int)tmp[lo]) * SUB_BITS;
   }
 }
-__global__ void __launch_bounds__(1024) jh_segs_kernel(Bufs b, HuffParams P, unsigned long long* tmp) { jh_segs_body(b, P, tmp); }
 
 // ---- tables --------------------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void jh_tables_body(const HuffSpecDev* spec, HuffTabDev* tabs, const Bufs& b, const HuffParams& P, int blk) {
@@ -267,7 +263,6 @@ __device__ __forceinline__ void jh_tables_body(const HuffSpecDev* spec, HuffTabD
     t.lut[e] = v;
   }
 }
-__global__ void __launch_bounds__(256) jh_tables_kernel(const HuffSpecDev* spec, HuffTabDev* tabs, Bufs b, HuffParams P) { jh_tables_body(spec, tabs, b, P, (int)blockIdx.x); }
 
 // ---- the decoding loop -----------------------------------------------------------------------------------------------------------------------
 struct HuffLds {
@@ -440,13 +435,6 @@ __device__ __forceinline__ void jh_sync_body(const Bufs& b, const HuffParams& P,
     if (!FIRST && exit_ != exit_at_load && (tid == NT - 1 || x.t == b.scal->T - 1)) atomicOr(&b.scal->changed, 1);
   }
 }
-template <bool FIRST>
-__global__ void __launch_bounds__(NT) jh_sync_kernel(Bufs b, HuffParams P) {
-  __shared__ HuffLds L;
-  if (blockIdx.x * NT >= b.scal->T) return;
-  jh_sync_body<FIRST>(b, P, L, (int)blockIdx.x);
-}
-
 // 4. exclusive segmented scan over the subsequences: one workgroup, every thread a contiguous run
 __device__ __forceinline__ void jh_prefix_body(const Bufs& b) {
   __shared__ int4 s_sum[1024];
@@ -479,7 +467,6 @@ __device__ __forceinline__ void jh_prefix_body(const Bufs& b) {
     run = add(run, b.cnt[t]);
   }
 }
-__global__ void __launch_bounds__(1024) jh_prefix_kernel(Bufs b) { jh_prefix_body(b); }
 
 // 5. the coefficients
 __device__ __forceinline__ void jh_write_body(const Bufs& b, const HuffParams& P, HuffLds& L, int blk) {
@@ -499,164 +486,12 @@ __device__ __forceinline__ void jh_write_body(const Bufs& b, const HuffParams& P
   }
   if (e) atomicOr(&b.scal->err, e);
 }
-__global__ void __launch_bounds__(NT) jh_write_kernel(Bufs b, HuffParams P) {
-  __shared__ HuffLds L;
-  if (blockIdx.x * NT >= b.scal->T) return;
-  jh_write_body(b, P, L, (int)blockIdx.x);
-}
 
-std::atomic<long long> g_stat_device{0}, g_stat_fallback{0}, g_stat_rounds{0};
-
-}  // namespace
-
-void jpeg_huff_stats(long long* device_decodes, long long* host_fallbacks, long long* extra_sync_rounds) {
-  if (device_decodes) *device_decodes = g_stat_device.load();
-  if (host_fallbacks) *host_fallbacks = g_stat_fallback.load();
-  if (extra_sync_rounds) *extra_sync_rounds = g_stat_rounds.load();
-}
-void jpeg_huff_note_fallback() { g_stat_fallback.fetch_add(1); }
-
-struct JpegHuffWs {
-  HostPinned stage;                              // table specs + raw bytes on their way up, the scalars on their way back
-  DevBuf raw, clean, tiles, tmp, seg_start, first_sub, sub_start, sub_seg, entry, exit_, cnt, pref, tabs, scal;
-  Bufs b;                                        // the decode in flight
-  HuffParams P;
-  int sub_wgs = 0;
-  size_t scal_off = 0;
-};
-void jpeg_huff_ws_delete(JpegHuffWs* w) { delete w; }
-
-namespace {
-void queue_scan_and_write(JpegHuffWs& H, const JpegScan& s, JpegDecodeWs& ws, hipStream_t st) {
-  hipLaunchKernelGGL(jh_prefix_kernel, dim3(1), dim3(1024), 0, st, H.b);
-  hipLaunchKernelGGL(jh_write_kernel, dim3(H.sub_wgs), dim3(NT), 0, st, H.b, H.P);
-  FFP_HIP(hipGetLastError());
-  FFP_HIP(hipMemcpyAsync(static_cast<unsigned char*>(H.stage.p) + H.scal_off, H.scal.p, sizeof(Scal), hipMemcpyDeviceToHost, st));
-  (void)s; (void)ws;
-}
-void zero_planes(const JpegScan& s, JpegDecodeWs& ws, hipStream_t st) {
-  (void)s;
-  FFP_HIP(hipMemsetAsync(ws.coef_all.p, 0, ws.coef_bytes, st));        // the three planes are one allocation
-}
-}  // namespace
-
-// Queues the whole entropy decode of the scan on `st` (coefficient planes: ws.dev[c]) under the assumption that ONE round of
-// synchronisation across workgroups is enough — it practically always is; jpeg_huff_finish() checks after the caller's
-// synchronisation. Nothing is synchronised here.
-bool jpeg_huff_decode_async(const unsigned char* data, long long n, const JpegScan& s, const JpegHead& head, JpegDecodeWs& ws, hipStream_t st) {
-  // limits of THIS decoder are not errors of the file: 32-bit bit offsets (a scan + trailer of 256 MiB or more) and six blocks per MCU.
-  // The caller then takes the host decoder, as round 2 did for every file.
-  const long long n_raw = n - head.data_off;
-  if (n_raw <= 0 || n_raw >= (1ll << 28)) return false;
-  {
-    int bpm = 0;
-    for (int c = 0; c < s.ncomp; ++c) bpm += s.comp[c].hs * s.comp[c].vs;
-    if (bpm > 6) return false;
-  }
-  if (!ws.huff) ws.huff = new JpegHuffWs();
-  JpegHuffWs& H = *ws.huff;
-  HuffParams P;
-  std::memset(&P, 0, sizeof(P));
-  P.ncomp = s.ncomp;
-  for (int c = 0; c < s.ncomp; ++c) {
-    P.hs[c] = s.comp[c].hs; P.vs[c] = s.comp[c].vs; P.blocks_x[c] = s.comp[c].blocks_x;
-    for (int dy = 0; dy < s.comp[c].vs; ++dy)
-      for (int dx = 0; dx < s.comp[c].hs; ++dx) {
-        FFP_CHECK(P.bpm < 6, FFP_ERR_ARG, "jpeg: more than 6 blocks per MCU");
-        P.blk_comp[P.bpm] = c; P.blk_dx[P.bpm] = dx; P.blk_dy[P.bpm] = dy; ++P.bpm;
-      }
-    P.coef[c] = ws.dev[c];
-  }
-  P.mcus_x = s.comp[0].blocks_x / s.comp[0].hs;
-  P.total_mcus = P.mcus_x * (s.comp[0].blocks_y / s.comp[0].vs);
-  P.dri = head.dri;
-  P.n_raw = (int)n_raw;
-  const int n_seg_expected = head.dri ? (P.total_mcus + head.dri - 1) / head.dri : 1;
-  P.seg_cap = n_seg_expected + 1;
-  P.t_cap = (int)((n_raw * 8 + SUB_BITS - 1) / SUB_BITS) + n_seg_expected + 1;
-  const int n_tiles = (int)((n_raw + TILE - 1) / TILE);
-  const size_t clean_bytes = (size_t)n_raw + LDS_WORDS * 4 + 64;
-
-  auto grow = [](DevBuf& d, size_t bytes) { if (bytes > d.n) d.alloc(bytes + (bytes >> 2)); };
-  constexpr size_t SPEC_BYTES = (sizeof(HuffSpecDev) * 6 + 255) & ~(size_t)255;       // [table specs][entropy-coded bytes]: one upload
-  grow(H.raw, SPEC_BYTES + (size_t)n_raw + 16); grow(H.clean, clean_bytes);
-  grow(H.tiles, sizeof(unsigned long long) * (size_t)(n_tiles + 1));
-  grow(H.tmp, sizeof(unsigned long long) * (size_t)(P.seg_cap + 1));
-  grow(H.seg_start, sizeof(int) * (size_t)(P.seg_cap + 2)); grow(H.first_sub, sizeof(int) * (size_t)(P.seg_cap + 2));
-  grow(H.sub_start, sizeof(unsigned) * (size_t)P.t_cap); grow(H.sub_seg, sizeof(int) * (size_t)P.t_cap);
-  grow(H.entry, sizeof(unsigned long long) * (size_t)P.t_cap); grow(H.exit_, sizeof(unsigned long long) * (size_t)P.t_cap);
-  grow(H.cnt, sizeof(int4) * (size_t)P.t_cap); grow(H.pref, sizeof(int4) * (size_t)P.t_cap);
-  grow(H.tabs, sizeof(HuffTabDev) * 6); grow(H.scal, sizeof(Scal));
-  const size_t scal_off = (SPEC_BYTES + (size_t)n_raw + 63) & ~(size_t)63;
-  if (scal_off + sizeof(Scal) > H.stage.n) H.stage.ensure((scal_off + sizeof(Scal)) * 5 / 4);
-  unsigned char* hp = static_cast<unsigned char*>(H.stage.p);
-  HuffSpecDev* specs = reinterpret_cast<HuffSpecDev*>(hp);
-  std::memset(specs, 0, SPEC_BYTES);
-  for (int c = 0; c < s.ncomp; ++c)
-    for (int k = 0; k < 2; ++k) {
-      const JpegHuffSpec& hs = k ? head.ac[s.comp[c].ta] : head.dc[s.comp[c].td];
-      std::memcpy(specs[c * 2 + k].bits, hs.bits, 16);
-      std::memcpy(specs[c * 2 + k].vals, hs.vals, (size_t)hs.n);
-    }
-  std::memcpy(hp + SPEC_BYTES, data + head.data_off, (size_t)n_raw);
-  FFP_HIP(hipMemcpyAsync(H.raw.p, hp, SPEC_BYTES + (size_t)n_raw, hipMemcpyHostToDevice, st));
-  zero_planes(s, ws, st);
-
-  Bufs b;
-  b.raw = H.raw.as<unsigned char>() + SPEC_BYTES; b.clean = H.clean.as<unsigned char>(); b.tile_cnt = H.tiles.as<unsigned long long>();
-  b.seg_start = H.seg_start.as<int>(); b.first_sub = H.first_sub.as<int>(); b.sub_start = H.sub_start.as<unsigned>(); b.sub_seg = H.sub_seg.as<int>();
-  b.entry = H.entry.as<unsigned long long>(); b.exit_ = H.exit_.as<unsigned long long>(); b.cnt = H.cnt.as<int4>(); b.pref = H.pref.as<int4>();
-  b.tabs = H.tabs.as<HuffTabDev>(); b.scal = H.scal.as<Scal>();
-  H.b = b; H.P = P; H.sub_wgs = (P.t_cap + NT - 1) / NT; H.scal_off = scal_off;
-  hipLaunchKernelGGL(jh_tables_kernel, dim3(6), dim3(256), 0, st, H.raw.as<HuffSpecDev>(), H.tabs.as<HuffTabDev>(), b, P);
-  hipLaunchKernelGGL(jh_end_kernel, dim3(n_tiles), dim3(256), 0, st, b, P);
-  hipLaunchKernelGGL(jh_count_kernel, dim3(n_tiles), dim3(256), 0, st, b, P);
-  hipLaunchKernelGGL(jh_scan_tiles_kernel, dim3(1), dim3(1024), 0, st, b, P, n_tiles, n_seg_expected);
-  hipLaunchKernelGGL(jh_scatter_kernel, dim3(n_tiles), dim3(256), 0, st, b, P);
-  hipLaunchKernelGGL(jh_segs_kernel, dim3(1), dim3(1024), 0, st, b, P, H.tmp.as<unsigned long long>());
-  hipLaunchKernelGGL(jh_sync_kernel<true>, dim3(H.sub_wgs), dim3(NT), 0, st, b, P);
-  hipLaunchKernelGGL(jh_sync_kernel<false>, dim3(H.sub_wgs), dim3(NT), 0, st, b, P);
-  queue_scan_and_write(H, s, ws, st);
-  return true;
-}
-
-// After the stream has been synchronised: 1 = the coefficient planes are right; 2 = they are right NOW, after more rounds of
-// synchronisation (the reconstruction kernels have to run again); 0 = the stream needs the host decoder.
-int jpeg_huff_finish(const JpegScan& s, JpegDecodeWs& ws, hipStream_t st) {
-  JpegHuffWs& H = *ws.huff;
-  const Scal* sc = reinterpret_cast<const Scal*>(static_cast<unsigned char*>(H.stage.p) + H.scal_off);
-  int rc = 1;
-  if (sc->changed && !(sc->err & (E_SEGS | E_CAP))) {
-    // a workgroup's last exit state moved in the round that was queued blindly: keep going until a round changes none, then redo the rest
-    rc = 2;
-    int rounds = 0;
-    const int limit = H.sub_wgs + 2;             // information travels at least one workgroup per round
-    do {
-      FFP_HIP(hipMemsetAsync(reinterpret_cast<unsigned char*>(H.scal.p) + offsetof(Scal, changed), 0, sizeof(int), st));
-      hipLaunchKernelGGL(jh_sync_kernel<false>, dim3(H.sub_wgs), dim3(NT), 0, st, H.b, H.P);
-      FFP_HIP(hipMemcpyAsync(static_cast<unsigned char*>(H.stage.p) + H.scal_off, H.scal.p, sizeof(Scal), hipMemcpyDeviceToHost, st));
-      FFP_HIP(hipStreamSynchronize(st));
-      g_stat_rounds.fetch_add(1);
-    } while (sc->changed && ++rounds < limit);
-    if (sc->changed) return 0;
-    FFP_HIP(hipMemsetAsync(reinterpret_cast<unsigned char*>(H.scal.p) + offsetof(Scal, err), 0, sizeof(int), st));     // flags of the premature write pass
-    zero_planes(s, ws, st);
-    queue_scan_and_write(H, s, ws, st);
-    FFP_HIP(hipStreamSynchronize(st));
-  }
-  if (sc->err) return 0;
-  g_stat_device.fetch_add(1);
-  return rc;
-}
-
-
-// ---- a batch of files in one pass ----------------------------------------------------------------------------------------------------------
-// Every file owns whole workgroups and whole unstuffing tiles (jpeg_batch_plan.hpp), and a descriptor in device memory with what the
-// single-file kernels get as arguments. The stage bodies above run unchanged; only where b, P and `blk` come from differs. Because a file's
-// first subsequence is a segment head (its entry state is exact and it adopts nobody's exit state) and b.exit_ is the file's own array,
-// nothing travels from one file's last subsequence into the next file's first.
-namespace {
-
+// ---- the kernels: a batch of files in one pass -------------------------------------------------------------------------------------------
+// Every file owns whole workgroups and whole unstuffing tiles (jpeg_batch_plan.hpp), and a descriptor in device memory with its Bufs and
+// HuffParams. A kernel looks its file up and hands the stage body the workgroup's index inside the file; one file is a batch of one. Because
+// a file's first subsequence is a segment head (its entry state is exact and it adopts nobody's exit state) and b.exit_ is the file's own
+// array, nothing travels from one file's last subsequence into the next file's first.
 struct BatchFile {
   Bufs b;
   HuffParams P;
@@ -720,44 +555,149 @@ __global__ void __launch_bounds__(NT) jhb_write_kernel(const BatchFile* __restri
   jh_write_body(b, sP, L, blk);
 }
 
-struct BatchWs { HostPinned stage; DevBuf up, work, coef; };
-std::mutex g_batch_mu;                           // one batch at a time per process: the workspaces below are shared
-std::map<int, BatchWs*> g_batch_ws;              // per device, never freed (as the pooled single-file workspaces)
+std::atomic<long long> g_stat_device{0}, g_stat_fallback{0}, g_stat_rounds{0};
 std::atomic<long long> g_batch_count{0}, g_batch_launches{0}, g_batch_syncs{0};
 
-struct BatchCounters { long long launches = 0, syncs = 0; };
+// ---- workspaces ----------------------------------------------------------------------------------------------------------------------------
+// The three arenas of jpeg_batch_plan.hpp and the pinned image of `up` (with the scalars' landing place behind it). A decode borrows one for
+// its length, so decodes on different threads run side by side, each on its own stream. What stays pooled when nobody decodes: at most
+// kPoolCap workspaces, and per device at most one that holds more than kFrameBytes (a batch of many files, a 16K frame); a second such one is
+// freed when it comes back.
+struct BatchWs {
+  HostPinned stage;
+  DevBuf up, work, coef;
+  int device = 0;                                // buffers live on the device that was current when the workspace was made
+  size_t held() const { return stage.n + up.n + work.n + coef.n; }
+};
+constexpr size_t kPoolCap = 32;                  // as many as the host decoder's pool keeps (jpeg.hip)
+constexpr size_t kFrameBytes = 160u << 20;       // above what a 3840 x 2160 frame takes: ~55 MiB at 4:2:0 quality 95, ~145 MiB at 4:4:4 with an 8 MB stream
+std::mutex g_ws_mu;
+std::vector<BatchWs*> g_ws_free;
 
-// the host decoder for one file of a batch (what jpeg_decode_to_device does when the device decoder gave up)
-void host_decode_one(const unsigned char* data, long long n, JpegScan& s, unsigned char* d_out, long long stride, int bgr, hipStream_t st, BatchCounters& k) {
-  JpegDecodeWs* ws = jpeg_ws_acquire();
-  try {
-    ws->ensure_host(s);
-    jpeg_entropy_decode(data, n, s, false);
-    jpeg_reconstruct_device(s, *ws, d_out, stride, bgr, st, true);
-    FFP_HIP(hipStreamSynchronize(st));
-    k.launches += 2; k.syncs += 1;
-  } catch (...) {
-    jpeg_ws_release(ws);
-    throw;
+struct BatchWsLease {
+  BatchWs* w = nullptr;
+  BatchWsLease() {
+    int dev = 0;
+    FFP_HIP(hipGetDevice(&dev));
+    {
+      std::lock_guard<std::mutex> lock(g_ws_mu);
+      for (size_t i = 0; i < g_ws_free.size() && !w; ++i)
+        if (g_ws_free[i]->device == dev) { w = g_ws_free[i]; g_ws_free.erase(g_ws_free.begin() + i); }
+    }
+    if (!w) { w = new BatchWs(); w->device = dev; }
   }
-  jpeg_ws_release(ws);
+  BatchWsLease(const BatchWsLease&) = delete;
+  BatchWsLease& operator=(const BatchWsLease&) = delete;
+  ~BatchWsLease() {
+    {
+      std::lock_guard<std::mutex> lock(g_ws_mu);
+      bool big_kept = false;
+      for (const BatchWs* f : g_ws_free) big_kept = big_kept || (f->device == w->device && f->held() > kFrameBytes);
+      if (g_ws_free.size() < kPoolCap && !(big_kept && w->held() > kFrameBytes)) { g_ws_free.push_back(w); return; }
+    }
+    int cur = 0;                                 // freed with the owning device current
+    const int owner = w->device;
+    (void)hipGetDevice(&cur);
+    if (cur != owner) (void)hipSetDevice(owner);
+    delete w;
+    if (cur != owner) (void)hipSetDevice(cur);
+  }
+};
+
+// the host decoder for one file: a stream the device decoder flagged, a file outside its limits, everything under FFP_JPEG_HOST_HUFFMAN=1.
+// It reproduces libjpeg's behaviour on damaged streams, and its refusals are the error reports of the decoding entries.
+void host_decode_one(const unsigned char* data, long long n, JpegScan& s, unsigned char* d_out, long long stride, int bgr, hipStream_t st, JpegBatchCost& k) {
+  JpegWsLease ws;
+  ws->ensure_host(s);
+  jpeg_entropy_decode(data, n, s, false);
+  jpeg_reconstruct_device(s, *ws, d_out, stride, bgr, st);
+  FFP_HIP(hipStreamSynchronize(st));             // the staging planes go back to the pool after this
+  k.launches += 2; k.syncs += 1;
+}
+
+// Everything the kernels are told about one file — slot j of sub-batch S — written into hp, the pinned image of the `up` arena: its descriptor
+// (Bufs, HuffParams), its rows of the workgroup -> file and tile -> file tables, quantisation tables, Huffman specs, IDCT and colour
+// descriptors and the entropy-coded bytes. The caller has zeroed the tables of hp.
+struct Arenas { unsigned char *hp, *up, *work, *coef; };
+void fill_file(const Arenas& A, const jbp::SubPlan& S, const jbp::FilePlan& p, int j, const JpegScan& s, const JpegHead& head, const unsigned char* data, long long n_raw,
+               unsigned char* out, long long stride) {
+  unsigned char* const work = A.work;
+  BatchFile& f = reinterpret_cast<BatchFile*>(A.hp + S.desc.off)[j];
+  HuffParams& P = f.P;
+  P.ncomp = s.ncomp;
+  for (int c = 0; c < s.ncomp; ++c) {
+    P.hs[c] = s.comp[c].hs; P.vs[c] = s.comp[c].vs; P.blocks_x[c] = s.comp[c].blocks_x;
+    for (int dy = 0; dy < s.comp[c].vs; ++dy)
+      for (int dx = 0; dx < s.comp[c].hs; ++dx) { P.blk_comp[P.bpm] = c; P.blk_dx[P.bpm] = dx; P.blk_dy[P.bpm] = dy; ++P.bpm; }       // the planner admitted bpm <= 6
+    P.coef[c] = reinterpret_cast<short*>(A.coef + p.coef[c].off);
+  }
+  P.mcus_x = p.mcus_x; P.total_mcus = p.total_mcus; P.dri = head.dri; P.n_raw = (int)n_raw;
+  P.seg_cap = p.seg_cap; P.t_cap = p.t_cap;
+  Bufs& b = f.b;
+  b.raw = A.up + p.raw.off; b.clean = work + p.clean.off;
+  b.tile_cnt = reinterpret_cast<unsigned long long*>(work + p.tile_cnt.off);
+  b.seg_start = reinterpret_cast<int*>(work + p.seg_start.off); b.first_sub = reinterpret_cast<int*>(work + p.first_sub.off);
+  b.sub_start = reinterpret_cast<unsigned*>(work + p.sub_start.off); b.sub_seg = reinterpret_cast<int*>(work + p.sub_seg.off);
+  b.entry = reinterpret_cast<unsigned long long*>(work + p.entry.off); b.exit_ = reinterpret_cast<unsigned long long*>(work + p.exit_.off);
+  b.cnt = reinterpret_cast<int4*>(work + p.cnt.off); b.pref = reinterpret_cast<int4*>(work + p.pref.off);
+  b.tabs = reinterpret_cast<const HuffTabDev*>(work + p.tabs.off); b.scal = reinterpret_cast<Scal*>(work + p.scal.off);
+  f.tmp = reinterpret_cast<unsigned long long*>(work + p.tmp.off);
+  f.spec = reinterpret_cast<const HuffSpecDev*>(A.up + S.spec.off) + (size_t)j * 6;
+  f.tabs = reinterpret_cast<HuffTabDev*>(work + p.tabs.off);
+  f.wg0 = p.wg0; f.tile0 = p.tile0; f.n_tiles = p.n_tiles; f.n_seg_expected = p.n_seg_expected;
+  int* wg_file = reinterpret_cast<int*>(A.hp + S.wg_file.off);
+  int* tile_file = reinterpret_cast<int*>(A.hp + S.tile_file.off);
+  std::fill(wg_file + p.wg0, wg_file + p.wg0 + p.n_wg, j);
+  std::fill(tile_file + p.tile0, tile_file + p.tile0 + p.n_tiles, j);
+  std::memcpy(reinterpret_cast<unsigned short*>(A.hp + S.qt.off) + (size_t)j * 256, s.qt, sizeof(unsigned short) * 256);
+  HuffSpecDev* specs = reinterpret_cast<HuffSpecDev*>(A.hp + S.spec.off) + (size_t)j * 6;
+  JpegBatchIdct* idct = reinterpret_cast<JpegBatchIdct*>(A.hp + S.idct.off) + p.idct_slot0;
+  for (int c = 0; c < s.ncomp; ++c) {
+    for (int t = 0; t < 2; ++t) {
+      const JpegHuffSpec& sp = t ? head.ac[s.comp[c].ta] : head.dc[s.comp[c].td];
+      std::memcpy(specs[c * 2 + t].bits, sp.bits, 16);
+      std::memcpy(specs[c * 2 + t].vals, sp.vals, (size_t)sp.n);
+    }
+    idct[c] = JpegBatchIdct{P.coef[c], work + p.plane[c].off, reinterpret_cast<const unsigned short*>(A.up + S.qt.off) + (size_t)j * 256 + 64 * s.comp[c].tq,
+                            s.comp[c].blocks_x * s.comp[c].blocks_y, s.comp[c].blocks_x, p.idct_wg0[c], 0};
+  }
+  const int hsub = s.ncomp == 3 ? s.hmax : 1, vsub = s.ncomp == 3 ? s.vmax : 1;
+  JpegBatchColour& cd = reinterpret_cast<JpegBatchColour*>(A.hp + S.colour.off)[j];
+  cd.py = work + p.plane[0].off;
+  cd.pcb = s.ncomp == 3 ? work + p.plane[1].off : nullptr;
+  cd.pcr = s.ncomp == 3 ? work + p.plane[2].off : nullptr;
+  cd.out = out; cd.stride = stride;
+  cd.h = s.h; cd.w = s.w; cd.pitch_y = s.comp[0].blocks_x * 8; cd.pitch_c = s.ncomp == 3 ? s.comp[1].blocks_x * 8 : 0;
+  cd.ch = (s.h + vsub - 1) / vsub; cd.cw = (s.w + hsub - 1) / hsub; cd.hsub = hsub; cd.vsub = vsub; cd.ncomp = s.ncomp;
+  cd.wg0 = p.px_wg0; cd.wgs_x = p.px_wgs_x; cd.pad = 0;
+  std::memcpy(A.hp + p.raw.off, data, (size_t)n_raw);
 }
 
 }  // namespace
+
+void jpeg_huff_stats(long long* device_decodes, long long* host_fallbacks, long long* extra_sync_rounds) {
+  if (device_decodes) *device_decodes = g_stat_device.load();
+  if (host_fallbacks) *host_fallbacks = g_stat_fallback.load();
+  if (extra_sync_rounds) *extra_sync_rounds = g_stat_rounds.load();
+}
 
 void jpeg_batch_stats(long long* batches, long long* launches_last_batch, long long* syncs_last_batch) {
   if (batches) *batches = g_batch_count.load();
   if (launches_last_batch) *launches_last_batch = g_batch_launches.load();
   if (syncs_last_batch) *syncs_last_batch = g_batch_syncs.load();
 }
+void jpeg_batch_note(const JpegBatchCost& k) {
+  g_batch_count.fetch_add(1);
+  g_batch_launches.store(k.launches);
+  g_batch_syncs.store(k.syncs);
+}
 
 void jpeg_decode_batch_to_device(int n, const unsigned char* const* datas, const long long* sizes, int bgr, unsigned char* d_base, const long long* offsets,
-                                 const long long* strides, long long cap, int* hs, int* ws, int* status, std::string* first_error, hipStream_t st) {
-  if (first_error) first_error->clear();
+                                 const long long* strides, long long cap, int* hs, int* ws, int* status, std::string* why, JpegBatchCost* cost, hipStream_t st) {
   if (n <= 0) return;
-  auto note = [&](int i, int code, const char* why) {
-    status[i] = -code;
-    if (first_error && first_error->empty()) *first_error = "file " + std::to_string(i) + ": " + why;
+  auto refuse = [&](int i, const Error& e) {
+    status[i] = -e.code;
+    if (why) why[i] = e.what();
   };
   // 1. the markers of every file; an unreadable one keeps its status and is not looked at again
   std::vector<JpegScan> scans((size_t)n);
@@ -766,13 +706,14 @@ void jpeg_decode_batch_to_device(int n, const unsigned char* const* datas, const
   std::vector<long long> stride((size_t)n, 0);
   for (int i = 0; i < n; ++i) {
     hs[i] = ws[i] = 0; status[i] = 0;
+    if (why) why[i].clear();
     try {
       FFP_CHECK(datas[i] && sizes[i] > 0, FFP_ERR_ARG, "jpeg_decode_batch: no data");
       jpeg_entropy_decode(datas[i], sizes[i], scans[i], true, &heads[i]);
       hs[i] = scans[i].h; ws[i] = scans[i].w;
       readable[i] = 1;
     } catch (const Error& e) {
-      note(i, e.code, e.what());
+      refuse(i, e);
     }
   }
   // 2. every readable file's region inside cap, before anything is queued
@@ -783,7 +724,8 @@ void jpeg_decode_batch_to_device(int n, const unsigned char* const* datas, const
     FFP_CHECK(offsets[i] >= 0 && stride[i] >= (long long)s.w * 3 && offsets[i] <= cap && stride[i] * (s.h - 1) + (long long)s.w * 3 <= cap - offsets[i], FFP_ERR_ARG,
               "jpeg_decode_batch: image %d (%dx%d at offset %lld, row pitch %lld) does not lie inside the %lld bytes of the output", i, s.w, s.h, offsets[i], stride[i], cap);
   }
-  // 3. the layout
+  // 3. the layout: every buffer of the device decoder is sized here, from header fields the planner has checked. Not an error of the file but a
+  // limit of THIS decoder (the host decoder takes the file): 32-bit bit offsets (a scan + trailer of 256 MiB or more), six blocks per MCU
   std::vector<jbp::FileIn> in((size_t)n);
   for (int i = 0; i < n; ++i) {
     if (!readable[i]) continue;
@@ -792,181 +734,120 @@ void jpeg_decode_batch_to_device(int n, const unsigned char* const* datas, const
     f.n_raw = sizes[i] - heads[i].data_off; f.h = s.h; f.w = s.w; f.ncomp = s.ncomp; f.dri = heads[i].dri;
     for (int c = 0; c < s.ncomp; ++c) { f.hs[c] = s.comp[c].hs; f.vs[c] = s.comp[c].vs; f.blocks_x[c] = s.comp[c].blocks_x; f.blocks_y[c] = s.comp[c].blocks_y; }
   }
-  const bool host_only = sw().jpeg_host_huffman;
+  const bool host_only = sw().jpeg_host_huffman;  // FFP_JPEG_HOST_HUFFMAN=1: entropy decoding on the host for every file (A/B and the fallback's own tests)
   std::vector<unsigned char> for_device = readable;
   if (host_only) std::fill(for_device.begin(), for_device.end(), 0);
   const jbp::Sizes sz{(long long)sizeof(BatchFile), (long long)sizeof(JpegBatchIdct), (long long)sizeof(JpegBatchColour), (long long)sizeof(HuffTabDev),
                       (long long)sizeof(HuffSpecDev), (long long)sizeof(Scal)};
   const jbp::Plan plan = jbp::plan_batch(in.data(), for_device.data(), n, sz);
 
-  std::lock_guard<std::mutex> lock(g_batch_mu);
-  BatchCounters k;
+  JpegBatchCost k;
   std::vector<unsigned char> to_host((size_t)n, 0);
   for (int i = 0; i < n; ++i) to_host[i] = readable[i] && plan.files[i].sub < 0;
-  int dev = 0;
-  FFP_HIP(hipGetDevice(&dev));
-  BatchWs*& Wp = g_batch_ws[dev];
-  if (!Wp) Wp = new BatchWs();
-  BatchWs& W = *Wp;
-
-  for (const jbp::SubPlan& S : plan.subs) {
-    const int m = (int)S.files.size();
-    const size_t scal_host = (size_t)jbp::align_up(S.up_bytes);
-    W.stage.ensure(scal_host + (size_t)S.scal.bytes);
-    if ((size_t)S.up_bytes > W.up.n) W.up.alloc((size_t)S.up_bytes * 5 / 4);
-    if ((size_t)S.work_bytes > W.work.n) W.work.alloc((size_t)S.work_bytes * 5 / 4);
-    if ((size_t)S.coef_bytes > W.coef.n) W.coef.alloc((size_t)S.coef_bytes * 5 / 4);
-    unsigned char* hp = static_cast<unsigned char*>(W.stage.p);
-    unsigned char* up = W.up.as<unsigned char>();
-    unsigned char* work = W.work.as<unsigned char>();
-    unsigned char* coef = W.coef.as<unsigned char>();
-    std::memset(hp, 0, (size_t)S.spec.off + (size_t)S.spec.bytes);          // the tables; the raw bytes behind them are copied in below
-    BatchFile* hF = reinterpret_cast<BatchFile*>(hp + S.desc.off);
-    int* h_wg_file = reinterpret_cast<int*>(hp + S.wg_file.off);
-    int* h_tile_file = reinterpret_cast<int*>(hp + S.tile_file.off);
-    JpegBatchIdct* hI = reinterpret_cast<JpegBatchIdct*>(hp + S.idct.off);
-    JpegBatchColour* hC = reinterpret_cast<JpegBatchColour*>(hp + S.colour.off);
-    unsigned short* hQ = reinterpret_cast<unsigned short*>(hp + S.qt.off);
-    HuffSpecDev* hS = reinterpret_cast<HuffSpecDev*>(hp + S.spec.off);
-    for (int j = 0; j < m; ++j) {
-      const int i = S.files[j];
-      const jbp::FilePlan& p = plan.files[i];
-      const JpegScan& s = scans[i];
-      const JpegHead& head = heads[i];
-      BatchFile& f = hF[j];
-      HuffParams& P = f.P;
-      P.ncomp = s.ncomp;
-      for (int c = 0; c < s.ncomp; ++c) {
-        P.hs[c] = s.comp[c].hs; P.vs[c] = s.comp[c].vs; P.blocks_x[c] = s.comp[c].blocks_x;
-        for (int dy = 0; dy < s.comp[c].vs; ++dy)
-          for (int dx = 0; dx < s.comp[c].hs; ++dx) { P.blk_comp[P.bpm] = c; P.blk_dx[P.bpm] = dx; P.blk_dy[P.bpm] = dy; ++P.bpm; }       // the planner admitted bpm <= 6
-        P.coef[c] = reinterpret_cast<short*>(coef + p.coef[c].off);
+  if (!plan.subs.empty()) {
+    BatchWsLease lease;
+    BatchWs& W = *lease.w;
+    for (const jbp::SubPlan& S : plan.subs) {
+      const int m = (int)S.files.size();
+      const size_t scal_host = (size_t)jbp::align_up(S.up_bytes);
+      W.stage.ensure(scal_host + (size_t)S.scal.bytes);
+      if ((size_t)S.up_bytes > W.up.n) W.up.alloc((size_t)S.up_bytes * 5 / 4);
+      if ((size_t)S.work_bytes > W.work.n) W.work.alloc((size_t)S.work_bytes * 5 / 4);
+      if ((size_t)S.coef_bytes > W.coef.n) W.coef.alloc((size_t)S.coef_bytes * 5 / 4);
+      const Arenas A{static_cast<unsigned char*>(W.stage.p), W.up.as<unsigned char>(), W.work.as<unsigned char>(), W.coef.as<unsigned char>()};
+      std::memset(A.hp, 0, (size_t)S.spec.off + (size_t)S.spec.bytes);          // the tables; the raw bytes behind them are copied in by fill_file
+      for (int j = 0; j < m; ++j) {
+        const int i = S.files[j];
+        fill_file(A, S, plan.files[i], j, scans[i], heads[i], datas[i] + heads[i].data_off, in[i].n_raw, d_base + offsets[i], stride[i]);
       }
-      P.mcus_x = p.mcus_x; P.total_mcus = p.total_mcus; P.dri = head.dri; P.n_raw = (int)in[i].n_raw;
-      P.seg_cap = p.seg_cap; P.t_cap = p.t_cap;
-      Bufs& b = f.b;
-      b.raw = up + p.raw.off; b.clean = work + p.clean.off;
-      b.tile_cnt = reinterpret_cast<unsigned long long*>(work + p.tile_cnt.off);
-      b.seg_start = reinterpret_cast<int*>(work + p.seg_start.off); b.first_sub = reinterpret_cast<int*>(work + p.first_sub.off);
-      b.sub_start = reinterpret_cast<unsigned*>(work + p.sub_start.off); b.sub_seg = reinterpret_cast<int*>(work + p.sub_seg.off);
-      b.entry = reinterpret_cast<unsigned long long*>(work + p.entry.off); b.exit_ = reinterpret_cast<unsigned long long*>(work + p.exit_.off);
-      b.cnt = reinterpret_cast<int4*>(work + p.cnt.off); b.pref = reinterpret_cast<int4*>(work + p.pref.off);
-      b.tabs = reinterpret_cast<const HuffTabDev*>(work + p.tabs.off); b.scal = reinterpret_cast<Scal*>(work + p.scal.off);
-      f.tmp = reinterpret_cast<unsigned long long*>(work + p.tmp.off);
-      f.spec = reinterpret_cast<const HuffSpecDev*>(up + S.spec.off) + (size_t)j * 6;
-      f.tabs = reinterpret_cast<HuffTabDev*>(work + p.tabs.off);
-      f.wg0 = p.wg0; f.tile0 = p.tile0; f.n_tiles = p.n_tiles; f.n_seg_expected = p.n_seg_expected;
-      std::fill(h_wg_file + p.wg0, h_wg_file + p.wg0 + p.n_wg, j);
-      std::fill(h_tile_file + p.tile0, h_tile_file + p.tile0 + p.n_tiles, j);
-      std::memcpy(hQ + (size_t)j * 256, s.qt, sizeof(unsigned short) * 256);
-      for (int c = 0; c < s.ncomp; ++c) {
-        for (int t = 0; t < 2; ++t) {
-          const JpegHuffSpec& sp = t ? head.ac[s.comp[c].ta] : head.dc[s.comp[c].td];
-          std::memcpy(hS[(size_t)j * 6 + c * 2 + t].bits, sp.bits, 16);
-          std::memcpy(hS[(size_t)j * 6 + c * 2 + t].vals, sp.vals, (size_t)sp.n);
-        }
-        hI[p.idct_slot0 + c] = JpegBatchIdct{P.coef[c], work + p.plane[c].off, reinterpret_cast<const unsigned short*>(up + S.qt.off) + (size_t)j * 256 + 64 * s.comp[c].tq,
-                                             s.comp[c].blocks_x * s.comp[c].blocks_y, s.comp[c].blocks_x, p.idct_wg0[c], 0};
+      const BatchFile* dF = reinterpret_cast<const BatchFile*>(A.up + S.desc.off);
+      const int* d_wg_file = reinterpret_cast<const int*>(A.up + S.wg_file.off);
+      const int* d_tile_file = reinterpret_cast<const int*>(A.up + S.tile_file.off);
+      JpegBatchColour* hC = reinterpret_cast<JpegBatchColour*>(A.hp + S.colour.off);
+      Scal* h_scal = reinterpret_cast<Scal*>(A.hp + scal_host);
+      auto download = [&]() {
+        FFP_HIP(hipMemcpyAsync(h_scal, A.work + S.scal.off, (size_t)S.scal.bytes, hipMemcpyDeviceToHost, st));
+        FFP_HIP(hipStreamSynchronize(st));
+        k.syncs += 1;
+      };
+      auto scan_and_write = [&]() {
+        hipLaunchKernelGGL(jhb_prefix_kernel, dim3(m), dim3(1024), 0, st, dF);
+        hipLaunchKernelGGL(jhb_write_kernel, dim3(S.n_wg), dim3(NT), 0, st, dF, d_wg_file);
+        k.launches += 2;
+      };
+      // the whole entropy decode is queued under the assumption that ONE round of synchronisation across workgroups is enough — it practically
+      // always is; the scalars that come down say whether it was
+      FFP_HIP(hipMemcpyAsync(A.up, A.hp, (size_t)S.up_bytes, hipMemcpyHostToDevice, st));
+      FFP_HIP(hipMemsetAsync(A.coef, 0, (size_t)S.coef_bytes, st));
+      hipLaunchKernelGGL(jhb_tables_kernel, dim3(m * 6), dim3(256), 0, st, dF);
+      hipLaunchKernelGGL(jhb_end_kernel, dim3(S.n_tiles), dim3(256), 0, st, dF, d_tile_file);
+      hipLaunchKernelGGL(jhb_count_kernel, dim3(S.n_tiles), dim3(256), 0, st, dF, d_tile_file);
+      hipLaunchKernelGGL(jhb_scan_tiles_kernel, dim3(m), dim3(1024), 0, st, dF);
+      hipLaunchKernelGGL(jhb_scatter_kernel, dim3(S.n_tiles), dim3(256), 0, st, dF, d_tile_file);
+      hipLaunchKernelGGL(jhb_segs_kernel, dim3(m), dim3(1024), 0, st, dF);
+      hipLaunchKernelGGL(jhb_sync_kernel<true>, dim3(S.n_wg), dim3(NT), 0, st, dF, d_wg_file);
+      hipLaunchKernelGGL(jhb_sync_kernel<false>, dim3(S.n_wg), dim3(NT), 0, st, dF, d_wg_file);
+      k.launches += 8;
+      scan_and_write();
+      FFP_HIP(hipGetLastError());
+      // The reconstruction is NOT queued blindly: it writes into the caller's memory, and the region of a file that is not decoded in the end
+      // (flagged here, then refused by the host decoder too) has to stay untouched. So the scalars come down first, and the two reconstruction
+      // launches follow with the flagged files blanked out: two synchronisations per sub-batch, always.
+      download();
+      std::vector<int> sticky((size_t)m, 0);
+      bool more = false;
+      for (int j = 0; j < m; ++j) {
+        sticky[j] = h_scal[j].err & (E_SEGS | E_CAP);
+        if (h_scal[j].changed && !sticky[j]) more = true;
       }
-      const int hsub = s.ncomp == 3 ? s.hmax : 1, vsub = s.ncomp == 3 ? s.vmax : 1;
-      JpegBatchColour& cd = hC[j];
-      cd.py = work + p.plane[0].off;
-      cd.pcb = s.ncomp == 3 ? work + p.plane[1].off : nullptr;
-      cd.pcr = s.ncomp == 3 ? work + p.plane[2].off : nullptr;
-      cd.out = d_base + offsets[i]; cd.stride = stride[i];
-      cd.h = s.h; cd.w = s.w; cd.pitch_y = s.comp[0].blocks_x * 8; cd.pitch_c = s.ncomp == 3 ? s.comp[1].blocks_x * 8 : 0;
-      cd.ch = (s.h + vsub - 1) / vsub; cd.cw = (s.w + hsub - 1) / hsub; cd.hsub = hsub; cd.vsub = vsub; cd.ncomp = s.ncomp;
-      cd.wg0 = p.px_wg0; cd.wgs_x = p.px_wgs_x; cd.pad = 0;
-      std::memcpy(hp + p.raw.off, datas[i] + head.data_off, (size_t)in[i].n_raw);
-    }
-    const BatchFile* dF = reinterpret_cast<const BatchFile*>(up + S.desc.off);
-    const int* d_wg_file = reinterpret_cast<const int*>(up + S.wg_file.off);
-    const int* d_tile_file = reinterpret_cast<const int*>(up + S.tile_file.off);
-    Scal* h_scal = reinterpret_cast<Scal*>(hp + scal_host);
-    auto download = [&]() {
-      FFP_HIP(hipMemcpyAsync(h_scal, work + S.scal.off, (size_t)S.scal.bytes, hipMemcpyDeviceToHost, st));
-      FFP_HIP(hipStreamSynchronize(st));
-      k.syncs += 1;
-    };
-    auto scan_and_write = [&]() {
-      hipLaunchKernelGGL(jhb_prefix_kernel, dim3(m), dim3(1024), 0, st, dF);
-      hipLaunchKernelGGL(jhb_write_kernel, dim3(S.n_wg), dim3(NT), 0, st, dF, d_wg_file);
-      k.launches += 2;
-    };
-    auto reconstruct = [&]() {
-      jpeg_batch_reconstruct(reinterpret_cast<const JpegBatchIdct*>(up + S.idct.off), S.n_idct, S.n_idct_wg, reinterpret_cast<const JpegBatchColour*>(up + S.colour.off), m,
+      if (more) {
+        // some workgroup's last exit state moved in the round that was queued blindly: rounds for the sub-batch until none moves (information
+        // travels at least one workgroup per round), then the scan and the write pass again, for all files (the ones that did not move get the
+        // same coefficients again)
+        int rounds = 0;
+        const int limit = S.n_wg + 2;
+        do {
+          FFP_HIP(hipMemset2DAsync(A.work + S.scal.off + offsetof(Scal, changed), sizeof(Scal), 0, sizeof(int), (size_t)m, st));
+          hipLaunchKernelGGL(jhb_sync_kernel<false>, dim3(S.n_wg), dim3(NT), 0, st, dF, d_wg_file);
+          k.launches += 1;
+          download();
+          g_stat_rounds.fetch_add(1);
+          more = false;
+          for (int j = 0; j < m; ++j) more = more || (h_scal[j].changed && !sticky[j]);
+        } while (more && ++rounds < limit);
+        for (int j = 0; j < m; ++j)
+          if (h_scal[j].changed) sticky[j] |= E_CAP;                             // did not settle: the host decoder
+        FFP_HIP(hipMemset2DAsync(A.work + S.scal.off + offsetof(Scal, err), sizeof(Scal), 0, sizeof(int), (size_t)m, st));     // flags of the premature write pass
+        FFP_HIP(hipMemsetAsync(A.coef, 0, (size_t)S.coef_bytes, st));
+        scan_and_write();
+        download();
+      }
+      // files whose flags are set leave the batch: blank out their colour descriptors (h = 0: no pixel is written), the rest is reconstructed
+      bool any_bad = false;
+      for (int j = 0; j < m; ++j)
+        if (h_scal[j].err | sticky[j]) { hC[j].h = 0; to_host[S.files[j]] = 1; any_bad = true; }
+      if (any_bad) FFP_HIP(hipMemcpyAsync(A.up + S.colour.off, hC, (size_t)S.colour.bytes, hipMemcpyHostToDevice, st));
+      jpeg_batch_reconstruct(reinterpret_cast<const JpegBatchIdct*>(A.up + S.idct.off), S.n_idct, S.n_idct_wg, reinterpret_cast<const JpegBatchColour*>(A.up + S.colour.off), m,
                              S.n_px_wg, bgr, st);
       k.launches += 2;
-    };
-    FFP_HIP(hipMemcpyAsync(up, hp, (size_t)S.up_bytes, hipMemcpyHostToDevice, st));
-    FFP_HIP(hipMemsetAsync(coef, 0, (size_t)S.coef_bytes, st));
-    hipLaunchKernelGGL(jhb_tables_kernel, dim3(m * 6), dim3(256), 0, st, dF);
-    hipLaunchKernelGGL(jhb_end_kernel, dim3(S.n_tiles), dim3(256), 0, st, dF, d_tile_file);
-    hipLaunchKernelGGL(jhb_count_kernel, dim3(S.n_tiles), dim3(256), 0, st, dF, d_tile_file);
-    hipLaunchKernelGGL(jhb_scan_tiles_kernel, dim3(m), dim3(1024), 0, st, dF);
-    hipLaunchKernelGGL(jhb_scatter_kernel, dim3(S.n_tiles), dim3(256), 0, st, dF, d_tile_file);
-    hipLaunchKernelGGL(jhb_segs_kernel, dim3(m), dim3(1024), 0, st, dF);
-    hipLaunchKernelGGL(jhb_sync_kernel<true>, dim3(S.n_wg), dim3(NT), 0, st, dF, d_wg_file);
-    hipLaunchKernelGGL(jhb_sync_kernel<false>, dim3(S.n_wg), dim3(NT), 0, st, dF, d_wg_file);
-    k.launches += 8;
-    scan_and_write();
-    FFP_HIP(hipGetLastError());
-    // Unlike the single-file path, the reconstruction is NOT queued blindly: it writes into the caller's memory, and the region of a file
-    // that is not decoded in the end (flagged here, then refused by the host decoder too) has to stay untouched. So the scalars come down
-    // first, and the two reconstruction launches follow with the flagged files blanked out: two synchronisations per sub-batch, always.
-    download();
-    std::vector<int> sticky((size_t)m, 0);
-    bool more = false;
-    for (int j = 0; j < m; ++j) {
-      sticky[j] = h_scal[j].err & (E_SEGS | E_CAP);
-      if (h_scal[j].changed && !sticky[j]) more = true;
-    }
-    if (more) {
-      // some workgroup's last exit state moved in the round that was queued blindly: rounds for the sub-batch until none moves, then the
-      // scan and the write pass again, for all files (the ones that did not move get the same coefficients again)
-      int rounds = 0;
-      const int limit = S.n_wg + 2;
-      do {
-        FFP_HIP(hipMemset2DAsync(work + S.scal.off + offsetof(Scal, changed), sizeof(Scal), 0, sizeof(int), (size_t)m, st));
-        hipLaunchKernelGGL(jhb_sync_kernel<false>, dim3(S.n_wg), dim3(NT), 0, st, dF, d_wg_file);
-        k.launches += 1;
-        download();
-        g_stat_rounds.fetch_add(1);
-        more = false;
-        for (int j = 0; j < m; ++j) more = more || (h_scal[j].changed && !sticky[j]);
-      } while (more && ++rounds < limit);
+      FFP_HIP(hipStreamSynchronize(st));
+      k.syncs += 1;
       for (int j = 0; j < m; ++j)
-        if (h_scal[j].changed) sticky[j] |= E_CAP;                             // did not settle: the host decoder
-      FFP_HIP(hipMemset2DAsync(work + S.scal.off + offsetof(Scal, err), sizeof(Scal), 0, sizeof(int), (size_t)m, st));     // flags of the premature write pass
-      FFP_HIP(hipMemsetAsync(coef, 0, (size_t)S.coef_bytes, st));
-      scan_and_write();
-      download();
+        if (!to_host[S.files[j]]) g_stat_device.fetch_add(1);
     }
-    // files whose flags are set leave the batch: blank out their colour descriptors (h = 0: no pixel is written), the rest is reconstructed
-    bool any_bad = false;
-    for (int j = 0; j < m; ++j)
-      if (h_scal[j].err | sticky[j]) { hC[j].h = 0; to_host[S.files[j]] = 1; any_bad = true; }
-    if (any_bad) FFP_HIP(hipMemcpyAsync(up + S.colour.off, hC, (size_t)S.colour.bytes, hipMemcpyHostToDevice, st));
-    reconstruct();
-    FFP_HIP(hipStreamSynchronize(st));
-    k.syncs += 1;
-    for (int j = 0; j < m; ++j)
-      if (!to_host[S.files[j]]) g_stat_device.fetch_add(1);
   }
   // 4. the host decoder, file by file, for what the device decoder did not take or gave up on
   for (int i = 0; i < n; ++i) {
     if (!to_host[i]) continue;
-    if (!host_only) jpeg_huff_note_fallback();
+    if (!host_only) g_stat_fallback.fetch_add(1);
     try {
       host_decode_one(datas[i], sizes[i], scans[i], d_base + offsets[i], stride[i], bgr, st, k);
       status[i] = 1;
     } catch (const Error& e) {
-      note(i, e.code, e.what());
+      refuse(i, e);
     }
   }
-  g_batch_count.fetch_add(1);
-  g_batch_launches.store(k.launches);
-  g_batch_syncs.store(k.syncs);
+  if (cost) *cost = k;
 }
 
 }  // namespace ffp

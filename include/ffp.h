@@ -366,7 +366,10 @@ int ffp_jpeg_encode_batch_dev(int device, const uint8_t* d_base, int n, const in
  * on the device; the host parses the markers. Progressive / arithmetic-coded files: FFP_ERR_ARG. ffp_jpeg_info reads the header only. out: h*w*3 bytes, BGR
  * when bgr = 1 (cv2's order; grayscale files give three equal channels like IMREAD_COLOR). _dev writes into device memory (row
  * pitch in bytes): the frame is ready for ffp_det_infer_tiles_dev; what crosses PCIe is the file itself (through pinned staging kept in a
- * pool), neither coefficients nor pixels are ever materialised on the host. */
+ * pool), neither coefficients nor pixels are ever materialised on the host. One file is decoded as a batch of one (the routine behind
+ * ffp_jpeg_decode_batch_dev below), so the batch's rules hold: when the call fails — a file the markers refuse, a buffer that is too small, a
+ * damaged stream that the host decoder refuses too — the output region (out / d_out) is untouched; and one decode costs TWO stream
+ * synchronisations (the entropy decoder's verdict comes down before the reconstruction is queued). Calls on different threads run side by side. */
 int ffp_jpeg_info(const uint8_t* data, int64_t n, int32_t* out_h, int32_t* out_w, int32_t* out_ncomp);
 int ffp_jpeg_decode(int device, const uint8_t* data, int64_t n, int bgr, uint8_t* out, int64_t cap);
 int ffp_jpeg_decode_dev(int device, const uint8_t* data, int64_t n, int bgr, uint8_t* d_out, int64_t row_stride, int64_t cap);
@@ -386,7 +389,8 @@ int ffp_jpeg_decode_stats(int64_t* device_decodes, int64_t* host_fallbacks, int6
  * launch per stage, one download of all files' scalars); batches whose streams would pass 256 MiB are cut into sub-batches.
  * ffp_jpeg_decode_batch: the same into n host buffers of caps[i] bytes (a readable file whose buffer is too small: FFP_ERR_ARG).
  * ffp_jpeg_decode_stats keeps counting files; FFP_JPEG_HOST_HUFFMAN=1 sends every file of a batch to the host decoder.
- * ffp_jpeg_decode_batch_stats: batches since load, kernel launches and stream synchronisations of the latest one. */
+ * ffp_jpeg_decode_batch_stats: calls of these two entries since load, kernel launches and stream synchronisations of the latest one
+ * (ffp_jpeg_decode / ffp_jpeg_decode_dev do not move them). Batches on different threads run side by side, each with a pooled workspace. */
 int ffp_jpeg_decode_batch_dev(int device, int n, const uint8_t* const* datas, const int64_t* sizes, int bgr,
                               uint8_t* d_base, const int64_t* offsets, const int64_t* strides, int64_t cap,
                               int32_t* hs, int32_t* ws, int32_t* status);

@@ -1,7 +1,9 @@
 """A batch of JPEG files decoded on the device in one pass (ffp_jpeg_decode_batch*, csrc/jpeg_huff.hip + csrc/jpeg_batch_plan.hpp): the read
 side of the reference's per-crop loop (utils/enhancer.py:344-391, one cv2.imread per crop). The bar is the single-file decoder's: pixels
 identical to libjpeg-turbo (Pillow) and to `jpeg_decode`, every valid file decoded on the device, whatever its neighbours in the batch
-are; an unreadable file costs its own status and nothing else; the number of launches does not depend on the number of files."""
+are; an unreadable file costs its own status and nothing else; the number of launches does not depend on the number of files. `jpeg_decode` is
+the same routine with one file, so the comparisons with it check that a file's pixels do not depend on its batch, and Pillow stays the independent
+oracle; single-file decodes and batches run side by side on pooled workspaces, and a refused single-file decode writes nothing."""
 import io
 
 import numpy as np
@@ -207,6 +209,67 @@ def test_unreadable_files_cost_their_own_status_only(gpu_lib):
     files, refs = ordinary_files(6)
     for g, r in zip(decode_all(gpu_lib, files), refs):
         assert np.array_equal(g, r)
+
+
+def test_single_file_decodes_and_a_batch_run_side_by_side(gpu_lib):
+    """A single file is a batch of one, and every call borrows a workspace from a pool: three threads of single-file decodes (one workgroup,
+    odd size, many workgroups) and one thread of batches at the same time, every result equal to Pillow's."""
+    import threading
+    files, refs = mixed_files()
+    picks = []
+    for shape in ((1, 1), (17, 33), (200, 264)):
+        picks.append(next(i for i, r in enumerate(refs) if r.shape[:2] == shape))
+    crops, crop_refs = ordinary_files(6)
+    wrong = []
+
+    def singles(i):
+        for k in range(5):
+            if not np.array_equal(gpu_lib.jpeg_decode(files[i]), refs[i]):
+                wrong.append(("single", i, k))
+
+    def batches():
+        for k in range(5):
+            got = gpu_lib.jpeg_decode_batch(crops)
+            if not all(isinstance(g, np.ndarray) and np.array_equal(g, r) for g, r in zip(got, crop_refs)):
+                wrong.append(("batch", k))
+
+    threads = [threading.Thread(target=singles, args=(i,)) for i in picks] + [threading.Thread(target=batches)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join(timeout=120)
+    assert not any(t.is_alive() for t in threads), "a decoding thread did not return"
+    assert wrong == []
+
+
+def test_the_batch_counter_ignores_single_file_decodes(gpu_lib):
+    files, refs = ordinary_files(6)
+    b0 = gpu_lib.jpeg_decode_batch_stats()[0]
+    for k in range(10):
+        assert np.array_equal(gpu_lib.jpeg_decode(files[k % 6]), refs[k % 6])
+    assert gpu_lib.jpeg_decode_batch_stats()[0] == b0
+    decode_all(gpu_lib, files)
+    assert gpu_lib.jpeg_decode_batch_stats()[0] == b0 + 1
+
+
+def test_a_refused_single_file_decode_leaves_the_buffer_untouched(gpu_lib):
+    import ctypes as C
+    import torch
+    from ffp_amd import synth
+    img = synth.synthetic_frame(48, 64, seed=9)
+    b = io.BytesIO()
+    Image.fromarray(img).save(b, "JPEG", quality=90, progressive=True)
+    junk = bytes(np.random.default_rng(1).integers(0, 256, 64, dtype=np.uint8))
+    cap = 48 * 64 * 3
+    d = torch.full((cap,), 0xA5, dtype=torch.uint8, device="cuda")
+    for data in (b.getvalue(), junk):
+        with pytest.raises(gpu_lib.FfpError) as e:
+            gpu_lib.jpeg_decode_dev(data, d.data_ptr(), 0, cap, bgr=True)
+        assert e.value.code == gpu_lib.FFP_ERR_ARG
+        buf = np.frombuffer(data, np.uint8)                      # the C entry itself (the wrapper above asks ffp_jpeg_info first)
+        rc = gpu_lib.lib().ffp_jpeg_decode_dev(0, buf.ctypes.data_as(C.POINTER(C.c_uint8)), len(buf), 1, C.c_void_p(d.data_ptr()), 0, cap)
+        assert rc == gpu_lib.FFP_ERR_ARG
+        assert (d.cpu().numpy() == 0xA5).all()
 
 
 def test_launches_and_synchronisations_do_not_depend_on_the_number_of_files(gpu_lib):

@@ -119,8 +119,8 @@ def test_decoder_states_need_no_extra_rounds_on_photographs(gpu_lib):
 
 def test_stream_that_never_self_synchronises_takes_extra_rounds(gpu_lib):
     """Flat areas coded with optimised tables are one-bit codes: a decoder that starts out of phase stays out of phase, nothing
-    synchronises by itself and the exact states have to travel from workgroup to workgroup — the path behind jpeg_huff_finish's
-    return code 2 (one host round trip per round). Still pixel-identical, still on the device."""
+    synchronises by itself and the exact states have to travel from workgroup to workgroup — the extra-rounds loop of
+    jpeg_decode_batch_to_device (one host round trip per round). Still pixel-identical, still on the device."""
     img = np.zeros((1600, 2048, 3), np.uint8)
     img[:, :1024] = (200, 30, 90)
     img[:, 1024:] = (20, 180, 240)
@@ -142,6 +142,8 @@ def test_corrupted_streams_never_hang_or_crash(gpu_lib):
     img = synth.synthetic_frame(200, 264, seed=12)
     files = [save(img, quality=90), save(img, quality=60, subsampling=0, optimize=True), save(img, quality=85, restart_marker_blocks=5)]
     outcomes = {"device": 0, "host": 0, "error": 0}
+    import torch
+    canvas = torch.full((200 * 264 * 3,), 0xA5, dtype=torch.uint8, device="cuda")
     for k in range(120):
         data = bytearray(files[k % 3])
         sos = data.index(b"\xff\xda") + 14
@@ -174,5 +176,10 @@ def test_corrupted_streams_never_hang_or_crash(gpu_lib):
                     assert np.array_equal(out, ref), k
         except RuntimeError:
             outcomes["error"] += 1
+            # both decoders refused the stream: the single-file decode has written nothing
+            with pytest.raises(gpu_lib.FfpError) as e:
+                gpu_lib.jpeg_decode_dev(bytes(data), canvas.data_ptr(), 0, canvas.numel(), bgr=True)
+            assert e.value.code == gpu_lib.FFP_ERR_ARG, k
+            assert (canvas.cpu().numpy() == 0xA5).all(), k
     assert sum(outcomes.values()) == 120 and outcomes["host"] + outcomes["error"] > 0
     assert np.array_equal(decode_on_device(gpu_lib, files[0]), pil_decode(files[0]))

@@ -10,6 +10,9 @@ memory, (a) a loop of ffp_jpeg_decode_dev, (b) one ffp_jpeg_decode_batch_dev. Ho
 "crops_dir": compat/utils/enhancer.py::enhance_face_crops_batch over a directory of 4, 16, 64 and 256 such files (x4 model, synthetic weights,
 tile 400, fp16), the batch route against the route that reads file by file, in the same form.
 
+--single (with --baseline-lib) -> profiles/jpeg_decode_single_mi355x.json: only "single" — one file through ffp_jpeg_decode_dev of the parent
+commit's build and of the library under test, a quality-95 crop and a 3840 x 2160 quality-95 4:2:0 frame, in the same form.
+
 --baseline-lib: a libffp.so built from the PARENT commit. Route (a) and the old crops-directory route then run on it (this change shares
 code with the single-file decoder, so the old routes are timed on the code as it was); without it they run on the library under test, and
 the file says so."""
@@ -109,6 +112,38 @@ def decode_probe(base):
     return out
 
 
+def single_probe(base):
+    """One file through ffp_jpeg_decode_dev of the parent library and of the library under test (where one file is a batch of one): a quality-95
+    crop and a 3840 x 2160 quality-95 4:2:0 frame. Same form as above; "inside" says whether the new median lies in the parent's min-max range."""
+    import torch
+    from PIL import Image
+    b = io.BytesIO()
+    Image.fromarray(synth.synthetic_frame(2160, 3840, seed=11)).save(b, "JPEG", quality=95, subsampling=2)
+    out = {}
+    for name, data in (("crop", crop_files(1, seed=101)[0]), ("frame_3840x2160", b.getvalue())):
+        h, w, _ = _lib.jpeg_info(data)
+        cap = h * w * 3
+        bufs = {k: torch.zeros(cap, dtype=torch.uint8, device="cuda") for k in ("parent", "new")}
+        torch.cuda.synchronize()
+        buf = np.frombuffer(data, np.uint8)
+        ptr = buf.ctypes.data_as(C.POINTER(C.c_uint8))
+
+        def route(l, d):
+            def go():
+                rc = l.ffp_jpeg_decode_dev(0, ptr, len(buf), 1, C.c_void_p(d.data_ptr()), 0, cap)
+                assert rc == 0, rc
+            return go
+
+        r = alternate({"parent": route(base, bufs["parent"]), "new": route(_lib.lib(), bufs["new"])}, reps=256 if name == "crop" else 16)
+        assert torch.equal(bufs["parent"], bufs["new"]), f"the two libraries' pixels differ ({name})"
+        r["file_bytes"], r["height"], r["width"] = len(data), h, w
+        r["new_median_inside_parent_range"] = bool(r["parent"]["min_ms"] <= r["new"]["median_ms"] <= r["parent"]["max_ms"])
+        r["new_median_above_parent_max"] = bool(r["new"]["median_ms"] > r["parent"]["max_ms"])
+        out[name] = r
+        print("single", name, json.dumps(r), flush=True)
+    return out
+
+
 def crops_dir_probe(base):
     from ffp_amd import compat
     compat.install()
@@ -158,10 +193,24 @@ def main():
     ap.add_argument("--baseline-lib", default=None)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "jpeg_decode_batch_mi355x.json"))
     ap.add_argument("--no-crops-dir", action="store_true")
+    ap.add_argument("--single", action="store_true", help="only the single-file section (needs --baseline-lib) -> profiles/jpeg_decode_single_mi355x.json")
     a = ap.parse_args()
     if _lib.device_count() < 1:
         raise SystemExit("no GPU: nothing is measured here")
     base = load_library(a.baseline_lib) if a.baseline_lib else _lib.lib()
+    if a.single:
+        if not a.baseline_lib:
+            raise SystemExit("--single compares against a build of the parent commit: give --baseline-lib")
+        out = a.out if a.out != ap.get_default("out") else os.path.join(ROOT, "profiles", "jpeg_decode_single_mi355x.json")
+        doc = {"what": "one file through ffp_jpeg_decode_dev, host clock in ms around the call (it ends in a stream synchronisation); median / min / max of 10 samples per "
+               "library, the parent commit's build and the library under test alternating in one process on one MI355X after one warm-up pass each; a sample is "
+               "the mean of 256 (crop) or 16 (frame) calls; tools/jpeg_batch_probe.py --single",
+               "single": single_probe(base)}
+        with open(out, "w") as fh:
+            json.dump(doc, fh, indent=1)
+            fh.write("\n")
+        print("wrote", out)
+        return
     doc = {"what": "host clock in ms around calls that end in a stream synchronisation; median / min / max of 10 samples per route, the two routes alternating in one process "
            "on one MI355X after one warm-up pass each; tools/jpeg_batch_probe.py",
            "old_routes_run_on": "a build of the parent commit" if a.baseline_lib else "the library under test",
