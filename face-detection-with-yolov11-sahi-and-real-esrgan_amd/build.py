@@ -147,8 +147,8 @@ def build_asan(verbose: bool = True) -> str:
     return ASAN_OUT
 
 
-def _build_host_check(out: str, driver: str, headers: list, verbose: bool) -> str:
-    """One stand-alone driver (own main, no HIP) built with the host compiler under AddressSanitizer + UBSan into csrc/build/<out>."""
+def _build_host_check(out: str, driver: str, headers: list, verbose: bool, sanitize: tuple = ("-fsanitize=address,undefined", "-fno-sanitize-recover=undefined")) -> str:
+    """One stand-alone driver (own main, no HIP) built with the host compiler under AddressSanitizer + UBSan (or `sanitize`) into csrc/build/<out>."""
     clang = os.path.join(os.path.dirname(os.path.realpath(_hipcc())), "..", "lib", "llvm", "bin", "clang++")
     if not os.path.exists(clang):
         clang = "/opt/rocm/lib/llvm/bin/clang++"
@@ -157,8 +157,7 @@ def _build_host_check(out: str, driver: str, headers: list, verbose: bool) -> st
     srcs = [os.path.join(CSRC, f) for f in [driver, *headers]]
     if os.path.exists(out) and os.path.getmtime(out) > max(os.path.getmtime(s) for s in srcs):
         return out
-    cmd = [clang, "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
-           srcs[0], "-o", out]
+    cmd = [clang, "-std=c++17", "-O1", "-g", "-Wall", *sanitize, "-fno-omit-frame-pointer", srcs[0], "-o", out]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"sanitizer build failed:\n{r.stdout}\n{r.stderr}")
@@ -193,6 +192,14 @@ def build_jpeg_batch_plan_check(verbose: bool = True) -> str:
     return _build_host_check("jpeg_batch_plan_host_check", "jpeg_batch_plan_host_check.cpp", ["jpeg_batch_plan.hpp"], verbose)
 
 
+def build_ws_pool_check(verbose: bool = True) -> tuple:
+    """The codecs' workspace pool (csrc/ws_pool.hpp, no HIP in it): seeded acquire / resize / release sequences against a shadow model and a threaded
+    phase, one driver built twice: under AddressSanitizer + UBSan and under ThreadSanitizer."""
+    args = ("ws_pool_host_check.cpp", ["ws_pool.hpp"], verbose)
+    return (_build_host_check("ws_pool_host_check_asan", *args, sanitize=("-pthread", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined")),
+            _build_host_check("ws_pool_host_check_tsan", *args, sanitize=("-pthread", "-fsanitize=thread")))
+
+
 if __name__ == "__main__":
     if "--asan" in sys.argv:
         build_asan()
@@ -206,6 +213,8 @@ if __name__ == "__main__":
         build_switches_check()
     elif "--jpeg-batch-plan-check" in sys.argv:
         build_jpeg_batch_plan_check()
+    elif "--ws-pool-check" in sys.argv:
+        build_ws_pool_check()
     elif "--variant" in sys.argv:
         build_variant(sys.argv[sys.argv.index("--variant") + 1])
     else:

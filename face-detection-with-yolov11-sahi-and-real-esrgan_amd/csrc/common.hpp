@@ -15,6 +15,7 @@
 
 #include "../../include/ffp.h"
 #include "switches.hpp"
+#include "ws_pool.hpp"
 
 namespace ffp {
 
@@ -95,6 +96,23 @@ struct HostPinned {
     n = bytes;
   }
 };
+
+// ---- the codecs' workspace pools (ws_pool.hpp) -------------------------------------------------------------
+// the pools' destroy hook: a workspace's buffers are freed with the device they live on current, and the caller's device is restored
+template <class W> void delete_on_owner_device(W* w) {
+  int cur = 0;
+  const int owner = w->device;
+  (void)hipGetDevice(&cur);
+  if (cur != owner) (void)hipSetDevice(owner);
+  delete w;
+  if (cur != owner) (void)hipSetDevice(cur);
+}
+// a workspace of the current device for the length of a scope; left by an exception, the lease waits for `st` before the workspace goes back
+template <class W> typename WsPool<W>::Lease lease_ws(WsPool<W>& pool, hipStream_t st) {
+  int dev = 0;
+  FFP_HIP(hipGetDevice(&dev));
+  return pool.acquire(dev, [st] { FFP_HIP(hipStreamSynchronize(st)); });
+}
 
 // ---- a batch of images at one resolution ("level") -------------------------------------------------------
 // Activations are NHWC; the images of a batch may differ in size (ragged) and are stored back to back, so a level is

@@ -11,8 +11,6 @@
 // Headers are written by the host (a few hundred bytes).
 #include <algorithm>
 #include <cstring>
-#include <map>
-#include <mutex>
 #include <vector>
 
 #include <cstdlib>
@@ -388,13 +386,21 @@ void put_seg(std::vector<unsigned char>& o, int marker, const std::vector<unsign
   o.insert(o.end(), payload.begin(), payload.end());
 }
 
+// What one encode in flight holds, borrowed from a pool (ws_pool.hpp), so that encodes on different threads run side by side
 struct Workspace {
   DevBuf coef, len, off, sums, total, words, cnt, cnt_off, cnt_sums, cnt_total, out, hd, qdiv, imgs, img_vals, img_len, first_chunk, chunk_img;
   size_t cap_blocks = 0, cap_words = 0, cap_imgs = 0;
   bool tables = false;
+  int device = 0;
+  size_t held() const {
+    size_t b = 0;
+    for (const DevBuf* d : {&coef, &len, &off, &sums, &total, &words, &cnt, &cnt_off, &cnt_sums, &cnt_total, &out, &hd, &qdiv, &imgs, &img_vals, &img_len, &first_chunk, &chunk_img})
+      b += d->n;
+    return b;
+  }
 };
-std::mutex g_mu;
-std::map<int, Workspace> g_ws;
+// at most 8 idle ones, none above 768 MB (never destroyed: nothing is freed at exit, when the runtime may be gone)
+WsPool<Workspace>& g_pool = *new WsPool<Workspace>(WsPolicy{8, 0, 768u << 20}, delete_on_owner_device<Workspace>);
 
 void exclusive_scan(const unsigned* d_in, int n, unsigned long long* d_out, unsigned long long* d_sums, unsigned long long* d_total, hipStream_t st) {
   const int groups = (n + 1023) / 1024;
@@ -433,10 +439,8 @@ std::vector<unsigned char> jpeg_header(int h, int w, int quality) {
 void jpeg_encode_batch_device(const JpegSrc* src, int n_img, int bgr, int quality, std::vector<std::vector<unsigned char>>& files, hipStream_t st) {
   files.assign(n_img, {});
   if (n_img == 0) return;
-  int dev = 0;
-  FFP_HIP(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lock(g_mu);
-  Workspace& ws = g_ws[dev];
+  auto lease = lease_ws(g_pool, st);
+  Workspace& ws = *lease;
   if (!ws.tables) {
     HuffDev hd;
     std::memset(&hd, 0, sizeof(hd));
@@ -719,39 +723,6 @@ void JpegDecodeWs::ensure_host(const JpegScan& s) {
     host[c].ensure(cap[c] * 64 * sizeof(short));
     const_cast<JpegScan&>(s).coef[c] = static_cast<short*>(host[c].p);
   }
-}
-
-namespace {
-std::mutex g_dec_mu;
-std::vector<JpegDecodeWs*> g_dec_free;
-}  // namespace
-
-JpegDecodeWs* jpeg_ws_acquire() {
-  int dev = 0;
-  FFP_HIP(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lock(g_dec_mu);
-  for (size_t i = 0; i < g_dec_free.size(); ++i)
-    if (g_dec_free[i]->device == dev) {               // a workspace's buffers live on the device that was current when it was made
-      JpegDecodeWs* w = g_dec_free[i];
-      g_dec_free.erase(g_dec_free.begin() + i);
-      return w;
-    }
-  JpegDecodeWs* w = new JpegDecodeWs();
-  w->device = dev;
-  return w;
-}
-
-void jpeg_ws_release(JpegDecodeWs* ws) {
-  constexpr size_t kPoolCap = 32;                     // a handful of frames' worth of staging per device; beyond that, free
-  std::unique_lock<std::mutex> lock(g_dec_mu);
-  if (g_dec_free.size() < kPoolCap) { g_dec_free.push_back(ws); return; }
-  lock.unlock();
-  int cur = 0;
-  const int owner = ws->device;
-  (void)hipGetDevice(&cur);
-  if (cur != owner) (void)hipSetDevice(owner);
-  delete ws;
-  if (cur != owner) (void)hipSetDevice(cur);
 }
 
 void jpeg_reconstruct_device(const JpegScan& s, JpegDecodeWs& ws, unsigned char* d_out, long long stride, int bgr, hipStream_t st) {

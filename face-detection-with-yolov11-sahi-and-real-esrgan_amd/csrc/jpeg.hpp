@@ -71,7 +71,7 @@ void jpeg_batch_reconstruct(const JpegBatchIdct* d_idct, int n_idct, int n_idct_
 
 // ---- decoding: the host decoder's staging (jpeg.hip) ------------------------------------------------------------------------------------
 // One host-decoded file in flight: pinned host coefficient planes (the entropy decoder writes them, the copies to the device run at full
-// PCIe rate) and their device twins + sample planes; kept in a pool so that concurrent decodes neither allocate nor free
+// PCIe rate) and their device twins + sample planes; kept in a pool (jpeg_huff.hip) so that concurrent decodes neither allocate nor free
 struct JpegDecodeWs {
   HostPinned host[3];                           // allocated on first use
   DevBuf coef_all, plane[3], qt;                // the three coefficient planes are one allocation
@@ -83,20 +83,10 @@ struct JpegDecodeWs {
   JpegDecodeWs& operator=(const JpegDecodeWs&) = delete;
   void ensure(const JpegScan& s);               // sizes the device planes for the scan
   void ensure_host(const JpegScan& s);          // ... and the pinned host planes, and points s.coef at them
-};
-JpegDecodeWs* jpeg_ws_acquire();
-void jpeg_ws_release(JpegDecodeWs* ws);
-struct JpegWsLease {                            // a pooled workspace for the length of a scope
-  JpegDecodeWs* const ws = jpeg_ws_acquire();
-  JpegWsLease() = default;
-  JpegWsLease(const JpegWsLease&) = delete;
-  JpegWsLease& operator=(const JpegWsLease&) = delete;
-  ~JpegWsLease() { jpeg_ws_release(ws); }
-  JpegDecodeWs* operator->() const { return ws; }
-  JpegDecodeWs& operator*() const { return *ws; }
+  size_t held() const { return host[0].n + host[1].n + host[2].n + coef_all.n + plane[0].n + plane[1].n + plane[2].n + qt.n; }
 };
 // the coefficients in s.coef (host decoder) go up; dequantisation + integer IDCT + upsampling + colour conversion into d_out (h x w x 3
-// uint8, row pitch `stride`, RGB or BGR). Queues on `st`, no synchronisation.
+// uint8, row pitch `stride`, RGB or BGR). Queues on `st`, no synchronisation: the caller waits for `st` before ws goes back to its pool.
 void jpeg_reconstruct_device(const JpegScan& s, JpegDecodeWs& ws, unsigned char* d_out, long long stride, int bgr, hipStream_t st);
 
 }  // namespace ffp

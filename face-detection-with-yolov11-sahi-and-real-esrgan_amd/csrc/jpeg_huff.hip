@@ -26,7 +26,6 @@
 #include <atomic>
 #include <cstddef>
 #include <cstring>
-#include <mutex>
 #include <string>
 #include <vector>
 
@@ -560,54 +559,24 @@ std::atomic<long long> g_batch_count{0}, g_batch_launches{0}, g_batch_syncs{0};
 
 // ---- workspaces ----------------------------------------------------------------------------------------------------------------------------
 // The three arenas of jpeg_batch_plan.hpp and the pinned image of `up` (with the scalars' landing place behind it). A decode borrows one for
-// its length, so decodes on different threads run side by side, each on its own stream. What stays pooled when nobody decodes: at most
-// kPoolCap workspaces, and per device at most one that holds more than kFrameBytes (a batch of many files, a 16K frame); a second such one is
-// freed when it comes back.
+// its length (ws_pool.hpp), so decodes on different threads run side by side, each on its own stream. What stays pooled when nobody decodes:
+// at most 32 workspaces, and per device at most one that holds more than kFrameBytes (a batch of many files, a 16K frame); a second such one
+// is freed when it comes back.
 struct BatchWs {
   HostPinned stage;
   DevBuf up, work, coef;
   int device = 0;                                // buffers live on the device that was current when the workspace was made
   size_t held() const { return stage.n + up.n + work.n + coef.n; }
 };
-constexpr size_t kPoolCap = 32;                  // as many as the host decoder's pool keeps (jpeg.hip)
 constexpr size_t kFrameBytes = 160u << 20;       // above what a 3840 x 2160 frame takes: ~55 MiB at 4:2:0 quality 95, ~145 MiB at 4:4:4 with an 8 MB stream
-std::mutex g_ws_mu;
-std::vector<BatchWs*> g_ws_free;
-
-struct BatchWsLease {
-  BatchWs* w = nullptr;
-  BatchWsLease() {
-    int dev = 0;
-    FFP_HIP(hipGetDevice(&dev));
-    {
-      std::lock_guard<std::mutex> lock(g_ws_mu);
-      for (size_t i = 0; i < g_ws_free.size() && !w; ++i)
-        if (g_ws_free[i]->device == dev) { w = g_ws_free[i]; g_ws_free.erase(g_ws_free.begin() + i); }
-    }
-    if (!w) { w = new BatchWs(); w->device = dev; }
-  }
-  BatchWsLease(const BatchWsLease&) = delete;
-  BatchWsLease& operator=(const BatchWsLease&) = delete;
-  ~BatchWsLease() {
-    {
-      std::lock_guard<std::mutex> lock(g_ws_mu);
-      bool big_kept = false;
-      for (const BatchWs* f : g_ws_free) big_kept = big_kept || (f->device == w->device && f->held() > kFrameBytes);
-      if (g_ws_free.size() < kPoolCap && !(big_kept && w->held() > kFrameBytes)) { g_ws_free.push_back(w); return; }
-    }
-    int cur = 0;                                 // freed with the owning device current
-    const int owner = w->device;
-    (void)hipGetDevice(&cur);
-    if (cur != owner) (void)hipSetDevice(owner);
-    delete w;
-    if (cur != owner) (void)hipSetDevice(cur);
-  }
-};
+// (never destroyed: nothing is freed at exit, when the runtime may be gone)
+WsPool<BatchWs>& g_batch_pool = *new WsPool<BatchWs>(WsPolicy{32, kFrameBytes, 0}, delete_on_owner_device<BatchWs>);
+WsPool<JpegDecodeWs>& g_host_pool = *new WsPool<JpegDecodeWs>(WsPolicy{32, 0, 0}, delete_on_owner_device<JpegDecodeWs>);     // the host decoder's staging
 
 // the host decoder for one file: a stream the device decoder flagged, a file outside its limits, everything under FFP_JPEG_HOST_HUFFMAN=1.
 // It reproduces libjpeg's behaviour on damaged streams, and its refusals are the error reports of the decoding entries.
 void host_decode_one(const unsigned char* data, long long n, JpegScan& s, unsigned char* d_out, long long stride, int bgr, hipStream_t st, JpegBatchCost& k) {
-  JpegWsLease ws;
+  auto ws = lease_ws(g_host_pool, st);
   ws->ensure_host(s);
   jpeg_entropy_decode(data, n, s, false);
   jpeg_reconstruct_device(s, *ws, d_out, stride, bgr, st);
@@ -745,8 +714,8 @@ void jpeg_decode_batch_to_device(int n, const unsigned char* const* datas, const
   std::vector<unsigned char> to_host((size_t)n, 0);
   for (int i = 0; i < n; ++i) to_host[i] = readable[i] && plan.files[i].sub < 0;
   if (!plan.subs.empty()) {
-    BatchWsLease lease;
-    BatchWs& W = *lease.w;
+    auto lease = lease_ws(g_batch_pool, st);
+    BatchWs& W = *lease;
     for (const jbp::SubPlan& S : plan.subs) {
       const int m = (int)S.files.size();
       const size_t scal_host = (size_t)jbp::align_up(S.up_bytes);

@@ -10,8 +10,6 @@
 //   png_scan_kernel / png_gather_kernel   prefix sum of the chunk sizes; chunks copied from their worst-case slots to their final
 //                         offsets; signature, IHDR, the Adler-32 trailer (its own 4-byte IDAT) and IEND per image
 // What a PNG reader decodes is the contract (tests/test_gpu_png.py), not libpng's bytes.
-#include <map>
-#include <mutex>
 #include <vector>
 
 #include "png.hpp"
@@ -554,11 +552,14 @@ __global__ void __launch_bounds__(256) png_gather_kernel(const PngImg* __restric
   put_be32(t + 24, crc_serial(t + 20, 4));
 }
 
+// What one encode in flight holds, borrowed from a pool (ws_pool.hpp), so that encodes on different threads run side by side
 struct Workspace {
   DevBuf filt, slots, out, slot_len, seg_adler, seg_off, imgs, seg_img, file_off;
+  int device = 0;
+  size_t held() const { return filt.n + slots.n + out.n; }     // the three that grow with the image; the rest is a few bytes per segment
 };
-std::mutex g_mu;
-std::map<int, Workspace> g_ws;
+// at most 8 idle ones; a 16K frame's gigabyte is not kept (never destroyed: nothing is freed at exit, when the runtime may be gone)
+WsPool<Workspace>& g_pool = *new WsPool<Workspace>(WsPolicy{8, 0, 768u << 20}, delete_on_owner_device<Workspace>);
 
 void ensure(DevBuf& b, size_t bytes) {
   if (b.n < bytes) b = DevBuf(bytes + bytes / 4);
@@ -604,10 +605,8 @@ long long png_encode_batch_device(const PngSrc* src, int n_img, int channels, in
   long long out_bound = 0;
   for (int i = 0; i < n_img; ++i) out_bound += png_bound(src[i].h, src[i].w, channels, bit_depth);
 
-  int dev = 0;
-  FFP_HIP(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lock(g_mu);
-  Workspace& ws = g_ws[dev];
+  auto lease = lease_ws(g_pool, st);
+  Workspace& ws = *lease;
   ensure(ws.filt, (size_t)filt_total + 16);
   ensure(ws.slots, (size_t)n_seg * kSlot);
   ensure(ws.out, (size_t)out_bound + 16);
@@ -642,7 +641,6 @@ long long png_encode_batch_device(const PngSrc* src, int n_img, int channels, in
   const long long total = offsets[n_img];
   FFP_CHECK(total > 0 && total <= out_bound, FFP_ERR_STATE, "png: the encoder reported %lld bytes (bound %lld)", total, out_bound);
   if (out && cap >= total) FFP_HIP(hipMemcpy(out, ws.out.p, (size_t)total, hipMemcpyDeviceToHost));
-  if (ws.filt.n + ws.slots.n + ws.out.n > (768u << 20)) { ws.filt = DevBuf(); ws.slots = DevBuf(); ws.out = DevBuf(); }   // a 16K frame's gigabyte is not kept
   return total;
 }
 

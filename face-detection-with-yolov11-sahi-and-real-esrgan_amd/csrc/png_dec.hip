@@ -13,9 +13,7 @@
 // inflates the file (png_dec.cpp, the same core), the filtered stream goes up, and the same unfilter kernel runs.
 // No workgroup waits for another: the only synchronisation is __syncthreads() and stream order. Every loop is bounded (see each).
 #include <atomic>
-#include <mutex>
 
-#include "jpeg.hpp"
 #include "png_dec.hpp"
 #include "png_inflate.hpp"
 
@@ -407,53 +405,18 @@ template <int CH, int BPS> void launch_unfilter(const UnfArgs& a, hipStream_t st
   hipLaunchKernelGGL((png_unfilter_kernel<CH, BPS>), dim3(1), dim3(256), 0, st, a);
 }
 
-// What one decode in flight holds: device buffers from a pool of this file (one workspace per concurrent decode and device, as the JPEG decoder keeps
-// them), and the pinned staging of a workspace borrowed from the pool ffp_jpeg_decode_dev uses (jpeg_ws_acquire): the file on its way up (serial route:
-// the filtered stream), the scalars on their way back. No lock is held while a file is decoded.
+// What one decode in flight holds, borrowed from a pool (ws_pool.hpp: one workspace per concurrent decode and device, as the JPEG decoder keeps them):
+// the device buffers and the pinned staging: the file on its way up (serial route: the filtered stream), the scalars on their way back. No lock is held
+// while a file is decoded.
 struct Workspace {
   int device = 0;
   DevBuf file, filt, spans, span_len, span_status, off, small, sums, carry;
-  HostPinned* stage = nullptr;     // of the borrowed JpegDecodeWs, for the length of one decode
+  HostPinned stage;
+  size_t held() const { return file.n + filt.n + spans.n + span_len.n + span_status.n + off.n + small.n + sums.n + carry.n + stage.n; }
 };
-std::mutex g_mu;
-std::vector<Workspace*> g_free;
+// at most 8 idle ones; a 16K frame's buffers are not kept (never destroyed: nothing is freed at exit, when the runtime may be gone)
+WsPool<Workspace>& g_pool = *new WsPool<Workspace>(WsPolicy{8, 0, 768u << 20}, delete_on_owner_device<Workspace>);
 std::atomic<long long> g_parallel{0}, g_serial{0};
-constexpr size_t kPoolCap = 8, kKeepBytes = 768u << 20;      // a 16K frame's buffers are not kept
-
-struct Lease {
-  Workspace* ws = nullptr;
-  JpegDecodeWs* jw = nullptr;
-  hipStream_t st;
-  explicit Lease(hipStream_t s) : st(s) {
-    int dev = 0;
-    FFP_HIP(hipGetDevice(&dev));
-    {
-      std::lock_guard<std::mutex> lock(g_mu);
-      for (size_t i = 0; i < g_free.size(); ++i)
-        if (g_free[i]->device == dev) { ws = g_free[i]; g_free.erase(g_free.begin() + i); break; }
-    }
-    if (!ws) { ws = new Workspace(); ws->device = dev; }
-    try {
-      jw = jpeg_ws_acquire();
-    } catch (...) {
-      delete ws;
-      throw;
-    }
-    ws->stage = &jw->host[0];
-  }
-  ~Lease() {
-    (void)hipStreamSynchronize(st);                            // on a throw, copies out of the staging may still be in flight
-    ws->stage = nullptr;
-    if (jw->host[0].n > kKeepBytes) delete jw; else jpeg_ws_release(jw);
-    if (ws->file.n + ws->filt.n > kKeepBytes) { delete ws; return; }
-    std::unique_lock<std::mutex> lock(g_mu);
-    if (g_free.size() < kPoolCap) { g_free.push_back(ws); return; }
-    lock.unlock();
-    delete ws;
-  }
-  Lease(const Lease&) = delete;
-  Lease& operator=(const Lease&) = delete;
-};
 
 // device words of Workspace::small
 struct Small {
@@ -492,16 +455,16 @@ bool decode_parallel(Workspace& ws, const unsigned char* data, long long n, cons
   const unsigned long long want = (unsigned long long)f.filtered_len();
   std::vector<DSpan> spans((size_t)ns);
   for (int s = 0; s < ns; ++s) spans[s] = DSpan{(unsigned long long)f.idat[s].off + (s == 0 ? 2ull : 0ull), (unsigned long long)(f.idat[s].off + f.idat[s].len)};
-  ws.stage->ensure((size_t)n + 64);
-  std::memcpy(ws.stage->p, data, (size_t)n);
+  ws.stage.ensure((size_t)n + 64);
+  std::memcpy(ws.stage.p, data, (size_t)n);
   ws.file.ensure((size_t)n + 64);
   ws.spans.ensure((size_t)ns * sizeof(DSpan));
   ws.span_len.ensure((size_t)ns * sizeof(unsigned long long));
   ws.span_status.ensure((size_t)ns * sizeof(int));
   ws.off.ensure(((size_t)ns + 1) * sizeof(unsigned long long));
   Small* sm = ws.small.as<Small>();
-  Small* back = reinterpret_cast<Small*>(static_cast<unsigned char*>(ws.stage->p) + (((size_t)n + 15) & ~(size_t)15));
-  FFP_HIP(hipMemcpyAsync(ws.file.p, ws.stage->p, (size_t)n, hipMemcpyHostToDevice, st));
+  Small* back = reinterpret_cast<Small*>(static_cast<unsigned char*>(ws.stage.p) + (((size_t)n + 15) & ~(size_t)15));
+  FFP_HIP(hipMemcpyAsync(ws.file.p, ws.stage.p, (size_t)n, hipMemcpyHostToDevice, st));
   FFP_HIP(hipMemcpyAsync(ws.spans.p, spans.data(), sizeof(DSpan) * (size_t)ns, hipMemcpyHostToDevice, st));
   FFP_HIP(hipMemsetAsync(ws.small.p, 0, sizeof(Small), st));
   hipLaunchKernelGGL(png_inflate_kernel<false>, dim3((unsigned)ns), dim3(64), 0, st, ws.file.as<unsigned char>(), ws.spans.as<DSpan>(), ns, want,
@@ -533,10 +496,10 @@ bool decode_parallel(Workspace& ws, const unsigned char* data, long long n, cons
 
 void decode_serial(Workspace& ws, const unsigned char* data, const PngFile& f, int bgr, void* d_out, long long stride, hipStream_t st) {
   const long long want = f.filtered_len();
-  ws.stage->ensure((size_t)want + 64);
-  png_inflate_serial(data, f, static_cast<unsigned char*>(ws.stage->p));
+  ws.stage.ensure((size_t)want + 64);
+  png_inflate_serial(data, f, static_cast<unsigned char*>(ws.stage.p));
   ws.filt.ensure((size_t)want + 64);
-  FFP_HIP(hipMemcpyAsync(ws.filt.p, ws.stage->p, (size_t)want, hipMemcpyHostToDevice, st));
+  FFP_HIP(hipMemcpyAsync(ws.filt.p, ws.stage.p, (size_t)want, hipMemcpyHostToDevice, st));
   FFP_HIP(hipMemsetAsync(ws.small.p, 0, sizeof(Small), st));
   run_unfilter(ws, f, bgr, d_out, stride, st);
   FFP_HIP(hipStreamSynchronize(st));
@@ -562,8 +525,8 @@ void png_decode_to_device(const unsigned char* data, long long n, const PngFile&
   FFP_CHECK(cap >= (long long)(f.h - 1) * stride + row, FFP_ERR_ARG, "png_decode: output buffer too small for %d x %d x %d at %d bits (%lld bytes needed)", f.w, f.h,
             f.channels, f.bit_depth, (long long)(f.h - 1) * stride + row);
   FFP_CHECK((flags & ~kPngDecSerial) == 0, FFP_ERR_ARG, "png_decode: unknown flags 0x%x", flags);
-  Lease lease(st);
-  Workspace& ws = *lease.ws;
+  auto lease = lease_ws(g_pool, st);
+  Workspace& ws = *lease;
   ws.small.ensure(sizeof(Small));
   bool done = false;
   if (!(flags & kPngDecSerial) && f.adler_alone && f.zlib_header && f.idat[0].len >= 2 && f.idat.size() - 1 < (1u << 30))

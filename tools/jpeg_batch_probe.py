@@ -13,6 +13,10 @@ tile 400, fp16), the batch route against the route that reads file by file, in t
 --single (with --baseline-lib) -> profiles/jpeg_decode_single_mi355x.json: only "single" — one file through ffp_jpeg_decode_dev of the parent
 commit's build and of the library under test, a quality-95 crop and a 3840 x 2160 quality-95 4:2:0 frame, in the same form.
 
+--codec-pool (with --baseline-lib) -> profiles/codec_pool_mi355x.json: one call each of ffp_jpeg_encode_dev, ffp_png_encode_dev, ffp_png_decode_dev and
+ffp_jpeg_decode_dev (the four entries behind the workspace pool, csrc/ws_pool.hpp) of the parent commit's build and of the library under test, at a
+crop size and at 3840 x 2160, in the same form; the files and pixels of the two libraries are compared once per case.
+
 --baseline-lib: a libffp.so built from the PARENT commit. Route (a) and the old crops-directory route then run on it (this change shares
 code with the single-file decoder, so the old routes are timed on the code as it was); without it they run on the library under test, and
 the file says so."""
@@ -144,6 +148,59 @@ def single_probe(base):
     return out
 
 
+def codec_pool_probe(base):
+    """One call of each of the four codec entries of the parent library and of the library under test, a crop (the size pipeline.sr_crop_sizes draws first)
+    and a 3840 x 2160 frame. Same form as single_probe; the two libraries' bytes and pixels are compared."""
+    import torch
+    from PIL import Image
+    cur = _lib.lib()
+    s = int(pipeline.sr_crop_sizes(1, seed=101)[0])
+    frame = synth.synthetic_frame(2160, 3840, seed=11)
+    out = {}
+    for name, img in (("crop", np.ascontiguousarray(frame[:s, :s])), ("frame_3840x2160", frame)):
+        h, w = img.shape[:2]
+        d_img = torch.from_numpy(img).cuda()
+        b = io.BytesIO()
+        Image.fromarray(img).save(b, "JPEG", quality=95)
+        jpg = np.frombuffer(b.getvalue(), np.uint8)
+        png = np.frombuffer(_lib.png_encode(img), np.uint8)
+        cap = max(1024 + h * w * 3, _lib.png_bound(h, w))
+        reps = 64 if name == "crop" else 4
+        u8 = C.POINTER(C.c_uint8)
+        for entry in ("jpeg_encode_dev", "png_encode_dev", "png_decode_dev", "jpeg_decode_dev"):
+            host = {k: np.zeros(cap, np.uint8) for k in ("parent", "new")}
+            dev = {k: torch.zeros(h * w * 3, dtype=torch.uint8, device="cuda") for k in ("parent", "new")}
+            size = {k: C.c_int64(0) for k in ("parent", "new")}
+            torch.cuda.synchronize()
+
+            def route(l, k):
+                def go():
+                    if entry == "jpeg_encode_dev":
+                        rc = l.ffp_jpeg_encode_dev(0, C.c_void_p(d_img.data_ptr()), h, w, w * 3, 0, 95, host[k].ctypes.data_as(u8), cap, C.byref(size[k]))
+                    elif entry == "png_encode_dev":
+                        rc = l.ffp_png_encode_dev(0, C.c_void_p(d_img.data_ptr()), h, w, 3, 8, w * 3, 0, 1, host[k].ctypes.data_as(u8), cap, C.byref(size[k]))
+                    elif entry == "png_decode_dev":
+                        rc = l.ffp_png_decode_dev(0, png.ctypes.data_as(u8), len(png), 0, 0, C.c_void_p(dev[k].data_ptr()), 0, h * w * 3)
+                    else:
+                        rc = l.ffp_jpeg_decode_dev(0, jpg.ctypes.data_as(u8), len(jpg), 0, C.c_void_p(dev[k].data_ptr()), 0, h * w * 3)
+                    assert rc == 0, (entry, rc)
+                return go
+
+            r = alternate({"parent": route(base, "parent"), "new": route(cur, "new")}, reps=reps)
+            if entry.endswith("encode_dev"):
+                assert size["parent"].value == size["new"].value > 0 and np.array_equal(host["parent"], host["new"]), f"the two libraries' files differ ({entry}, {name})"
+                r["file_bytes"] = int(size["new"].value)
+            else:
+                assert torch.equal(dev["parent"], dev["new"]) and bool(dev["new"].any()), f"the two libraries' pixels differ ({entry}, {name})"
+                r["file_bytes"] = int(len(png) if entry == "png_decode_dev" else len(jpg))
+            r["height"], r["width"] = h, w
+            r["new_median_inside_parent_range"] = bool(r["parent"]["min_ms"] <= r["new"]["median_ms"] <= r["parent"]["max_ms"])
+            r["new_median_above_parent_max"] = bool(r["new"]["median_ms"] > r["parent"]["max_ms"])
+            out[f"{entry}/{name}"] = r
+            print("codec_pool", entry, name, json.dumps(r), flush=True)
+    return out
+
+
 def crops_dir_probe(base):
     from ffp_amd import compat
     compat.install()
@@ -194,10 +251,25 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "jpeg_decode_batch_mi355x.json"))
     ap.add_argument("--no-crops-dir", action="store_true")
     ap.add_argument("--single", action="store_true", help="only the single-file section (needs --baseline-lib) -> profiles/jpeg_decode_single_mi355x.json")
+    ap.add_argument("--codec-pool", action="store_true", help="only the four codec entries (needs --baseline-lib) -> profiles/codec_pool_mi355x.json")
     a = ap.parse_args()
     if _lib.device_count() < 1:
         raise SystemExit("no GPU: nothing is measured here")
     base = load_library(a.baseline_lib) if a.baseline_lib else _lib.lib()
+    if a.codec_pool:
+        if not a.baseline_lib:
+            raise SystemExit("--codec-pool compares against a build of the parent commit: give --baseline-lib")
+        out = a.out if a.out != ap.get_default("out") else os.path.join(ROOT, "profiles", "codec_pool_mi355x.json")
+        doc = {"what": "one call of each codec entry, host clock in ms around the call (it ends in a stream synchronisation); median / min / max of 10 samples per "
+               "library, the parent commit's build and the library under test alternating in one process on one MI355X after one warm-up pass each; a sample is "
+               "the mean of 64 (crop) or 4 (frame) calls; tools/jpeg_batch_probe.py --codec-pool",
+               "codec_pool": codec_pool_probe(base)}
+        doc["medians_above_parent_max"] = [k for k, r in doc["codec_pool"].items() if r["new_median_above_parent_max"]]
+        with open(out, "w") as fh:
+            json.dump(doc, fh, indent=1)
+            fh.write("\n")
+        print("wrote", out)
+        return
     if a.single:
         if not a.baseline_lib:
             raise SystemExit("--single compares against a build of the parent commit: give --baseline-lib")
