@@ -242,6 +242,8 @@ _SIGS = {
                                         _p(C.c_double), _p(C.c_double), C.c_int64, _p(C.c_int64)]),
     "ffp_iqa_niqe_luma": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_float)]),
     "ffp_iqa_niqe_score": (C.c_int, [_p(C.c_double), _p(C.c_int64), C.c_int, _p(C.c_double), _p(C.c_double), _p(C.c_double)]),
+    "ffp_overlay_draw_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),
+    "ffp_overlay_draw": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -1507,17 +1509,57 @@ def jpeg_encode_dev(d_ptr: int, h: int, w: int, row_stride: int, quality: int = 
     return out[:n.value].tobytes()
 
 
-def jpeg_encode_batch_dev(d_base: int, offsets, hs, ws, quality: int = 95, bgr: bool = True, device: int = 0):
-    """n device-resident images (d_base + offsets[i], hs[i] x ws[i] x 3, tightly packed rows) -> list of JPEG files, one pass on the GPU."""
+def jpeg_encode_batch_dev(d_base: int, offsets, hs, ws, quality: int = 95, bgr: bool = True, device: int = 0, strides=None):
+    """n device-resident images (d_base + offsets[i], hs[i] x ws[i] x 3, tightly packed rows, or with row pitches of strides[i] bytes: views of one
+    frame) -> list of JPEG files, one pass on the GPU."""
     offsets = np.ascontiguousarray(offsets, np.int64)
     hs, ws = np.ascontiguousarray(hs, np.int32), np.ascontiguousarray(ws, np.int32)
     n = len(offsets)
+    st = None if strides is None else np.ascontiguousarray(strides, np.int64)
     cap = int(1024 * n + 3 * (hs.astype(np.int64) * ws).sum())
     out = np.empty(max(cap, 1), np.uint8)
     oo = np.zeros(n + 1, np.int64)
     _check(lib().ffp_jpeg_encode_batch_dev(device, C.c_void_p(d_base), n, offsets.ctypes.data_as(_p(C.c_int64)), hs.ctypes.data_as(_p(C.c_int32)),
-                                           ws.ctypes.data_as(_p(C.c_int32)), None, int(bgr), quality, out.ctypes.data_as(_p(C.c_uint8)), cap, oo.ctypes.data_as(_p(C.c_int64))))
+                                           ws.ctypes.data_as(_p(C.c_int32)), None if st is None else st.ctypes.data_as(_p(C.c_int64)), int(bgr), quality,
+                                           out.ctypes.data_as(_p(C.c_uint8)), cap, oo.ctypes.data_as(_p(C.c_int64))))
     return [out[oo[i]:oo[i + 1]].tobytes() for i in range(n)]
+
+
+OVERLAY_RECT, OVERLAY_STAMP = 0, 1          # include/ffp.h
+OVERLAY_MAX_PRIMS = 1 << 20
+OVERLAY_PRIM_BYTES = 32
+
+
+class OverlayPrim(C.Structure):
+    """ffp_overlay_prim (include/ffp.h). RECT: corners (x0, y0)..(x1, y1) inclusive, width 0 = fill / >= 1 = frame. STAMP: top-left (x0, y0),
+    x1 x y1 the mask's width x height, width its row pitch, mask_off its first byte in the pool."""
+    _fields_ = [("kind", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32), ("y1", C.c_int32), ("width", C.c_int32),
+                ("mask_off", C.c_int32), ("color", C.c_uint8 * 4)]
+
+
+OVERLAY_PRIM_DTYPE = np.dtype(OverlayPrim)      # the same 32 bytes as a numpy record: what the primitive builders fill
+
+
+def _overlay_args(prims, masks):
+    prims = np.ascontiguousarray(prims, OVERLAY_PRIM_DTYPE).reshape(-1)
+    masks = np.zeros(0, np.uint8) if masks is None else np.ascontiguousarray(masks, np.uint8).reshape(-1)
+    return prims, masks, C.c_void_p(prims.ctypes.data if prims.size else None), C.c_void_p(masks.ctypes.data if masks.size else None)
+
+
+def overlay_draw_dev(d_ptr: int, h: int, w: int, row_stride: int, prims, masks=None, device: int = 0) -> None:
+    """Paints `prims` (records of OVERLAY_PRIM_DTYPE, in painter's order) into the h x w x 3 uint8 image in device memory at d_ptr (row pitch
+    in bytes, any base alignment), in place (csrc/overlay.hip). masks: the uint8 pool the stamps point into."""
+    prims, masks, pp, mp = _overlay_args(prims, masks)
+    _check(lib().ffp_overlay_draw_dev(device, C.c_void_p(d_ptr), h, w, row_stride, pp, len(prims), mp, masks.size))
+
+
+def overlay_draw(img: np.ndarray, prims, masks=None, device: int = 0) -> np.ndarray:
+    """The same on a host image (h x w x 3 uint8, rows w*3 bytes apart or further), in place; returns it."""
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3 or img.strides[1:] != (3, 1) or img.strides[0] < img.shape[1] * 3 or not img.flags.writeable:
+        raise ValueError("overlay_draw: a writeable h x w x 3 uint8 array with contiguous pixels")
+    prims, masks, pp, mp = _overlay_args(prims, masks)
+    _check(lib().ffp_overlay_draw(device, C.c_void_p(img.ctypes.data), img.shape[0], img.shape[1], img.strides[0], pp, len(prims), mp, masks.size))
+    return img
 
 
 def png_bound(h: int, w: int, channels: int = 3, bit_depth: int = 8) -> int:

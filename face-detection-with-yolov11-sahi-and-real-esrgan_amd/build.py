@@ -15,7 +15,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libffp.so")
-SOURCES = ["common.cpp", "weights.cpp", "engine.cpp", "conv_route.cpp", "conv_mfma.hip", "conv_rows.hip", "conv_rows16.hip", "conv_rows16pc.hip", "conv_trunk.hip", "conv_pw.hip", "conv_k3d.hip", "conv_dwpw.hip", "ops_misc.hip", "det_post.hip", "merge.hip", "eval.hip", "coco_eval.hip", "iqa.hip", "jpeg.hip", "jpeg_huff.hip", "jpeg_dec.cpp", "png.hip", "png_dec.cpp", "png_dec.hip",
+SOURCES = ["common.cpp", "weights.cpp", "engine.cpp", "conv_route.cpp", "conv_mfma.hip", "conv_rows.hip", "conv_rows16.hip", "conv_rows16pc.hip", "conv_trunk.hip", "conv_pw.hip", "conv_k3d.hip", "conv_dwpw.hip", "ops_misc.hip", "det_post.hip", "merge.hip", "eval.hip", "coco_eval.hip", "iqa.hip", "jpeg.hip", "jpeg_huff.hip", "jpeg_dec.cpp", "png.hip", "png_dec.cpp", "png_dec.hip", "overlay.hip",
            "sr_ops.hip", "resize.hip", "yolo11.cpp", "rrdb.cpp", "onnx_graph.cpp", "scrfd_ops.hip", "scrfd.cpp", "rtdetr_ops.hip", "rtdetr.cpp", "sliced.cpp", "api.cpp",
            "api_eval.cpp", "api_codec.cpp", "api_ops.cpp"]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-result",

@@ -1,6 +1,8 @@
-// api_codec.cpp — the C-ABI of libffp.so, part three of four (see api.cpp): JPEG and PNG at the file boundaries. They take a device number, not a handle.
+// api_codec.cpp — the C-ABI of libffp.so, part three of four (see api.cpp): JPEG and PNG at the file boundaries, and the overlay drawing between a decode and an
+// encode. They take a device number, not a handle.
 #include "api_util.hpp"
 #include "jpeg.hpp"
+#include "overlay.hpp"
 #include "png.hpp"
 #include "png_dec.hpp"
 
@@ -282,6 +284,37 @@ int ffp_png_unfilter_geometry(int32_t* rows_per_group, int32_t* cols_per_step) {
   png_unfilter_geometry(&r, &c);
   if (rows_per_group) *rows_per_group = r;
   if (cols_per_step) *cols_per_step = c;
+  FFP_API_END
+}
+
+// ---- detection overlays on a frame that stays on the device (overlay.hip) ------------------------------------------------------------
+// Every refusal comes from overlay_check, before the device is chosen: a refused call has touched nothing.
+int ffp_overlay_draw_dev(int device, uint8_t* d_img, int h, int w, int64_t row_stride, const ffp_overlay_prim* prims, int n, const uint8_t* masks,
+                         int64_t mask_bytes) {
+  FFP_API_BEGIN
+  static_assert(sizeof(ffp_overlay_prim) == FFP_OVERLAY_PRIM_BYTES && FFP_OVERLAY_MAX_PRIMS == kOverlayMaxPrims, "include/ffp.h states the struct's size and the cap");
+  FFP_CHECK(d_img, FFP_ERR_ARG, "overlay_draw: the image is null");
+  overlay_check(h, w, row_stride, prims, n, masks, mask_bytes);
+  if (n > 0) {
+    ScopedStream cx(device, "overlay_draw", ScopedStream::Io);
+    overlay_draw_device(d_img, h, w, row_stride, prims, n, masks, mask_bytes, cx.st);
+  }
+  FFP_API_END
+}
+
+int ffp_overlay_draw(int device, uint8_t* img, int h, int w, int64_t row_stride, const ffp_overlay_prim* prims, int n, const uint8_t* masks,
+                     int64_t mask_bytes) {
+  FFP_API_BEGIN
+  FFP_CHECK(img, FFP_ERR_ARG, "overlay_draw: the image is null");
+  overlay_check(h, w, row_stride, prims, n, masks, mask_bytes);
+  if (n > 0) {
+    ScopedStream cx(device, "overlay_draw", ScopedStream::Io);
+    const size_t row = (size_t)w * 3;
+    DevBuf d((size_t)h * row);
+    FFP_HIP(hipMemcpy2D(d.p, row, img, (size_t)row_stride, row, (size_t)h, hipMemcpyHostToDevice));
+    overlay_draw_device(d.as<unsigned char>(), h, w, (long long)row, prims, n, masks, mask_bytes, cx.st);
+    FFP_HIP(hipMemcpy2D(img, (size_t)row_stride, d.p, row, row, (size_t)h, hipMemcpyDeviceToHost));
+  }
   FFP_API_END
 }
 

@@ -363,10 +363,10 @@ int ffp_op_cls_tower(int device, int n, const int32_t* hs, const int32_t* ws, in
   Level L;
   L.build(std::vector<int>(hs, hs + n), std::vector<int>(ws, ws + n), cx.st, px_align);
   DevBuf dx = op_upload(L, F32, x, cin), dhead = op_upload(L, F32, head, head_cs);
-  FFP_HIP(hipMemset(static_cast<char*>(dhead.p) + (size_t)L.total_px * head_cs * 4, 0xFF, 256));      // the slack behind the records: a known pattern too (stray)
+  fill_bytes(static_cast<char*>(dhead.p) + (size_t)L.total_px * head_cs * 4, 0xFF, 256);      // the slack behind the records: a known pattern too (stray)
   DevBuf de1((size_t)L.total_px * C3 * 4 + 256), de2((size_t)L.total_px * C3 * 4 + 256);
-  FFP_HIP(hipMemset(de1.p, 0xFF, de1.n));      // NaN: padding pixels are never written
-  FFP_HIP(hipMemset(de2.p, 0xFF, de2.n));
+  fill_bytes(de1.p, 0xFF, de1.n);      // NaN: padding pixels are never written
+  fill_bytes(de2.p, 0xFF, de2.n);
   // a max-|value| slot per (tensor, image): x's from the data, the others raised by their producers
   std::vector<unsigned> slots(3 * (size_t)n, 0u);
   {
@@ -494,7 +494,7 @@ int ffp_op_conv2d_views(int device, int precision, int n, const int32_t* hs, con
   DevBuf dslots(slots.size() * 4), dgate;
   auto upload_outputs = [&]() {      // padding pixels go up as NaN (op_upload), the slack behind the records as 0xFF bytes
     dout = op_upload(lout, T, y, y_cs);
-    FFP_HIP(hipMemset(static_cast<char*>(dout.p) + ybytes, 0xFF, 256));
+    fill_bytes(static_cast<char*>(dout.p) + ybytes, 0xFF, 256);
     std::copy(amax_out, amax_out + ns, slots.begin() + ns);
     FFP_HIP(hipMemcpy(dslots.p, slots.data(), slots.size() * 4, hipMemcpyHostToDevice));
   };
@@ -1078,13 +1078,13 @@ DevBuf op_upload_frame(const uint8_t* frame, int H, int W) {
   const size_t nb = (size_t)H * W * 3;
   DevBuf b(nb + 256);
   FFP_HIP(hipMemcpy(b.p, frame, nb, hipMemcpyHostToDevice));
-  FFP_HIP(hipMemset(static_cast<char*>(b.p) + nb, 0xFF, 256));
+  fill_bytes(static_cast<char*>(b.p) + nb, 0xFF, 256);
   return b;
 }
 
 DevBuf op_nan_buffer(size_t bytes) {
   DevBuf b(bytes + 256);
-  FFP_HIP(hipMemset(b.p, 0xFF, b.n));
+  fill_bytes(b.p, 0xFF, b.n);
   return b;
 }
 

@@ -23,6 +23,14 @@ template <typename T> DevBuf upload(const T* src, size_t n) {
   if (n) FFP_HIP(hipMemcpy(b.p, src, n * sizeof(T), hipMemcpyHostToDevice));
   return b;
 }
+// A fill that has run when this returns. hipMemset queues the fill on the null stream and returns before it has run, and the streams the entries
+// work on are non-blocking (ScopedStream): nothing orders a kernel on one of them behind such a fill. With other work on the card the 0xFF fill of
+// an output buffer landed on top of what the kernel had written: ffp_op_image_input on one 64 x 64 box returned all NaN in 872 of 4000 calls while
+// another thread kept the card busy, and in none with this wait (tests/test_gpu_image_input.py failed that way once in a while on a shared card).
+inline void fill_bytes(void* p, int value, size_t n) {
+  FFP_HIP(hipMemset(p, value, n));
+  FFP_HIP(hipStreamSynchronize(nullptr));
+}
 inline void check_offsets(const int64_t* off, int n, const char* what) {
   FFP_CHECK(off && off[0] == 0, FFP_ERR_ARG, "%s offsets must start at 0", what);
   for (int i = 0; i < n; ++i) FFP_CHECK(off[i + 1] >= off[i], FFP_ERR_ARG, "%s offsets must not decrease (image %d)", what, i);

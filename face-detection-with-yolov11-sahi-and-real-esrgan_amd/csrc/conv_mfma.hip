@@ -1038,6 +1038,7 @@ static const void* conv_device_zeros() {
   FFP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_kernel<X3, 3, 2, 4, 1, 1, 1, 16, true>), hipFuncAttributeMaxDynamicSharedMemorySize, StemGn::LDS));
   DevBuf b(256);
   FFP_HIP(hipMemset(b.p, 0, 256));
+  FFP_HIP(hipStreamSynchronize(nullptr));      // the fill is queued on the null stream, which the engines' non-blocking streams do not wait for
   return zeros.emplace(dev, std::move(b)).first->second.p;      // last: a device whose set-up threw has no record and is set up again
 }
 

@@ -448,6 +448,43 @@ int ffp_png_decode_dev(int device, const uint8_t* data, int64_t n, int bgr, int 
 int ffp_png_decode_stats(int64_t* parallel_decodes, int64_t* serial_decodes);
 int ffp_png_unfilter_geometry(int32_t* rows_per_group, int32_t* cols_per_step);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Detection overlays drawn on the device (between ffp_jpeg_decode_dev / ffp_png_decode_dev and ffp_jpeg_encode_dev / ffp_png_encode_dev)
+ * ------------------------------------------------------------------------------------------------------- */
+
+/* Replaces the drawing of draw_detections / draw_detections_on_image (/root/reference/utils/visualization.py:78-183: cv2.rectangle,
+ * cv2.putText, and draw_keypoints_and_skeleton's cv2.line / cv2.circle, :37-76) on a frame that stays in device memory: an ORDERED list of
+ * primitives is painted in place, in list order (painter's order: where two overlap, the later one wins), into an h x w x 3 uint8 image
+ * with a row pitch in bytes; the image's base may have any byte alignment (a view inside a larger buffer). Two kinds:
+ *   FFP_OVERLAY_RECT   inclusive corners (x0, y0)..(x1, y1), partly or wholly outside the image if they like; width 0 fills it, width >= 1
+ *                      paints the pixels within `width` of an edge (a frame; a rectangle under 2*width wide or high is therefore filled).
+ *   FFP_OVERLAY_STAMP  an x1 x y1 (width x height) 8-bit mask laid with its top-left corner at (x0, y0): mask pixel (i, j) is byte
+ *                      mask_off + j*width + i of the mask pool (`width` holds the mask's row pitch), and every covered pixel and channel becomes
+ *                      t = dst*(255 - m) + c*m + 128; dst = ((t >> 8) + t) >> 8  — Pillow's blend: m == 0 keeps dst, m == 255 gives c.
+ * color: three bytes in the image's channel order. The result is a function of the image and the list alone. Bytes between w*3 and the
+ * row pitch are never written, and a tile no primitive touches is neither read nor written.
+ * Everything is checked before anything is launched, and a refused call (FFP_ERR_ARG) leaves the image untouched: a null list or image,
+ * n < 0 or n > FFP_OVERLAY_MAX_PRIMS, row_stride < w*3, an unknown kind, a negative frame width, a stamp with a negative size or offset or a
+ * pitch below its width, a stamp whose mask does not lie inside mask_bytes (at most 2^31 - 1). n == 0: FFP_OK, nothing is launched.
+ * The list and the pool go up through a pooled workspace, so calls on different threads run side by side.
+ * ffp_overlay_draw: the same on a host image (its w*3 bytes of every row go up, are drawn on and come down), for tests and small callers. */
+#define FFP_OVERLAY_RECT 0
+#define FFP_OVERLAY_STAMP 1
+#define FFP_OVERLAY_MAX_PRIMS 1048576
+#define FFP_OVERLAY_PRIM_BYTES 32
+typedef struct ffp_overlay_prim {
+  int32_t kind;     /* FFP_OVERLAY_RECT / FFP_OVERLAY_STAMP */
+  int32_t x0, y0;   /* RECT: first corner. STAMP: where the mask's top-left corner lies (may be negative) */
+  int32_t x1, y1;   /* RECT: last corner, inclusive. STAMP: the mask's width and height */
+  int32_t width;    /* RECT: 0 fill, >= 1 frame width. STAMP: the mask's row pitch in bytes */
+  int32_t mask_off; /* STAMP: offset of the mask's first byte in the pool */
+  uint8_t color[4]; /* [0..2] in the image's channel order; [3] is not read */
+} ffp_overlay_prim; /* sizeof == FFP_OVERLAY_PRIM_BYTES */
+int ffp_overlay_draw_dev(int device, uint8_t* d_img, int h, int w, int64_t row_stride, const ffp_overlay_prim* prims, int n, const uint8_t* masks,
+                         int64_t mask_bytes);
+int ffp_overlay_draw(int device, uint8_t* img, int h, int w, int64_t row_stride, const ffp_overlay_prim* prims, int n, const uint8_t* masks,
+                     int64_t mask_bytes);
+
 /* 1x1 conv over the virtual concat [nearest_x2(coarse) | fine] (the YOLO neck's Upsample + Concat + C3k2.cv1 without
  * materialising the upsampled tensor: /root/reference's model graph via ultralytics' yolo11-pose.yaml layers 11-13 and 14-16).
  * coarse: [n][h/2][w/2][c_up] (c_up a multiple of 64), fine: [n][h][w][c_fine]; wt: [cout][c_up + c_fine] (input channel
