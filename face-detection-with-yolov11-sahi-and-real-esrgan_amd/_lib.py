@@ -196,6 +196,14 @@ _SIGS = {
                               _p(C.c_float), C.c_int, C.c_int, C.c_int, _p(C.c_float)]),
     "ffp_op_stem_conv": (C.c_int, [C.c_int, _p(C.c_uint8), C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_int32), C.c_int, _p(C.c_float), _p(C.c_float),
                                    C.c_int, _p(C.c_float), _p(C.c_float), _p(C.c_float)]),
+    "ffp_op_sr_tiles": (C.c_int, [C.c_int, _p(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_int32), _p(C.c_int32),
+                                  _p(C.c_int32), _p(C.c_int32)]),
+    "ffp_op_sr_pre": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, _p(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                _p(C.c_int64), C.c_void_p, C.c_size_t, _p(C.c_int64)]),
+    "ffp_op_sr_post": (C.c_int, [C.c_int, C.c_int, _p(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                 _p(C.c_int64), C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
+    "ffp_op_alpha_linear": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "ffp_op_crop_gather": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, _p(C.c_int32), _p(C.c_int64), C.c_void_p, C.c_size_t]),
     "ffp_scrfd_create": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, _p(C.c_void_p)]),
     "ffp_scrfd_destroy": (None, [C.c_void_p]),
     "ffp_scrfd_describe": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
@@ -1898,6 +1906,94 @@ def op_resize_lanczos4(img: np.ndarray, out_h: int, out_w: int, device: int = 0)
     _check(lib().ffp_op_resize_lanczos4(device, a.ctypes.data, h, w, 1 if a.ndim == 2 else a.shape[2], 8 * a.itemsize, int(out_h), int(out_w),
                                         out.ctypes.data))
     return out
+
+
+SR_SEL_BGR, SR_SEL_GRAY, SR_SEL_ALPHA = 0, 1, 2      # channel selection of an image of the ffp_op_sr_* entries
+
+
+def _sr_images(images) -> np.ndarray:
+    """Images of the ffp_op_sr_* entries: rows (byte offset, bytes per row, h, w, channels, bits, range, selection) as int64."""
+    a = np.ascontiguousarray(np.asarray(images, np.int64).reshape(-1, 8))
+    return a
+
+
+def _i64p(a: np.ndarray):
+    return a.ctypes.data_as(_p(C.c_int64))
+
+
+def op_sr_tiles(images, scale: int, tile: int = 0, tile_pad: int = 10, pre_pad: int = 0, precision: int = PREC_F32):
+    """The padded tiles the enhancer cuts a batch into (ffp_op_sr_tiles, no device): ([(h, w), ...] in tile order, 16x16 body tiles,
+    channels of the network's input record in `precision`)."""
+    im = _sr_images(images)
+    cap = 1 << 16
+    hw = np.zeros((cap, 2), np.int32)
+    n, t16, ch = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    _check(lib().ffp_op_sr_tiles(im.shape[0], _i64p(im), scale, tile, tile_pad, pre_pad, precision, cap, _ip(hw), C.byref(n), C.byref(t16), C.byref(ch)))
+    return [(int(h), int(w)) for h, w in hw[:n.value]], t16.value, ch.value
+
+
+def op_sr_pre(buf: np.ndarray, images, scale: int, tile: int = 0, tile_pad: int = 10, pre_pad: int = 0, precision: int = PREC_F32, fill=None,
+              cap_t16: int = 0, first=None, device: int = 0):
+    """The enhancer's input kernel alone (ffp_op_sr_pre) on the images described inside the uint8 buffer `buf`: (per-tile arrays
+    (h/f, w/f, channels) float32, the level's whole flat buffer (records, channels), first record of every tile). fill: the flat buffer's
+    contents going in (scalar or array); cap_t16 > 0: a capacity-mode level, with `first` (images of an earlier batch) run before."""
+    b = np.ascontiguousarray(buf, np.uint8).reshape(-1)
+    im = _sr_images(images)
+    tiles, _, ch = op_sr_tiles(im, scale, tile, tile_pad, pre_pad, precision)
+    f = 2 if scale == 2 else 1
+    sizes = [(h // f, w // f) for h, w in tiles]
+    npx = 256 * cap_t16 if cap_t16 > 0 else sum(h * w for h, w in sizes)
+    flat = np.empty((npx, ch), np.float32)
+    flat[...] = 0.0 if fill is None else fill
+    offs = np.zeros(max(len(tiles), 1), np.int64)
+    im1 = _sr_images(first) if first is not None else np.zeros((0, 8), np.int64)
+    _check(lib().ffp_op_sr_pre(device, precision, b.ctypes.data, b.size, im.shape[0], _i64p(im), scale, tile, tile_pad, pre_pad, cap_t16, im1.shape[0],
+                               _i64p(im1) if im1.shape[0] else None, flat.ctypes.data, npx, _i64p(offs)))
+    out = [flat[o:o + h * w].reshape(h, w, ch).copy() for o, (h, w) in zip(offs.tolist(), sizes)]
+    return out, flat, offs[:len(tiles)].copy()
+
+
+def _sr_net_records(nets, cs: int) -> np.ndarray:
+    return np.ascontiguousarray(np.concatenate([np.asarray(t, np.float32).reshape(-1, cs) for t in nets], axis=0))
+
+
+def op_sr_post(canvas: np.ndarray, images, nets, scale: int, tile: int = 0, tile_pad: int = 10, pre_pad: int = 0, cap_t16: int = 0, first=None,
+               only_tile: int = -1, device: int = 0) -> np.ndarray:
+    """The enhancer's output kernel alone (ffp_op_sr_post): `canvas` (uint8 bytes, returned as a new array) holds the canvases `images`
+    describe (h, w: the input size); nets: every tile's network output (scale * h, scale * w, cs >= 3) float32 in tile order. cap_t16 > 0:
+    capacity-mode level and tables; first = (images, nets) of an earlier batch run before; only_tile >= 0: every other tile's core is emptied."""
+    out = np.ascontiguousarray(canvas, np.uint8).reshape(-1).copy()
+    im = _sr_images(images)
+    cs = int(np.asarray(nets[0]).shape[-1])
+    net = _sr_net_records(nets, cs)
+    im1, net1 = (np.zeros((0, 8), np.int64), None) if first is None else (_sr_images(first[0]), _sr_net_records(first[1], cs))
+    _check(lib().ffp_op_sr_post(device, im.shape[0], _i64p(im), scale, tile, tile_pad, pre_pad, net.ctypes.data, cs, cap_t16, im1.shape[0],
+                                _i64p(im1) if im1.shape[0] else None, net1.ctypes.data if net1 is not None else None, int(only_tile), out.ctypes.data, out.size))
+    return out
+
+
+def op_alpha_linear(src: np.ndarray, dst: np.ndarray, max_range: int, device: int = 0) -> np.ndarray:
+    """The 'cv2' alpha upsampler alone (ffp_op_alpha_linear): src HxWx4 uint8 / uint16, dst (out_h, out_w, 4) uint8 / uint16 going in;
+    returns dst with channel 3 = rint(resize_linear(src[..., 3] / max_range) * max_range)."""
+    s, d = np.ascontiguousarray(src), np.ascontiguousarray(dst).copy()
+    if s.dtype not in (np.uint8, np.uint16) or d.dtype not in (np.uint8, np.uint16) or s.ndim != 3 or d.ndim != 3 or s.shape[2] != 4 or d.shape[2] != 4:
+        raise ValueError("expected HxWx4 uint8 / uint16 arrays")
+    _check(lib().ffp_op_alpha_linear(device, s.ctypes.data, s.shape[0], s.shape[1], 8 * s.itemsize, int(max_range), d.shape[0], d.shape[1],
+                                     8 * d.itemsize, d.ctypes.data))
+    return d
+
+
+def op_crop_gather(frame: np.ndarray, boxes_xywh, offs, out: np.ndarray, device: int = 0) -> np.ndarray:
+    """The crop gather alone (ffp_op_crop_gather): box i (x0, y0, w, h) of an HxWx3 uint8 frame -> w * h * 3 bytes at offs[i] of a copy of `out`."""
+    f = _as_frame(frame)
+    b = np.ascontiguousarray(np.asarray(boxes_xywh, np.int32).reshape(-1, 4))
+    o = np.ascontiguousarray(np.asarray(offs, np.int64).reshape(-1))
+    if o.size != b.shape[0]:
+        raise ValueError("one offset per box")
+    res = np.ascontiguousarray(out, np.uint8).reshape(-1).copy()
+    _check(lib().ffp_op_crop_gather(device, f.ctypes.data, f.shape[0], f.shape[1], b.shape[0], _ip(b) if b.shape[0] else None,
+                                    _i64p(o) if o.size else None, res.ctypes.data, res.size))
+    return res
 
 
 def op_conv2d_shape(shape: int = -1) -> None:

@@ -192,6 +192,12 @@ def build_jpeg_batch_plan_check(verbose: bool = True) -> str:
     return _build_host_check("jpeg_batch_plan_host_check", "jpeg_batch_plan_host_check.cpp", ["jpeg_batch_plan.hpp"], verbose)
 
 
+def build_sr_tiles_check(verbose: bool = True) -> str:
+    """The tile geometry of the Real-ESRGAN path (csrc/sr_tiles.hpp, no HIP in it): a dense grid and seeded random batches; sources in bounds, cores a
+    partition of the canvas, every refusal a stated one."""
+    return _build_host_check("sr_tiles_host_check", "sr_tiles_host_check.cpp", ["sr_tiles.hpp"], verbose)
+
+
 def build_ws_pool_check(verbose: bool = True) -> tuple:
     """The codecs' workspace pool (csrc/ws_pool.hpp, no HIP in it): seeded acquire / resize / release sequences against a shadow model and a threaded
     phase, one driver built twice: under AddressSanitizer + UBSan and under ThreadSanitizer."""
@@ -213,6 +219,8 @@ if __name__ == "__main__":
         build_switches_check()
     elif "--jpeg-batch-plan-check" in sys.argv:
         build_jpeg_batch_plan_check()
+    elif "--sr-tiles-check" in sys.argv:
+        build_sr_tiles_check()
     elif "--ws-pool-check" in sys.argv:
         build_ws_pool_check()
     elif "--variant" in sys.argv:

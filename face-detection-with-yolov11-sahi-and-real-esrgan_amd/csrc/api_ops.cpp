@@ -1303,3 +1303,247 @@ int ffp_op_resize_lanczos4(int device, const void* src, int h, int w, int channe
 }
 
 }  // extern "C"
+
+// ---- single-operator entry points of the Real-ESRGAN pre/post kernels (tests/test_gpu_sr_ops.py) --------------------------------------
+// An image is eight int64: byte offset and row stride inside the caller's buffer, h, w (the INPUT size: a canvas is scale times as large), channels,
+// bits, range, selection. The tiles and the descriptor tables come from the functions the engine calls (sr_tiles.hpp), the levels from Level::build
+// or — capacity mode — Level::reserve / assign with the capacities SrEngine::build_plan gives them. No weights, no plan.
+namespace {
+
+constexpr int kSrImgFields = 8;
+
+SrFmt op_sr_fmt(const char* what, int i, const int64_t* d) {
+  const int64_t cn = d[4], bits = d[5], range = d[6], sel = d[7];
+  FFP_CHECK(cn == 1 || cn == 3 || cn == 4, FFP_ERR_ARG, "%s: image %d has %lld channels (1, 3 or 4)", what, i, (long long)cn);
+  FFP_CHECK(bits == 8 || bits == 16, FFP_ERR_ARG, "%s: image %d has %lld bits (8 or 16)", what, i, (long long)bits);
+  FFP_CHECK(range == 255 || (range == 65535 && bits == 16), FFP_ERR_ARG, "%s: image %d has range %lld in %lld-bit storage", what, i, (long long)range, (long long)bits);
+  FFP_CHECK((sel == SR_SEL_BGR && cn >= 3) || sel == SR_SEL_GRAY || (sel == SR_SEL_ALPHA && cn == 4), FFP_ERR_ARG, "%s: image %d selects %lld of %lld channels", what, i,
+            (long long)sel, (long long)cn);
+  SrFmt f;
+  f.cn = (int)cn; f.wide = bits == 16; f.range = (float)range; f.sel = (int)sel;
+  return f;
+}
+
+// the images of one batch; canvas = false: the descriptions are sources of sr_pre, true: canvases of sr_post. Every byte a kernel may touch lies in [0, bytes).
+std::vector<SrImage> op_sr_images(const char* what, int n, const int64_t* imgs, int scale, bool canvas, size_t bytes) {
+  FFP_CHECK(imgs && n >= 1 && n <= 256, FFP_ERR_ARG, "%s: %d images", what, n);
+  std::vector<SrImage> v(n);
+  for (int i = 0; i < n; ++i) {
+    const int64_t* d = imgs + (size_t)i * kSrImgFields;
+    const SrFmt f = op_sr_fmt(what, i, d);
+    const int64_t off = d[0], stride = d[1], h = d[2], w = d[3];
+    FFP_CHECK(h >= 1 && w >= 1 && h <= 4096 && w <= 4096, FFP_ERR_ARG, "%s: image %d is %lldx%lld", what, i, (long long)w, (long long)h);
+    const int64_t k = canvas ? scale : 1, row = w * k * f.px_bytes(), es = 1 << f.wide;
+    FFP_CHECK(off >= 0 && stride >= row && stride <= (1 << 24) && off % es == 0 && stride % es == 0, FFP_ERR_ARG, "%s: image %d at offset %lld with rows of %lld bytes (%lld used)",
+              what, i, (long long)off, (long long)stride, (long long)row);
+    FFP_CHECK((uint64_t)(off + (h * k - 1) * stride + row) <= bytes, FFP_ERR_ARG, "%s: image %d ends behind the buffer of %zu bytes", what, i, bytes);
+    SrImage& im = v[i];
+    im = SrImage{};
+    im.h = (int)h; im.w = (int)w;
+    if (canvas) { im.out_off = off; im.out_stride = (int)stride; im.out_fmt = f; }
+    else { im.in_off = off; im.in_stride = (int)stride; im.in_fmt = f; }
+  }
+  return v;
+}
+
+void op_sr_scale(const char* what, int scale) { FFP_CHECK(scale == 4 || scale == 2, FFP_ERR_ARG, "%s: scale %d (no kernel: 4 or 2)", what, scale); }
+
+// the network's input record of a (precision, scale) pair: conv_first's padded input channels, as SrEngine::build_plan takes them from the packed conv
+int op_sr_in_channels(DType T, int scale) { return conv_cin_aligned(3 * sr_shuffle(scale) * sr_shuffle(scale), T); }
+
+// One level the way the engine has it: exact (cap_t16 == 0) or reserved for cap_t16 body tiles of 16x16, `up` = 1 (body) or 4 (the x4 level).
+struct OpSrLevel {
+  Level L;
+  int cap_t16;
+  OpSrLevel(int cap, int up) : cap_t16(cap) {
+    if (cap > 0) L.reserve(cap, 256ll * up * up * cap, up * up * cap, nullptr);
+  }
+  void set(const std::vector<int>& hs, const std::vector<int>& ws, hipStream_t st) {
+    if (cap_t16 > 0) L.assign(hs, ws, st);
+    else L.build(hs, ws, st);
+  }
+};
+
+// a level's whole flat buffer, padding and unused capacity included, as `count` fp32 values on the host
+DevBuf op_upload_records(DType T, const float* src, size_t count) {
+  DevBuf b(count * dsize(T) + 256);
+  if (T == F32) {
+    FFP_HIP(hipMemcpy(b.p, src, count * 4, hipMemcpyHostToDevice));
+  } else {
+    std::vector<_Float16> h(count);
+    for (size_t i = 0; i < count; ++i) h[i] = (_Float16)src[i];
+    FFP_HIP(hipMemcpy(b.p, h.data(), count * 2, hipMemcpyHostToDevice));
+  }
+  return b;
+}
+void op_download_records(DType T, const DevBuf& b, size_t count, float* dst) {
+  if (T == F32) {
+    FFP_HIP(hipMemcpy(dst, b.p, count * 4, hipMemcpyDeviceToHost));
+  } else {
+    std::vector<_Float16> h(count);
+    FFP_HIP(hipMemcpy(h.data(), b.p, count * 2, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < count; ++i) dst[i] = (float)h[i];
+  }
+}
+
+void op_sr_check_cap(const char* what, int cap_t16, const SrLevelSizes& z) {
+  FFP_CHECK(cap_t16 >= 0 && cap_t16 <= 4096, FFP_ERR_ARG, "%s: capacity %d", what, cap_t16);
+  FFP_CHECK(cap_t16 == 0 || z.t16 <= cap_t16, FFP_ERR_ARG, "%s: batch of %lld 16x16 tiles exceeds the capacity of %d", what, z.t16, cap_t16);
+}
+
+}  // namespace
+
+extern "C" {
+
+int ffp_op_sr_tiles(int n, const int64_t* imgs, int scale, int tile, int tile_pad, int pre_pad, int precision, int cap_tiles, int32_t* out_hw,
+                    int32_t* out_n, int32_t* out_t16, int32_t* out_channels) {
+  FFP_API_BEGIN
+  FFP_CHECK(imgs && out_hw && out_n && out_t16 && out_channels && cap_tiles >= 0, FFP_ERR_ARG, "sr_tiles: null argument");
+  op_sr_scale("sr_tiles", scale);
+  const DType T = op_dtype("sr_tiles", precision);
+  const std::vector<SrImage> v = op_sr_images("sr_tiles", n, imgs, 1, false, SIZE_MAX);
+  const std::vector<SrTile> tiles = sr_tiles_checked(v, scale, tile, tile_pad, pre_pad);
+  FFP_CHECK((int)tiles.size() <= cap_tiles, FFP_ERR_ARG, "sr_tiles: %d tiles, room for %d", (int)tiles.size(), cap_tiles);
+  for (size_t i = 0; i < tiles.size(); ++i) { out_hw[2 * i] = tiles[i].h; out_hw[2 * i + 1] = tiles[i].w; }
+  *out_n = (int32_t)tiles.size();
+  *out_t16 = (int32_t)sr_level_sizes(tiles, scale).t16;
+  *out_channels = op_sr_in_channels(T, scale);
+  FFP_API_END
+}
+
+int ffp_op_sr_pre(int device, int precision, const uint8_t* src, size_t src_bytes, int n, const int64_t* imgs, int scale, int tile, int tile_pad,
+                  int pre_pad, int cap_t16, int n_first, const int64_t* imgs_first, float* flat, size_t flat_px, int64_t* out_off) {
+  FFP_API_BEGIN
+  FFP_CHECK(src && flat && out_off && src_bytes > 0, FFP_ERR_ARG, "sr_pre: null argument");
+  FFP_CHECK(n_first == 0 || (n_first > 0 && imgs_first && cap_t16 > 0), FFP_ERR_ARG, "sr_pre: an earlier batch needs a capacity-mode level");
+  op_sr_scale("sr_pre", scale);
+  const DType T = op_dtype("sr_pre", precision);
+  const int C = op_sr_in_channels(T, scale), shuf = sr_shuffle(scale);
+  std::vector<std::vector<SrTile>> batches;
+  if (n_first > 0) batches.push_back(sr_tiles_checked(op_sr_images("sr_pre", n_first, imgs_first, scale, false, src_bytes), scale, tile, tile_pad, pre_pad));
+  batches.push_back(sr_tiles_checked(op_sr_images("sr_pre", n, imgs, scale, false, src_bytes), scale, tile, tile_pad, pre_pad));
+  std::vector<SrLevelSizes> sizes;
+  for (const auto& b : batches) {
+    sizes.push_back(sr_level_sizes(b, scale));
+    op_sr_check_cap("sr_pre", cap_t16, sizes.back());
+  }
+  long long px = 0;
+  for (size_t i = 0; i < batches.back().size(); ++i) px += (long long)sizes.back().hs[i] * sizes.back().ws[i];
+  const long long want_px = cap_t16 > 0 ? 256ll * cap_t16 : px;
+  FFP_CHECK((long long)flat_px == want_px, FFP_ERR_ARG, "sr_pre: the level holds %lld pixel records, the buffer %zu", want_px, flat_px);
+  ScopedStream cx(device, "sr_pre");
+  OpSrLevel lb(cap_t16, 1);
+  // the caller's contents go up once, every record of the level: a later batch runs over what the earlier one left
+  DevBuf d_src = upload(src, src_bytes), d_flat = op_upload_records(T, flat, flat_px * C), d_srcs;
+  for (size_t b = 0; b < batches.size(); ++b) {
+    const std::vector<SrTile>& tiles = batches[b];
+    const int nt = (int)tiles.size(), cap = cap_t16 > 0 ? cap_t16 : nt;
+    FFP_HIP(hipStreamSynchronize(cx.st));      // the earlier batch has read its tables
+    lb.set(sizes[b].hs, sizes[b].ws, cx.st);
+    std::vector<SrSrc> srcs(nt);
+    std::vector<SrDst> dsts(cap);
+    std::vector<long long> coff((size_t)cap + 1);
+    sr_fill_descriptors(tiles, cap, srcs.data(), dsts.data(), coff.data());
+    d_srcs = upload(srcs.data(), srcs.size());
+    const TView vout{d_flat.p, T, C, 0, C, &lb.L};
+    launch_sr_pre(d_src.as<uint8_t>(), d_srcs.as<SrSrc>(), vout, shuf, cx.st);
+  }
+  FFP_HIP(hipStreamSynchronize(cx.st));
+  op_download_records(T, d_flat, flat_px * C, flat);
+  for (size_t i = 0; i < batches.back().size(); ++i) out_off[i] = lb.L.off[i];
+  FFP_API_END
+}
+
+int ffp_op_sr_post(int device, int n, const int64_t* imgs, int scale, int tile, int tile_pad, int pre_pad, const float* net, int cs, int cap_t16,
+                   int n_first, const int64_t* imgs_first, const float* net_first, int only_tile, uint8_t* canvas, size_t canvas_bytes) {
+  FFP_API_BEGIN
+  FFP_CHECK(net && canvas && canvas_bytes > 0, FFP_ERR_ARG, "sr_post: null argument");
+  FFP_CHECK(cs >= 3 && cs <= 64, FFP_ERR_ARG, "sr_post: network output records of %d channels", cs);
+  FFP_CHECK(n_first == 0 || (n_first > 0 && imgs_first && net_first && cap_t16 > 0), FFP_ERR_ARG, "sr_post: an earlier batch needs a capacity-mode level");
+  op_sr_scale("sr_post", scale);
+  std::vector<std::vector<SrTile>> batches;
+  std::vector<const float*> nets;
+  if (n_first > 0) {
+    batches.push_back(sr_tiles_checked(op_sr_images("sr_post", n_first, imgs_first, scale, true, canvas_bytes), scale, tile, tile_pad, pre_pad));
+    nets.push_back(net_first);
+  }
+  batches.push_back(sr_tiles_checked(op_sr_images("sr_post", n, imgs, scale, true, canvas_bytes), scale, tile, tile_pad, pre_pad));
+  nets.push_back(net);
+  std::vector<SrLevelSizes> sizes;
+  for (const auto& b : batches) {
+    sizes.push_back(sr_level_sizes(b, scale));
+    op_sr_check_cap("sr_post", cap_t16, sizes.back());
+  }
+  FFP_CHECK(only_tile >= -1 && only_tile < (int)batches.back().size(), FFP_ERR_ARG, "sr_post: tile %d of %d", only_tile, (int)batches.back().size());
+  ScopedStream cx(device, "sr_post");
+  OpSrLevel l2(cap_t16, 4);
+  DevBuf d_canvas = upload(canvas, canvas_bytes), d_net, d_dsts, d_coff;
+  for (size_t b = 0; b < batches.size(); ++b) {
+    const std::vector<SrTile>& tiles = batches[b];
+    const int nt = (int)tiles.size(), cap = cap_t16 > 0 ? cap_t16 : nt;
+    FFP_HIP(hipStreamSynchronize(cx.st));      // the earlier batch has read its tables and its network output
+    l2.set(sizes[b].h2, sizes[b].w2, cx.st);
+    d_net = op_upload(l2.L, F32, nets[b], cs);      // NaN behind the batch's last pixel
+    std::vector<SrSrc> srcs(nt);
+    std::vector<SrDst> dsts(cap);
+    std::vector<long long> coff((size_t)cap + 1);
+    sr_fill_descriptors(tiles, cap, srcs.data(), dsts.data(), coff.data());
+    if (only_tile >= 0 && b + 1 == batches.size()) {      // every other core emptied: what this tile writes is not covered by its neighbours
+      long long tot = 0;
+      for (int i = 0; i < cap; ++i) {
+        if (i != only_tile) dsts[i].cw = dsts[i].ch = 0;
+        coff[i] = tot;
+        tot += (long long)dsts[i].cw * dsts[i].ch;
+      }
+      coff[cap] = tot;
+    }
+    d_dsts = upload(dsts.data(), dsts.size());
+    d_coff = upload(coff.data(), coff.size());
+    const TView vnet{d_net.p, F32, cs, 0, cs, &l2.L};
+    launch_sr_post(vnet, d_dsts.as<SrDst>(), d_coff.as<long long>(), l2.L.total_px, d_canvas.as<uint8_t>(), cx.st);      // as SrEngine::enhance_dev launches it
+  }
+  FFP_HIP(hipStreamSynchronize(cx.st));
+  FFP_HIP(hipMemcpy(canvas, d_canvas.p, canvas_bytes, hipMemcpyDeviceToHost));
+  FFP_API_END
+}
+
+int ffp_op_alpha_linear(int device, const void* src, int h, int w, int src_bits, int range, int out_h, int out_w, int dst_bits, void* dst) {
+  FFP_API_BEGIN
+  FFP_CHECK(src && dst, FFP_ERR_ARG, "alpha_linear: null argument");
+  FFP_CHECK(h >= 1 && w >= 1 && out_h >= 1 && out_w >= 1 && h <= 8192 && w <= 8192 && out_h <= 8192 && out_w <= 8192, FFP_ERR_ARG,
+            "alpha_linear: %dx%d -> %dx%d", h, w, out_h, out_w);
+  FFP_CHECK((src_bits == 8 || src_bits == 16) && (dst_bits == 8 || dst_bits == 16), FFP_ERR_ARG, "alpha_linear: bits %d -> %d (8 or 16)", src_bits, dst_bits);
+  FFP_CHECK(src_bits == 16 || dst_bits == 8, FFP_ERR_ARG, "alpha_linear: 8-bit input with a 16-bit canvas");
+  FFP_CHECK(range == 255 || (range == 65535 && src_bits == 16 && dst_bits == 16), FFP_ERR_ARG, "alpha_linear: range %d in %d-bit -> %d-bit storage", range, src_bits, dst_bits);
+  const size_t in_bytes = ((size_t)h * w * 4) << (src_bits == 16), out_bytes = ((size_t)out_h * out_w * 4) << (dst_bits == 16);
+  ScopedStream cx(device, "alpha_linear");
+  DevBuf d_src = upload(static_cast<const uint8_t*>(src), in_bytes), d_dst = upload(static_cast<const uint8_t*>(dst), out_bytes);
+  launch_alpha_linear(d_src.p, h, w, src_bits == 16, (float)range, out_h, out_w, d_dst.p, dst_bits == 16, cx.st);
+  FFP_HIP(hipStreamSynchronize(cx.st));
+  FFP_HIP(hipMemcpy(dst, d_dst.p, out_bytes, hipMemcpyDeviceToHost));
+  FFP_API_END
+}
+
+int ffp_op_crop_gather(int device, const uint8_t* frame, int H, int W, int n, const int32_t* boxes_xywh, const int64_t* offs, uint8_t* out,
+                       size_t out_bytes) {
+  FFP_API_BEGIN
+  FFP_CHECK(frame && out && out_bytes > 0 && (n == 0 || (boxes_xywh && offs)), FFP_ERR_ARG, "crop_gather: null argument");
+  FFP_CHECK(H >= 1 && W >= 1 && H <= 16384 && W <= 16384 && n >= 0 && n <= 4096, FFP_ERR_ARG, "crop_gather: %d boxes of a %d x %d frame", n, W, H);
+  std::vector<int4> hb(n);
+  std::vector<long long> ho(n);
+  for (int i = 0; i < n; ++i) {
+    const int x0 = boxes_xywh[4 * i], y0 = boxes_xywh[4 * i + 1], w = boxes_xywh[4 * i + 2], h = boxes_xywh[4 * i + 3];
+    FFP_CHECK(x0 >= 0 && y0 >= 0 && w >= 1 && h >= 1 && w <= W - x0 && h <= H - y0, FFP_ERR_ARG, "crop_gather: box %d (%d, %d, %dx%d) leaves the frame", i, x0, y0, w, h);
+    FFP_CHECK(offs[i] >= 0 && (uint64_t)offs[i] + (uint64_t)w * h * 3 <= out_bytes, FFP_ERR_ARG, "crop_gather: box %d ends behind the output of %zu bytes", i, out_bytes);
+    hb[i] = make_int4(x0, y0, w, h);
+    ho[i] = offs[i];
+  }
+  ScopedStream cx(device, "crop_gather");
+  DevBuf d_frame = op_upload_frame(frame, H, W), d_out = upload(out, out_bytes), d_boxes = upload(hb.data(), hb.size()), d_offs = upload(ho.data(), ho.size());
+  launch_crop_gather(d_frame.as<uint8_t>(), W, d_boxes.as<int4>(), d_offs.as<long long>(), n, d_out.as<uint8_t>(), cx.st);
+  FFP_HIP(hipStreamSynchronize(cx.st));
+  FFP_HIP(hipMemcpy(out, d_out.p, out_bytes, hipMemcpyDeviceToHost));
+  FFP_API_END
+}
+
+}  // extern "C"

@@ -184,69 +184,39 @@ void SrEngine::wait_done() {
   }
 }
 
+std::vector<SrTile> sr_tiles_checked(const std::vector<SrImage>& imgs, int scale, int tile, int tile_pad, int pre_pad) {
+  std::vector<SrTile> tiles;
+  switch (sr_tiles(imgs, scale, tile, tile_pad, pre_pad, tiles)) {
+    case SR_TILES_OK: break;
+    case SR_TILES_EMPTY_BATCH: fail(FFP_ERR_ARG, "enhance: empty batch");
+    case SR_TILES_NEGATIVE_PAD: fail(FFP_ERR_ARG, "enhance: negative padding");
+    case SR_TILES_EMPTY_IMAGE: fail(FFP_ERR_ARG, "enhance: empty image");
+    case SR_TILES_PRE_PAD: fail(FFP_ERR_ARG, "enhance: pre_pad %d >= image size (reflect padding undefined)", pre_pad);
+    case SR_TILES_TOO_SMALL: fail(FFP_ERR_ARG, "enhance: image too small for reflect padding");
+    case SR_TILES_ODD_X2: fail(FFP_ERR_ARG, "enhance: x2 model needs even tile geometry (tile %d, pad %d)", tile, tile_pad);
+  }
+  return tiles;
+}
+
 void SrEngine::enhance_dev(const uint8_t* d_in, uint8_t* d_out, const std::vector<SrImage>& imgs, int tile, int tile_pad, int pre_pad, bool wait) {
   FFP_HIP(hipSetDevice(device_));
   if (pending_) wait_done();
-  FFP_CHECK(!imgs.empty(), FFP_ERR_ARG, "enhance: empty batch");
-  FFP_CHECK(tile_pad >= 0 && pre_pad >= 0, FFP_ERR_ARG, "enhance: negative padding");
-  const int s = scale_;
-  const int shuf = s == 2 ? 2 : 1;
-  std::vector<TileDesc> tiles;
-  for (const SrImage& im : imgs) {
-    FFP_CHECK(im.h >= 1 && im.w >= 1, FFP_ERR_ARG, "enhance: empty image");
-    // pre_pad (reflect, bottom/right), then mod pad to a multiple of 2 for the x2 model (RealESRGANer.pre_process)
-    FFP_CHECK(pre_pad < im.h && pre_pad < im.w, FFP_ERR_ARG, "enhance: pre_pad %d >= image size (reflect padding undefined)", pre_pad);
-    int H = im.h + pre_pad, W = im.w + pre_pad;
-    int mph = 0, mpw = 0;
-    if (s == 2) { if (H % 2) mph = 2 - H % 2; if (W % 2) mpw = 2 - W % 2; }
-    FFP_CHECK((mph == 0 || H >= 2) && (mpw == 0 || W >= 2), FFP_ERR_ARG, "enhance: image too small for reflect padding");
-    H += mph; W += mpw;
-    const int out_h = im.h * s, out_w = im.w * s;     // pads are cropped off again (post_process)
-    int tsz = tile > 0 ? tile : std::max(H, W);
-    const int txn = (W + tsz - 1) / tsz, tyn = (H + tsz - 1) / tsz;
-    for (int ty = 0; ty < tyn; ++ty)
-      for (int tx = 0; tx < txn; ++tx) {
-        const int sx = tx * tsz, ex = std::min(sx + tsz, W), sy = ty * tsz, ey = std::min(sy + tsz, H);
-        int sxp = sx, exp_ = ex, syp = sy, eyp = ey;
-        if (tile > 0) { sxp = std::max(sx - tile_pad, 0); exp_ = std::min(ex + tile_pad, W); syp = std::max(sy - tile_pad, 0); eyp = std::min(ey + tile_pad, H); }
-        TileDesc t;
-        t.h = eyp - syp; t.w = exp_ - sxp;
-        FFP_CHECK(shuf == 1 || (t.h % 2 == 0 && t.w % 2 == 0 && sxp % 2 == 0 && syp % 2 == 0), FFP_ERR_ARG,
-                  "enhance: x2 model needs even tile geometry (tile %d, pad %d)", tile, tile_pad);
-        t.src.src_off = im.in_off; t.src.src_stride = im.in_stride; t.src.src_h = im.h; t.src.src_w = im.w; t.src.pre_h = im.h + pre_pad; t.src.pre_w = im.w + pre_pad;
-        t.src.x0 = sxp; t.src.y0 = syp; t.src.fmt = im.in_fmt;
-        // core region in output pixels, clipped to the un-padded output
-        const int ox = sx * s, oy = sy * s;
-        const int cw = std::min(ex * s, out_w) - ox, chh = std::min(ey * s, out_h) - oy;
-        t.dst.dst_off = im.out_off; t.dst.dst_stride = im.out_stride; t.dst.fmt = im.out_fmt;
-        t.dst.ox = ox; t.dst.oy = oy; t.dst.cw = std::max(cw, 0); t.dst.ch = std::max(chh, 0);
-        t.dst.tx = (sx - sxp) * s; t.dst.ty = (sy - syp) * s;
-        tiles.push_back(t);
-      }
-  }
+  const int shuf = sr_shuffle(scale_);
+  const std::vector<SrTile> tiles = sr_tiles_checked(imgs, scale_, tile, tile_pad, pre_pad);
   const int n = (int)tiles.size();
-  std::vector<int> hs(n), ws(n), h1(n), w1(n), h2(n), w2(n);
-  long long t16 = 0;
-  for (int i = 0; i < n; ++i) {
-    hs[i] = tiles[i].h / shuf; ws[i] = tiles[i].w / shuf;
-    h1[i] = hs[i] * 2; w1[i] = ws[i] * 2; h2[i] = hs[i] * 4; w2[i] = ws[i] * 4;
-    t16 += (long long)((hs[i] + 15) / 16) * ((ws[i] + 15) / 16);
-  }
+  const SrLevelSizes z = sr_level_sizes(tiles, scale_);
   // The plan depends on a CAPACITY, not on the sizes: a new multiset of crop sizes (every frame of a real stream) costs table
   // uploads only — no allocation, no tuning, no graph capture (the reference enhances arbitrary crops back to back,
   // utils/enhancer.py:344-391).
-  SrPlan& P = plan_for(t16);
-  P.Lb->assign(hs, ws, st_);
-  P.L1->assign(h1, w1, st_);
-  P.L2->assign(h2, w2, st_);
+  SrPlan& P = plan_for(z.t16);
+  P.Lb->assign(z.hs, z.ws, st_);
+  P.L1->assign(z.h1, z.w1, st_);
+  P.L2->assign(z.h2, z.w2, st_);
   const int cap = P.cap_t16;
   SrSrc* srcs = reinterpret_cast<SrSrc*>(P.stage);
   SrDst* dsts = reinterpret_cast<SrDst*>(srcs + cap);
   long long* coff = reinterpret_cast<long long*>(dsts + cap);
-  long long tot = 0;
-  for (int i = 0; i < n; ++i) { srcs[i] = tiles[i].src; dsts[i] = tiles[i].dst; coff[i] = tot; tot += (long long)dsts[i].cw * dsts[i].ch; }
-  for (int i = n; i < cap; ++i) { dsts[i] = SrDst{}; coff[i] = tot; }       // padding entries: empty cores behind the last real one
-  coff[cap] = tot;
+  sr_fill_descriptors(tiles, cap, srcs, dsts, coff);      // with padding entries: empty cores behind the last real one
   FFP_HIP(hipMemcpyAsync(P.d_srcs.p, srcs, sizeof(SrSrc) * n, hipMemcpyHostToDevice, st_));
   FFP_HIP(hipMemcpyAsync(P.d_dsts.p, dsts, sizeof(SrDst) * cap, hipMemcpyHostToDevice, st_));
   FFP_HIP(hipMemcpyAsync(P.d_core_off.p, coff, sizeof(long long) * (cap + 1), hipMemcpyHostToDevice, st_));

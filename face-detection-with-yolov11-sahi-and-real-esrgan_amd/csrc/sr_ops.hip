@@ -21,12 +21,6 @@ __device__ __forceinline__ int find_img(const int4* tab, int n, long long gp) {
   return lo;
 }
 
-__device__ __forceinline__ int reflect2(int i, int n_pre, int n) {   // F.pad(..., 'reflect') twice on the high side:
-  if (i >= n_pre) i = 2 * (n_pre - 1) - i;                           // mod pad reflects the pre-padded image,
-  if (i >= n) i = 2 * (n - 1) - i;                                   // pre_pad reflects the source
-  return i;
-}
-
 __device__ __forceinline__ float ld_px(const uint8_t* p, int c, int wide) {
   return wide ? (float)reinterpret_cast<const uint16_t*>(p)[c] : (float)p[c];
 }

@@ -2,40 +2,12 @@
 #pragma once
 #include "engine.hpp"
 #include "plan_cache.hpp"
+#include "sr_tiles.hpp"
 
 namespace ffp {
 
-// Pixel format of an image the SR path reads or writes (realesrgan 0.3.0 RealESRGANer.enhance, reference call
-// utils/enhancer.py:214). The default is today's 3-channel uint8 BGR.
-enum SrSel : int {
-  SR_SEL_BGR = 0,        // read: BGR from channels 0-2 (3- or 4-channel pixel); write: BGR into channels 0-2
-  SR_SEL_GRAY = 1,       // read: channel 0 replicated to RGB (mode 'L'); write: BGR2GRAY into channel 0 (1-channel canvas)
-  SR_SEL_ALPHA = 2,      // read: channel 3 replicated to RGB (mode 'RGBA'); write: BGR2GRAY into channel 3 (4-channel canvas)
-};
-struct SrFmt {
-  int cn = 3;            // channels per pixel (1, 3, 4)
-  int wide = 0;          // 0: 8-bit storage, 1: 16-bit storage
-  float range = 255.f;   // max_range: value = stored / range on read, rint(value * range) on write
-  int sel = SR_SEL_BGR;
-  __host__ __device__ int px_bytes() const { return cn << wide; }
-};
-
-struct SrSrc {          // where one network tile reads its pixels
-  long long src_off;    // byte offset of the source image inside the base allocation
-  int src_stride;       // bytes per source row
-  int src_h, src_w;     // source size
-  int pre_h, pre_w;     // size after pre_pad; rows beyond reflect about it first (mod pad), then about the source
-  int x0, y0;           // tile origin in padded-source coordinates
-  SrFmt fmt;
-};
-struct SrDst {          // where the core of one tile's output lands
-  long long dst_off;    // byte offset of the output canvas inside the base allocation
-  int dst_stride;       // bytes per canvas row
-  int ox, oy;           // core origin in the canvas
-  int cw, ch;           // core size (output pixels)
-  int tx, ty;           // core origin inside the tile's network output
-  SrFmt fmt;
-};
+// sr_tiles (sr_tiles.hpp) with its refusals raised as FFP_ERR_ARG (rrdb.cpp)
+std::vector<SrTile> sr_tiles_checked(const std::vector<SrImage>& imgs, int scale, int tile, int tile_pad, int pre_pad);
 
 void launch_sr_pre(const uint8_t* d_base, const SrSrc* d_srcs, const TView& out, int shuf, hipStream_t st);
 void launch_sr_post(const TView& net_out, const SrDst* d_dsts, const long long* d_core_off, long long total_core, uint8_t* d_base,
@@ -78,12 +50,6 @@ struct SrPlan : Plan {
   ~SrPlan();
 };
 
-struct SrImage {           // one image of a batch: offsets are relative to the in/out base allocations
-  long long in_off; int in_stride; int h, w;
-  long long out_off; int out_stride;
-  SrFmt in_fmt, out_fmt;   // strides are in bytes; two images may share a buffer and differ in their channel selection
-};
-
 class SrEngine {
  public:
   SrEngine(const void* weights, size_t nbytes, int scale, int num_block, int device, int half);
@@ -115,7 +81,6 @@ class SrEngine {
   int plans_built = 0;          // plans laid out so far (a steady stream of varying crop sizes must not grow this)
 
  private:
-  struct TileDesc { SrSrc src; SrDst dst; int h, w; };
   void build_plan(SrPlan& P, int cap_t16);
   SrPlan& plan_for(long long t16);
   const PackedConv* conv(const std::string& name) const;

@@ -70,8 +70,7 @@ void pack_conv(PackedConv& pc, const std::string& name, const float* w, const fl
   std::vector<float> wpad;
   const int cin_real = cin;
   if (groups == 1) {   // activations are addressed in 16-byte vectors: pad the input channels with zero weights
-    const int epv = dt == F16 ? 8 : 4;
-    const int cin_al = (cin + epv - 1) / epv * epv;
+    const int cin_al = conv_cin_aligned(cin, dt);
     if (cin_al != cin) {
       wpad.assign((size_t)cout * cin_al * taps, 0.f);
       for (int n = 0; n < cout; ++n)

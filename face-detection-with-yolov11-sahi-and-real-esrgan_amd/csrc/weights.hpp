@@ -47,6 +47,13 @@ struct PackedConv {
   bool depthwise() const { return groups > 1; }
 };
 
+// PackedConv::cin of a dense conv with `cin` real input channels: activations are addressed in 16-byte vectors, so a record holds a multiple of
+// 4 fp32 / 8 fp16 channels (pack_conv pads the weights with zeros; a kernel that writes such a record zeroes the padding channels)
+inline int conv_cin_aligned(int cin, DType dt) {
+  const int epv = dt == F16 ? 8 : 4;
+  return (cin + epv - 1) / epv * epv;
+}
+
 // w: (cout, cin/groups, k, k) fp32 OIHW, b: (cout) or null (zeros)
 void pack_conv(PackedConv& pc, const std::string& name, const float* w, const float* b, int cout, int cin, int k,
                int groups, DType dt, hipStream_t st, bool split = false);

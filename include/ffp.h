@@ -692,6 +692,34 @@ int ffp_op_stem(int device, int precision, int fused, const uint8_t* frame, int 
 int ffp_op_stem_conv(int device, const uint8_t* frame, int H, int W, int chan_order, int n, const int32_t* boxes_xyxy, int imgsz, const float* stem_w,
                      const float* stem_b, int stem_cout, const float* conv_w, const float* conv_b, float* out);
 
+/* Tests only: the kernels around the Real-ESRGAN network alone — no weights, no plan. An image is 8 int64 {byte offset, bytes per row, h, w, channels
+ * (1, 3, 4), bits (8, 16), range (255, or 65535 in 16-bit storage), selection (0 BGR, 1 gray: channel 0, 2 alpha: channel 3 of 4)} inside ONE host
+ * buffer; offsets and strides are multiples of the element size, rows may be padded and images may share bytes (a colour and an alpha image over one
+ * BGRA buffer). h and w are the INPUT size; a canvas is scale times as large. scale is 4 or 2. Tiles, descriptor tables and level sizes come from the
+ * code the enhancer runs. cap_t16 == 0: exact levels (Level::build); cap_t16 > 0: levels reserved for that many 16x16 body tiles and assigned, as a
+ * plan's are; then an earlier batch (n_first > 0, same buffer) may be assigned and run first. FFP_ERR_ARG leaves every buffer as it was.
+ *
+ * ffp_op_sr_tiles (no device): h and w of every padded tile in tile order -> out_hw [cap_tiles][2], their number, the 16x16 body tiles a plan's
+ * capacity counts, and the channels of the network's input record in `precision` (conv_first's padded input channels).
+ * ffp_op_sr_pre: flat [flat_px][channels] fp32 in/out is the body level's WHOLE buffer (flat_px: sum of h/f * w/f over the tiles, f the pixel_unshuffle
+ * factor scale == 2 ? 2 : 1, or 256 * cap_t16): the caller's contents go up (rounded to fp16 in FFP_PREC_F16), the batches run, everything comes
+ * back; out_off [tiles]: first record of every tile.
+ * ffp_op_sr_post: net holds every tile's network output back to back, [scale * h][scale * w][cs] fp32 with RGB in channels 0-2; canvas in/out is
+ * the whole buffer the images lie in. The launch is the enhancer's: total_core is the x4 level's pixel count, the tables are padded to the capacity.
+ * only_tile >= 0 empties the core of every other tile of the batch, so that what one tile writes is not covered by its neighbours (-1: all tiles). */
+int ffp_op_sr_tiles(int n, const int64_t* imgs, int scale, int tile, int tile_pad, int pre_pad, int precision, int cap_tiles, int32_t* out_hw,
+                    int32_t* out_n, int32_t* out_t16, int32_t* out_channels);
+int ffp_op_sr_pre(int device, int precision, const uint8_t* src, size_t src_bytes, int n, const int64_t* imgs, int scale, int tile, int tile_pad,
+                  int pre_pad, int cap_t16, int n_first, const int64_t* imgs_first, float* flat, size_t flat_px, int64_t* out_off);
+int ffp_op_sr_post(int device, int n, const int64_t* imgs, int scale, int tile, int tile_pad, int pre_pad, const float* net, int cs, int cap_t16,
+                   int n_first, const int64_t* imgs_first, const float* net_first, int only_tile, uint8_t* canvas, size_t canvas_bytes);
+/* The 'cv2' alpha upsampler alone: src h x w x 4 (uint8, or uint16 with src_bits 16), dst out_h x out_w x 4 in/out (dst_bits 8 or 16; 16 needs a
+ * 16-bit source, range 65535 needs both): channel 3 = rint(resize_linear(src[..., 3] / range) * range), channels 0-2 stay. */
+int ffp_op_alpha_linear(int device, const void* src, int h, int w, int src_bits, int range, int out_h, int out_w, int dst_bits, void* dst);
+/* The crop gather alone: box i {x0, y0, w, h} of an H x W x 3 uint8 frame -> w * h * 3 bytes at out + offs[i]; out in/out. n == 0 is accepted. */
+int ffp_op_crop_gather(int device, const uint8_t* frame, int H, int W, int n, const int32_t* boxes_xywh, const int64_t* offs, uint8_t* out,
+                       size_t out_bytes);
+
 /* Tuning hook: mean device time (HIP events, microseconds) of `iters` back-to-back launches of one dense convolution on
  * synthetic data. dbg_mask skips kernel phases (1 stores, 2 MFMAs, 4 chunk refetch, 8 LDS stash) to attribute time —
  * results are then wrong by construction; force_shape pins the workgroup shape (-1: automatic). */
