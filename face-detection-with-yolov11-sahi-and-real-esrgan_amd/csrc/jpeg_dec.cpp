@@ -147,13 +147,17 @@ void jpeg_entropy_decode(const unsigned char* d, long long n, JpegScan& out, boo
         out.comp[c].hs = s[7 + 3 * c] >> 4; out.comp[c].vs = s[7 + 3 * c] & 15; out.comp[c].tq = s[8 + 3 * c];
         FFP_CHECK(out.comp[c].tq < 4, FFP_ERR_ARG, "jpeg: bad table selector");
       }
+      if (out.ncomp == 1) {     // a lone component is never subsampled: its MCU is one block, whatever (legal: 1..4) factors it declares
+        FFP_CHECK(out.comp[0].hs >= 1 && out.comp[0].hs <= 4 && out.comp[0].vs >= 1 && out.comp[0].vs <= 4, FFP_ERR_ARG, "jpeg: bad sampling factors %dx%d",
+                  out.comp[0].hs, out.comp[0].vs);
+        out.comp[0].hs = out.comp[0].vs = 1;
+      }
       out.hmax = out.comp[0].hs; out.vmax = out.comp[0].vs;
       for (int c = 1; c < out.ncomp; ++c) {
         FFP_CHECK(out.comp[c].hs == 1 && out.comp[c].vs == 1, FFP_ERR_ARG, "jpeg: chroma sampling factors other than 1x1 are not supported");
       }
       FFP_CHECK((out.hmax == 1 && out.vmax == 1) || (out.hmax == 2 && out.vmax == 1) || (out.hmax == 2 && out.vmax == 2), FFP_ERR_ARG,
                 "jpeg: luma sampling %dx%d is not supported (4:4:4, 4:2:2, 4:2:0 are)", out.hmax, out.vmax);
-      if (out.ncomp == 1) { out.comp[0].hs = out.comp[0].vs = 1; out.hmax = out.vmax = 1; }     // a lone component is never subsampled
       sof = true;
     } else if (m == 0xC2 || m == 0xC3 || (m >= 0xC5 && m <= 0xC7) || (m >= 0xC9 && m <= 0xCB) || (m >= 0xCD && m <= 0xCF)) {
       fail(FFP_ERR_ARG, "jpeg: progressive / lossless / arithmetic-coded files are not supported (marker 0x%02X)", m);

@@ -295,6 +295,8 @@ def parse(data: bytes) -> dict:
             for c in range(ns):
                 comp = next(x for x in out["comps"] if x["id"] == seg[1 + 2 * c])
                 comp["td"], comp["ta"] = seg[2 + 2 * c] >> 4, seg[2 + 2 * c] & 15
+            if len(out["comps"]) == 1:                              # jdinput.c per_scan_setup: a lone component's MCU is one block,
+                out["comps"][0]["hs"] = out["comps"][0]["vs"] = 1   # whatever sampling factors it declares
             out["scan"] = i + 2 + L
             return out
         i += 2 + L
@@ -351,7 +353,10 @@ def decode_coefficients(data: bytes, info: dict):
         for m_x in range(mx):
             if info["dri"] and count and count % info["dri"] == 0:
                 nb = 0                                              # byte-align, skip RSTn, reset predictions
-                assert data[pos] == 0xFF and 0xD0 <= data[pos + 1] <= 0xD7
+                assert data[pos] == 0xFF
+                while data[pos + 1] == 0xFF:                        # fill bytes before the marker (jdmarker.c next_marker skips them)
+                    pos += 1
+                assert 0xD0 <= data[pos + 1] <= 0xD7
                 pos += 2
                 last = [0] * len(info["comps"])
             count += 1
