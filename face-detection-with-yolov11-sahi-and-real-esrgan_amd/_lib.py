@@ -140,6 +140,18 @@ _SIGS = {
     "ffp_jpeg_decode_batch": (C.c_int, [C.c_int, C.c_int, _p(C.c_void_p), _p(C.c_int64), C.c_int, _p(C.c_void_p), _p(C.c_int64), _p(C.c_int32), _p(C.c_int32),
                                         _p(C.c_int32)]),
     "ffp_jpeg_decode_batch_stats": (C.c_int, [_p(C.c_int64), _p(C.c_int64), _p(C.c_int64)]),
+    "ffp_exif_orientation": (C.c_int, [_p(C.c_uint8), C.c_int64, _p(C.c_int32)]),
+    "ffp_jpeg_decode_oriented": (C.c_int, [C.c_int, _p(C.c_uint8), C.c_int64, C.c_int, C.c_int, _p(C.c_uint8), C.c_int64, _p(C.c_int32), _p(C.c_int32)]),
+    "ffp_jpeg_decode_oriented_dev": (C.c_int, [C.c_int, _p(C.c_uint8), C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, _p(C.c_int32), _p(C.c_int32)]),
+    "ffp_jpeg_decode_batch_oriented_dev": (C.c_int, [C.c_int, C.c_int, _p(C.c_void_p), _p(C.c_int64), C.c_int, _p(C.c_int32), C.c_void_p, _p(C.c_int64), _p(C.c_int64),
+                                                     C.c_int64, _p(C.c_int32), _p(C.c_int32), _p(C.c_int32)]),
+    "ffp_image_orient_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int64]),
+    "ffp_image_orient": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int64]),
+    "ffp_image_orient_batch_dev": (C.c_int, [C.c_int, C.c_int, C.c_void_p, _p(C.c_int64), _p(C.c_int32), _p(C.c_int32), C.c_int, _p(C.c_int64), _p(C.c_int32), C.c_void_p,
+                                             _p(C.c_int64), _p(C.c_int64), C.c_int64]),
+    "ffp_image_orient_time_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int, _p(C.c_float), _p(C.c_float)]),
+    "ffp_image_orient_geometry": (C.c_int, [_p(C.c_int32)]),
+    "ffp_image_orient_stats": (C.c_int, [_p(C.c_int64), _p(C.c_int64)]),
     "ffp_png_info": (C.c_int, [_p(C.c_uint8), C.c_int64, _p(C.c_int32), _p(C.c_int32), _p(C.c_int32), _p(C.c_int32)]),
     "ffp_png_decode": (C.c_int, [C.c_int, _p(C.c_uint8), C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int64]),
     "ffp_png_decode_dev": (C.c_int, [C.c_int, _p(C.c_uint8), C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64]),
@@ -1641,21 +1653,106 @@ def jpeg_info(data: bytes):
     return h.value, w.value, nc.value
 
 
-def jpeg_decode(data: bytes, bgr: bool = False, device: int = 0) -> np.ndarray:
-    """JPEG stream -> h x w x 3 uint8 (host Huffman decoding, device IDCT / upsampling / colour conversion), what cv2.imread returns (bgr=True)."""
+def _orient_arg(orient) -> int:
+    """the `orient` of the decoding entries as the C entries' orientation: True -> 0 (the file's own EXIF tag), 1..8 -> that value"""
+    if isinstance(orient, (bool, np.bool_)):
+        return 0 if orient else 1
+    return int(orient)
+
+
+def jpeg_decode(data: bytes, bgr: bool = False, device: int = 0, orient=False) -> np.ndarray:
+    """JPEG stream -> h x w x 3 uint8 (host Huffman decoding, device IDCT / upsampling / colour conversion), what cv2.imread returns (bgr=True).
+    orient: False as stored; True with the file's EXIF orientation applied on the device (the frame cv2.imread returns); 1..8 with that one."""
     h, w, _ = jpeg_info(data)
     buf = np.frombuffer(data, np.uint8)
     out = np.empty((h, w, 3), np.uint8)
-    _check(lib().ffp_jpeg_decode(device, buf.ctypes.data_as(_p(C.c_uint8)), len(buf), int(bgr), out.ctypes.data_as(_p(C.c_uint8)), out.size))
-    return out
+    if isinstance(orient, (bool, np.bool_)) and not orient:
+        _check(lib().ffp_jpeg_decode(device, buf.ctypes.data_as(_p(C.c_uint8)), len(buf), int(bgr), out.ctypes.data_as(_p(C.c_uint8)), out.size))
+        return out
+    oh, ow = C.c_int32(0), C.c_int32(0)
+    _check(lib().ffp_jpeg_decode_oriented(device, buf.ctypes.data_as(_p(C.c_uint8)), len(buf), int(bgr), _orient_arg(orient), out.ctypes.data_as(_p(C.c_uint8)), out.size,
+                                          C.byref(oh), C.byref(ow)))
+    return out.reshape(oh.value, ow.value, 3)
 
 
-def jpeg_decode_dev(data: bytes, d_ptr: int, row_stride: int, cap: int, bgr: bool = True, device: int = 0):
-    """Same into device memory (pointer, row pitch and capacity in bytes); returns (h, w)."""
-    h, w, _ = jpeg_info(data)
+def jpeg_decode_dev(data: bytes, d_ptr: int, row_stride: int, cap: int, bgr: bool = True, device: int = 0, orient=False):
+    """Same into device memory (pointer, row pitch and capacity in bytes); returns (h, w). orient as in jpeg_decode: the pitch, the capacity and the
+    returned size are then the oriented image's."""
     buf = np.frombuffer(data, np.uint8)
-    _check(lib().ffp_jpeg_decode_dev(device, buf.ctypes.data_as(_p(C.c_uint8)), len(buf), int(bgr), C.c_void_p(d_ptr), row_stride, cap))
-    return h, w
+    if isinstance(orient, (bool, np.bool_)) and not orient:
+        h, w, _ = jpeg_info(data)
+        _check(lib().ffp_jpeg_decode_dev(device, buf.ctypes.data_as(_p(C.c_uint8)), len(buf), int(bgr), C.c_void_p(d_ptr), row_stride, cap))
+        return h, w
+    oh, ow = C.c_int32(0), C.c_int32(0)
+    _check(lib().ffp_jpeg_decode_oriented_dev(device, buf.ctypes.data_as(_p(C.c_uint8)), len(buf), int(bgr), _orient_arg(orient), C.c_void_p(d_ptr), row_stride, cap,
+                                              C.byref(oh), C.byref(ow)))
+    return oh.value, ow.value
+
+
+def exif_orientation(data: bytes) -> int:
+    """The EXIF orientation of a JPEG or PNG file from its bytes (csrc/exif.hpp): 1..8, 1 for everything that is not a well-formed tag. No device."""
+    buf = np.frombuffer(data, np.uint8) if len(data) else np.zeros(1, np.uint8)
+    o = C.c_int32(0)
+    _check(lib().ffp_exif_orientation(buf.ctypes.data_as(_p(C.c_uint8)), len(data), C.byref(o)))
+    return o.value
+
+
+def image_orient_geometry() -> int:
+    """pixels along the side of the tile one workgroup of the orient kernel moves: test hook"""
+    t = C.c_int32(0)
+    _check(lib().ffp_image_orient_geometry(C.byref(t)))
+    return t.value
+
+
+def image_orient_stats():
+    """(images turned, orient launches) since load"""
+    a, b = C.c_int64(0), C.c_int64(0)
+    _check(lib().ffp_image_orient_stats(C.byref(a), C.byref(b)))
+    return a.value, b.value
+
+
+def image_orient_dev(d_src: int, h: int, w: int, px: int, src_stride: int, orientation: int, d_dst: int, dst_stride: int, cap: int, device: int = 0):
+    """The h x w image of px (1, 3, 4) bytes per pixel at device pointer d_src (row pitch in bytes) into d_dst with EXIF orientation 1..8, out of
+    place (csrc/orient.hip); cap: the bytes there are from d_dst on. Returns the destination's (h, w): (w, h) for 5..8."""
+    _check(lib().ffp_image_orient_dev(device, C.c_void_p(d_src), h, w, px, src_stride, orientation, C.c_void_p(d_dst), dst_stride, cap))
+    return (w, h) if orientation >= 5 else (h, w)
+
+
+def image_orient_time_dev(d_src: int, h: int, w: int, px: int, orientation: int, d_dst: int, cap: int, iters: int = 400, device: int = 0):
+    """(microseconds per orient launch, microseconds per device-to-device copy of the same bytes), each over `iters` runs between two events; both
+    images packed (tools/orient_probe.py)."""
+    k, c = C.c_float(0), C.c_float(0)
+    _check(lib().ffp_image_orient_time_dev(device, C.c_void_p(d_src), h, w, px, orientation, C.c_void_p(d_dst), cap, iters, C.byref(k), C.byref(c)))
+    return k.value, c.value
+
+
+def image_orient_batch_dev(d_src_base: int, src_offsets, hs, ws, px: int, src_strides, orientations, d_dst_base: int, dst_offsets, dst_strides, cap: int,
+                           device: int = 0) -> None:
+    """n images in ONE launch: image i is hs[i] x ws[i] at d_src_base + src_offsets[i] and goes to d_dst_base + dst_offsets[i] with orientations[i];
+    cap: the bytes there are from d_dst_base on."""
+    i64 = lambda a: np.ascontiguousarray(np.asarray(a, np.int64).reshape(-1))
+    i32 = lambda a: np.ascontiguousarray(np.asarray(a, np.int32).reshape(-1))
+    so, do, ss, ds_, hh, ww, oo = i64(src_offsets), i64(dst_offsets), i64(src_strides), i64(dst_strides), i32(hs), i32(ws), i32(orientations)
+    n = len(so)
+    if not all(len(a) == n for a in (do, ss, ds_, hh, ww, oo)):
+        raise ValueError("image_orient_batch_dev: one entry per image in every table")
+    p64 = lambda a: a.ctypes.data_as(_p(C.c_int64))
+    p32 = lambda a: a.ctypes.data_as(_p(C.c_int32))
+    _check(lib().ffp_image_orient_batch_dev(device, n, C.c_void_p(d_src_base), p64(so), p32(hh), p32(ww), px, p64(ss), p32(oo), C.c_void_p(d_dst_base), p64(do), p64(ds_), cap))
+
+
+def image_orient(img: np.ndarray, orientation: int, device: int = 0) -> np.ndarray:
+    """The same on a host image (h x w or h x w x {1, 3, 4} uint8, rows of any pitch): up, turned on the device, down."""
+    if img.dtype != np.uint8 or img.ndim not in (2, 3) or img.size == 0:
+        raise ValueError("image_orient: an h x w or h x w x c uint8 array")
+    h, w = img.shape[:2]
+    px = img.shape[2] if img.ndim == 3 else 1
+    if (img.ndim == 3 and px > 1 and img.strides[2] != 1) or (w > 1 and img.strides[1] != px) or (h > 1 and img.strides[0] < w * px):
+        raise ValueError("image_orient: pixels contiguous in memory, rows at a pitch of at least a row")
+    out = np.empty((w, h) + img.shape[2:] if 5 <= orientation <= 8 else img.shape, np.uint8)
+    _check(lib().ffp_image_orient(device, C.c_void_p(img.ctypes.data), h, w, px, img.strides[0] if h > 1 else w * px, orientation, C.c_void_p(out.ctypes.data),
+                                  out.strides[0], out.nbytes))
+    return out
 
 
 def _file_table(datas):
@@ -1666,10 +1763,11 @@ def _file_table(datas):
     return ptrs, sizes, bufs
 
 
-def jpeg_decode_batch_dev(datas, d_base: int, offsets, strides, cap: int, bgr: bool = True, device: int = 0):
+def jpeg_decode_batch_dev(datas, d_base: int, offsets, strides, cap: int, bgr: bool = True, device: int = 0, orientations=None):
     """n JPEG streams -> n images in device memory in ONE pass (ffp_jpeg_decode_batch_dev): image i at d_base + offsets[i], row pitch strides[i]
     (None: packed). Returns (hs, ws, status) as int32 arrays; status 0: decoded on the device, 1: by the host decoder, < 0: minus the error code
-    of a file that was not decoded (its region is untouched)."""
+    of a file that was not decoded (its region is untouched). orientations: None as stored; True every file's own EXIF orientation; or one value
+    per file, 0 the file's own and 1..8 that one — applied on the device, and the pitches, the capacity, hs and ws are then the oriented images'."""
     n = len(datas)
     ptrs, sizes, keep = _file_table(datas)
     offsets = np.ascontiguousarray(np.asarray(offsets, np.int64).reshape(-1))
@@ -1681,8 +1779,16 @@ def jpeg_decode_batch_dev(datas, d_base: int, offsets, strides, cap: int, bgr: b
     hs, ws, status = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
     i64 = lambda a: a.ctypes.data_as(_p(C.c_int64))
     i32 = lambda a: a.ctypes.data_as(_p(C.c_int32))
-    _check(lib().ffp_jpeg_decode_batch_dev(device, n, ptrs, i64(np.ascontiguousarray(sizes)) if n else i64(np.zeros(1, np.int64)), int(bgr), C.c_void_p(d_base),
-                                           i64(offsets) if n else i64(np.zeros(1, np.int64)), None if st is None else i64(st), cap, i32(hs), i32(ws), i32(status)))
+    if orientations is None:
+        _check(lib().ffp_jpeg_decode_batch_dev(device, n, ptrs, i64(np.ascontiguousarray(sizes)) if n else i64(np.zeros(1, np.int64)), int(bgr), C.c_void_p(d_base),
+                                               i64(offsets) if n else i64(np.zeros(1, np.int64)), None if st is None else i64(st), cap, i32(hs), i32(ws), i32(status)))
+    else:
+        oo = None if orientations is True else np.ascontiguousarray(np.asarray(orientations, np.int32).reshape(-1))
+        if oo is not None and len(oo) != n:
+            raise ValueError("jpeg_decode_batch_dev: one orientation per file")
+        _check(lib().ffp_jpeg_decode_batch_oriented_dev(device, n, ptrs, i64(np.ascontiguousarray(sizes)) if n else i64(np.zeros(1, np.int64)), int(bgr),
+                                                        None if oo is None or n == 0 else i32(oo), C.c_void_p(d_base), i64(offsets) if n else i64(np.zeros(1, np.int64)),
+                                                        None if st is None else i64(st), cap, i32(hs), i32(ws), i32(status)))
     del keep
     return hs[:n], ws[:n], status[:n]
 

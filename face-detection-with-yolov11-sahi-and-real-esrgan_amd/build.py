@@ -15,7 +15,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libffp.so")
-SOURCES = ["common.cpp", "weights.cpp", "engine.cpp", "conv_route.cpp", "conv_mfma.hip", "conv_rows.hip", "conv_rows16.hip", "conv_rows16pc.hip", "conv_trunk.hip", "conv_pw.hip", "conv_k3d.hip", "conv_dwpw.hip", "ops_misc.hip", "det_post.hip", "merge.hip", "eval.hip", "coco_eval.hip", "iqa.hip", "jpeg.hip", "jpeg_huff.hip", "jpeg_dec.cpp", "png.hip", "png_dec.cpp", "png_dec.hip", "overlay.hip",
+SOURCES = ["common.cpp", "weights.cpp", "engine.cpp", "conv_route.cpp", "conv_mfma.hip", "conv_rows.hip", "conv_rows16.hip", "conv_rows16pc.hip", "conv_trunk.hip", "conv_pw.hip", "conv_k3d.hip", "conv_dwpw.hip", "ops_misc.hip", "det_post.hip", "merge.hip", "eval.hip", "coco_eval.hip", "iqa.hip", "jpeg.hip", "jpeg_huff.hip", "jpeg_dec.cpp", "png.hip", "png_dec.cpp", "png_dec.hip", "overlay.hip", "orient.hip",
            "sr_ops.hip", "resize.hip", "yolo11.cpp", "rrdb.cpp", "onnx_graph.cpp", "scrfd_ops.hip", "scrfd.cpp", "rtdetr_ops.hip", "rtdetr.cpp", "sliced.cpp", "api.cpp",
            "api_eval.cpp", "api_codec.cpp", "api_ops.cpp"]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-result",
@@ -206,6 +206,12 @@ def build_ws_pool_check(verbose: bool = True) -> tuple:
             _build_host_check("ws_pool_host_check_tsan", *args, sanitize=("-pthread", "-fsanitize=thread")))
 
 
+def build_exif_check(verbose: bool = True) -> str:
+    """The EXIF orientation parser (csrc/exif.hpp, no HIP in it): the test corpus, every prefix of it and seeded single-byte corruptions, each in a heap
+    block of its own length."""
+    return _build_host_check("exif_host_check", "exif_host_check.cpp", ["exif.hpp"], verbose)
+
+
 if __name__ == "__main__":
     if "--asan" in sys.argv:
         build_asan()
@@ -223,6 +229,8 @@ if __name__ == "__main__":
         build_sr_tiles_check()
     elif "--ws-pool-check" in sys.argv:
         build_ws_pool_check()
+    elif "--exif-check" in sys.argv:
+        build_exif_check()
     elif "--variant" in sys.argv:
         build_variant(sys.argv[sys.argv.index("--variant") + 1])
     else:

@@ -13,7 +13,8 @@ libpng's, the same pixels (tests/test_gpu_png.py), 10 to 100 times sooner than P
 8-bit gray / RGB / RGBA `.png` files are read by the device decoder (csrc/png_dec.hip: ffp_png_decode) and come back as Pillow's
 `convert("RGB")` gives them; 16-bit, palette, tRNS, gray+alpha and interlaced files stay with Pillow (profiles/png_decode_mi355x.json). Files the
 device codec does not read (progressive, RGB-coded with Adobe transform 0 or R/G/B component ids) and machines without a GPU use
-Pillow, and say so once on stderr. Like `cv2.imread`, `imread` applies the EXIF orientation tag (not with IMREAD_UNCHANGED).
+Pillow, and say so once on stderr. Like `cv2.imread`, `imread` applies the EXIF orientation tag (not with IMREAD_UNCHANGED): for `.jpg` files on
+the device, before the frame comes down, when ORIENT_DEVICE_ROUTE is set (csrc/orient.hip; off by default).
 """
 import importlib.machinery
 import importlib.util
@@ -49,6 +50,12 @@ else:
     INTER_NEAREST, INTER_LINEAR, INTER_CUBIC, INTER_AREA, INTER_LANCZOS4 = 0, 1, 2, 3, 4
 
     _state = {"gpu": None, "told": False, "told_png": False}
+
+    # .jpg / .jpeg, True: the EXIF orientation is read from the file's bytes and applied on the device before the frame comes down (csrc/exif.hpp,
+    # csrc/orient.hip). False: the tag through Pillow and a numpy transpose-and-copy on the host, as before. Off by default: the device route's
+    # median is 9 to 11 times lower, but in one of two visits its slowest sample (31.7 ms) did not beat the host route's fastest (24.5 ms), and a
+    # route is on only where it does (README, profiles/orient_mi355x.json).
+    ORIENT_DEVICE_ROUTE = False
 
     def _gpu_codec():
         if _state["gpu"] is None:
@@ -106,14 +113,17 @@ else:
         """HxWx3 uint8 BGR with the EXIF orientation applied (OpenCV's default), or None when the file cannot be read (OpenCV's
         convention: no exception)."""
         try:
-            o = _exif_orientation(path) if flags != IMREAD_UNCHANGED else 1
+            turn = flags != IMREAD_UNCHANGED
+            tag = lambda: _exif_orientation(path) if turn else 1       # through Pillow, for the host's transpose-and-copy
             if _is_jpeg(path):
                 codec = _gpu_codec()
                 if codec:
                     with open(path, "rb") as fh:
                         data = fh.read()
                     try:
-                        return _oriented(codec.jpeg_decode(data, bgr=True), o)
+                        if ORIENT_DEVICE_ROUTE:
+                            return codec.jpeg_decode(data, bgr=True, orient=turn)      # the tag from the bytes, the turn on the device
+                        return _oriented(codec.jpeg_decode(data, bgr=True), tag())
                     except codec.FfpError as e:               # e.g. a progressive or an RGB-coded (Adobe transform 0) file
                         _tell(str(e))
                 else:
@@ -124,8 +134,8 @@ else:
                     with open(path, "rb") as fh:
                         a = codec.png_read_rgb8(fh.read(), bgr=True)      # None: the file stays with Pillow (16-bit, palette, tRNS, a route left to Pillow)
                     if a is not None:
-                        return _oriented(a, o)
-            return _oriented(np.asarray(Image.open(path).convert("RGB"))[..., ::-1], o)
+                        return _oriented(a, tag())
+            return _oriented(np.asarray(Image.open(path).convert("RGB"))[..., ::-1], tag())
         except Exception:
             return None
 

@@ -243,6 +243,10 @@ def build_overlay_prims(result, width, height, show_confidence=True, show_keypoi
 # code of before, below); ROUTE_CALLS counts which route finished each call — the host routes are the only ones that bring the frame down.
 DRAW_DEVICE_ROUTE = True
 CROPS_DEVICE_ROUTE_MIN_CROPS = 1
+# A file whose EXIF orientation is 2..8 (what phones write) keeps the device routes: the tag is read from the file's bytes (csrc/exif.hpp) and the
+# frame is turned where it was decoded (csrc/orient.hip), so h and w below are the oriented frame's, the ones cv2.imread returns. False sends such
+# files to the host routes, as before (tools/orient_probe.py -> profiles/orient_mi355x.json measures both).
+ORIENT_DEVICE_ROUTE = True
 ROUTE_CALLS = {"draw_device": 0, "draw_host": 0, "crops_device": 0, "crops_host": 0}
 
 
@@ -252,8 +256,9 @@ def _ext(path):
 
 def _frame_on_device(image_path, data=None):
     """(torch uint8 tensor holding the packed BGR frame, h, w, _lib), or None when the file is not one for this route: no device, not a .jpg /
-    .jpeg / .png path, an EXIF orientation other than 1 (cv2.imread would turn the frame), a PNG that is not 8-bit RGB, or any refusal of
-    the decoder (progressive JPEG, ...). data: the file's bytes, when the caller has read them."""
+    .jpeg / .png path, a PNG that is not 8-bit RGB, or any refusal of the decoder (progressive JPEG, ...). The frame is the one cv2.imread
+    returns: a file with an EXIF orientation of 2..8 is turned on the device (h, w are the turned frame's), or is not one for this route when
+    ORIENT_DEVICE_ROUTE is off. data: the file's bytes, when the caller has read them."""
     try:
         ext = _ext(image_path)
         if ext not in (".jpg", ".jpeg", ".png"):
@@ -265,22 +270,27 @@ def _frame_on_device(image_path, data=None):
         if data is None:
             with open(image_path, "rb") as fh:
                 data = fh.read()
-        with Image.open(io.BytesIO(data)) as im:
-            if 2 <= int(im.getexif().get(0x0112, 1)) <= 8:          # the orientations cv2.imread applies
-                return None
+        o = _lib.exif_orientation(data)                             # 2..8: the orientations cv2.imread applies
+        if o != 1 and not ORIENT_DEVICE_ROUTE:
+            return None
         if ext == ".png":
             h, w, ch, depth = _lib.png_info(data)
             if ch != 3 or depth != 8 or _lib._png_has_trns(data):
                 return None
         else:
             h, w, _ = _lib.jpeg_info(data)
-        frame = torch.empty(h * w * 3, dtype=torch.uint8, device=torch.device("cuda", 0))
+        oh, ow = (w, h) if o >= 5 else (h, w)
+        size = h * w * 3
+        frame = torch.empty(size, dtype=torch.uint8, device=torch.device("cuda", 0))
+        stored = frame if o == 1 or ext != ".png" else torch.empty(size, dtype=torch.uint8, device=torch.device("cuda", 0))
         torch.cuda.synchronize(0)
         if ext == ".png":
-            _lib.png_decode_dev(data, frame.data_ptr(), w * 3, h * w * 3, bgr=True)
+            _lib.png_decode_dev(data, stored.data_ptr(), w * 3, size, bgr=True)
+            if o != 1:
+                _lib.image_orient_dev(stored.data_ptr(), h, w, 3, w * 3, o, frame.data_ptr(), ow * 3, size)
         else:
-            _lib.jpeg_decode_dev(data, frame.data_ptr(), w * 3, h * w * 3, bgr=True)
-        return frame, h, w, _lib
+            _lib.jpeg_decode_dev(data, frame.data_ptr(), ow * 3, size, bgr=True, orient=o if o != 1 else False)
+        return frame, oh, ow, _lib
     except Exception:
         return None
 
@@ -380,6 +390,8 @@ def _crops_on_device(image_path, result, min_crops):
         with open(image_path, "rb") as fh:
             data = fh.read()
         h, w = (_lib.png_info(data) if ext == ".png" else _lib.jpeg_info(data))[:2]          # the crop count decides the route: headers first
+        if _lib.exif_orientation(data) >= 5:                       # the boxes are the oriented frame's
+            h, w = w, h
         boxes = crop_boxes(result, w, h)
         if len(boxes) < min_crops:
             return None

@@ -1,7 +1,9 @@
 // api_codec.cpp — the C-ABI of libffp.so, part three of four (see api.cpp): JPEG and PNG at the file boundaries, and the overlay drawing between a decode and an
 // encode. They take a device number, not a handle.
 #include "api_util.hpp"
+#include "exif.hpp"
 #include "jpeg.hpp"
+#include "orient.hpp"
 #include "overlay.hpp"
 #include "png.hpp"
 #include "png_dec.hpp"
@@ -97,12 +99,12 @@ int ffp_jpeg_decode_stats(int64_t* device_decodes, int64_t* host_fallbacks, int6
 // and ffp_last_error names the first file that failed. What only a batch entry reports is done here, after the routine the single-file entries share:
 // the batch counters, and that name.
 static void decode_batch(int n, const uint8_t* const* datas, const int64_t* sizes, int bgr, uint8_t* d_base, const long long* offsets, const int64_t* strides,
-                         int64_t cap, int32_t* hs, int32_t* ws, int32_t* status, hipStream_t st) {
+                         int64_t cap, int32_t* hs, int32_t* ws, int32_t* status, hipStream_t st, const int32_t* orientations = nullptr) {
   static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(int) == sizeof(int32_t), "the ABI's integer types are the library's");
   std::vector<std::string> why((size_t)n);
   JpegBatchCost cost;
   jpeg_decode_batch_to_device(n, datas, reinterpret_cast<const long long*>(sizes), bgr, d_base, offsets, reinterpret_cast<const long long*>(strides), cap, hs, ws, status,
-                              why.data(), &cost, st);
+                              why.data(), &cost, st, orientations);
   jpeg_batch_note(cost);
   for (int i = 0; i < n; ++i)
     if (status[i] < 0) {
@@ -148,6 +150,49 @@ int ffp_jpeg_decode_batch(int device, int n, const uint8_t* const* datas, const 
     decode_batch(n, datas, sizes, bgr, d.as<unsigned char>(), off.data(), nullptr, total, hs, ws, status, cx.st);
     for (int i = 0; i < n; ++i)
       if (status[i] >= 0) FFP_HIP(hipMemcpy(outs[i], d.as<unsigned char>() + off[i], (size_t)hs[i] * ws[i] * 3, hipMemcpyDeviceToHost));
+  }
+  FFP_API_END
+}
+
+// ---- the same with the EXIF orientation applied on the device (exif.hpp, orient.hip) ------------------------------------------------------
+int ffp_exif_orientation(const uint8_t* data, int64_t n, int32_t* orientation) {
+  FFP_API_BEGIN
+  FFP_CHECK(data && orientation, FFP_ERR_ARG, "exif_orientation: null argument");
+  *orientation = exif::orientation(data, n);
+  FFP_API_END
+}
+
+int ffp_jpeg_decode_oriented_dev(int device, const uint8_t* data, int64_t n, int bgr, int orientation, uint8_t* d_out, int64_t row_stride, int64_t cap, int32_t* out_h,
+                                 int32_t* out_w) {
+  FFP_API_BEGIN
+  FFP_CHECK(data && d_out, FFP_ERR_ARG, "jpeg_decode_oriented: null argument");
+  ScopedStream cx(device, "jpeg_decode_oriented", ScopedStream::Io);
+  jpeg_decode_to_device(data, n, d_out, row_stride, cap, bgr, cx.st, orientation, out_h, out_w);
+  FFP_API_END
+}
+
+int ffp_jpeg_decode_oriented(int device, const uint8_t* data, int64_t n, int bgr, int orientation, uint8_t* out, int64_t cap, int32_t* out_h, int32_t* out_w) {
+  FFP_API_BEGIN
+  FFP_CHECK(data && out, FFP_ERR_ARG, "jpeg_decode_oriented: null argument");
+  ScopedStream cx(device, "jpeg_decode_oriented", ScopedStream::Io);
+  JpegScan s;
+  jpeg_entropy_decode(data, n, s, true);
+  const size_t bytes = (size_t)s.h * s.w * 3;              // the same for both shapes
+  FFP_CHECK(cap >= (int64_t)bytes, FFP_ERR_ARG, "jpeg_decode_oriented: output buffer too small for %dx%d", s.w, s.h);
+  DevBuf d(bytes);
+  jpeg_decode_to_device(data, n, d.as<unsigned char>(), 0, (long long)bytes, bgr, cx.st, orientation, out_h, out_w);
+  FFP_HIP(hipMemcpy(out, d.p, bytes, hipMemcpyDeviceToHost));
+  FFP_API_END
+}
+
+int ffp_jpeg_decode_batch_oriented_dev(int device, int n, const uint8_t* const* datas, const int64_t* sizes, int bgr, const int32_t* orientations, uint8_t* d_base,
+                                       const int64_t* offsets, const int64_t* strides, int64_t cap, int32_t* hs, int32_t* ws, int32_t* status) {
+  FFP_API_BEGIN
+  FFP_CHECK(n >= 0 && (n == 0 || (datas && sizes && d_base && offsets && hs && ws && status)), FFP_ERR_ARG, "jpeg_decode_batch_oriented: bad arguments");
+  if (n > 0) {
+    const std::vector<int32_t> own((size_t)n, 0);            // a null array: every file's own tag
+    ScopedStream cx(device, "jpeg_decode_batch_oriented", ScopedStream::Io);
+    decode_batch(n, datas, sizes, bgr, d_base, reinterpret_cast<const long long*>(offsets), strides, cap, hs, ws, status, cx.st, orientations ? orientations : own.data());
   }
   FFP_API_END
 }
@@ -315,6 +360,87 @@ int ffp_overlay_draw(int device, uint8_t* img, int h, int w, int64_t row_stride,
     overlay_draw_device(d.as<unsigned char>(), h, w, (long long)row, prims, n, masks, mask_bytes, cx.st);
     FFP_HIP(hipMemcpy2D(img, (size_t)row_stride, d.p, row, row, (size_t)h, hipMemcpyDeviceToHost));
   }
+  FFP_API_END
+}
+
+// ---- the EXIF orientation of an image that stays on the device (orient.hip) -----------------------------------------------------------
+// Every refusal comes from orient_check, before the device is chosen: a refused call has touched nothing.
+int ffp_image_orient_dev(int device, const uint8_t* d_src, int h, int w, int px, int64_t src_stride, int orientation, uint8_t* d_dst, int64_t dst_stride, int64_t cap) {
+  FFP_API_BEGIN
+  const OrientJob j{d_src, d_dst, src_stride, dst_stride, h, w, orientation};
+  orient_check(j, px, cap);
+  ScopedStream cx(device, "image_orient", ScopedStream::Io);
+  orient_batch_device(&j, 1, px, cx.st);
+  FFP_API_END
+}
+
+int ffp_image_orient_batch_dev(int device, int n, const uint8_t* d_src_base, const int64_t* src_offsets, const int32_t* hs, const int32_t* ws, int px,
+                               const int64_t* src_strides, const int32_t* orientations, uint8_t* d_dst_base, const int64_t* dst_offsets, const int64_t* dst_strides,
+                               int64_t cap) {
+  FFP_API_BEGIN
+  FFP_CHECK(n >= 0 && (n == 0 || (d_src_base && src_offsets && hs && ws && src_strides && orientations && d_dst_base && dst_offsets && dst_strides)), FFP_ERR_ARG,
+            "image_orient_batch: bad arguments");
+  std::vector<OrientJob> jobs((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    FFP_CHECK(src_offsets[i] >= 0 && dst_offsets[i] >= 0 && dst_offsets[i] <= cap, FFP_ERR_ARG, "image_orient_batch: image %d lies outside its buffer", i);
+    jobs[i] = OrientJob{d_src_base + src_offsets[i], d_dst_base + dst_offsets[i], src_strides[i], dst_strides[i], hs[i], ws[i], orientations[i]};
+    orient_check(jobs[i], px, cap - dst_offsets[i]);
+  }
+  // destinations that overlap one another would be written by two workgroups in no order, and a destination that overlaps ANY image's source
+  // would be written while another workgroup reads it
+  auto dst_lo = [&](int i) { return reinterpret_cast<uintptr_t>(jobs[i].dst); };
+  auto dst_hi = [&](int i) { return dst_lo(i) + (uintptr_t)((int64_t)(orient_out_h(jobs[i]) - 1) * dst_strides[i] + (int64_t)orient_out_w(jobs[i]) * px); };
+  auto src_lo = [&](int i) { return reinterpret_cast<uintptr_t>(jobs[i].src); };
+  auto src_hi = [&](int i) { return src_lo(i) + (uintptr_t)((int64_t)(hs[i] - 1) * src_strides[i] + (int64_t)ws[i] * px); };
+  for (int i = 0; i < n; ++i)
+    for (int k = 0; k < n; ++k) {
+      FFP_CHECK(k <= i || dst_hi(i) <= dst_lo(k) || dst_hi(k) <= dst_lo(i), FFP_ERR_ARG, "image_orient_batch: the destinations of images %d and %d overlap", i, k);
+      FFP_CHECK(dst_hi(i) <= src_lo(k) || src_hi(k) <= dst_lo(i), FFP_ERR_ARG, "image_orient_batch: the destination of image %d overlaps the source of image %d", i, k);
+    }
+  if (n > 0) {
+    ScopedStream cx(device, "image_orient_batch", ScopedStream::Io);
+    orient_batch_device(jobs.data(), n, px, cx.st);
+  }
+  FFP_API_END
+}
+
+int ffp_image_orient(int device, const uint8_t* src, int h, int w, int px, int64_t src_stride, int orientation, uint8_t* dst, int64_t dst_stride, int64_t cap) {
+  FFP_API_BEGIN
+  const OrientJob host{src, dst, src_stride, dst_stride, h, w, orientation};
+  orient_check(host, px, cap);
+  ScopedStream cx(device, "image_orient", ScopedStream::Io);
+  const size_t srow = (size_t)w * px, drow = (size_t)orient_out_w(host) * px, dh = (size_t)orient_out_h(host);
+  DevBuf ds((size_t)h * srow), dd(dh * drow);
+  FFP_HIP(hipMemcpy2D(ds.p, srow, src, (size_t)src_stride, srow, (size_t)h, hipMemcpyHostToDevice));
+  const OrientJob j{ds.as<unsigned char>(), dd.as<unsigned char>(), (long long)srow, (long long)drow, h, w, orientation};
+  orient_batch_device(&j, 1, px, cx.st);
+  FFP_HIP(hipMemcpy2D(dst, (size_t)dst_stride, dd.p, drow, drow, dh, hipMemcpyDeviceToHost));
+  FFP_API_END
+}
+
+int ffp_image_orient_time_dev(int device, const uint8_t* d_src, int h, int w, int px, int orientation, uint8_t* d_dst, int64_t cap, int iters, float* kernel_us,
+                              float* copy_us) {
+  FFP_API_BEGIN
+  FFP_CHECK(iters >= 1 && iters <= 10000 && kernel_us && copy_us, FFP_ERR_ARG, "image_orient_time: %d iterations (1..10000), or a null result", iters);
+  const OrientJob j{d_src, d_dst, (int64_t)w * px, (int64_t)(orientation >= 5 && orientation <= 8 ? h : w) * px, h, w, orientation};
+  orient_check(j, px, cap);
+  ScopedStream cx(device, "image_orient_time", ScopedStream::Io);
+  orient_time_device(j, px, iters, kernel_us, copy_us, cx.st);
+  FFP_API_END
+}
+
+int ffp_image_orient_geometry(int32_t* tile) {
+  FFP_API_BEGIN
+  if (tile) *tile = kOrientTile;
+  FFP_API_END
+}
+
+int ffp_image_orient_stats(int64_t* images, int64_t* launches) {
+  FFP_API_BEGIN
+  long long a = 0, b = 0;
+  orient_stats(&a, &b);
+  if (images) *images = a;
+  if (launches) *launches = b;
   FFP_API_END
 }
 

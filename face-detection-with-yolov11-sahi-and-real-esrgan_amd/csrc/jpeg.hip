@@ -15,6 +15,7 @@
 
 #include <cstdlib>
 
+#include "exif.hpp"
 #include "jpeg.hpp"
 #include "jpeg_batch_plan.hpp"
 
@@ -757,15 +758,21 @@ void jpeg_batch_reconstruct(const JpegBatchIdct* d_idct, int n_idct, int n_idct_
 // One file is a batch of one, as jpeg_encode_device is of jpeg_encode_batch_device. The header is read here first, so that whatever the
 // markers refuse, and a buffer that is too small, fail as a single file's always did, with nothing queued; what can come back in `status` is
 // then only the host decoder's refusal of a damaged stream, and it is thrown as it was recorded.
-void jpeg_decode_to_device(const unsigned char* data, long long n, unsigned char* d_out, long long stride, long long cap, int bgr, hipStream_t st) {
+void jpeg_decode_to_device(const unsigned char* data, long long n, unsigned char* d_out, long long stride, long long cap, int bgr, hipStream_t st, int orientation,
+                           int* out_h, int* out_w) {
   JpegScan s;
   jpeg_entropy_decode(data, n, s, true);
-  if (stride == 0) stride = (long long)s.w * 3;
-  FFP_CHECK(stride >= (long long)s.w * 3 && cap >= stride * (s.h - 1) + (long long)s.w * 3, FFP_ERR_ARG, "jpeg_decode: output buffer too small for %dx%d", s.w, s.h);
+  FFP_CHECK(orientation >= 0 && orientation <= 8, FFP_ERR_ARG, "jpeg_decode: orientation %d (0: the file's own, 1..8: forced)", orientation);
+  if (orientation == 0) orientation = exif::orientation(data, n);
+  const long long oh = orientation >= 5 ? s.w : s.h, ow = orientation >= 5 ? s.h : s.w;
+  if (out_h) *out_h = (int)oh;
+  if (out_w) *out_w = (int)ow;
+  if (stride == 0) stride = ow * 3;
+  FFP_CHECK(stride >= ow * 3 && cap >= stride * (oh - 1) + ow * 3, FFP_ERR_ARG, "jpeg_decode: output buffer too small for %lldx%lld", ow, oh);
   const long long offset = 0;
   int h = 0, w = 0, status = 0;
   std::string why;
-  jpeg_decode_batch_to_device(1, &data, &n, bgr, d_out, &offset, &stride, cap, &h, &w, &status, &why, nullptr, st);
+  jpeg_decode_batch_to_device(1, &data, &n, bgr, d_out, &offset, &stride, cap, &h, &w, &status, &why, nullptr, st, &orientation);
   if (status < 0) throw Error(-status, why);
 }
 

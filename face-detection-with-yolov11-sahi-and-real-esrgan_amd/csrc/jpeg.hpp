@@ -48,10 +48,17 @@ void jpeg_entropy_decode(const unsigned char* data, long long n, JpegScan& out, 
 // cost (or nullptr): what the call queued, for the batch entries' counters (jpeg_batch_note).
 struct JpegBatchCost { long long launches = 0, syncs = 0; };
 void jpeg_decode_batch_to_device(int n, const unsigned char* const* datas, const long long* sizes, int bgr, unsigned char* d_base, const long long* offsets,
-                                 const long long* strides, long long cap, int* hs, int* ws, int* status, std::string* why, JpegBatchCost* cost, hipStream_t st);
+                                 const long long* strides, long long cap, int* hs, int* ws, int* status, std::string* why, JpegBatchCost* cost, hipStream_t st,
+                                 const int* orientations = nullptr);
+// orientations (n entries, or nullptr: every file as stored): the EXIF orientation applied to file i — 0 the file's own tag (exif.hpp), 1..8 that
+// value. A turned file (2..8) is reconstructed into a pooled workspace image and turned into its region by the orient kernel (orient.hip): at most
+// ONE more launch per sub-batch, whatever n is, and none when every file is 1; offsets, strides, cap, hs and ws then describe the ORIENTED image,
+// and a file that is not decoded still leaves its region untouched. A value outside 0..8: FFP_ERR_ARG before anything is queued.
 // One file is a batch of one: throws what the markers refuse and "output buffer too small" before anything is queued, and the recorded
 // ffp::Error of a file that was not decoded (d_out is untouched then). stride 0: packed. Two stream synchronisations.
-void jpeg_decode_to_device(const unsigned char* data, long long n, unsigned char* d_out, long long stride, long long cap, int bgr, hipStream_t st);
+// orientation: as above (0: the file's own); stride, cap and out_h / out_w (or nullptr) are the oriented image's.
+void jpeg_decode_to_device(const unsigned char* data, long long n, unsigned char* d_out, long long stride, long long cap, int bgr, hipStream_t st, int orientation = 1,
+                           int* out_h = nullptr, int* out_w = nullptr);
 // counters: files (both kinds of entry) decoded on the device / by the host decoder after the device decoder gave up / extra rounds of
 // synchronisation; batches (ffp_jpeg_decode_batch* only: jpeg_batch_note) and the latest one's launches and synchronisations
 void jpeg_huff_stats(long long* device_decodes, long long* host_fallbacks, long long* extra_sync_rounds);

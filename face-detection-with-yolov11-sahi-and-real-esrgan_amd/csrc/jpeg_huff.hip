@@ -29,8 +29,10 @@
 #include <string>
 #include <vector>
 
+#include "exif.hpp"
 #include "jpeg.hpp"
 #include "jpeg_batch_plan.hpp"
+#include "orient.hpp"
 
 namespace ffp {
 
@@ -571,6 +573,14 @@ struct BatchWs {
 constexpr size_t kFrameBytes = 160u << 20;       // above what a 3840 x 2160 frame takes: ~55 MiB at 4:2:0 quality 95, ~145 MiB at 4:4:4 with an 8 MB stream
 // (never destroyed: nothing is freed at exit, when the runtime may be gone)
 WsPool<BatchWs>& g_batch_pool = *new WsPool<BatchWs>(WsPolicy{32, kFrameBytes, 0}, delete_on_owner_device<BatchWs>);
+// the images the turned files of ONE sub-batch (or one host-decoded file) are reconstructed into before the orient launch; at most one kept per
+// device that holds more than a 4K frame, none above 256 MiB
+struct TurnWs {
+  DevBuf img;
+  int device = 0;
+  size_t held() const { return img.n; }
+};
+WsPool<TurnWs>& g_turn_pool = *new WsPool<TurnWs>(WsPolicy{8, 32u << 20, 256u << 20}, delete_on_owner_device<TurnWs>);
 WsPool<JpegDecodeWs>& g_host_pool = *new WsPool<JpegDecodeWs>(WsPolicy{32, 0, 0}, delete_on_owner_device<JpegDecodeWs>);     // the host decoder's staging
 
 // the host decoder for one file: a stream the device decoder flagged, a file outside its limits, everything under FFP_JPEG_HOST_HUFFMAN=1.
@@ -662,8 +672,11 @@ void jpeg_batch_note(const JpegBatchCost& k) {
 }
 
 void jpeg_decode_batch_to_device(int n, const unsigned char* const* datas, const long long* sizes, int bgr, unsigned char* d_base, const long long* offsets,
-                                 const long long* strides, long long cap, int* hs, int* ws, int* status, std::string* why, JpegBatchCost* cost, hipStream_t st) {
+                                 const long long* strides, long long cap, int* hs, int* ws, int* status, std::string* why, JpegBatchCost* cost, hipStream_t st,
+                                 const int* orientations) {
   if (n <= 0) return;
+  for (int i = 0; orientations && i < n; ++i)
+    FFP_CHECK(orientations[i] >= 0 && orientations[i] <= 8, FFP_ERR_ARG, "jpeg_decode_batch: orientation %d of file %d (0: the file's own, 1..8: forced)", orientations[i], i);
   auto refuse = [&](int i, const Error& e) {
     status[i] = -e.code;
     if (why) why[i] = e.what();
@@ -673,13 +686,19 @@ void jpeg_decode_batch_to_device(int n, const unsigned char* const* datas, const
   std::vector<JpegHead> heads((size_t)n);
   std::vector<unsigned char> readable((size_t)n, 0);
   std::vector<long long> stride((size_t)n, 0);
+  // a turned file (EXIF orientation 2..8) is reconstructed into a pooled workspace image and turned into its region by ONE orient launch per
+  // sub-batch (orient.hip); hs / ws, the pitch and the region's bounds are the ORIENTED image's
+  std::vector<int> ori((size_t)n, 1);
+  std::vector<long long> turn_off((size_t)n, 0);                      // inside the turn workspace, laid out anew for every sub-batch
+  auto turn_slot = [&](int i) { return ((long long)scans[i].h * scans[i].w * 3 + 255) / 256 * 256; };
   for (int i = 0; i < n; ++i) {
     hs[i] = ws[i] = 0; status[i] = 0;
     if (why) why[i].clear();
     try {
       FFP_CHECK(datas[i] && sizes[i] > 0, FFP_ERR_ARG, "jpeg_decode_batch: no data");
       jpeg_entropy_decode(datas[i], sizes[i], scans[i], true, &heads[i]);
-      hs[i] = scans[i].h; ws[i] = scans[i].w;
+      if (orientations) ori[i] = orientations[i] ? orientations[i] : exif::orientation(datas[i], sizes[i]);
+      hs[i] = ori[i] >= 5 ? scans[i].w : scans[i].h; ws[i] = ori[i] >= 5 ? scans[i].h : scans[i].w;
       readable[i] = 1;
     } catch (const Error& e) {
       refuse(i, e);
@@ -688,11 +707,21 @@ void jpeg_decode_batch_to_device(int n, const unsigned char* const* datas, const
   // 2. every readable file's region inside cap, before anything is queued
   for (int i = 0; i < n; ++i) {
     if (!readable[i]) continue;
-    const JpegScan& s = scans[i];
-    stride[i] = strides && strides[i] ? strides[i] : (long long)s.w * 3;
-    FFP_CHECK(offsets[i] >= 0 && stride[i] >= (long long)s.w * 3 && offsets[i] <= cap && stride[i] * (s.h - 1) + (long long)s.w * 3 <= cap - offsets[i], FFP_ERR_ARG,
-              "jpeg_decode_batch: image %d (%dx%d at offset %lld, row pitch %lld) does not lie inside the %lld bytes of the output", i, s.w, s.h, offsets[i], stride[i], cap);
+    const long long oh = hs[i], ow = ws[i];
+    stride[i] = strides && strides[i] ? strides[i] : ow * 3;
+    FFP_CHECK(offsets[i] >= 0 && stride[i] >= ow * 3 && offsets[i] <= cap && stride[i] * (oh - 1) + ow * 3 <= cap - offsets[i], FFP_ERR_ARG,
+              "jpeg_decode_batch: image %d (%lldx%lld at offset %lld, row pitch %lld) does not lie inside the %lld bytes of the output", i, ow, oh, offsets[i], stride[i], cap);
   }
+  // Borrowed by every call, allocated by the ones that turn a file, and sized for one sub-batch at a time: every sub-batch (and every host-decoded
+  // file) ends in a synchronisation, so the next one may lay the workspace out again, or let it grow.
+  WsPool<TurnWs>::Lease turn_lease = lease_ws(g_turn_pool, st);
+  DevBuf& turn_img = turn_lease->img;
+  // where file i is reconstructed, and the job that turns it into its region afterwards (both read the workspace as it is when they are called)
+  auto raw_out = [&](int i) { return ori[i] != 1 ? turn_img.as<unsigned char>() + turn_off[i] : d_base + offsets[i]; };
+  auto raw_stride = [&](int i) { return ori[i] != 1 ? (long long)scans[i].w * 3 : stride[i]; };
+  auto turn_job = [&](int i) {
+    return OrientJob{turn_img.as<unsigned char>() + turn_off[i], d_base + offsets[i], (long long)scans[i].w * 3, stride[i], scans[i].h, scans[i].w, ori[i]};
+  };
   // 3. the layout: every buffer of the device decoder is sized here, from header fields the planner has checked. Not an error of the file but a
   // limit of THIS decoder (the host decoder takes the file): 32-bit bit offsets (a scan + trailer of 256 MiB or more), six blocks per MCU
   std::vector<jbp::FileIn> in((size_t)n);
@@ -725,9 +754,13 @@ void jpeg_decode_batch_to_device(int n, const unsigned char* const* datas, const
       if ((size_t)S.coef_bytes > W.coef.n) W.coef.alloc((size_t)S.coef_bytes * 5 / 4);
       const Arenas A{static_cast<unsigned char*>(W.stage.p), W.up.as<unsigned char>(), W.work.as<unsigned char>(), W.coef.as<unsigned char>()};
       std::memset(A.hp, 0, (size_t)S.spec.off + (size_t)S.spec.bytes);          // the tables; the raw bytes behind them are copied in by fill_file
+      long long turn_bytes = 0;
+      for (int j = 0; j < m; ++j)
+        if (ori[S.files[j]] != 1) { turn_off[S.files[j]] = turn_bytes; turn_bytes += turn_slot(S.files[j]); }
+      if (turn_bytes > 0) turn_img.ensure((size_t)turn_bytes);
       for (int j = 0; j < m; ++j) {
         const int i = S.files[j];
-        fill_file(A, S, plan.files[i], j, scans[i], heads[i], datas[i] + heads[i].data_off, in[i].n_raw, d_base + offsets[i], stride[i]);
+        fill_file(A, S, plan.files[i], j, scans[i], heads[i], datas[i] + heads[i].data_off, in[i].n_raw, raw_out(i), raw_stride(i));
       }
       const BatchFile* dF = reinterpret_cast<const BatchFile*>(A.up + S.desc.off);
       const int* d_wg_file = reinterpret_cast<const int*>(A.up + S.wg_file.off);
@@ -799,7 +832,15 @@ void jpeg_decode_batch_to_device(int n, const unsigned char* const* datas, const
       jpeg_batch_reconstruct(reinterpret_cast<const JpegBatchIdct*>(A.up + S.idct.off), S.n_idct, S.n_idct_wg, reinterpret_cast<const JpegBatchColour*>(A.up + S.colour.off), m,
                              S.n_px_wg, bgr, st);
       k.launches += 2;
-      FFP_HIP(hipStreamSynchronize(st));
+      std::vector<OrientJob> jobs;
+      for (int j = 0; j < m; ++j)
+        if (ori[S.files[j]] != 1 && !to_host[S.files[j]]) jobs.push_back(turn_job(S.files[j]));
+      if (!jobs.empty()) {
+        orient_batch_device(jobs.data(), (int)jobs.size(), 3, st);               // one launch for the sub-batch's turned files; waits for the stream
+        k.launches += 1;
+      } else {
+        FFP_HIP(hipStreamSynchronize(st));
+      }
       k.syncs += 1;
       for (int j = 0; j < m; ++j)
         if (!to_host[S.files[j]]) g_stat_device.fetch_add(1);
@@ -810,7 +851,13 @@ void jpeg_decode_batch_to_device(int n, const unsigned char* const* datas, const
     if (!to_host[i]) continue;
     if (!host_only) g_stat_fallback.fetch_add(1);
     try {
-      host_decode_one(datas[i], sizes[i], scans[i], d_base + offsets[i], stride[i], bgr, st, k);
+      if (ori[i] != 1) { turn_off[i] = 0; turn_img.ensure((size_t)turn_slot(i)); }
+      host_decode_one(datas[i], sizes[i], scans[i], raw_out(i), raw_stride(i), bgr, st, k);
+      if (ori[i] != 1) {
+        const OrientJob job = turn_job(i);
+        orient_batch_device(&job, 1, 3, st);
+        k.launches += 1; k.syncs += 1;
+      }
       status[i] = 1;
     } catch (const Error& e) {
       refuse(i, e);

@@ -398,6 +398,27 @@ int ffp_jpeg_decode_batch(int device, int n, const uint8_t* const* datas, const 
                           uint8_t* const* outs, const int64_t* caps, int32_t* hs, int32_t* ws, int32_t* status);
 int ffp_jpeg_decode_batch_stats(int64_t* batches, int64_t* launches_last_batch, int64_t* syncs_last_batch);
 
+/* The EXIF orientation, applied where the pixels already are. The reference applies the tag on every read: cv2.imread does
+ * (/root/reference/utils/visualization.py:95,198, utils/enhancer.py:254, every app), and so does read_image_as_pil(..., exif_fix=True) behind
+ * get_sliced_prediction (sahi/predict.py:608). ffp_exif_orientation finds the tag in a file's bytes (csrc/exif.hpp; host only, no device): a
+ * JPEG's first APP1 segment that starts with "Exif\0\0" in front of SOS, or a PNG's first eXIf chunk, holds a TIFF header ("II" / "MM", 42, the
+ * offset of IFD0) and IFD0, whose entry 0x0112 (SHORT or LONG, count 1) is the value. *orientation is 1..8; everything that is not a well-formed
+ * tag gives 1 (as stored): no tag, a value outside 1..8, a truncated segment, an IFD offset or entry count that leaves the segment, a file that is
+ * neither kind. Nothing outside data[0 .. n) is read. FFP_ERR_ARG only for a null argument.
+ * ffp_jpeg_decode_oriented / _oriented_dev / _batch_oriented_dev are ffp_jpeg_decode / _dev / _batch_dev with an orientation per file: 0 (or a
+ * null `orientations` array) the file's own tag, 1..8 that value, anything else FFP_ERR_ARG. It is one decoding routine: a file of orientation
+ * 2..8 is reconstructed into a pooled workspace image and turned into its region by the orient kernel below — at most ONE more launch per
+ * sub-batch, whatever n is, none when every file is 1 (such a batch queues exactly what ffp_jpeg_decode_batch_dev queues), and
+ * ffp_jpeg_decode_batch_stats counts it. row_stride / strides, cap, *out_h / *out_w, hs and ws describe the ORIENTED image (for 5..8 the file's
+ * width is the image's height). The rest of the contract holds unchanged: a file that is not decoded leaves its region untouched. */
+int ffp_exif_orientation(const uint8_t* data, int64_t n, int32_t* orientation);
+int ffp_jpeg_decode_oriented(int device, const uint8_t* data, int64_t n, int bgr, int orientation, uint8_t* out, int64_t cap, int32_t* out_h, int32_t* out_w);
+int ffp_jpeg_decode_oriented_dev(int device, const uint8_t* data, int64_t n, int bgr, int orientation, uint8_t* d_out, int64_t row_stride, int64_t cap,
+                                 int32_t* out_h, int32_t* out_w);
+int ffp_jpeg_decode_batch_oriented_dev(int device, int n, const uint8_t* const* datas, const int64_t* sizes, int bgr, const int32_t* orientations,
+                                       uint8_t* d_base, const int64_t* offsets, const int64_t* strides, int64_t cap,
+                                       int32_t* hs, int32_t* ws, int32_t* status);
+
 /* ---------------------------------------------------------------------------------------------------------
  * PNG at the file boundaries (written and read on the device; palette, sub-byte, gray+alpha and interlaced files stay with the host)
  * ------------------------------------------------------------------------------------------------------- */
@@ -484,6 +505,32 @@ int ffp_overlay_draw_dev(int device, uint8_t* d_img, int h, int w, int64_t row_s
                          int64_t mask_bytes);
 int ffp_overlay_draw(int device, uint8_t* img, int h, int w, int64_t row_stride, const ffp_overlay_prim* prims, int n, const uint8_t* masks,
                      int64_t mask_bytes);
+
+/* Replaces what cv2.imread does with the EXIF orientation after decoding (/root/reference/utils/visualization.py:95,198, utils/enhancer.py:254)
+ * and ImageOps.exif_transpose inside read_image_as_pil (sahi/predict.py:608) on an image that stays in device memory (csrc/orient.hip): the
+ * h x w image of px (1, 3 or 4) bytes per pixel at d_src (row pitch src_stride bytes) is written to d_dst (row pitch dst_stride) with
+ * orientation 1 as stored (a pitched copy), 2 mirrored in x, 3 in both, 4 in y, 5 transposed, 6 transposed then mirrored in x, 7 then in both,
+ * 8 then in y; for 5..8 the destination is w x h. Both bases may have any byte alignment; bytes between a row's w' * px and the pitch are never
+ * written. Out of place. FFP_ERR_ARG before anything is queued, the destination untouched: source and destination byte ranges that overlap, an
+ * orientation outside 1..8, px other than 1, 3, 4, a pitch smaller than a row, cap (the bytes there are from d_dst on) smaller than
+ * (h' - 1) * dst_stride + w' * px. ffp_image_orient_batch_dev: n images in ONE launch, image i hs[i] x ws[i] at d_src_base + src_offsets[i]
+ * to d_dst_base + dst_offsets[i] (cap: the bytes from d_dst_base on; a destination that overlaps another destination or ANY image's source is
+ * FFP_ERR_ARG as well).
+ * ffp_image_orient: the same through host memory (up, turned, down), for tests and small callers. ffp_image_orient_geometry: test hook, the side
+ * in pixels of the square tile one workgroup moves. ffp_image_orient_stats: images turned and launches queued since the library was loaded
+ * (the turned files of ffp_jpeg_decode_*oriented* count too). */
+int ffp_image_orient_dev(int device, const uint8_t* d_src, int h, int w, int px, int64_t src_stride, int orientation, uint8_t* d_dst, int64_t dst_stride,
+                         int64_t cap);
+int ffp_image_orient_batch_dev(int device, int n, const uint8_t* d_src_base, const int64_t* src_offsets, const int32_t* hs, const int32_t* ws, int px,
+                               const int64_t* src_strides, const int32_t* orientations, uint8_t* d_dst_base, const int64_t* dst_offsets,
+                               const int64_t* dst_strides, int64_t cap);
+int ffp_image_orient(int device, const uint8_t* src, int h, int w, int px, int64_t src_stride, int orientation, uint8_t* dst, int64_t dst_stride, int64_t cap);
+/* Measurement hook (tools/orient_probe.py): `iters` (1..10000; a few hundred make a window of several milliseconds) launches of the kernel on one packed image between two events, then as many
+ * device-to-device copies of the same h * w * px bytes between two more; microseconds per launch and per copy. d_dst holds the copy afterwards. */
+int ffp_image_orient_time_dev(int device, const uint8_t* d_src, int h, int w, int px, int orientation, uint8_t* d_dst, int64_t cap, int iters, float* kernel_us,
+                              float* copy_us);
+int ffp_image_orient_geometry(int32_t* tile);
+int ffp_image_orient_stats(int64_t* images, int64_t* launches);
 
 /* 1x1 conv over the virtual concat [nearest_x2(coarse) | fine] (the YOLO neck's Upsample + Concat + C3k2.cv1 without
  * materialising the upsampled tensor: /root/reference's model graph via ultralytics' yolo11-pose.yaml layers 11-13 and 14-16).
