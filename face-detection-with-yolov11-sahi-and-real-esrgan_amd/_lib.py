@@ -12,7 +12,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import weights_io
+from . import _abi, weights_io
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # FFP_LIB=<path> loads a DIAGNOSTIC build instead (build.build_variant: in-kernel stamps, phase-skip instantiations). Probe scripts set it;
@@ -42,230 +42,18 @@ def _p(t):
     return C.POINTER(t)
 
 
-_SIGS = {
-    "ffp_last_error": (C.c_char_p, []),
-    "ffp_version": (C.c_int, []),
-    "ffp_device_count": (C.c_int, [_p(C.c_int)]),
-    "ffp_switches": (C.c_int, [C.c_char_p, C.c_size_t]),
-    "ffp_slice_bboxes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _p(C.c_int32), C.c_int, _p(C.c_int32)]),
-    "ffp_tile_chunks": (C.c_int, [C.c_int, C.c_int, _p(C.c_int32), C.c_int, _p(C.c_int32)]),
-    "ffp_letterbox_geometry": (C.c_int, [C.c_int, C.c_int, C.c_int, _p(C.c_int32)]),
-    "ffp_det_create": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_void_p)]),
-    "ffp_det_destroy": (None, [C.c_void_p]),
-    "ffp_det_infer_tiles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _p(C.c_int32), C.c_int, C.c_int, C.c_float,
-                                      C.c_float, C.c_int, C.c_int, _p(C.c_float), _p(C.c_int32)]),
-    "ffp_det_infer_tiles_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _p(C.c_int32), C.c_int, C.c_int, C.c_float,
-                                          C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    "ffp_det_truncate_shift_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
-    "ffp_det_forward_raw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _p(C.c_int32), C.c_int, C.c_int, _p(C.c_float),
-                                      C.c_size_t, _p(C.c_int32)]),
-    "ffp_merge": (C.c_int, [C.c_int, _p(C.c_float), C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _p(C.c_float), _p(C.c_int32),
-                            _p(C.c_int32)]),
-    "ffp_merge_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p,
-                                C.c_int, C.c_void_p]),
-    "ffp_sliced_predict": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int,
-                                     C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _p(C.c_float),
-                                     C.c_int, _p(C.c_int32)]),
-    "ffp_det_stage_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int,
-                                    C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                    _p(C.c_int32), _p(C.c_int32)]),
-    "ffp_det_last_ms": (C.c_int, [C.c_void_p, C.c_int, _p(C.c_float)]),
-    "ffp_det_last_conv_stats": (C.c_int, [C.c_void_p, _p(C.c_double), _p(C.c_float), _p(C.c_int32)]),
-    "ffp_det_set_profile": (C.c_int, [C.c_void_p, C.c_int]),
-    "ffp_det_profile_count": (C.c_int, [C.c_void_p, _p(C.c_int32)]),
-    "ffp_det_profile_get": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_int, _p(C.c_double), _p(C.c_float), _p(C.c_int32)]),
-    "ffp_det_profile_detail": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_int, _p(C.c_double), _p(C.c_float)]),
-    "ffp_sr_profile_detail": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_int, _p(C.c_double), _p(C.c_float)]),
-    "ffp_sr_create": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_void_p)]),
-    "ffp_sr_destroy": (None, [C.c_void_p]),
-    "ffp_sr_enhance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "ffp_sr_enhance_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                    C.c_int, C.c_int, C.c_void_p]),
-    "ffp_sr_enhance_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "ffp_sr_enhance_batch": (C.c_int, [C.c_void_p, C.c_int, _p(C.c_void_p), _p(C.c_int32), _p(C.c_int32), C.c_int, C.c_int, C.c_int,
-                                       _p(C.c_void_p)]),
-    "ffp_sr_enhance_crops_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _p(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                           C.c_size_t, _p(C.c_int64)]),
-    "ffp_sr_enhance_crops_dev_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _p(C.c_int32), C.c_int, C.c_int, C.c_int,
-                                                 C.c_void_p, C.c_size_t, _p(C.c_int64)]),
-    "ffp_sr_wait": (C.c_int, [C.c_void_p]),
-    "ffp_sr_enhance_crops_multi_dev_async": (C.c_int, [C.c_void_p, C.c_int, _p(C.c_void_p), _p(C.c_int32), C.c_int, C.c_int, _p(C.c_int32),
-                                                       C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, _p(C.c_int64)]),
-    "ffp_sr_plan_state": (C.c_int, [C.c_void_p, _p(C.c_int32), _p(C.c_int32)]),
-    "ffp_det_graph_status": (C.c_int, [C.c_void_p, _p(C.c_int32)]),
-    "ffp_sr_set_fused_body": (C.c_int, [C.c_void_p, C.c_int]),
-    "ffp_det_drop_plans": (C.c_int, [C.c_void_p]),
-    "ffp_sr_drop_plans": (C.c_int, [C.c_void_p]),
-    "ffp_det_profile_bytes": (C.c_int, [C.c_void_p, C.c_int, _p(C.c_double)]),
-    "ffp_sr_profile_bytes": (C.c_int, [C.c_void_p, C.c_int, _p(C.c_double)]),
-    "ffp_conv_totals_enable": (C.c_int, [C.c_int]),
-    "ffp_conv_totals_count": (C.c_int, [_p(C.c_int32)]),
-    "ffp_conv_totals_get": (C.c_int, [C.c_int, C.c_char_p, C.c_int, _p(C.c_double), _p(C.c_double), _p(C.c_int64)]),
-    "ffp_sr_mem_bytes": (C.c_int, [C.c_void_p, _p(C.c_uint64), _p(C.c_uint64), _p(C.c_int32)]),
-    "ffp_det_mem_bytes": (C.c_int, [C.c_void_p, _p(C.c_uint64), _p(C.c_uint64), _p(C.c_int32)]),
-    "ffp_det_set_lanes": (C.c_int, [C.c_void_p, C.c_int]),
-    "ffp_det_set_buffer_reuse": (C.c_int, [C.c_void_p, C.c_int]),
-    "ffp_det_set_gate": (C.c_int, [C.c_void_p, C.c_int]),
-    "ffp_det_last_active": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
-    "ffp_det_mem_detail": (C.c_int, [C.c_void_p, _p(C.c_uint64), _p(C.c_uint64), _p(C.c_uint64)]),
-    "ffp_det_fill_steps": (C.c_int, [C.c_void_p, _p(C.c_int32), _p(C.c_int32)]),
-    "ffp_det_stream_wait_event": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "ffp_sr_last_ms": (C.c_int, [C.c_void_p, _p(C.c_float)]),
-    "ffp_sr_last_conv_stats": (C.c_int, [C.c_void_p, _p(C.c_double), _p(C.c_float), _p(C.c_int32)]),
-    "ffp_sr_set_profile": (C.c_int, [C.c_void_p, C.c_int]),
-    "ffp_sr_profile_count": (C.c_int, [C.c_void_p, _p(C.c_int32)]),
-    "ffp_sr_profile_get": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_int, _p(C.c_double), _p(C.c_float), _p(C.c_int32)]),
-    "ffp_eval_wider_pr": (C.c_int, [C.c_int, _p(C.c_double), _p(C.c_int64), _p(C.c_double), _p(C.c_int64), _p(C.c_uint8), C.c_int, C.c_double, C.c_int,
-                                    _p(C.c_int64)]),
-    "ffp_eval_dual_match": (C.c_int, [C.c_int, _p(C.c_double), _p(C.c_int64), _p(C.c_double), _p(C.c_int64), _p(C.c_uint8), C.c_int, C.c_double, _p(C.c_int32)]),
-    "ffp_eval_coco_bbox": (C.c_int, [C.c_int, C.c_int, C.c_int, _p(C.c_double), _p(C.c_int64), _p(C.c_double), _p(C.c_int64), _p(C.c_double), C.c_int,
-                                     _p(C.c_double), C.c_int, _p(C.c_double), C.c_int, _p(C.c_int32), C.c_int, _p(C.c_double), _p(C.c_double),
-                                     _p(C.c_double), _p(C.c_double), _p(C.c_uint8), _p(C.c_double), _p(C.c_uint8)]),
-    "ffp_jpeg_encode": (C.c_int, [C.c_int, _p(C.c_uint8), C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_uint8), C.c_int64, _p(C.c_int64)]),
-    "ffp_jpeg_encode_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _p(C.c_uint8), C.c_int64, _p(C.c_int64)]),
-    "ffp_jpeg_encode_batch_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, _p(C.c_int64), _p(C.c_int32), _p(C.c_int32), _p(C.c_int64), C.c_int, C.c_int, _p(C.c_uint8),
-                                            C.c_int64, _p(C.c_int64)]),
-    "ffp_png_bound": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
-    "ffp_png_segment_bytes": (C.c_int, []),
-    "ffp_png_encode": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_uint8), C.c_int64, _p(C.c_int64)]),
-    "ffp_png_encode_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _p(C.c_uint8), C.c_int64, _p(C.c_int64)]),
-    "ffp_png_encode_batch_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, _p(C.c_int64), _p(C.c_int32), _p(C.c_int32), _p(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_int,
-                                           _p(C.c_uint8), C.c_int64, _p(C.c_int64)]),
-    "ffp_jpeg_info": (C.c_int, [_p(C.c_uint8), C.c_int64, _p(C.c_int32), _p(C.c_int32), _p(C.c_int32)]),
-    "ffp_jpeg_decode": (C.c_int, [C.c_int, _p(C.c_uint8), C.c_int64, C.c_int, _p(C.c_uint8), C.c_int64]),
-    "ffp_jpeg_decode_dev": (C.c_int, [C.c_int, _p(C.c_uint8), C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int64]),
-    "ffp_jpeg_decode_stats": (C.c_int, [_p(C.c_int64), _p(C.c_int64), _p(C.c_int64)]),
-    "ffp_jpeg_decode_batch_dev": (C.c_int, [C.c_int, C.c_int, _p(C.c_void_p), _p(C.c_int64), C.c_int, C.c_void_p, _p(C.c_int64), _p(C.c_int64), C.c_int64,
-                                            _p(C.c_int32), _p(C.c_int32), _p(C.c_int32)]),
-    "ffp_jpeg_decode_batch": (C.c_int, [C.c_int, C.c_int, _p(C.c_void_p), _p(C.c_int64), C.c_int, _p(C.c_void_p), _p(C.c_int64), _p(C.c_int32), _p(C.c_int32),
-                                        _p(C.c_int32)]),
-    "ffp_jpeg_decode_batch_stats": (C.c_int, [_p(C.c_int64), _p(C.c_int64), _p(C.c_int64)]),
-    "ffp_exif_orientation": (C.c_int, [_p(C.c_uint8), C.c_int64, _p(C.c_int32)]),
-    "ffp_jpeg_decode_oriented": (C.c_int, [C.c_int, _p(C.c_uint8), C.c_int64, C.c_int, C.c_int, _p(C.c_uint8), C.c_int64, _p(C.c_int32), _p(C.c_int32)]),
-    "ffp_jpeg_decode_oriented_dev": (C.c_int, [C.c_int, _p(C.c_uint8), C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, _p(C.c_int32), _p(C.c_int32)]),
-    "ffp_jpeg_decode_batch_oriented_dev": (C.c_int, [C.c_int, C.c_int, _p(C.c_void_p), _p(C.c_int64), C.c_int, _p(C.c_int32), C.c_void_p, _p(C.c_int64), _p(C.c_int64),
-                                                     C.c_int64, _p(C.c_int32), _p(C.c_int32), _p(C.c_int32)]),
-    "ffp_image_orient_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int64]),
-    "ffp_image_orient": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int64]),
-    "ffp_image_orient_batch_dev": (C.c_int, [C.c_int, C.c_int, C.c_void_p, _p(C.c_int64), _p(C.c_int32), _p(C.c_int32), C.c_int, _p(C.c_int64), _p(C.c_int32), C.c_void_p,
-                                             _p(C.c_int64), _p(C.c_int64), C.c_int64]),
-    "ffp_image_orient_time_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int, _p(C.c_float), _p(C.c_float)]),
-    "ffp_image_orient_geometry": (C.c_int, [_p(C.c_int32)]),
-    "ffp_image_orient_stats": (C.c_int, [_p(C.c_int64), _p(C.c_int64)]),
-    "ffp_png_info": (C.c_int, [_p(C.c_uint8), C.c_int64, _p(C.c_int32), _p(C.c_int32), _p(C.c_int32), _p(C.c_int32)]),
-    "ffp_png_decode": (C.c_int, [C.c_int, _p(C.c_uint8), C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int64]),
-    "ffp_png_decode_dev": (C.c_int, [C.c_int, _p(C.c_uint8), C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64]),
-    "ffp_png_decode_stats": (C.c_int, [_p(C.c_int64), _p(C.c_int64)]),
-    "ffp_png_unfilter_geometry": (C.c_int, [_p(C.c_int32), _p(C.c_int32)]),
-    "ffp_op_conv2d_shape": (C.c_int, [C.c_int]),
-    "ffp_op_conv2d_shape_name": (C.c_int, [C.c_int, C.c_char_p, C.c_int]),
-    "ffp_op_conv2d_last_variant": (C.c_int, [C.c_char_p, C.c_int]),
-    "ffp_op_conv2d_act_post": (C.c_int, [C.c_int]),
-    "ffp_op_conv1x1_up2": (C.c_int, [C.c_int, C.c_int, _p(C.c_float), _p(C.c_float), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_float),
-                                     _p(C.c_float), C.c_int, C.c_int, _p(C.c_float)]),
-    "ffp_op_conv2d_time": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                     C.c_int, _p(C.c_float)]),
-    "ffp_op_conv2d": (C.c_int, [C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_float), _p(C.c_float), C.c_int,
-                                C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_float), C.c_float, _p(C.c_float)]),
-    "ffp_op_variant": (C.c_int, [C.c_int, C.c_int]),
-    "ffp_op_cls_tower_variant": (C.c_int, [C.c_int, C.c_int]),
-    "ffp_op_sppf_pool": (C.c_int, [C.c_int, C.c_int, C.c_int, _p(C.c_int32), _p(C.c_int32), C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int,
-                                   _p(C.c_float), C.c_int, C.c_int, C.c_int, C.c_int]),
-    "ffp_op_upsample2x": (C.c_int, [C.c_int, C.c_int, C.c_int, _p(C.c_int32), _p(C.c_int32), C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int,
-                                    _p(C.c_float), C.c_int, C.c_int]),
-    "ffp_op_psa_attention": (C.c_int, [C.c_int, C.c_int, C.c_int, _p(C.c_int32), _p(C.c_int32), C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int,
-                                       _p(C.c_float), C.c_int, C.c_int]),
-    "ffp_op_dwconv3x3": (C.c_int, [C.c_int, C.c_int, C.c_int, _p(C.c_int32), _p(C.c_int32), C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int,
-                                   C.c_int, C.c_int, C.c_int, _p(C.c_float), _p(C.c_float), C.c_int, _p(C.c_float), C.c_int, C.c_int,
-                                   _p(C.c_float), C.c_int, C.c_int]),
-    "ffp_op_cls_tower": (C.c_int, [C.c_int, C.c_int, _p(C.c_int32), _p(C.c_int32), C.c_int, C.c_int, C.c_int] + [_p(C.c_float)] * 13 + [C.c_int, C.c_int, _p(C.c_int64)]),
-    "ffp_op_conv2d_views": (C.c_int, [C.c_int, C.c_int, C.c_int, _p(C.c_int32), _p(C.c_int32), C.c_int, _p(C.c_float), C.c_int, C.c_int, C.c_int,
-                                      _p(C.c_float), _p(C.c_float), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_float), C.c_int,
-                                      C.c_int, C.c_float, _p(C.c_float), C.c_int, C.c_int, C.c_float, _p(C.c_float), C.c_int, C.c_int, C.c_int,
-                                      _p(C.c_uint32), _p(C.c_int32), _p(C.c_int32), _p(C.c_int64)]),
-    "ffp_op_det_post": (C.c_int, [C.c_int, C.c_int, _p(C.c_int32), _p(C.c_int32), C.c_int, C.c_int, C.c_int, _p(C.c_float), _p(C.c_float),
-                                  _p(C.c_float), _p(C.c_float), _p(C.c_int32), C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                  _p(C.c_float), _p(C.c_float), _p(C.c_int32)]),
-    "ffp_op_rt_topk": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, _p(C.c_int32)]),
-    "ffp_op_rt_dwconv": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, _p(C.c_float), _p(C.c_float), _p(C.c_float), C.c_int, C.c_int, _p(C.c_uint32)]),
-    "ffp_op_rt_maxpool2": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, _p(C.c_uint32)]),
-    "ffp_op_rt_add": (C.c_int, [C.c_int, C.c_longlong, C.c_int, _p(C.c_float), C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, C.c_longlong, _p(C.c_float), C.c_int, C.c_int, _p(C.c_uint32)]),
-    "ffp_op_rt_layernorm": (C.c_int, [C.c_int, C.c_longlong, _p(C.c_float), C.c_int, C.c_int, _p(C.c_float), _p(C.c_float), _p(C.c_float), C.c_int, C.c_int, _p(C.c_uint32)]),
-    "ffp_op_rt_gelu": (C.c_int, [C.c_int, C.c_longlong, C.c_int, _p(C.c_float), C.c_int, C.c_int, _p(C.c_uint32)]),
-    "ffp_op_rt_attention": (C.c_int, [C.c_int, C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, _p(C.c_uint32)]),
-    "ffp_op_rt_enc_prep": (C.c_int, [C.c_int, C.c_int, _p(C.c_int32), _p(C.c_int32), _p(C.c_float), _p(C.c_float), _p(C.c_float), _p(C.c_int32), _p(C.c_int32), _p(C.c_float), C.c_longlong, _p(C.c_float), _p(C.c_float), _p(C.c_uint32), _p(C.c_uint32)]),
-    "ffp_op_rt_gather": (C.c_int, [C.c_int, C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, _p(C.c_int32), _p(C.c_float), _p(C.c_float), C.c_int, C.c_int, _p(C.c_float), _p(C.c_uint32)]),
-    "ffp_op_rt_ref": (C.c_int, [C.c_int, C.c_longlong, _p(C.c_float), C.c_int, C.c_int, _p(C.c_float), _p(C.c_float), C.c_int, C.c_int, _p(C.c_uint32)]),
-    "ffp_op_rt_deform": (C.c_int, [C.c_int, C.c_int, _p(C.c_int32), _p(C.c_int32), _p(C.c_float), C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, _p(C.c_uint32)]),
-    "ffp_op_rt_decode": (C.c_int, [C.c_int, C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, C.c_float, _p(C.c_float), _p(C.c_float), _p(C.c_float), _p(C.c_int32)]),
-    "ffp_op_rt_post_tiles": (C.c_int, [C.c_int, C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, C.c_float, _p(C.c_int32), C.c_int, C.c_int, C.c_int, _p(C.c_float), _p(C.c_int32)]),
-    "ffp_op_scrfd_pool": (C.c_int, [C.c_int, C.c_int, _p(C.c_int32), _p(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int, _p(C.c_float), C.c_int, C.c_int]),
-    "ffp_op_scrfd_post": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_int32), C.c_int, _p(_p(C.c_float)), _p(C.c_int32), _p(C.c_int32), _p(C.c_float), C.c_float, C.c_float, C.c_int, _p(C.c_float), _p(C.c_int32), _p(C.c_float)]),
-    "ffp_op_resize_lanczos4": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "ffp_op_image_input": (C.c_int, [C.c_int, C.c_int, C.c_int, _p(C.c_uint8), C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_int32), C.c_int, C.c_int,
-                                     _p(C.c_float), _p(C.c_int32), _p(C.c_int32)]),
-    "ffp_op_stem": (C.c_int, [C.c_int, C.c_int, C.c_int, _p(C.c_uint8), C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_int32), C.c_int, _p(C.c_float),
-                              _p(C.c_float), C.c_int, C.c_int, C.c_int, _p(C.c_float)]),
-    "ffp_op_stem_conv": (C.c_int, [C.c_int, _p(C.c_uint8), C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_int32), C.c_int, _p(C.c_float), _p(C.c_float),
-                                   C.c_int, _p(C.c_float), _p(C.c_float), _p(C.c_float)]),
-    "ffp_op_sr_tiles": (C.c_int, [C.c_int, _p(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_int32), _p(C.c_int32),
-                                  _p(C.c_int32), _p(C.c_int32)]),
-    "ffp_op_sr_pre": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, _p(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                _p(C.c_int64), C.c_void_p, C.c_size_t, _p(C.c_int64)]),
-    "ffp_op_sr_post": (C.c_int, [C.c_int, C.c_int, _p(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                 _p(C.c_int64), C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
-    "ffp_op_alpha_linear": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "ffp_op_crop_gather": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, _p(C.c_int32), _p(C.c_int64), C.c_void_p, C.c_size_t]),
-    "ffp_scrfd_create": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, _p(C.c_void_p)]),
-    "ffp_scrfd_destroy": (None, [C.c_void_p]),
-    "ffp_scrfd_describe": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
-    "ffp_scrfd_infer_tiles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _p(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_float,
-                                        C.c_float, _p(C.c_float), C.c_int, _p(C.c_int32)]),
-    "ffp_scrfd_infer_tiles_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _p(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_float,
-                                           C.c_float, C.c_float, C.c_int, C.c_int, _p(C.c_float), C.c_int, _p(C.c_int32)]),
-    "ffp_scrfd_infer_tiles_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _p(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_float,
-                                            C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
-    "ffp_scrfd_sliced_predict": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int,
-                                           C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
-                                           _p(C.c_float), C.c_int, _p(C.c_int32)]),
-    "ffp_scrfd_sliced_predict_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int,
-                                               C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
-                                               C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
-    "ffp_scrfd_mem_bytes": (C.c_int, [C.c_void_p, _p(C.c_uint64), _p(C.c_int32)]),
-    "ffp_scrfd_drop_plans": (C.c_int, [C.c_void_p]),
-    "ffp_op_scrfd_sahi_rows": (C.c_int, [C.c_int, C.c_int, C.c_int, _p(C.c_int32), C.c_int, C.c_int, C.c_float, _p(C.c_float), _p(C.c_int32),
-                                         _p(C.c_int32)]),
-    "ffp_scrfd_forward_raw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _p(C.c_int32), C.c_int, C.c_int, C.c_int, _p(C.c_float),
-                                        C.c_size_t, _p(C.c_int64)]),
-    "ffp_scrfd_info": (C.c_int, [C.c_void_p, _p(C.c_int32), _p(C.c_double)]),
-    "ffp_scrfd_geometry": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_int32), _p(C.c_float)]),
-    "ffp_rtdetr_create": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, _p(C.c_void_p)]),
-    "ffp_rtdetr_destroy": (None, [C.c_void_p]),
-    "ffp_rtdetr_predict": (C.c_int, [C.c_void_p, _p(C.c_void_p), _p(C.c_int32), C.c_int, C.c_int, C.c_float, _p(C.c_float), _p(C.c_int32)]),
-    "ffp_rtdetr_forward_raw": (C.c_int, [C.c_void_p, _p(C.c_void_p), _p(C.c_int32), C.c_int, C.c_int, _p(C.c_float), _p(C.c_int32)]),
-    "ffp_rtdetr_infer_tiles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _p(C.c_int32), C.c_int, C.c_int, C.c_float, C.c_int, C.c_int,
-                                         _p(C.c_float), _p(C.c_int32)]),
-    "ffp_rtdetr_infer_tiles_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _p(C.c_int32), C.c_int, C.c_int, C.c_float, C.c_int,
-                                             C.c_int, C.c_void_p, C.c_void_p]),
-    "ffp_rtdetr_sliced_predict": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int,
-                                            C.c_float, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _p(C.c_float), C.c_int, _p(C.c_int32)]),
-    "ffp_rtdetr_mem_bytes": (C.c_int, [C.c_void_p, _p(C.c_uint64), _p(C.c_int32)]),
-    "ffp_rtdetr_drop_plans": (C.c_int, [C.c_void_p]),
-    "ffp_rtdetr_info": (C.c_int, [C.c_void_p, _p(C.c_int32), _p(C.c_double), _p(C.c_int32)]),
-    "ffp_rtdetr_set_profile": (C.c_int, [C.c_void_p, C.c_int]),
-    "ffp_rtdetr_profile_count": (C.c_int, [C.c_void_p, _p(C.c_int32)]),
-    "ffp_rtdetr_profile_get": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_int, _p(C.c_float)]),
-    "ffp_iqa_create": (C.c_int, [C.c_int, _p(C.c_void_p)]),
-    "ffp_iqa_destroy": (None, [C.c_void_p]),
-    "ffp_iqa_niqe_blocks": (C.c_int, [C.c_int, C.c_int, _p(C.c_int64)]),
-    "ffp_iqa_niqe_features": (C.c_int, [C.c_void_p, C.c_int, _p(C.c_void_p), _p(C.c_int32), _p(C.c_int32), _p(C.c_int32), C.c_int, C.c_int, C.c_int,
-                                        _p(C.c_double), _p(C.c_double), C.c_int64, _p(C.c_int64)]),
-    "ffp_iqa_niqe_luma": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p(C.c_float)]),
-    "ffp_iqa_niqe_score": (C.c_int, [_p(C.c_double), _p(C.c_int64), C.c_int, _p(C.c_double), _p(C.c_double), _p(C.c_double)]),
-    "ffp_overlay_draw_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),
-    "ffp_overlay_draw": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),
-}
+HEADER_PATH = os.path.join(_HERE, "..", "include", "ffp.h")
 
+
+def _load_sigs() -> dict:
+    """{name: (restype, [argtypes])} of every entry include/ffp.h declares (_abi.parse): the header is the only declaration."""
+    if not os.path.exists(HEADER_PATH):
+        raise RuntimeError(f"{HEADER_PATH} is missing: the ctypes signatures of libffp.so are read from it, so it travels with the package.")
+    with open(HEADER_PATH, encoding="utf-8") as f:
+        return _abi.parse(f.read())
+
+
+_SIGS = _load_sigs()
 EXPORTED_SYMBOLS = tuple(_SIGS)
 
 
@@ -326,12 +114,12 @@ def switches() -> dict:
     return out
 
 
-def _fp(a: np.ndarray):
-    return a.ctypes.data_as(_p(C.c_float))
+def _ptr_to(ctype):
+    """array -> POINTER(ctype) at its first element; None stays None (a NULL argument)."""
+    return lambda a: None if a is None else a.ctypes.data_as(_p(ctype))
 
 
-def _ip(a: np.ndarray):
-    return a.ctypes.data_as(_p(C.c_int32))
+_fp, _ip, _up, _u8p, _i64p = (_ptr_to(t) for t in (C.c_float, C.c_int32, C.c_uint32, C.c_uint8, C.c_int64))
 
 
 def slice_bboxes(H: int, W: int, slice_h: int, slice_w: int, overlap_h: float = 0.2, overlap_w: float = 0.2) -> np.ndarray:
@@ -391,8 +179,27 @@ def scrfd_geometry(h: int, w: int, net_w: int, net_h: int) -> Tuple[int, int, fl
     return int(o[0]), int(o[1]), float(s.value)
 
 
-class FaceDetector:
+class _Handle:
+    """Owner of one library handle (self._h, a c_void_p): close() destroys it once, through the entry the subclass names in _DESTROY."""
+
+    _DESTROY = ""
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            getattr(lib(), self._DESTROY)(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class FaceDetector(_Handle):
     """InsightFace's SCRFD face detector (an ONNX file of a model pack, e.g. buffalo_l/det_10g.onnx) on one GPU (ffp_scrfd_*)."""
+
+    _DESTROY = "ffp_scrfd_destroy"
 
     STRIDE = 21          # FFP_DET_STRIDE(5)
 
@@ -407,17 +214,6 @@ class FaceDetector:
         n_out = C.c_int32(0)
         _check(lib().ffp_scrfd_info(self._h, C.byref(n_out), None))
         self.n_outputs = int(n_out.value)
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            lib().ffp_scrfd_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def last_conv_flops(self) -> float:
         f = C.c_double(0)
@@ -530,9 +326,11 @@ class FaceDetector:
         return res
 
 
-class RTDETRDetector:
+class RTDETRDetector(_Handle):
     """Ultralytics RT-DETR-l (rtdetr-l.yaml) on one GPU (ffp_rtdetr_*): FFPW weights from weights_io.from_ultralytics_rtdetr_state_dict
     (or synth.rtdetr_l_weights), a path to them, or the tensors as a dict."""
+
+    _DESTROY = "ffp_rtdetr_destroy"
 
     NQ = 300
 
@@ -545,17 +343,6 @@ class RTDETRDetector:
         nc = C.c_int32(0)
         _check(lib().ffp_rtdetr_info(self._h, C.byref(nc), None, None))
         self.nc = int(nc.value)
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            lib().ffp_rtdetr_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def info(self) -> dict:
         f, g = C.c_double(0), C.c_int32(0)
@@ -643,8 +430,10 @@ class RTDETRDetector:
         _check(lib().ffp_rtdetr_drop_plans(self._h))
 
 
-class Detector:
+class Detector(_Handle):
     """YOLO11{n,s,m,l}-pose on one GPU (ffp_det_*); `arch` is the scale ("n", "s", "m" or "l", see arch.yolo11_scale_of)."""
+
+    _DESTROY = "ffp_det_destroy"
 
     def __init__(self, weights, arch: str = "s", nc: int = 1, nkpt: int = 5, device: int = 0, precision: int = PREC_F32):
         buf = _weights_bytes(weights)
@@ -660,17 +449,6 @@ class Detector:
     @property
     def handle(self):
         return self._h
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            lib().ffp_det_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def infer_tiles(self, frame: np.ndarray, tiles: Sequence[Sequence[int]], imgsz: int, conf: float, iou: float = 0.7,
                     max_det: int = 300, chan_order: int = CHAN_AS_BGR, round_boxes: bool = False) -> List[np.ndarray]:
@@ -854,8 +632,10 @@ def merge(rows: np.ndarray, pp_type: str = "GREEDYNMM", metric: str = "IOS", thr
     return out[:k.value].copy(), src[:k.value].copy()
 
 
-class Enhancer:
+class Enhancer(_Handle):
     """Real-ESRGAN RRDBNet on one GPU (ffp_sr_*)."""
+
+    _DESTROY = "ffp_sr_destroy"
 
     def __init__(self, weights, scale: int = 4, num_block: int = 23, device: int = 0, half: bool = True):
         buf = _weights_bytes(weights)
@@ -867,17 +647,6 @@ class Enhancer:
     @property
     def handle(self):
         return self._h
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            lib().ffp_sr_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def enhance(self, img_bgr: np.ndarray, tile: int = 0, tile_pad: int = 10, pre_pad: int = 0) -> np.ndarray:
         return self.enhance_batch([img_bgr], tile, tile_pad, pre_pad)[0]
@@ -985,8 +754,8 @@ def op_conv2d(x: np.ndarray, w: np.ndarray, b: Optional[np.ndarray], stride: int
     y = np.zeros((n, ho, wo, cout), np.float32)
     bb = np.ascontiguousarray(b, np.float32) if b is not None else None
     rr = np.ascontiguousarray(res, np.float32) if res is not None else None
-    _check(lib().ffp_op_conv2d(device, precision, _fp(x), n, h, wd, cin, _fp(w), _fp(bb) if bb is not None else None, cout, k, stride,
-                               groups, act, int(up), _fp(rr) if rr is not None else None, res_scale, _fp(y)))
+    _check(lib().ffp_op_conv2d(device, precision, _fp(x), n, h, wd, cin, _fp(w), _fp(bb), cout, k, stride,
+                               groups, act, int(up), _fp(rr), res_scale, _fp(y)))
     return y
 
 
@@ -1110,7 +879,7 @@ def op_dwconv3x3(x, c: int, x_coff: int, w: np.ndarray, b: Optional[np.ndarray],
         rf, hs3, ws3, rcs = _op_pack(res)
         _op_same_batch(hs, ws, hs3, ws3, "dwconv3x3 residual")
     _check(lib().ffp_op_dwconv3x3(device, precision, len(hs), _ip(hs), _ip(ws), px_align, c, _fp(xf), xcs, x_coff, grp, grp_stride, grp_off, _fp(w),
-                                  _fp(bb) if bb is not None else None, act, _fp(rf) if rf is not None else None, rcs, r_coff, _fp(yf), ycs, y_coff))
+                                  _fp(bb), act, _fp(rf), rcs, r_coff, _fp(yf), ycs, y_coff))
     return _op_unpack(yf, hs, ws)
 
 
@@ -1153,11 +922,10 @@ def op_conv2d_views(x, x_coff: int, w: np.ndarray, b: Optional[np.ndarray], y, y
             if g[i].shape != (n,):
                 raise ValueError(f"conv2d_views: gate {g[i].shape}, expected {(n,)}")
     stray = C.c_int64(-1)
-    opt = lambda a: _fp(a) if a is not None else None
-    _check(lib().ffp_op_conv2d_views(device, precision, n, _ip(hs), _ip(ws), px_align, _fp(xf), xcs, x_coff, cin, _fp(w), opt(bb), cout, k, stride, act,
-                                     act_post, int(bool(up)), opt(rf[0]), rcs[0], r1_coff, s1, opt(rf[1]), rcs[1], r2_coff, s2, _fp(yf), ycs, y_coff,
-                                     int(bool(per_image_amax)), _up(slots), _ip(g[0]) if g[0] is not None else None,
-                                     _ip(g[1]) if g[1] is not None else None, C.byref(stray)))
+    _check(lib().ffp_op_conv2d_views(device, precision, n, _ip(hs), _ip(ws), px_align, _fp(xf), xcs, x_coff, cin, _fp(w), _fp(bb), cout, k, stride, act,
+                                     act_post, int(bool(up)), _fp(rf[0]), rcs[0], r1_coff, s1, _fp(rf[1]), rcs[1], r2_coff, s2, _fp(yf), ycs, y_coff,
+                                     int(bool(per_image_amax)), _up(slots), _ip(g[0]),
+                                     _ip(g[1]), C.byref(stray)))
     cut = np.cumsum([0] + [int(h) * int(w_) for h, w_ in zip(hs2, ws2)])
     return [yf[cut[i]:cut[i + 1]].reshape(int(hs2[i]), int(ws2[i]), ycs) for i in range(n)], slots, int(stray.value)
 
@@ -1221,10 +989,6 @@ def _slot(amax):
     return None if amax is None else np.asarray([np.float32(amax)], np.float32).view(np.uint32).copy()
 
 
-def _up(s):
-    return s.ctypes.data_as(_p(C.c_uint32)) if s is not None else None
-
-
 def _ret(out, s):
     return out if s is None else (out, int(s[0]))
 
@@ -1268,7 +1032,7 @@ def op_rt_layernorm(x, x_coff: int, gamma, beta, y, y_coff: int, amax=None, devi
     if g.shape != (256,) or b.shape != (256,) or (xx is not None and xx.shape[0] != y.shape[0]):
         raise ValueError("rt_layernorm: shapes")
     sl = _slot(amax)
-    _check(lib().ffp_op_rt_layernorm(device, y.shape[0], _fp(xx) if xx is not None else None, xx.shape[1] if xx is not None else 0, x_coff, _fp(g), _fp(b),
+    _check(lib().ffp_op_rt_layernorm(device, y.shape[0], _fp(xx), xx.shape[1] if xx is not None else 0, x_coff, _fp(g), _fp(b),
                                      _fp(y), y.shape[1], y_coff, _up(sl)))
     return _ret(y, sl)
 
@@ -1329,7 +1093,7 @@ def op_rt_ref(delta, d_coff: int, ref, r_coff: int, anc=None, amax=None, device:
     if ref.shape[0] != delta.shape[0] or (an is not None and an.shape != (delta.shape[0], 4)):
         raise ValueError("rt_ref: shapes")
     sl = _slot(amax)
-    _check(lib().ffp_op_rt_ref(device, delta.shape[0], _fp(delta), delta.shape[1], d_coff, _fp(an) if an is not None else None, _fp(ref), ref.shape[1],
+    _check(lib().ffp_op_rt_ref(device, delta.shape[0], _fp(delta), delta.shape[1], d_coff, _fp(an), _fp(ref), ref.shape[1],
                                r_coff, _up(sl)))
     return _ret(ref, sl)
 
@@ -1363,8 +1127,8 @@ def op_rt_decode(ref, r_coff: int, scores, s_coff: int, nc: int, conf: Optional[
     if (o_raw is not None and o_raw.shape != (n, 300, 4 + nc)) or (o_det is not None and (o_det.shape != (n, 300, 6) or wh is None or wh.shape != (n, 2))):
         raise ValueError("rt_decode: output shapes")
     _check(lib().ffp_op_rt_decode(device, n, nc, _fp(ref), ref.shape[2], r_coff, _fp(scores), scores.shape[2], s_coff, float(conf or 0.0),
-                                  _fp(wh) if wh is not None else None, _fp(o_raw) if o_raw is not None else None,
-                                  _fp(o_det) if o_det is not None else None, _ip(cnt) if cnt is not None else None))
+                                  _fp(wh), _fp(o_raw),
+                                  _fp(o_det), _ip(cnt)))
     return o_raw, o_det, cnt
 
 
@@ -1425,7 +1189,7 @@ def op_scrfd_post(net_hw, A: int, score, bbox, kps, coffs, det_scale, thresh: fl
     per_img = sum((net_h // s) * (net_w // s) * A for s in strides)
     rs = np.zeros((n, per_img), np.float32) if raw_scores else None
     _check(lib().ffp_op_scrfd_post(device, n, net_h, net_w, A, _ip(st), px_align, ptrs, _ip(cs), _ip(co), _fp(ds), thresh, nms_thresh, o.shape[1], _fp(o),
-                                   _ip(cnt), _fp(rs) if rs is not None else None))
+                                   _ip(cnt), _fp(rs)))
     return (o, cnt, rs) if raw_scores else (o, cnt)
 
 
@@ -1448,10 +1212,6 @@ def op_scrfd_sahi_rows(dets: np.ndarray, counts, tiles, full_shape, conf: float,
 
 
 IMAGE_YOLO, IMAGE_RTDETR, IMAGE_SCRFD = 0, 1, 2      # ffp_op_image_input kind
-
-
-def _u8p(a: np.ndarray):
-    return a.ctypes.data_as(_p(C.c_uint8))
 
 
 def op_image_input(kind: int, frame: np.ndarray, boxes, size, chan_order: int = CHAN_AS_BGR, precision: int = PREC_F32,
@@ -2023,10 +1783,6 @@ def _sr_images(images) -> np.ndarray:
     return a
 
 
-def _i64p(a: np.ndarray):
-    return a.ctypes.data_as(_p(C.c_int64))
-
-
 def op_sr_tiles(images, scale: int, tile: int = 0, tile_pad: int = 10, pre_pad: int = 0, precision: int = PREC_F32):
     """The padded tiles the enhancer cuts a batch into (ffp_op_sr_tiles, no device): ([(h, w), ...] in tile order, 16x16 body tiles,
     channels of the network's input record in `precision`)."""
@@ -2157,24 +1913,15 @@ def niqe_score(feat: np.ndarray, block_off: np.ndarray, mu: np.ndarray, cov: np.
     return out
 
 
-class IQA:
+class IQA(_Handle):
     """No-reference image quality on one GPU (ffp_iqa_*): NIQE block features on the device, the score in float64 on the host."""
+
+    _DESTROY = "ffp_iqa_destroy"
 
     def __init__(self, device: int = 0):
         self._h = C.c_void_p()
         self.device = device
         _check(lib().ffp_iqa_create(device, C.byref(self._h)))
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            lib().ffp_iqa_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def niqe_features(self, images: Sequence[np.ndarray], chan_order: int = CHAN_AS_RGB) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """A ragged batch, all images in one form: float32 planar (C, H, W) or (H, W) in [0,1] (RGB), or uint8 (H, W, C) or (H, W) in

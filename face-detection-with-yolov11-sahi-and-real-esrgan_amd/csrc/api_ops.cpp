@@ -12,6 +12,189 @@
 
 using namespace ffp;
 
+// ---- the operand stager of the op entries ---------------------------------------------------------------------------------------------
+// Host arrays hold the images of a batch back to back, [sum h*w][cs] fp32 — whole pixel records, so a view may be a channel slice of a
+// wider buffer. On the device they sit in the layout of their Level (padding pixels between aligned images are NaN going in and are not
+// copied back), in the element type of the op. Output buffers are in/out: the caller's contents go up first, so bytes outside the written
+// slice come back as they went in. An entry declares its ScopedStream first, stages with blocking copies, launches, and fetches after
+// op_finish has drained the stream.
+namespace {
+
+void op_check_batch(const char* what, int n, const int32_t* hs, const int32_t* ws, int px_align) {
+  FFP_CHECK(n > 0 && n <= 4096 && hs && ws && px_align >= 1 && px_align <= 4096, FFP_ERR_ARG, "%s: bad batch description", what);
+  for (int i = 0; i < n; ++i) FFP_CHECK(hs[i] > 0 && ws[i] > 0 && hs[i] <= 8192 && ws[i] <= 8192, FFP_ERR_ARG, "%s: image %d is %dx%d", what, i, ws[i], hs[i]);
+}
+void op_check_view(const char* what, int cs, int coff, int C) {
+  FFP_CHECK(C > 0 && coff >= 0 && cs > 0 && coff + C <= cs, FFP_ERR_ARG, "%s: channels [%d, %d) do not fit records of %d", what, coff, coff + C, cs);
+}
+void op_check_view4(const char* what, int cs, int coff, int C) {
+  op_check_view(what, cs, coff, C);
+  FFP_CHECK(C % 4 == 0 && cs % 4 == 0 && coff % 4 == 0, FFP_ERR_ARG, "%s: channels, offset and record size must be multiples of 4 (%d at %d of %d)", what, C, coff, cs);
+}
+DType op_dtype(const char* what, int precision) {
+  FFP_CHECK(precision == FFP_PREC_F32 || precision == FFP_PREC_F16, FFP_ERR_ARG, "%s: precision must be FFP_PREC_F32 or FFP_PREC_F16", what);
+  return precision == FFP_PREC_F16 ? F16 : F32;
+}
+
+// output-size rules, per image side
+int op_conv_out(int v, int k, int stride) { return (v + 2 * (k / 2) - k) / stride + 1; }      // padding k / 2
+int op_avg_out(int v, int k) { return (v + k - 1) / k; }                                       // windows of k, the last one partial
+
+// the level of a ragged batch; `size` maps every side (an output-size rule)
+template <class F> void op_level(Level& L, const int32_t* hs, const int32_t* ws, int n, hipStream_t st, int px_align, F size) {
+  std::vector<int> h(n), w(n);
+  for (int i = 0; i < n; ++i) { h[i] = size(hs[i]); w[i] = size(ws[i]); }
+  L.build(h, w, st, px_align);
+}
+void op_level(Level& L, const int32_t* hs, const int32_t* ws, int n, hipStream_t st, int px_align = 1) {
+  op_level(L, hs, ws, n, st, px_align, [](int v) { return v; });
+}
+void op_level_same(Level& L, int n, int h, int w, hipStream_t st) { L.build(std::vector<int>(n, h), std::vector<int>(n, w), st); }      // n images of h x w
+void op_flat_level(Level& L, int n, long long per_image, hipStream_t st) {      // n images of per_image records each
+  FFP_CHECK(per_image >= 1 && per_image <= INT_MAX && n >= 1 && n <= 4096 && (long long)n * per_image <= (1ll << 28), FFP_ERR_ARG,
+            "op: %d images of %lld records", n, per_image);
+  op_level_same(L, n, 1, (int)per_image, st);
+}
+
+// fp32 host values <-> `count` elements of type T: the one place where a host array changes its element type
+void op_narrow(DType T, const float* src, size_t count, void* dst) {
+  if (T == F32) { std::memcpy(dst, src, count * sizeof(float)); return; }
+  _Float16* h = static_cast<_Float16*>(dst);
+  for (size_t i = 0; i < count; ++i) h[i] = (_Float16)src[i];
+}
+void op_widen(DType T, const void* src, size_t count, float* dst) {
+  if (T == F32) { std::memcpy(dst, src, count * sizeof(float)); return; }
+  const _Float16* h = static_cast<const _Float16*>(src);
+  for (size_t i = 0; i < count; ++i) dst[i] = (float)h[i];
+}
+// `count` fp32 host values as elements of type T at the head of a device buffer with `slack` bytes behind them, and back
+DevBuf op_put(DType T, const float* src, size_t count, size_t slack = 0) {
+  std::vector<unsigned char> raw(count * dsize(T));
+  op_narrow(T, src, count, raw.data());
+  DevBuf b(raw.size() + slack);
+  if (count) FFP_HIP(hipMemcpy(b.p, raw.data(), raw.size(), hipMemcpyHostToDevice));
+  return b;
+}
+void op_get(DType T, const DevBuf& b, size_t count, float* dst) {
+  std::vector<unsigned char> raw(count * dsize(T));
+  if (count) FFP_HIP(hipMemcpy(raw.data(), b.p, raw.size(), hipMemcpyDeviceToHost));
+  op_widen(T, raw.data(), count, dst);
+}
+
+constexpr size_t kOpSlack = 256;      // bytes behind the records of every staged tensor
+// the bits of the element op_stage stores where no image has a pixel
+uint32_t op_pad_value(DType T) {
+  volatile float nanv = std::nanf("");      // (volatile: the conversion op_stage runs, not a folded constant)
+  const float nan = nanv;
+  uint32_t bits = 0;
+  op_narrow(T, &nan, 1, &bits);
+  return bits;
+}
+
+// max-|value| slots of one buffer, one or one per image. From the caller: its bit patterns go up and the final ones come back (fetch). From data: up only.
+struct OpSlot {
+  DevBuf d;
+  uint32_t* host = nullptr;
+  int n = 1;
+  explicit OpSlot(uint32_t* h, int n_ = 1) : host(h), n(n_) { if (h) d = upload(h, (size_t)n); }
+  explicit OpSlot(const std::vector<unsigned>& bits) : n((int)bits.size()) { d = upload(bits.data(), bits.size()); }
+  unsigned* ptr() const { return d.as<unsigned>(); }      // null without slots
+  void fetch() { if (host) FFP_HIP(hipMemcpy(host, d.p, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost)); }
+};
+
+// One host array of whole pixel records on the device.
+struct OpTensor {
+  DevBuf buf;      // the level's records, then kOpSlack bytes
+  Level* lvl = nullptr;
+  DType T = F32;
+  int cs = 0;
+  size_t elems() const { return (size_t)lvl->total_px * cs; }
+  TView view(int coff, int C, const OpSlot* slot = nullptr) const {      // channels [coff, coff + C), raising `slot`
+    TView v{buf.p, T, cs, coff, C, lvl};
+    if (slot) { v.amax = slot->ptr(); v.amax_n = slot->n; }
+    return v;
+  }
+  void fetch(float* dst) const {      // the images' records back to back; call after the stream has drained
+    std::vector<float> t(elems());
+    op_get(T, buf, t.size(), t.data());
+    size_t sp = 0;
+    for (int i = 0; i < lvl->n; ++i) {
+      const size_t np = (size_t)lvl->h[i] * lvl->w[i];
+      std::memcpy(dst + sp * cs, &t[(size_t)lvl->off[i] * cs], np * cs * sizeof(float));
+      sp += np;
+    }
+  }
+};
+
+// src: [sum h*w][src_cs] (0: cs; fewer: channels [src_cs, cs) of a record are zero), or null: no contents, every element is the padding value.
+// slack_ff: the kOpSlack bytes behind the records are 0xFF, a known pattern for op_stray.
+OpTensor op_stage(Level& L, DType T, const float* src, int cs, bool slack_ff = false, int src_cs = 0) {
+  if (!src_cs) src_cs = cs;
+  OpTensor t;
+  t.lvl = &L; t.T = T; t.cs = cs;
+  std::vector<float> h(t.elems(), std::nanf(""));
+  size_t sp = 0;
+  for (int i = 0; src && i < L.n; ++i) {
+    const size_t np = (size_t)L.h[i] * L.w[i];
+    float* rec = &h[(size_t)L.off[i] * cs];
+    if (src_cs == cs) std::memcpy(rec, src + sp * cs, np * cs * sizeof(float));
+    else for (size_t p = 0; p < np; ++p, rec += cs) {
+      std::memcpy(rec, src + (sp + p) * src_cs, src_cs * sizeof(float));
+      std::fill(rec + src_cs, rec + cs, 0.f);
+    }
+    sp += np;
+  }
+  t.buf = op_put(T, h.data(), h.size(), kOpSlack);
+  if (slack_ff) fill_bytes(t.buf.as<char>() + h.size() * dsize(T), 0xFF, kOpSlack);
+  return t;
+}
+
+// max |value| over channels [coff, coff + C) of a host array of cs-wide records as fp32 bits, NaN left out: one per image of L, or one for the buffer
+std::vector<unsigned> op_amax_bits(const float* x, const Level& L, int cs, int coff, int C, bool per_image) {
+  std::vector<unsigned> bits(per_image ? L.n : 1, 0u);
+  size_t sp = 0;
+  for (int i = 0; i < L.n; ++i) {
+    const size_t np = (size_t)L.h[i] * L.w[i];
+    float m = 0.f;
+    for (size_t p = 0; p < np; ++p)
+      for (int c = 0; c < C; ++c) m = std::max(m, std::fabs(x[(sp + p) * cs + coff + c]));      // (max(m, NaN) is m)
+    unsigned b;
+    std::memcpy(&b, &m, 4);
+    unsigned& slot = bits[per_image ? i : 0];
+    slot = std::max(slot, b);      // non-negative floats order like their bits
+    sp += np;
+  }
+  return bits;
+}
+
+// What changed where no kernel may write: elements of the padding pixels behind each aligned image, against the value op_stage stored, and bytes of the
+// slack behind the records, against 0xFF (op_stage with slack_ff). may_write(image, channel): an element of that image's padding pixels is the kernel's to write.
+template <class F> int64_t op_stray(const OpTensor& t, F may_write) {
+  const Level& L = *t.lvl;
+  const size_t esz = dsize(t.T), rec_bytes = t.elems() * esz;
+  std::vector<unsigned char> now(rec_bytes + kOpSlack);
+  FFP_HIP(hipMemcpy(now.data(), t.buf.p, now.size(), hipMemcpyDeviceToHost));
+  const uint32_t pad = op_pad_value(t.T);
+  int64_t bad = 0;
+  for (int i = 0; i < L.n; ++i) {
+    const size_t p0 = (size_t)(L.off[i] + (int64_t)L.h[i] * L.w[i]), p1 = (size_t)(i + 1 < L.n ? L.off[i + 1] : L.total_px);
+    for (size_t p = p0; p < p1; ++p)
+      for (int c = 0; c < t.cs; ++c) bad += !may_write(i, c) && std::memcmp(&now[(p * t.cs + c) * esz], &pad, esz) != 0;
+  }
+  for (size_t e = rec_bytes; e < now.size(); ++e) bad += now[e] != 0xFF;
+  return bad;
+}
+int64_t op_stray(const OpTensor& t) { return op_stray(t, [](int, int) { return false; }); }
+
+// the tail of an entry: drain the stream, then the blocking copies back
+void op_finish(const ScopedStream& cx, std::initializer_list<std::pair<const OpTensor*, float*>> outs, std::initializer_list<OpSlot*> slots = {}) {
+  FFP_HIP(hipStreamSynchronize(cx.st));
+  for (const auto& o : outs) if (o.second) o.first->fetch(o.second);
+  for (OpSlot* s : slots) s->fetch();
+}
+
+}  // namespace
+
 extern "C" {
 
 static int g_op_conv_shape = SHAPE_AUTO;
@@ -58,40 +241,15 @@ int ffp_op_conv2d(int device, int precision, const float* x, int n, int h, int w
   const bool split = precision == FFP_PREC_F32X3;
   PackedConv pc;
   pack_conv(pc, "op", wt, bias, cout, cin, k, groups, T, cx.st, split);
-  const int hi = up ? h * 2 : h, wi = up ? w * 2 : w;
-  const int ho = (hi + 2 * (k / 2) - k) / stride + 1, wo = (wi + 2 * (k / 2) - k) / stride + 1;
   Level lin, lout;
-  lin.build(std::vector<int>(n, h), std::vector<int>(n, w), cx.st);
-  lout.build(std::vector<int>(n, ho), std::vector<int>(n, wo), cx.st);
+  op_level_same(lin, n, h, w, cx.st);
+  op_level_same(lout, n, op_conv_out(up ? h * 2 : h, k, stride), op_conv_out(up ? w * 2 : w, k, stride), cx.st);
   const int cin_s = pc.depthwise() ? cin : pc.cin;        // stored (padded) input channels
-  const size_t npx_in = (size_t)lin.total_px, npx_out = (size_t)lout.total_px;
-  auto to_dev = [&](const float* src, size_t px, int c, int c_store) {
-    DevBuf b(px * c_store * dsize(T) + 256);
-    if (T == F32) {
-      std::vector<float> t(px * c_store, 0.f);
-      for (size_t p = 0; p < px; ++p) std::memcpy(&t[p * c_store], src + p * c, sizeof(float) * c);
-      FFP_HIP(hipMemcpy(b.p, t.data(), t.size() * 4, hipMemcpyHostToDevice));
-    } else {
-      std::vector<_Float16> t(px * c_store, (_Float16)0.f);
-      for (size_t p = 0; p < px; ++p) for (int q = 0; q < c; ++q) t[p * c_store + q] = (_Float16)src[p * c + q];
-      FFP_HIP(hipMemcpy(b.p, t.data(), t.size() * 2, hipMemcpyHostToDevice));
-    }
-    return b;
-  };
-  DevBuf din = to_dev(x, npx_in, cin, cin_s);
-  DevBuf dres;
-  if (res) dres = to_dev(res, npx_out, cout, cout);
-  DevBuf dout(npx_out * cout * dsize(T) + 256);
-  TView vin{din.p, T, cin_s, 0, cin_s, &lin}, vout{dout.p, T, cout, 0, cout, &lout}, vres{dres.p, T, cout, 0, cout, &lout};
-  DevBuf slots(2 * sizeof(unsigned));                 // max-|value| slots of the input / output buffers (scaled split, see TView::amax)
-  {
-    float m = 0.f;
-    for (size_t i = 0; i < npx_in * (size_t)cin; ++i) m = std::max(m, std::fabs(x[i]));
-    unsigned hb[2] = {0u, 0u};
-    std::memcpy(&hb[0], &m, 4);
-    FFP_HIP(hipMemcpy(slots.p, hb, sizeof(hb), hipMemcpyHostToDevice));
-    vin.amax = slots.as<unsigned>(); vout.amax = slots.as<unsigned>() + 1;
-  }
+  const OpTensor tin = op_stage(lin, T, x, cin_s, false, cin), tout = op_stage(lout, T, nullptr, cout);
+  OpTensor tres;
+  if (res) tres = op_stage(lout, T, res, cout);
+  OpSlot sin(op_amax_bits(x, lin, cin, 0, cin, false)), sout(std::vector<unsigned>(1, 0u));      // max-|value| slots of the input / output buffers (scaled split, see TView::amax)
+  const TView vin = tin.view(0, cin_s, &sin), vout = tout.view(0, cout, &sout), vres = res ? tres.view(0, cout) : TView{};
   if (pc.depthwise()) {
     FFP_CHECK(k == 3 && stride == 1 && !up, FFP_ERR_ARG, "conv2d: depthwise is 3x3 stride 1");
     FFP_CHECK(g_op_conv_act_post == ACT_NONE, FFP_ERR_ARG, "conv2d: depthwise convs have no post-activation");
@@ -108,14 +266,7 @@ int ffp_op_conv2d(int device, int precision, const float* x, int n, int h, int w
     launch_conv(o, cx.st);
     tl_op_conv_variant = conv_variant(o);
   }
-  FFP_HIP(hipStreamSynchronize(cx.st));
-  if (T == F32) {
-    FFP_HIP(hipMemcpy(y, dout.p, npx_out * cout * 4, hipMemcpyDeviceToHost));
-  } else {
-    std::vector<_Float16> t(npx_out * cout);
-    FFP_HIP(hipMemcpy(t.data(), dout.p, t.size() * 2, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < t.size(); ++i) y[i] = (float)t[i];
-  }
+  op_finish(cx, {{&tout, y}});
   FFP_API_END
 }
 
@@ -132,41 +283,26 @@ int ffp_op_conv1x1_up2(int device, int precision, const float* coarse, const flo
   pack_conv(pc, "op", wt, bias, cout, cin, 1, 1, F32, cx.st, precision == FFP_PREC_F32X3);
   FFP_CHECK(pc.cin == cin, FFP_ERR_ARG, "conv1x1_up2: channel count %d needs padding", cin);
   Level lf, lc;
-  lf.build(std::vector<int>(n, h), std::vector<int>(n, w), cx.st);
-  lc.build(std::vector<int>(n, h / 2), std::vector<int>(n, w / 2), cx.st);
-  const size_t pf = (size_t)lf.total_px, pcs = (size_t)lc.total_px;
+  op_level_same(lf, n, h, w, cx.st);
+  op_level_same(lc, n, h / 2, w / 2, cx.st);
   // the concat buffer holds the fine channels at [c_up, cin); its first c_up channels are never written (filled with NaN here:
   // a kernel that read them would show)
-  std::vector<float> cat(pf * cin, std::nanf(""));
-  for (size_t p = 0; p < pf; ++p) std::memcpy(&cat[p * cin + c_up], fine + p * c_fine, sizeof(float) * c_fine);
-  DevBuf dcat(cat.size() * 4 + 256), dco(pcs * c_up * 4 + 256), dout(pf * cout * 4 + 256), slots(3 * sizeof(unsigned));
-  FFP_HIP(hipMemcpy(dcat.p, cat.data(), cat.size() * 4, hipMemcpyHostToDevice));
-  FFP_HIP(hipMemcpy(dco.p, coarse, pcs * c_up * 4, hipMemcpyHostToDevice));
-  float mf = 0.f, mc = 0.f;
-  for (size_t i = 0; i < pf * (size_t)c_fine; ++i) mf = std::max(mf, std::fabs(fine[i]));
-  for (size_t i = 0; i < pcs * (size_t)c_up; ++i) mc = std::max(mc, std::fabs(coarse[i]));
-  unsigned hb[3] = {0u, 0u, 0u};
-  std::memcpy(&hb[0], &mf, 4);
-  std::memcpy(&hb[1], &mc, 4);
-  FFP_HIP(hipMemcpy(slots.p, hb, sizeof(hb), hipMemcpyHostToDevice));
-  TView vin{dcat.p, F32, cin, 0, cin, &lf}, vco{dco.p, F32, c_up, 0, c_up, &lc}, vout{dout.p, F32, cout, 0, cout, &lf};
-  vin.amax = slots.as<unsigned>(); vco.amax = slots.as<unsigned>() + 1; vout.amax = slots.as<unsigned>() + 2;
+  std::vector<float> cat((size_t)lf.total_px * cin, std::nanf(""));
+  for (size_t p = 0; p < (size_t)lf.total_px; ++p) std::memcpy(&cat[p * cin + c_up], fine + p * c_fine, sizeof(float) * c_fine);
+  const OpTensor tcat = op_stage(lf, F32, cat.data(), cin), tco = op_stage(lc, F32, coarse, c_up), tout = op_stage(lf, F32, nullptr, cout);
+  OpSlot sfine(op_amax_bits(fine, lf, c_fine, 0, c_fine, false)), sco(op_amax_bits(coarse, lc, c_up, 0, c_up, false)), sout(std::vector<unsigned>(1, 0u));
+  const TView vin = tcat.view(0, cin, &sfine), vco = tco.view(0, c_up, &sco), vout = tout.view(0, cout, &sout);
   ConvOp o;
   o.pc = &pc; o.in = vin; o.out = vout; o.stride = 1; o.act = act;
   o.has_up2 = true; o.up2 = vco; o.up2_c = c_up; o.up2_map = lf.up2_map(&lc, cx.st);
   o.force_shape = g_op_conv_shape;
   launch_conv(o, cx.st);
   tl_op_conv_variant = conv_variant(o);
-  FFP_HIP(hipStreamSynchronize(cx.st));
-  FFP_HIP(hipMemcpy(y, dout.p, pf * cout * 4, hipMemcpyDeviceToHost));
+  op_finish(cx, {{&tout, y}});
   FFP_API_END
 }
 
 // ---- single-operator entry points of the detector's non-convolution kernels (tests/test_gpu_ops.py) --------------------------------
-// Host arrays hold the images of a ragged batch back to back, [sum h*w][cs] fp32 — whole pixel records, so a view may be a channel
-// slice of a wider buffer. On the device they sit in the layout of a Level built with `px_align` (padding pixels between images are
-// NaN going in and are not copied back); output buffers are in/out: the caller's contents go up first, so bytes outside the written
-// slice come back as they went in.
 static int g_op_variant[3] = {0, 0, 0};
 int ffp_op_variant(int family, int variant) {
   FFP_API_BEGIN
@@ -182,60 +318,6 @@ int ffp_op_cls_tower_variant(int rows, int wg_cap) {
   FFP_API_END
 }
 
-namespace {
-
-void op_check_batch(const char* what, int n, const int32_t* hs, const int32_t* ws, int px_align) {
-  FFP_CHECK(n > 0 && n <= 4096 && hs && ws && px_align >= 1 && px_align <= 4096, FFP_ERR_ARG, "%s: bad batch description", what);
-  for (int i = 0; i < n; ++i) FFP_CHECK(hs[i] > 0 && ws[i] > 0 && hs[i] <= 8192 && ws[i] <= 8192, FFP_ERR_ARG, "%s: image %d is %dx%d", what, i, ws[i], hs[i]);
-}
-void op_check_view(const char* what, int cs, int coff, int C) {
-  FFP_CHECK(C > 0 && coff >= 0 && cs > 0 && coff + C <= cs, FFP_ERR_ARG, "%s: channels [%d, %d) do not fit records of %d", what, coff, coff + C, cs);
-}
-DType op_dtype(const char* what, int precision) {
-  FFP_CHECK(precision == FFP_PREC_F32 || precision == FFP_PREC_F16, FFP_ERR_ARG, "%s: precision must be FFP_PREC_F32 or FFP_PREC_F16", what);
-  return precision == FFP_PREC_F16 ? F16 : F32;
-}
-
-DevBuf op_upload(const Level& L, DType T, const float* src, int cs) {
-  const size_t tot = (size_t)L.total_px * cs;
-  DevBuf b(tot * dsize(T) + 256);
-  std::vector<float> t(tot, std::nanf(""));
-  size_t sp = 0;
-  for (int i = 0; i < L.n; ++i) {
-    const size_t np = (size_t)L.h[i] * L.w[i];
-    std::memcpy(&t[(size_t)L.off[i] * cs], src + sp * cs, np * cs * sizeof(float));
-    sp += np;
-  }
-  if (T == F32) {
-    FFP_HIP(hipMemcpy(b.p, t.data(), tot * 4, hipMemcpyHostToDevice));
-  } else {
-    std::vector<_Float16> h(tot);
-    for (size_t i = 0; i < tot; ++i) h[i] = (_Float16)t[i];
-    FFP_HIP(hipMemcpy(b.p, h.data(), tot * 2, hipMemcpyHostToDevice));
-  }
-  return b;
-}
-
-void op_download(const Level& L, DType T, const DevBuf& b, int cs, float* dst) {
-  const size_t tot = (size_t)L.total_px * cs;
-  std::vector<float> t(tot);
-  if (T == F32) {
-    FFP_HIP(hipMemcpy(t.data(), b.p, tot * 4, hipMemcpyDeviceToHost));
-  } else {
-    std::vector<_Float16> h(tot);
-    FFP_HIP(hipMemcpy(h.data(), b.p, tot * 2, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < tot; ++i) t[i] = (float)h[i];
-  }
-  size_t sp = 0;
-  for (int i = 0; i < L.n; ++i) {
-    const size_t np = (size_t)L.h[i] * L.w[i];
-    std::memcpy(dst + sp * cs, &t[(size_t)L.off[i] * cs], np * cs * sizeof(float));
-    sp += np;
-  }
-}
-
-}  // namespace
-
 int ffp_op_sppf_pool(int device, int precision, int n, const int32_t* hs, const int32_t* ws, int px_align, int c, const float* x, int x_cs,
                      int x_coff, float* y, int y_cs, int y1_coff, int y2_coff, int y3_coff) {
   FFP_API_BEGIN
@@ -250,13 +332,10 @@ int ffp_op_sppf_pool(int device, int precision, int n, const int32_t* hs, const 
   const DType T = op_dtype("sppf_pool", precision);
   ScopedStream cx(device, "sppf_pool");
   Level L;
-  L.build(std::vector<int>(hs, hs + n), std::vector<int>(ws, ws + n), cx.st, px_align);
-  DevBuf din = op_upload(L, T, x, x_cs), dout = op_upload(L, T, y, y_cs);
-  const TView vin{din.p, T, x_cs, x_coff, c, &L};
-  const TView v1{dout.p, T, y_cs, y1_coff, c, &L}, v2{dout.p, T, y_cs, y2_coff, c, &L}, v3{dout.p, T, y_cs, y3_coff, c, &L};
-  launch_sppf_pool(vin, v1, v2, v3, cx.st, g_op_variant[0]);
-  FFP_HIP(hipStreamSynchronize(cx.st));
-  op_download(L, T, dout, y_cs, y);
+  op_level(L, hs, ws, n, cx.st, px_align);
+  const OpTensor tx = op_stage(L, T, x, x_cs), ty = op_stage(L, T, y, y_cs);
+  launch_sppf_pool(tx.view(x_coff, c), ty.view(y1_coff, c), ty.view(y2_coff, c), ty.view(y3_coff, c), cx.st, g_op_variant[0]);
+  op_finish(cx, {{&ty, y}});
   FFP_API_END
 }
 
@@ -270,14 +349,11 @@ int ffp_op_upsample2x(int device, int precision, int n, const int32_t* hs, const
   const DType T = op_dtype("upsample2x", precision);
   ScopedStream cx(device, "upsample2x");
   Level L, L2;
-  std::vector<int> h2(n), w2(n);
-  for (int i = 0; i < n; ++i) { h2[i] = hs[i] * 2; w2[i] = ws[i] * 2; }
-  L.build(std::vector<int>(hs, hs + n), std::vector<int>(ws, ws + n), cx.st, px_align);
-  L2.build(h2, w2, cx.st, px_align);
-  DevBuf din = op_upload(L, T, x, x_cs), dout = op_upload(L2, T, y, y_cs);
-  launch_upsample2x(TView{din.p, T, x_cs, x_coff, c, &L}, TView{dout.p, T, y_cs, y_coff, c, &L2}, cx.st);
-  FFP_HIP(hipStreamSynchronize(cx.st));
-  op_download(L2, T, dout, y_cs, y);
+  op_level(L, hs, ws, n, cx.st, px_align);
+  op_level(L2, hs, ws, n, cx.st, px_align, [](int v) { return v * 2; });
+  const OpTensor tx = op_stage(L, T, x, x_cs), ty = op_stage(L2, T, y, y_cs);
+  launch_upsample2x(tx.view(x_coff, c), ty.view(y_coff, c), cx.st);
+  op_finish(cx, {{&ty, y}});
   FFP_API_END
 }
 
@@ -292,12 +368,10 @@ int ffp_op_psa_attention(int device, int precision, int n, const int32_t* hs, co
   const DType T = op_dtype("psa_attention", precision);
   ScopedStream cx(device, "psa_attention");
   Level L;
-  L.build(std::vector<int>(hs, hs + n), std::vector<int>(ws, ws + n), cx.st, px_align);
-  DevBuf din = op_upload(L, T, qkv, q_cs), dout = op_upload(L, T, out, o_cs);
-  launch_psa_attention(TView{din.p, T, q_cs, q_coff, nh * (2 * KD + HD), &L}, TView{dout.p, T, o_cs, o_coff, nh * HD, &L}, nh, KD, HD, cx.st,
-                       g_op_variant[1]);
-  FFP_HIP(hipStreamSynchronize(cx.st));
-  op_download(L, T, dout, o_cs, out);
+  op_level(L, hs, ws, n, cx.st, px_align);
+  const OpTensor tq = op_stage(L, T, qkv, q_cs), to = op_stage(L, T, out, o_cs);
+  launch_psa_attention(tq.view(q_coff, nh * (2 * KD + HD)), to.view(o_coff, nh * HD), nh, KD, HD, cx.st, g_op_variant[1]);
+  op_finish(cx, {{&to, out}});
   FFP_API_END
 }
 
@@ -322,19 +396,19 @@ int ffp_op_dwconv3x3(int device, int precision, int n, const int32_t* hs, const 
   PackedConv pc;
   pack_conv(pc, "op", wt, bias, c, c, 3, c, T, cx.st, false);
   Level L;
-  L.build(std::vector<int>(hs, hs + n), std::vector<int>(ws, ws + n), cx.st, px_align);
-  DevBuf din = op_upload(L, T, x, x_cs), dout = op_upload(L, T, y, y_cs), dres;
-  if (res) dres = op_upload(L, T, res, r_cs);
+  op_level(L, hs, ws, n, cx.st, px_align);
+  const OpTensor tx = op_stage(L, T, x, x_cs), ty = op_stage(L, T, y, y_cs);
+  OpTensor tres;
+  if (res) tres = op_stage(L, T, res, r_cs);
   DwConvOp o;
   o.pc = &pc;
-  o.in = TView{din.p, T, x_cs, x_coff, c, &L};
-  o.out = TView{dout.p, T, y_cs, y_coff, c, &L};
+  o.in = tx.view(x_coff, c);
+  o.out = ty.view(y_coff, c);
   o.act = act; o.grp = grp; o.grp_stride = grp_stride; o.grp_off = grp_off;
-  if (res) { o.has_res = true; o.res = TView{dres.p, T, r_cs, r_coff, c, &L}; }
+  if (res) { o.has_res = true; o.res = tres.view(r_coff, c); }
   o.force = g_op_variant[2];
   launch_dwconv(o, cx.st);
-  FFP_HIP(hipStreamSynchronize(cx.st));
-  op_download(L, T, dout, y_cs, y);
+  op_finish(cx, {{&ty, y}});
   FFP_API_END
 }
 
@@ -361,38 +435,20 @@ int ffp_op_cls_tower(int device, int n, const int32_t* hs, const int32_t* ws, in
   FFP_HIP(hipMemcpy(dense.w.p, fin_w, sizeof(float) * nc * C3, hipMemcpyHostToDevice));
   FFP_HIP(hipMemcpy(dense.b.p, fin_b, sizeof(float) * nc, hipMemcpyHostToDevice));
   Level L;
-  L.build(std::vector<int>(hs, hs + n), std::vector<int>(ws, ws + n), cx.st, px_align);
-  DevBuf dx = op_upload(L, F32, x, cin), dhead = op_upload(L, F32, head, head_cs);
-  fill_bytes(static_cast<char*>(dhead.p) + (size_t)L.total_px * head_cs * 4, 0xFF, 256);      // the slack behind the records: a known pattern too (stray)
-  DevBuf de1((size_t)L.total_px * C3 * 4 + 256), de2((size_t)L.total_px * C3 * 4 + 256);
-  fill_bytes(de1.p, 0xFF, de1.n);      // NaN: padding pixels are never written
-  fill_bytes(de2.p, 0xFF, de2.n);
+  op_level(L, hs, ws, n, cx.st, px_align);
+  // e1 / e2 have no contents going up: padding pixels are never written, and the slack behind every record buffer is a known pattern too (stray)
+  const OpTensor tx = op_stage(L, F32, x, cin), thead = op_stage(L, F32, head, head_cs, true), te1 = op_stage(L, F32, nullptr, C3, true),
+                 te2 = op_stage(L, F32, nullptr, C3, true);
   // a max-|value| slot per (tensor, image): x's from the data, the others raised by their producers
-  std::vector<unsigned> slots(3 * (size_t)n, 0u);
-  {
-    size_t sp = 0;
-    for (int i = 0; i < n; ++i) {
-      const size_t np = (size_t)hs[i] * ws[i] * cin;
-      float m = 0.f;
-      for (size_t k = 0; k < np; ++k) m = std::max(m, std::fabs(x[sp + k]));
-      std::memcpy(&slots[i], &m, 4);
-      sp += np;
-    }
-  }
-  DevBuf dslots(slots.size() * 4);
-  FFP_HIP(hipMemcpy(dslots.p, slots.data(), slots.size() * 4, hipMemcpyHostToDevice));
-  auto view = [&](void* p, int cs, int coff, int c, int slot) {
-    TView v{p, F32, cs, coff, c, &L};
-    if (slot >= 0) { v.amax = dslots.as<unsigned>() + (size_t)slot * n; v.amax_n = n; }
-    return v;
-  };
+  OpSlot sx(op_amax_bits(x, L, cin, 0, cin, true)), s1(std::vector<unsigned>(n, 0u)), s2(std::vector<unsigned>(n, 0u));
   const bool fuse_fin = nc <= 4;
   ConvOp t1, t2;
   t1.pc = &pw0; t1.dw = &dw0; t1.dw_act = ACT_SILU; t1.act = ACT_SILU;
-  t1.in = view(dx.p, cin, 0, cin, 0); t1.out = view(de1.p, C3, 0, C3, 1);
+  t1.in = tx.view(0, cin, &sx); t1.out = te1.view(0, C3, &s1);
   t2.pc = &pw1; t2.dw = &dw1; t2.dw_act = ACT_SILU; t2.act = ACT_SILU;
-  t2.in = t1.out; t2.out = view(fuse_fin ? nullptr : de2.p, C3, 0, C3, 2);
-  const TView logits = view(dhead.p, head_cs, head_coff, nc, -1);
+  t2.in = t1.out; t2.out = te2.view(0, C3, &s2);
+  if (fuse_fin) t2.out.ptr = nullptr;      // never stored
+  const TView logits = thead.view(head_coff, nc);
   if (fuse_fin) { t2.fin = &fin; t2.fin_w = &dense; t2.fin_out = logits; }
   t1.dwpw_force = t2.dwpw_force = g_op_cls_tower_force;
   launch_conv(t1, cx.st);
@@ -402,29 +458,11 @@ int ffp_op_cls_tower(int device, int n, const int32_t* hs, const int32_t* ws, in
     t3.pc = &fin; t3.in = t2.out; t3.out = logits; t3.act = ACT_NONE;
     launch_conv(t3, cx.st);
   }
-  FFP_HIP(hipStreamSynchronize(cx.st));
-  op_download(L, F32, dhead, head_cs, head);
-  if (e1) op_download(L, F32, de1, C3, e1);
+  op_finish(cx, {{&thead, head}, {&te1, e1}});
   if (stray) {
-    // pixels that belong to no image (behind each aligned image, and the slack behind the buffer) must still hold what went up: 0xFF bytes in e1 / e2,
-    // op_upload's NaN in the head record
-    const float nanv = std::nanf("");
-    unsigned nan_bits;
-    std::memcpy(&nan_bits, &nanv, 4);
-    auto changed = [&](const DevBuf& b, int cs, unsigned want, unsigned want_slack) {
-      std::vector<unsigned> h(b.n / 4);
-      FFP_HIP(hipMemcpy(h.data(), b.p, h.size() * 4, hipMemcpyDeviceToHost));
-      int64_t bad = 0;
-      for (int i = 0; i < n; ++i) {
-        const size_t p0 = (size_t)(L.off[i] + (int64_t)hs[i] * ws[i]) * cs, p1 = (size_t)(i + 1 < n ? L.off[i + 1] : L.total_px) * cs;
-        for (size_t k = p0; k < p1; ++k) bad += h[k] != want;
-      }
-      for (size_t k = (size_t)L.total_px * cs; k < h.size(); ++k) bad += h[k] != want_slack;
-      return bad;
-    };
-    *stray = changed(de1, C3, 0xFFFFFFFFu, 0xFFFFFFFFu) + changed(de2, C3, 0xFFFFFFFFu, 0xFFFFFFFFu);
+    *stray = op_stray(te1) + op_stray(te2);
     // nc > 4: the head record is written by the plain 1x1 conv, and the flat-pixel 1x1 kernels compute padding pixels like any pixel (common.hpp, Level::build)
-    if (fuse_fin) *stray += changed(dhead, head_cs, nan_bits, 0xFFFFFFFFu);
+    if (fuse_fin) *stray += op_stray(thead);
   }
   FFP_API_END
 }
@@ -454,12 +492,6 @@ int ffp_op_conv2d_views(int device, int precision, int n, const int32_t* hs, con
   op_check_view("conv2d_views output", y_cs, y_coff, cout);
   if (res1) op_check_view("conv2d_views res1", r1_cs, r1_coff, cout);
   if (res2) op_check_view("conv2d_views res2", r2_cs, r2_coff, cout);
-  std::vector<int> hi(hs, hs + n), wi(ws, ws + n), ho(n), wo(n);
-  for (int i = 0; i < n; ++i) {
-    const int hv = up ? hi[i] * 2 : hi[i], wv = up ? wi[i] * 2 : wi[i];
-    ho[i] = (hv + 2 * (k / 2) - k) / stride + 1;
-    wo[i] = (wv + 2 * (k / 2) - k) / stride + 1;
-  }
   ScopedStream cx(device, "conv2d_views");
   conv_kernels_init();
   tl_op_conv_variant.clear();
@@ -467,97 +499,44 @@ int ffp_op_conv2d_views(int device, int precision, int n, const int32_t* hs, con
   pack_conv(pc, "op", wt, bias, cout, cin, k, 1, T, cx.st, precision == FFP_PREC_F32X3);
   FFP_CHECK(pc.cin == cin_s, FFP_ERR_STATE, "conv2d_views: packed conv reads %d channels, expected %d", pc.cin, cin_s);
   Level lin, lout;
-  lin.build(hi, wi, cx.st, px_align);
-  lout.build(ho, wo, cx.st, px_align);
+  op_level(lin, hs, ws, n, cx.st, px_align);
+  op_level(lout, hs, ws, n, cx.st, px_align, [&](int v) { return op_conv_out(up ? v * 2 : v, k, stride); });
   lout.gate_compact = &launch_gate_compact;
-  const size_t esz = dsize(T), ybytes = (size_t)lout.total_px * y_cs * esz;
-  DevBuf din = op_upload(lin, T, x, x_cs), dout, dr1, dr2;
-  if (res1) dr1 = op_upload(lout, T, res1, r1_cs);
-  if (res2) dr2 = op_upload(lout, T, res2, r2_cs);
-  // max-|value| slots: [0, ns) the input's — from the data, per image over the view's own channels, NaN (an inactive image on its way up) left out —
-  // and [ns, 2 ns) the output's, which start from the caller's bit patterns
+  const OpTensor tin = op_stage(lin, T, x, x_cs);
+  OpTensor tout, tr1, tr2;
+  if (res1) tr1 = op_stage(lout, T, res1, r1_cs);
+  if (res2) tr2 = op_stage(lout, T, res2, r2_cs);
+  // max-|value| slots: the input's from the data, per image over the view's own channels, NaN (an inactive image on its way up) left out; the
+  // output's start from the caller's bit patterns
   const int ns = per_image_amax ? n : 1;
-  std::vector<unsigned> slots(2 * (size_t)ns, 0u);
-  {
-    size_t sp = 0;
-    for (int i = 0; i < n; ++i) {
-      const size_t np = (size_t)hi[i] * wi[i];
-      float m = 0.f;
-      for (size_t p = 0; p < np; ++p)
-        for (int c = 0; c < cin; ++c) m = std::max(m, std::fabs(x[(sp + p) * x_cs + x_coff + c]));
-      unsigned b;
-      std::memcpy(&b, &m, 4);
-      slots[per_image_amax ? i : 0] = std::max(slots[per_image_amax ? i : 0], b);
-      sp += np;
-    }
-  }
-  DevBuf dslots(slots.size() * 4), dgate;
-  auto upload_outputs = [&]() {      // padding pixels go up as NaN (op_upload), the slack behind the records as 0xFF bytes
-    dout = op_upload(lout, T, y, y_cs);
-    fill_bytes(static_cast<char*>(dout.p) + ybytes, 0xFF, 256);
-    std::copy(amax_out, amax_out + ns, slots.begin() + ns);
-    FFP_HIP(hipMemcpy(dslots.p, slots.data(), slots.size() * 4, hipMemcpyHostToDevice));
-  };
-  upload_outputs();
-  if (gate) dgate = upload(gate_prev ? gate_prev : gate, (size_t)n);
-  auto view = [&](void* p, int cs, int coff, int c, Level* L, int slot) {
-    TView v{p, T, cs, coff, c, L};
-    if (slot >= 0) { v.amax = dslots.as<unsigned>() + (size_t)slot * ns; v.amax_n = ns; }
-    return v;
-  };
+  OpSlot sin(op_amax_bits(x, lin, x_cs, x_coff, cin, per_image_amax != 0)), sout(nullptr);
+  DevBuf dgate;
   ConvOp o;
-  o.pc = &pc; o.stride = stride; o.act = act; o.act_post = act_post; o.up = up;
-  o.in = view(din.p, x_cs, x_coff, cin_s, &lin, 0);
-  auto bind_out = [&]() {      // dout is a new allocation after every upload
-    o.out = view(dout.p, y_cs, y_coff, cout, &lout, 1);
+  auto stage_outputs = [&]() {      // a new allocation every time: the view is bound again
+    tout = op_stage(lout, T, y, y_cs, true);
+    sout = OpSlot(amax_out, ns);
+    o.out = tout.view(y_coff, cout, &sout);
   };
-  bind_out();
-  if (res1) { o.has_res1 = true; o.res1 = view(dr1.p, r1_cs, r1_coff, cout, &lout, -1); o.s1 = s1; }
-  if (res2) { o.has_res2 = true; o.res2 = view(dr2.p, r2_cs, r2_coff, cout, &lout, -1); o.s2 = s2; }
+  stage_outputs();
+  if (gate) dgate = upload(gate_prev ? gate_prev : gate, (size_t)n);
+  o.pc = &pc; o.stride = stride; o.act = act; o.act_post = act_post; o.up = up;
+  o.in = tin.view(x_coff, cin_s, &sin);
+  if (res1) { o.has_res1 = true; o.res1 = tr1.view(r1_coff, cout); o.s1 = s1; }
+  if (res2) { o.has_res2 = true; o.res2 = tr2.view(r2_coff, cout); o.s2 = s2; }
   if (gate) o.gate = dgate.as<int>();
   o.force_shape = g_op_conv_shape;
   launch_conv(o, cx.st);
   tl_op_conv_variant = conv_variant(o);
   FFP_HIP(hipStreamSynchronize(cx.st));
   if (gate_prev) {      // what a captured plan does between two runs with different gates: same tables, same launches, the mask rewritten and the gated tables compacted again
-    upload_outputs();
-    bind_out();
+    stage_outputs();
     FFP_HIP(hipMemcpy(dgate.p, gate, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
     lout.compact_gated(cx.st);
     launch_conv(o, cx.st);
-    FFP_HIP(hipStreamSynchronize(cx.st));
   }
-  // one copy of the whole buffer back: the images' records for the caller, the rest for the stray count
-  std::vector<unsigned char> now(ybytes + 256);
-  FFP_HIP(hipMemcpy(now.data(), dout.p, now.size(), hipMemcpyDeviceToHost));
-  {
-    size_t sp = 0;
-    for (int i = 0; i < n; ++i) {
-      const size_t ne = (size_t)ho[i] * wo[i] * y_cs, e0 = (size_t)lout.off[i] * y_cs;
-      if (T == F32) std::memcpy(y + sp, &now[e0 * 4], ne * 4);
-      else for (size_t e = 0; e < ne; ++e) y[sp + e] = (float)reinterpret_cast<const _Float16*>(now.data())[e0 + e];
-      sp += ne;
-    }
-  }
-  FFP_HIP(hipMemcpy(slots.data(), dslots.p, slots.size() * 4, hipMemcpyDeviceToHost));
-  std::copy(slots.begin() + ns, slots.end(), amax_out);
-  if (stray) {
-    volatile float nanv = std::nanf("");            // (volatile: the conversion op_upload ran, not a folded constant)
-    const float nanf32 = nanv;
-    const _Float16 nanf16 = (_Float16)nanf32;      // what op_upload stored in a padding pixel
-    const void* want_pad = T == F32 ? static_cast<const void*>(&nanf32) : static_cast<const void*>(&nanf16);
-    int64_t bad = 0;
-    for (int i = 0; i < n; ++i) {
-      const size_t p0 = (size_t)(lout.off[i] + (int64_t)ho[i] * wo[i]), p1 = (size_t)(i + 1 < n ? lout.off[i + 1] : lout.total_px);
-      for (size_t p = p0; p < p1; ++p)
-        for (int c = 0; c < y_cs; ++c) {
-          if (k == 1 && c >= y_coff && c < y_coff + cout && (!gate || gate[i])) continue;      // (behind an inactive image they are nobody's to write)
-          bad += std::memcmp(&now[(p * y_cs + c) * esz], want_pad, esz) != 0;
-        }
-    }
-    for (size_t e = ybytes; e < now.size(); ++e) bad += now[e] != 0xFF;
-    *stray = bad;
-  }
+  op_finish(cx, {{&tout, y}}, {&sout});
+  // (a 1x1 conv computes the padding pixels of its own slice like any pixel; behind an inactive image they are nobody's to write)
+  if (stray) *stray = op_stray(tout, [&](int i, int c) { return k == 1 && c >= y_coff && c < y_coff + cout && (!gate || gate[i]); });
   FFP_API_END
 }
 
@@ -576,13 +555,11 @@ int ffp_op_det_post(int device, int n, const int32_t* hs, const int32_t* ws, int
   ScopedStream cx(device, "det_post");
   const int cs = 64 + nc + 3 * nkpt, no = 4 + nc + 3 * nkpt, stride = 6 + 3 * nkpt;
   Level L[3];
-  DevBuf dh[3];
+  OpTensor th[3];
   const float* heads[3] = {head8, head16, head32};
   for (int l = 0; l < 3; ++l) {
-    std::vector<int> h(n), w(n);
-    for (int i = 0; i < n; ++i) { h[i] = hs[i] / (8 << l); w[i] = ws[i] / (8 << l); }
-    L[l].build(h, w, cx.st, px_align);
-    dh[l] = op_upload(L[l], F32, heads[l], cs);
+    op_level(L[l], hs, ws, n, cx.st, px_align, [l](int v) { return v / (8 << l); });
+    th[l] = op_stage(L[l], F32, heads[l], cs);
   }
   std::vector<int> aoff(n + 1, 0);
   std::vector<long long> roff(n);
@@ -602,7 +579,7 @@ int ffp_op_det_post(int device, int n, const int32_t* hs, const int32_t* ws, int
   }
   DevBuf d_aoff = upload(aoff.data(), aoff.size()), d_roff = upload(roff.data(), roff.size()), d_imgs = upload(di.data(), di.size());
   DecodeArgs a{};
-  for (int l = 0; l < 3; ++l) { a.head[l] = dh[l].as<float>(); a.tab[l] = L[l].d_tab.as<int4>(); }
+  for (int l = 0; l < 3; ++l) { a.head[l] = th[l].buf.as<float>(); a.tab[l] = L[l].d_tab.as<int4>(); }
   a.head_cs = cs; a.nc = nc; a.nkpt = nkpt; a.n_img = n; a.anchor_off = d_aoff.as<int>(); a.total_anchors = total;
   if (out_raw) {
     DevBuf d_raw(sizeof(float) * (size_t)rtot);
@@ -633,43 +610,22 @@ int ffp_op_rt_topk(int device, int n, int nt, int nc, const float* scores, int s
   op_check_view("rt_topk scores", s_cs, s_coff, nc);
   ScopedStream cx(device, "rt_topk");
   const size_t tok = (size_t)n * nt;
-  DevBuf ds = upload(scores, tok * s_cs), keys(sizeof(unsigned) * tok), idx(sizeof(int) * (size_t)n * RT_NQ);
+  DevBuf keys(sizeof(unsigned) * tok), idx(sizeof(int) * (size_t)n * RT_NQ);
   Level L;
-  L.build(std::vector<int>(n, 1), std::vector<int>(n, nt), cx.st);
-  launch_rt_topk(TView{ds.p, F32, s_cs, s_coff, nc, &L}, nc, nt, n, keys.as<unsigned>(), idx.as<int>(), cx.st);
+  op_level_same(L, n, 1, nt, cx.st);
+  const OpTensor ts = op_stage(L, F32, scores, s_cs);
+  launch_rt_topk(ts.view(s_coff, nc), nc, nt, n, keys.as<unsigned>(), idx.as<int>(), cx.st);
   FFP_HIP(hipStreamSynchronize(cx.st));
   FFP_HIP(hipMemcpy(out_idx, idx.p, sizeof(int) * (size_t)n * RT_NQ, hipMemcpyDeviceToHost));
   FFP_API_END
 }
 
 // ---- single-operator entry points of the RT-DETR and SCRFD kernels (tests/test_gpu_rtdetr_ops.py, tests/test_gpu_scrfd_ops.py) -------
-// The rt_* kernels address image i at i * h * w without padding, so host arrays go up as they are; the launches are the plans' own.
+// The rt_* kernels address image i at i * h * w without padding: their levels are built without alignment, where staging is a plain copy; the
+// launches are the plans' own.
 namespace {
 
-struct OpSlot {       // a max-|value| slot: the caller's bit pattern goes up, the final one comes back
-  DevBuf d;
-  uint32_t* host;
-  explicit OpSlot(uint32_t* h) : host(h) { if (h) d = upload(h, 1); }
-  unsigned* ptr() const { return host ? d.as<unsigned>() : nullptr; }
-  void fetch() { if (host) FFP_HIP(hipMemcpy(host, d.p, sizeof(uint32_t), hipMemcpyDeviceToHost)); }
-};
-
-void op_check_view4(const char* what, int cs, int coff, int C) {
-  op_check_view(what, cs, coff, C);
-  FFP_CHECK(C % 4 == 0 && cs % 4 == 0 && coff % 4 == 0, FFP_ERR_ARG, "%s: channels, offset and record size must be multiples of 4 (%d at %d of %d)", what, C, coff, cs);
-}
-
-void op_flat_level(Level& L, int n, long long per_image, hipStream_t st) {      // n images of per_image records each
-  FFP_CHECK(per_image >= 1 && per_image <= INT_MAX && n >= 1 && n <= 4096 && (long long)n * per_image <= (1ll << 28), FFP_ERR_ARG,
-            "op: %d images of %lld records", n, per_image);
-  L.build(std::vector<int>(n, 1), std::vector<int>(n, (int)per_image), st);
-}
-
-struct OpView : TView {      // fp32 channels [coff, coff + C) of a buffer of cs-wide records
-  OpView(const DevBuf& b, int cs_, int coff_, int C_, Level* L, unsigned* slot = nullptr) : TView{b.p, F32, cs_, coff_, C_, L} { amax = slot; }
-};
-
-void op_fetch(const DevBuf& b, float* dst, size_t n) { FFP_HIP(hipMemcpy(dst, b.p, n * sizeof(float), hipMemcpyDeviceToHost)); }
+void op_fetch(const DevBuf& b, float* dst, size_t n) { FFP_HIP(hipMemcpy(dst, b.p, n * sizeof(float), hipMemcpyDeviceToHost)); }      // a flat fp32 array
 
 void op_rt_levels(const char* what, const int32_t* hs, const int32_t* ws, RtLevels& lv) {
   FFP_CHECK(hs && ws, FFP_ERR_ARG, "%s: null level sizes", what);
@@ -692,18 +648,16 @@ int ffp_op_rt_dwconv(int device, int n, int h, int w, int c, int k, int s, int a
   FFP_CHECK(n >= 1 && n <= 4096 && h >= 1 && w >= 1 && h <= 8192 && w <= 8192, FFP_ERR_ARG, "rt_dwconv: %d images of %dx%d", n, w, h);
   op_check_view4("rt_dwconv input", x_cs, x_coff, c);
   op_check_view4("rt_dwconv output", y_cs, y_coff, c);
-  const int ho = (h - 1) / s + 1, wo = (w - 1) / s + 1;
   ScopedStream cx(device, "rt_dwconv");
   Level Li, Lo;
-  Li.build(std::vector<int>(n, h), std::vector<int>(n, w), cx.st);
-  Lo.build(std::vector<int>(n, ho), std::vector<int>(n, wo), cx.st);
+  op_level_same(Li, n, h, w, cx.st);
+  op_level_same(Lo, n, op_conv_out(h, k, s), op_conv_out(w, k, s), cx.st);
   const std::vector<float> wp = rtdetr_pack_depthwise(wt, c, k * k);
-  DevBuf dx = upload(x, (size_t)n * h * w * x_cs), dy = upload(y, (size_t)n * ho * wo * y_cs), dw = upload(wp.data(), wp.size()), db = upload(bias, (size_t)c);
+  const OpTensor tx = op_stage(Li, F32, x, x_cs), ty = op_stage(Lo, F32, y, y_cs);
+  DevBuf dw = upload(wp.data(), wp.size()), db = upload(bias, (size_t)c);
   OpSlot slot(amax);
-  launch_rt_dwconv(OpView(dx, x_cs, x_coff, c, &Li), OpView(dy, y_cs, y_coff, c, &Lo, slot.ptr()), dw.as<float>(), db.as<float>(), k, s, act, cx.st);
-  FFP_HIP(hipStreamSynchronize(cx.st));
-  op_fetch(dy, y, (size_t)n * ho * wo * y_cs);
-  slot.fetch();
+  launch_rt_dwconv(tx.view(x_coff, c), ty.view(y_coff, c, &slot), dw.as<float>(), db.as<float>(), k, s, act, cx.st);
+  op_finish(cx, {{&ty, y}}, {&slot});
   FFP_API_END
 }
 
@@ -715,14 +669,11 @@ int ffp_op_rt_maxpool2(int device, int n, int h, int w, int c, const float* x, i
   op_check_view4("rt_maxpool2 output", y_cs, y_coff, c);
   ScopedStream cx(device, "rt_maxpool2");
   Level L;
-  L.build(std::vector<int>(n, h), std::vector<int>(n, w), cx.st);
-  const size_t px = (size_t)n * h * w;
-  DevBuf dx = upload(x, px * x_cs), dy = upload(y, px * y_cs);
+  op_level_same(L, n, h, w, cx.st);
+  const OpTensor tx = op_stage(L, F32, x, x_cs), ty = op_stage(L, F32, y, y_cs);
   OpSlot slot(amax);
-  launch_rt_maxpool2(OpView(dx, x_cs, x_coff, c, &L), OpView(dy, y_cs, y_coff, c, &L, slot.ptr()), cx.st);
-  FFP_HIP(hipStreamSynchronize(cx.st));
-  op_fetch(dy, y, px * y_cs);
-  slot.fetch();
+  launch_rt_maxpool2(tx.view(x_coff, c), ty.view(y_coff, c, &slot), cx.st);
+  op_finish(cx, {{&ty, y}}, {&slot});
   FFP_API_END
 }
 
@@ -737,12 +688,11 @@ int ffp_op_rt_add(int device, long long npx, int c, const float* a, int a_cs, in
   ScopedStream cx(device, "rt_add");
   Level L;
   op_flat_level(L, 1, npx, cx.st);
-  DevBuf da = upload(a, (size_t)npx * a_cs), db = upload(b, (size_t)(period ? period : npx) * b_cs), dy = upload(y, (size_t)npx * y_cs);
+  const OpTensor ta = op_stage(L, F32, a, a_cs), ty = op_stage(L, F32, y, y_cs);
+  DevBuf db = upload(b, (size_t)(period ? period : npx) * b_cs);
   OpSlot slot(amax);
-  launch_rt_add(OpView(da, a_cs, a_coff, c, &L), db.as<float>() + b_coff, b_cs, period, OpView(dy, y_cs, y_coff, c, &L, slot.ptr()), cx.st);
-  FFP_HIP(hipStreamSynchronize(cx.st));
-  op_fetch(dy, y, (size_t)npx * y_cs);
-  slot.fetch();
+  launch_rt_add(ta.view(a_coff, c), db.as<float>() + b_coff, b_cs, period, ty.view(y_coff, c, &slot), cx.st);
+  op_finish(cx, {{&ty, y}}, {&slot});
   FFP_API_END
 }
 
@@ -755,14 +705,14 @@ int ffp_op_rt_layernorm(int device, long long npx, const float* x, int x_cs, int
   ScopedStream cx(device, "rt_layernorm");
   Level L;
   op_flat_level(L, 1, npx, cx.st);
-  DevBuf dy = upload(y, (size_t)npx * y_cs), dx, dg = upload(gamma, (size_t)256), db = upload(beta, (size_t)256);
-  if (x) dx = upload(x, (size_t)npx * x_cs);
+  const OpTensor ty = op_stage(L, F32, y, y_cs);
+  OpTensor tx;
+  if (x) tx = op_stage(L, F32, x, x_cs);
+  DevBuf dg = upload(gamma, (size_t)256), db = upload(beta, (size_t)256);
   OpSlot slot(amax);
-  const TView out = OpView(dy, y_cs, y_coff, 256, &L, slot.ptr());
-  launch_rt_layernorm(x ? OpView(dx, x_cs, x_coff, 256, &L) : out, dg.as<float>(), db.as<float>(), out, cx.st);
-  FFP_HIP(hipStreamSynchronize(cx.st));
-  op_fetch(dy, y, (size_t)npx * y_cs);
-  slot.fetch();
+  const TView out = ty.view(y_coff, 256, &slot);
+  launch_rt_layernorm(x ? tx.view(x_coff, 256) : out, dg.as<float>(), db.as<float>(), out, cx.st);
+  op_finish(cx, {{&ty, y}}, {&slot});
   FFP_API_END
 }
 
@@ -773,12 +723,10 @@ int ffp_op_rt_gelu(int device, long long npx, int c, float* x, int cs, int coff,
   ScopedStream cx(device, "rt_gelu");
   Level L;
   op_flat_level(L, 1, npx, cx.st);
-  DevBuf dx = upload(x, (size_t)npx * cs);
+  const OpTensor tx = op_stage(L, F32, x, cs);
   OpSlot slot(amax);
-  launch_rt_gelu(OpView(dx, cs, coff, c, &L, slot.ptr()), cx.st);
-  FFP_HIP(hipStreamSynchronize(cx.st));
-  op_fetch(dx, x, (size_t)npx * cs);
-  slot.fetch();
+  launch_rt_gelu(tx.view(coff, c, &slot), cx.st);
+  op_finish(cx, {{&tx, x}}, {&slot});
   FFP_API_END
 }
 
@@ -792,13 +740,10 @@ int ffp_op_rt_attention(int device, int n, int L, const float* qk, int qk_cs, in
   ScopedStream cx(device, "rt_attention");
   Level Lv;
   op_flat_level(Lv, n, L, cx.st);
-  const size_t tok = (size_t)n * L;
-  DevBuf dq = upload(qk, tok * qk_cs), dv = upload(v, tok * v_cs), dy = upload(y, tok * y_cs);
+  const OpTensor tq = op_stage(Lv, F32, qk, qk_cs), tv = op_stage(Lv, F32, v, v_cs), ty = op_stage(Lv, F32, y, y_cs);
   OpSlot slot(amax);
-  launch_rt_attention(OpView(dq, qk_cs, qk_coff, 512, &Lv), OpView(dv, v_cs, v_coff, 256, &Lv), OpView(dy, y_cs, y_coff, 256, &Lv, slot.ptr()), L, cx.st);
-  FFP_HIP(hipStreamSynchronize(cx.st));
-  op_fetch(dy, y, tok * y_cs);
-  slot.fetch();
+  launch_rt_attention(tq.view(qk_coff, 512), tv.view(v_coff, 256), ty.view(y_coff, 256, &slot), L, cx.st);
+  op_finish(cx, {{&ty, y}}, {&slot});
   FFP_API_END
 }
 
@@ -820,16 +765,16 @@ int ffp_op_rt_enc_prep(int device, int n, const int32_t* hs, const int32_t* ws, 
     lv.src[l] = ds[l].as<float>() + src_coff[l];
     lv.src_cs[l] = src_cs[l];
   }
-  Level LT;
+  Level LT, LR;      // the tokens the kernel writes, and the `rows` records the caller's buffers hold
   op_flat_level(LT, n, NT, cx.st);
-  DevBuf dv = upload(valid, (size_t)NT), dt = upload(t, (size_t)rows * 256), dtm = upload(tm, (size_t)rows * 256);
+  op_flat_level(LR, 1, rows, cx.st);
+  DevBuf dv = upload(valid, (size_t)NT);
+  const OpTensor tt = op_stage(LR, F32, t, 256), ttm = op_stage(LR, F32, tm, 256);
   OpSlot st(amax_t), stm(amax_tm);
-  launch_rt_enc_prep(lv, dv.as<float>(), OpView(dt, 256, 0, 256, &LT, st.ptr()), OpView(dtm, 256, 0, 256, &LT, stm.ptr()), n, cx.st);
-  FFP_HIP(hipStreamSynchronize(cx.st));
-  op_fetch(dt, t, (size_t)rows * 256);
-  op_fetch(dtm, tm, (size_t)rows * 256);
-  st.fetch();
-  stm.fetch();
+  TView vt = tt.view(0, 256, &st), vtm = ttm.view(0, 256, &stm);
+  vt.lvl = vtm.lvl = &LT;
+  launch_rt_enc_prep(lv, dv.as<float>(), vt, vtm, n, cx.st);
+  op_finish(cx, {{&tt, t}, {&ttm, tm}}, {&st, &stm});
   FFP_API_END
 }
 
@@ -845,16 +790,16 @@ int ffp_op_rt_gather(int device, int n, int nt, const float* e, int e_cs, int e_
   op_flat_level(LT, n, nt, cx.st);
   op_flat_level(LQ, n, RT_NQ, cx.st);
   const size_t nq = (size_t)n * RT_NQ;
-  DevBuf de = upload(e, (size_t)n * nt * e_cs), di = upload(idx, nq), da = upload(anchors, (size_t)nt * 4), dq = upload(q, nq * q_cs), dan = upload(anc_out, nq * 4);
+  const OpTensor te = op_stage(LT, F32, e, e_cs), tq = op_stage(LQ, F32, q, q_cs);
+  DevBuf di = upload(idx, nq), da = upload(anchors, (size_t)nt * 4), dan = upload(anc_out, nq * 4);
   OpSlot slot(amax);
   // the kernel takes whole 256-channel records: the slices start at the views' pointers
-  TView ve{de.as<float>() + e_coff, F32, e_cs, 0, 256, &LT}, vq{dq.as<float>() + q_coff, F32, q_cs, 0, 256, &LQ};
-  vq.amax = slot.ptr();
+  TView ve = te.view(0, 256), vq = tq.view(0, 256, &slot);
+  ve.ptr = te.buf.as<float>() + e_coff;
+  vq.ptr = tq.buf.as<float>() + q_coff;
   launch_rt_gather(ve, di.as<int>(), da.as<float>(), nt, n, vq, dan.as<float>(), cx.st);
-  FFP_HIP(hipStreamSynchronize(cx.st));
-  op_fetch(dq, q, nq * q_cs);
+  op_finish(cx, {{&tq, q}}, {&slot});
   op_fetch(dan, anc_out, nq * 4);
-  slot.fetch();
   FFP_API_END
 }
 
@@ -867,13 +812,12 @@ int ffp_op_rt_ref(int device, long long nq, const float* delta, int d_cs, int d_
   ScopedStream cx(device, "rt_ref");
   Level L;
   op_flat_level(L, 1, nq, cx.st);
-  DevBuf dd = upload(delta, (size_t)nq * d_cs), dr = upload(ref, (size_t)nq * r_cs), da;
+  const OpTensor td = op_stage(L, F32, delta, d_cs), tr = op_stage(L, F32, ref, r_cs);
+  DevBuf da;
   if (anc) da = upload(anc, (size_t)nq * 4);
   OpSlot slot(amax);
-  launch_rt_ref(OpView(dd, d_cs, d_coff, 4, &L), anc ? da.as<float>() : nullptr, OpView(dr, r_cs, r_coff, 4, &L, slot.ptr()), cx.st);
-  FFP_HIP(hipStreamSynchronize(cx.st));
-  op_fetch(dr, ref, (size_t)nq * r_cs);
-  slot.fetch();
+  launch_rt_ref(td.view(d_coff, 4), anc ? da.as<float>() : nullptr, tr.view(r_coff, 4, &slot), cx.st);
+  op_finish(cx, {{&tr, ref}}, {&slot});
   FFP_API_END
 }
 
@@ -892,14 +836,10 @@ int ffp_op_rt_deform(int device, int n, const int32_t* hs, const int32_t* ws, co
   Level LT, LQ;
   op_flat_level(LT, n, NT, cx.st);
   op_flat_level(LQ, n, RT_NQ, cx.st);
-  const size_t nq = (size_t)n * RT_NQ;
-  DevBuf dv = upload(val, (size_t)n * NT * v_cs), doa = upload(oa, nq * oa_cs), dr = upload(ref, nq * r_cs), dy = upload(y, nq * y_cs);
+  const OpTensor tv = op_stage(LT, F32, val, v_cs), toa = op_stage(LQ, F32, oa, oa_cs), tr = op_stage(LQ, F32, ref, r_cs), ty = op_stage(LQ, F32, y, y_cs);
   OpSlot slot(amax);
-  launch_rt_deform(OpView(dv, v_cs, v_coff, 256, &LT), OpView(doa, oa_cs, oa_coff, 288, &LQ), OpView(dr, r_cs, r_coff, 4, &LQ), lv,
-                   OpView(dy, y_cs, y_coff, 256, &LQ, slot.ptr()), cx.st);
-  FFP_HIP(hipStreamSynchronize(cx.st));
-  op_fetch(dy, y, nq * y_cs);
-  slot.fetch();
+  launch_rt_deform(tv.view(v_coff, 256), toa.view(oa_coff, 288), tr.view(r_coff, 4), lv, ty.view(y_coff, 256, &slot), cx.st);
+  op_finish(cx, {{&ty, y}}, {&slot});
   FFP_API_END
 }
 
@@ -915,8 +855,8 @@ int ffp_op_rt_decode(int device, int n, int nc, const float* ref, int r_cs, int 
   Level LQ;
   op_flat_level(LQ, n, RT_NQ, cx.st);
   const size_t nq = (size_t)n * RT_NQ;
-  DevBuf dr = upload(ref, nq * r_cs), ds = upload(scores, nq * s_cs);
-  const TView vr = OpView(dr, r_cs, r_coff, 4, &LQ), vs = OpView(ds, s_cs, s_coff, nc, &LQ);
+  const OpTensor tr = op_stage(LQ, F32, ref, r_cs), ts = op_stage(LQ, F32, scores, s_cs);
+  const TView vr = tr.view(r_coff, 4), vs = ts.view(s_coff, nc);
   if (out_raw) {
     DevBuf d_raw = upload(out_raw, nq * (4 + nc));
     launch_rt_raw(vr, vs, nc, d_raw.as<float>(), cx.st);
@@ -945,9 +885,9 @@ int ffp_op_rt_post_tiles(int device, int n, int nc, const float* ref, int r_cs, 
   Level LQ;
   op_flat_level(LQ, n, RT_NQ, cx.st);
   const size_t nq = (size_t)n * RT_NQ;
-  DevBuf dr = upload(ref, nq * r_cs), ds = upload(scores, nq * s_cs), dt = upload(tiles_xyxy, (size_t)n * 4);
-  DevBuf d_det = upload(out_dets, nq * 6), d_counts = upload(out_counts, (size_t)n);
-  launch_rt_post_tiles(OpView(dr, r_cs, r_coff, 4, &LQ), OpView(ds, s_cs, s_coff, nc, &LQ), nc, conf, dt.as<int4>(), n, full_h, full_w, mode,
+  const OpTensor tr = op_stage(LQ, F32, ref, r_cs), ts = op_stage(LQ, F32, scores, s_cs);
+  DevBuf dt = upload(tiles_xyxy, (size_t)n * 4), d_det = upload(out_dets, nq * 6), d_counts = upload(out_counts, (size_t)n);
+  launch_rt_post_tiles(tr.view(r_coff, 4), ts.view(s_coff, nc), nc, conf, dt.as<int4>(), n, full_h, full_w, mode,
                        d_det.as<float>(), d_counts.as<int>(), cx.st);
   FFP_HIP(hipStreamSynchronize(cx.st));
   op_fetch(d_det, out_dets, nq * 6);
@@ -964,18 +904,12 @@ int ffp_op_scrfd_pool(int device, int n, const int32_t* hs, const int32_t* ws, i
   op_check_view("scrfd_pool input", x_cs, x_coff, c);
   op_check_view("scrfd_pool output", y_cs, y_coff, c);
   ScopedStream cx(device, "scrfd_pool");
-  std::vector<int> ho(n), wo(n);
-  for (int i = 0; i < n; ++i) {
-    ho[i] = maxpool ? (hs[i] - 1) / 2 + 1 : (hs[i] + k - 1) / k;
-    wo[i] = maxpool ? (ws[i] - 1) / 2 + 1 : (ws[i] + k - 1) / k;
-  }
   Level Li, Lo;
-  Li.build(std::vector<int>(hs, hs + n), std::vector<int>(ws, ws + n), cx.st, px_align);
-  Lo.build(ho, wo, cx.st, px_align);
-  DevBuf dx = op_upload(Li, F32, x, x_cs), dy = op_upload(Lo, F32, y, y_cs);
-  launch_scrfd_pool(OpView(dx, x_cs, x_coff, c, &Li), OpView(dy, y_cs, y_coff, c, &Lo), maxpool ? 1 : 0, k, cx.st);
-  FFP_HIP(hipStreamSynchronize(cx.st));
-  op_download(Lo, F32, dy, y_cs, y);
+  op_level(Li, hs, ws, n, cx.st, px_align);
+  op_level(Lo, hs, ws, n, cx.st, px_align, [&](int v) { return maxpool ? op_conv_out(v, 3, 2) : op_avg_out(v, k); });
+  const OpTensor tx = op_stage(Li, F32, x, x_cs), ty = op_stage(Lo, F32, y, y_cs);
+  launch_scrfd_pool(tx.view(x_coff, c), ty.view(y_coff, c), maxpool ? 1 : 0, k, cx.st);
+  op_finish(cx, {{&ty, y}});
   FFP_API_END
 }
 
@@ -996,7 +930,7 @@ int ffp_op_scrfd_post(int device, int n, int net_h, int net_w, int A, const int3
   for (int i = 0; i < n; ++i) FFP_CHECK(det_scale[i] > 0.f, FFP_ERR_ARG, "scrfd_post: det_scale of image %d", i);
   ScopedStream cx(device, "scrfd_post");
   Level L[3];
-  DevBuf dh[3][3];
+  OpTensor th[3][3];
   ScrfdHeads h{};
   h.A = A;
   h.a_off[0] = 0;
@@ -1006,13 +940,13 @@ int ffp_op_scrfd_post(int device, int n, int net_h, int net_w, int A, const int3
     L[l].build(std::vector<int>(n, lh), std::vector<int>(n, lw), cx.st, px_align);
     for (int kind = 0; kind < 3; ++kind) {
       if (!heads[3 * kind + l]) continue;
-      dh[kind][l] = op_upload(L[l], F32, heads[3 * kind + l], cs[kind]);
+      th[kind][l] = op_stage(L[l], F32, heads[3 * kind + l], cs[kind]);
       h.cs[kind][l] = cs[kind];
       h.coff[kind][l] = coff[kind];
     }
-    h.score[l] = dh[0][l].as<float>();
-    h.bbox[l] = dh[1][l].as<float>();
-    h.kps[l] = use_kps ? dh[2][l].as<float>() : nullptr;
+    h.score[l] = th[0][l].buf.as<float>();
+    h.bbox[l] = th[1][l].buf.as<float>();
+    h.kps[l] = th[2][l].buf.as<float>();      // null without keypoints
     h.tab[l] = L[l].d_tab.as<int4>();
     h.stride[l] = strides[l];
     h.a_off[l + 1] = h.a_off[l] + lh * lw * A;
@@ -1045,11 +979,12 @@ int ffp_op_scrfd_sahi_rows(int device, int n_tiles, int cap, const int32_t* tile
             "scrfd_sahi_rows: bad sizes");
   if (out_bad) *out_bad = -1;
   ScopedStream cx(device, "scrfd_sahi_rows");
-  const size_t nd = (size_t)n_tiles * cap * FFP_DET_STRIDE(5);
-  DevBuf dd = upload(dets, nd), dc = upload(counts, (size_t)n_tiles), dt = upload(tiles_xyxy, (size_t)n_tiles * 4), de(sizeof(unsigned));
-  launch_scrfd_sahi_rows(dd.as<float>(), dc.as<int>(), dt.as<int4>(), n_tiles, cap, conf, full_h, full_w, de.as<unsigned>(), cx.st);
-  FFP_HIP(hipStreamSynchronize(cx.st));
-  op_fetch(dd, dets, nd);
+  Level L;
+  op_flat_level(L, 1, (long long)n_tiles * cap, cx.st);
+  const OpTensor td = op_stage(L, F32, dets, FFP_DET_STRIDE(5));
+  DevBuf dc = upload(counts, (size_t)n_tiles), dt = upload(tiles_xyxy, (size_t)n_tiles * 4), de(sizeof(unsigned));
+  launch_scrfd_sahi_rows(td.buf.as<float>(), dc.as<int>(), dt.as<int4>(), n_tiles, cap, conf, full_h, full_w, de.as<unsigned>(), cx.st);
+  op_finish(cx, {{&td, dets}});
   FFP_HIP(hipMemcpy(counts, dc.p, sizeof(int) * (size_t)n_tiles, hipMemcpyDeviceToHost));
   unsigned bad = SCRFD_NO_BAD_ROW;
   FFP_HIP(hipMemcpy(&bad, de.p, sizeof(unsigned), hipMemcpyDeviceToHost));
@@ -1064,7 +999,7 @@ int ffp_op_scrfd_sahi_rows(int device, int n_tiles, int cap, const int32_t* tile
 // ---- single-operator entry points of the image-input kernels (tests/test_gpu_image_input.py) -----------------------------------------
 // The frame is H x W x 3 u8 on the host, the items are boxes {x0, y0, x1, y1} of it; their LetterboxImg records come from the functions
 // the engines call (det_tile_geometry, rtdetr_tile_records, scrfd_tile_records), so a geometry mistake shows as well. Outputs hold the
-// items back to back; every output buffer goes up as 0xFF bytes (NaN), so a pixel no kernel wrote comes back as NaN.
+// items back to back; every output tensor goes up without contents (all NaN), so a pixel no kernel wrote comes back as NaN.
 namespace {
 
 void op_check_frame(const char* what, const uint8_t* frame, int H, int W, int chan_order, int n, const int32_t* boxes) {
@@ -1079,12 +1014,6 @@ DevBuf op_upload_frame(const uint8_t* frame, int H, int W) {
   DevBuf b(nb + 256);
   FFP_HIP(hipMemcpy(b.p, frame, nb, hipMemcpyHostToDevice));
   fill_bytes(static_cast<char*>(b.p) + nb, 0xFF, 256);
-  return b;
-}
-
-DevBuf op_nan_buffer(size_t bytes) {
-  DevBuf b(bytes + 256);
-  fill_bytes(b.p, 0xFF, b.n);
   return b;
 }
 
@@ -1123,14 +1052,14 @@ int ffp_op_image_input(int device, int kind, int precision, const uint8_t* frame
   ScopedStream cx(device, "image_input");
   const int cs = T == F16 ? 8 : 4;
   Level L;
-  L.build(hs, ws, cx.st);
-  DevBuf d_frame = op_upload_frame(frame, H, W), d_imgs = upload(lb.data(), lb.size()), dout = op_nan_buffer((size_t)L.total_px * cs * dsize(T));
-  const TView vout{dout.p, T, cs, 0, cs, &L};
+  op_level(L, hs.data(), ws.data(), n, cx.st);
+  DevBuf d_frame = op_upload_frame(frame, H, W), d_imgs = upload(lb.data(), lb.size());
+  const OpTensor tout = op_stage(L, T, nullptr, cs, true);
+  const TView vout = tout.view(0, cs);
   const int flip = chan_order == FFP_CHAN_AS_BGR ? 1 : 0;
   if (kind == 2) launch_scrfd_preproc(d_frame.as<uint8_t>(), W, flip, d_imgs.as<LetterboxImg>(), vout, cx.st);
   else launch_letterbox(d_frame.as<uint8_t>(), H, W, flip, d_imgs, vout, cx.st);
-  FFP_HIP(hipStreamSynchronize(cx.st));
-  op_download(L, T, dout, cs, out);
+  op_finish(cx, {{&tout, out}});
   std::copy(hs.begin(), hs.end(), out_hs);
   std::copy(ws.begin(), ws.end(), out_ws);
   FFP_API_END
@@ -1145,25 +1074,23 @@ int ffp_op_stem(int device, int precision, int fused, const uint8_t* frame, int 
             FFP_ERR_ARG, "stem: fused %d (0, 1), cout %d (16, 32, 64), stride %d (1, 2), activation code %d (0..3)", fused, cout, stride, act);
   const DType T = op_dtype("stem", precision);
   const std::vector<LetterboxImg> lb = op_det_records(H, W, boxes_xyxy, n, imgsz);
-  std::vector<int> hi(n), wi(n), ho(n), wo(n);
-  for (int i = 0; i < n; ++i) {
-    hi[i] = lb[i].net_h; wi[i] = lb[i].net_w;
-    ho[i] = (hi[i] - 1) / stride + 1; wo[i] = (wi[i] - 1) / stride + 1;
-  }
+  std::vector<int> hi(n), wi(n);
+  for (int i = 0; i < n; ++i) { hi[i] = lb[i].net_h; wi[i] = lb[i].net_w; }
   ScopedStream cx(device, "stem");
   PackedConv pc;
   pack_conv(pc, "op_stem", w, bias, cout, 3, 3, 1, T, cx.st, false);
   Level lin, lout;
-  lin.build(hi, wi, cx.st);
-  lout.build(ho, wo, cx.st);
+  op_level(lin, hi.data(), wi.data(), n, cx.st);
+  op_level(lout, hi.data(), wi.data(), n, cx.st, 1, [&](int v) { return op_conv_out(v, 3, stride); });
   const int cin0 = T == F16 ? 8 : 4;
-  DevBuf d_frame = op_upload_frame(frame, H, W), d_imgs = upload(lb.data(), lb.size()), din,
-         dout = op_nan_buffer((size_t)lout.total_px * cout * dsize(T));
-  if (!fused) din = op_nan_buffer((size_t)lin.total_px * cin0 * dsize(T));
+  DevBuf d_frame = op_upload_frame(frame, H, W), d_imgs = upload(lb.data(), lb.size());
+  const OpTensor tout = op_stage(lout, T, nullptr, cout, true);
+  OpTensor tin;
+  if (!fused) tin = op_stage(lin, T, nullptr, cin0, true);
   ConvOp o;
   o.pc = &pc; o.stride = stride; o.act = act;
-  o.in = TView{din.p, T, cin0, 0, cin0, &lin};      // fused: the level and the channel padding only
-  o.out = TView{dout.p, T, cout, 0, cout, &lout};
+  o.in = TView{tin.buf.p, T, cin0, 0, cin0, &lin};      // fused: the level and the channel padding only
+  o.out = tout.view(0, cout);
   const int flip = chan_order == FFP_CHAN_AS_BGR ? 1 : 0;
   if (fused) {
     launch_stem_from_frame(d_frame.as<uint8_t>(), H, W, flip, d_imgs, o, cx.st);
@@ -1171,8 +1098,7 @@ int ffp_op_stem(int device, int precision, int fused, const uint8_t* frame, int 
     launch_letterbox(d_frame.as<uint8_t>(), H, W, flip, d_imgs, o.in, cx.st);
     launch_conv_direct(o, cx.st);
   }
-  FFP_HIP(hipStreamSynchronize(cx.st));
-  op_download(lout, T, dout, cout, out);
+  op_finish(cx, {{&tout, out}});
   FFP_API_END
 }
 
@@ -1183,12 +1109,8 @@ int ffp_op_stem_conv(int device, const uint8_t* frame, int H, int W, int chan_or
   op_check_frame("stem_conv", frame, H, W, chan_order, n, boxes_xyxy);
   FFP_CHECK(stem_cout == 16 || stem_cout == 32, FFP_ERR_ARG, "stem_conv: %d stem channels (16 or 32: the loader holds one or two 16-channel chunks)", stem_cout);
   const std::vector<LetterboxImg> lb = op_det_records(H, W, boxes_xyxy, n, imgsz);
-  std::vector<int> h0(n), w0(n), h1(n), w1(n), h2(n), w2(n);
-  for (int i = 0; i < n; ++i) {
-    h0[i] = lb[i].net_h; w0[i] = lb[i].net_w;
-    h1[i] = (h0[i] - 1) / 2 + 1; w1[i] = (w0[i] - 1) / 2 + 1;
-    h2[i] = (h1[i] - 1) / 2 + 1; w2[i] = (w1[i] - 1) / 2 + 1;
-  }
+  std::vector<int> h0(n), w0(n);
+  for (int i = 0; i < n; ++i) { h0[i] = lb[i].net_h; w0[i] = lb[i].net_w; }
   ScopedStream cx(device, "stem_conv");
   conv_kernels_init();
   const int cc = 2 * stem_cout;
@@ -1198,33 +1120,29 @@ int ffp_op_stem_conv(int device, const uint8_t* frame, int H, int W, int chan_or
   // as a split plan lays it out: levels aligned to 32 pixels, one max-|value| slot per (buffer, image); the stem output's slots hold the bound the
   // plan knows from the weights alone, the conv output's start at zero
   Level L0, L1, L2;
-  L0.build(h0, w0, cx.st, 32);
-  L1.build(h1, w1, cx.st, 32);
-  L2.build(h2, w2, cx.st, 32);
-  std::vector<unsigned> slots(2 * (size_t)n, 0u);
-  {
-    const float bound = std::max(ps.out_bound, 0.3f);
-    unsigned b;
-    std::memcpy(&b, &bound, 4);
-    std::fill(slots.begin(), slots.begin() + n, b);
-  }
-  DevBuf d_frame = op_upload_frame(frame, H, W), d_imgs = upload(lb.data(), lb.size()), dslots = upload(slots.data(), slots.size()),
-         dout = op_nan_buffer((size_t)L2.total_px * cc * 4), d_stem_w;
+  const auto half = [](int v) { return op_conv_out(v, 3, 2); };
+  op_level(L0, h0.data(), w0.data(), n, cx.st, 32);
+  op_level(L1, h0.data(), w0.data(), n, cx.st, 32, half);
+  op_level(L2, h0.data(), w0.data(), n, cx.st, 32, [&](int v) { return half(half(v)); });
+  const float bound = std::max(ps.out_bound, 0.3f);
+  unsigned bound_bits;
+  std::memcpy(&bound_bits, &bound, 4);
+  OpSlot s_stem(std::vector<unsigned>(n, bound_bits)), s_conv(std::vector<unsigned>(n, 0u));
+  DevBuf d_frame = op_upload_frame(frame, H, W), d_imgs = upload(lb.data(), lb.size()), d_stem_w;
+  const OpTensor tout = op_stage(L2, F32, nullptr, cc, true);
   ConvOp stem, conv;
   stem.pc = &ps; stem.stride = 2; stem.act = ACT_SILU;
   stem.in = TView{nullptr, F32, 4, 0, 4, &L0};
   stem.out = TView{nullptr, F32, stem_cout, 0, stem_cout, &L1};      // never stored
-  stem.out.amax = dslots.as<unsigned>(); stem.out.amax_n = n;
+  stem.out.amax = s_stem.ptr(); stem.out.amax_n = n;
   conv.pc = &pc; conv.stride = 2; conv.act = ACT_SILU;
   conv.in = stem.out;
-  conv.out = TView{dout.p, F32, cc, 0, cc, &L2};
-  conv.out.amax = dslots.as<unsigned>() + n; conv.out.amax_n = n;
+  conv.out = tout.view(0, cc, &s_conv);
   FFP_CHECK(stem_conv_eligible(stem, conv), FFP_ERR_ARG, "stem_conv: the stem-fused loader refuses this pair of convs");
   const int flip = chan_order == FFP_CHAN_AS_BGR ? 1 : 0;
   stem_conv_pack(stem, flip, d_stem_w, cx.st);
   launch_stem_conv(d_frame.as<uint8_t>(), H, W, d_imgs, d_stem_w, stem, conv, cx.st);
-  FFP_HIP(hipStreamSynchronize(cx.st));
-  op_download(L2, F32, dout, cc, out);
+  op_finish(cx, {{&tout, out}});
   FFP_API_END
 }
 
@@ -1242,23 +1160,18 @@ int ffp_op_conv2d_time(int device, int precision, int n, int h, int w, int cin, 
   for (auto& v : wt) v = rnd() * 0.1f;
   PackedConv pc;
   pack_conv(pc, "bench", wt.data(), bias.data(), cout, cin, k, 1, T, cx.st, precision == FFP_PREC_F32X3);
-  const int hi = up ? h * 2 : h, wi = up ? w * 2 : w;
-  const int ho = (hi + 2 * (k / 2) - k) / stride + 1, wo = (wi + 2 * (k / 2) - k) / stride + 1;
   Level lin, lout;
-  lin.build(std::vector<int>(n, h), std::vector<int>(n, w), cx.st);
-  lout.build(std::vector<int>(n, ho), std::vector<int>(n, wo), cx.st);
+  op_level_same(lin, n, h, w, cx.st);
+  op_level_same(lout, n, op_conv_out(up ? h * 2 : h, k, stride), op_conv_out(up ? w * 2 : w, k, stride), cx.st);
   const size_t nin = (size_t)lin.total_px * pc.cin, nout = (size_t)lout.total_px * cout;
   DevBuf din(nin * dsize(T) + 256), dout(nout * dsize(T) + 256);
   {
     std::vector<float> hx(std::min(nin, (size_t)1 << 22));
     for (auto& v : hx) v = rnd();
-    if (T == F32) {
-      for (size_t o = 0; o < nin; o += hx.size()) FFP_HIP(hipMemcpy((float*)din.p + o, hx.data(), std::min(hx.size(), nin - o) * 4, hipMemcpyHostToDevice));
-    } else {
-      std::vector<_Float16> hh(hx.size());
-      for (size_t i = 0; i < hx.size(); ++i) hh[i] = (_Float16)hx[i];
-      for (size_t o = 0; o < nin; o += hh.size()) FFP_HIP(hipMemcpy((_Float16*)din.p + o, hh.data(), std::min(hh.size(), nin - o) * 2, hipMemcpyHostToDevice));
-    }
+    std::vector<unsigned char> raw(hx.size() * dsize(T));
+    op_narrow(T, hx.data(), hx.size(), raw.data());
+    for (size_t o = 0; o < nin; o += hx.size())
+      FFP_HIP(hipMemcpy(din.as<char>() + o * dsize(T), raw.data(), std::min(hx.size(), nin - o) * dsize(T), hipMemcpyHostToDevice));
   }
   ConvOp o;
   o.pc = &pc; o.stride = stride; o.act = precision == FFP_PREC_F16 ? ACT_LRELU : ACT_SILU; o.up = up; o.dbg = dbg_mask; o.force_shape = force_shape;   // the activation each precision's network uses
@@ -1364,28 +1277,6 @@ struct OpSrLevel {
   }
 };
 
-// a level's whole flat buffer, padding and unused capacity included, as `count` fp32 values on the host
-DevBuf op_upload_records(DType T, const float* src, size_t count) {
-  DevBuf b(count * dsize(T) + 256);
-  if (T == F32) {
-    FFP_HIP(hipMemcpy(b.p, src, count * 4, hipMemcpyHostToDevice));
-  } else {
-    std::vector<_Float16> h(count);
-    for (size_t i = 0; i < count; ++i) h[i] = (_Float16)src[i];
-    FFP_HIP(hipMemcpy(b.p, h.data(), count * 2, hipMemcpyHostToDevice));
-  }
-  return b;
-}
-void op_download_records(DType T, const DevBuf& b, size_t count, float* dst) {
-  if (T == F32) {
-    FFP_HIP(hipMemcpy(dst, b.p, count * 4, hipMemcpyDeviceToHost));
-  } else {
-    std::vector<_Float16> h(count);
-    FFP_HIP(hipMemcpy(h.data(), b.p, count * 2, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < count; ++i) dst[i] = (float)h[i];
-  }
-}
-
 void op_sr_check_cap(const char* what, int cap_t16, const SrLevelSizes& z) {
   FFP_CHECK(cap_t16 >= 0 && cap_t16 <= 4096, FFP_ERR_ARG, "%s: capacity %d", what, cap_t16);
   FFP_CHECK(cap_t16 == 0 || z.t16 <= cap_t16, FFP_ERR_ARG, "%s: batch of %lld 16x16 tiles exceeds the capacity of %d", what, z.t16, cap_t16);
@@ -1434,7 +1325,7 @@ int ffp_op_sr_pre(int device, int precision, const uint8_t* src, size_t src_byte
   ScopedStream cx(device, "sr_pre");
   OpSrLevel lb(cap_t16, 1);
   // the caller's contents go up once, every record of the level: a later batch runs over what the earlier one left
-  DevBuf d_src = upload(src, src_bytes), d_flat = op_upload_records(T, flat, flat_px * C), d_srcs;
+  DevBuf d_src = upload(src, src_bytes), d_flat = op_put(T, flat, flat_px * C, kOpSlack), d_srcs;      // the level's whole flat buffer, padding and unused capacity included
   for (size_t b = 0; b < batches.size(); ++b) {
     const std::vector<SrTile>& tiles = batches[b];
     const int nt = (int)tiles.size(), cap = cap_t16 > 0 ? cap_t16 : nt;
@@ -1449,7 +1340,7 @@ int ffp_op_sr_pre(int device, int precision, const uint8_t* src, size_t src_byte
     launch_sr_pre(d_src.as<uint8_t>(), d_srcs.as<SrSrc>(), vout, shuf, cx.st);
   }
   FFP_HIP(hipStreamSynchronize(cx.st));
-  op_download_records(T, d_flat, flat_px * C, flat);
+  op_get(T, d_flat, flat_px * C, flat);
   for (size_t i = 0; i < batches.back().size(); ++i) out_off[i] = lb.L.off[i];
   FFP_API_END
 }
@@ -1477,13 +1368,14 @@ int ffp_op_sr_post(int device, int n, const int64_t* imgs, int scale, int tile, 
   FFP_CHECK(only_tile >= -1 && only_tile < (int)batches.back().size(), FFP_ERR_ARG, "sr_post: tile %d of %d", only_tile, (int)batches.back().size());
   ScopedStream cx(device, "sr_post");
   OpSrLevel l2(cap_t16, 4);
-  DevBuf d_canvas = upload(canvas, canvas_bytes), d_net, d_dsts, d_coff;
+  DevBuf d_canvas = upload(canvas, canvas_bytes), d_dsts, d_coff;
+  OpTensor t_net;
   for (size_t b = 0; b < batches.size(); ++b) {
     const std::vector<SrTile>& tiles = batches[b];
     const int nt = (int)tiles.size(), cap = cap_t16 > 0 ? cap_t16 : nt;
     FFP_HIP(hipStreamSynchronize(cx.st));      // the earlier batch has read its tables and its network output
     l2.set(sizes[b].h2, sizes[b].w2, cx.st);
-    d_net = op_upload(l2.L, F32, nets[b], cs);      // NaN behind the batch's last pixel
+    t_net = op_stage(l2.L, F32, nets[b], cs);      // NaN behind the batch's last pixel
     std::vector<SrSrc> srcs(nt);
     std::vector<SrDst> dsts(cap);
     std::vector<long long> coff((size_t)cap + 1);
@@ -1499,8 +1391,7 @@ int ffp_op_sr_post(int device, int n, const int64_t* imgs, int scale, int tile, 
     }
     d_dsts = upload(dsts.data(), dsts.size());
     d_coff = upload(coff.data(), coff.size());
-    const TView vnet{d_net.p, F32, cs, 0, cs, &l2.L};
-    launch_sr_post(vnet, d_dsts.as<SrDst>(), d_coff.as<long long>(), l2.L.total_px, d_canvas.as<uint8_t>(), cx.st);      // as SrEngine::enhance_dev launches it
+    launch_sr_post(t_net.view(0, cs), d_dsts.as<SrDst>(), d_coff.as<long long>(), l2.L.total_px, d_canvas.as<uint8_t>(), cx.st);      // as SrEngine::enhance_dev launches it
   }
   FFP_HIP(hipStreamSynchronize(cx.st));
   FFP_HIP(hipMemcpy(canvas, d_canvas.p, canvas_bytes, hipMemcpyDeviceToHost));

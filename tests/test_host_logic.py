@@ -29,6 +29,19 @@ def test_every_declared_symbol_is_exported(lib):
         assert hasattr(lib, name), f"{name} declared in include/ffp.h but not exported by libffp.so"
     assert declared == set(_lib.EXPORTED_SYMBOLS), declared ^ set(_lib.EXPORTED_SYMBOLS)
     assert lib.ffp_version() >= 200
+    # the ctypes table is derived from the header (_abi.parse): a row per prototype, every row set on the loaded library
+    assert declared == set(_lib._SIGS) and len(re.findall(r"\bffp_[a-z0-9_]+\s*\([^()]*\)\s*;", hdr)) == len(_lib._SIGS)
+    for name, (res, args) in _lib._SIGS.items():
+        f = getattr(lib, name)
+        assert f.restype is res and list(f.argtypes) == args, name
+    assert _lib._SIGS["ffp_last_error"] == (C.c_char_p, []) and _lib._SIGS["ffp_det_destroy"] == (None, [C.c_void_p])
+    assert _lib._SIGS["ffp_op_scrfd_post"][1][7] is C.POINTER(C.POINTER(C.c_float))
+    # nothing is skipped: a prototype outside the vocabulary is refused by name
+    from ffp_amd import _abi
+    for text, what in (("int ffp_x(int (*cb)(int));", "ffp_x"), ("int ffp_y(int a[4]);", "ffp_y"), ("int ffp_z(unsigned a);", "ffp_z"),
+                       ("int ffp_ok(int a);\nint ffp_half(int a", "ffp_half")):
+        with pytest.raises(ValueError, match=what):
+            _abi.parse(text)
 
 
 def test_conv_shape_table_through_shape_name(lib):
